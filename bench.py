@@ -26,6 +26,7 @@ HIP events on the pass's stream (`roofline`: the border product against the FP64
 shards on this box's host cores — timed as the CPU figure, compared pose by pose with identically built GPU shards (`parity`).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--robots-per-gpu R] [--no-cpu] [--frames F] [--ingest-only] [--no-parity]
+       [--dump-outputs DIR]  (the poses and landmark estimates the last timed step left, DIR/<name>.npy, for comparing two builds)
 Multi-GPU: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -76,6 +77,39 @@ def build_shard(s, log, frames=None, ingest_only=False):
 
 def all_poses(gb, P):
     return np.array([gb.graph.get_pose12(0, k)[1] for k in range(P)])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, shards, final, dist=None, world=1, rank=0):
+    """--dump-outputs: what the timed passes left in the graphs — every robot's poses (robot, pose, 12: rotation row-major, then
+    translation) and every robot's landmark estimates by class (rows of all robots in robot order) — as float64 .npy files, so that
+    two builds run with the same arguments can be compared array for array.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of
+    rows is written instead (the row indices beside it).  Collective at world > 1: every rank passes its robots, rank 0 writes."""
+    mine = {"poses": final}
+    for cls, name in enumerate(("cyl", "cube", "point")):
+        rows = [gb.graph.get_landmark(cls, i)[1] for gb in shards for i in range(gb.counts()[name])]
+        mine[f"landmarks_{name}"] = np.array(rows, dtype=np.float64).reshape(len(rows), (7, 15, 3)[cls])
+    parts = [mine]
+    if dist is not None and world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+    if rank != 0:
+        return
+    out = {k: np.concatenate([np.asarray(p[k], dtype=np.float64) for p in parts], axis=0) for k in mine}
+    if sum(a.nbytes for a in out.values()) > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(0)
+        rows = {k: a.reshape(-1, a.shape[-1]) for k, a in out.items()}
+        frac = (DUMP_LIMIT_BYTES - 65536) / sum(a.nbytes + 8 * len(a) for a in rows.values())     # (the row indices count too)
+        for k, a in rows.items():
+            keep = np.sort(rng.choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            out[k], out[k + "_rows"] = a[keep], keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    sys.stderr.write(f"bench.py: outputs of the last timed step written to {out_dir}: " +
+                     ", ".join(f"{k}{list(a.shape)}" for k, a in out.items()) + "\n")
 
 
 def _oracle_shard(L, po, log, frames, threads):
@@ -649,7 +683,11 @@ def main():
     ap.add_argument("--no-dense-relmeas", action="store_true", help="skip the leg with SURVEY 8d's relative-pose density (reported beside the headline)")
     ap.add_argument("--pcg", type=int, default=8, help="--joint pcg: PCG iterations per pass")
     ap.add_argument("--pcg-tol", type=float, default=0.0, help="--joint pcg: relative tolerance on sqrt(r^T M^-1 r) (0: every iteration counts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (every robot's poses and landmark estimates) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global DENSE_PROFILE, DENSE_LEG, CHART
     CHART = 1 if args.chart == "expmap" else 0
     DENSE_PROFILE = args.dense_profile
@@ -662,6 +700,8 @@ def main():
         # `python bench.py --gpus N` as the driver may call it: start the N ranks ourselves (torch.distributed.run, one process per GPU)
         # as a CHILD process, before torch or anything that touches the GPU is imported here, relay its output (rank 0 prints the JSON
         # line) and leave with its exit code.
+        if args.dump_outputs:       # (the ranks start in the repository root: the last --dump-outputs, absolute, is the one they take)
+            sys.argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         raise SystemExit(self_launch(args.gpus))
     import torch            # torch first: it must initialise the device before this library's HIP runtime is loaded
     dist = None
@@ -779,6 +819,8 @@ def main():
         dt = float(tt.item())
     n_passes = n_probe + args.warmup + args.steps
     final = np.stack([all_poses(gb, P) for gb in shards])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shards, final, dist if use_dist else None, world, rank)
     finite = bool(np.isfinite(final).all())
     final_chi2 = sum(gb.graph.chi2()["total"] for gb in shards) if multi else None
 

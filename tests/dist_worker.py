@@ -77,6 +77,10 @@ def main_threads(R):
     if rank == 0:
         np.savez(out_path, poses=np.array([p for part in gathered for p in part]), n_slots=out[0][1]["n_slots"],
                  n_global=np.array(out[0][1]["n_global"]), n_gslots=0)
+    # every rank tears the group down together: a rank that leaves with its group alive while a peer is still connected can abort
+    # in the teardown of the group's threads ("terminate called without an active exception")
+    dist.barrier()
+    dist.destroy_process_group()
 
 
 def main_driver(R):
