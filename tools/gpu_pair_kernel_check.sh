@@ -16,7 +16,7 @@ rc=$?
 tail -15 gpurun_out/r5_pair_exact.log
 if [ $rc -ne 0 ]; then exit 1; fi
 python -c "import slide_slam_amd as s; print('pair timeouts', s.pair_timeouts())"
-B="python bench.py --steps 100 --warmup 10 --no-cpu --no-parity --no-dense-leg --probe 0 --no-dense-relmeas"
+B="python bench.py --full --steps 100 --warmup 10 --no-cpu --no-parity --no-dense-leg --probe 0 --no-dense-relmeas"
 pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d["roofline"]["exact_joint_pass"]; print(sys.argv[1], round(d["ms_per_step"], 4), {k: round(v, 4) for k, v in e["stages_ms"].items()})'
 for v in SLIDE_CHOL_PAIR=0 SLIDE_CHOL_PAIR=15 SLIDE_CHOL_PAIR=1 SLIDE_CHOL_PAIR=2 SLIDE_CHOL_PAIR=4 SLIDE_CHOL_PAIR=8; do
   env $v timeout -k 10 300 $B 2> gpurun_out/r5_pair_bench.err | python -c "$pick" "$v" || exit 1
