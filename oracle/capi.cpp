@@ -215,6 +215,33 @@ int orc_backend_landmark_table(void* h, int cls, double* xyz, int* label, int ca
 }
 // force a full relinearisation on the next solve (batch Gauss-Newton mode = threshold 0)
 void orc_graph_set_relin_threshold(void* h, double thr) { ((Graph*)h)->P.relin_threshold = thr; }
+// the merged graph as data (pending values and factors are merged first, as solve() would): counts[0] = variables, counts[1] =
+// factors; with non-null outputs also, per variable, its type, key and value (theta: before the first solve, the initial value;
+// 15 doubles, layouts of graph.hpp), and per factor its type, variable indices (v1 = -1 for a prior), measurement z (15) and the
+// sigmas graph.hpp's add* functions chose (9).  Test infrastructure: an independent least-squares step is built from these with
+// orc_linearize and needs no Schur elimination.
+void orc_graph_export(void* h, int* counts, int* var_type, uint64_t* var_key, double* var_val, int* f_type, int* f_v,
+                      double* f_z, double* f_sigma) {
+  Graph* g = (Graph*)h;
+  g->merge_pending();
+  counts[0] = (int)g->vars.size();
+  counts[1] = (int)g->factors.size();
+  if (var_type)
+    for (size_t i = 0; i < g->vars.size(); ++i) {
+      var_type[i] = g->vars[i].type;
+      var_key[i] = g->var_keys[i];
+      std::memcpy(var_val + 15 * i, g->vars[i].val, 15 * sizeof(double));
+    }
+  if (f_type)
+    for (size_t i = 0; i < g->factors.size(); ++i) {
+      const Factor& f = g->factors[i];
+      f_type[i] = f.type;
+      f_v[2 * i] = f.v0;
+      f_v[2 * i + 1] = f.v1;
+      std::memcpy(f_z + 15 * i, f.z, 15 * sizeof(double));
+      std::memcpy(f_sigma + 9 * i, f.sigma, 9 * sizeof(double));
+    }
+}
 // [GTSAM] iSAM2's wildfire threshold on the back-substitution (Graph::wildfire_bound); 0 = off (the default); out3: blocks kept in
 // total, in the last solve, the last solve's first dirty block column
 void orc_graph_set_wildfire(void* h, double thr) { ((Graph*)h)->P.wildfire_threshold = thr > 0.0 ? thr : 0.0; }

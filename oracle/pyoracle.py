@@ -236,6 +236,18 @@ class OracleGraph:
         self.L.orc_graph_add_relative_meas_ghost(self.h, _p(_d(rel7)), C.c_uint64(idx), C.c_int(robot), C.c_int(slot),
                                                  C.c_int(int(local_first)))
 
+    def export(self):
+        """The merged graph as arrays (pending entries are merged first, as solve() would): per variable type, key and value
+        (15 doubles; before the first solve the initial value), per factor type, (v0, v1) variable indices (v1 = -1: prior),
+        measurement z (15) and sigmas (9) as the graph chose them (oracle/capi.cpp orc_graph_export)."""
+        cnt = np.zeros(2, np.int32)
+        self.L.orc_graph_export(self.h, _p(cnt), None, None, None, None, None, None, None)
+        nv, nf = int(cnt[0]), int(cnt[1])
+        vt, vk, vv = np.zeros(nv, np.int32), np.zeros(nv, np.uint64), np.zeros((nv, 15))
+        ft, fv, fz, fs = np.zeros(nf, np.int32), np.zeros((nf, 2), np.int32), np.zeros((nf, 15)), np.zeros((nf, 9))
+        self.L.orc_graph_export(self.h, _p(cnt), _p(vt), _p(vk), _p(vv), _p(ft), _p(fv), _p(fz), _p(fs))
+        return dict(var_type=vt, var_key=vk, var_val=vv, f_type=ft, f_v=fv, f_z=fz, f_sigma=fs)
+
     def stats(self):
         out = np.zeros(8)
         self.L.orc_graph_stats(self.h, _p(out))

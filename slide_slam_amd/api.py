@@ -141,8 +141,17 @@ def _i(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+class _Ptr(C.c_void_p):
+    """A pointer argument that holds the array it points into (a slot: no per-call attribute dictionary)."""
+    __slots__ = ("keep",)
+
+
 def _p(a):
-    return C.c_void_p(a.ctypes.data)      # (ndarray.ctypes.data_as costs 2.9 us a call, this 1.1: a streaming frame passes eighteen pointers)
+    # (ndarray.ctypes.data_as costs 2.9 us a call, this 1.1: a streaming frame passes eighteen pointers.)  The pointer carries the
+    # array: _p(_d(list)) converts into a temporary that nothing else holds, and freed memory would be passed otherwise.
+    v = _Ptr(a.ctypes.data)
+    v.keep = a
+    return v
 
 
 class SlideGraph:

@@ -461,6 +461,7 @@ void HostGraph::join_batch(CholBatch* b, int slot) {
     batch = b;
     batch_slot = slot;
     factor_valid = false;   // (batched passes factor into the same S: a factor left by one is not the streaming path's)
+    wf_T = 0;               // (nor is its dp the last streaming solve's solution)
     topo_dirty = true;      // (the joint-solve buffers depend on the batch's setting: upload_new looks again)
   }
   if (old && old != b) old->detach(this);
@@ -1955,6 +1956,14 @@ int HostGraph::upload_new() {
     g_last_error = "Schur LDS lookup capacity exceeded (about 60000 landmarks in one graph)";
     return SLIDE_ERR_CAPACITY;
   }
+  // ... and the table's entries are positions in the column pose's landmark-factor list (shorts): a longer list would wrap them
+  // negative and k_schur would drop those landmarks' Schur terms
+  for (const std::vector<int>& pl : pose_fids)
+    if (pl.size() > 32768) {
+      (void)ub.flush(s);
+      g_last_error = "Schur LDS lookup capacity exceeded (a pose with more than 32768 landmark factors)";
+      return SLIDE_ERR_CAPACITY;
+    }
   if (up_csr(csr_bt, d_pose_bt_ptr, d_pose_bt, pose_bt, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   {
     const size_t f0 = std::min<size_t>((size_t)std::max(lm_first_from, 0), std::min(up_L, Ln));      // (new landmarks and every touched one)
@@ -2447,6 +2456,13 @@ int HostGraph::run_update(double relin_thr, int iterations) {
   thread_capture_mode_local();
   hipStream_t s = stream;
   if (G.P == 0) return SLIDE_OK;
+  // dp is overwritten from the first launch on: unless this update ends in the success path below (which sets wf_T = G.T), no
+  // later update may keep a block of it (the bounded back-substitution) — every early return included
+  struct WfReset {
+    int& T;
+    bool keep = false;
+    ~WfReset() { if (!keep) T = 0; }
+  } wf_reset{wf_T};
   G.relin_thr = relin_thr;
   if (!status_clean) SL_HIP(hipMemsetAsync(d_status.d, 0, 8 * sizeof(int), s));      // (k_final_pack of the last update left them at zero otherwise)
   status_clean = false;
@@ -2588,6 +2604,7 @@ int HostGraph::run_update(double relin_thr, int iterations) {
   lin_solved_gen = lin_gen;         // (every linearisation buffer holds this solve's state)
   dirty_min_pose = 1 << 30;
   wf_T = G.T;                       // (dp holds this solve's solution for every block column)
+  wf_reset.keep = true;
   last_wf_kept = st[3];
   n_wf_kept += st[3];
   return SLIDE_OK;
@@ -2760,6 +2777,7 @@ int HostGraph::dist_phase(int phase, double* d_buf) {
   pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   hipStream_t s = stream;
   factor_valid = false;      // (the phases move linearisation points and factor into S on their own schedule)
+  wf_T = 0;                  // (and leave dp holding no streaming solve's solution)
   if (phase >= 0 && phase <= 2) {
     if (phase == 0) {
       int rc = merge_pending();
@@ -2818,6 +2836,7 @@ int HostGraph::dist_phase(int phase, double* d_buf) {
 int HostGraph::dist_pass_local(double* d_buf) {
   pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   if (!batch) { g_last_error = "dist_pass_local: the graph is in no batch"; return SLIDE_ERR_INVALID; }
+  wf_T = 0;      // (the pass moves the linearisation points: the last streaming solve's dp is no previous solution of the next)
   hipStream_t s = stream;
   int rc = merge_pending();
   if (rc != SLIDE_OK) return rc;
@@ -2921,6 +2940,7 @@ int HostGraph::chi2(double* out4) {
   G.relin_thr = 0.0;
   launch_relin(G, s);                 // theta <- theta (+) delta ...
   SL_HIP(hipMemsetAsync(G.pose_delta, 0, 6 * (size_t)G.P * sizeof(double), s));      // ... and delta <- 0: the next update must not apply it again
+  wf_T = 0;                           // (nor may the bounded back-substitution keep a block of the last solve's dp: it is folded in now)
   if (G.L) SL_HIP(hipMemsetAsync(G.lm_delta, 0, 9 * (size_t)G.L * sizeof(double), s));
   launch_linearize(G, s);
   launch_estimate(G, s);

@@ -1,5 +1,6 @@
 """The C-ABI library loads on a GPU-less host and exports every symbol include/slide_gpu.h declares;
 compute entry points fail loudly (no CPU fallback)."""
+import ctypes
 import os
 import re
 
@@ -268,3 +269,17 @@ def test_cpp_adaptor_compiles_and_links(tmp_path):
     import subprocess
     exe = _build_adaptor_check(tmp_path)
     assert subprocess.run([exe]).returncode == 0          # no argument: link check only
+
+
+def test_pointer_keeps_its_converted_array():
+    """api._p(api._d(list)) converts into a temporary nothing else holds: the pointer must keep it alive for the call, or two such
+    arguments of one call (add_keypose_between's rel and est) can share freed memory and read the second's contents."""
+    import gc
+    from slide_slam_amd import api
+    a = api._p(api._d([1.0, 2, 3, 4, 5, 6, 7]))
+    b = api._p(api._d([10.0, 20, 30, 40, 50, 60, 70]))
+    gc.collect()
+    assert a.value != b.value
+    ra = np.ctypeslib.as_array((ctypes.c_double * 7).from_address(a.value))
+    rb = np.ctypeslib.as_array((ctypes.c_double * 7).from_address(b.value))
+    assert np.array_equal(ra, np.arange(1, 8)) and np.array_equal(rb, 10 * np.arange(1, 8))
