@@ -108,6 +108,29 @@ int slide_graph_get_landmark(slide_graph_t* g, int cls, uint64_t idx, double* ou
  * linearisation point of the last solve (a forward substitution with six right-hand sides on the resident Cholesky factor).
  * SLIDE_MISSING for an unknown pose, SLIDE_ERR_INVALID before the first solve. */
 int slide_graph_get_pose_covariance(slide_graph_t* g, int robot, uint64_t idx, double cov36[36]);
+/* Marginals of the dormant active-SLAM API (SemanticFactorGraph::logEntropy / estimateClosureInfoGain, graph.h:106,113; bodies
+ * commented out in graph.cpp:421-625), on the single-graph path only: SLIDE_ERR_INVALID in sharded or exact-joint mode (ghost factors,
+ * shared-landmark slots, a graph joined to a slide_chol_batch), before the first solve, after slide_graph_chi2, and once a call merged
+ * pending factors or variables after the last solve (e.g. slide_graph_get_tile_profile); SLIDE_MISSING for an unknown key.  Every
+ * value is taken at the linearisation point of the resident factor, from its selected inverse Sigma = S^-1 on the factor's tile
+ * profile (computed once per factorisation).
+ * isam->marginalCovariance(X(idx[q])) (graph.cpp:314-323) for n poses: out36n[36 q ..], 6x6 row-major, tangent order [rot, trans]. */
+int slide_graph_get_pose_covariances(slide_graph_t* g, int robot, const uint64_t* idx, int n, double* out36n);
+/* isam->marginalCovariance(L / C / U(idx[q])) (graph.cpp:444): d x d row-major per landmark, d = 7 / 9 / 3 for cylinder / cube /
+ * point (SLIDE_CLS_ELLIPSOID), tangent order of the retraction: cylinder [ray, root, radius], cube pose (6) then scale (3), point xyz. */
+int slide_graph_get_landmark_covariances(slide_graph_t* g, int cls, const uint64_t* idx, int n, double* out);
+/* logEntropy (graph.cpp:423-466): out4 = {sum of the marginal traces of the robot's poses, sum over the point landmarks (U(i),
+ * ellipsoids included), #poses, #landmarks}. */
+int slide_graph_marginal_traces(slide_graph_t* g, int robot, double out4[4]);
+/* estimateClosureInfoGain (graph.cpp:469-623): the drop of those trace sums when Between factors (traj[i+1], traj[i]), i < n - 1, with
+ * noise sigma_per_m * travel[i] and zero residual are added (graph.cpp:503-545); sigma_per_m = NULL: the graph's noise_model_odom_vec
+ * (the reference's noise_model_pose_vec_per_m, graph.h:115, is never set).  out3 = {10 pose + landmark, pose, landmark}
+ * (graph.cpp:622).  Linear-Gaussian model of the resident factor (a rank-6(n-1) update, nothing is re-factored and the graph is left
+ * exactly as it was); unlike iSAM2's update it does not relinearise variables while the fake factors are in.  SLIDE_ERR_INVALID for
+ * n < 2, a travel distance or sigma <= 0; SLIDE_ERR_CAPACITY for n - 1 > SLIDE_INFO_GAIN_MAX_STEPS. */
+#define SLIDE_INFO_GAIN_MAX_STEPS 64
+int slide_graph_closure_info_gain(slide_graph_t* g, int robot, const uint64_t* traj, int n, const double* travel, const double sigma_per_m[6],
+                                  double out3[3]);
 /* counts: [poses, landmarks, factors, relinearised vars in the last solve, chol dim] */
 int slide_graph_stats(slide_graph_t* g, int64_t out5[5]);
 /* Sum of squared whitened residuals of every factor at the current estimate (= 2 x gtsam::NonlinearFactorGraph::error of the graph

@@ -166,6 +166,34 @@ class SemanticFactorGraph {
     detail::check(slide_graph_get_pose_covariance(g_, robotID, (uint64_t)idx, c.data()), "getPoseCovariance");
     return c;
   }
+  // ---- the dormant active-SLAM API (graph.h:106-115; bodies commented out in graph.cpp:421-625) ----------------------------------
+  // logEntropy (graph.cpp:423-466) without its log file: the sums of the marginal-covariance traces of the robot's poses X(i) and of
+  // the point landmarks U(i), and how many of each were summed
+  struct EntropyTerms { double sum_entropy_pose, sum_entropy_landmark; size_t num_valid_poses, num_valid_landmarks; };
+  EntropyTerms logEntropy(const int& robotID = 0) const {
+    double o[4];
+    detail::check(slide_graph_marginal_traces(g_, robotID, o), "logEntropy");
+    return EntropyTerms{o[0], o[1], (size_t)o[2], (size_t)o[3]};
+  }
+  // estimateClosureInfoGain (graph.cpp:469-623): 10 * info_gain_pose + info_gain_landmark of Between factors along the candidate
+  // trajectory (noise noise_model_pose_vec_per_m * travel distance); the graph is left as it was
+  double estimateClosureInfoGain(const std::vector<size_t>& candidateTrajPoseIndices, const std::vector<double>& travel_distances,
+                                 const int& robotID = 0) const {
+    if (candidateTrajPoseIndices.size() != travel_distances.size() + 1)
+      throw Error(SLIDE_ERR_INVALID, "estimateClosureInfoGain: one travel distance per step of the trajectory");
+    std::vector<uint64_t> traj(candidateTrajPoseIndices.begin(), candidateTrajPoseIndices.end());
+    double o[3];
+    if (!noise_model_pose_vec_per_m.empty() && noise_model_pose_vec_per_m.size() != 6)
+      throw Error(SLIDE_ERR_INVALID, "estimateClosureInfoGain: noise_model_pose_vec_per_m has six entries");
+    const int rc = slide_graph_closure_info_gain(g_, robotID, traj.data(), (int)traj.size(), travel_distances.data(),
+                                                 noise_model_pose_vec_per_m.empty() ? nullptr : noise_model_pose_vec_per_m.data(), o);
+    detail::check(rc, "estimateClosureInfoGain");
+    if (rc == SLIDE_MISSING) throw std::out_of_range("estimateClosureInfoGain: trajectory pose not in the graph");
+    return o[0];
+  }
+  // graph.h:115 (never set in the reference): empty = the graph's own noise_model_odom_vec, else six sigmas per metre
+  std::vector<double> noise_model_pose_vec_per_m;
+
   slide_graph_t* handle() const { return g_; }
 
  protected:

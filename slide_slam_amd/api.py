@@ -28,7 +28,7 @@ EXPORTS = [
     "slide_graph_add_loop_closure", "slide_graph_add_relative_meas", "slide_graph_add_point_landmark",
     "slide_graph_add_range_bearing", "slide_graph_add_cube", "slide_graph_add_cylinder", "slide_graph_solve",
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
-    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
+    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
     "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
@@ -251,6 +251,55 @@ class SlideGraph:
         if st < 0:
             _check(st)
         return st, out.reshape(6, 6)
+
+    def get_pose_covariances(self, robot, idx):
+        """isam->marginalCovariance(X(i)) for every pose index in `idx` of `robot`: (n, 6, 6), tangent order [rot, trans].  One
+        selected inversion of the resident factor per factorisation serves every later call.  KeyError for an unknown pose."""
+        ids = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros(36 * len(ids))
+        st = self.L.slide_graph_get_pose_covariances(self.h, C.c_int(robot), _p(ids), C.c_int(len(ids)), _p(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"pose of robot {robot} not in the graph")
+        _check(st)
+        return out.reshape(-1, 6, 6)
+
+    def get_landmark_covariances(self, cls, idx):
+        """Marginal covariances of landmarks of class `cls` (CLS_*): (n, d, d), d = 7 / 9 / 3 for cylinder / cube / point, tangent
+        order cylinder [ray, root, radius], cube pose (6) then scale (3), point xyz.  KeyError for an unknown landmark."""
+        d = {CLS_CYLINDER: 7, CLS_CUBE: 9}.get(cls, 3)
+        ids = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros(d * d * len(ids))
+        st = self.L.slide_graph_get_landmark_covariances(self.h, C.c_int(cls), _p(ids), C.c_int(len(ids)), _p(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"landmark of class {cls} not in the graph")
+        _check(st)
+        return out.reshape(-1, d, d)
+
+    def marginal_traces(self, robot=0):
+        """logEntropy (graph.cpp:423-466): [pose trace sum, point-landmark trace sum, #poses, #point landmarks]."""
+        out = np.zeros(4)
+        _check(self.L.slide_graph_marginal_traces(self.h, C.c_int(robot), _p(out)))
+        return out
+
+    def closure_info_gain(self, robot, traj, travel, sigma_per_m=None):
+        """estimateClosureInfoGain (graph.cpp:469-623): [10 pose + landmark, pose, landmark] information gain of Between factors
+        (traj[i+1], traj[i]) with noise sigma_per_m * travel[i] (None: the graph's own noise_model_odom_vec), at the resident factor."""
+        t = np.ascontiguousarray(traj, dtype=np.uint64).reshape(-1)
+        tr = _d(travel).reshape(-1)
+        if len(tr) != max(len(t) - 1, 0):
+            raise ValueError("travel needs one distance per step of traj")
+        sg = None
+        if sigma_per_m is not None:
+            sg = _d(sigma_per_m).reshape(-1)
+            if len(sg) != 6:
+                raise ValueError("sigma_per_m has six entries")
+        out = np.zeros(3)
+        st = self.L.slide_graph_closure_info_gain(self.h, C.c_int(robot), _p(t), C.c_int(len(t)), _p(tr),
+                                                  _p(sg) if sg is not None else None, _p(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"trajectory pose of robot {robot} not in the graph")
+        _check(st)
+        return out
 
     def set_ghosts(self, own_robot, own_idx):
         r = _i(own_robot)

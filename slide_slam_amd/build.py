@@ -23,6 +23,7 @@ SOURCES = [
     # AGPR destinations every such edit costs v_accvgpr copies and hazard nops
     ("chol_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("pcg_kernels.hip", []),
+    ("cov_kernels.hip", []),
     ("assoc_kernels.hip", ["-ffp-contract=off"]),
     ("place_kernels.hip", ["-ffp-contract=off"]),
     ("clipper_kernels.hip", ["-ffp-contract=off"]),

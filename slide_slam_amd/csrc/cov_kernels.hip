@@ -1,0 +1,437 @@
+// Marginal covariances and loop-closure information gain on the resident Cholesky factor of the reduced pose system
+// (the dormant active-SLAM API of the reference: SemanticFactorGraph::logEntropy / estimateClosureInfoGain, graph.h:106,113).
+//
+// Layout as in chol_kernels.hip: S column-major with leading dimension ld, tile edge NB = 64, the diagonal blocks L_kk as their
+// off-diagonal 16x16 sub-blocks in Ld (64x64 column-major per block) plus the inverses of their four 16x16 diagonal sub-blocks in
+// Winv (1024 doubles per block, (L_bb^-1)[r][j] at b * 256 + j * 16 + r).  Sigma = S^-1 has S's layout and ld; only tiles inside the
+// tile profile are written or read, and the diagonal tiles hold the full symmetric 64x64 block.
+//
+// Selected inversion (backward over the block columns k, I = k+1 .. prof[k]):
+//     Z_I      = L_Ik L_kk^-1                         k_sinv_prep (every k at once)
+//     Sigma_Ik = - Sigma_II Z_I                       k_sinv_tile<false>, one workgroup per output tile
+//     Sigma_kk = L_kk^-T L_kk^-1 - Sigma_Ik^T Z_I     k_sinv_tile<true>
+// Every Sigma(i, j) with i, j in I lies inside the profile (eliminating column k fills exactly that), so the recursion never reads a
+// tile outside it.  The products are 64x64 tiles with K = 64 |I| on v_mfma_f64_16x16x4_f64.
+// f64 MFMA lane maps (cdna_hip_programming.md §3): A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
+// D[row = (lane>>4) + 4*reg][col = lane&15].
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "graph_dev.hpp"
+#include "kernels.hpp"
+
+namespace sl {
+
+namespace {
+typedef double v4d __attribute__((ext_vector_type(4)));
+__device__ inline v4d mfma_f64(double a, double b, v4d c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+// Sigma(R, C) of the selected inverse: the lower triangle is stored (and both halves of a diagonal tile)
+__device__ __forceinline__ double sig_at(const double* __restrict__ Sg, int ld, int R, int C) {
+  return R >= C ? Sg[(size_t)C * ld + R] : Sg[(size_t)R * ld + C];
+}
+
+// X[c][r] = (L_kk^-1)[r][c]: block forward substitution on the 64 unit columns, as k_cov_fwd walks the four 16x16 sub-blocks
+__device__ void linv_block(double (*X)[NB + 1], const double* __restrict__ Ldk, const double* __restrict__ Wk) {
+  const int tid = threadIdx.x;
+  for (int e = tid; e < NB * NB; e += 256) X[e >> 6][e & 63] = (e >> 6) == (e & 63) ? 1.0 : 0.0;
+  __syncthreads();
+  const int c = tid & 63, rq = tid >> 6;        // column c, rows 4 rq .. 4 rq + 3 of a 16-block
+#pragma unroll 1
+  for (int b = 0; b < 4; ++b) {
+    double t[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) s += Wk[b * 256 + j * 16 + 4 * rq + rr] * X[c][16 * b + j];
+      t[rr] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) X[c][16 * b + 4 * rq + rr] = t[rr];
+    __syncthreads();
+    const int nr = 16 * (3 - b);
+    for (int e = tid; e < NB * nr; e += 256) {     // rows below block b: y[m] -= sum_n L[m][16 b + n] x[16 b + n]
+      const int cc = e / nr, m = 16 * (b + 1) + e % nr;
+      double s = 0.0;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) s += Ldk[(size_t)(16 * b + n) * NB + m] * X[cc][16 * b + n];
+      X[cc][m] -= s;
+    }
+    __syncthreads();
+  }
+}
+}  // namespace
+
+// blockIdx.x = k; blockIdx.y = 0: Sigma_kk <- L_kk^-T L_kk^-1; blockIdx.y = b > 0: Z(k + b, k) = L(k + b, k) L_kk^-1 if inside the profile.
+// Every workgroup of column k rebuilds L_kk^-1 in LDS (band + 1 times the work of one): cheap at the chain's band of 2-3 tiles (this
+// launch is ~3% of the inversion there); a wide profile would rather build it once per column and read it back.
+__global__ __launch_bounds__(256) void k_sinv_prep(const double* __restrict__ S, int ld, int T, const double* __restrict__ Ld,
+                                                   const double* __restrict__ Winv, const int* __restrict__ prof, double* __restrict__ Sg,
+                                                   double* __restrict__ Z) {
+  const int k = blockIdx.x, i = k + (int)blockIdx.y;
+  if (i >= T || (prof && i > prof[k])) return;
+  __shared__ double X[NB][NB + 1];
+  linv_block(X, Ld + (size_t)k * NB * NB, Winv + (size_t)k * 1024);
+  const int tid = threadIdx.x;
+  if (i == k) {
+    for (int e = tid; e < NB * NB; e += 256) {
+      const int b = e >> 6, a = e & 63;
+      double s = 0.0;
+      for (int r = (a > b ? a : b); r < NB; ++r) s += X[a][r] * X[b][r];      // (L^-1 lower triangular)
+      Sg[(size_t)(k * NB + b) * ld + (size_t)k * NB + a] = s;
+    }
+    return;
+  }
+  const double* L = S + (size_t)(k * NB) * ld + (size_t)i * NB;
+  for (int e = tid; e < NB * NB; e += 256) {
+    const int c = e >> 6, row = e & 63;
+    double s = 0.0;
+    for (int q = c; q < NB; ++q) s += L[(size_t)q * ld + row] * X[c][q];
+    Z[(size_t)(k * NB + c) * ld + (size_t)i * NB + row] = s;
+  }
+}
+
+// DIAG = false: blockIdx.x -> tile row i = k + 1 + blockIdx.x, Sigma(i, k) = - sum_{j = k+1 .. i1} Sigma(i, j) Z(j, k).
+// DIAG = true (one workgroup): Sigma(k, k) -= sum_{i = k+1 .. i1} Sigma(i, k)^T Z(i, k), then symmetrised.
+// Four waves, a 32x32 quadrant each (2 x 2 accumulators); the operand tiles of one K step of 64 are staged in LDS as [k][row / col].
+template <bool DIAG>
+__global__ __launch_bounds__(256) void k_sinv_tile(double* __restrict__ Sg, const double* __restrict__ Z, int ld, int k, int i1) {
+  __shared__ double As[NB][NB + 1];
+  __shared__ double Bs[NB][NB + 1];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4, rh = w & 1, ch = w >> 1;
+  const int i = DIAG ? k : k + 1 + (int)blockIdx.x;
+  v4d acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (int j = k + 1; j <= i1; ++j) {
+    if (DIAG) {            // A[r][q] = Sigma(j, k)[q][r]
+      const double* src = Sg + (size_t)(k * NB) * ld + (size_t)j * NB;
+      for (int e = tid; e < NB * NB; e += 256) { const int r = e >> 6, q = e & 63; As[q][r] = src[(size_t)r * ld + q]; }
+    } else if (j <= i) {   // A[r][q] = Sigma(i, j)[r][q]
+      const double* src = Sg + (size_t)(j * NB) * ld + (size_t)i * NB;
+      for (int e = tid; e < NB * NB; e += 256) { const int q = e >> 6, r = e & 63; As[q][r] = src[(size_t)q * ld + r]; }
+    } else {               // A[r][q] = Sigma(j, i)[q][r]
+      const double* src = Sg + (size_t)(i * NB) * ld + (size_t)j * NB;
+      for (int e = tid; e < NB * NB; e += 256) { const int r = e >> 6, q = e & 63; As[q][r] = src[(size_t)r * ld + q]; }
+    }
+    {                      // B[q][c] = Z(j, k)[q][c]
+      const double* src = Z + (size_t)(k * NB) * ld + (size_t)j * NB;
+      for (int e = tid; e < NB * NB; e += 256) { const int c = e >> 6, q = e & 63; Bs[q][c] = src[(size_t)c * ld + q]; }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int q0 = 0; q0 < NB; q0 += 4) {
+      double a[2], b[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        a[t] = As[q0 + lk][32 * rh + 16 * t + lr];
+        b[t] = Bs[q0 + lk][32 * ch + 16 * t + lr];
+      }
+#pragma unroll
+      for (int ra = 0; ra < 2; ++ra)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) acc[ra][cb] = mfma_f64(a[ra], b[cb], acc[ra][cb]);
+    }
+    __syncthreads();
+  }
+  if (!DIAG) {
+    double* dst = Sg + (size_t)(k * NB) * ld + (size_t)i * NB;
+#pragma unroll
+    for (int ra = 0; ra < 2; ++ra)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int row = 32 * rh + 16 * ra + lk + 4 * g, col = 32 * ch + 16 * cb + lr;
+          dst[(size_t)col * ld + row] = -acc[ra][cb][g];
+        }
+    return;
+  }
+  double* dst = Sg + (size_t)(k * NB) * ld + (size_t)k * NB;
+#pragma unroll
+  for (int ra = 0; ra < 2; ++ra)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int row = 32 * rh + 16 * ra + lk + 4 * g, col = 32 * ch + 16 * cb + lr;
+        As[row][col] = dst[(size_t)col * ld + row] - acc[ra][cb][g];
+      }
+  __syncthreads();
+  for (int e = tid; e < NB * NB; e += 256) {
+    const int col = e >> 6, row = e & 63;
+    dst[(size_t)col * ld + row] = 0.5 * (As[row][col] + As[col][row]);
+  }
+}
+
+// host: the selected inverse of the factor (prof: host copy of the tile profile, or null: dense; d_prof the device copy or null)
+void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
+                             double* Sg, double* Z, hipStream_t s) {
+  if (T <= 0) return;
+  int band = 0;
+  for (int k = 0; k < T; ++k) band = std::max(band, (prof ? prof[k] : T - 1) - k);
+  hipLaunchKernelGGL(k_sinv_prep, dim3(T, band + 1), dim3(256), 0, s, S, ld, T, Ld, Winv, prof ? d_prof : nullptr, Sg, Z);
+  for (int k = T - 1; k >= 0; --k) {
+    const int i1 = prof ? prof[k] : T - 1;
+    if (i1 <= k) continue;
+    hipLaunchKernelGGL((k_sinv_tile<false>), dim3(i1 - k), dim3(256), 0, s, Sg, (const double*)Z, ld, k, i1);
+    hipLaunchKernelGGL((k_sinv_tile<true>), dim3(1), dim3(256), 0, s, Sg, (const double*)Z, ld, k, i1);
+  }
+}
+
+// 6x6 diagonal blocks of the poses rows[p] (pose indices) out of the selected inverse: out[36 p + 6 a + b]
+__global__ void k_pose_blocks(const double* __restrict__ Sg, int ld, const int* __restrict__ poses, int n, double* __restrict__ out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 36 * n) return;
+  const int p = e / 36, a = (e % 36) / 6, b = e % 6;
+  const int r0 = 6 * poses[p];
+  out[e] = sig_at(Sg, ld, r0 + a, r0 + b);
+}
+void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_pose_blocks, dim3((36 * n + 255) / 256), dim3(256), 0, s, Sg, ld, poses, n, out);
+}
+
+// Landmark marginal (Schur identity): Sigma_ll = H_ll^-1 + sum_{f, g in factors(l)} F_f^T Sigma(p_f, p_g) F_g, F = E H_ll^-1 (ebuf).
+// One wavefront per landmark lids[q]; out[81 q ..] = the d x d block, row-major.  Per factor f: Q_f = sum_g Sigma(p_f, p_g) F_g
+// (6 x d, lane a d + c), then every lane adds its entries of F_f^T Q_f.
+__global__ __launch_bounds__(64) void k_lm_cov(GraphDev G, const double* __restrict__ Sg, int ld, const int* __restrict__ lids, int n,
+                                               double* __restrict__ out) {
+  const int q = blockIdx.x, lane = threadIdx.x;
+  if (q >= n) return;
+  __shared__ double Qs[54];
+  const int l = lids[q];
+  const int D = lm_dim(G.lm_type[l]);
+  const int f0 = G.lm_ptr[l], nf = G.lm_ptr[l + 1] - f0;
+  double acc[2] = {0.0, 0.0};
+  const int a = lane / D, c = lane - (lane / D) * D;
+  for (int qf = 0; qf < nf; ++qf) {
+    const int f = G.lm_fids[f0 + qf];
+    const int rf = 6 * G.lf_pose[f];
+    if (lane < 6 * D) {
+      double s = 0.0;
+      for (int qg = 0; qg < nf; ++qg) {
+        const int g = G.lm_fids[f0 + qg];
+        const int rg = 6 * G.lf_pose[g];
+        const double* Fg = G.ebuf + G.lf_eoff[g] + 6 * D;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) s += sig_at(Sg, ld, rf + a, rg + b) * Fg[b * D + c];
+      }
+      Qs[lane] = s;
+    }
+    __syncthreads();
+    const double* Ff = G.ebuf + G.lf_eoff[f] + 6 * D;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = lane + 64 * h;
+      if (e < D * D) {
+        const int r = e / D, cc = e - r * D;
+        double s = 0.0;
+#pragma unroll
+        for (int aa = 0; aa < 6; ++aa) s += Ff[aa * D + r] * Qs[aa * D + cc];
+        acc[h] += s;
+      }
+    }
+    __syncthreads();
+  }
+  const double* Hi = G.lm_Hinv + 81 * (size_t)l;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int e = lane + 64 * h;
+    if (e < D * D) out[81 * (size_t)q + e] = Hi[e] + acc[h];
+  }
+}
+void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_lm_cov, dim3(n), dim3(64), 0, s, G, Sg, ld, lids, n, out);
+}
+
+// ---- many right-hand sides: U = S^-1 B (B: nrhs columns of nT = T * NB rows, column-major) --------------------------------------------
+// Forward, one launch per block column k: blockIdx.y = chunk of 16 columns; workgroup 0 solves the 64 x 16 block of L_kk and stores
+// x_k into X (tile row k), workgroup b > 0 applies tile (k + b, k) to its own rows of Y (in place).  Tile row k of Y is only read in
+// this launch, so no workgroup sees another's write.
+__global__ __launch_bounds__(256) void k_sub_fwd(const double* __restrict__ S, int ld, int k, const double* __restrict__ Ldk,
+                                                 const double* __restrict__ Wk, double* __restrict__ Y, double* __restrict__ X, int nT,
+                                                 int nrhs) {
+  __shared__ double yk[16][NB];
+  __shared__ double xk[16][NB];
+  const int tid = threadIdx.x, c0 = 16 * (int)blockIdx.y;
+  const int nc = nrhs - c0 < 16 ? nrhs - c0 : 16;
+  for (int e = tid; e < 16 * NB; e += 256) {
+    const int cc = e / NB, r = e % NB;
+    yk[cc][r] = cc < nc ? Y[(size_t)(c0 + cc) * nT + (size_t)k * NB + r] : 0.0;
+  }
+  __syncthreads();
+  const int c = tid >> 4, r = tid & 15;
+#pragma unroll 1
+  for (int b = 0; b < 4; ++b) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s += Wk[(size_t)b * 256 + j * 16 + r] * yk[c][16 * b + j];
+    xk[c][16 * b + r] = s;
+    __syncthreads();
+    for (int e = tid; e < 16 * 16 * (3 - b); e += 256) {
+      const int cc = e / (16 * (3 - b)), m = 16 * (b + 1) + e % (16 * (3 - b));
+      double t = 0.0;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) t += Ldk[(size_t)(16 * b + n) * NB + m] * xk[cc][16 * b + n];
+      yk[cc][m] -= t;
+    }
+    __syncthreads();
+  }
+  if (blockIdx.x == 0) {
+    for (int e = tid; e < nc * NB; e += 256) X[(size_t)(c0 + e / NB) * nT + (size_t)k * NB + e % NB] = xk[e / NB][e % NB];
+    return;
+  }
+  const int i = k + (int)blockIdx.x;
+  const double* tile = S + (size_t)(k * NB) * ld + (size_t)i * NB;
+  for (int e = tid; e < nc * NB; e += 256) {
+    const int cc = e / NB, row = e % NB;
+    double s = 0.0;
+#pragma unroll 8
+    for (int q = 0; q < NB; ++q) s += tile[(size_t)q * ld + row] * xk[cc][q];
+    Y[(size_t)(c0 + cc) * nT + (size_t)i * NB + row] -= s;
+  }
+}
+// Backward, one launch per block column k (from the last): x_k = L_kk^-T (x_k - sum_{i = k+1 .. i1} L_ik^T x_i), in place in X;
+// one workgroup per chunk of 16 columns.
+__global__ __launch_bounds__(256) void k_sub_bwd(const double* __restrict__ S, int ld, int k, int i1, const double* __restrict__ Ldk,
+                                                 const double* __restrict__ Wk, double* __restrict__ X, int nT, int nrhs) {
+  __shared__ double Lt[NB][NB + 1];
+  __shared__ double xi[16][NB];
+  __shared__ double tk[16][NB];
+  const int tid = threadIdx.x, c0 = 16 * (int)blockIdx.x;
+  const int nc = nrhs - c0 < 16 ? nrhs - c0 : 16;
+  for (int e = tid; e < 16 * NB; e += 256) {
+    const int cc = e / NB, r = e % NB;
+    tk[cc][r] = cc < nc ? X[(size_t)(c0 + cc) * nT + (size_t)k * NB + r] : 0.0;
+  }
+#pragma unroll 1
+  for (int i = k + 1; i <= i1; ++i) {
+    const double* tile = S + (size_t)(k * NB) * ld + (size_t)i * NB;
+    for (int e = tid; e < NB * NB; e += 256) { const int m = e >> 6, row = e & 63; Lt[m][row] = tile[(size_t)m * ld + row]; }
+    for (int e = tid; e < 16 * NB; e += 256) {
+      const int cc = e / NB, r = e % NB;
+      xi[cc][r] = cc < nc ? X[(size_t)(c0 + cc) * nT + (size_t)i * NB + r] : 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < 16 * NB; e += 256) {
+      const int cc = e / NB, m = e % NB;
+      double s = 0.0;
+#pragma unroll 8
+      for (int row = 0; row < NB; ++row) s += Lt[m][row] * xi[cc][row];
+      tk[cc][m] -= s;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  const int c = tid >> 4, r = tid & 15;
+#pragma unroll 1
+  for (int b = 3; b >= 0; --b) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s += Wk[(size_t)b * 256 + r * 16 + j] * tk[c][16 * b + j];      // (L_bb^-1)[j][r]
+    __syncthreads();
+    tk[c][16 * b + r] = s;
+    __syncthreads();
+    for (int e = tid; e < 16 * 16 * b; e += 256) {       // rows n of the blocks before b: t[n] -= sum_m L[16 b + m][n] x[16 b + m]
+      const int cc = e / (16 * b), n = e % (16 * b);
+      double t = 0.0;
+#pragma unroll
+      for (int m = 0; m < 16; ++m) t += Ldk[(size_t)n * NB + 16 * b + m] * tk[cc][16 * b + m];
+      tk[cc][n] -= t;
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < nc * NB; e += 256) X[(size_t)(c0 + e / NB) * nT + (size_t)k * NB + e % NB] = tk[e / NB][e % NB];
+}
+// B (nrhs columns of T * NB rows) is overwritten; X = S^-1 B
+void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* X,
+                        int nrhs, hipStream_t s) {
+  const int nT = T * NB, nch = (nrhs + 15) / 16;
+  if (T <= 0 || nrhs <= 0) return;
+  for (int k = 0; k < T; ++k) {
+    const int i1 = prof ? prof[k] : T - 1;
+    hipLaunchKernelGGL(k_sub_fwd, dim3(i1 - k + 1, nch), dim3(256), 0, s, S, ld, k, Ld + (size_t)k * NB * NB, Winv + (size_t)k * 1024,
+                       B, X, nT, nrhs);
+  }
+  for (int k = T - 1; k >= 0; --k) {
+    const int i1 = prof ? prof[k] : T - 1;
+    hipLaunchKernelGGL(k_sub_bwd, dim3(nch), dim3(256), 0, s, S, ld, k, i1, Ld + (size_t)k * NB * NB, Winv + (size_t)k * 1024, X, nT, nrhs);
+  }
+}
+
+// M[a][b] = sum_q X[a ldx + row_q] X[b ldx + row_q] (a, b < ncol), rows = the list or (null) 0 .. nrows-1.  16x16 output tiles.
+__global__ __launch_bounds__(256) void k_gram(const double* __restrict__ X, size_t ldx, int ncol, const int* __restrict__ rows, int nrows,
+                                              double* __restrict__ M) {
+  __shared__ double xa[16][65], xb[16][65];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int a0 = 16 * (int)blockIdx.y, b0 = 16 * (int)blockIdx.x;
+  double s = 0.0;
+  for (int q0 = 0; q0 < nrows; q0 += 64) {
+    for (int e = threadIdx.x; e < 16 * 64; e += 256) {
+      const int cc = e >> 6, qq = e & 63, q = q0 + qq;
+      const int row = q < nrows ? (rows ? rows[q] : q) : -1;
+      xa[cc][qq] = (row >= 0 && a0 + cc < ncol) ? X[(size_t)(a0 + cc) * ldx + row] : 0.0;
+      xb[cc][qq] = (row >= 0 && b0 + cc < ncol) ? X[(size_t)(b0 + cc) * ldx + row] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int qq = 0; qq < 64; ++qq) s += xa[ty][qq] * xb[tx][qq];
+    __syncthreads();
+  }
+  if (a0 + ty < ncol && b0 + tx < ncol) M[(size_t)(a0 + ty) * ncol + b0 + tx] = s;
+}
+void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nrows, double* M, hipStream_t s) {
+  const int nb = (ncol + 15) / 16;
+  if (ncol > 0) hipLaunchKernelGGL(k_gram, dim3(nb, nb), dim3(256), 0, s, X, ldx, ncol, rows, nrows, M);
+}
+
+// V_l = sum_{f in factors(l)} U_{p_f} F_f for the landmarks lids[q]: V[a ldv + 9 q + c] (6m x d, c < 9, zero for c >= d).
+// U: ncol columns of nT rows.  One workgroup per landmark, threads over the columns a.
+__global__ __launch_bounds__(256) void k_lm_V(GraphDev G, const double* __restrict__ U, int nT, int ncol, const int* __restrict__ lids,
+                                              int n, double* __restrict__ V, size_t ldv) {
+  const int q = blockIdx.x;
+  if (q >= n) return;
+  const int l = lids[q];
+  const int D = lm_dim(G.lm_type[l]);
+  const int f0 = G.lm_ptr[l], f1 = G.lm_ptr[l + 1];
+  for (int a = threadIdx.x; a < ncol; a += 256) {
+    double v[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) v[c] = 0.0;
+    for (int qf = f0; qf < f1; ++qf) {
+      const int f = G.lm_fids[qf];
+      const double* u = U + (size_t)a * nT + 6 * (size_t)G.lf_pose[f];
+      const double* F = G.ebuf + G.lf_eoff[f] + 6 * D;
+#pragma unroll
+      for (int b = 0; b < 6; ++b) {
+        const double ub = u[b];
+#pragma unroll
+        for (int c = 0; c < 9; ++c)
+          if (c < D) v[c] += ub * F[b * D + c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) V[(size_t)a * ldv + 9 * (size_t)q + c] = v[c];
+  }
+}
+void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_lm_V, dim3(n), dim3(256), 0, s, G, U, nT, ncol, lids, n, V, ldv);
+}
+
+// scatter (row, col, value) entries into a column-major matrix of nT rows (the whitened Jacobian rows of the candidate closure)
+__global__ void k_jt_scatter(const int* __restrict__ rc, const double* __restrict__ val, int n, double* __restrict__ B, int nT) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) B[(size_t)rc[2 * e + 1] * nT + rc[2 * e]] = val[e];
+}
+void launch_scatter(const int* rc, const double* val, int n, double* B, int nT, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_jt_scatter, dim3((n + 255) / 256), dim3(256), 0, s, rc, val, n, B, nT);
+}
+
+}  // namespace sl

@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <unordered_map>
 
 namespace sl {
 
@@ -2600,6 +2602,8 @@ int HostGraph::run_update(double relin_thr, int iterations) {
     pred_valid = (try_inc || wf_full_path);
   }
   factor_valid = true;
+  ++fact_serial;
+  fact_shape_now(fact_shape);
   fact_gen = S_gen;
   lin_solved_gen = lin_gen;         // (every linearisation buffer holds this solve's state)
   dirty_min_pose = 1 << 30;
@@ -2991,6 +2995,291 @@ void HostGraph::set_dense_profile(bool on) {
   force_dense = on;
   topo_dirty = true;
 }
+// ---- marginals and loop-closure information gain (logEntropy / estimateClosureInfoGain, graph.cpp:421-625) -----------------------
+// Single-graph path only: a shard's factor (ghost factors, shared-landmark slots) or a factor shared with a CholBatch is not the
+// system of this graph alone.
+int HostGraph::marginal_state(const char* who) const {
+  if (batch || arrow_on() || up_gh > 0 || !h_gslot_pose.empty() || !h_sh_lid.empty()) {
+    g_last_error = std::string(who) + ": marginals are served on the single-graph path only (not in sharded or exact-joint mode)";
+    return SLIDE_ERR_INVALID;
+  }
+  if (!factor_valid || G.T == 0) { g_last_error = std::string(who) + ": no factorisation yet (call solve first)"; return SLIDE_ERR_INVALID; }
+  // factors or variables merged since the last solve (any call that uploads pending additions) change the system the device buffers
+  // describe — and may re-allocate S, Ld and Winv, or grow ld — while the resident factor is still the old one's
+  size_t now[8];
+  fact_shape_now(now);
+  if (fact_gen != S_gen || std::memcmp(now, fact_shape, sizeof(now)) != 0) {
+    g_last_error = std::string(who) + ": the graph changed since the last solve (call solve first)";
+    return SLIDE_ERR_INVALID;
+  }
+  return SLIDE_OK;
+}
+void HostGraph::fact_shape_now(size_t* out) const {
+  const size_t v[8] = {(size_t)G.T, (size_t)G.ld, up_P, up_L, up_pr, up_bt, up_lf, up_gh};
+  std::memcpy(out, v, sizeof(v));
+}
+// the selected inverse of the resident factor, computed once per factorisation
+// (marginal_state first: the factor is the one of the uploaded system, so G.T / G.ld are its geometry)
+int HostGraph::ensure_sigma() {
+  if (sig_serial == fact_serial && sig_T == G.T && sig_ld == G.ld) return SLIDE_OK;
+  hipStream_t s = stream;
+  const size_t n = (size_t)G.ld * G.T * NB;
+  sig_serial = ~0ull;
+  if (d_sig.cap != n && d_sig.ensure_exact(n, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  DevArr<double> Z;      // Z_I = L_Ik L_kk^-1 of the recursion: only while it runs (freed at the end of this scope, after a sync)
+  if (Z.ensure_exact(n, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  const bool dense = h_prof.size() != (size_t)G.T;
+  launch_selected_inverse(G.S, G.ld, G.T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), dense ? nullptr : G.prof, d_sig.d, Z.d, s);
+  SL_HIP(hipGetLastError());
+  SL_HIP(hipStreamSynchronize(s));
+  sig_serial = fact_serial;
+  sig_T = G.T;
+  sig_ld = G.ld;
+  return SLIDE_OK;
+}
+void HostGraph::robot_poses(int robot, std::vector<int>& out) const {
+  out.clear();
+  const uint64_t tag = pose_key(robot, 0) >> 56;
+  for (const auto& kv : key2pose)
+    if ((kv.first >> 56) == tag && (size_t)kv.second < up_P) out.push_back(kv.second);
+  std::sort(out.begin(), out.end());
+}
+void HostGraph::point_landmarks(std::vector<int>& out) const {
+  out.clear();
+  for (size_t l = 0; l < up_L && l < h_lm_type.size(); ++l)
+    if (h_lm_type[l] == VT_POINT) out.push_back((int)l);
+}
+// isam->marginalCovariance(X(idx)) for n poses of one robot: out36n[36 q ..] row-major, tangent order [rot, trans]
+int HostGraph::pose_covariances(int robot, const uint64_t* idx, int n, double* out36n) {
+  if (!robot_ok(robot) || n < 0 || (n > 0 && (!idx || !out36n))) return SLIDE_ERR_INVALID;
+  for (int i = 0; i < 36 * n; ++i) out36n[i] = 0.0;
+  int rc = marginal_state("get_pose_covariances");
+  if (rc != SLIDE_OK) return rc;
+  std::vector<int> ids(n);
+  for (int q = 0; q < n; ++q) {
+    auto it = key2pose.find(pose_key(robot, idx[q]));
+    if (it == key2pose.end() || (size_t)it->second >= up_P) return SLIDE_MISSING;
+    ids[q] = it->second;
+  }
+  if (n == 0) return SLIDE_OK;
+  if ((rc = ensure_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = stream;
+  if (d_midx.ensure(n, 0, s) != SLIDE_OK || d_mout.ensure(36 * (size_t)n, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  SL_HIP(hipMemcpyAsync(d_midx.d, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_pose_blocks(d_sig.d, G.ld, d_midx.d, n, d_mout.d, s);
+  SL_HIP(hipMemcpyAsync(out36n, d_mout.d, 36 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  return SLIDE_OK;
+}
+// isam->marginalCovariance(L / C / U(idx)) for n landmarks of one class: d x d each (d = 7 / 9 / 3), tangent order of var_retract
+int HostGraph::landmark_covariances(int cls, const uint64_t* idx, int n, double* out) {
+  if ((cls != SLIDE_CLS_CYLINDER && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_ELLIPSOID) || n < 0 || (n > 0 && (!idx || !out)))
+    return SLIDE_ERR_INVALID;
+  const int d = cls == SLIDE_CLS_CYLINDER ? 7 : (cls == SLIDE_CLS_CUBE ? 9 : 3);
+  for (int i = 0; i < d * d * n; ++i) out[i] = 0.0;
+  int rc = marginal_state("get_landmark_covariances");
+  if (rc != SLIDE_OK) return rc;
+  std::vector<int> ids(n);
+  for (int q = 0; q < n; ++q)
+    if ((ids[q] = lm_lid(cls, idx[q])) < 0) return SLIDE_MISSING;
+  if (n == 0) return SLIDE_OK;
+  if ((rc = ensure_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = stream;
+  if (d_midx.ensure(n, 0, s) != SLIDE_OK || d_mout.ensure(81 * (size_t)n, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  SL_HIP(hipMemcpyAsync(d_midx.d, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_landmark_covariances(G, d_sig.d, G.ld, d_midx.d, n, d_mout.d, s);
+  std::vector<double> h(81 * (size_t)n);
+  SL_HIP(hipMemcpyAsync(h.data(), d_mout.d, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  for (int q = 0; q < n; ++q)
+    for (int e = 0; e < d * d; ++e) out[(size_t)q * d * d + e] = h[81 * (size_t)q + e];
+  return SLIDE_OK;
+}
+// logEntropy (graph.cpp:423-466): {sum of the robot's pose marginal traces, sum of the point landmarks' traces, #poses, #landmarks}
+int HostGraph::marginal_traces(int robot, double* out4) {
+  for (int i = 0; i < 4; ++i) out4[i] = 0.0;
+  if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
+  int rc = marginal_state("marginal_traces");
+  if (rc != SLIDE_OK) return rc;
+  std::vector<int> poses, lms;
+  robot_poses(robot, poses);
+  point_landmarks(lms);
+  if ((rc = ensure_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = stream;
+  const size_t np = poses.size(), nl = lms.size();
+  if (d_midx.ensure(np + nl + 1, 0, s) != SLIDE_OK || d_mout.ensure(36 * np + 81 * nl + 1, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (np) SL_HIP(hipMemcpyAsync(d_midx.d, poses.data(), np * sizeof(int), hipMemcpyHostToDevice, s));
+  if (nl) SL_HIP(hipMemcpyAsync(d_midx.d + np, lms.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_pose_blocks(d_sig.d, G.ld, d_midx.d, (int)np, d_mout.d, s);
+  launch_landmark_covariances(G, d_sig.d, G.ld, d_midx.d + np, (int)nl, d_mout.d + 36 * np, s);
+  std::vector<double> h(36 * np + 81 * nl);
+  if (!h.empty()) SL_HIP(hipMemcpyAsync(h.data(), d_mout.d, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  for (size_t p = 0; p < np; ++p)
+    for (int a = 0; a < 6; ++a) out4[0] += h[36 * p + 7 * a];
+  for (size_t l = 0; l < nl; ++l)
+    for (int a = 0; a < 3; ++a) out4[1] += h[36 * np + 81 * l + 4 * a];
+  out4[2] = (double)np;
+  out4[3] = (double)nl;
+  return SLIDE_OK;
+}
+// estimateClosureInfoGain (graph.cpp:469-623) in the linear-Gaussian model of the resident factor.  Fake factor i is a Between factor
+// (c_{i+1}, c_i) measuring the relative pose of the linearisation values (residual 0), noise sigma_per_m * travel[i]; its whitened
+// Jacobian there is  -Ad(T_{c_i}^-1 T_{c_{i+1}}) / sigma  on c_{i+1} and  I / sigma  on c_i (both charts).  With J (6m x n) these rows,
+// U = Sigma J^T (substitutions with 6m right-hand sides on the factor), C = I + J U:
+//     Sigma - (H + J^T J)^-1 = U C^-1 U^T      (Woodbury)
+// so the trace drops are tr(C^-1 sum_p U_p U_p^T) over the robot's poses and tr(C^-1 sum_l V_l V_l^T) over the point landmarks,
+// V_l = sum_f U_{p_f} F_f (Sigma_lP = -sum_f F_f^T Sigma(p_f, :)).  total = 10 pose + landmark (graph.cpp:622).  iSAM2's update could
+// relinearise variables while the fake factors are in; this linear model does not.  The graph, its factor and Sigma are left untouched.
+int HostGraph::closure_info_gain(int robot, const uint64_t* traj, int n, const double* travel, const double* sigma6, double* out3) {
+  for (int i = 0; i < 3; ++i) out3[i] = 0.0;
+  if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
+  const int m = n - 1;
+  if (m < 1 || !traj || !travel) { g_last_error = "closure_info_gain: the trajectory needs at least two poses"; return SLIDE_ERR_INVALID; }
+  if (m > SLIDE_INFO_GAIN_MAX_STEPS) { g_last_error = "closure_info_gain: more than SLIDE_INFO_GAIN_MAX_STEPS steps"; return SLIDE_ERR_CAPACITY; }
+  for (int i = 0; i < m; ++i)
+    if (!(travel[i] > 0.0) || !std::isfinite(travel[i])) { g_last_error = "closure_info_gain: travel distances must be > 0"; return SLIDE_ERR_INVALID; }
+  if (!sigma6) sigma6 = P.noise_model_odom_vec;      // (noise_model_pose_vec_per_m, graph.h:115, is never set in the reference)
+  for (int a = 0; a < 6; ++a)
+    if (!(sigma6[a] > 0.0) || !std::isfinite(sigma6[a])) { g_last_error = "closure_info_gain: sigma_per_m must be > 0"; return SLIDE_ERR_INVALID; }
+  int rc = marginal_state("closure_info_gain");
+  if (rc != SLIDE_OK) return rc;
+  std::vector<int> ids(n);
+  for (int q = 0; q < n; ++q) {
+    auto it = key2pose.find(pose_key(robot, traj[q]));
+    if (it == key2pose.end() || (size_t)it->second >= up_P) return SLIDE_MISSING;
+    ids[q] = it->second;
+  }
+  hipStream_t s = stream;
+  const int ncol = 6 * m, T = G.T, nT = T * NB;
+  // the linearisation values of the trajectory's poses
+  std::vector<double> val(12 * (size_t)n);
+  for (int q = 0; q < n; ++q)
+    SL_HIP(hipMemcpyAsync(val.data() + 12 * q, G.pose_val + 12 * (size_t)ids[q], 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  // J^T, entry by entry (row of the reduced system, column 6 i + a); a repeated pose sums its blocks
+  std::map<std::pair<int, int>, double> jt;
+  for (int i = 0; i < m; ++i) {
+    const double* Ta = val.data() + 12 * (i + 1);      // c_{i+1}
+    const double* Tb = val.data() + 12 * i;            // c_i
+    double R[9], t[3], dt[3] = {Ta[9] - Tb[9], Ta[10] - Tb[10], Ta[11] - Tb[11]};
+    for (int r = 0; r < 3; ++r) {                      // T_b^-1 T_a = (Rb^T Ra, Rb^T (ta - tb))
+      for (int c = 0; c < 3; ++c) R[3 * r + c] = Tb[r] * Ta[c] + Tb[3 + r] * Ta[3 + c] + Tb[6 + r] * Ta[6 + c];
+      t[r] = Tb[r] * dt[0] + Tb[3 + r] * dt[1] + Tb[6 + r] * dt[2];
+    }
+    double Ad[6][6] = {};                              // [R 0; t^ R  R]
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        Ad[r][c] = R[3 * r + c];
+        Ad[3 + r][3 + c] = R[3 * r + c];
+      }
+    const double tx[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) Ad[3 + r][c] = tx[3 * r] * R[c] + tx[3 * r + 1] * R[3 + c] + tx[3 * r + 2] * R[6 + c];
+    for (int a = 0; a < 6; ++a) {
+      const double w = 1.0 / (sigma6[a] * travel[i]);
+      for (int c = 0; c < 6; ++c) jt[{6 * ids[i + 1] + c, 6 * i + a}] += -Ad[a][c] * w;
+      jt[{6 * ids[i] + a, 6 * i + a}] += w;
+    }
+  }
+  std::vector<int> rcv;
+  std::vector<double> vv;
+  for (const auto& kv : jt) { rcv.push_back(kv.first.first); rcv.push_back(kv.first.second); vv.push_back(kv.second); }
+  const int ne = (int)vv.size();
+  std::vector<int> poses, lms;
+  robot_poses(robot, poses);
+  point_landmarks(lms);
+  std::vector<int> prow;
+  for (int p : poses)
+    for (int a = 0; a < 6; ++a) prow.push_back(6 * p + a);
+  const size_t nl = lms.size(), ldv = std::max<size_t>(9 * nl, 1);
+  if (d_igB.ensure((size_t)ncol * nT, 0, s) != SLIDE_OK || d_igU.ensure((size_t)ncol * nT, 0, s) != SLIDE_OK ||
+      d_igV.ensure((size_t)ncol * ldv, 0, s) != SLIDE_OK || d_igM.ensure(2 * (size_t)ncol * ncol, 0, s) != SLIDE_OK ||
+      d_igrc.ensure(2 * (size_t)ne + prow.size() + nl + 1, 0, s) != SLIDE_OK || d_igval.ensure(ne, 0, s) != SLIDE_OK)
+    return SLIDE_ERR_HIP;
+  int* d_rows = d_igrc.d + 2 * ne;
+  int* d_lms = d_rows + prow.size();
+  SL_HIP(hipMemsetAsync(d_igB.d, 0, (size_t)ncol * nT * sizeof(double), s));
+  SL_HIP(hipMemcpyAsync(d_igrc.d, rcv.data(), rcv.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  SL_HIP(hipMemcpyAsync(d_igval.d, vv.data(), ne * sizeof(double), hipMemcpyHostToDevice, s));
+  if (!prow.empty()) SL_HIP(hipMemcpyAsync(d_rows, prow.data(), prow.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  if (nl) SL_HIP(hipMemcpyAsync(d_lms, lms.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_scatter(d_igrc.d, d_igval.d, ne, d_igB.d, nT, s);
+  const bool dense = h_prof.size() != (size_t)T;
+  launch_multi_solve(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), d_igB.d, d_igU.d, ncol, s);
+  double* Mp = d_igM.d;
+  double* Ml = d_igM.d + (size_t)ncol * ncol;
+  launch_gram(d_igU.d, nT, ncol, d_rows, (int)prow.size(), Mp, s);
+  SL_HIP(hipMemsetAsync(Ml, 0, (size_t)ncol * ncol * sizeof(double), s));
+  if (nl) {
+    launch_landmark_V(G, d_igU.d, nT, ncol, d_lms, (int)nl, d_igV.d, ldv, s);
+    launch_gram(d_igV.d, ldv, ncol, nullptr, (int)(9 * nl), Ml, s);
+  }
+  // the rows of U at the trajectory's poses (for C = I + J U)
+  std::vector<double> M(2 * (size_t)ncol * ncol), Urow((size_t)n * 6 * ncol);
+  SL_HIP(hipMemcpyAsync(M.data(), d_igM.d, M.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  for (int q = 0; q < n; ++q)
+    SL_HIP(hipMemcpy2DAsync(Urow.data() + (size_t)q * 6 * ncol, 6 * sizeof(double), d_igU.d + 6 * (size_t)ids[q], (size_t)nT * sizeof(double),
+                            6 * sizeof(double), ncol, hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  std::unordered_map<int, int> row_of;      // reduced-system pose row block -> trajectory slot
+  for (int q = 0; q < n; ++q) row_of.emplace(ids[q], q);
+  std::vector<double> Cm((size_t)ncol * ncol, 0.0);
+  for (int a = 0; a < ncol; ++a) Cm[(size_t)a * ncol + a] = 1.0;
+  for (size_t e = 0; e < vv.size(); ++e) {          // (J U)[jrow][col] += J[jrow][row] U[row][col]
+    const int row = rcv[2 * e], jrow = rcv[2 * e + 1];
+    const double* u = Urow.data() + (size_t)row_of[row / 6] * 6 * ncol + row % 6;
+    for (int c = 0; c < ncol; ++c) Cm[(size_t)jrow * ncol + c] += vv[e] * u[6 * (size_t)c];
+  }
+  // C^-1 by Cholesky (C = I + J Sigma J^T is SPD); the gains are sum_ab (C^-1)_ab M_ab of the symmetrised matrices
+  for (int a = 0; a < ncol; ++a)
+    for (int b = 0; b < a; ++b) Cm[(size_t)a * ncol + b] = Cm[(size_t)b * ncol + a] = 0.5 * (Cm[(size_t)a * ncol + b] + Cm[(size_t)b * ncol + a]);
+  std::vector<double> Lc((size_t)ncol * ncol, 0.0);
+  for (int j = 0; j < ncol; ++j) {
+    double d = Cm[(size_t)j * ncol + j];
+    for (int k = 0; k < j; ++k) d -= Lc[(size_t)j * ncol + k] * Lc[(size_t)j * ncol + k];
+    if (!(d > 0.0)) { g_last_error = "closure_info_gain: I + J Sigma J^T is not positive definite"; return SLIDE_ERR_NOT_SPD; }
+    const double ljj = std::sqrt(d);
+    Lc[(size_t)j * ncol + j] = ljj;
+    for (int i = j + 1; i < ncol; ++i) {
+      double v = Cm[(size_t)i * ncol + j];
+      for (int k = 0; k < j; ++k) v -= Lc[(size_t)i * ncol + k] * Lc[(size_t)j * ncol + k];
+      Lc[(size_t)i * ncol + j] = v / ljj;
+    }
+  }
+  // (on the host: O((6m)^3), about 10^8 flops at the cap m = 64 — the largest part of such a query; a device version is a follow-up)
+  std::vector<double> LcT((size_t)ncol * ncol), Ci((size_t)ncol * ncol, 0.0), col(ncol);
+  for (int i = 0; i < ncol; ++i)
+    for (int k = 0; k < ncol; ++k) LcT[(size_t)i * ncol + k] = Lc[(size_t)k * ncol + i];
+  for (int j = 0; j < ncol; ++j) {                   // column j of C^-1: L L^T x = e_j (L^-1 e_j is zero above row j)
+    for (int i = 0; i < j; ++i) col[i] = 0.0;
+    for (int i = j; i < ncol; ++i) {
+      double v = i == j ? 1.0 : 0.0;
+      for (int k = j; k < i; ++k) v -= Lc[(size_t)i * ncol + k] * col[k];
+      col[i] = v / Lc[(size_t)i * ncol + i];
+    }
+    for (int i = ncol - 1; i >= 0; --i) {
+      double v = col[i];
+      for (int k = i + 1; k < ncol; ++k) v -= LcT[(size_t)i * ncol + k] * col[k];
+      col[i] = v / Lc[(size_t)i * ncol + i];
+    }
+    for (int i = 0; i < ncol; ++i) Ci[(size_t)i * ncol + j] = col[i];
+  }
+  double gp = 0.0, gl = 0.0;
+  for (size_t e = 0; e < (size_t)ncol * ncol; ++e) {
+    gp += Ci[e] * M[e];
+    gl += Ci[e] * M[(size_t)ncol * ncol + e];
+  }
+  out3[0] = 10.0 * gp + gl;
+  out3[1] = gp;
+  out3[2] = gl;
+  return SLIDE_OK;
+}
+
 int HostGraph::pcg_stats(double* out8) {
   for (int i = 0; i < 8; ++i) out8[i] = 0.0;
   if (!d_pcg_scal.d) return SLIDE_OK;

@@ -314,6 +314,11 @@ class HostGraph {
   int add_relative_meas_ghost(const double* rel7, uint64_t idx, int robot, int slot, bool local_first);
   int set_ghosts(const int32_t* own_robot, const int64_t* own_idx, int n_slots);
   int pose_covariance(int robot, uint64_t idx, double* cov36);
+  // marginals on the selected inverse of the resident factor, loop-closure information gain (cov_kernels.hip; single-graph path only)
+  int pose_covariances(int robot, const uint64_t* idx, int n, double* out36n);
+  int landmark_covariances(int cls, const uint64_t* idx, int n, double* out);
+  int marginal_traces(int robot, double* out4);
+  int closure_info_gain(int robot, const uint64_t* traj, int n, const double* travel, const double* sigma6, double* out3);
   void join_batch(CholBatch* b, int slot);      // takes the graph's lock itself (never while the batch's is held the other way round)
   int dist_pass_local(double* d_buf);     // one distributed pass when every robot of the job is in this graph's batch (no host syncs inside)
   int add_point_landmark(uint64_t idx, const double* xyz);
@@ -489,6 +494,19 @@ class HostGraph {
   DevArr<int> d_cctr;
   DevArr<double> d_covY;
   bool factor_valid = false;            // S / Ld / Winv hold the factor of the system of the last solve
+  unsigned long long fact_serial = 0;   // +1 whenever a solve leaves a new factorisation
+  size_t fact_shape[8] = {};            // what that factorisation was of: T, ld, the uploaded counts (marginal_state compares)
+  void fact_shape_now(size_t* out) const;
+  unsigned long long sig_serial = ~0ull;     // the factorisation d_sig is the selected inverse of ...
+  int sig_T = -1, sig_ld = -1;               // ... and its geometry
+  DevArr<double> d_sig;                 // Sigma = S^-1 on the tile profile (S's layout and ld)
+  DevArr<double> d_mout, d_igB, d_igU, d_igV, d_igM;
+  DevArr<int> d_midx, d_igrc;
+  DevArr<double> d_igval;
+  int marginal_state(const char* who) const;      // SLIDE_ERR_INVALID (+ message) unless a single-graph factorisation is resident
+  int ensure_sigma();
+  void robot_poses(int robot, std::vector<int>& out) const;
+  void point_landmarks(std::vector<int>& out) const;
   DevArr<int> d_status;
   UploadBatch ub;
   CholBatch* batch = nullptr;           // shared factor + solve with the other graphs of this GPU (not owned)

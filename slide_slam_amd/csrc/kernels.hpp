@@ -108,6 +108,17 @@ void launch_chol_bwd_all(const double* S, int ld, int T, const double* Ld, const
 // marginal covariance of the pose whose first tangent row is row0 (Y: 6 * T * NB scratch doubles holding the six unit columns)
 void launch_pose_covariance(const double* S, int ld, int T, const double* Ld, const double* Winv, double* Y, int row0, double* cov36,
                             hipStream_t s);
+// cov_kernels.hip — selected inverse Sigma = S^-1 on the tile profile (prof: host copy, null = dense; d_prof its device copy) into Sg,
+// with Z (S's size) as scratch; marginal blocks out of it; many right-hand sides on the factor; the information-gain products
+void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
+                             double* Sg, double* Z, hipStream_t s);
+void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s);                 // out: 36 per pose
+void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s);   // out: 81 per landmark (d x d used)
+void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* X,
+                        int nrhs, hipStream_t s);      // X = S^-1 B (B: nrhs columns of T * NB rows, overwritten)
+void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nrows, double* M, hipStream_t s);
+void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s);
+void launch_scatter(const int* rc, const double* val, int n, double* B, int nT, hipStream_t s);
 // stand-alone dense SPD solve on device buffers (used by the unit tests and the roofline bench leg)
 void launch_chol_solve_bwd(const CholSystem& cs, hipStream_t s);   // yv -> dp after launch_chol_extract_y: one-workgroup substitution for narrow profiles, else the chained kernel
 int chol_factor_solve(double* S, int ld, int T, double* Ld, double* Winv, double* yv, double* dp, int* status, int* ctr, hipStream_t s);
