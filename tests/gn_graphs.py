@@ -28,11 +28,11 @@ def p7(R, t, qscale=1.0, log=None):
 
 
 class World:
-    """Ground-truth poses (R, t) of robot 0 and the calls that put a graph on them."""
+    """Ground-truth poses (R, t) of one robot (`robot`, default 0) and the calls that put a graph on them."""
 
     def __init__(self, G, P, seed=0, full3d=True, step=1.0, origin=(1.0, 2.0, 0.5), noise=0.02, qscale=1.0, rel_rots=None,
-                 r0=(0.1, -0.2, 0.3), perturb=None, rperturb=None):
-        self.G, self.rng = G, np.random.default_rng(seed)
+                 r0=(0.1, -0.2, 0.3), perturb=None, rperturb=None, robot=0):
+        self.G, self.rng, self.robot = G, np.random.default_rng(seed), robot
         self.noise, self.qscale = noise, qscale
         self.quats = []          # every quaternion this world passes at the ABI (as passed)
         R = rot(r0 if full3d else [0, 0, 0.3])
@@ -47,7 +47,7 @@ class World:
             R, t = R @ dR, t + R @ dt
             self.T.append((R, t))
         self.est = []
-        G.set_prior(0, p7(*self.T[0], qscale, self.quats))
+        G.set_prior(robot, p7(*self.T[0], qscale, self.quats))
         self.est.append(p7(*self.T[0], qscale))
         for k in range(1, P):
             (Ra, ta), (Rb, tb) = self.T[k - 1], self.T[k]
@@ -55,7 +55,7 @@ class World:
             Re = Rb @ rot(self.rng.normal(0, noise, 3)) @ rot((rperturb or {}).get(k, np.zeros(3)))
             te = tb + self.rng.normal(0, noise * 5, 3) + np.asarray((perturb or {}).get(k, 0.0))
             e = p7(Re, te, qscale, self.quats)
-            G.add_keypose_between(0, k - 1, k, rel, e)
+            G.add_keypose_between(robot, k - 1, k, rel, e)
             self.est.append(e)
 
     def point(self, idx, xyz, observers):
@@ -64,18 +64,18 @@ class World:
         for k in observers:
             R, t = self.T[k]
             q = R.T @ (xyz - t)
-            self.G.add_range_bearing(0, k, idx, q / np.linalg.norm(q), float(np.linalg.norm(q)))
+            self.G.add_range_bearing(self.robot, k, idx, q / np.linalg.norm(q), float(np.linalg.norm(q)))
 
     def cylinder(self, idx, root, ray, radius, observers):
         root, ray = np.asarray(root, float), np.asarray(ray, float)
         for n, k in enumerate(observers):
             rt = root + (self.rng.normal(0, self.noise, 3) if n == 0 else 0.0)
-            self.G.add_cylinder(0, k, idx, self.est[k], rt, ray, radius, n > 0)
+            self.G.add_cylinder(self.robot, k, idx, self.est[k], rt, ray, radius, n > 0)
 
     def cube(self, idx, R, t, scale, observers):
         for n, k in enumerate(observers):
             c7 = p7(R, np.asarray(t, float) + (self.rng.normal(0, self.noise, 3) if n == 0 else 0.0), self.qscale, self.quats)
-            self.G.add_cube(0, k, idx, self.est[k], c7, np.asarray(scale, float) + (0.01 if n == 0 else 0.0), n > 0)
+            self.G.add_cube(self.robot, k, idx, self.est[k], c7, np.asarray(scale, float) + (0.01 if n == 0 else 0.0), n > 0)
 
 
 def around(W, k, rng, r=6.0):
