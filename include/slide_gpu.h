@@ -179,6 +179,22 @@ int slide_graph_dist_pass_local(slide_graph_t* g, double* d_buf);
  * the batch's stream around the exchanges and the batched factor + solve, captured once and replayed as one hipGraph per pass.
  * d_bufs[i] = exchange buffer (device) of the graph in slot i. */
 int slide_chol_batch_pass(slide_chol_batch_t* b, double* const* d_bufs);
+/* Marginal covariances on the JOINT multi-robot graph (exact joint passes, slide_chol_batch_set_exact_joint): what a sloam_node's full
+ * replica of the multi-robot graph answers (graph.cpp:325-371), from the factor the last slide_chol_batch_pass left — the selected
+ * inverse over its elimination tree (segments, windows, separator leaves and top block, lambda block), computed once per pass and
+ * cached.  Shared landmarks and inter-robot factors shrink these, unlike the single-graph getters (which keep refusing on a joined graph).
+ * SLIDE_ERR_INVALID (+ slide_last_error) before the first whole exact pass, once any joined graph changed after it (pending or merged
+ * factors / variables, a re-join), in PCG or block-Jacobi mode, and on a rank that owns one separator leaf (a job spread over GPUs);
+ * SLIDE_MISSING for an unknown index.  The queries run on the batch's stream outside any capture and write nothing a pass reads.
+ * getPoseCovariance(idx, robotID) (graph.cpp:314-323) / getCurrPose(.., cov) (graphWrapper.cpp:277-297) for n poses of the robot whose
+ * graph is in `slot`, by its pose indices: out36n[36 q ..], 6x6 row-major, tangent order [rot, trans]. */
+int slide_chol_batch_get_pose_covariances(slide_chol_batch_t* b, int slot, const uint64_t* idx, int n, double* out36n);
+/* isam->marginalCovariance(L / C / U(idx[q])) (graph.cpp:444) on the joint graph for n landmarks of the graph in `slot`, by that graph's
+ * landmark ids: d x d row-major each, d = 7 / 9 / 3 for cylinder / cube / point; a shared landmark reads the same numbers from every slot. */
+int slide_chol_batch_get_landmark_covariances(slide_chol_batch_t* b, int slot, int cls, const uint64_t* idx, int n, double* out);
+/* logEntropy (graph.cpp:423-466) on the joint graph: out4 = {sum of the traces of the pose marginals of the robot in `slot`, sum over the
+ * job's point landmarks (every graph's private ones, each shared one once), #poses, #point landmarks}. */
+int slide_chol_batch_marginal_traces(slide_chol_batch_t* b, int slot, double out4[4]);
 /* The same pass for a job that spans GPUs, cut at its two exchanges (8 / N robots on each of N GPUs): every part is a captured
  * hipGraph replayed on the batch's stream.
  *   part 0: phase 0 of every robot + the local sum -> every local buffer holds this GPU's sum of the 54-doubles-per-slot blocks;

@@ -28,7 +28,7 @@ EXPORTS = [
     "slide_graph_add_loop_closure", "slide_graph_add_relative_meas", "slide_graph_add_point_landmark",
     "slide_graph_add_range_bearing", "slide_graph_add_cube", "slide_graph_add_cylinder", "slide_graph_solve",
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
-    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
+    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
     "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
@@ -446,6 +446,34 @@ class CholBatch:
         """One distributed pass of all joined graphs from this thread; buf_ptrs[i] = device address of slot i's exchange buffer."""
         arr = (C.c_void_p * len(buf_ptrs))(*[int(p) for p in buf_ptrs])
         return _check(self.L.slide_chol_batch_pass(C.c_void_p(self.h), arr))
+
+    def get_pose_covariances(self, slot, idx):
+        """Marginal covariances on the JOINT graph (exact joint passes; slide_gpu.h) of the poses `idx` of the robot whose graph is in
+        `slot`: (n, 6, 6), tangent order [rot, trans].  KeyError for an unknown pose."""
+        ids = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros(36 * len(ids))
+        st = self.L.slide_chol_batch_get_pose_covariances(C.c_void_p(self.h), C.c_int(slot), _p(ids), C.c_int(len(ids)), _p(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"pose of slot {slot} not in the graph")
+        _check(st)
+        return out.reshape(-1, 6, 6)
+
+    def get_landmark_covariances(self, slot, cls, idx):
+        """Joint-graph marginal covariances of the landmarks `idx` (that graph's ids) of class `cls` of the graph in `slot`: (n, d, d)."""
+        d = {CLS_CYLINDER: 7, CLS_CUBE: 9}.get(cls, 3)
+        ids = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros(d * d * len(ids))
+        st = self.L.slide_chol_batch_get_landmark_covariances(C.c_void_p(self.h), C.c_int(slot), C.c_int(cls), _p(ids), C.c_int(len(ids)), _p(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"landmark of class {cls} not in slot {slot}")
+        _check(st)
+        return out.reshape(-1, d, d)
+
+    def marginal_traces(self, slot):
+        """logEntropy on the joint graph: [pose trace sum of the robot in `slot`, the job's point-landmark trace sum, #poses, #points]."""
+        out = np.zeros(4)
+        _check(self.L.slide_chol_batch_marginal_traces(C.c_void_p(self.h), C.c_int(slot), _p(out)))
+        return out
 
     def set_pcg(self, iterations, tol=0.0):
         """PCG iterations of the joint solve after the factorisations (0 = every robot's own block solve only); tol > 0: iterations

@@ -24,6 +24,7 @@ SOURCES = [
     ("chol_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("pcg_kernels.hip", []),
     ("cov_kernels.hip", []),
+    ("joint_cov_kernels.hip", []),
     ("assoc_kernels.hip", ["-ffp-contract=off"]),
     ("place_kernels.hip", ["-ffp-contract=off"]),
     ("clipper_kernels.hip", ["-ffp-contract=off"]),

@@ -186,23 +186,25 @@ void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, c
   }
 }
 
-// 6x6 diagonal blocks of the poses rows[p] (pose indices) out of the selected inverse: out[36 p + 6 a + b]
-__global__ void k_pose_blocks(const double* __restrict__ Sg, int ld, const int* __restrict__ poses, int n, double* __restrict__ out) {
+// 6x6 diagonal blocks of the poses rows[p] (pose indices) out of the selected inverse: out[36 p + 6 a + b].  prow: first row of a pose's
+// coordinates in Sg (null: 6 p; joint_cov_kernels.hip: a cut's poses live in the border rows)
+__global__ void k_pose_blocks(const double* __restrict__ Sg, int ld, const int* __restrict__ poses, int n, double* __restrict__ out,
+                              const int* __restrict__ prow) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= 36 * n) return;
   const int p = e / 36, a = (e % 36) / 6, b = e % 6;
-  const int r0 = 6 * poses[p];
+  const int r0 = prow ? prow[poses[p]] : 6 * poses[p];
   out[e] = sig_at(Sg, ld, r0 + a, r0 + b);
 }
-void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_pose_blocks, dim3((36 * n + 255) / 256), dim3(256), 0, s, Sg, ld, poses, n, out);
+void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s, const int* prow) {
+  if (n > 0) hipLaunchKernelGGL(k_pose_blocks, dim3((36 * n + 255) / 256), dim3(256), 0, s, Sg, ld, poses, n, out, prow);
 }
 
 // Landmark marginal (Schur identity): Sigma_ll = H_ll^-1 + sum_{f, g in factors(l)} F_f^T Sigma(p_f, p_g) F_g, F = E H_ll^-1 (ebuf).
 // One wavefront per landmark lids[q]; out[81 q ..] = the d x d block, row-major.  Per factor f: Q_f = sum_g Sigma(p_f, p_g) F_g
 // (6 x d, lane a d + c), then every lane adds its entries of F_f^T Q_f.
 __global__ __launch_bounds__(64) void k_lm_cov(GraphDev G, const double* __restrict__ Sg, int ld, const int* __restrict__ lids, int n,
-                                               double* __restrict__ out) {
+                                               double* __restrict__ out, const int* __restrict__ prow) {
   const int q = blockIdx.x, lane = threadIdx.x;
   if (q >= n) return;
   __shared__ double Qs[54];
@@ -213,12 +215,12 @@ __global__ __launch_bounds__(64) void k_lm_cov(GraphDev G, const double* __restr
   const int a = lane / D, c = lane - (lane / D) * D;
   for (int qf = 0; qf < nf; ++qf) {
     const int f = G.lm_fids[f0 + qf];
-    const int rf = 6 * G.lf_pose[f];
+    const int rf = prow ? prow[G.lf_pose[f]] : 6 * G.lf_pose[f];
     if (lane < 6 * D) {
       double s = 0.0;
       for (int qg = 0; qg < nf; ++qg) {
         const int g = G.lm_fids[f0 + qg];
-        const int rg = 6 * G.lf_pose[g];
+        const int rg = prow ? prow[G.lf_pose[g]] : 6 * G.lf_pose[g];
         const double* Fg = G.ebuf + G.lf_eoff[g] + 6 * D;
 #pragma unroll
         for (int b = 0; b < 6; ++b) s += sig_at(Sg, ld, rf + a, rg + b) * Fg[b * D + c];
@@ -247,8 +249,9 @@ __global__ __launch_bounds__(64) void k_lm_cov(GraphDev G, const double* __restr
     if (e < D * D) out[81 * (size_t)q + e] = Hi[e] + acc[h];
   }
 }
-void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_lm_cov, dim3(n), dim3(64), 0, s, G, Sg, ld, lids, n, out);
+void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s,
+                                 const int* prow) {
+  if (n > 0) hipLaunchKernelGGL(k_lm_cov, dim3(n), dim3(64), 0, s, G, Sg, ld, lids, n, out, prow);
 }
 
 // ---- many right-hand sides: U = S^-1 B (B: nrhs columns of nT = T * NB rows, column-major) --------------------------------------------

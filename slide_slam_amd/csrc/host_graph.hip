@@ -479,6 +479,7 @@ CholBatch::~CholBatch() {
   if (ev_out) (void)hipEventDestroy(ev_out);
   if (ev_fork) (void)hipEventDestroy(ev_fork);
   if (pass_exec) (void)hipGraphExecDestroy(pass_exec);
+  free_joint_sigma();
   free_separator();
   free_ll_band_plans();
   if (d_ctr2) (void)hipFree(d_ctr2);
@@ -839,6 +840,7 @@ void CholBatch::free_separator() {
 }
 void CholBatch::set_segments(int n) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;      // (a changed configuration: the joint marginals wait for the next pass)
   std::vector<HostGraph*> gs;
   {
     std::lock_guard<std::mutex> lk(mtx);
@@ -851,6 +853,7 @@ void CholBatch::set_segments(int n) {
 }
 int CholBatch::set_separator_profile(const int32_t* prof, int n) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;      // (a changed configuration: the joint marginals wait for the next pass)
   std::lock_guard<std::mutex> lk(mtx);
   for (int c = 0; c < n; ++c)
     if (prof[c] < c || prof[c] >= n || (c && prof[c] < prof[c - 1])) { g_last_error = "separator profile: prof[c] must be monotone with c <= prof[c] < n"; return SLIDE_ERR_INVALID; }
@@ -860,6 +863,7 @@ int CholBatch::set_separator_profile(const int32_t* prof, int n) {
 }
 int CholBatch::set_separator_blocks(int Ta, int Tb, int used_a, int used_b) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;      // (a changed configuration: the joint marginals wait for the next pass)
   std::lock_guard<std::mutex> lk(mtx);
   if (Ta < 0 || Tb < 0 || (Ta > 0) != (Tb > 0) || used_a < 0 || used_b < 0 || used_a > Ta * NB || used_b > Tb * NB || (Ta > 0 && (used_a <= (Ta - 1) * NB || used_b <= (Tb - 1) * NB))) {
     g_last_error = "separator blocks: two leaf blocks of Ta, Tb > 0 tile columns whose last tiles hold at least one used coordinate (or 0, 0: not dissected)";
@@ -871,6 +875,7 @@ int CholBatch::set_separator_blocks(int Ta, int Tb, int used_a, int used_b) {
 }
 int CholBatch::set_separator_owner(int leaf, bool leader) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;      // (a changed configuration: the joint marginals wait for the next pass)
   std::lock_guard<std::mutex> lk(mtx);
   if (leaf < -1 || leaf > 1) { g_last_error = "separator owner: leaf 0, 1 or -1 (none)"; return SLIDE_ERR_INVALID; }
   sep_owner = leaf; sep_leader = leader;
@@ -889,6 +894,7 @@ void CholBatch::sep_segment(int ms, int lam, int Ta, int Tb, int which, long lon
 }
 int CholBatch::set_arrow(bool on, double* sep_buf, long long len) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;      // (a changed configuration: the joint marginals wait for the next pass)
   std::vector<HostGraph*> gs;
   {
     std::lock_guard<std::mutex> lk(mtx);
@@ -1327,6 +1333,7 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
 // solve, the back-substitutions}, *n_sep_steps = block columns of the separator system
 int CholBatch::profile_arrow(double* const* d_bufs, double* out6, int* n_sep_steps) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;
   bool same = false;
   int rc = begin_pass(d_bufs, &same);
   if (rc != SLIDE_OK) return rc;
@@ -1458,6 +1465,7 @@ int CholBatch::capture_pass(double* const* d_bufs, int part, hipGraphExec_t* exe
 // time and launch count (the bench's roofline of k_chol_step_batched).
 int CholBatch::profile_pass(double* const* d_bufs, double* ms_steps, int* n_launches) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;
   {
     std::lock_guard<std::mutex> lk(mtx);
     for (int i = 0; i < n; ++i)
@@ -1607,6 +1615,7 @@ int CholBatch::factor_all(hipEvent_t after) {
 
 void CholBatch::set_pcg(int iters, double tol) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;      // (a changed configuration: the joint marginals wait for the next pass)
   std::vector<HostGraph*> gs;
   {
     std::lock_guard<std::mutex> lk(mtx);
@@ -1674,19 +1683,33 @@ hipStream_t CholBatch::pass_stream() {
 
 int CholBatch::pass_all(double* const* d_bufs) {
   std::lock_guard<std::mutex> pl(pass_mtx);
+  exact_serial = 0;
   bool same = false;
   int rc = begin_pass(d_bufs, &same);
   if (rc != SLIDE_OK) return rc;
   if (!pass_exec && (rc = capture_pass(d_bufs, -1, &pass_exec)) != SLIDE_OK) return rc;
   SL_HIP(hipGraphLaunch(pass_exec, master));
   last_part = -1;
-  return end_pass();
+  rc = end_pass();
+  if (rc == SLIDE_OK && arrow && pcg_iters == 0 && n > 0 && hG[0].n_slots > 0) {
+    // (the joint marginals read this pass's factor: what each graph's uploaded system was when it ran)
+    exact_shape.assign(n, std::vector<size_t>(10));
+    for (int i = 0; i < n; ++i) {
+      HostGraph* g = graphs[i];
+      std::lock_guard<std::mutex> gl(g->mtx);
+      g->fact_shape_now(exact_shape[i].data());
+      exact_shape[i][8] = (size_t)g->fact_serial; exact_shape[i][9] = (size_t)g->S_gen;
+    }
+    exact_serial = ++n_exact;
+  }
+  return rc;
 }
 
 // The pass in three stream-ordered parts for a job that spans GPUs (see enqueue_pass): parts 0 and 1 return without a host
 // synchronisation — the caller's collective goes onto stream() behind them — part 2 ends with the one synchronisation of the pass.
 int CholBatch::pass_part(double* const* d_bufs, int part) {
   thread_capture_mode_local();
+  { std::lock_guard<std::mutex> pl(pass_mtx); exact_serial = 0; }      // (the joint marginals are served after whole passes only)
   const int slot = part >= 0 && part <= 2 ? part : (part >= 10 && part <= 12 ? part - 7 : (part == 20 ? 6 : -1));
   if (slot < 0) return SLIDE_ERR_INVALID;
   std::lock_guard<std::mutex> pl(pass_mtx);
@@ -3285,6 +3308,365 @@ int HostGraph::pcg_stats(double* out8) {
   if (!d_pcg_scal.d) return SLIDE_OK;
   SL_HIP(hipMemcpyAsync(out8, d_pcg_scal.d, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));
   SL_HIP(hipStreamSynchronize(stream));
+  return SLIDE_OK;
+}
+
+// ---- marginals on the joint graph: the selected inverse over the exact joint pass's factor (joint_cov_kernels.hip) -------
+// What the pass leaves behind and this reads (nothing of it is scratch of the pass): every robot's band factor in S (segments' diagonal
+// blocks in Ld / Winv, their border rows W^T below the band), the windows' second-level factor in bord (Ld2 / Winv2), the separator's
+// leaves and top block in sepS (sep_Ld / sep_Winv; the top block holds the factor of the per-half sums after the canonical pass), its lambda
+// rows below them, and the lambda block's negative factored in lamS (lam_Ld / lam_Winv).  The queries write none of it.
+void CholBatch::free_joint_sigma() {
+  if (jsig_sep) (void)hipFree(jsig_sep);
+  jsig_sep = nullptr;
+  for (double* p : jsig_rob) if (p) (void)hipFree(p);
+  for (int* p : jsig_prow) if (p) (void)hipFree(p);
+  jsig_rob.clear(); jsig_prow.clear(); jsig_lds.clear();
+  jsig_serial = 0;
+}
+int CholBatch::joint_state(const char* who, int slot) {
+  const std::string w = std::string(who) + ": ";
+  if (slot < 0 || slot >= n) { g_last_error = w + "no such slot"; return SLIDE_ERR_INVALID; }
+  if (!arrow || pcg_iters > 0) { g_last_error = w + "the batch does not run exact joint passes (a PCG or block-Jacobi pass leaves no joint factor)"; return SLIDE_ERR_INVALID; }
+  if (sep_owner >= 0) { g_last_error = w + "this rank owns one leaf of the separator (a job spread over GPUs): it holds only that leaf's factor"; return SLIDE_ERR_INVALID; }
+  if (exact_serial == 0 || (int)exact_shape.size() != n) {
+    g_last_error = w + "no whole exact joint pass has run since the batch was configured (call pass_all first)";
+    return SLIDE_ERR_INVALID;
+  }
+  {
+    std::lock_guard<std::mutex> lk(mtx);
+    if (pass_dirty) { g_last_error = w + "the batch's graphs changed since the last pass"; return SLIDE_ERR_INVALID; }
+  }
+  for (int i = 0; i < n; ++i) {
+    HostGraph* g = graphs[i];
+    if (!g) { g_last_error = w + "a slot of the batch is empty"; return SLIDE_ERR_INVALID; }
+    std::lock_guard<std::mutex> gl(g->mtx);
+    std::vector<size_t> now(10);
+    g->fact_shape_now(now.data());
+    now[8] = (size_t)g->fact_serial; now[9] = (size_t)g->S_gen;
+    if (!g->pend_facs.empty() || !g->pend_vars.empty() || now != exact_shape[i]) {
+      g_last_error = w + "the graphs changed since the last exact joint pass (run a pass first)";
+      return SLIDE_ERR_INVALID;
+    }
+  }
+  return SLIDE_OK;
+}
+int CholBatch::joint_robot(int slot) const {
+  const HostGraph* g = graphs[slot];
+  for (const auto& kv : g->key2pose)
+    if (kv.second == 0)
+      for (int r = 0; r < SLIDE_MAX_ROBOTS; ++r)
+        if ((HostGraph::pose_key(r, 0) >> 56) == (kv.first >> 56)) return r;
+  return 0;
+}
+// Sigma of the separator system and of every robot's band + border, computed once per exact pass (joint_state first: the buffers hold
+// that pass's factor and hG / the graphs' host tables describe it).  Scratch (Z, the row lists, the border maps) lives only in here.
+int CholBatch::ensure_joint_sigma() {
+  if (jsig_serial == exact_serial && jsig_sep) return SLIDE_OK;
+  free_joint_sigma();
+  hipStream_t s = master;
+  const int Ts = sep_Ts, nl = sep_nl, Tsep = Ts + nl;
+  std::vector<JSinvSys> Y;
+  std::vector<int> rp{0}, rows;
+  std::vector<double*> Zs;
+  auto cleanup = [&]() { for (double* z : Zs) if (z) (void)hipFree(z); };
+  auto add_col = [&](const std::vector<int>& r) { rows.insert(rows.end(), r.begin(), r.end()); rp.push_back((int)rows.size()); };
+  // system 0: the separator — leaf a, leaf b (no rows of the other leaf), the top block, then the lambda block (D = -I)
+  {
+    JSinvSys y{};
+    y.S = sepS; y.ld = (Ts + nl + 1) * NB; y.Tb = Ts; y.B = lamS; y.ldb = (nl + 1) * NB;
+    y.Ld = sep_Ld; y.Winv = sep_Winv; y.Ld2 = lam_Ld; y.Winv2 = lam_Winv; y.neg0 = Ts; y.col0 = 0; y.lds = (long long)Tsep * NB;
+    const int sTa = sep_leafT[0], sTL = sep_dissected() ? sTa + sep_leafT[1] : 0;
+    for (int k = 0; k < Tsep; ++k) {
+      std::vector<int> r;
+      if (k < Ts) {
+        int hi = Ts - 1, top0 = Ts;
+        if (sep_dissected() && k < sTL) {
+          const int b = k >= sTa, t0 = b ? sTa : 0;
+          hi = t0 + h_leaf_prof[b][k - t0];
+          top0 = sTL;
+        } else if (!sep_dissected() && sep_prof_on && (int)h_sep_prof.size() == Ts) hi = h_sep_prof[k];
+        for (int i = k + 1; i <= hi; ++i) r.push_back(i);
+        for (int i = top0; i < Ts; ++i) r.push_back(i);      // (a leaf's column: the top block's rows, past the leaf)
+        for (int i = Ts; i < Tsep; ++i) r.push_back(i);
+      } else {
+        for (int i = k + 1; i < Tsep; ++i) r.push_back(i);
+      }
+      add_col(r);
+    }
+    Y.push_back(y);
+  }
+  // systems 1 .. n: the robots — band columns of the segments (a segment's profile, its active border rows), then the windows (dense)
+  std::vector<std::vector<std::vector<int>>> steps(n);      // per robot: the columns of each backward step
+  JSigGather gA{};
+  std::vector<int*> maps(n, nullptr);
+  int max_gn = 0;
+  jsig_rob.assign(n, nullptr); jsig_prow.assign(n, nullptr); jsig_lds.assign(n, 0);
+  for (int i = 0; i < n; ++i) {
+    HostGraph* g = graphs[i];
+    const GraphDev& G = hG[i];
+    const int T = G.T, nbr = G.nbr, nsep = G.nsep > 0 && !g->segs.empty() ? G.nsep : 0, Tc = T + nsep, Trow = T + nbr;
+    JSinvSys y{};
+    y.S = G.S; y.ld = G.ld; y.Tb = T; y.B = G.bord; y.ldb = G.ldb; y.Ld = G.Ld; y.Winv = G.Winv; y.Ld2 = g->d_Ld2.d; y.Winv2 = g->d_Winv2.d;
+    y.neg0 = 1 << 30; y.col0 = (int)rp.size() - 1; y.lds = (long long)Trow * NB;
+    std::vector<std::vector<int>> colrows(Tc);
+    std::vector<std::pair<int, int>> ranges;            // the column ranges factored side by side
+    if (nsep > 0) {
+      const int NS = (int)g->segs.size();
+      for (int q = 0; q < NS; ++q) {
+        const HostGraph::Seg sg = g->segs[q];
+        ranges.emplace_back(sg.t0, sg.t1);
+        for (int k = sg.t0; k < sg.t1; ++k) {
+          const int hi = std::min(sg.t1 - 1, sg.t0 + g->seg_prof[q][k - sg.t0]);
+          for (int r = k + 1; r <= hi; ++r) colrows[k].push_back(r);
+          for (int t = 0; t < nbr; ++t) {
+            const size_t e = 1 + (size_t)NS + (size_t)q * (nbr + 1) + t;
+            const int sf = e < g->seg_tab.size() ? g->seg_tab[e] : 0;
+            if (sf <= k) colrows[k].push_back(T + t);
+          }
+        }
+      }
+      for (int k = T; k < Tc; ++k)
+        for (int r = k + 1; r < Trow; ++r) colrows[k].push_back(r);
+    } else {
+      ranges.emplace_back(0, T);
+      const bool dense = g->h_prof.size() != (size_t)T;
+      for (int k = 0; k < T; ++k) {
+        const int hi = dense ? T - 1 : g->h_prof[k];
+        for (int r = k + 1; r <= hi; ++r) colrows[k].push_back(r);
+        for (int t = 0; t < nbr; ++t)
+          if ((size_t)t >= g->h_bfirst.size() || g->h_bfirst[t] <= k) colrows[k].push_back(T + t);
+      }
+    }
+    for (int k = 0; k < Tc; ++k) add_col(colrows[k]);
+    for (int k = Tc - 1; k >= T; --k) steps[i].push_back({k});
+    for (int st = 0;; ++st) {
+      std::vector<int> cs;
+      for (const auto& rg : ranges) if (rg.second - 1 - st >= rg.first) cs.push_back(rg.second - 1 - st);
+      if (cs.empty()) break;
+      steps[i].push_back(cs);
+    }
+    // Sigma, Z; the border map (border coordinate past the windows -> row of the separator's Sigma) and the pose rows
+    const size_t nsg = (size_t)y.lds * y.lds, nz = (size_t)y.lds * Tc * NB;
+    double* Z = nullptr;
+    SL_HIP(hipMalloc(reinterpret_cast<void**>(&jsig_rob[i]), nsg * sizeof(double)));
+    if (hipMalloc(reinterpret_cast<void**>(&Z), std::max<size_t>(nz, 1) * sizeof(double)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
+    Zs.push_back(Z);
+    SL_HIP(hipMemsetAsync(jsig_rob[i], 0, nsg * sizeof(double), s));
+    y.Sg = jsig_rob[i]; y.Z = Z;
+    jsig_lds[i] = y.lds;
+    Y.push_back(y);
+    const int gn = (nbr - nsep) * NB, m = g->h_sep_off.empty() ? 0 : g->h_sep_off.back();
+    std::vector<int> mp(std::max(gn, 1), -1);
+    for (size_t c = 0; c < g->h_sep_map.size(); ++c) {
+      const int o = g->h_sep_map[c] - nsep * NB;
+      if (o >= 0 && o < gn) mp[o] = (int)c < m ? (int)c : Ts * NB + ((int)c - m);
+    }
+    std::vector<int> prow(std::max<size_t>(G.P, 1), 0);
+    for (int p = 0; p < G.P; ++p)
+      prow[p] = (size_t)p < g->h_pose_sep.size() && g->h_pose_sep[p] >= 0 ? T * NB + g->h_pose_sep[p] : 6 * p;
+    if (hipMalloc(reinterpret_cast<void**>(&maps[i]), mp.size() * sizeof(int)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&jsig_prow[i]), prow.size() * sizeof(int)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
+    SL_HIP(hipMemcpyAsync(maps[i], mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    SL_HIP(hipMemcpyAsync(jsig_prow[i], prow.data(), prow.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    gA.dst[i] = jsig_rob[i]; gA.map[i] = maps[i]; gA.lds[i] = y.lds; gA.o0[i] = Tc * NB; gA.n[i] = gn;
+    max_gn = std::max(max_gn, gn);
+  }
+  // the separator's Sigma and Z
+  jsig_lds_sep = (long long)Tsep * NB;
+  {
+    const size_t nsg = (size_t)jsig_lds_sep * jsig_lds_sep, nz = (size_t)jsig_lds_sep * Tsep * NB;
+    double* Z = nullptr;
+    SL_HIP(hipMalloc(reinterpret_cast<void**>(&jsig_sep), nsg * sizeof(double)));
+    if (hipMalloc(reinterpret_cast<void**>(&Z), nz * sizeof(double)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
+    Zs.push_back(Z);
+    SL_HIP(hipMemsetAsync(jsig_sep, 0, nsg * sizeof(double), s));
+    Y[0].Sg = jsig_sep; Y[0].Z = Z;
+  }
+  gA.src = jsig_sep; gA.lds_src = jsig_lds_sep;
+  // the jobs: the separator's columns one step each (last first), then the robots' steps side by side
+  std::vector<int2> jobs;
+  std::vector<std::pair<int, int>> step_at;          // (first job, jobs) per step
+  std::vector<int> step_rows;
+  auto nrows = [&](int sy, int k) { const int b = Y[sy].col0 + k; return rp[b + 1] - rp[b]; };
+  for (int k = Tsep - 1; k >= 0; --k) {
+    step_at.emplace_back((int)jobs.size(), 1);
+    step_rows.push_back(nrows(0, k));
+    jobs.push_back(make_int2(0, k));
+  }
+  const int n_sep_steps = (int)step_at.size();
+  size_t nst = 0;
+  for (int i = 0; i < n; ++i) nst = std::max(nst, steps[i].size());
+  for (size_t st = 0; st < nst; ++st) {
+    const int j0 = (int)jobs.size();
+    int mr = 0;
+    for (int i = 0; i < n; ++i)
+      if (st < steps[i].size())
+        for (int k : steps[i][st]) { jobs.push_back(make_int2(1 + i, k)); mr = std::max(mr, nrows(1 + i, k)); }
+    step_at.emplace_back(j0, (int)jobs.size() - j0);
+    step_rows.push_back(mr);
+  }
+  int max_rows = 0;
+  for (int r : step_rows) max_rows = std::max(max_rows, r);
+  JSinvSys* d_sys = nullptr; int2* d_jobs = nullptr; int *d_rp = nullptr, *d_rows = nullptr;
+  auto free_tables = [&]() {
+    if (d_sys) (void)hipFree(d_sys);
+    if (d_jobs) (void)hipFree(d_jobs);
+    if (d_rp) (void)hipFree(d_rp);
+    if (d_rows) (void)hipFree(d_rows);
+    for (int* p : maps) if (p) (void)hipFree(p);
+    cleanup();
+  };
+  if (hipMalloc(reinterpret_cast<void**>(&d_sys), Y.size() * sizeof(JSinvSys)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&d_jobs), std::max<size_t>(jobs.size(), 1) * sizeof(int2)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&d_rp), rp.size() * sizeof(int)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&d_rows), std::max<size_t>(rows.size(), 1) * sizeof(int)) != hipSuccess) { free_tables(); return SLIDE_ERR_HIP; }
+  SL_HIP(hipMemcpyAsync(d_sys, Y.data(), Y.size() * sizeof(JSinvSys), hipMemcpyHostToDevice, s));
+  SL_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  SL_HIP(hipMemcpyAsync(d_rp, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  if (!rows.empty()) SL_HIP(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_jsinv_prep(d_sys, d_jobs, (int)jobs.size(), max_rows, d_rp, d_rows, s);
+  for (int q = 0; q < (int)step_at.size(); ++q) {
+    if (q == n_sep_steps) launch_jsig_gather(gA, n, max_gn, s);      // (the robots' rows of separator coordinates, once it is complete)
+    launch_jsinv_step(d_sys, d_jobs + step_at[q].first, step_at[q].second, step_rows[q], d_rp, d_rows, s);
+  }
+  if ((int)step_at.size() == n_sep_steps) launch_jsig_gather(gA, n, max_gn, s);
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
+  free_tables();
+  if (!hip_ok(e1, "joint selected inverse") || !hip_ok(e2, "joint selected inverse")) { free_joint_sigma(); return SLIDE_ERR_HIP; }
+  jsig_serial = exact_serial;
+  return SLIDE_OK;
+}
+// isam->marginalCovariance(X(idx)) on the joint graph (graph.cpp:314-323 on a replica): the poses of the robot of `slot`
+int CholBatch::joint_pose_covariances(int slot, const uint64_t* idx, int n_q, double* out36n) {
+  if (n_q < 0 || (n_q > 0 && (!idx || !out36n))) return SLIDE_ERR_INVALID;
+  for (int i = 0; i < 36 * n_q; ++i) out36n[i] = 0.0;
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("get_pose_covariances", slot);
+  if (rc != SLIDE_OK) return rc;
+  HostGraph* g = graphs[slot];
+  const int robot = joint_robot(slot);
+  std::vector<int> ids(n_q);
+  for (int q = 0; q < n_q; ++q) {
+    auto it = g->key2pose.find(HostGraph::pose_key(robot, idx[q]));
+    if (it == g->key2pose.end() || (size_t)it->second >= g->up_P) return SLIDE_MISSING;
+    ids[q] = it->second;
+  }
+  if (n_q == 0) return SLIDE_OK;
+  if ((rc = ensure_joint_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = master;
+  int* d_idx = nullptr; double* d_out = nullptr;
+  SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), n_q * sizeof(int)));
+  if (hipMalloc(reinterpret_cast<void**>(&d_out), 36 * (size_t)n_q * sizeof(double)) != hipSuccess) { (void)hipFree(d_idx); return SLIDE_ERR_HIP; }
+  hipError_t e = hipMemcpyAsync(d_idx, ids.data(), n_q * sizeof(int), hipMemcpyHostToDevice, s);
+  launch_pose_blocks(jsig_rob[slot], (int)jsig_lds[slot], d_idx, n_q, d_out, s, jsig_prow[slot]);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(out36n, d_out, 36 * (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d_idx); (void)hipFree(d_out);
+  SL_HIP(e);
+  return SLIDE_OK;
+}
+// isam->marginalCovariance(L / C / U(idx)) on the joint graph: a private landmark through its robot's pose Sigma (k_lm_cov), a shared one
+// straight from the separator's Sigma at its slot's coordinates — every replica reads the same numbers
+int CholBatch::joint_landmark_covariances(int slot, int cls, const uint64_t* idx, int n_q, double* out) {
+  if ((cls != SLIDE_CLS_CYLINDER && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_ELLIPSOID) || n_q < 0 || (n_q > 0 && (!idx || !out)))
+    return SLIDE_ERR_INVALID;
+  const int d = cls == SLIDE_CLS_CYLINDER ? 7 : (cls == SLIDE_CLS_CUBE ? 9 : 3);
+  for (int i = 0; i < d * d * n_q; ++i) out[i] = 0.0;
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("get_landmark_covariances", slot);
+  if (rc != SLIDE_OK) return rc;
+  HostGraph* g = graphs[slot];
+  std::vector<int> priv, pq, row0, dims, sq;
+  for (int q = 0; q < n_q; ++q) {
+    const int l = g->lm_lid(cls, idx[q]);
+    if (l < 0) return SLIDE_MISSING;
+    int sl = -1;
+    if ((size_t)l < g->h_lm_bord.size() && g->h_lm_bord[l] >= 0)
+      for (size_t k = 0; k < g->h_sh_lid.size(); ++k) if (g->h_sh_lid[k] == l) { sl = (int)k; break; }
+    if (sl >= 0) { row0.push_back(g->h_sep_off[sl]); dims.push_back(d); sq.push_back(q); }
+    else { priv.push_back(l); pq.push_back(q); }
+  }
+  if (n_q == 0) return SLIDE_OK;
+  if ((rc = ensure_joint_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = master;
+  const size_t np = priv.size(), ns = row0.size();
+  int* d_i = nullptr; double* d_out = nullptr;
+  SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_i), (np + 2 * ns + 1) * sizeof(int)));
+  if (hipMalloc(reinterpret_cast<void**>(&d_out), 81 * (np + ns) * sizeof(double)) != hipSuccess) { (void)hipFree(d_i); return SLIDE_ERR_HIP; }
+  hipError_t e = hipSuccess;
+  if (np) e = hipMemcpyAsync(d_i, priv.data(), np * sizeof(int), hipMemcpyHostToDevice, s);
+  if (ns && e == hipSuccess) e = hipMemcpyAsync(d_i + np, row0.data(), ns * sizeof(int), hipMemcpyHostToDevice, s);
+  if (ns && e == hipSuccess) e = hipMemcpyAsync(d_i + np + ns, dims.data(), ns * sizeof(int), hipMemcpyHostToDevice, s);
+  launch_landmark_covariances(hG[slot], jsig_rob[slot], (int)jsig_lds[slot], d_i, (int)np, d_out, s, jsig_prow[slot]);
+  launch_sym_blocks(jsig_sep, (size_t)jsig_lds_sep, d_i + np, d_i + np + ns, (int)ns, d_out + 81 * np, s);
+  std::vector<double> h(81 * (np + ns));
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d_i); (void)hipFree(d_out);
+  SL_HIP(e);
+  for (size_t k = 0; k < np; ++k)
+    for (int v = 0; v < d * d; ++v) out[(size_t)pq[k] * d * d + v] = h[81 * k + v];
+  for (size_t k = 0; k < ns; ++k)
+    for (int v = 0; v < d * d; ++v) out[(size_t)sq[k] * d * d + v] = h[81 * (np + k) + v];
+  return SLIDE_OK;
+}
+// logEntropy (graph.cpp:423-466) on the joint graph: {the traces of the robot's pose marginals, the traces of the job's point landmarks
+// (every graph's private ones, each shared slot once), #poses, #point landmarks}
+int CholBatch::joint_marginal_traces(int slot, double* out4) {
+  for (int i = 0; i < 4; ++i) out4[i] = 0.0;
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("marginal_traces", slot);
+  if (rc != SLIDE_OK) return rc;
+  if ((rc = ensure_joint_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = master;
+  std::vector<int> poses;
+  graphs[slot]->robot_poses(joint_robot(slot), poses);
+  std::vector<std::vector<int>> priv(n);
+  std::vector<int> row0, dims;
+  std::vector<char> seen;
+  for (int i = 0; i < n; ++i) {
+    const HostGraph* g = graphs[i];
+    for (size_t l = 0; l < g->up_L && l < g->h_lm_type.size(); ++l)
+      if (g->h_lm_type[l] == VT_POINT && !(l < g->h_lm_bord.size() && g->h_lm_bord[l] >= 0)) priv[i].push_back((int)l);
+    seen.resize(std::max(seen.size(), g->h_sh_lid.size()), 0);
+    for (size_t k = 0; k < g->h_sh_lid.size(); ++k) {
+      const int l = g->h_sh_lid[k];
+      if (l < 0 || (size_t)l >= g->up_L || g->h_lm_type[l] != VT_POINT || seen[k]) continue;
+      seen[k] = 1;
+      row0.push_back(g->h_sep_off[k]); dims.push_back(3);
+    }
+  }
+  size_t nq = poses.size() + row0.size();
+  for (int i = 0; i < n; ++i) nq += priv[i].size();
+  int* d_i = nullptr; double* d_out = nullptr;
+  SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_i), (nq + row0.size() + 1) * sizeof(int)));
+  if (hipMalloc(reinterpret_cast<void**>(&d_out), (81 * nq + 1) * sizeof(double)) != hipSuccess) { (void)hipFree(d_i); return SLIDE_ERR_HIP; }
+  hipError_t e = hipSuccess;
+  size_t o = 0;
+  auto up = [&](const std::vector<int>& v) { if (!v.empty() && e == hipSuccess) e = hipMemcpyAsync(d_i + o, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s); o += v.size(); };
+  const size_t o_pose = o; up(poses);
+  std::vector<size_t> o_priv(n);
+  for (int i = 0; i < n; ++i) { o_priv[i] = o; up(priv[i]); }
+  const size_t o_sh = o; up(row0); up(dims);
+  launch_pose_blocks(jsig_rob[slot], (int)jsig_lds[slot], d_i + o_pose, (int)poses.size(), d_out, s, jsig_prow[slot]);
+  for (int i = 0; i < n; ++i)
+    launch_landmark_covariances(hG[i], jsig_rob[i], (int)jsig_lds[i], d_i + o_priv[i], (int)priv[i].size(), d_out + 81 * o_priv[i], s, jsig_prow[i]);
+  launch_sym_blocks(jsig_sep, (size_t)jsig_lds_sep, d_i + o_sh, d_i + o_sh + row0.size(), (int)row0.size(), d_out + 81 * o_sh, s);
+  std::vector<double> h(81 * nq);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess && !h.empty()) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(d_i); (void)hipFree(d_out);
+  SL_HIP(e);
+  for (size_t p = 0; p < poses.size(); ++p)      // (pose blocks: 36 per pose, packed from the front of d_out)
+    for (int a = 0; a < 6; ++a) out4[0] += h[36 * p + 7 * a];
+  for (size_t q = o_priv.empty() ? o_sh : o_priv[0]; q < o_sh + row0.size(); ++q)
+    for (int a = 0; a < 3; ++a) out4[1] += h[81 * q + 4 * a];
+  out4[2] = (double)poses.size();
+  out4[3] = (double)(o_sh + row0.size() - poses.size());
   return SLIDE_OK;
 }
 

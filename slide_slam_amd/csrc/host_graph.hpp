@@ -190,6 +190,11 @@ class CholBatch {
   hipStream_t pass_stream();                             // the stream the passes run on (created on first use)
   int profile_pass(double* const* d_bufs, double* ms_steps, int* n_launches);
   int profile_arrow(double* const* d_bufs, double* out6, int* n_sep_steps);
+  // marginal covariances on the JOINT graph, from the factor the last exact joint pass (pass_all) left (joint_cov_kernels.hip): the
+  // poses of the graph in `slot` by its pose indices, its landmarks by its landmark ids, logEntropy's trace sums (job-wide landmarks)
+  int joint_pose_covariances(int slot, const uint64_t* idx, int n, double* out36n);
+  int joint_landmark_covariances(int slot, int cls, const uint64_t* idx, int n, double* out);
+  int joint_marginal_traces(int slot, double* out4);
 
  private:
   int n;
@@ -296,6 +301,17 @@ class CholBatch {
   int* d_status_all = nullptr;           // the joined graphs' status words, gathered by the last node of a pass
   int ctr_cap = 0;
   int factor_all(hipEvent_t after);      // the batched factor + solve of all joined systems, in one to four overlapping launch sequences
+  // joint marginals: exact_serial = the number of the last whole exact pass whose factor the buffers still hold (0: none — no pass yet, or
+  // the last pass was cut, profiled or not exact); per graph, what that pass factored (HostGraph::fact_shape_now + fact_serial)
+  unsigned long long n_exact = 0, exact_serial = 0, jsig_serial = 0;
+  std::vector<std::vector<size_t>> exact_shape;
+  double* jsig_sep = nullptr; long long jsig_lds_sep = 0;                // Sigma of the separator system (landmark coordinates, then lambdas)
+  std::vector<double*> jsig_rob; std::vector<long long> jsig_lds;       // per graph: Sigma over its band, window and border rows
+  std::vector<int*> jsig_prow;                                          // per graph: a pose's first row in its Sigma
+  void free_joint_sigma();
+  int joint_state(const char* who, int slot);      // SLIDE_ERR_INVALID (+ message) unless the last exact pass's factor is resident
+  int ensure_joint_sigma();
+  int joint_robot(int slot) const;                 // robot id of the graph's own poses
 };
 
 class HostGraph {

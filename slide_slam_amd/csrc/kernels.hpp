@@ -112,13 +112,28 @@ void launch_pose_covariance(const double* S, int ld, int T, const double* Ld, co
 // with Z (S's size) as scratch; marginal blocks out of it; many right-hand sides on the factor; the information-gain products
 void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
                              double* Sg, double* Z, hipStream_t s);
-void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s);                 // out: 36 per pose
-void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s);   // out: 81 per landmark (d x d used)
+void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s, const int* prow = nullptr);     // out: 36 per pose; prow: a pose's first row (null: 6 p)
+void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s,
+                                 const int* prow = nullptr);      // out: 81 per landmark (d x d used)
 void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* X,
                         int nrhs, hipStream_t s);      // X = S^-1 B (B: nrhs columns of T * NB rows, overwritten)
 void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nrows, double* M, hipStream_t s);
 void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s);
 void launch_scatter(const int* rc, const double* val, int n, double* B, int nT, hipStream_t s);
+// joint_cov_kernels.hip — the selected inverse over the exact joint pass's elimination tree (CholBatch::ensure_joint_sigma).  One system:
+// factor columns [0, Tb) in S (ld; rows past Tb = its stored border rows), [Tb, Tc) in B (ldb, rows and columns counted from Tb); their
+// diagonal blocks in Ld / Winv and Ld2 / Winv2; D = -I on the columns >= neg0; Sigma and Z dense lower with leading dimension lds.
+// col0: the system's first entry in the row-list offsets rp (rp[col0 + c] .. rp[col0 + c + 1] index the tile rows of column c)
+struct JSinvSys { const double* S; int ld, Tb; const double* B; int ldb; const double *Ld, *Winv, *Ld2, *Winv2; int neg0, col0;
+                  double* Sg; double* Z; long long lds; };
+// per robot r: dst[r] (its Sigma, leading dimension lds[r]) rows / columns o0[r] .. o0[r] + n[r] - 1 <- src through map[r] (-1: zero)
+constexpr int JSIG_ROBOTS_MAX = 8;      // (a CholBatch's slots)
+struct JSigGather { double* dst[JSIG_ROBOTS_MAX]; const int* map[JSIG_ROBOTS_MAX]; long long lds[JSIG_ROBOTS_MAX]; int o0[JSIG_ROBOTS_MAX], n[JSIG_ROBOTS_MAX];
+                    const double* src; long long lds_src; };
+void launch_jsinv_prep(const JSinvSys* d_sys, const int2* d_jobs, int njobs, int max_rows, const int* d_rp, const int* d_rows, hipStream_t s);
+void launch_jsinv_step(const JSinvSys* d_sys, const int2* d_jobs, int njobs, int max_rows, const int* d_rp, const int* d_rows, hipStream_t s);   // two launches
+void launch_jsig_gather(const JSigGather& A, int n_robots, int max_n, hipStream_t s);
+void launch_sym_blocks(const double* Sg, size_t ld, const int* row0, const int* dim, int n, double* out, hipStream_t s);      // out: 81 per block (d x d used)
 // stand-alone dense SPD solve on device buffers (used by the unit tests and the roofline bench leg)
 void launch_chol_solve_bwd(const CholSystem& cs, hipStream_t s);   // yv -> dp after launch_chol_extract_y: one-workgroup substitution for narrow profiles, else the chained kernel
 int chol_factor_solve(double* S, int ld, int T, double* Ld, double* Winv, double* yv, double* dp, int* status, int* ctr, hipStream_t s);

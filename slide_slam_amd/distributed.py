@@ -645,6 +645,40 @@ class PassDriver:
     def _all(self, count):
         self._local_sum(count); self._exchange(count); self._local_bcast(count)
 
+    # ---- marginal covariances on the joint graph (the exact joint pass's factor; CholBatch.get_pose_covariances, slide_gpu.h) ----------
+    def _joint_ok(self):
+        if self.batch is None or not self.arrow:
+            raise ValueError("joint marginals need a CholBatch running exact joint passes (arrow=True)")
+        if self.world > 1:
+            raise ValueError("joint marginals are served when the job is this process alone (world == 1)")
+
+    def get_pose_covariances(self, robot, idx):
+        """(n, 6, 6) joint-graph marginals of the poses `idx` of robot `robot` (= its shard's slot)."""
+        self._joint_ok()
+        return self.batch.get_pose_covariances(robot, idx)
+
+    def get_landmark_covariances(self, cls, gids, gid):
+        """(n, d, d) joint-graph marginals of the job's landmarks `gids` (global ids) of class `cls`; gid[r][cls][local] = the global id
+        of robot r's landmark (setup_local_shards' id table).  A shared landmark is read from the first robot that holds it."""
+        self._joint_ok()
+        where = {}
+        for r in range(len(self.shards)):
+            for loc, g in enumerate(gid[r][cls]):
+                where.setdefault(int(g), (r, loc))
+        d = {0: 7, 1: 9}.get(cls, 3)
+        out = np.zeros((len(gids), d, d))
+        for k, g in enumerate(np.asarray(gids).reshape(-1)):
+            if int(g) not in where:
+                raise KeyError(f"landmark {int(g)} of class {cls} not in the job")
+            r, loc = where[int(g)]
+            out[k] = self.batch.get_landmark_covariances(r, cls, [loc])[0]
+        return out
+
+    def marginal_traces(self, robot):
+        """logEntropy on the joint graph for robot `robot`: [pose trace sum, the job's point-landmark trace sum, #poses, #points]."""
+        self._joint_ok()
+        return self.batch.marginal_traces(robot)
+
     def one_pass(self):
         n54, n9, K = 54 * self.n_slots, 9 * self.n_slots, self.pcg_iters
         if self.batch is not None:
