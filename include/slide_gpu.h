@@ -195,6 +195,20 @@ int slide_chol_batch_get_landmark_covariances(slide_chol_batch_t* b, int slot, i
 /* logEntropy (graph.cpp:423-466) on the joint graph: out4 = {sum of the traces of the pose marginals of the robot in `slot`, sum over the
  * job's point landmarks (every graph's private ones, each shared one once), #poses, #point landmarks}. */
 int slide_chol_batch_marginal_traces(slide_chol_batch_t* b, int slot, double out4[4]);
+/* estimateClosureInfoGain (graph.cpp:469-623) on the JOINT graph — what a sloam_node's replica of the whole multi-robot graph
+ * (graph.cpp:325-371) answers an active-SLAM planner: the drop of logEntropy's trace sums when Between factors (traj[i+1], traj[i]),
+ * i < n - 1, with noise sigma_per_m * travel[i] and zero residual are added.  Pose q is pose traj[q] of the robot whose graph is in slot
+ * traj_slots[q] (traj_slots = NULL: every pose in `slot`); different slots make an inter-robot candidate (a rendezvous).
+ * sigma_per_m = NULL: the noise_model_odom_vec of the graph in `slot`.  out4 = {10 pose + landmark (graph.cpp:622), the pose drop of the
+ * robot in `slot`, the drop over the job's point landmarks (as slide_chol_batch_marginal_traces), the pose drop summed over every robot}.
+ * Linear-Gaussian model of the factor the last slide_chol_batch_pass left: a rank-6(n-1) Woodbury update with J at the pass's
+ * linearisation point, nothing re-factored; unlike iSAM2's update it does not relinearise variables while the candidate factors are in.
+ * Refusals as the joint marginals (SLIDE_ERR_INVALID before a whole exact pass, after any graph changed, in PCG / block-Jacobi mode, on
+ * a rank owning one separator leaf); SLIDE_MISSING for an unknown pose; SLIDE_ERR_INVALID for n < 2 or a travel / sigma <= 0;
+ * SLIDE_ERR_CAPACITY for n - 1 > SLIDE_INFO_GAIN_MAX_STEPS; SLIDE_ERR_NOT_SPD if I + J Sigma J^T is not positive definite.  Runs on
+ * the batch's stream outside any capture and writes nothing a pass reads (the cached joint Sigma included). */
+int slide_chol_batch_closure_info_gain(slide_chol_batch_t* b, int slot, const int32_t* traj_slots, const uint64_t* traj, int n,
+                                       const double* travel, const double sigma_per_m[6], double out4[4]);
 /* The same pass for a job that spans GPUs, cut at its two exchanges (8 / N robots on each of N GPUs): every part is a captured
  * hipGraph replayed on the batch's stream.
  *   part 0: phase 0 of every robot + the local sum -> every local buffer holds this GPU's sum of the 54-doubles-per-slot blocks;

@@ -28,7 +28,7 @@ EXPORTS = [
     "slide_graph_add_loop_closure", "slide_graph_add_relative_meas", "slide_graph_add_point_landmark",
     "slide_graph_add_range_bearing", "slide_graph_add_cube", "slide_graph_add_cylinder", "slide_graph_solve",
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
-    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
+    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_closure_info_gain", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
     "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
@@ -473,6 +473,32 @@ class CholBatch:
         """logEntropy on the joint graph: [pose trace sum of the robot in `slot`, the job's point-landmark trace sum, #poses, #points]."""
         out = np.zeros(4)
         _check(self.L.slide_chol_batch_marginal_traces(C.c_void_p(self.h), C.c_int(slot), _p(out)))
+        return out
+
+    def closure_info_gain(self, slot, traj, travel, sigma_per_m=None, traj_slots=None):
+        """estimateClosureInfoGain on the JOINT graph (slide_gpu.h): [10 pose + landmark, pose drop of the robot in `slot`, the job's
+        point-landmark drop, pose drop of every robot] of Between factors (traj[i+1], traj[i]) with noise sigma_per_m * travel[i] (None:
+        the noise_model_odom_vec of the graph in `slot`).  traj_slots[q]: the slot whose robot owns pose traj[q] (None: all `slot`)."""
+        t = np.ascontiguousarray(traj, dtype=np.uint64).reshape(-1)
+        tr = _d(travel).reshape(-1)
+        if len(tr) != max(len(t) - 1, 0):
+            raise ValueError("travel needs one distance per step of traj")
+        sg = None
+        if sigma_per_m is not None:
+            sg = _d(sigma_per_m).reshape(-1)
+            if len(sg) != 6:
+                raise ValueError("sigma_per_m has six entries")
+        ts = None
+        if traj_slots is not None:
+            ts = np.ascontiguousarray(traj_slots, dtype=np.int32).reshape(-1)
+            if len(ts) != len(t):
+                raise ValueError("traj_slots needs one slot per pose of traj")
+        out = np.zeros(4)
+        st = self.L.slide_chol_batch_closure_info_gain(C.c_void_p(self.h), C.c_int(slot), _p(ts) if ts is not None else None, _p(t),
+                                                       C.c_int(len(t)), _p(tr), _p(sg) if sg is not None else None, _p(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"trajectory pose not in the joint graph (slot {slot})")
+        _check(st)
         return out
 
     def set_pcg(self, iterations, tol=0.0):

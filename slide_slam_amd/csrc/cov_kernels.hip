@@ -396,9 +396,10 @@ void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nro
 }
 
 // V_l = sum_{f in factors(l)} U_{p_f} F_f for the landmarks lids[q]: V[a ldv + 9 q + c] (6m x d, c < 9, zero for c >= d).
-// U: ncol columns of nT rows.  One workgroup per landmark, threads over the columns a.
+// U: ncol columns of nT rows; prow: a pose's first row in U (null: 6 p; a joint system's window poses sit in its border rows).
+// One workgroup per landmark, threads over the columns a.
 __global__ __launch_bounds__(256) void k_lm_V(GraphDev G, const double* __restrict__ U, int nT, int ncol, const int* __restrict__ lids,
-                                              int n, double* __restrict__ V, size_t ldv) {
+                                              int n, double* __restrict__ V, size_t ldv, const int* __restrict__ prow) {
   const int q = blockIdx.x;
   if (q >= n) return;
   const int l = lids[q];
@@ -410,7 +411,7 @@ __global__ __launch_bounds__(256) void k_lm_V(GraphDev G, const double* __restri
     for (int c = 0; c < 9; ++c) v[c] = 0.0;
     for (int qf = f0; qf < f1; ++qf) {
       const int f = G.lm_fids[qf];
-      const double* u = U + (size_t)a * nT + 6 * (size_t)G.lf_pose[f];
+      const double* u = U + (size_t)a * nT + (prow ? (size_t)prow[G.lf_pose[f]] : 6 * (size_t)G.lf_pose[f]);
       const double* F = G.ebuf + G.lf_eoff[f] + 6 * D;
 #pragma unroll
       for (int b = 0; b < 6; ++b) {
@@ -424,8 +425,9 @@ __global__ __launch_bounds__(256) void k_lm_V(GraphDev G, const double* __restri
     for (int c = 0; c < 9; ++c) V[(size_t)a * ldv + 9 * (size_t)q + c] = v[c];
   }
 }
-void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_lm_V, dim3(n), dim3(256), 0, s, G, U, nT, ncol, lids, n, V, ldv);
+void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s,
+                       const int* prow) {
+  if (n > 0) hipLaunchKernelGGL(k_lm_V, dim3(n), dim3(256), 0, s, G, U, nT, ncol, lids, n, V, ldv, prow);
 }
 
 // scatter (row, col, value) entries into a column-major matrix of nT rows (the whitened Jacobian rows of the candidate closure)

@@ -3149,6 +3149,68 @@ int HostGraph::marginal_traces(int robot, double* out4) {
   out4[3] = (double)nl;
   return SLIDE_OK;
 }
+// The Adjoint of T_b^-1 T_a (row-major 12-double poses: R row-major, then t): the whitened Jacobian of a Between factor (a, b) at zero
+// residual is -Ad / sigma on a and I / sigma on b (both charts)
+static void between_adjoint(const double* Ta, const double* Tb, double Ad[6][6]) {
+  double R[9], t[3], dt[3] = {Ta[9] - Tb[9], Ta[10] - Tb[10], Ta[11] - Tb[11]};
+  for (int r = 0; r < 3; ++r) {                      // T_b^-1 T_a = (Rb^T Ra, Rb^T (ta - tb))
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = Tb[r] * Ta[c] + Tb[3 + r] * Ta[3 + c] + Tb[6 + r] * Ta[6 + c];
+    t[r] = Tb[r] * dt[0] + Tb[3 + r] * dt[1] + Tb[6 + r] * dt[2];
+  }
+  for (int r = 0; r < 6; ++r)                        // [R 0; t^ R  R]
+    for (int c = 0; c < 6; ++c) Ad[r][c] = 0.0;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      Ad[r][c] = R[3 * r + c];
+      Ad[3 + r][3 + c] = R[3 * r + c];
+    }
+  const double tx[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Ad[3 + r][c] = tx[3 * r] * R[c] + tx[3 * r + 1] * R[3 + c] + tx[3 * r + 2] * R[6 + c];
+}
+// The Woodbury step's host part: C (ncol x ncol, row-major, C = I + J U) symmetrised, C^-1 by Cholesky, g[k] = sum_ab (C^-1)_ab M_k,ab
+static int woodbury_drops(std::vector<double>& Cm, int ncol, const double* const* M, int nM, double* g) {
+  // C^-1 by Cholesky (C = I + J Sigma J^T is SPD); the gains are sum_ab (C^-1)_ab M_ab of the symmetrised matrices
+  for (int a = 0; a < ncol; ++a)
+    for (int b = 0; b < a; ++b) Cm[(size_t)a * ncol + b] = Cm[(size_t)b * ncol + a] = 0.5 * (Cm[(size_t)a * ncol + b] + Cm[(size_t)b * ncol + a]);
+  std::vector<double> Lc((size_t)ncol * ncol, 0.0);
+  for (int j = 0; j < ncol; ++j) {
+    double d = Cm[(size_t)j * ncol + j];
+    for (int k = 0; k < j; ++k) d -= Lc[(size_t)j * ncol + k] * Lc[(size_t)j * ncol + k];
+    if (!(d > 0.0)) { g_last_error = "closure_info_gain: I + J Sigma J^T is not positive definite"; return SLIDE_ERR_NOT_SPD; }
+    const double ljj = std::sqrt(d);
+    Lc[(size_t)j * ncol + j] = ljj;
+    for (int i = j + 1; i < ncol; ++i) {
+      double v = Cm[(size_t)i * ncol + j];
+      for (int k = 0; k < j; ++k) v -= Lc[(size_t)i * ncol + k] * Lc[(size_t)j * ncol + k];
+      Lc[(size_t)i * ncol + j] = v / ljj;
+    }
+  }
+  // (on the host: O((6m)^3), about 10^8 flops at the cap m = 64 — the largest part of such a query; a device version is a follow-up)
+  std::vector<double> LcT((size_t)ncol * ncol), Ci((size_t)ncol * ncol, 0.0), col(ncol);
+  for (int i = 0; i < ncol; ++i)
+    for (int k = 0; k < ncol; ++k) LcT[(size_t)i * ncol + k] = Lc[(size_t)k * ncol + i];
+  for (int j = 0; j < ncol; ++j) {                   // column j of C^-1: L L^T x = e_j (L^-1 e_j is zero above row j)
+    for (int i = 0; i < j; ++i) col[i] = 0.0;
+    for (int i = j; i < ncol; ++i) {
+      double v = i == j ? 1.0 : 0.0;
+      for (int k = j; k < i; ++k) v -= Lc[(size_t)i * ncol + k] * col[k];
+      col[i] = v / Lc[(size_t)i * ncol + i];
+    }
+    for (int i = ncol - 1; i >= 0; --i) {
+      double v = col[i];
+      for (int k = i + 1; k < ncol; ++k) v -= LcT[(size_t)i * ncol + k] * col[k];
+      col[i] = v / Lc[(size_t)i * ncol + i];
+    }
+    for (int i = 0; i < ncol; ++i) Ci[(size_t)i * ncol + j] = col[i];
+  }
+  for (int k = 0; k < nM; ++k) {
+    double gk = 0.0;
+    for (size_t e = 0; e < (size_t)ncol * ncol; ++e) gk += Ci[e] * M[k][e];
+    g[k] = gk;
+  }
+  return SLIDE_OK;
+}
 // estimateClosureInfoGain (graph.cpp:469-623) in the linear-Gaussian model of the resident factor.  Fake factor i is a Between factor
 // (c_{i+1}, c_i) measuring the relative pose of the linearisation values (residual 0), noise sigma_per_m * travel[i]; its whitened
 // Jacobian there is  -Ad(T_{c_i}^-1 T_{c_{i+1}}) / sigma  on c_{i+1} and  I / sigma  on c_i (both charts).  With J (6m x n) these rows,
@@ -3186,22 +3248,8 @@ int HostGraph::closure_info_gain(int robot, const uint64_t* traj, int n, const d
   // J^T, entry by entry (row of the reduced system, column 6 i + a); a repeated pose sums its blocks
   std::map<std::pair<int, int>, double> jt;
   for (int i = 0; i < m; ++i) {
-    const double* Ta = val.data() + 12 * (i + 1);      // c_{i+1}
-    const double* Tb = val.data() + 12 * i;            // c_i
-    double R[9], t[3], dt[3] = {Ta[9] - Tb[9], Ta[10] - Tb[10], Ta[11] - Tb[11]};
-    for (int r = 0; r < 3; ++r) {                      // T_b^-1 T_a = (Rb^T Ra, Rb^T (ta - tb))
-      for (int c = 0; c < 3; ++c) R[3 * r + c] = Tb[r] * Ta[c] + Tb[3 + r] * Ta[3 + c] + Tb[6 + r] * Ta[6 + c];
-      t[r] = Tb[r] * dt[0] + Tb[3 + r] * dt[1] + Tb[6 + r] * dt[2];
-    }
-    double Ad[6][6] = {};                              // [R 0; t^ R  R]
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) {
-        Ad[r][c] = R[3 * r + c];
-        Ad[3 + r][3 + c] = R[3 * r + c];
-      }
-    const double tx[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) Ad[3 + r][c] = tx[3 * r] * R[c] + tx[3 * r + 1] * R[3 + c] + tx[3 * r + 2] * R[6 + c];
+    double Ad[6][6];
+    between_adjoint(val.data() + 12 * (i + 1), val.data() + 12 * i, Ad);      // (c_{i+1}, c_i)
     for (int a = 0; a < 6; ++a) {
       const double w = 1.0 / (sigma6[a] * travel[i]);
       for (int c = 0; c < 6; ++c) jt[{6 * ids[i + 1] + c, 6 * i + a}] += -Ad[a][c] * w;
@@ -3258,45 +3306,10 @@ int HostGraph::closure_info_gain(int robot, const uint64_t* traj, int n, const d
     const double* u = Urow.data() + (size_t)row_of[row / 6] * 6 * ncol + row % 6;
     for (int c = 0; c < ncol; ++c) Cm[(size_t)jrow * ncol + c] += vv[e] * u[6 * (size_t)c];
   }
-  // C^-1 by Cholesky (C = I + J Sigma J^T is SPD); the gains are sum_ab (C^-1)_ab M_ab of the symmetrised matrices
-  for (int a = 0; a < ncol; ++a)
-    for (int b = 0; b < a; ++b) Cm[(size_t)a * ncol + b] = Cm[(size_t)b * ncol + a] = 0.5 * (Cm[(size_t)a * ncol + b] + Cm[(size_t)b * ncol + a]);
-  std::vector<double> Lc((size_t)ncol * ncol, 0.0);
-  for (int j = 0; j < ncol; ++j) {
-    double d = Cm[(size_t)j * ncol + j];
-    for (int k = 0; k < j; ++k) d -= Lc[(size_t)j * ncol + k] * Lc[(size_t)j * ncol + k];
-    if (!(d > 0.0)) { g_last_error = "closure_info_gain: I + J Sigma J^T is not positive definite"; return SLIDE_ERR_NOT_SPD; }
-    const double ljj = std::sqrt(d);
-    Lc[(size_t)j * ncol + j] = ljj;
-    for (int i = j + 1; i < ncol; ++i) {
-      double v = Cm[(size_t)i * ncol + j];
-      for (int k = 0; k < j; ++k) v -= Lc[(size_t)i * ncol + k] * Lc[(size_t)j * ncol + k];
-      Lc[(size_t)i * ncol + j] = v / ljj;
-    }
-  }
-  // (on the host: O((6m)^3), about 10^8 flops at the cap m = 64 — the largest part of such a query; a device version is a follow-up)
-  std::vector<double> LcT((size_t)ncol * ncol), Ci((size_t)ncol * ncol, 0.0), col(ncol);
-  for (int i = 0; i < ncol; ++i)
-    for (int k = 0; k < ncol; ++k) LcT[(size_t)i * ncol + k] = Lc[(size_t)k * ncol + i];
-  for (int j = 0; j < ncol; ++j) {                   // column j of C^-1: L L^T x = e_j (L^-1 e_j is zero above row j)
-    for (int i = 0; i < j; ++i) col[i] = 0.0;
-    for (int i = j; i < ncol; ++i) {
-      double v = i == j ? 1.0 : 0.0;
-      for (int k = j; k < i; ++k) v -= Lc[(size_t)i * ncol + k] * col[k];
-      col[i] = v / Lc[(size_t)i * ncol + i];
-    }
-    for (int i = ncol - 1; i >= 0; --i) {
-      double v = col[i];
-      for (int k = i + 1; k < ncol; ++k) v -= LcT[(size_t)i * ncol + k] * col[k];
-      col[i] = v / Lc[(size_t)i * ncol + i];
-    }
-    for (int i = 0; i < ncol; ++i) Ci[(size_t)i * ncol + j] = col[i];
-  }
-  double gp = 0.0, gl = 0.0;
-  for (size_t e = 0; e < (size_t)ncol * ncol; ++e) {
-    gp += Ci[e] * M[e];
-    gl += Ci[e] * M[(size_t)ncol * ncol + e];
-  }
+  const double* Ms[2] = {M.data(), M.data() + (size_t)ncol * ncol};
+  double gs[2];
+  if ((rc = woodbury_drops(Cm, ncol, Ms, 2, gs)) != SLIDE_OK) return rc;
+  const double gp = gs[0], gl = gs[1];
   out3[0] = 10.0 * gp + gl;
   out3[1] = gp;
   out3[2] = gl;
@@ -3359,17 +3372,15 @@ int CholBatch::joint_robot(int slot) const {
         if ((HostGraph::pose_key(r, 0) >> 56) == (kv.first >> 56)) return r;
   return 0;
 }
-// Sigma of the separator system and of every robot's band + border, computed once per exact pass (joint_state first: the buffers hold
-// that pass's factor and hG / the graphs' host tables describe it).  Scratch (Z, the row lists, the border maps) lives only in here.
-int CholBatch::ensure_joint_sigma() {
-  if (jsig_serial == exact_serial && jsig_sep) return SLIDE_OK;
-  free_joint_sigma();
-  hipStream_t s = master;
+// The elimination tree of the last exact pass (joint_state first: hG / the graphs' host tables describe the factor the buffers hold).
+// Shared by the selected inverse and the many-right-hand-side solve.
+void CholBatch::joint_tree(JointTree& t) const {
   const int Ts = sep_Ts, nl = sep_nl, Tsep = Ts + nl;
-  std::vector<JSinvSys> Y;
-  std::vector<int> rp{0}, rows;
-  std::vector<double*> Zs;
-  auto cleanup = [&]() { for (double* z : Zs) if (z) (void)hipFree(z); };
+  t.Ts = Ts; t.Tsep = Tsep;
+  t.sTa = sep_leafT[0]; t.sTL = sep_dissected() ? t.sTa + sep_leafT[1] : 0;
+  std::vector<JSinvSys>& Y = t.Y;
+  std::vector<int>& rp = t.rp;
+  std::vector<int>& rows = t.rows;
   auto add_col = [&](const std::vector<int>& r) { rows.insert(rows.end(), r.begin(), r.end()); rp.push_back((int)rows.size()); };
   // system 0: the separator — leaf a, leaf b (no rows of the other leaf), the top block, then the lambda block (D = -I)
   {
@@ -3397,20 +3408,17 @@ int CholBatch::ensure_joint_sigma() {
     Y.push_back(y);
   }
   // systems 1 .. n: the robots — band columns of the segments (a segment's profile, its active border rows), then the windows (dense)
-  std::vector<std::vector<std::vector<int>>> steps(n);      // per robot: the columns of each backward step
-  JSigGather gA{};
-  std::vector<int*> maps(n, nullptr);
-  int max_gn = 0;
-  jsig_rob.assign(n, nullptr); jsig_prow.assign(n, nullptr); jsig_lds.assign(n, 0);
+  t.steps.assign(n, {}); t.ranges.assign(n, {});
+  t.T.assign(n, 0); t.Tc.assign(n, 0); t.Trow.assign(n, 0); t.gn.assign(n, 0); t.map.assign(n, {}); t.prow.assign(n, {});
   for (int i = 0; i < n; ++i) {
-    HostGraph* g = graphs[i];
+    const HostGraph* g = graphs[i];
     const GraphDev& G = hG[i];
     const int T = G.T, nbr = G.nbr, nsep = G.nsep > 0 && !g->segs.empty() ? G.nsep : 0, Tc = T + nsep, Trow = T + nbr;
     JSinvSys y{};
     y.S = G.S; y.ld = G.ld; y.Tb = T; y.B = G.bord; y.ldb = G.ldb; y.Ld = G.Ld; y.Winv = G.Winv; y.Ld2 = g->d_Ld2.d; y.Winv2 = g->d_Winv2.d;
     y.neg0 = 1 << 30; y.col0 = (int)rp.size() - 1; y.lds = (long long)Trow * NB;
     std::vector<std::vector<int>> colrows(Tc);
-    std::vector<std::pair<int, int>> ranges;            // the column ranges factored side by side
+    std::vector<std::pair<int, int>>& ranges = t.ranges[i];      // the column ranges factored side by side
     if (nsep > 0) {
       const int NS = (int)g->segs.size();
       for (int q = 0; q < NS; ++q) {
@@ -3419,10 +3427,10 @@ int CholBatch::ensure_joint_sigma() {
         for (int k = sg.t0; k < sg.t1; ++k) {
           const int hi = std::min(sg.t1 - 1, sg.t0 + g->seg_prof[q][k - sg.t0]);
           for (int r = k + 1; r <= hi; ++r) colrows[k].push_back(r);
-          for (int t = 0; t < nbr; ++t) {
-            const size_t e = 1 + (size_t)NS + (size_t)q * (nbr + 1) + t;
+          for (int tt = 0; tt < nbr; ++tt) {
+            const size_t e = 1 + (size_t)NS + (size_t)q * (nbr + 1) + tt;
             const int sf = e < g->seg_tab.size() ? g->seg_tab[e] : 0;
-            if (sf <= k) colrows[k].push_back(T + t);
+            if (sf <= k) colrows[k].push_back(T + tt);
           }
         }
       }
@@ -3434,19 +3442,57 @@ int CholBatch::ensure_joint_sigma() {
       for (int k = 0; k < T; ++k) {
         const int hi = dense ? T - 1 : g->h_prof[k];
         for (int r = k + 1; r <= hi; ++r) colrows[k].push_back(r);
-        for (int t = 0; t < nbr; ++t)
-          if ((size_t)t >= g->h_bfirst.size() || g->h_bfirst[t] <= k) colrows[k].push_back(T + t);
+        for (int tt = 0; tt < nbr; ++tt)
+          if ((size_t)tt >= g->h_bfirst.size() || g->h_bfirst[tt] <= k) colrows[k].push_back(T + tt);
       }
     }
     for (int k = 0; k < Tc; ++k) add_col(colrows[k]);
-    for (int k = Tc - 1; k >= T; --k) steps[i].push_back({k});
+    for (int k = Tc - 1; k >= T; --k) t.steps[i].push_back({k});
     for (int st = 0;; ++st) {
       std::vector<int> cs;
       for (const auto& rg : ranges) if (rg.second - 1 - st >= rg.first) cs.push_back(rg.second - 1 - st);
       if (cs.empty()) break;
-      steps[i].push_back(cs);
+      t.steps[i].push_back(cs);
     }
-    // Sigma, Z; the border map (border coordinate past the windows -> row of the separator's Sigma) and the pose rows
+    Y.push_back(y);
+    // the border map (border coordinate past the windows -> row of the separator's system) and the pose rows
+    const int gn = (nbr - nsep) * NB, m = g->h_sep_off.empty() ? 0 : g->h_sep_off.back();
+    std::vector<int>& mp = t.map[i];
+    mp.assign(std::max(gn, 1), -1);
+    for (size_t c = 0; c < g->h_sep_map.size(); ++c) {
+      const int o = g->h_sep_map[c] - nsep * NB;
+      if (o >= 0 && o < gn) mp[o] = (int)c < m ? (int)c : Ts * NB + ((int)c - m);
+    }
+    std::vector<int>& prow = t.prow[i];
+    prow.assign(std::max<size_t>(G.P, 1), 0);
+    for (int p = 0; p < G.P; ++p)
+      prow[p] = (size_t)p < g->h_pose_sep.size() && g->h_pose_sep[p] >= 0 ? T * NB + g->h_pose_sep[p] : 6 * p;
+    t.T[i] = T; t.Tc[i] = Tc; t.Trow[i] = Trow; t.gn[i] = gn;
+  }
+}
+// Sigma of the separator system and of every robot's band + border, computed once per exact pass (joint_state first: the buffers hold
+// that pass's factor and hG / the graphs' host tables describe it).  Scratch (Z, the row lists, the border maps) lives only in here.
+int CholBatch::ensure_joint_sigma() {
+  if (jsig_serial == exact_serial && jsig_sep) return SLIDE_OK;
+  free_joint_sigma();
+  hipStream_t s = master;
+  JointTree t;
+  joint_tree(t);
+  const int Tsep = t.Tsep;
+  std::vector<JSinvSys>& Y = t.Y;
+  const std::vector<int>& rp = t.rp;
+  const std::vector<int>& rows = t.rows;
+  const std::vector<std::vector<std::vector<int>>>& steps = t.steps;      // per robot: the columns of each backward step
+  std::vector<double*> Zs;
+  auto cleanup = [&]() { for (double* z : Zs) if (z) (void)hipFree(z); };
+  JSigGather gA{};
+  std::vector<int*> maps(n, nullptr);
+  int max_gn = 0;
+  jsig_rob.assign(n, nullptr); jsig_prow.assign(n, nullptr); jsig_lds.assign(n, 0);
+  for (int i = 0; i < n; ++i) {
+    JSinvSys& y = Y[1 + i];
+    const int Tc = t.Tc[i], gn = t.gn[i];
+    // Sigma, Z; the border map and the pose rows
     const size_t nsg = (size_t)y.lds * y.lds, nz = (size_t)y.lds * Tc * NB;
     double* Z = nullptr;
     SL_HIP(hipMalloc(reinterpret_cast<void**>(&jsig_rob[i]), nsg * sizeof(double)));
@@ -3455,16 +3501,8 @@ int CholBatch::ensure_joint_sigma() {
     SL_HIP(hipMemsetAsync(jsig_rob[i], 0, nsg * sizeof(double), s));
     y.Sg = jsig_rob[i]; y.Z = Z;
     jsig_lds[i] = y.lds;
-    Y.push_back(y);
-    const int gn = (nbr - nsep) * NB, m = g->h_sep_off.empty() ? 0 : g->h_sep_off.back();
-    std::vector<int> mp(std::max(gn, 1), -1);
-    for (size_t c = 0; c < g->h_sep_map.size(); ++c) {
-      const int o = g->h_sep_map[c] - nsep * NB;
-      if (o >= 0 && o < gn) mp[o] = (int)c < m ? (int)c : Ts * NB + ((int)c - m);
-    }
-    std::vector<int> prow(std::max<size_t>(G.P, 1), 0);
-    for (int p = 0; p < G.P; ++p)
-      prow[p] = (size_t)p < g->h_pose_sep.size() && g->h_pose_sep[p] >= 0 ? T * NB + g->h_pose_sep[p] : 6 * p;
+    const std::vector<int>& mp = t.map[i];
+    const std::vector<int>& prow = t.prow[i];
     if (hipMalloc(reinterpret_cast<void**>(&maps[i]), mp.size() * sizeof(int)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&jsig_prow[i]), prow.size() * sizeof(int)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
     SL_HIP(hipMemcpyAsync(maps[i], mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice, s));
@@ -3670,4 +3708,313 @@ int CholBatch::joint_marginal_traces(int slot, double* out4) {
   return SLIDE_OK;
 }
 
+
+// estimateClosureInfoGain (graph.cpp:469-623) on the joint graph (graph.cpp:325-371: every replica holds the whole multi-robot graph),
+// in the linear-Gaussian model of the last exact pass's factor K = L D L^T, as the single-graph call: U = K^-1 J^T by substitutions with
+// 6m right-hand sides through the pass's elimination tree (joint_cov_kernels.hip's k_jms_*), C = I + J U, the drops tr(C^-1 U_P^T U_P).
+// A candidate's endpoints may sit in different robots' graphs (a rendezvous); J is taken at the graphs' pose_val, the pass's
+// linearisation point.  Every system's U lives in one buffer (robots first, then the separator; leading dimension N), so the grams run
+// over row lists of it.  Nothing the pass reads is written and the cached joint Sigma is left as it was.
+int CholBatch::joint_closure_info_gain(int slot, const int32_t* traj_slots, const uint64_t* traj, int n_q, const double* travel,
+                                       const double* sigma6, double* out4) {
+  for (int i = 0; i < 4; ++i) out4[i] = 0.0;
+  const int m = n_q - 1;
+  if (m < 1 || !traj || !travel) { g_last_error = "closure_info_gain: the trajectory needs at least two poses"; return SLIDE_ERR_INVALID; }
+  if (m > SLIDE_INFO_GAIN_MAX_STEPS) { g_last_error = "closure_info_gain: more than SLIDE_INFO_GAIN_MAX_STEPS steps"; return SLIDE_ERR_CAPACITY; }
+  for (int i = 0; i < m; ++i)
+    if (!(travel[i] > 0.0) || !std::isfinite(travel[i])) { g_last_error = "closure_info_gain: travel distances must be > 0"; return SLIDE_ERR_INVALID; }
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("closure_info_gain", slot);
+  if (rc != SLIDE_OK) return rc;
+  if (!sigma6) sigma6 = graphs[slot]->P.noise_model_odom_vec;
+  for (int a = 0; a < 6; ++a)
+    if (!(sigma6[a] > 0.0) || !std::isfinite(sigma6[a])) { g_last_error = "closure_info_gain: sigma_per_m must be > 0"; return SLIDE_ERR_INVALID; }
+  std::vector<int> qs(n_q), ids(n_q);
+  for (int q = 0; q < n_q; ++q) {
+    const int sl = traj_slots ? traj_slots[q] : slot;
+    if (sl < 0 || sl >= n) { g_last_error = "closure_info_gain: no such slot in traj_slots"; return SLIDE_ERR_INVALID; }
+    const HostGraph* g = graphs[sl];
+    auto it = g->key2pose.find(HostGraph::pose_key(joint_robot(sl), traj[q]));
+    if (it == g->key2pose.end() || (size_t)it->second >= g->up_P) return SLIDE_MISSING;
+    qs[q] = sl; ids[q] = it->second;
+  }
+  hipStream_t s = master;
+  const int ncol = 6 * m;
+  JointTree t;
+  joint_tree(t);
+  const int Tsep = t.Tsep;
+  // the rows of every system in the buffers S (solutions, U at the end) and R (right-hand sides)
+  std::vector<size_t> off(n + 1);
+  size_t N = 0;
+  for (int i = 0; i < n; ++i) { off[1 + i] = N; N += (size_t)t.Trow[i] * NB; }
+  off[0] = N; N += (size_t)Tsep * NB;
+  auto prow_of = [&](int sl, int p) { return (int)off[1 + sl] + t.prow[sl][p]; };
+  // J^T, entry by entry (row of X, column 6 i + a); a repeated pose sums its blocks
+  std::vector<double> val(12 * (size_t)n_q);
+  for (int q = 0; q < n_q; ++q)
+    SL_HIP(hipMemcpyAsync(val.data() + 12 * q, hG[qs[q]].pose_val + 12 * (size_t)ids[q], 12 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  std::map<std::pair<int, int>, double> jt;
+  std::unordered_map<int, int> row_of;      // row of X -> 6 (trajectory slot) + coordinate
+  for (int q = 0; q < n_q; ++q)
+    for (int a = 0; a < 6; ++a) row_of.emplace(prow_of(qs[q], ids[q]) + a, 6 * q + a);
+  for (int i = 0; i < m; ++i) {
+    double Ad[6][6];
+    between_adjoint(val.data() + 12 * (i + 1), val.data() + 12 * i, Ad);      // (c_{i+1}, c_i)
+    const int ra = prow_of(qs[i + 1], ids[i + 1]), rb = prow_of(qs[i], ids[i]);
+    for (int a = 0; a < 6; ++a) {
+      const double w = 1.0 / (sigma6[a] * travel[i]);
+      for (int c = 0; c < 6; ++c) jt[{ra + c, 6 * i + a}] += -Ad[a][c] * w;
+      jt[{rb + a, 6 * i + a}] += w;
+    }
+  }
+  std::vector<int> rcv;
+  std::vector<double> vv;
+  for (const auto& kv : jt) { rcv.push_back(kv.first.first); rcv.push_back(kv.first.second); vv.push_back(kv.second); }
+  const int ne = (int)vv.size();
+  // the solve's schedule.  Nodes: a robot's band segments (level 0), its windows (1), its rows of separator coordinates (2, no columns);
+  // the separator's leaves (3), its top block with the lambda block (4; all of it when the separator is not dissected)
+  const int NS = 1 + n;
+  std::vector<std::vector<int>> node(NS);
+  for (int i = 0; i < n; ++i) {
+    node[1 + i].assign(t.Trow[i], 2000);
+    for (size_t q = 0; q < t.ranges[i].size(); ++q)
+      for (int k = t.ranges[i][q].first; k < t.ranges[i][q].second; ++k) node[1 + i][k] = (int)q;
+    for (int k = t.T[i]; k < t.Tc[i]; ++k) node[1 + i][k] = 1000;
+  }
+  node[0].assign(Tsep, 4000);
+  for (int k = 0; k < t.sTL; ++k) node[0][k] = k < t.sTa ? 3000 : 3001;
+  auto level = [](int nd) { return nd < 1000 ? 0 : nd / 1000; };
+  auto ncols = [&](int sy) { return sy == 0 ? Tsep : t.Tc[sy - 1]; };
+  // per system and tile: the forward push rows (same node), backward push columns (same node, transposed), forward pull columns
+  // (nodes below), backward pull rows (nodes above)
+  std::vector<std::vector<std::vector<int>>> fpush(NS), bpush(NS), fpull(NS), bpull(NS);
+  for (int sy = 0; sy < NS; ++sy) {
+    const int nt = (int)node[sy].size();
+    fpush[sy].assign(nt, {}); bpush[sy].assign(nt, {}); fpull[sy].assign(nt, {}); bpull[sy].assign(nt, {});
+    for (int c = 0; c < ncols(sy); ++c) {
+      const int b = t.Y[sy].col0 + c;
+      for (int q = t.rp[b]; q < t.rp[b + 1]; ++q) {
+        const int i = t.rows[q];
+        if (node[sy][i] == node[sy][c]) { fpush[sy][c].push_back(i); bpush[sy][i].push_back(c); }
+        else { fpull[sy][i].push_back(c); bpull[sy][c].push_back(i); }
+      }
+    }
+  }
+  std::vector<int4> jobs;
+  std::vector<int> lst;
+  struct Launch { int kind, bwd, j0, nj, maxl; };      // kind 0: push, 1: pull, 2: sum, 3: gather
+  std::vector<Launch> plan;
+  auto add_job = [&](int sy, int k, const std::vector<int>& l) {
+    jobs.push_back(make_int4(sy, k, (int)lst.size(), (int)(lst.size() + l.size())));
+    lst.insert(lst.end(), l.begin(), l.end());
+    return (int)l.size();
+  };
+  // a push launch: the columns cols (system, column) side by side
+  auto push = [&](const std::vector<std::pair<int, int>>& cols, bool bwd) {
+    if (cols.empty()) return;
+    Launch L{0, bwd, (int)jobs.size(), 0, 0};
+    for (const auto& sc : cols) L.maxl = std::max(L.maxl, add_job(sc.first, sc.second, (bwd ? bpush : fpush)[sc.first][sc.second]));
+    L.nj = (int)jobs.size() - L.j0;
+    plan.push_back(L);
+  };
+  // a pull launch over the tiles of the given level (forward, a tile with nothing to take is left out; backward, every column starts
+  // its right-hand side there: R_k = D_k S_k - ..)
+  auto pull = [&](int lev, bool bwd) {
+    Launch L{1, bwd, (int)jobs.size(), 0, 0};
+    for (int sy = 0; sy < NS; ++sy)
+      for (int k = 0; k < (int)node[sy].size(); ++k) {
+        if (level(node[sy][k]) != lev || (bwd && k >= ncols(sy))) continue;
+        const std::vector<int>& l = (bwd ? bpull : fpull)[sy][k];
+        if (l.empty() && !bwd) continue;
+        add_job(sy, k, l);
+      }
+    L.nj = (int)jobs.size() - L.j0;
+    if (L.nj > 0) plan.push_back(L);
+  };
+  auto robot_band_steps = [&](bool bwd) {
+    int nst = 0;
+    for (int i = 0; i < n; ++i) for (const auto& rg : t.ranges[i]) nst = std::max(nst, rg.second - rg.first);
+    for (int st = 0; st < nst; ++st) {
+      std::vector<std::pair<int, int>> cols;
+      for (int i = 0; i < n; ++i)
+        for (const auto& rg : t.ranges[i])
+          if (st < rg.second - rg.first) cols.emplace_back(1 + i, bwd ? rg.second - 1 - st : rg.first + st);
+      push(cols, bwd);
+    }
+  };
+  auto robot_window_steps = [&](bool bwd) {
+    int nst = 0;
+    for (int i = 0; i < n; ++i) nst = std::max(nst, t.Tc[i] - t.T[i]);
+    for (int st = 0; st < nst; ++st) {
+      std::vector<std::pair<int, int>> cols;
+      for (int i = 0; i < n; ++i)
+        if (st < t.Tc[i] - t.T[i]) cols.emplace_back(1 + i, bwd ? t.Tc[i] - 1 - st : t.T[i] + st);
+      push(cols, bwd);
+    }
+  };
+  auto leaf_steps = [&](bool bwd) {
+    const int na = t.sTa, nb = t.sTL > 0 ? t.sTL - t.sTa : 0;
+    if (t.sTL == 0) return;
+    for (int st = 0; st < std::max(na, nb); ++st) {
+      std::vector<std::pair<int, int>> cols;
+      if (st < na) cols.emplace_back(0, bwd ? na - 1 - st : st);
+      if (st < nb) cols.emplace_back(0, bwd ? t.sTL - 1 - st : na + st);
+      push(cols, bwd);
+    }
+  };
+  auto top_steps = [&](bool bwd) {
+    for (int st = 0; st < Tsep - t.sTL; ++st) push({{0, bwd ? Tsep - 1 - st : t.sTL + st}}, bwd);
+  };
+  robot_band_steps(false);
+  pull(1, false); robot_window_steps(false);
+  pull(2, false);
+  plan.push_back({2, 0, 0, 0, 0});
+  leaf_steps(false);
+  pull(4, false); top_steps(false);
+  pull(4, true); top_steps(true);
+  pull(3, true); leaf_steps(true);
+  plan.push_back({3, 0, 0, 0, 0});
+  pull(1, true); robot_window_steps(true);
+  pull(0, true); robot_band_steps(true);
+  // the separator's rows from the robots' (the inverse of the border maps, robot order)
+  std::vector<std::vector<int2>> inv(Tsep * NB);
+  int max_gn = 0;
+  for (int i = 0; i < n; ++i) {
+    for (int o = 0; o < t.gn[i]; ++o)
+      if (t.map[i][o] >= 0) inv[t.map[i][o]].push_back(make_int2(i, t.Tc[i] * NB + o));
+    max_gn = std::max(max_gn, t.gn[i]);
+  }
+  std::vector<int> sptr{0};
+  std::vector<int2> sent;
+  for (const auto& v : inv) { sent.insert(sent.end(), v.begin(), v.end()); sptr.push_back((int)sent.size()); }
+  // the grams' row lists: the poses of the robot in `slot`, of every robot, the job's shared point landmarks (each slot once); the
+  // private point landmarks of every graph (k_lm_V on its robot's rows)
+  std::vector<int> rows_slot, rows_all, rows_sh, lms, lm0(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    std::vector<int> poses;
+    graphs[i]->robot_poses(joint_robot(i), poses);
+    for (int p : poses)
+      for (int a = 0; a < 6; ++a) {
+        rows_all.push_back(prow_of(i, p) + a);
+        if (i == slot) rows_slot.push_back(prow_of(i, p) + a);
+      }
+  }
+  std::vector<char> seen;
+  for (int i = 0; i < n; ++i) {
+    const HostGraph* g = graphs[i];
+    for (size_t l = 0; l < g->up_L && l < g->h_lm_type.size(); ++l)
+      if (g->h_lm_type[l] == VT_POINT && !(l < g->h_lm_bord.size() && g->h_lm_bord[l] >= 0)) lms.push_back((int)l);
+    lm0[i + 1] = (int)lms.size();
+    seen.resize(std::max(seen.size(), g->h_sh_lid.size()), 0);
+    for (size_t k = 0; k < g->h_sh_lid.size(); ++k) {
+      const int l = g->h_sh_lid[k];
+      if (l < 0 || (size_t)l >= g->up_L || g->h_lm_type[l] != VT_POINT || seen[k]) continue;
+      seen[k] = 1;
+      for (int a = 0; a < 3; ++a) rows_sh.push_back((int)off[0] + g->h_sep_off[k] + a);
+    }
+  }
+  const size_t nl = lms.size(), ldv = std::max<size_t>(9 * nl, 1);
+  // device scratch of this query (freed before it returns)
+  std::vector<void*> bufs;
+  bool oom = false;
+  auto dalloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) { oom = true; return nullptr; }
+    bufs.push_back(p);
+    return p;
+  };
+  auto release = [&]() { for (void* p : bufs) (void)hipFree(p); bufs.clear(); };
+  double* X = static_cast<double*>(dalloc(N * ncol * sizeof(double)));
+  double* Rb = static_cast<double*>(dalloc(N * ncol * sizeof(double)));
+  double* V = static_cast<double*>(dalloc(ldv * ncol * sizeof(double)));
+  double* Md = static_cast<double*>(dalloc(4 * (size_t)ncol * ncol * sizeof(double)));
+  JSinvSys* d_sys = static_cast<JSinvSys*>(dalloc(NS * sizeof(JSinvSys)));
+  int4* d_jobs = static_cast<int4*>(dalloc(jobs.size() * sizeof(int4)));
+  int2* d_sent = static_cast<int2*>(dalloc(sent.size() * sizeof(int2)));
+  const size_t ni = lst.size() + sptr.size() + 2 * (size_t)ne + rows_slot.size() + rows_all.size() + rows_sh.size() + nl;
+  int* d_i = static_cast<int*>(dalloc(ni * sizeof(int)));
+  std::vector<int*> d_prow(n, nullptr), d_map(n, nullptr);
+  for (int i = 0; i < n; ++i) {
+    d_prow[i] = static_cast<int*>(dalloc(t.prow[i].size() * sizeof(int)));
+    d_map[i] = static_cast<int*>(dalloc(t.map[i].size() * sizeof(int)));
+  }
+  double* d_val = static_cast<double*>(dalloc(std::max(ne, 1) * sizeof(double)));
+  if (oom) { (void)hipGetLastError(); release(); g_last_error = "closure_info_gain: out of device memory"; return SLIDE_ERR_HIP; }
+  for (int sy = 0; sy < NS; ++sy) { t.Y[sy].Sg = X + off[sy]; t.Y[sy].Z = Rb + off[sy]; t.Y[sy].lds = (long long)N; }
+  int* d_lst = d_i;
+  int* d_sptr = d_lst + lst.size();
+  int* d_rc = d_sptr + sptr.size();
+  int* d_rslot = d_rc + 2 * ne;
+  int* d_rall = d_rslot + rows_slot.size();
+  int* d_rsh = d_rall + rows_all.size();
+  int* d_lms = d_rsh + rows_sh.size();
+  hipError_t e = hipMemsetAsync(X, 0, N * ncol * sizeof(double), s);
+  if (e == hipSuccess) e = hipMemsetAsync(Rb, 0, N * ncol * sizeof(double), s);
+  auto up = [&](void* dst, const void* src, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); };
+  up(d_sys, t.Y.data(), NS * sizeof(JSinvSys));
+  up(d_jobs, jobs.data(), jobs.size() * sizeof(int4));
+  up(d_sent, sent.data(), sent.size() * sizeof(int2));
+  up(d_lst, lst.data(), lst.size() * sizeof(int));
+  up(d_sptr, sptr.data(), sptr.size() * sizeof(int));
+  up(d_rc, rcv.data(), rcv.size() * sizeof(int));
+  up(d_rslot, rows_slot.data(), rows_slot.size() * sizeof(int));
+  up(d_rall, rows_all.data(), rows_all.size() * sizeof(int));
+  up(d_rsh, rows_sh.data(), rows_sh.size() * sizeof(int));
+  up(d_lms, lms.data(), nl * sizeof(int));
+  up(d_val, vv.data(), ne * sizeof(double));
+  for (int i = 0; i < n; ++i) { up(d_prow[i], t.prow[i].data(), t.prow[i].size() * sizeof(int)); up(d_map[i], t.map[i].data(), t.map[i].size() * sizeof(int)); }
+  if (e != hipSuccess) { (void)hipStreamSynchronize(s); release(); SL_HIP(e); }
+  // R = J^T, then X = K^-1 R in S
+  launch_scatter(d_rc, d_val, ne, Rb, (int)N, s);
+  JMSum sA{};
+  JSigGather gA{};
+  for (int i = 0; i < n; ++i) {
+    sA.src[i] = Rb + off[1 + i];
+    gA.dst[i] = X + off[1 + i]; gA.map[i] = d_map[i]; gA.lds[i] = (long long)N; gA.o0[i] = t.Tc[i] * NB; gA.n[i] = t.gn[i];
+  }
+  sA.dst = Rb + off[0]; sA.ld = (long long)N;
+  gA.src = X + off[0]; gA.lds_src = (long long)N;
+  for (const Launch& L : plan) {
+    if (L.kind == 0) launch_jms_push(d_sys, d_jobs + L.j0, L.nj, L.maxl, d_lst, ncol, L.bwd, s);
+    else if (L.kind == 1) launch_jms_pull(d_sys, d_jobs + L.j0, L.nj, d_lst, ncol, L.bwd, s);
+    else if (L.kind == 2) launch_jms_sum(sA, d_sptr, d_sent, Tsep * NB, ncol, s);
+    else launch_jms_gather(gA, n, max_gn, ncol, s);
+  }
+  // the grams: poses of `slot`, poses of every robot, private point landmarks (through V), shared point landmarks
+  double* Mp = Md;
+  launch_gram(X, N, ncol, d_rslot, (int)rows_slot.size(), Mp, s);
+  launch_gram(X, N, ncol, d_rall, (int)rows_all.size(), Mp + (size_t)ncol * ncol, s);
+  for (int i = 0; i < n; ++i)
+    launch_landmark_V(hG[i], X + off[1 + i], (int)N, ncol, d_lms + lm0[i], lm0[i + 1] - lm0[i], V + 9 * (size_t)lm0[i], ldv, s, d_prow[i]);
+  launch_gram(V, ldv, ncol, nullptr, (int)(9 * nl), Mp + 2 * (size_t)ncol * ncol, s);
+  launch_gram(X, N, ncol, d_rsh, (int)rows_sh.size(), Mp + 3 * (size_t)ncol * ncol, s);
+  // the rows of U at the trajectory's poses (for C = I + J U)
+  std::vector<double> M(4 * (size_t)ncol * ncol), Urow((size_t)n_q * 6 * ncol);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(M.data(), Md, M.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+  for (int q = 0; q < n_q && e == hipSuccess; ++q)
+    e = hipMemcpy2DAsync(Urow.data() + (size_t)q * 6 * ncol, 6 * sizeof(double), X + prow_of(qs[q], ids[q]), N * sizeof(double),
+                         6 * sizeof(double), ncol, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  release();
+  SL_HIP(e);
+  SL_HIP(e2);
+  std::vector<double> Cm((size_t)ncol * ncol, 0.0);
+  for (int a = 0; a < ncol; ++a) Cm[(size_t)a * ncol + a] = 1.0;
+  for (size_t k = 0; k < vv.size(); ++k) {          // (J U)[jrow][col] += J[jrow][row] U[row][col]
+    const int row = rcv[2 * k], jrow = rcv[2 * k + 1];
+    const int qa = row_of[row];
+    const double* u = Urow.data() + (size_t)(qa / 6) * 6 * ncol + qa % 6;
+    for (int c = 0; c < ncol; ++c) Cm[(size_t)jrow * ncol + c] += vv[k] * u[6 * (size_t)c];
+  }
+  const double* Ms[4] = {M.data(), M.data() + (size_t)ncol * ncol, M.data() + 2 * (size_t)ncol * ncol, M.data() + 3 * (size_t)ncol * ncol};
+  double gs[4];
+  if ((rc = woodbury_drops(Cm, ncol, Ms, 4, gs)) != SLIDE_OK) return rc;
+  out4[1] = gs[0];
+  out4[2] = gs[2] + gs[3];
+  out4[0] = 10.0 * out4[1] + out4[2];
+  out4[3] = gs[1];
+  return SLIDE_OK;
+}
 }  // namespace sl

@@ -195,6 +195,11 @@ class CholBatch {
   int joint_pose_covariances(int slot, const uint64_t* idx, int n, double* out36n);
   int joint_landmark_covariances(int slot, int cls, const uint64_t* idx, int n, double* out);
   int joint_marginal_traces(int slot, double* out4);
+  // estimateClosureInfoGain on the JOINT graph (the same factor): Between factors (traj[q + 1], traj[q]), pose q of the graph in
+  // traj_slots[q] (null: all in `slot`); out4 = {10 pose + landmark, the robot of `slot`'s pose drop, the job's point landmarks' drop,
+  // every robot's pose drop}
+  int joint_closure_info_gain(int slot, const int32_t* traj_slots, const uint64_t* traj, int n, const double* travel, const double* sigma6,
+                              double* out4);
 
  private:
   int n;
@@ -311,6 +316,18 @@ class CholBatch {
   void free_joint_sigma();
   int joint_state(const char* who, int slot);      // SLIDE_ERR_INVALID (+ message) unless the last exact pass's factor is resident
   int ensure_joint_sigma();
+  // the exact joint pass's elimination tree (system 0: the separator, 1 + i: robot i): every system's JSinvSys (Sg, Z left null, lds its
+  // rows), the tile rows of every column, and per robot its backward steps, segments, border map and pose rows
+  struct JointTree {
+    std::vector<JSinvSys> Y;
+    std::vector<int> rp{0}, rows;
+    std::vector<std::vector<std::vector<int>>> steps;          // per robot: the columns of each step of the backward recursion
+    std::vector<std::vector<std::pair<int, int>>> ranges;      // per robot: the band's column ranges factored side by side
+    std::vector<int> T, Tc, Trow, gn;                          // per robot: band, factor columns, rows; rows of separator coordinates past Tc NB
+    std::vector<std::vector<int>> map, prow;                   // per robot: border coordinate -> separator row (-1: padding); a pose's first row
+    int Ts = 0, Tsep = 0, sTa = 0, sTL = 0;                    // separator: landmark tiles, all tiles, end of leaf a, end of leaf b (0: not dissected)
+  };
+  void joint_tree(JointTree& t) const;
   int joint_robot(int slot) const;                 // robot id of the graph's own poses
 };
 

@@ -118,7 +118,8 @@ void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, co
 void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* X,
                         int nrhs, hipStream_t s);      // X = S^-1 B (B: nrhs columns of T * NB rows, overwritten)
 void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nrows, double* M, hipStream_t s);
-void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s);
+void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s,
+                       const int* prow = nullptr);      // prow: a pose's first row in U (null: 6 p)
 void launch_scatter(const int* rc, const double* val, int n, double* B, int nT, hipStream_t s);
 // joint_cov_kernels.hip — the selected inverse over the exact joint pass's elimination tree (CholBatch::ensure_joint_sigma).  One system:
 // factor columns [0, Tb) in S (ld; rows past Tb = its stored border rows), [Tb, Tc) in B (ldb, rows and columns counted from Tb); their
@@ -134,6 +135,16 @@ void launch_jsinv_prep(const JSinvSys* d_sys, const int2* d_jobs, int njobs, int
 void launch_jsinv_step(const JSinvSys* d_sys, const int2* d_jobs, int njobs, int max_rows, const int* d_rp, const int* d_rows, hipStream_t s);   // two launches
 void launch_jsig_gather(const JSigGather& A, int n_robots, int max_n, hipStream_t s);
 void launch_sym_blocks(const double* Sg, size_t ld, const int* row0, const int* dim, int n, double* out, hipStream_t s);      // out: 81 per block (d x d used)
+// X = K^-1 B over the same tree (CholBatch::joint_closure_info_gain): every system's right-hand sides R (JSinvSys::Z, B to start with)
+// and solutions S (JSinvSys::Sg, X at the end) in column-major buffers with leading dimension lds.  Jobs {system, tile, list begin, list
+// end}.  push: one column of each job's node, applied to the list's rows (forward) / columns (backward) of that node; pull: the rows of
+// the nodes below (forward) / above (backward) a tile, the backward one with the D step.  sum: separator rows of R from the robots'
+// (CSR of (robot, row) per separator row).  gather: the robots' rows of separator coordinates of S from the separator's.
+struct JMSum { const double* src[JSIG_ROBOTS_MAX]; double* dst; long long ld; };
+void launch_jms_push(const JSinvSys* d_sys, const int4* d_jobs, int njobs, int max_list, const int* d_list, int ncol, bool bwd, hipStream_t s);
+void launch_jms_pull(const JSinvSys* d_sys, const int4* d_jobs, int njobs, const int* d_list, int ncol, bool bwd, hipStream_t s);
+void launch_jms_sum(const JMSum& A, const int* d_ptr, const int2* d_ent, int nrows, int ncol, hipStream_t s);
+void launch_jms_gather(const JSigGather& A, int n_robots, int max_n, int ncol, hipStream_t s);      // dst[r][o0 + a] = src[map[r][a]], every column
 // stand-alone dense SPD solve on device buffers (used by the unit tests and the roofline bench leg)
 void launch_chol_solve_bwd(const CholSystem& cs, hipStream_t s);   // yv -> dp after launch_chol_extract_y: one-workgroup substitution for narrow profiles, else the chained kernel
 int chol_factor_solve(double* S, int ld, int T, double* Ld, double* Winv, double* yv, double* dp, int* status, int* ctr, hipStream_t s);

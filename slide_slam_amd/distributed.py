@@ -679,6 +679,12 @@ class PassDriver:
         self._joint_ok()
         return self.batch.marginal_traces(robot)
 
+    def closure_info_gain(self, robot, traj, travel, sigma_per_m=None, traj_robots=None):
+        """estimateClosureInfoGain on the joint graph for robot `robot`: [10 pose + landmark, its pose drop, the job's point-landmark
+        drop, every robot's pose drop]; traj_robots[q] = the robot of pose traj[q] (None: all `robot`; another robot: a rendezvous)."""
+        self._joint_ok()
+        return self.batch.closure_info_gain(robot, traj, travel, sigma_per_m, traj_robots)
+
     def one_pass(self):
         n54, n9, K = 54 * self.n_slots, 9 * self.n_slots, self.pcg_iters
         if self.batch is not None:
