@@ -29,6 +29,7 @@ SOURCES = [
     ("place_kernels.hip", ["-ffp-contract=off"]),
     ("clipper_kernels.hip", ["-ffp-contract=off"]),
     ("host_graph.hip", ["-ffp-contract=off"]),
+    ("host_marginals.hip", ["-ffp-contract=off"]),     # (its Woodbury step runs on the host: same rounding as host_graph.hip)
     ("host_backend.hip", ["-ffp-contract=off"]),
     ("capi.hip", ["-ffp-contract=off"]),
     ("wire.hip", ["-ffp-contract=off"]),     # host code only: sloam_msgs wire codec + rosbag reader (include/slide_wire.h)

@@ -142,7 +142,6 @@ int HostGraph::init() {
   return SLIDE_OK;
 }
 
-static bool robot_ok(int r) { return r >= 0 && r < SLIDE_MAX_ROBOTS; }
 static void put12(const SE3& T, double* z) { to12(T, z); }
 
 int HostGraph::set_prior(int robot, const double* pose7) {
@@ -3018,1003 +3017,12 @@ void HostGraph::set_dense_profile(bool on) {
   force_dense = on;
   topo_dirty = true;
 }
-// ---- marginals and loop-closure information gain (logEntropy / estimateClosureInfoGain, graph.cpp:421-625) -----------------------
-// Single-graph path only: a shard's factor (ghost factors, shared-landmark slots) or a factor shared with a CholBatch is not the
-// system of this graph alone.
-int HostGraph::marginal_state(const char* who) const {
-  if (batch || arrow_on() || up_gh > 0 || !h_gslot_pose.empty() || !h_sh_lid.empty()) {
-    g_last_error = std::string(who) + ": marginals are served on the single-graph path only (not in sharded or exact-joint mode)";
-    return SLIDE_ERR_INVALID;
-  }
-  if (!factor_valid || G.T == 0) { g_last_error = std::string(who) + ": no factorisation yet (call solve first)"; return SLIDE_ERR_INVALID; }
-  // factors or variables merged since the last solve (any call that uploads pending additions) change the system the device buffers
-  // describe — and may re-allocate S, Ld and Winv, or grow ld — while the resident factor is still the old one's
-  size_t now[8];
-  fact_shape_now(now);
-  if (fact_gen != S_gen || std::memcmp(now, fact_shape, sizeof(now)) != 0) {
-    g_last_error = std::string(who) + ": the graph changed since the last solve (call solve first)";
-    return SLIDE_ERR_INVALID;
-  }
-  return SLIDE_OK;
-}
-void HostGraph::fact_shape_now(size_t* out) const {
-  const size_t v[8] = {(size_t)G.T, (size_t)G.ld, up_P, up_L, up_pr, up_bt, up_lf, up_gh};
-  std::memcpy(out, v, sizeof(v));
-}
-// the selected inverse of the resident factor, computed once per factorisation
-// (marginal_state first: the factor is the one of the uploaded system, so G.T / G.ld are its geometry)
-int HostGraph::ensure_sigma() {
-  if (sig_serial == fact_serial && sig_T == G.T && sig_ld == G.ld) return SLIDE_OK;
-  hipStream_t s = stream;
-  const size_t n = (size_t)G.ld * G.T * NB;
-  sig_serial = ~0ull;
-  if (d_sig.cap != n && d_sig.ensure_exact(n, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-  DevArr<double> Z;      // Z_I = L_Ik L_kk^-1 of the recursion: only while it runs (freed at the end of this scope, after a sync)
-  if (Z.ensure_exact(n, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-  const bool dense = h_prof.size() != (size_t)G.T;
-  launch_selected_inverse(G.S, G.ld, G.T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), dense ? nullptr : G.prof, d_sig.d, Z.d, s);
-  SL_HIP(hipGetLastError());
-  SL_HIP(hipStreamSynchronize(s));
-  sig_serial = fact_serial;
-  sig_T = G.T;
-  sig_ld = G.ld;
-  return SLIDE_OK;
-}
-void HostGraph::robot_poses(int robot, std::vector<int>& out) const {
-  out.clear();
-  const uint64_t tag = pose_key(robot, 0) >> 56;
-  for (const auto& kv : key2pose)
-    if ((kv.first >> 56) == tag && (size_t)kv.second < up_P) out.push_back(kv.second);
-  std::sort(out.begin(), out.end());
-}
-void HostGraph::point_landmarks(std::vector<int>& out) const {
-  out.clear();
-  for (size_t l = 0; l < up_L && l < h_lm_type.size(); ++l)
-    if (h_lm_type[l] == VT_POINT) out.push_back((int)l);
-}
-// isam->marginalCovariance(X(idx)) for n poses of one robot: out36n[36 q ..] row-major, tangent order [rot, trans]
-int HostGraph::pose_covariances(int robot, const uint64_t* idx, int n, double* out36n) {
-  if (!robot_ok(robot) || n < 0 || (n > 0 && (!idx || !out36n))) return SLIDE_ERR_INVALID;
-  for (int i = 0; i < 36 * n; ++i) out36n[i] = 0.0;
-  int rc = marginal_state("get_pose_covariances");
-  if (rc != SLIDE_OK) return rc;
-  std::vector<int> ids(n);
-  for (int q = 0; q < n; ++q) {
-    auto it = key2pose.find(pose_key(robot, idx[q]));
-    if (it == key2pose.end() || (size_t)it->second >= up_P) return SLIDE_MISSING;
-    ids[q] = it->second;
-  }
-  if (n == 0) return SLIDE_OK;
-  if ((rc = ensure_sigma()) != SLIDE_OK) return rc;
-  hipStream_t s = stream;
-  if (d_midx.ensure(n, 0, s) != SLIDE_OK || d_mout.ensure(36 * (size_t)n, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-  SL_HIP(hipMemcpyAsync(d_midx.d, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
-  launch_pose_blocks(d_sig.d, G.ld, d_midx.d, n, d_mout.d, s);
-  SL_HIP(hipMemcpyAsync(out36n, d_mout.d, 36 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  SL_HIP(hipGetLastError());
-  return SLIDE_OK;
-}
-// isam->marginalCovariance(L / C / U(idx)) for n landmarks of one class: d x d each (d = 7 / 9 / 3), tangent order of var_retract
-int HostGraph::landmark_covariances(int cls, const uint64_t* idx, int n, double* out) {
-  if ((cls != SLIDE_CLS_CYLINDER && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_ELLIPSOID) || n < 0 || (n > 0 && (!idx || !out)))
-    return SLIDE_ERR_INVALID;
-  const int d = cls == SLIDE_CLS_CYLINDER ? 7 : (cls == SLIDE_CLS_CUBE ? 9 : 3);
-  for (int i = 0; i < d * d * n; ++i) out[i] = 0.0;
-  int rc = marginal_state("get_landmark_covariances");
-  if (rc != SLIDE_OK) return rc;
-  std::vector<int> ids(n);
-  for (int q = 0; q < n; ++q)
-    if ((ids[q] = lm_lid(cls, idx[q])) < 0) return SLIDE_MISSING;
-  if (n == 0) return SLIDE_OK;
-  if ((rc = ensure_sigma()) != SLIDE_OK) return rc;
-  hipStream_t s = stream;
-  if (d_midx.ensure(n, 0, s) != SLIDE_OK || d_mout.ensure(81 * (size_t)n, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-  SL_HIP(hipMemcpyAsync(d_midx.d, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
-  launch_landmark_covariances(G, d_sig.d, G.ld, d_midx.d, n, d_mout.d, s);
-  std::vector<double> h(81 * (size_t)n);
-  SL_HIP(hipMemcpyAsync(h.data(), d_mout.d, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  SL_HIP(hipGetLastError());
-  for (int q = 0; q < n; ++q)
-    for (int e = 0; e < d * d; ++e) out[(size_t)q * d * d + e] = h[81 * (size_t)q + e];
-  return SLIDE_OK;
-}
-// logEntropy (graph.cpp:423-466): {sum of the robot's pose marginal traces, sum of the point landmarks' traces, #poses, #landmarks}
-int HostGraph::marginal_traces(int robot, double* out4) {
-  for (int i = 0; i < 4; ++i) out4[i] = 0.0;
-  if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
-  int rc = marginal_state("marginal_traces");
-  if (rc != SLIDE_OK) return rc;
-  std::vector<int> poses, lms;
-  robot_poses(robot, poses);
-  point_landmarks(lms);
-  if ((rc = ensure_sigma()) != SLIDE_OK) return rc;
-  hipStream_t s = stream;
-  const size_t np = poses.size(), nl = lms.size();
-  if (d_midx.ensure(np + nl + 1, 0, s) != SLIDE_OK || d_mout.ensure(36 * np + 81 * nl + 1, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (np) SL_HIP(hipMemcpyAsync(d_midx.d, poses.data(), np * sizeof(int), hipMemcpyHostToDevice, s));
-  if (nl) SL_HIP(hipMemcpyAsync(d_midx.d + np, lms.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
-  launch_pose_blocks(d_sig.d, G.ld, d_midx.d, (int)np, d_mout.d, s);
-  launch_landmark_covariances(G, d_sig.d, G.ld, d_midx.d + np, (int)nl, d_mout.d + 36 * np, s);
-  std::vector<double> h(36 * np + 81 * nl);
-  if (!h.empty()) SL_HIP(hipMemcpyAsync(h.data(), d_mout.d, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  SL_HIP(hipGetLastError());
-  for (size_t p = 0; p < np; ++p)
-    for (int a = 0; a < 6; ++a) out4[0] += h[36 * p + 7 * a];
-  for (size_t l = 0; l < nl; ++l)
-    for (int a = 0; a < 3; ++a) out4[1] += h[36 * np + 81 * l + 4 * a];
-  out4[2] = (double)np;
-  out4[3] = (double)nl;
-  return SLIDE_OK;
-}
-// The Adjoint of T_b^-1 T_a (row-major 12-double poses: R row-major, then t): the whitened Jacobian of a Between factor (a, b) at zero
-// residual is -Ad / sigma on a and I / sigma on b (both charts)
-static void between_adjoint(const double* Ta, const double* Tb, double Ad[6][6]) {
-  double R[9], t[3], dt[3] = {Ta[9] - Tb[9], Ta[10] - Tb[10], Ta[11] - Tb[11]};
-  for (int r = 0; r < 3; ++r) {                      // T_b^-1 T_a = (Rb^T Ra, Rb^T (ta - tb))
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = Tb[r] * Ta[c] + Tb[3 + r] * Ta[3 + c] + Tb[6 + r] * Ta[6 + c];
-    t[r] = Tb[r] * dt[0] + Tb[3 + r] * dt[1] + Tb[6 + r] * dt[2];
-  }
-  for (int r = 0; r < 6; ++r)                        // [R 0; t^ R  R]
-    for (int c = 0; c < 6; ++c) Ad[r][c] = 0.0;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      Ad[r][c] = R[3 * r + c];
-      Ad[3 + r][3 + c] = R[3 * r + c];
-    }
-  const double tx[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) Ad[3 + r][c] = tx[3 * r] * R[c] + tx[3 * r + 1] * R[3 + c] + tx[3 * r + 2] * R[6 + c];
-}
-// The Woodbury step's host part: C (ncol x ncol, row-major, C = I + J U) symmetrised, C^-1 by Cholesky, g[k] = sum_ab (C^-1)_ab M_k,ab
-static int woodbury_drops(std::vector<double>& Cm, int ncol, const double* const* M, int nM, double* g) {
-  // C^-1 by Cholesky (C = I + J Sigma J^T is SPD); the gains are sum_ab (C^-1)_ab M_ab of the symmetrised matrices
-  for (int a = 0; a < ncol; ++a)
-    for (int b = 0; b < a; ++b) Cm[(size_t)a * ncol + b] = Cm[(size_t)b * ncol + a] = 0.5 * (Cm[(size_t)a * ncol + b] + Cm[(size_t)b * ncol + a]);
-  std::vector<double> Lc((size_t)ncol * ncol, 0.0);
-  for (int j = 0; j < ncol; ++j) {
-    double d = Cm[(size_t)j * ncol + j];
-    for (int k = 0; k < j; ++k) d -= Lc[(size_t)j * ncol + k] * Lc[(size_t)j * ncol + k];
-    if (!(d > 0.0)) { g_last_error = "closure_info_gain: I + J Sigma J^T is not positive definite"; return SLIDE_ERR_NOT_SPD; }
-    const double ljj = std::sqrt(d);
-    Lc[(size_t)j * ncol + j] = ljj;
-    for (int i = j + 1; i < ncol; ++i) {
-      double v = Cm[(size_t)i * ncol + j];
-      for (int k = 0; k < j; ++k) v -= Lc[(size_t)i * ncol + k] * Lc[(size_t)j * ncol + k];
-      Lc[(size_t)i * ncol + j] = v / ljj;
-    }
-  }
-  // (on the host: O((6m)^3), about 10^8 flops at the cap m = 64 — the largest part of such a query; a device version is a follow-up)
-  std::vector<double> LcT((size_t)ncol * ncol), Ci((size_t)ncol * ncol, 0.0), col(ncol);
-  for (int i = 0; i < ncol; ++i)
-    for (int k = 0; k < ncol; ++k) LcT[(size_t)i * ncol + k] = Lc[(size_t)k * ncol + i];
-  for (int j = 0; j < ncol; ++j) {                   // column j of C^-1: L L^T x = e_j (L^-1 e_j is zero above row j)
-    for (int i = 0; i < j; ++i) col[i] = 0.0;
-    for (int i = j; i < ncol; ++i) {
-      double v = i == j ? 1.0 : 0.0;
-      for (int k = j; k < i; ++k) v -= Lc[(size_t)i * ncol + k] * col[k];
-      col[i] = v / Lc[(size_t)i * ncol + i];
-    }
-    for (int i = ncol - 1; i >= 0; --i) {
-      double v = col[i];
-      for (int k = i + 1; k < ncol; ++k) v -= LcT[(size_t)i * ncol + k] * col[k];
-      col[i] = v / Lc[(size_t)i * ncol + i];
-    }
-    for (int i = 0; i < ncol; ++i) Ci[(size_t)i * ncol + j] = col[i];
-  }
-  for (int k = 0; k < nM; ++k) {
-    double gk = 0.0;
-    for (size_t e = 0; e < (size_t)ncol * ncol; ++e) gk += Ci[e] * M[k][e];
-    g[k] = gk;
-  }
-  return SLIDE_OK;
-}
-// estimateClosureInfoGain (graph.cpp:469-623) in the linear-Gaussian model of the resident factor.  Fake factor i is a Between factor
-// (c_{i+1}, c_i) measuring the relative pose of the linearisation values (residual 0), noise sigma_per_m * travel[i]; its whitened
-// Jacobian there is  -Ad(T_{c_i}^-1 T_{c_{i+1}}) / sigma  on c_{i+1} and  I / sigma  on c_i (both charts).  With J (6m x n) these rows,
-// U = Sigma J^T (substitutions with 6m right-hand sides on the factor), C = I + J U:
-//     Sigma - (H + J^T J)^-1 = U C^-1 U^T      (Woodbury)
-// so the trace drops are tr(C^-1 sum_p U_p U_p^T) over the robot's poses and tr(C^-1 sum_l V_l V_l^T) over the point landmarks,
-// V_l = sum_f U_{p_f} F_f (Sigma_lP = -sum_f F_f^T Sigma(p_f, :)).  total = 10 pose + landmark (graph.cpp:622).  iSAM2's update could
-// relinearise variables while the fake factors are in; this linear model does not.  The graph, its factor and Sigma are left untouched.
-int HostGraph::closure_info_gain(int robot, const uint64_t* traj, int n, const double* travel, const double* sigma6, double* out3) {
-  for (int i = 0; i < 3; ++i) out3[i] = 0.0;
-  if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
-  const int m = n - 1;
-  if (m < 1 || !traj || !travel) { g_last_error = "closure_info_gain: the trajectory needs at least two poses"; return SLIDE_ERR_INVALID; }
-  if (m > SLIDE_INFO_GAIN_MAX_STEPS) { g_last_error = "closure_info_gain: more than SLIDE_INFO_GAIN_MAX_STEPS steps"; return SLIDE_ERR_CAPACITY; }
-  for (int i = 0; i < m; ++i)
-    if (!(travel[i] > 0.0) || !std::isfinite(travel[i])) { g_last_error = "closure_info_gain: travel distances must be > 0"; return SLIDE_ERR_INVALID; }
-  if (!sigma6) sigma6 = P.noise_model_odom_vec;      // (noise_model_pose_vec_per_m, graph.h:115, is never set in the reference)
-  for (int a = 0; a < 6; ++a)
-    if (!(sigma6[a] > 0.0) || !std::isfinite(sigma6[a])) { g_last_error = "closure_info_gain: sigma_per_m must be > 0"; return SLIDE_ERR_INVALID; }
-  int rc = marginal_state("closure_info_gain");
-  if (rc != SLIDE_OK) return rc;
-  std::vector<int> ids(n);
-  for (int q = 0; q < n; ++q) {
-    auto it = key2pose.find(pose_key(robot, traj[q]));
-    if (it == key2pose.end() || (size_t)it->second >= up_P) return SLIDE_MISSING;
-    ids[q] = it->second;
-  }
-  hipStream_t s = stream;
-  const int ncol = 6 * m, T = G.T, nT = T * NB;
-  // the linearisation values of the trajectory's poses
-  std::vector<double> val(12 * (size_t)n);
-  for (int q = 0; q < n; ++q)
-    SL_HIP(hipMemcpyAsync(val.data() + 12 * q, G.pose_val + 12 * (size_t)ids[q], 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  // J^T, entry by entry (row of the reduced system, column 6 i + a); a repeated pose sums its blocks
-  std::map<std::pair<int, int>, double> jt;
-  for (int i = 0; i < m; ++i) {
-    double Ad[6][6];
-    between_adjoint(val.data() + 12 * (i + 1), val.data() + 12 * i, Ad);      // (c_{i+1}, c_i)
-    for (int a = 0; a < 6; ++a) {
-      const double w = 1.0 / (sigma6[a] * travel[i]);
-      for (int c = 0; c < 6; ++c) jt[{6 * ids[i + 1] + c, 6 * i + a}] += -Ad[a][c] * w;
-      jt[{6 * ids[i] + a, 6 * i + a}] += w;
-    }
-  }
-  std::vector<int> rcv;
-  std::vector<double> vv;
-  for (const auto& kv : jt) { rcv.push_back(kv.first.first); rcv.push_back(kv.first.second); vv.push_back(kv.second); }
-  const int ne = (int)vv.size();
-  std::vector<int> poses, lms;
-  robot_poses(robot, poses);
-  point_landmarks(lms);
-  std::vector<int> prow;
-  for (int p : poses)
-    for (int a = 0; a < 6; ++a) prow.push_back(6 * p + a);
-  const size_t nl = lms.size(), ldv = std::max<size_t>(9 * nl, 1);
-  if (d_igB.ensure((size_t)ncol * nT, 0, s) != SLIDE_OK || d_igU.ensure((size_t)ncol * nT, 0, s) != SLIDE_OK ||
-      d_igV.ensure((size_t)ncol * ldv, 0, s) != SLIDE_OK || d_igM.ensure(2 * (size_t)ncol * ncol, 0, s) != SLIDE_OK ||
-      d_igrc.ensure(2 * (size_t)ne + prow.size() + nl + 1, 0, s) != SLIDE_OK || d_igval.ensure(ne, 0, s) != SLIDE_OK)
-    return SLIDE_ERR_HIP;
-  int* d_rows = d_igrc.d + 2 * ne;
-  int* d_lms = d_rows + prow.size();
-  SL_HIP(hipMemsetAsync(d_igB.d, 0, (size_t)ncol * nT * sizeof(double), s));
-  SL_HIP(hipMemcpyAsync(d_igrc.d, rcv.data(), rcv.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  SL_HIP(hipMemcpyAsync(d_igval.d, vv.data(), ne * sizeof(double), hipMemcpyHostToDevice, s));
-  if (!prow.empty()) SL_HIP(hipMemcpyAsync(d_rows, prow.data(), prow.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  if (nl) SL_HIP(hipMemcpyAsync(d_lms, lms.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
-  launch_scatter(d_igrc.d, d_igval.d, ne, d_igB.d, nT, s);
-  const bool dense = h_prof.size() != (size_t)T;
-  launch_multi_solve(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), d_igB.d, d_igU.d, ncol, s);
-  double* Mp = d_igM.d;
-  double* Ml = d_igM.d + (size_t)ncol * ncol;
-  launch_gram(d_igU.d, nT, ncol, d_rows, (int)prow.size(), Mp, s);
-  SL_HIP(hipMemsetAsync(Ml, 0, (size_t)ncol * ncol * sizeof(double), s));
-  if (nl) {
-    launch_landmark_V(G, d_igU.d, nT, ncol, d_lms, (int)nl, d_igV.d, ldv, s);
-    launch_gram(d_igV.d, ldv, ncol, nullptr, (int)(9 * nl), Ml, s);
-  }
-  // the rows of U at the trajectory's poses (for C = I + J U)
-  std::vector<double> M(2 * (size_t)ncol * ncol), Urow((size_t)n * 6 * ncol);
-  SL_HIP(hipMemcpyAsync(M.data(), d_igM.d, M.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  for (int q = 0; q < n; ++q)
-    SL_HIP(hipMemcpy2DAsync(Urow.data() + (size_t)q * 6 * ncol, 6 * sizeof(double), d_igU.d + 6 * (size_t)ids[q], (size_t)nT * sizeof(double),
-                            6 * sizeof(double), ncol, hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  SL_HIP(hipGetLastError());
-  std::unordered_map<int, int> row_of;      // reduced-system pose row block -> trajectory slot
-  for (int q = 0; q < n; ++q) row_of.emplace(ids[q], q);
-  std::vector<double> Cm((size_t)ncol * ncol, 0.0);
-  for (int a = 0; a < ncol; ++a) Cm[(size_t)a * ncol + a] = 1.0;
-  for (size_t e = 0; e < vv.size(); ++e) {          // (J U)[jrow][col] += J[jrow][row] U[row][col]
-    const int row = rcv[2 * e], jrow = rcv[2 * e + 1];
-    const double* u = Urow.data() + (size_t)row_of[row / 6] * 6 * ncol + row % 6;
-    for (int c = 0; c < ncol; ++c) Cm[(size_t)jrow * ncol + c] += vv[e] * u[6 * (size_t)c];
-  }
-  const double* Ms[2] = {M.data(), M.data() + (size_t)ncol * ncol};
-  double gs[2];
-  if ((rc = woodbury_drops(Cm, ncol, Ms, 2, gs)) != SLIDE_OK) return rc;
-  const double gp = gs[0], gl = gs[1];
-  out3[0] = 10.0 * gp + gl;
-  out3[1] = gp;
-  out3[2] = gl;
-  return SLIDE_OK;
-}
 
 int HostGraph::pcg_stats(double* out8) {
   for (int i = 0; i < 8; ++i) out8[i] = 0.0;
   if (!d_pcg_scal.d) return SLIDE_OK;
   SL_HIP(hipMemcpyAsync(out8, d_pcg_scal.d, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));
   SL_HIP(hipStreamSynchronize(stream));
-  return SLIDE_OK;
-}
-
-// ---- marginals on the joint graph: the selected inverse over the exact joint pass's factor (joint_cov_kernels.hip) -------
-// What the pass leaves behind and this reads (nothing of it is scratch of the pass): every robot's band factor in S (segments' diagonal
-// blocks in Ld / Winv, their border rows W^T below the band), the windows' second-level factor in bord (Ld2 / Winv2), the separator's
-// leaves and top block in sepS (sep_Ld / sep_Winv; the top block holds the factor of the per-half sums after the canonical pass), its lambda
-// rows below them, and the lambda block's negative factored in lamS (lam_Ld / lam_Winv).  The queries write none of it.
-void CholBatch::free_joint_sigma() {
-  if (jsig_sep) (void)hipFree(jsig_sep);
-  jsig_sep = nullptr;
-  for (double* p : jsig_rob) if (p) (void)hipFree(p);
-  for (int* p : jsig_prow) if (p) (void)hipFree(p);
-  jsig_rob.clear(); jsig_prow.clear(); jsig_lds.clear();
-  jsig_serial = 0;
-}
-int CholBatch::joint_state(const char* who, int slot) {
-  const std::string w = std::string(who) + ": ";
-  if (slot < 0 || slot >= n) { g_last_error = w + "no such slot"; return SLIDE_ERR_INVALID; }
-  if (!arrow || pcg_iters > 0) { g_last_error = w + "the batch does not run exact joint passes (a PCG or block-Jacobi pass leaves no joint factor)"; return SLIDE_ERR_INVALID; }
-  if (sep_owner >= 0) { g_last_error = w + "this rank owns one leaf of the separator (a job spread over GPUs): it holds only that leaf's factor"; return SLIDE_ERR_INVALID; }
-  if (exact_serial == 0 || (int)exact_shape.size() != n) {
-    g_last_error = w + "no whole exact joint pass has run since the batch was configured (call pass_all first)";
-    return SLIDE_ERR_INVALID;
-  }
-  {
-    std::lock_guard<std::mutex> lk(mtx);
-    if (pass_dirty) { g_last_error = w + "the batch's graphs changed since the last pass"; return SLIDE_ERR_INVALID; }
-  }
-  for (int i = 0; i < n; ++i) {
-    HostGraph* g = graphs[i];
-    if (!g) { g_last_error = w + "a slot of the batch is empty"; return SLIDE_ERR_INVALID; }
-    std::lock_guard<std::mutex> gl(g->mtx);
-    std::vector<size_t> now(10);
-    g->fact_shape_now(now.data());
-    now[8] = (size_t)g->fact_serial; now[9] = (size_t)g->S_gen;
-    if (!g->pend_facs.empty() || !g->pend_vars.empty() || now != exact_shape[i]) {
-      g_last_error = w + "the graphs changed since the last exact joint pass (run a pass first)";
-      return SLIDE_ERR_INVALID;
-    }
-  }
-  return SLIDE_OK;
-}
-int CholBatch::joint_robot(int slot) const {
-  const HostGraph* g = graphs[slot];
-  for (const auto& kv : g->key2pose)
-    if (kv.second == 0)
-      for (int r = 0; r < SLIDE_MAX_ROBOTS; ++r)
-        if ((HostGraph::pose_key(r, 0) >> 56) == (kv.first >> 56)) return r;
-  return 0;
-}
-// The elimination tree of the last exact pass (joint_state first: hG / the graphs' host tables describe the factor the buffers hold).
-// Shared by the selected inverse and the many-right-hand-side solve.
-void CholBatch::joint_tree(JointTree& t) const {
-  const int Ts = sep_Ts, nl = sep_nl, Tsep = Ts + nl;
-  t.Ts = Ts; t.Tsep = Tsep;
-  t.sTa = sep_leafT[0]; t.sTL = sep_dissected() ? t.sTa + sep_leafT[1] : 0;
-  std::vector<JSinvSys>& Y = t.Y;
-  std::vector<int>& rp = t.rp;
-  std::vector<int>& rows = t.rows;
-  auto add_col = [&](const std::vector<int>& r) { rows.insert(rows.end(), r.begin(), r.end()); rp.push_back((int)rows.size()); };
-  // system 0: the separator — leaf a, leaf b (no rows of the other leaf), the top block, then the lambda block (D = -I)
-  {
-    JSinvSys y{};
-    y.S = sepS; y.ld = (Ts + nl + 1) * NB; y.Tb = Ts; y.B = lamS; y.ldb = (nl + 1) * NB;
-    y.Ld = sep_Ld; y.Winv = sep_Winv; y.Ld2 = lam_Ld; y.Winv2 = lam_Winv; y.neg0 = Ts; y.col0 = 0; y.lds = (long long)Tsep * NB;
-    const int sTa = sep_leafT[0], sTL = sep_dissected() ? sTa + sep_leafT[1] : 0;
-    for (int k = 0; k < Tsep; ++k) {
-      std::vector<int> r;
-      if (k < Ts) {
-        int hi = Ts - 1, top0 = Ts;
-        if (sep_dissected() && k < sTL) {
-          const int b = k >= sTa, t0 = b ? sTa : 0;
-          hi = t0 + h_leaf_prof[b][k - t0];
-          top0 = sTL;
-        } else if (!sep_dissected() && sep_prof_on && (int)h_sep_prof.size() == Ts) hi = h_sep_prof[k];
-        for (int i = k + 1; i <= hi; ++i) r.push_back(i);
-        for (int i = top0; i < Ts; ++i) r.push_back(i);      // (a leaf's column: the top block's rows, past the leaf)
-        for (int i = Ts; i < Tsep; ++i) r.push_back(i);
-      } else {
-        for (int i = k + 1; i < Tsep; ++i) r.push_back(i);
-      }
-      add_col(r);
-    }
-    Y.push_back(y);
-  }
-  // systems 1 .. n: the robots — band columns of the segments (a segment's profile, its active border rows), then the windows (dense)
-  t.steps.assign(n, {}); t.ranges.assign(n, {});
-  t.T.assign(n, 0); t.Tc.assign(n, 0); t.Trow.assign(n, 0); t.gn.assign(n, 0); t.map.assign(n, {}); t.prow.assign(n, {});
-  for (int i = 0; i < n; ++i) {
-    const HostGraph* g = graphs[i];
-    const GraphDev& G = hG[i];
-    const int T = G.T, nbr = G.nbr, nsep = G.nsep > 0 && !g->segs.empty() ? G.nsep : 0, Tc = T + nsep, Trow = T + nbr;
-    JSinvSys y{};
-    y.S = G.S; y.ld = G.ld; y.Tb = T; y.B = G.bord; y.ldb = G.ldb; y.Ld = G.Ld; y.Winv = G.Winv; y.Ld2 = g->d_Ld2.d; y.Winv2 = g->d_Winv2.d;
-    y.neg0 = 1 << 30; y.col0 = (int)rp.size() - 1; y.lds = (long long)Trow * NB;
-    std::vector<std::vector<int>> colrows(Tc);
-    std::vector<std::pair<int, int>>& ranges = t.ranges[i];      // the column ranges factored side by side
-    if (nsep > 0) {
-      const int NS = (int)g->segs.size();
-      for (int q = 0; q < NS; ++q) {
-        const HostGraph::Seg sg = g->segs[q];
-        ranges.emplace_back(sg.t0, sg.t1);
-        for (int k = sg.t0; k < sg.t1; ++k) {
-          const int hi = std::min(sg.t1 - 1, sg.t0 + g->seg_prof[q][k - sg.t0]);
-          for (int r = k + 1; r <= hi; ++r) colrows[k].push_back(r);
-          for (int tt = 0; tt < nbr; ++tt) {
-            const size_t e = 1 + (size_t)NS + (size_t)q * (nbr + 1) + tt;
-            const int sf = e < g->seg_tab.size() ? g->seg_tab[e] : 0;
-            if (sf <= k) colrows[k].push_back(T + tt);
-          }
-        }
-      }
-      for (int k = T; k < Tc; ++k)
-        for (int r = k + 1; r < Trow; ++r) colrows[k].push_back(r);
-    } else {
-      ranges.emplace_back(0, T);
-      const bool dense = g->h_prof.size() != (size_t)T;
-      for (int k = 0; k < T; ++k) {
-        const int hi = dense ? T - 1 : g->h_prof[k];
-        for (int r = k + 1; r <= hi; ++r) colrows[k].push_back(r);
-        for (int tt = 0; tt < nbr; ++tt)
-          if ((size_t)tt >= g->h_bfirst.size() || g->h_bfirst[tt] <= k) colrows[k].push_back(T + tt);
-      }
-    }
-    for (int k = 0; k < Tc; ++k) add_col(colrows[k]);
-    for (int k = Tc - 1; k >= T; --k) t.steps[i].push_back({k});
-    for (int st = 0;; ++st) {
-      std::vector<int> cs;
-      for (const auto& rg : ranges) if (rg.second - 1 - st >= rg.first) cs.push_back(rg.second - 1 - st);
-      if (cs.empty()) break;
-      t.steps[i].push_back(cs);
-    }
-    Y.push_back(y);
-    // the border map (border coordinate past the windows -> row of the separator's system) and the pose rows
-    const int gn = (nbr - nsep) * NB, m = g->h_sep_off.empty() ? 0 : g->h_sep_off.back();
-    std::vector<int>& mp = t.map[i];
-    mp.assign(std::max(gn, 1), -1);
-    for (size_t c = 0; c < g->h_sep_map.size(); ++c) {
-      const int o = g->h_sep_map[c] - nsep * NB;
-      if (o >= 0 && o < gn) mp[o] = (int)c < m ? (int)c : Ts * NB + ((int)c - m);
-    }
-    std::vector<int>& prow = t.prow[i];
-    prow.assign(std::max<size_t>(G.P, 1), 0);
-    for (int p = 0; p < G.P; ++p)
-      prow[p] = (size_t)p < g->h_pose_sep.size() && g->h_pose_sep[p] >= 0 ? T * NB + g->h_pose_sep[p] : 6 * p;
-    t.T[i] = T; t.Tc[i] = Tc; t.Trow[i] = Trow; t.gn[i] = gn;
-  }
-}
-// Sigma of the separator system and of every robot's band + border, computed once per exact pass (joint_state first: the buffers hold
-// that pass's factor and hG / the graphs' host tables describe it).  Scratch (Z, the row lists, the border maps) lives only in here.
-int CholBatch::ensure_joint_sigma() {
-  if (jsig_serial == exact_serial && jsig_sep) return SLIDE_OK;
-  free_joint_sigma();
-  hipStream_t s = master;
-  JointTree t;
-  joint_tree(t);
-  const int Tsep = t.Tsep;
-  std::vector<JSinvSys>& Y = t.Y;
-  const std::vector<int>& rp = t.rp;
-  const std::vector<int>& rows = t.rows;
-  const std::vector<std::vector<std::vector<int>>>& steps = t.steps;      // per robot: the columns of each backward step
-  std::vector<double*> Zs;
-  auto cleanup = [&]() { for (double* z : Zs) if (z) (void)hipFree(z); };
-  JSigGather gA{};
-  std::vector<int*> maps(n, nullptr);
-  int max_gn = 0;
-  jsig_rob.assign(n, nullptr); jsig_prow.assign(n, nullptr); jsig_lds.assign(n, 0);
-  for (int i = 0; i < n; ++i) {
-    JSinvSys& y = Y[1 + i];
-    const int Tc = t.Tc[i], gn = t.gn[i];
-    // Sigma, Z; the border map and the pose rows
-    const size_t nsg = (size_t)y.lds * y.lds, nz = (size_t)y.lds * Tc * NB;
-    double* Z = nullptr;
-    SL_HIP(hipMalloc(reinterpret_cast<void**>(&jsig_rob[i]), nsg * sizeof(double)));
-    if (hipMalloc(reinterpret_cast<void**>(&Z), std::max<size_t>(nz, 1) * sizeof(double)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
-    Zs.push_back(Z);
-    SL_HIP(hipMemsetAsync(jsig_rob[i], 0, nsg * sizeof(double), s));
-    y.Sg = jsig_rob[i]; y.Z = Z;
-    jsig_lds[i] = y.lds;
-    const std::vector<int>& mp = t.map[i];
-    const std::vector<int>& prow = t.prow[i];
-    if (hipMalloc(reinterpret_cast<void**>(&maps[i]), mp.size() * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&jsig_prow[i]), prow.size() * sizeof(int)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
-    SL_HIP(hipMemcpyAsync(maps[i], mp.data(), mp.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    SL_HIP(hipMemcpyAsync(jsig_prow[i], prow.data(), prow.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    gA.dst[i] = jsig_rob[i]; gA.map[i] = maps[i]; gA.lds[i] = y.lds; gA.o0[i] = Tc * NB; gA.n[i] = gn;
-    max_gn = std::max(max_gn, gn);
-  }
-  // the separator's Sigma and Z
-  jsig_lds_sep = (long long)Tsep * NB;
-  {
-    const size_t nsg = (size_t)jsig_lds_sep * jsig_lds_sep, nz = (size_t)jsig_lds_sep * Tsep * NB;
-    double* Z = nullptr;
-    SL_HIP(hipMalloc(reinterpret_cast<void**>(&jsig_sep), nsg * sizeof(double)));
-    if (hipMalloc(reinterpret_cast<void**>(&Z), nz * sizeof(double)) != hipSuccess) { cleanup(); return SLIDE_ERR_HIP; }
-    Zs.push_back(Z);
-    SL_HIP(hipMemsetAsync(jsig_sep, 0, nsg * sizeof(double), s));
-    Y[0].Sg = jsig_sep; Y[0].Z = Z;
-  }
-  gA.src = jsig_sep; gA.lds_src = jsig_lds_sep;
-  // the jobs: the separator's columns one step each (last first), then the robots' steps side by side
-  std::vector<int2> jobs;
-  std::vector<std::pair<int, int>> step_at;          // (first job, jobs) per step
-  std::vector<int> step_rows;
-  auto nrows = [&](int sy, int k) { const int b = Y[sy].col0 + k; return rp[b + 1] - rp[b]; };
-  for (int k = Tsep - 1; k >= 0; --k) {
-    step_at.emplace_back((int)jobs.size(), 1);
-    step_rows.push_back(nrows(0, k));
-    jobs.push_back(make_int2(0, k));
-  }
-  const int n_sep_steps = (int)step_at.size();
-  size_t nst = 0;
-  for (int i = 0; i < n; ++i) nst = std::max(nst, steps[i].size());
-  for (size_t st = 0; st < nst; ++st) {
-    const int j0 = (int)jobs.size();
-    int mr = 0;
-    for (int i = 0; i < n; ++i)
-      if (st < steps[i].size())
-        for (int k : steps[i][st]) { jobs.push_back(make_int2(1 + i, k)); mr = std::max(mr, nrows(1 + i, k)); }
-    step_at.emplace_back(j0, (int)jobs.size() - j0);
-    step_rows.push_back(mr);
-  }
-  int max_rows = 0;
-  for (int r : step_rows) max_rows = std::max(max_rows, r);
-  JSinvSys* d_sys = nullptr; int2* d_jobs = nullptr; int *d_rp = nullptr, *d_rows = nullptr;
-  auto free_tables = [&]() {
-    if (d_sys) (void)hipFree(d_sys);
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_rp) (void)hipFree(d_rp);
-    if (d_rows) (void)hipFree(d_rows);
-    for (int* p : maps) if (p) (void)hipFree(p);
-    cleanup();
-  };
-  if (hipMalloc(reinterpret_cast<void**>(&d_sys), Y.size() * sizeof(JSinvSys)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_jobs), std::max<size_t>(jobs.size(), 1) * sizeof(int2)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_rp), rp.size() * sizeof(int)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&d_rows), std::max<size_t>(rows.size(), 1) * sizeof(int)) != hipSuccess) { free_tables(); return SLIDE_ERR_HIP; }
-  SL_HIP(hipMemcpyAsync(d_sys, Y.data(), Y.size() * sizeof(JSinvSys), hipMemcpyHostToDevice, s));
-  SL_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-  SL_HIP(hipMemcpyAsync(d_rp, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  if (!rows.empty()) SL_HIP(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  launch_jsinv_prep(d_sys, d_jobs, (int)jobs.size(), max_rows, d_rp, d_rows, s);
-  for (int q = 0; q < (int)step_at.size(); ++q) {
-    if (q == n_sep_steps) launch_jsig_gather(gA, n, max_gn, s);      // (the robots' rows of separator coordinates, once it is complete)
-    launch_jsinv_step(d_sys, d_jobs + step_at[q].first, step_at[q].second, step_rows[q], d_rp, d_rows, s);
-  }
-  if ((int)step_at.size() == n_sep_steps) launch_jsig_gather(gA, n, max_gn, s);
-  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
-  free_tables();
-  if (!hip_ok(e1, "joint selected inverse") || !hip_ok(e2, "joint selected inverse")) { free_joint_sigma(); return SLIDE_ERR_HIP; }
-  jsig_serial = exact_serial;
-  return SLIDE_OK;
-}
-// isam->marginalCovariance(X(idx)) on the joint graph (graph.cpp:314-323 on a replica): the poses of the robot of `slot`
-int CholBatch::joint_pose_covariances(int slot, const uint64_t* idx, int n_q, double* out36n) {
-  if (n_q < 0 || (n_q > 0 && (!idx || !out36n))) return SLIDE_ERR_INVALID;
-  for (int i = 0; i < 36 * n_q; ++i) out36n[i] = 0.0;
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  int rc = joint_state("get_pose_covariances", slot);
-  if (rc != SLIDE_OK) return rc;
-  HostGraph* g = graphs[slot];
-  const int robot = joint_robot(slot);
-  std::vector<int> ids(n_q);
-  for (int q = 0; q < n_q; ++q) {
-    auto it = g->key2pose.find(HostGraph::pose_key(robot, idx[q]));
-    if (it == g->key2pose.end() || (size_t)it->second >= g->up_P) return SLIDE_MISSING;
-    ids[q] = it->second;
-  }
-  if (n_q == 0) return SLIDE_OK;
-  if ((rc = ensure_joint_sigma()) != SLIDE_OK) return rc;
-  hipStream_t s = master;
-  int* d_idx = nullptr; double* d_out = nullptr;
-  SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), n_q * sizeof(int)));
-  if (hipMalloc(reinterpret_cast<void**>(&d_out), 36 * (size_t)n_q * sizeof(double)) != hipSuccess) { (void)hipFree(d_idx); return SLIDE_ERR_HIP; }
-  hipError_t e = hipMemcpyAsync(d_idx, ids.data(), n_q * sizeof(int), hipMemcpyHostToDevice, s);
-  launch_pose_blocks(jsig_rob[slot], (int)jsig_lds[slot], d_idx, n_q, d_out, s, jsig_prow[slot]);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out36n, d_out, 36 * (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d_idx); (void)hipFree(d_out);
-  SL_HIP(e);
-  return SLIDE_OK;
-}
-// isam->marginalCovariance(L / C / U(idx)) on the joint graph: a private landmark through its robot's pose Sigma (k_lm_cov), a shared one
-// straight from the separator's Sigma at its slot's coordinates — every replica reads the same numbers
-int CholBatch::joint_landmark_covariances(int slot, int cls, const uint64_t* idx, int n_q, double* out) {
-  if ((cls != SLIDE_CLS_CYLINDER && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_ELLIPSOID) || n_q < 0 || (n_q > 0 && (!idx || !out)))
-    return SLIDE_ERR_INVALID;
-  const int d = cls == SLIDE_CLS_CYLINDER ? 7 : (cls == SLIDE_CLS_CUBE ? 9 : 3);
-  for (int i = 0; i < d * d * n_q; ++i) out[i] = 0.0;
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  int rc = joint_state("get_landmark_covariances", slot);
-  if (rc != SLIDE_OK) return rc;
-  HostGraph* g = graphs[slot];
-  std::vector<int> priv, pq, row0, dims, sq;
-  for (int q = 0; q < n_q; ++q) {
-    const int l = g->lm_lid(cls, idx[q]);
-    if (l < 0) return SLIDE_MISSING;
-    int sl = -1;
-    if ((size_t)l < g->h_lm_bord.size() && g->h_lm_bord[l] >= 0)
-      for (size_t k = 0; k < g->h_sh_lid.size(); ++k) if (g->h_sh_lid[k] == l) { sl = (int)k; break; }
-    if (sl >= 0) { row0.push_back(g->h_sep_off[sl]); dims.push_back(d); sq.push_back(q); }
-    else { priv.push_back(l); pq.push_back(q); }
-  }
-  if (n_q == 0) return SLIDE_OK;
-  if ((rc = ensure_joint_sigma()) != SLIDE_OK) return rc;
-  hipStream_t s = master;
-  const size_t np = priv.size(), ns = row0.size();
-  int* d_i = nullptr; double* d_out = nullptr;
-  SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_i), (np + 2 * ns + 1) * sizeof(int)));
-  if (hipMalloc(reinterpret_cast<void**>(&d_out), 81 * (np + ns) * sizeof(double)) != hipSuccess) { (void)hipFree(d_i); return SLIDE_ERR_HIP; }
-  hipError_t e = hipSuccess;
-  if (np) e = hipMemcpyAsync(d_i, priv.data(), np * sizeof(int), hipMemcpyHostToDevice, s);
-  if (ns && e == hipSuccess) e = hipMemcpyAsync(d_i + np, row0.data(), ns * sizeof(int), hipMemcpyHostToDevice, s);
-  if (ns && e == hipSuccess) e = hipMemcpyAsync(d_i + np + ns, dims.data(), ns * sizeof(int), hipMemcpyHostToDevice, s);
-  launch_landmark_covariances(hG[slot], jsig_rob[slot], (int)jsig_lds[slot], d_i, (int)np, d_out, s, jsig_prow[slot]);
-  launch_sym_blocks(jsig_sep, (size_t)jsig_lds_sep, d_i + np, d_i + np + ns, (int)ns, d_out + 81 * np, s);
-  std::vector<double> h(81 * (np + ns));
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d_i); (void)hipFree(d_out);
-  SL_HIP(e);
-  for (size_t k = 0; k < np; ++k)
-    for (int v = 0; v < d * d; ++v) out[(size_t)pq[k] * d * d + v] = h[81 * k + v];
-  for (size_t k = 0; k < ns; ++k)
-    for (int v = 0; v < d * d; ++v) out[(size_t)sq[k] * d * d + v] = h[81 * (np + k) + v];
-  return SLIDE_OK;
-}
-// logEntropy (graph.cpp:423-466) on the joint graph: {the traces of the robot's pose marginals, the traces of the job's point landmarks
-// (every graph's private ones, each shared slot once), #poses, #point landmarks}
-int CholBatch::joint_marginal_traces(int slot, double* out4) {
-  for (int i = 0; i < 4; ++i) out4[i] = 0.0;
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  int rc = joint_state("marginal_traces", slot);
-  if (rc != SLIDE_OK) return rc;
-  if ((rc = ensure_joint_sigma()) != SLIDE_OK) return rc;
-  hipStream_t s = master;
-  std::vector<int> poses;
-  graphs[slot]->robot_poses(joint_robot(slot), poses);
-  std::vector<std::vector<int>> priv(n);
-  std::vector<int> row0, dims;
-  std::vector<char> seen;
-  for (int i = 0; i < n; ++i) {
-    const HostGraph* g = graphs[i];
-    for (size_t l = 0; l < g->up_L && l < g->h_lm_type.size(); ++l)
-      if (g->h_lm_type[l] == VT_POINT && !(l < g->h_lm_bord.size() && g->h_lm_bord[l] >= 0)) priv[i].push_back((int)l);
-    seen.resize(std::max(seen.size(), g->h_sh_lid.size()), 0);
-    for (size_t k = 0; k < g->h_sh_lid.size(); ++k) {
-      const int l = g->h_sh_lid[k];
-      if (l < 0 || (size_t)l >= g->up_L || g->h_lm_type[l] != VT_POINT || seen[k]) continue;
-      seen[k] = 1;
-      row0.push_back(g->h_sep_off[k]); dims.push_back(3);
-    }
-  }
-  size_t nq = poses.size() + row0.size();
-  for (int i = 0; i < n; ++i) nq += priv[i].size();
-  int* d_i = nullptr; double* d_out = nullptr;
-  SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_i), (nq + row0.size() + 1) * sizeof(int)));
-  if (hipMalloc(reinterpret_cast<void**>(&d_out), (81 * nq + 1) * sizeof(double)) != hipSuccess) { (void)hipFree(d_i); return SLIDE_ERR_HIP; }
-  hipError_t e = hipSuccess;
-  size_t o = 0;
-  auto up = [&](const std::vector<int>& v) { if (!v.empty() && e == hipSuccess) e = hipMemcpyAsync(d_i + o, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s); o += v.size(); };
-  const size_t o_pose = o; up(poses);
-  std::vector<size_t> o_priv(n);
-  for (int i = 0; i < n; ++i) { o_priv[i] = o; up(priv[i]); }
-  const size_t o_sh = o; up(row0); up(dims);
-  launch_pose_blocks(jsig_rob[slot], (int)jsig_lds[slot], d_i + o_pose, (int)poses.size(), d_out, s, jsig_prow[slot]);
-  for (int i = 0; i < n; ++i)
-    launch_landmark_covariances(hG[i], jsig_rob[i], (int)jsig_lds[i], d_i + o_priv[i], (int)priv[i].size(), d_out + 81 * o_priv[i], s, jsig_prow[i]);
-  launch_sym_blocks(jsig_sep, (size_t)jsig_lds_sep, d_i + o_sh, d_i + o_sh + row0.size(), (int)row0.size(), d_out + 81 * o_sh, s);
-  std::vector<double> h(81 * nq);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess && !h.empty()) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(d_i); (void)hipFree(d_out);
-  SL_HIP(e);
-  for (size_t p = 0; p < poses.size(); ++p)      // (pose blocks: 36 per pose, packed from the front of d_out)
-    for (int a = 0; a < 6; ++a) out4[0] += h[36 * p + 7 * a];
-  for (size_t q = o_priv.empty() ? o_sh : o_priv[0]; q < o_sh + row0.size(); ++q)
-    for (int a = 0; a < 3; ++a) out4[1] += h[81 * q + 4 * a];
-  out4[2] = (double)poses.size();
-  out4[3] = (double)(o_sh + row0.size() - poses.size());
-  return SLIDE_OK;
-}
-
-
-// estimateClosureInfoGain (graph.cpp:469-623) on the joint graph (graph.cpp:325-371: every replica holds the whole multi-robot graph),
-// in the linear-Gaussian model of the last exact pass's factor K = L D L^T, as the single-graph call: U = K^-1 J^T by substitutions with
-// 6m right-hand sides through the pass's elimination tree (joint_cov_kernels.hip's k_jms_*), C = I + J U, the drops tr(C^-1 U_P^T U_P).
-// A candidate's endpoints may sit in different robots' graphs (a rendezvous); J is taken at the graphs' pose_val, the pass's
-// linearisation point.  Every system's U lives in one buffer (robots first, then the separator; leading dimension N), so the grams run
-// over row lists of it.  Nothing the pass reads is written and the cached joint Sigma is left as it was.
-int CholBatch::joint_closure_info_gain(int slot, const int32_t* traj_slots, const uint64_t* traj, int n_q, const double* travel,
-                                       const double* sigma6, double* out4) {
-  for (int i = 0; i < 4; ++i) out4[i] = 0.0;
-  const int m = n_q - 1;
-  if (m < 1 || !traj || !travel) { g_last_error = "closure_info_gain: the trajectory needs at least two poses"; return SLIDE_ERR_INVALID; }
-  if (m > SLIDE_INFO_GAIN_MAX_STEPS) { g_last_error = "closure_info_gain: more than SLIDE_INFO_GAIN_MAX_STEPS steps"; return SLIDE_ERR_CAPACITY; }
-  for (int i = 0; i < m; ++i)
-    if (!(travel[i] > 0.0) || !std::isfinite(travel[i])) { g_last_error = "closure_info_gain: travel distances must be > 0"; return SLIDE_ERR_INVALID; }
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  int rc = joint_state("closure_info_gain", slot);
-  if (rc != SLIDE_OK) return rc;
-  if (!sigma6) sigma6 = graphs[slot]->P.noise_model_odom_vec;
-  for (int a = 0; a < 6; ++a)
-    if (!(sigma6[a] > 0.0) || !std::isfinite(sigma6[a])) { g_last_error = "closure_info_gain: sigma_per_m must be > 0"; return SLIDE_ERR_INVALID; }
-  std::vector<int> qs(n_q), ids(n_q);
-  for (int q = 0; q < n_q; ++q) {
-    const int sl = traj_slots ? traj_slots[q] : slot;
-    if (sl < 0 || sl >= n) { g_last_error = "closure_info_gain: no such slot in traj_slots"; return SLIDE_ERR_INVALID; }
-    const HostGraph* g = graphs[sl];
-    auto it = g->key2pose.find(HostGraph::pose_key(joint_robot(sl), traj[q]));
-    if (it == g->key2pose.end() || (size_t)it->second >= g->up_P) return SLIDE_MISSING;
-    qs[q] = sl; ids[q] = it->second;
-  }
-  hipStream_t s = master;
-  const int ncol = 6 * m;
-  JointTree t;
-  joint_tree(t);
-  const int Tsep = t.Tsep;
-  // the rows of every system in the buffers S (solutions, U at the end) and R (right-hand sides)
-  std::vector<size_t> off(n + 1);
-  size_t N = 0;
-  for (int i = 0; i < n; ++i) { off[1 + i] = N; N += (size_t)t.Trow[i] * NB; }
-  off[0] = N; N += (size_t)Tsep * NB;
-  auto prow_of = [&](int sl, int p) { return (int)off[1 + sl] + t.prow[sl][p]; };
-  // J^T, entry by entry (row of X, column 6 i + a); a repeated pose sums its blocks
-  std::vector<double> val(12 * (size_t)n_q);
-  for (int q = 0; q < n_q; ++q)
-    SL_HIP(hipMemcpyAsync(val.data() + 12 * q, hG[qs[q]].pose_val + 12 * (size_t)ids[q], 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  std::map<std::pair<int, int>, double> jt;
-  std::unordered_map<int, int> row_of;      // row of X -> 6 (trajectory slot) + coordinate
-  for (int q = 0; q < n_q; ++q)
-    for (int a = 0; a < 6; ++a) row_of.emplace(prow_of(qs[q], ids[q]) + a, 6 * q + a);
-  for (int i = 0; i < m; ++i) {
-    double Ad[6][6];
-    between_adjoint(val.data() + 12 * (i + 1), val.data() + 12 * i, Ad);      // (c_{i+1}, c_i)
-    const int ra = prow_of(qs[i + 1], ids[i + 1]), rb = prow_of(qs[i], ids[i]);
-    for (int a = 0; a < 6; ++a) {
-      const double w = 1.0 / (sigma6[a] * travel[i]);
-      for (int c = 0; c < 6; ++c) jt[{ra + c, 6 * i + a}] += -Ad[a][c] * w;
-      jt[{rb + a, 6 * i + a}] += w;
-    }
-  }
-  std::vector<int> rcv;
-  std::vector<double> vv;
-  for (const auto& kv : jt) { rcv.push_back(kv.first.first); rcv.push_back(kv.first.second); vv.push_back(kv.second); }
-  const int ne = (int)vv.size();
-  // the solve's schedule.  Nodes: a robot's band segments (level 0), its windows (1), its rows of separator coordinates (2, no columns);
-  // the separator's leaves (3), its top block with the lambda block (4; all of it when the separator is not dissected)
-  const int NS = 1 + n;
-  std::vector<std::vector<int>> node(NS);
-  for (int i = 0; i < n; ++i) {
-    node[1 + i].assign(t.Trow[i], 2000);
-    for (size_t q = 0; q < t.ranges[i].size(); ++q)
-      for (int k = t.ranges[i][q].first; k < t.ranges[i][q].second; ++k) node[1 + i][k] = (int)q;
-    for (int k = t.T[i]; k < t.Tc[i]; ++k) node[1 + i][k] = 1000;
-  }
-  node[0].assign(Tsep, 4000);
-  for (int k = 0; k < t.sTL; ++k) node[0][k] = k < t.sTa ? 3000 : 3001;
-  auto level = [](int nd) { return nd < 1000 ? 0 : nd / 1000; };
-  auto ncols = [&](int sy) { return sy == 0 ? Tsep : t.Tc[sy - 1]; };
-  // per system and tile: the forward push rows (same node), backward push columns (same node, transposed), forward pull columns
-  // (nodes below), backward pull rows (nodes above)
-  std::vector<std::vector<std::vector<int>>> fpush(NS), bpush(NS), fpull(NS), bpull(NS);
-  for (int sy = 0; sy < NS; ++sy) {
-    const int nt = (int)node[sy].size();
-    fpush[sy].assign(nt, {}); bpush[sy].assign(nt, {}); fpull[sy].assign(nt, {}); bpull[sy].assign(nt, {});
-    for (int c = 0; c < ncols(sy); ++c) {
-      const int b = t.Y[sy].col0 + c;
-      for (int q = t.rp[b]; q < t.rp[b + 1]; ++q) {
-        const int i = t.rows[q];
-        if (node[sy][i] == node[sy][c]) { fpush[sy][c].push_back(i); bpush[sy][i].push_back(c); }
-        else { fpull[sy][i].push_back(c); bpull[sy][c].push_back(i); }
-      }
-    }
-  }
-  std::vector<int4> jobs;
-  std::vector<int> lst;
-  struct Launch { int kind, bwd, j0, nj, maxl; };      // kind 0: push, 1: pull, 2: sum, 3: gather
-  std::vector<Launch> plan;
-  auto add_job = [&](int sy, int k, const std::vector<int>& l) {
-    jobs.push_back(make_int4(sy, k, (int)lst.size(), (int)(lst.size() + l.size())));
-    lst.insert(lst.end(), l.begin(), l.end());
-    return (int)l.size();
-  };
-  // a push launch: the columns cols (system, column) side by side
-  auto push = [&](const std::vector<std::pair<int, int>>& cols, bool bwd) {
-    if (cols.empty()) return;
-    Launch L{0, bwd, (int)jobs.size(), 0, 0};
-    for (const auto& sc : cols) L.maxl = std::max(L.maxl, add_job(sc.first, sc.second, (bwd ? bpush : fpush)[sc.first][sc.second]));
-    L.nj = (int)jobs.size() - L.j0;
-    plan.push_back(L);
-  };
-  // a pull launch over the tiles of the given level (forward, a tile with nothing to take is left out; backward, every column starts
-  // its right-hand side there: R_k = D_k S_k - ..)
-  auto pull = [&](int lev, bool bwd) {
-    Launch L{1, bwd, (int)jobs.size(), 0, 0};
-    for (int sy = 0; sy < NS; ++sy)
-      for (int k = 0; k < (int)node[sy].size(); ++k) {
-        if (level(node[sy][k]) != lev || (bwd && k >= ncols(sy))) continue;
-        const std::vector<int>& l = (bwd ? bpull : fpull)[sy][k];
-        if (l.empty() && !bwd) continue;
-        add_job(sy, k, l);
-      }
-    L.nj = (int)jobs.size() - L.j0;
-    if (L.nj > 0) plan.push_back(L);
-  };
-  auto robot_band_steps = [&](bool bwd) {
-    int nst = 0;
-    for (int i = 0; i < n; ++i) for (const auto& rg : t.ranges[i]) nst = std::max(nst, rg.second - rg.first);
-    for (int st = 0; st < nst; ++st) {
-      std::vector<std::pair<int, int>> cols;
-      for (int i = 0; i < n; ++i)
-        for (const auto& rg : t.ranges[i])
-          if (st < rg.second - rg.first) cols.emplace_back(1 + i, bwd ? rg.second - 1 - st : rg.first + st);
-      push(cols, bwd);
-    }
-  };
-  auto robot_window_steps = [&](bool bwd) {
-    int nst = 0;
-    for (int i = 0; i < n; ++i) nst = std::max(nst, t.Tc[i] - t.T[i]);
-    for (int st = 0; st < nst; ++st) {
-      std::vector<std::pair<int, int>> cols;
-      for (int i = 0; i < n; ++i)
-        if (st < t.Tc[i] - t.T[i]) cols.emplace_back(1 + i, bwd ? t.Tc[i] - 1 - st : t.T[i] + st);
-      push(cols, bwd);
-    }
-  };
-  auto leaf_steps = [&](bool bwd) {
-    const int na = t.sTa, nb = t.sTL > 0 ? t.sTL - t.sTa : 0;
-    if (t.sTL == 0) return;
-    for (int st = 0; st < std::max(na, nb); ++st) {
-      std::vector<std::pair<int, int>> cols;
-      if (st < na) cols.emplace_back(0, bwd ? na - 1 - st : st);
-      if (st < nb) cols.emplace_back(0, bwd ? t.sTL - 1 - st : na + st);
-      push(cols, bwd);
-    }
-  };
-  auto top_steps = [&](bool bwd) {
-    for (int st = 0; st < Tsep - t.sTL; ++st) push({{0, bwd ? Tsep - 1 - st : t.sTL + st}}, bwd);
-  };
-  robot_band_steps(false);
-  pull(1, false); robot_window_steps(false);
-  pull(2, false);
-  plan.push_back({2, 0, 0, 0, 0});
-  leaf_steps(false);
-  pull(4, false); top_steps(false);
-  pull(4, true); top_steps(true);
-  pull(3, true); leaf_steps(true);
-  plan.push_back({3, 0, 0, 0, 0});
-  pull(1, true); robot_window_steps(true);
-  pull(0, true); robot_band_steps(true);
-  // the separator's rows from the robots' (the inverse of the border maps, robot order)
-  std::vector<std::vector<int2>> inv(Tsep * NB);
-  int max_gn = 0;
-  for (int i = 0; i < n; ++i) {
-    for (int o = 0; o < t.gn[i]; ++o)
-      if (t.map[i][o] >= 0) inv[t.map[i][o]].push_back(make_int2(i, t.Tc[i] * NB + o));
-    max_gn = std::max(max_gn, t.gn[i]);
-  }
-  std::vector<int> sptr{0};
-  std::vector<int2> sent;
-  for (const auto& v : inv) { sent.insert(sent.end(), v.begin(), v.end()); sptr.push_back((int)sent.size()); }
-  // the grams' row lists: the poses of the robot in `slot`, of every robot, the job's shared point landmarks (each slot once); the
-  // private point landmarks of every graph (k_lm_V on its robot's rows)
-  std::vector<int> rows_slot, rows_all, rows_sh, lms, lm0(n + 1, 0);
-  for (int i = 0; i < n; ++i) {
-    std::vector<int> poses;
-    graphs[i]->robot_poses(joint_robot(i), poses);
-    for (int p : poses)
-      for (int a = 0; a < 6; ++a) {
-        rows_all.push_back(prow_of(i, p) + a);
-        if (i == slot) rows_slot.push_back(prow_of(i, p) + a);
-      }
-  }
-  std::vector<char> seen;
-  for (int i = 0; i < n; ++i) {
-    const HostGraph* g = graphs[i];
-    for (size_t l = 0; l < g->up_L && l < g->h_lm_type.size(); ++l)
-      if (g->h_lm_type[l] == VT_POINT && !(l < g->h_lm_bord.size() && g->h_lm_bord[l] >= 0)) lms.push_back((int)l);
-    lm0[i + 1] = (int)lms.size();
-    seen.resize(std::max(seen.size(), g->h_sh_lid.size()), 0);
-    for (size_t k = 0; k < g->h_sh_lid.size(); ++k) {
-      const int l = g->h_sh_lid[k];
-      if (l < 0 || (size_t)l >= g->up_L || g->h_lm_type[l] != VT_POINT || seen[k]) continue;
-      seen[k] = 1;
-      for (int a = 0; a < 3; ++a) rows_sh.push_back((int)off[0] + g->h_sep_off[k] + a);
-    }
-  }
-  const size_t nl = lms.size(), ldv = std::max<size_t>(9 * nl, 1);
-  // device scratch of this query (freed before it returns)
-  std::vector<void*> bufs;
-  bool oom = false;
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) { oom = true; return nullptr; }
-    bufs.push_back(p);
-    return p;
-  };
-  auto release = [&]() { for (void* p : bufs) (void)hipFree(p); bufs.clear(); };
-  double* X = static_cast<double*>(dalloc(N * ncol * sizeof(double)));
-  double* Rb = static_cast<double*>(dalloc(N * ncol * sizeof(double)));
-  double* V = static_cast<double*>(dalloc(ldv * ncol * sizeof(double)));
-  double* Md = static_cast<double*>(dalloc(4 * (size_t)ncol * ncol * sizeof(double)));
-  JSinvSys* d_sys = static_cast<JSinvSys*>(dalloc(NS * sizeof(JSinvSys)));
-  int4* d_jobs = static_cast<int4*>(dalloc(jobs.size() * sizeof(int4)));
-  int2* d_sent = static_cast<int2*>(dalloc(sent.size() * sizeof(int2)));
-  const size_t ni = lst.size() + sptr.size() + 2 * (size_t)ne + rows_slot.size() + rows_all.size() + rows_sh.size() + nl;
-  int* d_i = static_cast<int*>(dalloc(ni * sizeof(int)));
-  std::vector<int*> d_prow(n, nullptr), d_map(n, nullptr);
-  for (int i = 0; i < n; ++i) {
-    d_prow[i] = static_cast<int*>(dalloc(t.prow[i].size() * sizeof(int)));
-    d_map[i] = static_cast<int*>(dalloc(t.map[i].size() * sizeof(int)));
-  }
-  double* d_val = static_cast<double*>(dalloc(std::max(ne, 1) * sizeof(double)));
-  if (oom) { (void)hipGetLastError(); release(); g_last_error = "closure_info_gain: out of device memory"; return SLIDE_ERR_HIP; }
-  for (int sy = 0; sy < NS; ++sy) { t.Y[sy].Sg = X + off[sy]; t.Y[sy].Z = Rb + off[sy]; t.Y[sy].lds = (long long)N; }
-  int* d_lst = d_i;
-  int* d_sptr = d_lst + lst.size();
-  int* d_rc = d_sptr + sptr.size();
-  int* d_rslot = d_rc + 2 * ne;
-  int* d_rall = d_rslot + rows_slot.size();
-  int* d_rsh = d_rall + rows_all.size();
-  int* d_lms = d_rsh + rows_sh.size();
-  hipError_t e = hipMemsetAsync(X, 0, N * ncol * sizeof(double), s);
-  if (e == hipSuccess) e = hipMemsetAsync(Rb, 0, N * ncol * sizeof(double), s);
-  auto up = [&](void* dst, const void* src, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); };
-  up(d_sys, t.Y.data(), NS * sizeof(JSinvSys));
-  up(d_jobs, jobs.data(), jobs.size() * sizeof(int4));
-  up(d_sent, sent.data(), sent.size() * sizeof(int2));
-  up(d_lst, lst.data(), lst.size() * sizeof(int));
-  up(d_sptr, sptr.data(), sptr.size() * sizeof(int));
-  up(d_rc, rcv.data(), rcv.size() * sizeof(int));
-  up(d_rslot, rows_slot.data(), rows_slot.size() * sizeof(int));
-  up(d_rall, rows_all.data(), rows_all.size() * sizeof(int));
-  up(d_rsh, rows_sh.data(), rows_sh.size() * sizeof(int));
-  up(d_lms, lms.data(), nl * sizeof(int));
-  up(d_val, vv.data(), ne * sizeof(double));
-  for (int i = 0; i < n; ++i) { up(d_prow[i], t.prow[i].data(), t.prow[i].size() * sizeof(int)); up(d_map[i], t.map[i].data(), t.map[i].size() * sizeof(int)); }
-  if (e != hipSuccess) { (void)hipStreamSynchronize(s); release(); SL_HIP(e); }
-  // R = J^T, then X = K^-1 R in S
-  launch_scatter(d_rc, d_val, ne, Rb, (int)N, s);
-  JMSum sA{};
-  JSigGather gA{};
-  for (int i = 0; i < n; ++i) {
-    sA.src[i] = Rb + off[1 + i];
-    gA.dst[i] = X + off[1 + i]; gA.map[i] = d_map[i]; gA.lds[i] = (long long)N; gA.o0[i] = t.Tc[i] * NB; gA.n[i] = t.gn[i];
-  }
-  sA.dst = Rb + off[0]; sA.ld = (long long)N;
-  gA.src = X + off[0]; gA.lds_src = (long long)N;
-  for (const Launch& L : plan) {
-    if (L.kind == 0) launch_jms_push(d_sys, d_jobs + L.j0, L.nj, L.maxl, d_lst, ncol, L.bwd, s);
-    else if (L.kind == 1) launch_jms_pull(d_sys, d_jobs + L.j0, L.nj, d_lst, ncol, L.bwd, s);
-    else if (L.kind == 2) launch_jms_sum(sA, d_sptr, d_sent, Tsep * NB, ncol, s);
-    else launch_jms_gather(gA, n, max_gn, ncol, s);
-  }
-  // the grams: poses of `slot`, poses of every robot, private point landmarks (through V), shared point landmarks
-  double* Mp = Md;
-  launch_gram(X, N, ncol, d_rslot, (int)rows_slot.size(), Mp, s);
-  launch_gram(X, N, ncol, d_rall, (int)rows_all.size(), Mp + (size_t)ncol * ncol, s);
-  for (int i = 0; i < n; ++i)
-    launch_landmark_V(hG[i], X + off[1 + i], (int)N, ncol, d_lms + lm0[i], lm0[i + 1] - lm0[i], V + 9 * (size_t)lm0[i], ldv, s, d_prow[i]);
-  launch_gram(V, ldv, ncol, nullptr, (int)(9 * nl), Mp + 2 * (size_t)ncol * ncol, s);
-  launch_gram(X, N, ncol, d_rsh, (int)rows_sh.size(), Mp + 3 * (size_t)ncol * ncol, s);
-  // the rows of U at the trajectory's poses (for C = I + J U)
-  std::vector<double> M(4 * (size_t)ncol * ncol), Urow((size_t)n_q * 6 * ncol);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(M.data(), Md, M.size() * sizeof(double), hipMemcpyDeviceToHost, s);
-  for (int q = 0; q < n_q && e == hipSuccess; ++q)
-    e = hipMemcpy2DAsync(Urow.data() + (size_t)q * 6 * ncol, 6 * sizeof(double), X + prow_of(qs[q], ids[q]), N * sizeof(double),
-                         6 * sizeof(double), ncol, hipMemcpyDeviceToHost, s);
-  const hipError_t e2 = hipStreamSynchronize(s);
-  release();
-  SL_HIP(e);
-  SL_HIP(e2);
-  std::vector<double> Cm((size_t)ncol * ncol, 0.0);
-  for (int a = 0; a < ncol; ++a) Cm[(size_t)a * ncol + a] = 1.0;
-  for (size_t k = 0; k < vv.size(); ++k) {          // (J U)[jrow][col] += J[jrow][row] U[row][col]
-    const int row = rcv[2 * k], jrow = rcv[2 * k + 1];
-    const int qa = row_of[row];
-    const double* u = Urow.data() + (size_t)(qa / 6) * 6 * ncol + qa % 6;
-    for (int c = 0; c < ncol; ++c) Cm[(size_t)jrow * ncol + c] += vv[k] * u[6 * (size_t)c];
-  }
-  const double* Ms[4] = {M.data(), M.data() + (size_t)ncol * ncol, M.data() + 2 * (size_t)ncol * ncol, M.data() + 3 * (size_t)ncol * ncol};
-  double gs[4];
-  if ((rc = woodbury_drops(Cm, ncol, Ms, 4, gs)) != SLIDE_OK) return rc;
-  out4[1] = gs[0];
-  out4[2] = gs[2] + gs[3];
-  out4[0] = 10.0 * out4[1] + out4[2];
-  out4[3] = gs[1];
   return SLIDE_OK;
 }
 }  // namespace sl

@@ -23,6 +23,7 @@ namespace sl {
 extern thread_local std::string g_last_error;
 void thread_capture_mode_local();      // (host_graph.hip) once per host thread: stream-capture mode thread-local
 bool hip_ok(hipError_t e, const char* what);
+inline bool robot_ok(int r) { return r >= 0 && r < SLIDE_MAX_ROBOTS; }
 int decode_status(const int* st8);      // status words of a pass -> SLIDE_OK / SLIDE_ERR_NOT_SPD / SLIDE_ERR_RUNTIME (+ g_last_error)
 #define SL_HIP(x)                                     \
   do {                                                \
@@ -145,6 +146,8 @@ struct PendFac {
 // all of them, and every graph's stream continues behind the batch.  All joined graphs must solve in lockstep (the distributed
 // pass does); a rendezvous that is not completed within 60 s returns SLIDE_ERR_RUNTIME.
 class HostGraph;
+// what an information-gain query reads back: the gram matrices, the rows of U at the trajectory's poses (for C = I + J U)
+struct GainFetched { std::vector<double> M, Urow; };
 class CholBatch {
  public:
   explicit CholBatch(int n);
@@ -190,6 +193,7 @@ class CholBatch {
   hipStream_t pass_stream();                             // the stream the passes run on (created on first use)
   int profile_pass(double* const* d_bufs, double* ms_steps, int* n_launches);
   int profile_arrow(double* const* d_bufs, double* out6, int* n_sep_steps);
+  // (the queries from here on: host_marginals.hip)
   // marginal covariances on the JOINT graph, from the factor the last exact joint pass (pass_all) left (joint_cov_kernels.hip): the
   // poses of the graph in `slot` by its pose indices, its landmarks by its landmark ids, logEntropy's trace sums (job-wide landmarks)
   int joint_pose_covariances(int slot, const uint64_t* idx, int n, double* out36n);
@@ -316,6 +320,10 @@ class CholBatch {
   void free_joint_sigma();
   int joint_state(const char* who, int slot);      // SLIDE_ERR_INVALID (+ message) unless the last exact pass's factor is resident
   int ensure_joint_sigma();
+  // kept between the joint gain queries (under pass_mtx): freeing these megabytes right after device-to-host copies filled them
+  // made glibc trim the heap under the runtime's pinning, 14 - 25 ms per m = 64 query
+  GainFetched ig_host;
+  int compute_joint_sigma();                       // (ensure_joint_sigma's work; it drops the jsig_* buffers when this fails)
   // the exact joint pass's elimination tree (system 0: the separator, 1 + i: robot i): every system's JSinvSys (Sg, Z left null, lds its
   // rows), the tile rows of every column, and per robot its backward steps, segments, border map and pose rows
   struct JointTree {
@@ -326,9 +334,23 @@ class CholBatch {
     std::vector<int> T, Tc, Trow, gn;                          // per robot: band, factor columns, rows; rows of separator coordinates past Tc NB
     std::vector<std::vector<int>> map, prow;                   // per robot: border coordinate -> separator row (-1: padding); a pose's first row
     int Ts = 0, Tsep = 0, sTa = 0, sTL = 0;                    // separator: landmark tiles, all tiles, end of leaf a, end of leaf b (0: not dissected)
+    // K X = R with many right-hand sides through the tree (k_jms_*): the launches in stream order, their jobs (system, tile, [l0, l1)
+    // of lst), and the separator's rows as sums of the robots' (the inverse of the border maps, robot order)
+    struct SolvePlan {
+      struct Launch { int kind, bwd, j0, nj, maxl; };          // kind 0: push, 1: pull, 2: sum, 3: gather
+      std::vector<Launch> launches;
+      std::vector<int4> jobs;
+      std::vector<int> lst, sptr{0};
+      std::vector<int2> sent;
+      int max_gn = 0;
+    };
+    void solve_plan(SolvePlan& p) const;
   };
   void joint_tree(JointTree& t) const;
   int joint_robot(int slot) const;                 // robot id of the graph's own poses
+  // the job's point landmarks: every graph's private ones (landmark ids), and of each shared slot that holds one, once, its offset in
+  // the separator system
+  void job_point_landmarks(std::vector<std::vector<int>>& priv, std::vector<int>& shared_off) const;
 };
 
 class HostGraph {
@@ -347,7 +369,8 @@ class HostGraph {
   int add_relative_meas_ghost(const double* rel7, uint64_t idx, int robot, int slot, bool local_first);
   int set_ghosts(const int32_t* own_robot, const int64_t* own_idx, int n_slots);
   int pose_covariance(int robot, uint64_t idx, double* cov36);
-  // marginals on the selected inverse of the resident factor, loop-closure information gain (cov_kernels.hip; single-graph path only)
+  // marginals on the selected inverse of the resident factor, loop-closure information gain (host_marginals.hip, cov_kernels.hip;
+  // single-graph path only)
   int pose_covariances(int robot, const uint64_t* idx, int n, double* out36n);
   int landmark_covariances(int cls, const uint64_t* idx, int n, double* out);
   int marginal_traces(int robot, double* out4);
@@ -538,6 +561,7 @@ class HostGraph {
   DevArr<double> d_igval;
   int marginal_state(const char* who) const;      // SLIDE_ERR_INVALID (+ message) unless a single-graph factorisation is resident
   int ensure_sigma();
+  int pose_id(int robot, uint64_t idx) const;     // the uploaded pose's index, or -1
   void robot_poses(int robot, std::vector<int>& out) const;
   void point_landmarks(std::vector<int>& out) const;
   DevArr<int> d_status;

@@ -1,5 +1,5 @@
 """estimateClosureInfoGain on the JOINT multi-robot graph (CholBatch.closure_info_gain / PassDriver.closure_info_gain,
-joint_cov_kernels.hip's k_jms_*) against the dense joint Gauss-Newton H of gn_reference, which shares no code with the kernels.
+joint_cov_kernels.hip's k_jms_*, host side in host_marginals.hip) against the dense joint Gauss-Newton H of gn_reference, which shares no code with the kernels.
 
 Per case: the shards of tests/test_gpu_joint_step.py's Run, H at the values read before one exact joint pass (the point the pass
 linearises at), the candidate Between rows J_f from orc_linearize(F_BETWEEN, ..) at those values with (robot, index) endpoints, and the

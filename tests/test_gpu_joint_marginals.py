@@ -1,5 +1,5 @@
 """Marginal covariances on the JOINT multi-robot graph (CholBatch.get_pose_covariances / get_landmark_covariances / marginal_traces,
-joint_cov_kernels.hip) against the dense inverse of the joint Gauss-Newton H of gn_reference (the full whitened Jacobian of one graph
+joint_cov_kernels.hip, host side in host_marginals.hip) against the dense inverse of the joint Gauss-Newton H of gn_reference (the full whitened Jacobian of one graph
 holding every robot, tests/joint_graphs.py), which shares no code with the kernels.
 
 Per case: the shards of tests/test_gpu_joint_step.py's Run, one exact joint pass, then every pose of every robot and every landmark of

@@ -1,5 +1,5 @@
-"""The many-right-hand-side solve over the exact joint pass's elimination tree (joint_cov_kernels.hip's k_jms_*, CholBatch::
-joint_closure_info_gain), restated in numpy on the synthetic layout of tests/test_joint_selected_inverse.py and checked
+"""The many-right-hand-side solve over the exact joint pass's elimination tree (joint_cov_kernels.hip's k_jms_*; host side
+CholBatch::joint_closure_info_gain and its schedule JointTree::solve_plan in host_marginals.hip), restated in numpy on the synthetic layout of tests/test_joint_selected_inverse.py and checked
 against np.linalg.solve.  The joint factor is split into the systems the device holds: every robot (its own tiles, then its rows of
 separator coordinates, reached through a border map with a padding tile) and the separator.  The schedule is the host's: per node,
 forward pushes inside the node and pulls from the nodes below; the robots' separator rows summed into the separator in robot order;

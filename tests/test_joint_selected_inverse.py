@@ -1,4 +1,5 @@
-"""The selected inverse over the exact joint pass's elimination tree (joint_cov_kernels.hip), restated in numpy on
+"""The selected inverse over the exact joint pass's elimination tree (joint_cov_kernels.hip; host side CholBatch::joint_tree /
+ensure_joint_sigma in host_marginals.hip), restated in numpy on
 synthetic systems laid out like the pass — two robots whose bands fall into segments with a window of poses between them, a separator
 of two leaves and a top block, and a lambda block factored as its negative (D = -I) — and checked against np.linalg.inv.  Plus the
 C-ABI: the three joint calls are declared in slide_gpu.h and exported by the built library."""
