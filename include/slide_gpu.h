@@ -492,6 +492,12 @@ void slide_place_default_params(slide_place_params_t* p);
  * (caller buffers of nq entries).  Returns the best inlier count (>= 0) or a negative SLIDE_ERR_*. */
 int slide_match_maps(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t* p,
                      double best_xyyaw[3], int32_t* pair_ref_idx, int32_t* pair_qry_idx, int64_t* n_candidates);
+/* The same sweep (the same host path and launches as slide_match_maps), read back whole: cand_xyyaw (3 per candidate) and
+ * cand_inliers (1 per candidate) in lattice order (ring, x, y, then yaw), best_index = the candidate the device arg-max chose (the first
+ * of the maximum; -1 when the lattice is empty).  n_candidates is always filled; SLIDE_ERR_CAPACITY when it exceeds `capacity`
+ * (nothing is launched then) or when the maps exceed the kernels' on-chip image.  A test seam: the product calls slide_match_maps. */
+int slide_match_maps_sweep(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t* p, double* cand_xyyaw,
+                           int32_t* cand_inliers, int64_t capacity, int64_t* n_candidates, int64_t* best_index);
 /* PlaceRecognition::findInterLoopClosure :498-538 (centring, sweep, inlier gate, Kabsch refinement).
  * Returns 1 found / 0 not found / negative error.  tf16: 4x4 row-major query->reference. */
 int slide_find_inter_loop_closure(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t* p,

@@ -537,6 +537,43 @@ int orc_match_maps(const double* ref7, int nr, const double* qry7, int nq, const
   for (size_t i = 0; i < R.ref_idx.size(); ++i) { pair_ref_idx[i] = R.ref_idx[i]; pair_qry_idx[i] = R.qry_idx[i]; }
   return R.best_inliers;
 }
+// Inlier count of EVERY candidate of the same sweep, in lattice order (ring, x, y, then yaw): the loops of match_maps_ranges around
+// slidematch_count, the candidates spread over OpenMP threads (each count is independent).  Returns the number of candidates; writes
+// counts (and, when xyyaw_out is given, the candidate triples) only when it is <= cap.
+long long orc_match_maps_counts(const double* ref7, int nr, const double* qry7, int nq, const OrcPlaceParams* p, int* counts_out,
+                                double* xyyaw_out, long long cap) {
+  PlaceParams P = place_params_from(p);
+  double mx = 0, my = 0;
+  for (int i = 0; i < nr; ++i) { mx = std::max(mx, std::fabs(ref7[7 * i + 1])); my = std::max(my, std::fabs(ref7[7 * i + 2])); }
+  for (int i = 0; i < nq; ++i) { mx = std::max(mx, std::fabs(qry7[7 * i + 1])); my = std::max(my, std::fabs(qry7[7 * i + 2])); }
+  if (!P.disable_yaw_search) { mx = my = std::max(mx, my); }
+  const double x_half = mx * P.dilation_factor, y_half = my * P.dilation_factor;
+  std::vector<double> yaws, cand;
+  slidematch_yaws(P, yaws);
+  const double outer = 10 * P.xy_step;
+  const int steps = (int)std::ceil(std::min(x_half, y_half) / outer);
+  if (steps <= 0) return 0;
+  const double sx = x_half / (double)steps, sy = y_half / (double)steps;
+  if (sx < P.xy_step || sy < P.xy_step) return 0;
+  const int nrings = (P.max_rings >= 0) ? std::min(P.max_rings, steps) : steps;
+  for (int cur = 0; cur < nrings; ++cur) {
+    const double cs = (double)cur;
+    const double x_pe = (cs + 1) * sx, x_ns = -(cs + 1) * sx, x_lb = -cs * sx, x_rb = cs * sx;
+    const double y_pe = (cs + 1) * sy, y_ns = -(cs + 1) * sy, y_lb = -cs * sy, y_rb = cs * sy;
+    for (double x = x_ns; x <= x_pe; x += P.xy_step)
+      for (double y = y_ns; y <= y_pe; y += P.xy_step) {
+        if ((x >= x_lb && x <= x_rb) && (y >= y_lb && y <= y_rb)) continue;
+        for (double yaw : yaws) { cand.push_back(x); cand.push_back(y); cand.push_back(yaw); }
+      }
+  }
+  const long long n = (long long)(cand.size() / 3);
+  if (n > cap) return n;
+  if (xyyaw_out) std::memcpy(xyyaw_out, cand.data(), sizeof(double) * cand.size());
+#pragma omp parallel for schedule(dynamic, 64)
+  for (long long c = 0; c < n; ++c)
+    counts_out[c] = slidematch_count(ref7, nr, qry7, nq, cand[3 * c], cand[3 * c + 1], cand[3 * c + 2], P, nullptr, nullptr);
+  return n;
+}
 int orc_find_transformation(const double* ref7, int nr, const double* qry7, int nq, const OrcPlaceParams* p,
                             double* tf16, int* inliers, double* xyzyaw) {
   PlaceParams P = place_params_from(p);

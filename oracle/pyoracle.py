@@ -61,6 +61,7 @@ def lib(native: bool = False):
     L.orc_graph_create.restype = C.c_void_p
     L.orc_backend_create.restype = C.c_void_p
     L.orc_backend_graph.restype = C.c_void_p
+    L.orc_match_maps_counts.restype = C.c_longlong
     if not native:
         _LIB = L
     return L

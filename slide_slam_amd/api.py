@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libslide_gpu.so")
 _LIB = None
 
 SLIDE_OK, SLIDE_MISSING = 0, 1
+SLIDE_ERR_CAPACITY = -3
 ERR = {-1: "SLIDE_ERR_INVALID", -2: "SLIDE_ERR_NOT_SPD", -3: "SLIDE_ERR_CAPACITY", -4: "SLIDE_ERR_HIP", -5: "SLIDE_ERR_RUNTIME"}
 CHART_CAYLEY, CHART_EXPMAP = 0, 1
 CLS_CYLINDER, CLS_CUBE, CLS_ELLIPSOID = 0, 1, 2
@@ -33,7 +34,7 @@ EXPORTS = [
     "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
-    "slide_place_default_params", "slide_match_maps", "slide_find_inter_loop_closure", "slide_find_intra_loop_closure",
+    "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_intra_loop_closure",
     "slide_loop_candidate_idx", "slide_clipper_affinity",
     "slide_closest_stamp", "slide_clipper_default_params", "slide_clipper_dense_clique", "slide_match_triangles",
     "slide_estimate_tf2d", "slide_semantic_clipper", "slide_find_relative_meas_match", "slide_delaunay_2d", "slide_run_semantic_clipper",
@@ -755,6 +756,31 @@ def match_maps(ref7, qry7, params: PlaceParams):
         _check(inl)
     k = max(inl, 0)
     return dict(inliers=int(inl), xyyaw=best, ref_idx=pr[:k], qry_idx=pq[:k], candidates=int(nc.value))
+
+
+def match_maps_sweep(ref7, qry7, params: PlaceParams, capacity=None):
+    """slide_match_maps_sweep: the whole sweep of match_maps read back.  Returns dict(status, candidates, xyyaw (n, 3), inliers (n,),
+    best_index); status SLIDE_ERR_CAPACITY (candidates still filled) when the lattice exceeds `capacity` or the maps the on-chip image.
+    capacity=None: sized by a first call that launches nothing."""
+    ref7, qry7 = _d(ref7), _d(qry7)
+    nr, nq = ref7.shape[0], qry7.shape[0]
+    nc, bi = C.c_int64(0), C.c_int64(-1)
+
+    def call(cap):
+        xy, inl = np.zeros((max(cap, 1), 3)), np.zeros(max(cap, 1), np.int32)
+        rc = lib().slide_match_maps_sweep(_p(ref7), C.c_int(nr), _p(qry7), C.c_int(nq), C.byref(params), _p(xy), _p(inl),
+                                          C.c_int64(cap), C.byref(nc), C.byref(bi))
+        return rc, xy, inl
+    if capacity is None:
+        rc, xy, inl = call(0)
+        if rc == SLIDE_ERR_CAPACITY and nc.value > 0:
+            rc, xy, inl = call(nc.value)
+    else:
+        rc, xy, inl = call(int(capacity))
+    if rc not in (SLIDE_OK, SLIDE_ERR_CAPACITY):
+        _check(rc)
+    n = nc.value if rc == SLIDE_OK else 0
+    return dict(status=int(rc), candidates=int(nc.value), xyyaw=xy[:n], inliers=inl[:n], best_index=int(bi.value))
 
 
 def find_inter_loop_closure(ref7, qry7, params: PlaceParams):

@@ -302,6 +302,9 @@ void launch_place_sweep(const PlaceDev& P, hipStream_t s) {
     hipLaunchKernelGGL(k_place_sweep_b, dim3((unsigned)blocks), dim3(256), lds, s, P, cosv, sinv);
     return;
   }
+  // (the same opt-in as above: a reference map of more than 1365 objects takes more than the 64 KiB a launch gets without it)
+  static const bool attr_plain = (hipFuncSetAttribute(reinterpret_cast<const void*>(k_place_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), true);
+  (void)attr_plain;
   hipLaunchKernelGGL(k_place_sweep, dim3((unsigned)blocks), dim3(256), (size_t)P.nr * 6 * sizeof(double), s, P, cosv, sinv);
 }
 void launch_place_argmax(const int32_t* inliers, long long n, long long* best_idx, int32_t* best_val, hipStream_t s) {
