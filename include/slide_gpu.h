@@ -131,6 +131,20 @@ int slide_graph_marginal_traces(slide_graph_t* g, int robot, double out4[4]);
 #define SLIDE_INFO_GAIN_MAX_STEPS 64
 int slide_graph_closure_info_gain(slide_graph_t* g, int robot, const uint64_t* traj, int n, const double* travel, const double sigma_per_m[6],
                                   double out3[3]);
+/* estimateClosureInfoGain (graph.cpp:469-623; the planner's request is srv/EvaluateLoopClosure.srv) for a LIST of candidates, ranked in
+ * one call: candidate k is the trajectory traj[off[k] .. off[k+1]), travel runs parallel to traj (entry off[k] + i belongs to step i of
+ * candidate k; the last entry of each candidate is not read), sigma_per_m = NULL as above.  out3n[3 k ..] is exactly what
+ * slide_graph_closure_info_gain documents for candidate k alone: every candidate is evaluated by itself against the resident factor,
+ * candidates do not accumulate, and a candidate's result does not depend on what else is in the list.  The list is cut into sweeps of
+ * whole candidates of at most SLIDE_INFO_GAIN_SWEEP_COLS columns (six per step); a sweep is one many-column solve, per-candidate
+ * block-diagonal grams and a per-candidate Woodbury step on the device.  Any n_cand >= 1.
+ * Whole-call refusals are those of slide_graph_closure_info_gain (nothing is written then); n_cand < 1, off = NULL or a decreasing off:
+ * SLIDE_ERR_INVALID.  Otherwise SLIDE_OK, and a candidate's own fault goes to status[k] (status may be NULL) with zeros in its outputs:
+ * SLIDE_MISSING for an unknown pose, SLIDE_ERR_INVALID for fewer than two poses or a travel distance <= 0, SLIDE_ERR_CAPACITY for more
+ * than SLIDE_INFO_GAIN_MAX_STEPS steps, SLIDE_ERR_NOT_SPD if its I + J Sigma J^T is not positive definite. */
+#define SLIDE_INFO_GAIN_SWEEP_COLS 384
+int slide_graph_closure_info_gain_batch(slide_graph_t* g, int robot, int n_cand, const int32_t* off, const uint64_t* traj,
+                                        const double* travel, const double sigma_per_m[6], double* out3n, int32_t* status);
 /* counts: [poses, landmarks, factors, relinearised vars in the last solve, chol dim] */
 int slide_graph_stats(slide_graph_t* g, int64_t out5[5]);
 /* Sum of squared whitened residuals of every factor at the current estimate (= 2 x gtsam::NonlinearFactorGraph::error of the graph
@@ -209,6 +223,14 @@ int slide_chol_batch_marginal_traces(slide_chol_batch_t* b, int slot, double out
  * the batch's stream outside any capture and writes nothing a pass reads (the cached joint Sigma included). */
 int slide_chol_batch_closure_info_gain(slide_chol_batch_t* b, int slot, const int32_t* traj_slots, const uint64_t* traj, int n,
                                        const double* travel, const double sigma_per_m[6], double out4[4]);
+/* estimateClosureInfoGain (graph.cpp:469-623; srv/EvaluateLoopClosure.srv) on the JOINT graph for a LIST of candidates: the arguments of
+ * slide_graph_closure_info_gain_batch, with traj_slots running parallel to traj (NULL: every pose in `slot`).  out4n[4 k ..] is exactly
+ * what slide_chol_batch_closure_info_gain documents for candidate k alone; sweeps, per-candidate status and independence as there.
+ * Whole-call refusals are those of slide_chol_batch_closure_info_gain (nothing is written then); a slot of traj_slots outside the batch
+ * is that candidate's SLIDE_ERR_INVALID. */
+int slide_chol_batch_closure_info_gain_batch(slide_chol_batch_t* b, int slot, int n_cand, const int32_t* off, const int32_t* traj_slots,
+                                             const uint64_t* traj, const double* travel, const double sigma_per_m[6], double* out4n,
+                                             int32_t* status);
 /* The same pass for a job that spans GPUs, cut at its two exchanges (8 / N robots on each of N GPUs): every part is a captured
  * hipGraph replayed on the batch's stream.
  *   part 0: phase 0 of every robot + the local sum -> every local buffer holds this GPU's sum of the 54-doubles-per-slot blocks;

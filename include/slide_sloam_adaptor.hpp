@@ -30,6 +30,8 @@ namespace slide {
 struct Error : std::runtime_error {
   int code;
   Error(int c, const char* what) : std::runtime_error(std::string(what) + ": " + slide_last_error()), code(c) {}
+  // the whole message (a fault the library reported in a status word, not through slide_last_error)
+  Error(int c, const std::string& message) : std::runtime_error(message), code(c) {}
 };
 
 // tx ty tz qx qy qz qw — geometry_msgs/Pose order, T_world<-sensor (graph.h:44)
@@ -190,6 +192,44 @@ class SemanticFactorGraph {
     detail::check(rc, "estimateClosureInfoGain");
     if (rc == SLIDE_MISSING) throw std::out_of_range("estimateClosureInfoGain: trajectory pose not in the graph");
     return o[0];
+  }
+  // estimateClosureInfoGain for a list of candidates, ranked in one call (slide_graph_closure_info_gain_batch): one value per
+  // candidate, 10 * info_gain_pose + info_gain_landmark as above, each candidate evaluated alone; throws as estimateClosureInfoGain
+  // does, for the first candidate with a fault
+  std::vector<double> estimateClosureInfoGains(const std::vector<std::vector<size_t>>& candidateTrajPoseIndices,
+                                               const std::vector<std::vector<double>>& travel_distances, const int& robotID = 0) const {
+    if (candidateTrajPoseIndices.size() != travel_distances.size())
+      throw Error(SLIDE_ERR_INVALID, "estimateClosureInfoGains: one list of travel distances per candidate");
+    if (!noise_model_pose_vec_per_m.empty() && noise_model_pose_vec_per_m.size() != 6)
+      throw Error(SLIDE_ERR_INVALID, "estimateClosureInfoGains: noise_model_pose_vec_per_m has six entries");
+    const size_t n = candidateTrajPoseIndices.size();
+    std::vector<int32_t> off(n + 1, 0), status(n, 0);
+    std::vector<uint64_t> traj;
+    std::vector<double> travel;
+    for (size_t k = 0; k < n; ++k) {
+      const std::vector<size_t>& t = candidateTrajPoseIndices[k];
+      if (t.size() != travel_distances[k].size() + 1)
+        throw Error(SLIDE_ERR_INVALID, "estimateClosureInfoGains: one travel distance per step of the trajectory");
+      traj.insert(traj.end(), t.begin(), t.end());
+      travel.insert(travel.end(), travel_distances[k].begin(), travel_distances[k].end());
+      travel.push_back(0.0);                        // (parallel to traj: a candidate's last entry is not read)
+      off[k + 1] = (int32_t)traj.size();
+    }
+    std::vector<double> o(3 * n, 0.0), gains(n, 0.0);
+    detail::check(slide_graph_closure_info_gain_batch(g_, robotID, (int)n, off.data(), traj.data(), travel.data(),
+                                                      noise_model_pose_vec_per_m.empty() ? nullptr : noise_model_pose_vec_per_m.data(),
+                                                      o.data(), status.data()),
+                  "estimateClosureInfoGains");
+    for (size_t k = 0; k < n; ++k) {
+      if (status[k] == SLIDE_MISSING) throw std::out_of_range("estimateClosureInfoGains: trajectory pose not in the graph");
+      if (status[k] != SLIDE_OK)
+        throw Error(status[k], "estimateClosureInfoGains: candidate " + std::to_string(k) + ": " +
+                                   (status[k] == SLIDE_ERR_CAPACITY  ? "more than SLIDE_INFO_GAIN_MAX_STEPS steps"
+                                    : status[k] == SLIDE_ERR_NOT_SPD ? "I + J Sigma J^T is not positive definite"
+                                                                     : "fewer than two poses or a travel distance <= 0"));
+      gains[k] = o[3 * k];
+    }
+    return gains;
   }
   // graph.h:115 (never set in the reference): empty = the graph's own noise_model_odom_vec, else six sigmas per metre
   std::vector<double> noise_model_pose_vec_per_m;

@@ -29,7 +29,7 @@ EXPORTS = [
     "slide_graph_add_loop_closure", "slide_graph_add_relative_meas", "slide_graph_add_point_landmark",
     "slide_graph_add_range_bearing", "slide_graph_add_cube", "slide_graph_add_cylinder", "slide_graph_solve",
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
-    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_closure_info_gain", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
+    "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_closure_info_gain_batch", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_closure_info_gain", "slide_chol_batch_closure_info_gain_batch", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
     "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
@@ -153,6 +153,38 @@ def _p(a):
     v = _Ptr(a.ctypes.data)
     v.keep = a
     return v
+
+
+def _candidate_list(trajs, travels, traj_slots=None):
+    """The flat arguments of the *_closure_info_gain_batch calls: off (n + 1), traj, travel (parallel to traj: a candidate's last
+    entry is padding) and, when given, traj_slots."""
+    if len(trajs) != len(travels) or (traj_slots is not None and len(traj_slots) != len(trajs)):
+        raise ValueError("one list of travel distances (and of slots) per trajectory")
+    off = np.zeros(len(trajs) + 1, dtype=np.int32)
+    for k, t in enumerate(trajs):
+        off[k + 1] = off[k] + len(t)
+    traj = np.zeros(int(off[-1]), dtype=np.uint64)
+    travel = np.zeros(int(off[-1]), dtype=np.float64)
+    slots = np.zeros(int(off[-1]), dtype=np.int32) if traj_slots is not None else None
+    for k, (t, d) in enumerate(zip(trajs, travels)):
+        if len(d) != max(len(t) - 1, 0):
+            raise ValueError("travel needs one distance per step of traj")
+        traj[off[k]:off[k + 1]] = np.asarray(t, dtype=np.uint64).reshape(-1)
+        travel[off[k]:off[k] + len(d)] = np.asarray(d, dtype=np.float64).reshape(-1)
+        if slots is not None:
+            if len(traj_slots[k]) != len(t):
+                raise ValueError("traj_slots needs one slot per pose of traj")
+            slots[off[k]:off[k + 1]] = np.asarray(traj_slots[k], dtype=np.int32).reshape(-1)
+    return off, traj, travel, slots
+
+
+def _sigma6(sigma_per_m):
+    if sigma_per_m is None:
+        return None
+    sg = _d(sigma_per_m).reshape(-1)
+    if len(sg) != 6:
+        raise ValueError("sigma_per_m has six entries")
+    return sg
 
 
 class SlideGraph:
@@ -301,6 +333,20 @@ class SlideGraph:
             raise KeyError(f"trajectory pose of robot {robot} not in the graph")
         _check(st)
         return out
+
+    def closure_info_gain_batch(self, robot, trajs, travels, sigma_per_m=None):
+        """closure_info_gain for a list of candidates in one call (slide_graph_closure_info_gain_batch): trajs[k] / travels[k] as the
+        single call's arguments.  Returns ((n, 3) gains, (n,) int32 status): row k is what closure_info_gain gives for candidate k
+        alone; a candidate with a fault of its own (SLIDE_MISSING, SLIDE_ERR_INVALID, _CAPACITY, _NOT_SPD) has zeros and its code."""
+        off, traj, travel, _ = _candidate_list(trajs, travels)
+        sg = _sigma6(sigma_per_m)
+        out = np.zeros((len(trajs), 3))
+        status = np.zeros(len(trajs), dtype=np.int32)
+        vp = C.c_void_p
+        _check(self.L.slide_graph_closure_info_gain_batch(
+            self.h, C.c_int(robot), C.c_int(len(trajs)), off.ctypes.data_as(vp), traj.ctypes.data_as(vp), travel.ctypes.data_as(vp),
+            sg.ctypes.data_as(vp) if sg is not None else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
+        return out, status
 
     def set_ghosts(self, own_robot, own_idx):
         r = _i(own_robot)
@@ -501,6 +547,22 @@ class CholBatch:
             raise KeyError(f"trajectory pose not in the joint graph (slot {slot})")
         _check(st)
         return out
+
+    def closure_info_gain_batch(self, slot, trajs, travels, sigma_per_m=None, traj_slots=None):
+        """closure_info_gain on the JOINT graph for a list of candidates in one call (slide_chol_batch_closure_info_gain_batch):
+        trajs[k] / travels[k] / traj_slots[k] as the single call's arguments (traj_slots None: every pose in `slot`).  Returns
+        ((n, 4) gains, (n,) int32 status): row k is what closure_info_gain gives for candidate k alone; a candidate with a fault of
+        its own has zeros and its code."""
+        off, traj, travel, slots = _candidate_list(trajs, travels, traj_slots)
+        sg = _sigma6(sigma_per_m)
+        out = np.zeros((len(trajs), 4))
+        status = np.zeros(len(trajs), dtype=np.int32)
+        vp = C.c_void_p
+        _check(self.L.slide_chol_batch_closure_info_gain_batch(
+            C.c_void_p(self.h), C.c_int(slot), C.c_int(len(trajs)), off.ctypes.data_as(vp),
+            slots.ctypes.data_as(vp) if slots is not None else None, traj.ctypes.data_as(vp), travel.ctypes.data_as(vp),
+            sg.ctypes.data_as(vp) if sg is not None else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
+        return out, status
 
     def set_pcg(self, iterations, tol=0.0):
         """PCG iterations of the joint solve after the factorisations (0 = every robot's own block solve only); tol > 0: iterations

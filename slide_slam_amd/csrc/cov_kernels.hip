@@ -395,6 +395,182 @@ void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nro
   if (ncol > 0) hipLaunchKernelGGL(k_gram, dim3(nb, nb), dim3(256), 0, s, X, ldx, ncol, rows, nrows, M);
 }
 
+// ---- many candidates side by side (closure_info_gain_batch): candidate k owns the columns c0 .. c0 + nk - 1 of U -------------------------
+// Only the nk x nk diagonal blocks of U^T U are formed.  A job is one 16x16 tile of one candidate's block over one split of the row
+// list: {candidate, tile row, tile column, split}; split s of a candidate's nsplit covers the rows [s rps, (s + 1) rps), rps the
+// rows per split rounded up to 64.  nsplit depends on nk alone and the splits are added in their order by k_gram_reduce, so a block's
+// bits depend on its own columns and the row list only — not on what else is in the launch.  No atomics.
+__global__ __launch_bounds__(256) void k_gram_blocks(const double* __restrict__ X, size_t ldx, const int* __restrict__ rows, int nrows,
+                                                     const GainCandDev* __restrict__ cand, const int4* __restrict__ jobs,
+                                                     double* __restrict__ part) {
+  __shared__ double xa[16][65], xb[16][65];
+  const int4 job = jobs[blockIdx.x];
+  const GainCandDev cd = cand[job.x];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int la = 16 * job.y, lb = 16 * job.z, nk = cd.nk;
+  const int rps = ((nrows + cd.nsplit - 1) / cd.nsplit + 63) & ~63;
+  const int q_beg = job.w * rps, q_end = q_beg + rps < nrows ? q_beg + rps : nrows;
+  double s = 0.0;
+  for (int q0 = q_beg; q0 < q_end; q0 += 64) {
+    for (int e = threadIdx.x; e < 16 * 64; e += 256) {
+      const int cc = e >> 6, qq = e & 63, q = q0 + qq;
+      const int row = q < q_end ? (rows ? rows[q] : q) : -1;
+      xa[cc][qq] = (row >= 0 && la + cc < nk) ? X[(size_t)(cd.c0 + la + cc) * ldx + row] : 0.0;
+      xb[cc][qq] = (row >= 0 && lb + cc < nk) ? X[(size_t)(cd.c0 + lb + cc) * ldx + row] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int qq = 0; qq < 64; ++qq) s += xa[ty][qq] * xb[tx][qq];
+    __syncthreads();
+  }
+  if (la + ty < nk && lb + tx < nk) part[cd.poff + (size_t)job.w * nk * nk + (size_t)(la + ty) * nk + lb + tx] = s;
+}
+// M_k = the sum of candidate k's splits, first to last (blockIdx.x = k)
+__global__ __launch_bounds__(256) void k_gram_reduce(const GainCandDev* __restrict__ cand, const double* __restrict__ part,
+                                                     double* __restrict__ M) {
+  const GainCandDev cd = cand[blockIdx.x];
+  const int nn = cd.nk * cd.nk;
+  for (int e = threadIdx.x; e < nn; e += 256) {
+    double s = 0.0;
+    for (int sp = 0; sp < cd.nsplit; ++sp) s += part[cd.poff + (size_t)sp * nn + e];
+    M[cd.moff + e] = s;
+  }
+}
+int gain_gram_splits(int nk) {
+  const int tiles = ((nk + 15) / 16) * ((nk + 15) / 16);
+  return std::max(1, std::min(32, 1024 / tiles));
+}
+void launch_gram_blocks(const double* X, size_t ldx, const int* rows, int nrows, const GainCandDev* cand, int ncand, const int4* jobs,
+                        int njobs, double* part, double* M, hipStream_t s) {
+  if (ncand <= 0) return;
+  hipLaunchKernelGGL(k_gram_blocks, dim3(njobs), dim3(256), 0, s, X, ldx, rows, nrows, cand, jobs, part);
+  hipLaunchKernelGGL(k_gram_reduce, dim3(ncand), dim3(256), 0, s, cand, (const double*)part, M);
+}
+
+// The Woodbury step of one candidate per workgroup: C = I + J U from the candidate's rows of J (jptr / jrow / jval: per column of J^T
+// the rows of U it touches, ascending) symmetrised as the host's woodbury_drops does, C = L L^T in place (right-looking, lower triangle,
+// column-major), L^-1 in place, then g_q = sum_ab (L^-T L^-1)_ab M_q,ab for the nM grams.  C lives in LDS for nk <= GAIN_LDS_DIM
+// (SMALL; leading dimension nk | 1) and in the candidate's own slice of `work` otherwise; a launch of either kind leaves the other
+// kind's candidates alone.  A pivot that is not > 0: flag[k] = 1 and zeros.  Every loop's order depends on nk alone.
+template <bool SMALL>
+__global__ __launch_bounds__(256) void k_woodbury_blocks(const double* __restrict__ U, size_t ldu, const GainCandDev* __restrict__ cand,
+                                                         const int* __restrict__ jptr, const int* __restrict__ jrow,
+                                                         const double* __restrict__ jval, const double* __restrict__ M, size_t msz, int nM,
+                                                         double* __restrict__ work, double* __restrict__ gains, int* __restrict__ flag) {
+  extern __shared__ double w_lds[];
+  __shared__ double dg[6 * GAIN_MAX_STEPS], red[GAIN_MAX_GRAMS][256];
+  const GainCandDev cd = cand[blockIdx.x];
+  const int n = cd.nk, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if ((n <= GAIN_LDS_DIM) != SMALL) return;
+  double* A = SMALL ? w_lds : work + cd.woff;
+  const int lda = SMALL ? (n | 1) : n;
+  for (int e = tid; e < n * n; e += 256) {           // C[jr][c] at A[c lda + jr]
+    const int c = e / n, jr = e - c * n;
+    double v = jr == c ? 1.0 : 0.0;
+    const double* u = U + (size_t)(cd.c0 + c) * ldu;
+    for (int t = jptr[cd.c0 + jr]; t < jptr[cd.c0 + jr + 1]; ++t) v += jval[t] * u[jrow[t]];
+    A[(size_t)c * lda + jr] = v;
+  }
+  __syncthreads();
+  for (int e = tid; e < n * n; e += 256) {
+    const int c = e / n, r = e - c * n;
+    if (r > c) A[(size_t)c * lda + r] = A[(size_t)r * lda + c] = 0.5 * (A[(size_t)c * lda + r] + A[(size_t)r * lda + c]);
+  }
+  __syncthreads();
+  bool spd = true;
+#pragma unroll 1
+  for (int j = 0; j < n; ++j) {                      // (the diagonal of L in dg, A's own diagonal is left alone)
+    const double d = A[(size_t)j * lda + j];
+    if (!(d > 0.0)) { spd = false; break; }          // (every thread reads the same d)
+    const double ljj = sqrt(d);
+    double* Aj = A + (size_t)j * lda;
+    for (int i = j + 1 + tid; i < n; i += 256) Aj[i] /= ljj;
+    if (tid == 0) dg[j] = ljj;
+    __syncthreads();
+    for (int c = j + 1 + wv; c < n; c += 4) {
+      const double lcj = Aj[c];
+      double* Ac = A + (size_t)c * lda;
+      for (int i = c + lane; i < n; i += 64) Ac[i] -= Aj[i] * lcj;
+    }
+    __syncthreads();
+  }
+  if (!spd) {
+    if (tid < nM) gains[(size_t)blockIdx.x * GAIN_MAX_GRAMS + tid] = 0.0;
+    if (tid == 0) flag[blockIdx.x] = 1;
+    return;
+  }
+  // L^-1 in place, last column first: column j below the diagonal = -(L^-1)[j+1.., j+1..] L[j+1.., j] / L[j][j]; dg <- 1 / dg
+#pragma unroll 1
+  for (int j = n - 1; j >= 0; --j) {
+    const double ij = 1.0 / dg[j];
+    const double* Aj = A + (size_t)j * lda;
+    double v[2] = {0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int i = j + 1 + tid + 256 * h;
+      if (i < n) {
+        double t = 0.0;
+        for (int k = j + 1; k < i; ++k) t += A[(size_t)k * lda + i] * Aj[k];
+        v[h] = t + dg[i] * Aj[i];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int i = j + 1 + tid + 256 * h;
+      if (i < n) A[(size_t)j * lda + i] = -v[h] * ij;
+    }
+    if (tid == 0) dg[j] = ij;
+    __syncthreads();
+  }
+  // (C^-1)_ab = sum_{k >= a} (L^-1)_ka (L^-1)_kb for a >= b; the grams are taken as M_ab + M_ba off the diagonal
+  double acc[GAIN_MAX_GRAMS];
+#pragma unroll
+  for (int q = 0; q < GAIN_MAX_GRAMS; ++q) acc[q] = 0.0;
+  for (int e = tid; e < n * n; e += 256) {
+    const int a = e / n, b = e - a * n;
+    if (b > a) continue;
+    const double *Aa = A + (size_t)a * lda, *Ab = A + (size_t)b * lda;
+    double ci = a == b ? dg[a] * dg[a] : dg[a] * Ab[a];
+    for (int k = a + 1; k < n; ++k) ci += Aa[k] * Ab[k];
+#pragma unroll
+    for (int q = 0; q < GAIN_MAX_GRAMS; ++q)
+      if (q < nM) {
+        const double* Mq = M + q * msz + cd.moff;
+        acc[q] += ci * (a == b ? Mq[(size_t)a * n + a] : Mq[(size_t)a * n + b] + Mq[(size_t)b * n + a]);
+      }
+  }
+#pragma unroll
+  for (int q = 0; q < GAIN_MAX_GRAMS; ++q) red[q][tid] = acc[q];
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st)
+#pragma unroll
+      for (int q = 0; q < GAIN_MAX_GRAMS; ++q) red[q][tid] += red[q][tid + st];
+    __syncthreads();
+  }
+  if (tid < nM) gains[(size_t)blockIdx.x * GAIN_MAX_GRAMS + tid] = red[tid][0];
+  if (tid == 0) flag[blockIdx.x] = 0;
+}
+// gains: GAIN_MAX_GRAMS per candidate (nM used); flag: 0, or 1 where C was not positive definite; small / big: a candidate of that
+// kind is in the table.  Returns non-zero when the device refuses the LDS the small kind needs (nothing launched then)
+int launch_woodbury_blocks(const double* U, size_t ldu, const GainCandDev* cand, int ncand, const int* jptr, const int* jrow,
+                           const double* jval, const double* M, size_t msz, int nM, double* work, double* gains, int* flag, bool small,
+                           bool big, hipStream_t s) {
+  constexpr size_t lds = (size_t)GAIN_LDS_DIM * (GAIN_LDS_DIM | 1) * sizeof(double);      // (72.75 KiB: past the 64 KiB a launch gets unasked)
+  if (ncand <= 0) return 0;
+  if (small) {
+    // (asked for on every call: the attribute belongs to the current device, and a refusal must not surface as a launch error)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_woodbury_blocks<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return -1;
+    }
+    hipLaunchKernelGGL((k_woodbury_blocks<true>), dim3(ncand), dim3(256), lds, s, U, ldu, cand, jptr, jrow, jval, M, msz, nM, work, gains, flag);
+  }
+  if (big) hipLaunchKernelGGL((k_woodbury_blocks<false>), dim3(ncand), dim3(256), 0, s, U, ldu, cand, jptr, jrow, jval, M, msz, nM, work, gains, flag);
+  return 0;
+}
+
 // V_l = sum_{f in factors(l)} U_{p_f} F_f for the landmarks lids[q]: V[a ldv + 9 q + c] (6m x d, c < 9, zero for c >= d).
 // U: ncol columns of nT rows; prow: a pose's first row in U (null: 6 p; a joint system's window poses sit in its border rows).
 // One workgroup per landmark, threads over the columns a.

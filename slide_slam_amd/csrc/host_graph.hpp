@@ -204,6 +204,9 @@ class CholBatch {
   // every robot's pose drop}
   int joint_closure_info_gain(int slot, const int32_t* traj_slots, const uint64_t* traj, int n, const double* travel, const double* sigma6,
                               double* out4);
+  // a list of candidates in sweeps of one many-column solve each: candidate k = traj[off[k] .. off[k + 1]), out4n[4 k ..], status[k]
+  int joint_closure_info_gain_batch(int slot, int n_cand, const int32_t* off, const int32_t* traj_slots, const uint64_t* traj,
+                                    const double* travel, const double* sigma6, double* out4n, int32_t* status);
 
  private:
   int n;
@@ -347,6 +350,7 @@ class CholBatch {
     void solve_plan(SolvePlan& p) const;
   };
   void joint_tree(JointTree& t) const;
+  struct JointGain;                                // what the joint gain queries share: the tree, the solve's schedule, the grams' row lists
   int joint_robot(int slot) const;                 // robot id of the graph's own poses
   // the job's point landmarks: every graph's private ones (landmark ids), and of each shared slot that holds one, once, its offset in
   // the separator system
@@ -375,6 +379,8 @@ class HostGraph {
   int landmark_covariances(int cls, const uint64_t* idx, int n, double* out);
   int marginal_traces(int robot, double* out4);
   int closure_info_gain(int robot, const uint64_t* traj, int n, const double* travel, const double* sigma6, double* out3);
+  int closure_info_gain_batch(int robot, int n_cand, const int32_t* off, const uint64_t* traj, const double* travel, const double* sigma6,
+                              double* out3n, int32_t* status);      // candidate k = traj[off[k] .. off[k + 1]): out3n[3 k ..], status[k]
   void join_batch(CholBatch* b, int slot);      // takes the graph's lock itself (never while the batch's is held the other way round)
   int dist_pass_local(double* d_buf);     // one distributed pass when every robot of the job is in this graph's batch (no host syncs inside)
   int add_point_landmark(uint64_t idx, const double* xyz);

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <map>
 #include <unordered_map>
 
@@ -258,43 +259,67 @@ static int woodbury_drops(std::vector<double>& Cm, int ncol, const double* M, in
 // The fake Between factors of one query.  The caller maps every pose of the trajectory to its first row of U (six consecutive rows) and
 // to its linearisation value on the device; gain_jt builds J^T from those; once U = K^-1 J^T is solved and the grams are queued,
 // gain_fetch brings what the host needs of them and gain_drops gives the trace drops.
+// A batch holds several candidates: candidate k's poses are p0[k] .. p0[k + 1] - 1 of row / val_src and its fake factors own the
+// columns col0[k] .. col0[k + 1] - 1 of J^T, so the candidates' column blocks stand side by side and share no column.
 struct GainQuery {
-  explicit GainQuery(int n) : n(n), m(n - 1), ncol(6 * (n - 1)), row(n), val_src(n) {}
-  const int n, m, ncol;                     // poses of the trajectory, fake factors, columns of J^T
+  explicit GainQuery(int n) : GainQuery(std::vector<int>{0, n}) {}
+  explicit GainQuery(const std::vector<int>& p0)
+      : p0(p0), n(p0.back()), m(n - ((int)p0.size() - 1)), ncol(6 * m), row(n), val_src(n) {
+    for (size_t k = 0; k < p0.size(); ++k) col0.push_back(6 * (p0[k] - (int)k));
+  }
+  const std::vector<int> p0;                // first pose of every candidate, then the number of poses
+  const int n, m, ncol;                     // poses of the trajectories, fake factors, columns of J^T
+  std::vector<int> col0;                    // first column of every candidate, then ncol
   std::vector<int> row;
   std::vector<const double*> val_src;
   std::vector<int> rcv;                     // J^T's entries ordered by (row, column): the pairs ...
   std::vector<double> vv;                   // ... and the values
+  int cands() const { return (int)p0.size() - 1; }
 };
-static int gain_check_steps(const uint64_t* traj, int n, const double* travel) {
+// what is wrong with one trajectory, or null
+static const char* gain_steps_fault(const uint64_t* traj, int n, const double* travel, int* code) {
   const int m = n - 1;
-  if (m < 1 || !traj || !travel) { g_last_error = "closure_info_gain: the trajectory needs at least two poses"; return SLIDE_ERR_INVALID; }
-  if (m > SLIDE_INFO_GAIN_MAX_STEPS) { g_last_error = "closure_info_gain: more than SLIDE_INFO_GAIN_MAX_STEPS steps"; return SLIDE_ERR_CAPACITY; }
+  *code = SLIDE_ERR_INVALID;
+  if (m < 1 || !traj || !travel) return "closure_info_gain: the trajectory needs at least two poses";
+  if (m > SLIDE_INFO_GAIN_MAX_STEPS) { *code = SLIDE_ERR_CAPACITY; return "closure_info_gain: more than SLIDE_INFO_GAIN_MAX_STEPS steps"; }
   for (int i = 0; i < m; ++i)
-    if (!(travel[i] > 0.0) || !std::isfinite(travel[i])) { g_last_error = "closure_info_gain: travel distances must be > 0"; return SLIDE_ERR_INVALID; }
-  return SLIDE_OK;
+    if (!(travel[i] > 0.0) || !std::isfinite(travel[i])) return "closure_info_gain: travel distances must be > 0";
+  *code = SLIDE_OK;
+  return nullptr;
+}
+static int gain_check_steps(const uint64_t* traj, int n, const double* travel) {
+  int rc;
+  if (const char* why = gain_steps_fault(traj, n, travel, &rc)) g_last_error = why;
+  return rc;
 }
 static int gain_check_sigma(const double* sigma6) {
   for (int a = 0; a < 6; ++a)
     if (!(sigma6[a] > 0.0) || !std::isfinite(sigma6[a])) { g_last_error = "closure_info_gain: sigma_per_m must be > 0"; return SLIDE_ERR_INVALID; }
   return SLIDE_OK;
 }
-// J^T, entry by entry (row of U, column 6 i + a); a repeated pose sums its blocks
+// J^T, entry by entry (row of U, column col0[k] + 6 i + a for step i of candidate k); a repeated pose sums its blocks.  val: the
+// linearisation values of the poses (12 each), travel: one entry per pose (a candidate's last one is not read)
+static void gain_jt(GainQuery& q, const double* val, const double* travel, const double* sigma6) {
+  std::map<std::pair<int, int>, double> jt;
+  for (int k = 0; k < q.cands(); ++k)
+    for (int p = q.p0[k]; p + 1 < q.p0[k + 1]; ++p) {
+      const int col = q.col0[k] + 6 * (p - q.p0[k]);
+      double Ad[6][6];
+      between_adjoint(val + 12 * (size_t)(p + 1), val + 12 * (size_t)p, Ad);      // (c_{i+1}, c_i)
+      for (int a = 0; a < 6; ++a) {
+        const double w = 1.0 / (sigma6[a] * travel[p]);
+        for (int c = 0; c < 6; ++c) jt[{q.row[p + 1] + c, col + a}] += -Ad[a][c] * w;
+        jt[{q.row[p] + a, col + a}] += w;
+      }
+    }
+  for (const auto& kv : jt) { q.rcv.push_back(kv.first.first); q.rcv.push_back(kv.first.second); q.vv.push_back(kv.second); }
+}
+// the same with the values read from the device, pose by pose (val_src)
 static int gain_jt(GainQuery& q, const double* travel, const double* sigma6, hipStream_t s) {
-  std::vector<double> val(12 * (size_t)q.n);      // the linearisation values of the trajectory's poses
+  std::vector<double> val(12 * (size_t)q.n);
   for (int k = 0; k < q.n; ++k) SL_HIP(hipMemcpyAsync(val.data() + 12 * k, q.val_src[k], 12 * sizeof(double), hipMemcpyDeviceToHost, s));
   SL_HIP(hipStreamSynchronize(s));
-  std::map<std::pair<int, int>, double> jt;
-  for (int i = 0; i < q.m; ++i) {
-    double Ad[6][6];
-    between_adjoint(val.data() + 12 * (i + 1), val.data() + 12 * i, Ad);      // (c_{i+1}, c_i)
-    for (int a = 0; a < 6; ++a) {
-      const double w = 1.0 / (sigma6[a] * travel[i]);
-      for (int c = 0; c < 6; ++c) jt[{q.row[i + 1] + c, 6 * i + a}] += -Ad[a][c] * w;
-      jt[{q.row[i] + a, 6 * i + a}] += w;
-    }
-  }
-  for (const auto& kv : jt) { q.rcv.push_back(kv.first.first); q.rcv.push_back(kv.first.second); q.vv.push_back(kv.second); }
+  gain_jt(q, val.data(), travel, sigma6);
   return SLIDE_OK;
 }
 // Behind the solve and the grams: U (leading dimension ldu) and the nM gram matrices Md on the device, to the host
@@ -325,6 +350,142 @@ static int gain_drops(const GainQuery& q, const GainFetched& h, int nM, double* 
     for (int c = 0; c < ncol; ++c) Cm[(size_t)jrow * ncol + c] += q.vv[e] * u[6 * (size_t)c];
   }
   return woodbury_drops(Cm, ncol, h.M.data(), nM, g);
+}
+
+// ---- many candidates in one call (closure_info_gain_batch on one graph and on the joint graph) -----------------------------------
+// The list is cut into sweeps of whole candidates, SLIDE_INFO_GAIN_SWEEP_COLS columns of J^T at the most.  Per sweep: the candidates'
+// column blocks of J^T side by side, ONE multi-column solve U = K^-1 J^T, per candidate the diagonal blocks of the grams
+// (k_gram_blocks) and the Woodbury step on the device (k_woodbury_blocks).  Of U, C and the grams nothing comes to the host: a sweep
+// reads back GAIN_MAX_GRAMS doubles and a flag per candidate.  Every candidate stands alone against the resident factor, and its bits do
+// not depend on its neighbours (the substitutions treat each column by itself; the new kernels' orders depend on the candidate alone).
+static_assert(GAIN_MAX_STEPS == SLIDE_INFO_GAIN_MAX_STEPS && 6 * GAIN_MAX_STEPS <= SLIDE_INFO_GAIN_SWEEP_COLS, "a sweep holds any one candidate");
+// One candidate as its back end checked and located it: st (a fault keeps it out of the sweeps), its poses' first rows in U and their
+// linearisation values, its travel distances
+struct GainCand { int st = SLIDE_OK; std::vector<int> row; std::vector<double> val; const double* travel = nullptr; };
+// What differs between the back ends.  alloc: R and U (ldu rows by the widest sweep's columns) and the back end's own tables, from the
+// query's scratch.  A sweep: begin (zero what the solve adds into), J^T scattered into R by the driver, solve (U = K^-1 R), grams (the
+// nM row sums, each through `gram`: rows of X, the list or null for 0 .. nrows - 1).
+struct GainBackend {
+  using Gram = std::function<void(int q, const double* X, size_t ldx, const int* rows, int nrows)>;
+  hipStream_t s = nullptr;
+  size_t ldu = 0;
+  int nM = 0;
+  double *R = nullptr, *U = nullptr;
+  std::function<int(Scratch& sc, int max_ncol)> alloc;
+  std::function<int(int ncol)> begin, solve;
+  std::function<void(int ncol, const Gram& gram)> grams;
+};
+// whole-call faults of a candidate list
+static int gain_check_list(int n_cand, const int32_t* off, const uint64_t* traj, const double* travel, const void* out) {
+  if (n_cand < 1 || !off || !out) { g_last_error = "closure_info_gain_batch: needs at least one candidate, its offsets and an output"; return SLIDE_ERR_INVALID; }
+  for (int k = 0; k < n_cand; ++k)
+    if (off[k] < 0 || off[k + 1] < off[k]) { g_last_error = "closure_info_gain_batch: the candidates' offsets must not decrease"; return SLIDE_ERR_INVALID; }
+  if (off[n_cand] > off[0] && (!traj || !travel)) { g_last_error = "closure_info_gain_batch: no trajectories"; return SLIDE_ERR_INVALID; }
+  return SLIDE_OK;
+}
+// g: GAIN_MAX_GRAMS doubles per candidate (nM written, zeros for a candidate with a fault); a candidate whose C is not positive definite
+// gets SLIDE_ERR_NOT_SPD
+static int gain_batch(GainBackend& be, std::vector<GainCand>& cands, const double* sigma6, double* g) {
+  hipStream_t s = be.s;
+  struct Sweep {
+    std::vector<int> ids, p0{0};
+    std::vector<GainCandDev> cd;
+    std::vector<int4> jobs;
+    size_t msz = 0, part = 0, work = 0;
+    int ncol = 0;
+  };
+  std::vector<Sweep> sweeps;
+  for (size_t k = 0; k < cands.size(); ++k) {
+    for (int q = 0; q < GAIN_MAX_GRAMS; ++q) g[GAIN_MAX_GRAMS * k + q] = 0.0;
+    if (cands[k].st != SLIDE_OK) continue;
+    const int nk = 6 * ((int)cands[k].row.size() - 1);
+    if (sweeps.empty() || sweeps.back().ncol + nk > SLIDE_INFO_GAIN_SWEEP_COLS) sweeps.emplace_back();
+    Sweep& w = sweeps.back();
+    GainCandDev cd{w.ncol, nk, gain_gram_splits(nk), 0, (long long)w.msz, (long long)w.part, (long long)w.work};
+    const int nt = (nk + 15) / 16;
+    for (int ta = 0; ta < nt; ++ta)
+      for (int tb = 0; tb < nt; ++tb)
+        for (int sp = 0; sp < cd.nsplit; ++sp) w.jobs.push_back(make_int4((int)w.ids.size(), ta, tb, sp));
+    w.msz += (size_t)nk * nk;
+    w.part += (size_t)nk * nk * cd.nsplit;
+    if (nk > GAIN_LDS_DIM) w.work += (size_t)nk * nk;
+    w.ncol += nk;
+    w.p0.push_back(w.p0.back() + (int)cands[k].row.size());
+    w.ids.push_back((int)k);
+    w.cd.push_back(cd);
+  }
+  if (sweeps.empty()) return SLIDE_OK;
+  size_t max_nc = 0, max_jobs = 0, max_msz = 0, max_part = 0, max_work = 0;
+  int max_ncol = 0;
+  for (const Sweep& w : sweeps) {
+    max_nc = std::max(max_nc, w.ids.size()); max_jobs = std::max(max_jobs, w.jobs.size()); max_msz = std::max(max_msz, w.msz);
+    max_part = std::max(max_part, w.part); max_work = std::max(max_work, w.work); max_ncol = std::max(max_ncol, w.ncol);
+  }
+  const size_t max_ne = 7 * (size_t)max_ncol;        // (a row of J: six entries on c_{i+1}, one on c_i)
+  Scratch sc(s);
+  int rc = be.alloc(sc, max_ncol);
+  if (rc != SLIDE_OK) return rc;
+  int* d_rc = sc.alloc<int>(2 * max_ne);
+  int* d_jptr = sc.alloc<int>((size_t)max_ncol + 1);
+  int* d_jrow = sc.alloc<int>(max_ne);
+  int* d_flag = sc.alloc<int>(max_nc);
+  double* d_val = sc.alloc<double>(max_ne);
+  double* d_jval = sc.alloc<double>(max_ne);
+  double* d_g = sc.alloc<double>(GAIN_MAX_GRAMS * max_nc);
+  double* d_M = sc.alloc<double>(be.nM * max_msz);
+  double* d_part = sc.alloc<double>(max_part);
+  double* d_work = sc.alloc<double>(max_work);
+  GainCandDev* d_cd = sc.alloc<GainCandDev>(max_nc);
+  int4* d_jobs = sc.alloc<int4>(max_jobs);
+  if (!sc.ok()) { g_last_error = "closure_info_gain_batch: out of device memory"; return SLIDE_ERR_HIP; }
+  std::vector<double> hg(GAIN_MAX_GRAMS * max_nc);
+  std::vector<int> hflag(max_nc);
+  for (const Sweep& w : sweeps) {
+    const int nc = (int)w.ids.size();
+    GainQuery q(w.p0);
+    std::vector<double> val(12 * (size_t)q.n), tv(q.n, 0.0);
+    for (int k = 0; k < nc; ++k) {
+      const GainCand& c = cands[w.ids[k]];
+      std::copy(c.row.begin(), c.row.end(), q.row.begin() + w.p0[k]);
+      std::copy(c.val.begin(), c.val.end(), val.begin() + 12 * (size_t)w.p0[k]);
+      std::copy(c.travel, c.travel + c.row.size() - 1, tv.begin() + w.p0[k]);
+    }
+    gain_jt(q, val.data(), tv.data(), sigma6);
+    // the same entries by column of J^T (a row of J), rows ascending: what the Woodbury step walks
+    const int ne = (int)q.vv.size();
+    std::vector<int> jptr(q.ncol + 1, 0), jrow(ne);
+    std::vector<double> jval(ne);
+    for (int e = 0; e < ne; ++e) ++jptr[q.rcv[2 * e + 1] + 1];
+    for (int c = 0; c < q.ncol; ++c) jptr[c + 1] += jptr[c];
+    std::vector<int> at(jptr.begin(), jptr.end() - 1);
+    for (int e = 0; e < ne; ++e) { const int o = at[q.rcv[2 * e + 1]]++; jrow[o] = q.rcv[2 * e]; jval[o] = q.vv[e]; }
+    SL_HIP(sc.upload(d_rc, q.rcv));
+    SL_HIP(sc.upload(d_val, q.vv));
+    SL_HIP(sc.upload(d_jptr, jptr));
+    SL_HIP(sc.upload(d_jrow, jrow));
+    SL_HIP(sc.upload(d_jval, jval));
+    SL_HIP(sc.upload(d_cd, w.cd));
+    SL_HIP(sc.upload(d_jobs, w.jobs));
+    if ((rc = be.begin(q.ncol)) != SLIDE_OK) return rc;
+    launch_scatter(d_rc, d_val, ne, be.R, (int)be.ldu, s);
+    if ((rc = be.solve(q.ncol)) != SLIDE_OK) return rc;
+    be.grams(q.ncol, [&](int qi, const double* X, size_t ldx, const int* rows, int nrows) {
+      launch_gram_blocks(X, ldx, rows, nrows, d_cd, nc, d_jobs, (int)w.jobs.size(), d_part, d_M + qi * w.msz, s);
+    });
+    if (launch_woodbury_blocks(be.U, be.ldu, d_cd, nc, d_jptr, d_jrow, d_jval, d_M, w.msz, be.nM, d_work, d_g, d_flag, w.work < w.msz, w.work > 0, s)) {
+      g_last_error = "closure_info_gain_batch: the device refuses the Woodbury kernel's LDS";
+      return SLIDE_ERR_HIP;
+    }
+    SL_HIP(hipGetLastError());
+    SL_HIP(hipMemcpyAsync(hg.data(), d_g, GAIN_MAX_GRAMS * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < nc; ++k) {
+      if (hflag[k]) { cands[w.ids[k]].st = SLIDE_ERR_NOT_SPD; continue; }
+      for (int qi = 0; qi < be.nM; ++qi) g[GAIN_MAX_GRAMS * (size_t)w.ids[k] + qi] = hg[GAIN_MAX_GRAMS * (size_t)k + qi];
+    }
+  }
+  return SLIDE_OK;
 }
 
 // estimateClosureInfoGain (graph.cpp:469-623) in the linear-Gaussian model of the resident factor.  Fake factor i is a Between factor
@@ -390,6 +551,81 @@ int HostGraph::closure_info_gain(int robot, const uint64_t* traj, int n, const d
   out3[0] = 10.0 * gp + gl;
   out3[1] = gp;
   out3[2] = gl;
+  return SLIDE_OK;
+}
+// The same for a list: candidate k is traj[off[k] .. off[k + 1]) with the travel distances at the same places, out3n[3 k ..] what the
+// call above gives for it alone, status[k] its own fault (or null).  Whole-call refusals as above, nothing written then.
+int HostGraph::closure_info_gain_batch(int robot, int n_cand, const int32_t* off, const uint64_t* traj, const double* travel,
+                                       const double* sigma6, double* out3n, int32_t* status) {
+  if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
+  int rc = gain_check_list(n_cand, off, traj, travel, out3n);
+  if (rc != SLIDE_OK) return rc;
+  if (!sigma6) sigma6 = P.noise_model_odom_vec;
+  if ((rc = gain_check_sigma(sigma6)) != SLIDE_OK) return rc;
+  if ((rc = marginal_state("closure_info_gain")) != SLIDE_OK) return rc;
+  hipStream_t s = stream;
+  std::vector<double> pv(12 * up_P);                 // every pose's linearisation value, in one copy
+  SL_HIP(hipMemcpyAsync(pv.data(), G.pose_val, pv.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  std::vector<GainCand> cands(n_cand);
+  for (int k = 0; k < n_cand; ++k) {
+    GainCand& c = cands[k];
+    const int nk = off[k + 1] - off[k];
+    c.travel = travel + off[k];
+    if (gain_steps_fault(traj + off[k], nk, c.travel, &c.st)) continue;
+    for (int i = 0; i < nk && c.st == SLIDE_OK; ++i) {
+      const int id = pose_id(robot, traj[off[k] + i]);
+      if (id < 0) { c.st = SLIDE_MISSING; break; }
+      c.row.push_back(6 * id);
+      c.val.insert(c.val.end(), pv.begin() + 12 * (size_t)id, pv.begin() + 12 * (size_t)id + 12);
+    }
+  }
+  const int T = G.T, nT = T * NB;
+  std::vector<int> poses, lms, prow;
+  robot_poses(robot, poses);
+  point_landmarks(lms);
+  for (int p : poses)
+    for (int a = 0; a < 6; ++a) prow.push_back(6 * p + a);
+  const size_t nl = lms.size(), ldv = std::max<size_t>(9 * nl, 1);
+  const bool dense = h_prof.size() != (size_t)T;
+  int *d_rows = nullptr, *d_lms = nullptr;
+  double* V = nullptr;
+  GainBackend be;
+  be.s = s; be.ldu = nT; be.nM = 2;
+  be.alloc = [&](Scratch& sc, int max_ncol) -> int {
+    be.R = sc.alloc<double>((size_t)max_ncol * nT);
+    be.U = sc.alloc<double>((size_t)max_ncol * nT);
+    V = sc.alloc<double>((size_t)max_ncol * ldv);
+    d_rows = sc.alloc<int>(prow.size() + nl);
+    if (!sc.ok()) { g_last_error = "closure_info_gain_batch: out of device memory"; return SLIDE_ERR_HIP; }
+    d_lms = d_rows + prow.size();
+    SL_HIP(sc.upload(d_rows, prow));
+    SL_HIP(sc.upload(d_lms, lms));
+    return SLIDE_OK;
+  };
+  be.begin = [&](int ncol) -> int {
+    SL_HIP(hipMemsetAsync(be.R, 0, (size_t)ncol * nT * sizeof(double), s));
+    return SLIDE_OK;
+  };
+  be.solve = [&](int ncol) -> int {
+    launch_multi_solve(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), be.R, be.U, ncol, s);
+    return SLIDE_OK;
+  };
+  be.grams = [&](int ncol, const GainBackend::Gram& gram) {
+    gram(0, be.U, nT, d_rows, (int)prow.size());
+    if (nl) launch_landmark_V(G, be.U, nT, ncol, d_lms, (int)nl, V, ldv, s);
+    gram(1, V, ldv, nullptr, (int)(9 * nl));
+  };
+  std::vector<double> g(GAIN_MAX_GRAMS * (size_t)n_cand);
+  if ((rc = gain_batch(be, cands, sigma6, g.data())) != SLIDE_OK) return rc;
+  for (int k = 0; k < n_cand; ++k) {
+    const bool ok = cands[k].st == SLIDE_OK;
+    const double gp = ok ? g[GAIN_MAX_GRAMS * (size_t)k] : 0.0, gl = ok ? g[GAIN_MAX_GRAMS * (size_t)k + 1] : 0.0;
+    out3n[3 * k] = ok ? 10.0 * gp + gl : 0.0;
+    out3n[3 * k + 1] = gp;
+    out3n[3 * k + 2] = gl;
+    if (status) status[k] = cands[k].st;
+  }
   return SLIDE_OK;
 }
 
@@ -876,6 +1112,108 @@ int CholBatch::joint_marginal_traces(int slot, double* out4) {
   return SLIDE_OK;
 }
 
+// What the joint gain queries share: the last exact pass's elimination tree and the schedule of the many-right-hand-side solve over it,
+// where every system's rows lie in the buffers X (solutions, U at the end) and Rb (right-hand sides) — the robots first, then the
+// separator; leading dimension N — and the grams' row lists: the poses of the robot in `slot`, of every robot, the job's shared point
+// landmarks (each slot once); the private point landmarks of every graph (k_lm_V on its robot's rows)
+struct CholBatch::JointGain {
+  JointTree t;
+  JointTree::SolvePlan plan;
+  std::vector<size_t> off;
+  size_t N = 0, nl = 0, ldv = 1;
+  std::vector<int> rows_slot, rows_all, rows_sh, lms, lm0;
+  // the device side, from the query's scratch
+  JSinvSys* d_sys = nullptr;
+  int4* d_jobs = nullptr;
+  int2* d_sent = nullptr;
+  int *d_lst = nullptr, *d_sptr = nullptr, *d_rslot = nullptr, *d_rall = nullptr, *d_rsh = nullptr, *d_lms = nullptr;
+  std::vector<int*> d_prow, d_map;
+  int prow_of(int sl, int p) const { return (int)off[1 + sl] + t.prow[sl][p]; }
+  void build(const CholBatch& b, int slot) {
+    const int n = b.n;
+    b.joint_tree(t);
+    off.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) { off[1 + i] = N; N += (size_t)t.Trow[i] * NB; }
+    off[0] = N; N += (size_t)t.Tsep * NB;
+    t.solve_plan(plan);
+    lm0.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+      std::vector<int> poses;
+      b.graphs[i]->robot_poses(b.joint_robot(i), poses);
+      for (int p : poses)
+        for (int a = 0; a < 6; ++a) {
+          rows_all.push_back(prow_of(i, p) + a);
+          if (i == slot) rows_slot.push_back(prow_of(i, p) + a);
+        }
+    }
+    std::vector<std::vector<int>> priv;
+    std::vector<int> sh_off;
+    b.job_point_landmarks(priv, sh_off);
+    for (int i = 0; i < n; ++i) { lms.insert(lms.end(), priv[i].begin(), priv[i].end()); lm0[i + 1] = (int)lms.size(); }
+    for (int o : sh_off)
+      for (int a = 0; a < 3; ++a) rows_sh.push_back((int)off[0] + o + a);
+    nl = lms.size();
+    ldv = std::max<size_t>(9 * nl, 1);
+  }
+  // the tables to the device; X and Rb are bound.  ne, d_rc: room for that many (row, column) pairs of J^T behind the lists, d_rc points
+  // there (the batch keeps its pairs elsewhere)
+  int upload(Scratch& sc, double* X, double* Rb, size_t ne = 0, int** d_rc = nullptr) {
+    const int n = (int)t.T.size(), NS = 1 + n;
+    d_sys = sc.alloc<JSinvSys>(NS);
+    d_jobs = sc.alloc<int4>(plan.jobs.size());
+    d_sent = sc.alloc<int2>(plan.sent.size());
+    d_lst = sc.alloc<int>(plan.lst.size() + plan.sptr.size() + 2 * ne + rows_slot.size() + rows_all.size() + rows_sh.size() + nl);
+    d_prow.assign(n, nullptr); d_map.assign(n, nullptr);
+    for (int i = 0; i < n; ++i) {
+      d_prow[i] = sc.alloc<int>(t.prow[i].size());
+      d_map[i] = sc.alloc<int>(t.map[i].size());
+    }
+    if (!sc.ok()) return SLIDE_OK;                    // (the caller asks sc.ok() after its own allocations)
+    for (int sy = 0; sy < NS; ++sy) { t.Y[sy].Sg = X + off[sy]; t.Y[sy].Z = Rb + off[sy]; t.Y[sy].lds = (long long)N; }
+    d_sptr = d_lst + plan.lst.size();
+    int* pairs = d_sptr + plan.sptr.size();
+    if (d_rc) *d_rc = pairs;
+    d_rslot = pairs + 2 * ne;
+    d_rall = d_rslot + rows_slot.size();
+    d_rsh = d_rall + rows_all.size();
+    d_lms = d_rsh + rows_sh.size();
+    SL_HIP(sc.upload(d_sys, t.Y));
+    SL_HIP(sc.upload(d_jobs, plan.jobs));
+    SL_HIP(sc.upload(d_sent, plan.sent));
+    SL_HIP(sc.upload(d_lst, plan.lst));
+    SL_HIP(sc.upload(d_sptr, plan.sptr));
+    SL_HIP(sc.upload(d_rslot, rows_slot));
+    SL_HIP(sc.upload(d_rall, rows_all));
+    SL_HIP(sc.upload(d_rsh, rows_sh));
+    SL_HIP(sc.upload(d_lms, lms));
+    for (int i = 0; i < n; ++i) { SL_HIP(sc.upload(d_prow[i], t.prow[i])); SL_HIP(sc.upload(d_map[i], t.map[i])); }
+    return SLIDE_OK;
+  }
+  // X = K^-1 R in S (R = J^T in Rb on entry)
+  void solve(double* X, double* Rb, int ncol, hipStream_t s) const {
+    const int n = (int)t.T.size();
+    JMSum sA{};
+    JSigGather gA{};
+    for (int i = 0; i < n; ++i) {
+      sA.src[i] = Rb + off[1 + i];
+      gA.dst[i] = X + off[1 + i]; gA.map[i] = d_map[i]; gA.lds[i] = (long long)N; gA.o0[i] = t.Tc[i] * NB; gA.n[i] = t.gn[i];
+    }
+    sA.dst = Rb + off[0]; sA.ld = (long long)N;
+    gA.src = X + off[0]; gA.lds_src = (long long)N;
+    for (const JointTree::SolvePlan::Launch& L : plan.launches) {
+      if (L.kind == 0) launch_jms_push(d_sys, d_jobs + L.j0, L.nj, L.maxl, d_lst, ncol, L.bwd, s);
+      else if (L.kind == 1) launch_jms_pull(d_sys, d_jobs + L.j0, L.nj, d_lst, ncol, L.bwd, s);
+      else if (L.kind == 2) launch_jms_sum(sA, d_sptr, d_sent, t.Tsep * NB, ncol, s);
+      else launch_jms_gather(gA, n, plan.max_gn, ncol, s);
+    }
+  }
+  // V of every graph's private point landmarks from its robot's rows of X
+  void landmark_V(const CholBatch& b, const double* X, int ncol, double* V, hipStream_t s) const {
+    for (int i = 0; i < (int)t.T.size(); ++i)
+      launch_landmark_V(b.hG[i], X + off[1 + i], (int)N, ncol, d_lms + lm0[i], lm0[i + 1] - lm0[i], V + 9 * (size_t)lm0[i], ldv, s, d_prow[i]);
+  }
+};
+
 // estimateClosureInfoGain (graph.cpp:469-623) on the joint graph (graph.cpp:325-371: every replica holds the whole multi-robot graph),
 // in the linear-Gaussian model of the last exact pass's factor K = L D L^T, as the single-graph call: U = K^-1 J^T by substitutions with
 // 6m right-hand sides through the pass's elimination tree (joint_cov_kernels.hip's k_jms_*), C = I + J U, the drops tr(C^-1 U_P^T U_P).
@@ -898,104 +1236,40 @@ int CholBatch::joint_closure_info_gain(int slot, const int32_t* traj_slots, cons
     if ((ids[k] = graphs[qs[k]]->pose_id(joint_robot(qs[k]), traj[k])) < 0) return SLIDE_MISSING;
   }
   hipStream_t s = master;
-  JointTree t;
-  joint_tree(t);
-  const int Tsep = t.Tsep, NS = 1 + n;
-  // the rows of every system in the buffers X (solutions, U at the end) and Rb (right-hand sides): the robots first, then the separator
-  std::vector<size_t> off(n + 1);
-  size_t N = 0;
-  for (int i = 0; i < n; ++i) { off[1 + i] = N; N += (size_t)t.Trow[i] * NB; }
-  off[0] = N; N += (size_t)Tsep * NB;
-  auto prow_of = [&](int sl, int p) { return (int)off[1 + sl] + t.prow[sl][p]; };
+  JointGain jg;
+  jg.build(*this, slot);
+  const size_t N = jg.N;
   GainQuery q(n_q);
   for (int k = 0; k < n_q; ++k) {
-    q.row[k] = prow_of(qs[k], ids[k]);
+    q.row[k] = jg.prow_of(qs[k], ids[k]);
     q.val_src[k] = hG[qs[k]].pose_val + 12 * (size_t)ids[k];
   }
   if ((rc = gain_jt(q, travel, sigma6, s)) != SLIDE_OK) return rc;
   const int ncol = q.ncol, ne = (int)q.vv.size();
   const size_t nn = (size_t)ncol * ncol;
-  JointTree::SolvePlan plan;
-  t.solve_plan(plan);
-  // the grams' row lists: the poses of the robot in `slot`, of every robot, the job's shared point landmarks (each slot once); the
-  // private point landmarks of every graph (k_lm_V on its robot's rows)
-  std::vector<int> rows_slot, rows_all, rows_sh, lms, lm0(n + 1, 0);
-  for (int i = 0; i < n; ++i) {
-    std::vector<int> poses;
-    graphs[i]->robot_poses(joint_robot(i), poses);
-    for (int p : poses)
-      for (int a = 0; a < 6; ++a) {
-        rows_all.push_back(prow_of(i, p) + a);
-        if (i == slot) rows_slot.push_back(prow_of(i, p) + a);
-      }
-  }
-  std::vector<std::vector<int>> priv;
-  std::vector<int> sh_off;
-  job_point_landmarks(priv, sh_off);
-  for (int i = 0; i < n; ++i) { lms.insert(lms.end(), priv[i].begin(), priv[i].end()); lm0[i + 1] = (int)lms.size(); }
-  for (int o : sh_off)
-    for (int a = 0; a < 3; ++a) rows_sh.push_back((int)off[0] + o + a);
-  const size_t nl = lms.size(), ldv = std::max<size_t>(9 * nl, 1);
   Scratch sc(s);
   double* X = sc.alloc<double>(N * ncol);
   double* Rb = sc.alloc<double>(N * ncol);
-  double* V = sc.alloc<double>(ldv * ncol);
+  double* V = sc.alloc<double>(jg.ldv * ncol);
   double* Md = sc.alloc<double>(4 * nn);
-  JSinvSys* d_sys = sc.alloc<JSinvSys>(NS);
-  int4* d_jobs = sc.alloc<int4>(plan.jobs.size());
-  int2* d_sent = sc.alloc<int2>(plan.sent.size());
-  int* d_lst = sc.alloc<int>(plan.lst.size() + plan.sptr.size() + 2 * (size_t)ne + rows_slot.size() + rows_all.size() + rows_sh.size() + nl);
-  std::vector<int*> d_prow(n, nullptr), d_map(n, nullptr);
-  for (int i = 0; i < n; ++i) {
-    d_prow[i] = sc.alloc<int>(t.prow[i].size());
-    d_map[i] = sc.alloc<int>(t.map[i].size());
-  }
   double* d_val = sc.alloc<double>(ne);
+  int* d_rc = nullptr;
+  rc = jg.upload(sc, X, Rb, ne, &d_rc);
   if (!sc.ok()) { g_last_error = "closure_info_gain: out of device memory"; return SLIDE_ERR_HIP; }
-  for (int sy = 0; sy < NS; ++sy) { t.Y[sy].Sg = X + off[sy]; t.Y[sy].Z = Rb + off[sy]; t.Y[sy].lds = (long long)N; }
-  int* d_sptr = d_lst + plan.lst.size();
-  int* d_rc = d_sptr + plan.sptr.size();
-  int* d_rslot = d_rc + 2 * ne;
-  int* d_rall = d_rslot + rows_slot.size();
-  int* d_rsh = d_rall + rows_all.size();
-  int* d_lms = d_rsh + rows_sh.size();
+  if (rc != SLIDE_OK) return rc;
   SL_HIP(hipMemsetAsync(X, 0, N * ncol * sizeof(double), s));
   SL_HIP(hipMemsetAsync(Rb, 0, N * ncol * sizeof(double), s));
-  SL_HIP(sc.upload(d_sys, t.Y));
-  SL_HIP(sc.upload(d_jobs, plan.jobs));
-  SL_HIP(sc.upload(d_sent, plan.sent));
-  SL_HIP(sc.upload(d_lst, plan.lst));
-  SL_HIP(sc.upload(d_sptr, plan.sptr));
   SL_HIP(sc.upload(d_rc, q.rcv));
-  SL_HIP(sc.upload(d_rslot, rows_slot));
-  SL_HIP(sc.upload(d_rall, rows_all));
-  SL_HIP(sc.upload(d_rsh, rows_sh));
-  SL_HIP(sc.upload(d_lms, lms));
   SL_HIP(sc.upload(d_val, q.vv));
-  for (int i = 0; i < n; ++i) { SL_HIP(sc.upload(d_prow[i], t.prow[i])); SL_HIP(sc.upload(d_map[i], t.map[i])); }
   // R = J^T, then X = K^-1 R in S
   launch_scatter(d_rc, d_val, ne, Rb, (int)N, s);
-  JMSum sA{};
-  JSigGather gA{};
-  for (int i = 0; i < n; ++i) {
-    sA.src[i] = Rb + off[1 + i];
-    gA.dst[i] = X + off[1 + i]; gA.map[i] = d_map[i]; gA.lds[i] = (long long)N; gA.o0[i] = t.Tc[i] * NB; gA.n[i] = t.gn[i];
-  }
-  sA.dst = Rb + off[0]; sA.ld = (long long)N;
-  gA.src = X + off[0]; gA.lds_src = (long long)N;
-  for (const JointTree::SolvePlan::Launch& L : plan.launches) {
-    if (L.kind == 0) launch_jms_push(d_sys, d_jobs + L.j0, L.nj, L.maxl, d_lst, ncol, L.bwd, s);
-    else if (L.kind == 1) launch_jms_pull(d_sys, d_jobs + L.j0, L.nj, d_lst, ncol, L.bwd, s);
-    else if (L.kind == 2) launch_jms_sum(sA, d_sptr, d_sent, Tsep * NB, ncol, s);
-    else launch_jms_gather(gA, n, plan.max_gn, ncol, s);
-  }
+  jg.solve(X, Rb, ncol, s);
   // the grams: poses of `slot`, poses of every robot, private point landmarks (through V), shared point landmarks
-  launch_gram(X, N, ncol, d_rslot, (int)rows_slot.size(), Md, s);
-  launch_gram(X, N, ncol, d_rall, (int)rows_all.size(), Md + nn, s);
-  for (int i = 0; i < n; ++i)
-    launch_landmark_V(hG[i], X + off[1 + i], (int)N, ncol, d_lms + lm0[i], lm0[i + 1] - lm0[i], V + 9 * (size_t)lm0[i], ldv, s, d_prow[i]);
-  launch_gram(V, ldv, ncol, nullptr, (int)(9 * nl), Md + 2 * nn, s);
-  launch_gram(X, N, ncol, d_rsh, (int)rows_sh.size(), Md + 3 * nn, s);
+  launch_gram(X, N, ncol, jg.d_rslot, (int)jg.rows_slot.size(), Md, s);
+  launch_gram(X, N, ncol, jg.d_rall, (int)jg.rows_all.size(), Md + nn, s);
+  jg.landmark_V(*this, X, ncol, V, s);
+  launch_gram(V, jg.ldv, ncol, nullptr, (int)(9 * jg.nl), Md + 2 * nn, s);
+  launch_gram(X, N, ncol, jg.d_rsh, (int)jg.rows_sh.size(), Md + 3 * nn, s);
   double gs[4];
   GainFetched& h = ig_host;
   if ((rc = gain_fetch(q, X, N, Md, 4, s, h)) != SLIDE_OK) return rc;
@@ -1005,6 +1279,82 @@ int CholBatch::joint_closure_info_gain(int slot, const int32_t* traj_slots, cons
   out4[2] = gs[2] + gs[3];
   out4[0] = 10.0 * out4[1] + out4[2];
   out4[3] = gs[1];
+  return SLIDE_OK;
+}
+// The same for a list (the single-graph closure_info_gain_batch's arguments; traj_slots runs parallel to traj): out4n[4 k ..] what the
+// call above gives for candidate k alone, status[k] its own fault (or null).  Whole-call refusals as above, nothing written then.
+int CholBatch::joint_closure_info_gain_batch(int slot, int n_cand, const int32_t* off, const int32_t* traj_slots, const uint64_t* traj,
+                                             const double* travel, const double* sigma6, double* out4n, int32_t* status) {
+  int rc = gain_check_list(n_cand, off, traj, travel, out4n);
+  if (rc != SLIDE_OK) return rc;
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  if ((rc = joint_state("closure_info_gain", slot)) != SLIDE_OK) return rc;
+  if (!sigma6) sigma6 = graphs[slot]->P.noise_model_odom_vec;
+  if ((rc = gain_check_sigma(sigma6)) != SLIDE_OK) return rc;
+  hipStream_t s = master;
+  JointGain jg;
+  jg.build(*this, slot);
+  const size_t N = jg.N;
+  std::vector<std::vector<double>> pv(n);            // the linearisation values of a graph's poses, in one copy, once a candidate names it
+  std::vector<GainCand> cands(n_cand);
+  for (int k = 0; k < n_cand; ++k) {
+    GainCand& c = cands[k];
+    const int nk = off[k + 1] - off[k];
+    c.travel = travel + off[k];
+    if (gain_steps_fault(traj + off[k], nk, c.travel, &c.st)) continue;
+    for (int i = 0; i < nk; ++i) {
+      const int sl = traj_slots ? traj_slots[off[k] + i] : slot;
+      if (sl < 0 || sl >= n) { c.st = SLIDE_ERR_INVALID; break; }
+      const int id = graphs[sl]->pose_id(joint_robot(sl), traj[off[k] + i]);
+      if (id < 0) { c.st = SLIDE_MISSING; break; }
+      if (pv[sl].empty()) {
+        pv[sl].resize(12 * (size_t)hG[sl].P);
+        SL_HIP(hipMemcpyAsync(pv[sl].data(), hG[sl].pose_val, pv[sl].size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+      }
+      c.row.push_back(jg.prow_of(sl, id));
+      c.val.insert(c.val.end(), pv[sl].begin() + 12 * (size_t)id, pv[sl].begin() + 12 * (size_t)id + 12);
+    }
+  }
+  double* V = nullptr;
+  GainBackend be;
+  be.s = s; be.ldu = N; be.nM = 4;
+  be.alloc = [&](Scratch& sc, int max_ncol) -> int {
+    be.U = sc.alloc<double>(N * max_ncol);
+    be.R = sc.alloc<double>(N * max_ncol);
+    V = sc.alloc<double>(jg.ldv * max_ncol);
+    const int rc_up = jg.upload(sc, be.U, be.R);
+    if (!sc.ok()) { g_last_error = "closure_info_gain_batch: out of device memory"; return SLIDE_ERR_HIP; }
+    return rc_up;
+  };
+  be.begin = [&](int ncol) -> int {
+    SL_HIP(hipMemsetAsync(be.U, 0, N * ncol * sizeof(double), s));
+    SL_HIP(hipMemsetAsync(be.R, 0, N * ncol * sizeof(double), s));
+    return SLIDE_OK;
+  };
+  be.solve = [&](int ncol) -> int { jg.solve(be.U, be.R, ncol, s); return SLIDE_OK; };
+  // the grams as the single call's: poses of `slot`, poses of every robot, private point landmarks (through V), shared point landmarks
+  be.grams = [&](int ncol, const GainBackend::Gram& gram) {
+    gram(0, be.U, N, jg.d_rslot, (int)jg.rows_slot.size());
+    gram(1, be.U, N, jg.d_rall, (int)jg.rows_all.size());
+    jg.landmark_V(*this, be.U, ncol, V, s);
+    gram(2, V, jg.ldv, nullptr, (int)(9 * jg.nl));
+    gram(3, be.U, N, jg.d_rsh, (int)jg.rows_sh.size());
+  };
+  std::vector<double> g(GAIN_MAX_GRAMS * (size_t)n_cand);
+  if ((rc = gain_batch(be, cands, sigma6, g.data())) != SLIDE_OK) return rc;
+  for (int k = 0; k < n_cand; ++k) {
+    const double* gs = g.data() + GAIN_MAX_GRAMS * (size_t)k;
+    double* o = out4n + 4 * (size_t)k;
+    for (int i = 0; i < 4; ++i) o[i] = 0.0;
+    if (cands[k].st == SLIDE_OK) {
+      o[1] = gs[0];
+      o[2] = gs[2] + gs[3];
+      o[0] = 10.0 * o[1] + o[2];
+      o[3] = gs[1];
+    }
+    if (status) status[k] = cands[k].st;
+  }
   return SLIDE_OK;
 }
 }  // namespace sl

@@ -121,6 +121,20 @@ void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nro
 void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s,
                        const int* prow = nullptr);      // prow: a pose's first row in U (null: 6 p)
 void launch_scatter(const int* rc, const double* val, int n, double* B, int nT, hipStream_t s);
+// Many candidates in one sweep (closure_info_gain_batch): candidate k owns the columns c0 .. c0 + nk - 1 of U.  moff: its nk x nk block
+// in each gram; poff: its nsplit partial blocks (nsplit = gain_gram_splits(nk)); woff: its nk x nk slice of the Woodbury work buffer
+// (used past GAIN_LDS_DIM columns; smaller candidates are factored in LDS)
+constexpr int GAIN_MAX_STEPS = 64, GAIN_MAX_GRAMS = 4, GAIN_LDS_DIM = 96;
+struct GainCandDev { int c0, nk, nsplit, pad; long long moff, poff, woff; };
+int gain_gram_splits(int nk);
+// M_k = sum over the rows (the list, or null: 0 .. nrows - 1) of X_k^T X_k per candidate; jobs {candidate, tile row, tile column, split}
+void launch_gram_blocks(const double* X, size_t ldx, const int* rows, int nrows, const GainCandDev* cand, int ncand, const int4* jobs,
+                        int njobs, double* part, double* M, hipStream_t s);
+// per candidate: C = I + J U (J by columns of J^T: jptr / jrow / jval), its Cholesky factor, gains[GAIN_MAX_GRAMS k + q] = tr(C^-1 M_q)
+// (M_q at M + q msz), flag[k] = 1 where C is not positive definite; non-zero: the device refused the kernel's LDS, nothing launched
+int launch_woodbury_blocks(const double* U, size_t ldu, const GainCandDev* cand, int ncand, const int* jptr, const int* jrow,
+                           const double* jval, const double* M, size_t msz, int nM, double* work, double* gains, int* flag, bool small,
+                           bool big, hipStream_t s);
 // joint_cov_kernels.hip — the selected inverse over the exact joint pass's elimination tree (CholBatch::ensure_joint_sigma).  One system:
 // factor columns [0, Tb) in S (ld; rows past Tb = its stored border rows), [Tb, Tc) in B (ldb, rows and columns counted from Tb); their
 // diagonal blocks in Ld / Winv and Ld2 / Winv2; D = -I on the columns >= neg0; Sigma and Z dense lower with leading dimension lds.

@@ -685,6 +685,12 @@ class PassDriver:
         self._joint_ok()
         return self.batch.closure_info_gain(robot, traj, travel, sigma_per_m, traj_robots)
 
+    def closure_info_gain_batch(self, robot, trajs, travels, sigma_per_m=None, traj_robots=None):
+        """closure_info_gain for a list of candidates in one call: ((n, 4) gains, (n,) status), row k what closure_info_gain gives for
+        candidate k alone; traj_robots[k][q] = the robot of pose trajs[k][q] (None: all `robot`)."""
+        self._joint_ok()
+        return self.batch.closure_info_gain_batch(robot, trajs, travels, sigma_per_m, traj_robots)
+
     def one_pass(self):
         n54, n9, K = 54 * self.n_slots, 9 * self.n_slots, self.pcg_iters
         if self.batch is not None:
