@@ -563,6 +563,25 @@ void slide_clipper_default_params(slide_clipper_params_t* p);
  * projection, line-search and stopping decision in one persistent workgroup — no host round trip inside the iteration. */
 int slide_clipper_dense_clique(const double* M_upper, int n, const double* u0, const slide_clipper_params_t* p,
                                int32_t* nodes_out, int* n_nodes, double* u_out, double* score);
+/* scorePairwiseConsistency clipper.cpp:21-65 ending in M_ = M.sparseView(): the SYMMETRIC matrix without its diagonal as CSR,
+ * columns ascending (the matrix the solver multiplies with).  rowptr_out: m + 1 ints.  Two-call protocol: *nnz is always set;
+ * cap < *nnz -> SLIDE_ERR_CAPACITY, col_out / val_out untouched (rowptr_out still filled).  Built on the device row by row
+ * (k_affinity_csr: count, host prefix sum, emit) without the dense m x m form; the values are those of slide_clipper_affinity bit for
+ * bit (one shared scoring function), the same on every run.  More than 2^31 - 1 non-zeros: SLIDE_ERR_CAPACITY; an association outside
+ * D1 / D2: SLIDE_ERR_INVALID. */
+int slide_clipper_affinity_csr(const double* D1, int n1, const double* D2, int n2, int dim, const int32_t* A, int m,
+                               double sigma, double epsilon, double mindist, double affinityeps,
+                               int32_t* rowptr_out, int32_t* col_out, double* val_out, long long cap, long long* nnz);
+/* findDenseClique clipper.cpp:172-323 from that CSR (rowptr: n + 1 ints, col / val: rowptr[n] entries); otherwise as
+ * slide_clipper_dense_clique, and the same bits for the same matrix.  The CSR is checked on the host before the device is touched:
+ * rowptr[0] == 0 and non-decreasing, columns inside [0, n), strictly ascending within a row, none on the diagonal, every (i, j, v)
+ * with its (j, i, v); a violation is SLIDE_ERR_INVALID with the row in slide_last_error(). */
+int slide_clipper_dense_clique_csr(const int32_t* rowptr, const int32_t* col, const double* val, int n, const double* u0,
+                                   const slide_clipper_params_t* p, int32_t* nodes_out, int* n_nodes, double* u_out, double* score);
+/* scorePairwiseConsistency + solve + getSelectedAssociations (clipper.cpp:21-65, 172-323, 67-85) in one call: nothing of size m^2
+ * exists anywhere, on the host or the device.  sigma / epsilon / mindist / affinityeps from p.  nodes_out: m entries. */
+int slide_clipper_match(const double* D1, int n1, const double* D2, int n2, int dim, const int32_t* A, int m, const double* u0,
+                        const slide_clipper_params_t* p, int32_t* nodes_out, int* n_nodes, double* u_out, double* score);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the
@@ -579,13 +598,14 @@ enum {
   SLIDE_MS_CLQ_CSR = 2,           /* ms: k_clq_csr count + fill (CSR of the affinity matrix from its dense upper triangle) */
   SLIDE_MS_CLQ_SOLVE = 3,         /* ms: the projected-gradient solve (k_clq_solve or k_clq_solve_coop) */
   SLIDE_MS_AFFINITY = 4,          /* ms: k_clipper_affinity */
-  SLIDE_MS_CLQ_NNZ = 5,           /* count: non-zeros of the last solve's CSR */
+  SLIDE_MS_CLQ_NNZ = 5,           /* count: non-zeros of the last CSR built or solved (dense, from associations, or the caller's) */
   SLIDE_MS_PLACE_PAIR_TESTS = 6,  /* count: candidates x query objects x reference objects of the last sweep (a first hit ends a query
                                      object's scan early: upper bound of the pair tests executed) */
   SLIDE_MS_TRI_PAIRS = 7,         /* count: model triangles x data triangles of the last triangle match */
   SLIDE_MS_PLACE_DIST_TESTS = 8,  /* count: distance tests the bucketed sweep was given (candidates x sum over the query objects of the
                                      reference objects of their label): what is left of the pair tests once the label test is a table */
-  SLIDE_MS_COUNT = 9
+  SLIDE_MS_AFFINITY_CSR = 9,      /* ms: k_affinity_csr count + emit (CSR of the affinity matrix straight from the associations) */
+  SLIDE_MS_COUNT = 10
 };
 int slide_last_device_ms(int what, double* out);
 /* The same for several independent problems in ONE launch, a persistent workgroup per problem — the robot pairs of a multi-robot job
@@ -602,7 +622,8 @@ int slide_match_triangles(const double* tri_model, int ntm, const double* tri_da
 /* semantic_clipper::estimate_tf :122-138 (2-D Kabsch a -> b; tf3 row-major 3x3). */
 int slide_estimate_tf2d(const double* a_xy, const double* b_xy, int n, double tf3[9]);
 /* semantic_clipper::run_semantic_clipper :140-274 from the triangle lists on: triangle matching, identity association
- * list, affinity, dense clique, min_num_pairs gate, estimate_tf, yaw + xy in a 4x4 row-major tf16 (query -> reference;
+ * list, affinity (as CSR straight from the associations: no m x m matrix, any number of putative associations whose CSR stays below
+ * 2^31 non-zeros), dense clique, min_num_pairs gate, estimate_tf, yaw + xy in a 4x4 row-major tf16 (query -> reference;
  * the caller inverts as place_recognition.cpp:621-624 does).  u0: start weights for the 3 * n_pairs putative
  * associations or NULL (fixed-seed generator).  counts: {putative associations, inliers}.  *found = 1 / 0. */
 int slide_semantic_clipper(const double* tri_model, int ntm, const double* tri_data, int ntd, const slide_clipper_params_t* p,

@@ -35,7 +35,7 @@ EXPORTS = [
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
     "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_intra_loop_closure",
-    "slide_loop_candidate_idx", "slide_clipper_affinity",
+    "slide_loop_candidate_idx", "slide_clipper_affinity", "slide_clipper_affinity_csr", "slide_clipper_dense_clique_csr", "slide_clipper_match",
     "slide_closest_stamp", "slide_clipper_default_params", "slide_clipper_dense_clique", "slide_match_triangles",
     "slide_estimate_tf2d", "slide_semantic_clipper", "slide_find_relative_meas_match", "slide_delaunay_2d", "slide_run_semantic_clipper",
     "slide_pick_next_measurement", "slide_in_loop_closure_region",
@@ -921,8 +921,67 @@ def clipper_dense_clique(M_upper, u0=None, params=None):
     return nodes[:nn.value].copy(), u[:n].copy(), sc.value
 
 
+def clipper_affinity_csr(D1, D2, A, sigma=0.01, epsilon=0.06, mindist=0.0, affinityeps=1e-4):
+    """scorePairwiseConsistency (clipper.cpp:21-65) ending in M_ = M.sparseView(): the symmetric affinity matrix without its diagonal
+    as CSR, built on the device without the dense m x m form.  Returns (rowptr (m + 1), col, val), columns ascending; the values
+    are clipper_affinity's bit for bit.  (The two-call protocol of slide_clipper_affinity_csr: sizes first, then the arrays.)"""
+    D1, D2 = _d(D1), _d(D2)
+    A = _i(A).reshape(-1, 2)
+    m = A.shape[0]
+    rowptr = np.zeros(m + 1, np.int32)
+    nnz = C.c_longlong(0)
+
+    def call(col, val, cap):
+        return lib().slide_clipper_affinity_csr(_p(D1), C.c_int(D1.shape[0]), _p(D2), C.c_int(D2.shape[0]), C.c_int(D1.shape[1]), _p(A),
+                                                C.c_int(m), C.c_double(sigma), C.c_double(epsilon), C.c_double(mindist),
+                                                C.c_double(affinityeps), _p(rowptr), col, val, C.c_longlong(cap), C.byref(nnz))
+    rc = call(None, None, 0)
+    if rc == SLIDE_OK:                       # nothing to fetch
+        return rowptr, np.zeros(0, np.int32), np.zeros(0)
+    if rc != SLIDE_ERR_CAPACITY or nnz.value <= 0:
+        _check(rc)
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+    _check(call(_p(col), _p(val), nnz.value))
+    return rowptr, col, val
+
+
+def clipper_dense_clique_csr(rowptr, col, val, u0=None, params=None):
+    """CLIPPER::findDenseClique (clipper.cpp:172-323, DSD_HEU) from the CSR of the symmetric affinity matrix without its diagonal
+    (clipper_affinity_csr's output).  Returns (nodes, u, score) — clipper_dense_clique's for the same matrix, bit for bit."""
+    rowptr, col, val = _i(rowptr), _i(col), _d(val)
+    n = len(rowptr) - 1
+    if n < 0 or len(col) != len(val) or (n >= 0 and len(rowptr) and rowptr[-1] != len(col)):
+        raise SlideError(f"SLIDE_ERR_INVALID: clipper CSR, row {max(n - 1, 0)}: rowptr[n] = {rowptr[-1] if len(rowptr) else None} "
+                         f"is not the length of col ({len(col)}) / val ({len(val)})")
+    p = params or clipper_params()
+    nodes = np.zeros(max(n, 1), np.int32)
+    u = np.zeros(max(n, 1))
+    nn, sc = C.c_int(0), C.c_double(0)
+    u0a = _d(u0) if u0 is not None else None
+    _check(lib().slide_clipper_dense_clique_csr(_p(rowptr), _p(col), _p(val), C.c_int(n), _p(u0a) if u0a is not None else None,
+                                                C.byref(p), _p(nodes), C.byref(nn), _p(u), C.byref(sc)))
+    return nodes[:nn.value].copy(), u[:n].copy(), sc.value
+
+
+def clipper_match(D1, D2, A, u0=None, params=None):
+    """scorePairwiseConsistency + findDenseClique + getSelectedAssociations in one call (slide_clipper_match): from the associations
+    to the clique with nothing of size m^2 anywhere.  sigma / epsilon / mindist / affinityeps come from params.
+    Returns (nodes, u, score) = clipper_dense_clique_csr(*clipper_affinity_csr(...)), bit for bit."""
+    D1, D2 = _d(D1), _d(D2)
+    A = _i(A).reshape(-1, 2)
+    m = A.shape[0]
+    p = params or clipper_params()
+    nodes = np.zeros(max(m, 1), np.int32)
+    u = np.zeros(max(m, 1))
+    nn, sc = C.c_int(0), C.c_double(0)
+    u0a = _d(u0) if u0 is not None else None
+    _check(lib().slide_clipper_match(_p(D1), C.c_int(D1.shape[0]), _p(D2), C.c_int(D2.shape[0]), C.c_int(D1.shape[1]), _p(A), C.c_int(m),
+                                     _p(u0a) if u0a is not None else None, C.byref(p), _p(nodes), C.byref(nn), _p(u), C.byref(sc)))
+    return nodes[:nn.value].copy(), u[:m].copy(), sc.value
+
+
 def clipper_last_solve_info():
-    """(workgroups, gradient evaluations) of this process's last clipper_dense_clique call: > 1 workgroup = the cooperative solve of
+    """(workgroups, gradient evaluations) of this process's last clipper_dense_clique / _csr / clipper_match call: > 1 workgroup = the cooperative solve of
     one large problem (n >= 1024, or SLIDE_CLIPPER_WGS)."""
     w, e = C.c_int(0), C.c_double(0)
     lib().slide_clipper_last_solve_info(C.byref(w), C.byref(e))
@@ -930,6 +989,7 @@ def clipper_last_solve_info():
 
 
 MS_PLACE_SWEEP, MS_TRI_MATCH, MS_CLQ_CSR, MS_CLQ_SOLVE, MS_AFFINITY, MS_CLQ_NNZ, MS_PLACE_PAIR_TESTS, MS_TRI_PAIRS, MS_PLACE_DIST_TESTS = range(9)
+MS_AFFINITY_CSR = 9
 
 
 def last_device_ms(what):

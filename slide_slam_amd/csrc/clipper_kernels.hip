@@ -2,7 +2,8 @@
 //
 // The reference keeps the affinity matrix M and the constraint pattern C (= sparsity pattern of M, clipper.cpp:55-64) as Eigen
 // sparse matrices and runs projected gradient ascent with backtracking on F(u) = u^T (M + I - d (11^T - C - I)) u; d grows in an
-// outer loop until no constraint is active.  Here: M in CSR (built on the device from the upper-filled dense affinity matrix), and
+// outer loop until no constraint is active.  Here: M in CSR (built on the device, from the upper-filled dense affinity matrix by
+// k_clq_csr or straight from the associations by k_affinity_csr — the same CSR bit for bit), and
 // the WHOLE solve — every product, reduction, clamp, normalisation, line-search and stopping decision — in ONE launch with no host
 // round trip inside the loop: a persistent workgroup of 1024 threads per problem (k_clq_solve, k_clq_solve_b: the iteration is
 // strictly sequential with O(nnz) work per evaluation, and the problems sloam meets — tens to hundreds of associations — leave a
@@ -38,6 +39,101 @@ __global__ __launch_bounds__(256) void k_clq_csr(const double* __restrict__ Mup,
   if (!EMIT && lane == 0) rowcnt[i] = base;
 }
 
+// ---- the affinity matrix as CSR straight from the associations (clipper.cpp:21-65 ending in M_ = M.sparseView()) -------------------
+// Row i of the SYMMETRIC matrix without its diagonal, never passing through the dense m x m form: one wave per row, the lanes over
+// the columns in chunks of 64, every entry scored by clipper_pair_score (kernels.hpp: the text k_clipper_affinity evaluates) with the
+// smaller association index first, so entry (i, j), entry (j, i) and the dense kernel's (min, max) are one evaluation of the same
+// operands.  Ballot ranks keep the columns ascending; no atomics: the same bits every run.  Two passes as k_clq_csr: EMIT = false
+// counts, EMIT = true writes at rowptr[i].  DIM 2 / 3: the row's two points in registers; DIM 0: any dim, read per pair.
+// GATHERED: X1 / X2 are the associations' points (k_affinity_gather), else D1 / D2 indexed through A.
+__global__ __launch_bounds__(256) void k_affinity_gather(const double* __restrict__ D1, const double* __restrict__ D2, int dim,
+                                                         const int32_t* __restrict__ A, int m, double* __restrict__ P1, double* __restrict__ P2) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)m * dim) return;
+  const size_t j = t / dim;
+  const int k = (int)(t - j * dim);
+  P1[t] = D1[(size_t)A[2 * j] * dim + k];
+  P2[t] = D2[(size_t)A[2 * j + 1] * dim + k];
+}
+template <bool EMIT, int DIM, bool GATHERED>
+__global__ __launch_bounds__(256) void k_affinity_csr(const double* __restrict__ X1, const double* __restrict__ X2, int dim,
+                                                      const int32_t* __restrict__ A, int m, double sigma, double eps, double mindist,
+                                                      double affinityeps, int* __restrict__ rowcnt, const int* __restrict__ rowptr,
+                                                      int* __restrict__ col, double* __restrict__ val) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= m) return;
+  const int i0 = A[2 * (size_t)i], i1 = A[2 * (size_t)i + 1];
+  const double* ri1 = X1 + (size_t)(GATHERED ? i : i0) * dim;
+  const double* ri2 = X2 + (size_t)(GATHERED ? i : i1) * dim;
+  constexpr int ND = DIM > 0 ? DIM : 1;
+  double a1[ND], a2[ND];
+  if (DIM > 0) {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) { a1[k] = ri1[k]; a2[k] = ri2[k]; }
+  }
+  int base = EMIT ? rowptr[i] : 0;
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    const int j = c0 + lane;
+    double v = 0.0;
+    if (j < m && j != i) {
+      const int j0 = A[2 * (size_t)j], j1 = A[2 * (size_t)j + 1];
+      const double* cj1 = X1 + (size_t)(GATHERED ? j : j0) * dim;
+      const double* cj2 = X2 + (size_t)(GATHERED ? j : j1) * dim;
+      const bool up = j > i;          // the row is the smaller index
+      if (DIM > 0) {
+        double lo1[ND], hi1[ND], lo2[ND], hi2[ND];
+#pragma unroll
+        for (int k = 0; k < ND; ++k) {
+          const double b1 = cj1[k], b2 = cj2[k];
+          lo1[k] = up ? a1[k] : b1; hi1[k] = up ? b1 : a1[k];
+          lo2[k] = up ? a2[k] : b2; hi2[k] = up ? b2 : a2[k];
+        }
+        v = clipper_pair_score<DIM>(up ? i0 : j0, up ? i1 : j1, up ? j0 : i0, up ? j1 : i1, lo1, hi1, lo2, hi2, dim, sigma, eps, mindist,
+                                    affinityeps);
+      } else {
+        v = clipper_pair_score<0>(up ? i0 : j0, up ? i1 : j1, up ? j0 : i0, up ? j1 : i1, up ? ri1 : cj1, up ? cj1 : ri1, up ? ri2 : cj2,
+                                  up ? cj2 : ri2, dim, sigma, eps, mindist, affinityeps);
+      }
+    }
+    const unsigned long long hit = __ballot(v != 0.0);
+    if (EMIT && v != 0.0) {
+      const int k = base + __popcll(hit & ((1ull << lane) - 1ull));
+      col[k] = j;
+      val[k] = v;
+    }
+    base += __popcll(hit);
+  }
+  if (!EMIT && lane == 0) rowcnt[i] = base;
+}
+void launch_affinity_gather(const double* D1, const double* D2, int dim, const int32_t* A, int m, double* P1, double* P2, hipStream_t s) {
+  const size_t n = (size_t)m * dim;
+  if (n > 0) hipLaunchKernelGGL(k_affinity_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, D1, D2, dim, A, m, P1, P2);
+}
+namespace {
+template <bool EMIT, int DIM>
+void affinity_csr_go(const double* D1, const double* D2, const double* P1, const double* P2, int dim, const int32_t* A, int m, double sigma,
+                     double eps, double mindist, double affinityeps, int* rowcnt, const int* rowptr, int* col, double* val, hipStream_t s) {
+  const dim3 grid((m + 3) / 4), block(256);
+  if (P1 && P2)
+    hipLaunchKernelGGL((k_affinity_csr<EMIT, DIM, true>), grid, block, 0, s, P1, P2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val);
+  else
+    hipLaunchKernelGGL((k_affinity_csr<EMIT, DIM, false>), grid, block, 0, s, D1, D2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val);
+}
+template <bool EMIT>
+void affinity_csr_dim(const double* D1, const double* D2, const double* P1, const double* P2, int dim, const int32_t* A, int m, double sigma,
+                      double eps, double mindist, double affinityeps, int* rowcnt, const int* rowptr, int* col, double* val, hipStream_t s) {
+  if (dim == 2) affinity_csr_go<EMIT, 2>(D1, D2, P1, P2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val, s);
+  else if (dim == 3) affinity_csr_go<EMIT, 3>(D1, D2, P1, P2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val, s);
+  else affinity_csr_go<EMIT, 0>(D1, D2, P1, P2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val, s);
+}
+}  // namespace
+void launch_affinity_csr(bool emit, const double* D1, const double* D2, const double* P1, const double* P2, int dim, const int32_t* A, int m,
+                         double sigma, double eps, double mindist, double affinityeps, int* rowcnt, const int* rowptr, int* col, double* val,
+                         hipStream_t s) {
+  if (m <= 0) return;
+  if (emit) affinity_csr_dim<true>(D1, D2, P1, P2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val, s);
+  else affinity_csr_dim<false>(D1, D2, P1, P2, dim, A, m, sigma, eps, mindist, affinityeps, rowcnt, rowptr, col, val, s);
+}
 
 __device__ __forceinline__ double clq_block_sum(double x, double* sh) {
   const int tid = threadIdx.x;

@@ -256,5 +256,37 @@ void launch_clq_solve(const int* rowptr, const int* col, const double* val, int 
                       double beta, double eps, int maxin, int maxol, int maxls, int rescale, double* out4, hipStream_t s);
 void launch_clipper_affinity(const double* D1, const double* D2, int dim, const int32_t* A, int m, double sigma, double eps,
                              double mindist, double affinityeps, double* M, hipStream_t s);
+// The score of one pair of associations (clipper.cpp:30-52 with euclidean_distance.cpp:13-31), THE one text both k_clipper_affinity
+// (dense upper triangle, place_kernels.hip) and k_affinity_csr (the sparse rows, clipper_kernels.hip) evaluate, always called with
+// the smaller association index as (i): associations (i0, i1) and (j0, j1), their points pi1 / pj1 in the first set and pi2 / pj2 in
+// the second.  Both sources are compiled with -ffp-contract=off, so what is left are correctly rounded IEEE operations in one fixed
+// order plus the device library's exp: the same bits wherever it is inlined.  DIM > 0: a compile-time dimension (points in registers).
+template <int DIM>
+__device__ __forceinline__ double clipper_pair_score(int i0, int i1, int j0, int j1, const double* pi1, const double* pj1, const double* pi2,
+                                                     const double* pj2, int dim, double sigma, double eps, double mindist, double affinityeps) {
+  double out = 0.0;
+  if (i0 != j0 && i1 != j1) {
+    const int nd = DIM > 0 ? DIM : dim;
+    double s1 = 0, s2 = 0;
+    for (int k = 0; k < nd; ++k) {
+      s1 += (pi1[k] - pj1[k]) * (pi1[k] - pj1[k]);
+      s2 += (pi2[k] - pj2[k]) * (pi2[k] - pj2[k]);
+    }
+    const double l1 = sqrt(s1), l2 = sqrt(s2);
+    if (!(mindist > 0 && (l1 < mindist || l2 < mindist))) {
+      const double c = fabs(l1 - l2);
+      const double scr = (c < eps) ? exp(-0.5 * c * c / (sigma * sigma)) : 0.0;
+      if (scr > affinityeps) out = scr;
+    }
+  }
+  return out;
+}
+// The same matrix as CSR straight from the associations (scorePairwiseConsistency ending in M_ = M.sparseView(), clipper.cpp:21-65):
+// the symmetric matrix without its diagonal, columns ascending.  count: rowcnt[i]; emit: col / val at rowptr[i].  P1 / P2 non-null:
+// the associations' points gathered beforehand (launch_affinity_gather: P1[j] = D1[A[j,0]], P2[j] = D2[A[j,1]]), read instead of D1 / D2.
+void launch_affinity_gather(const double* D1, const double* D2, int dim, const int32_t* A, int m, double* P1, double* P2, hipStream_t s);
+void launch_affinity_csr(bool emit, const double* D1, const double* D2, const double* P1, const double* P2, int dim, const int32_t* A, int m,
+                         double sigma, double eps, double mindist, double affinityeps, int* rowcnt, const int* rowptr, int* col, double* val,
+                         hipStream_t s);
 
 }  // namespace sl

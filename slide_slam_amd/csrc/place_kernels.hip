@@ -194,22 +194,10 @@ __global__ void k_clipper_affinity(const double* __restrict__ D1, const double* 
   const int i = blockIdx.y;
   if (j >= m || i >= m) return;
   double out = 0.0;
-  if (j > i && A[2 * i] != A[2 * j] && A[2 * i + 1] != A[2 * j + 1]) {
-    const double* ai = D1 + (size_t)A[2 * i] * dim;
-    const double* aj = D1 + (size_t)A[2 * j] * dim;
-    const double* bi = D2 + (size_t)A[2 * i + 1] * dim;
-    const double* bj = D2 + (size_t)A[2 * j + 1] * dim;
-    double s1 = 0, s2 = 0;
-    for (int k = 0; k < dim; ++k) {
-      s1 += (ai[k] - aj[k]) * (ai[k] - aj[k]);
-      s2 += (bi[k] - bj[k]) * (bi[k] - bj[k]);
-    }
-    const double l1 = sqrt(s1), l2 = sqrt(s2);
-    if (!(mindist > 0 && (l1 < mindist || l2 < mindist))) {
-      const double c = fabs(l1 - l2);
-      const double scr = (c < eps) ? exp(-0.5 * c * c / (sigma * sigma)) : 0.0;
-      if (scr > affinityeps) out = scr;
-    }
+  if (j > i) {      // (i < j: the smaller index first, as k_affinity_csr calls it for both (i, j) and (j, i))
+    const int i0 = A[2 * i], i1 = A[2 * i + 1], j0 = A[2 * j], j1 = A[2 * j + 1];
+    out = clipper_pair_score<0>(i0, i1, j0, j1, D1 + (size_t)i0 * dim, D1 + (size_t)j0 * dim, D2 + (size_t)i1 * dim, D2 + (size_t)j1 * dim, dim,
+                                sigma, eps, mindist, affinityeps);
   }
   M[(size_t)i * m + j] = out;
 }
