@@ -665,6 +665,44 @@ int slide_run_semantic_clipper(const double* ref7, int nr, const double* qry7, i
                                int min_num_pairs, double matching_threshold, const double* u0, int n_u0, double tf16[16],
                                int counts[2], int* found);
 
+/* The SlideGraph parameters of PlaceRecognition, names and defaults of place_recognition.cpp:65-75 (ns "<prefix>_slidegraph"). */
+typedef struct {
+  double sigma;                     /* 0.1   sigma                          (:70-71) */
+  double epsilon;                   /* 0.1   epsilon                        (:72-73) */
+  int num_inliers_threshold;        /* 10    num_inliners_threshold         (:66-67) -> run_semantic_clipper's min_num_pairs */
+  double matching_threshold;        /* 0.1   descriptor_matching_threshold  (:68-69) */
+  int min_num_map_objects_to_start; /* 20    min_num_map_objects_to_start   (:74-75) */
+} slide_slidegraph_params_t;
+void slide_slidegraph_default_params(slide_slidegraph_params_t* p);
+/* PlaceRecognition::findInterLoopClosureWithClipper place_recognition.cpp:541-629 (seam S4), the method itself, in its order:
+ * 1. rows with x == 0.0 && y == 0.0 are dropped from both maps (:584, :601); 2. the matcher runs only when BOTH maps keep at least
+ * min_num_map_objects_to_start objects (:618); 3. run_semantic_clipper on the kept rows (:621: Delaunay, triangle matching, CSR
+ * affinity, clique, num_inliers_threshold); 4. tf16 is the INVERSE of what run_semantic_clipper estimated (:624), in the closed form of
+ * a planar rigid 4x4 (R^T, -R^T t) — the matrix the reference stores as tfFromQueryToRef.  Nothing found (gate, no matched triangle,
+ * too few inliers): *found = 0 and tf16 = identity.  Maps: rows [label, x, y, z, d1, d2, d3]; p NULL: the defaults; u0 / n_u0 as
+ * slide_run_semantic_clipper.  counts = {kept reference objects, kept query objects, putative associations, inliers}.  A pair
+ * stopped by the gate or without triangles never touches the device.  This is the list form below with one pair; the pair's
+ * status is the return value. */
+int slide_find_inter_loop_closure_clipper(const double* ref7, int nr, const double* qry7, int nq, const slide_slidegraph_params_t* p,
+                                          const double* u0, int n_u0, double tf16[16], int counts[4], int* found);
+/* The loop of SLOAMNode::interLoopClosureThread_ (sloamNode.cpp:587-694: one findInterLoopClosureWithClipper per robot without a
+ * loopClosureTf, 28 pairs in a central job over eight robots) as ONE call.  Map i = rows [map_off[i], map_off[i + 1]) of maps7;
+ * pair k = (reference map pairs[2 k], query map pairs[2 k + 1]).  Every map is filtered and triangulated once however many pairs
+ * name it; triangle matching (k_tri_match_seg), the CSRs (k_affinity_csr_seg) and the solves (k_clq_solve_b; a pair of 1024
+ * associations or more takes the single call's cooperative route on its slice) run for all pairs together, with three blocking
+ * read-backs per call (triangle totals, non-zero totals, results) whatever n_pairs is.  Pair k is evaluated by itself: tf16n + 16 k,
+ * counts4n + 4 k and found[k] are exactly what slide_find_inter_loop_closure_clipper gives for that pair alone, bit for bit,
+ * whatever else is in the list and wherever the pair stands in it.  u0 may be NULL, u0[k] may be NULL (the fixed-seed start).
+ * Refused as a whole on the host, before the device is touched and with nothing written (SLIDE_ERR_INVALID): n_pairs < 0, n_maps < 0,
+ * a NULL that is needed (pairs, map_off, tf16n, counts4n, found; maps7 when a map has rows; n_u0 when a u0[k] is given), a negative
+ * or decreasing map_off, a pair naming a map outside [0, n_maps).  Otherwise SLIDE_OK (SLIDE_ERR_HIP: no usable device), and a
+ * pair's own fault goes to status[k] (status may be NULL) with found[k] = 0 and identity in its tf16: SLIDE_ERR_INVALID for a u0[k]
+ * whose length is not the pair's number of putative associations, SLIDE_ERR_CAPACITY for a pair whose CSR would pass 2^31 - 1
+ * non-zeros or that would take the list's associations past 2^30 in total.  n_pairs == 0: SLIDE_OK without a device. */
+int slide_find_inter_loop_closures_clipper(const double* maps7, const int32_t* map_off, int n_maps, const int32_t* pairs, int n_pairs,
+                                           const slide_slidegraph_params_t* p, const double* const* u0, const int* n_u0, double* tf16n,
+                                           int32_t* counts4n, int32_t* found, int32_t* status);
+
 /* sloam::FindRelativeMeasurementMatch / GetIndexClosestPoseMstPair (src/core/sloam.cpp:321-440).
  * Stamps are (sec, nsec) pairs.  Host-side logic (tiny, sequential): no kernel. */
 int slide_closest_stamp(const int64_t* sec, const int64_t* nsec, int n, int64_t qsec, int64_t qnsec, int* idx, double* diff);

@@ -420,5 +420,80 @@ class SemanticFactorGraphWrapper : public SemanticFactorGraph {
   slide_backend_t* b_ = nullptr;
 };
 
+// ---- S4 (the SlideGraph side) ----------------------------------------------------------------------------------------------------
+// PlaceRecognition::findInterLoopClosureWithClipper include/core/place_recognition.h, src/core/place_recognition.cpp:541-629, with the
+// reference's argument order and container shapes: Objects = a container of rows indexable [0..6] ([label, x, y, z, d1, d2, d3];
+// std::vector<Eigen::Vector7d> at the call site), Mat4 = a 4x4 written through m(r, c) (Eigen::Matrix4d; slide::Mat4 below when Eigen
+// is absent).  The (0, 0) filter, the object-count gate and the inversion of run_semantic_clipper's estimate happen inside the
+// library; tfFromQueryToRef is the identity when nothing is found (sloamNode.cpp:618-620 starts from the identity).
+struct Mat4 {
+  double m[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  double& operator()(int r, int c) { return m[4 * r + c]; }
+  double operator()(int r, int c) const { return m[4 * r + c]; }
+};
+class PlaceRecognition {
+ public:
+  slide_slidegraph_params_t slidegraph;      // place_recognition.cpp:65-75: sigma, epsilon, num_inliners_threshold, descriptor_matching_threshold, min_num_map_objects_to_start
+  explicit PlaceRecognition(const slide_slidegraph_params_t* p = nullptr) {
+    if (p) slidegraph = *p; else slide_slidegraph_default_params(&slidegraph);
+  }
+
+  template <class Objects, class M4>
+  bool findInterLoopClosureWithClipper(const Objects& reference_objects, const Objects& query_objects, M4& tfFromQueryToRef) const {
+    std::vector<double> ref, qry;
+    flatten(reference_objects, ref);
+    flatten(query_objects, qry);
+    double tf[16];
+    int counts[4], found = 0;
+    detail::check(slide_find_inter_loop_closure_clipper(ref.data(), (int)(ref.size() / 7), qry.data(), (int)(qry.size() / 7), &slidegraph, nullptr, 0,
+                                                        tf, counts, &found),
+                  "findInterLoopClosureWithClipper");
+    assign(tfFromQueryToRef, tf);
+    return found != 0;
+  }
+
+  // The loop of SLOAMNode::interLoopClosureThread_ (sloamNode.cpp:600-694: the host robot's map against every robot without a
+  // loopClosureTf) as one call: tfs[k] / found[k] are what findInterLoopClosureWithClipper(reference_objects, query_maps[k], ...) gives.
+  template <class Objects, class M4>
+  void findInterLoopClosuresWithClipper(const Objects& reference_objects, const std::vector<Objects>& query_maps, std::vector<M4>& tfs,
+                                        std::vector<bool>& found) const {
+    const int n = (int)query_maps.size();
+    std::vector<double> flat;
+    std::vector<int32_t> off(1, 0), pairs;
+    flatten(reference_objects, flat);
+    off.push_back((int32_t)(flat.size() / 7));
+    for (int k = 0; k < n; ++k) {
+      flatten(query_maps[k], flat);
+      off.push_back((int32_t)(flat.size() / 7));
+      pairs.push_back(0);
+      pairs.push_back(k + 1);
+    }
+    std::vector<double> tf(16 * (size_t)n + 1);
+    std::vector<int32_t> counts(4 * (size_t)n + 1), f(n + 1), status(n + 1);
+    detail::check(slide_find_inter_loop_closures_clipper(flat.data(), off.data(), n + 1, pairs.data(), n, &slidegraph, nullptr, nullptr, tf.data(),
+                                                         counts.data(), f.data(), status.data()),
+                  "findInterLoopClosuresWithClipper");
+    tfs.resize(n);
+    found.assign(n, false);
+    for (int k = 0; k < n; ++k) {
+      if (status[k] < 0) throw Error(status[k], "findInterLoopClosuresWithClipper: query map " + std::to_string(k) + ": more associations or non-zeros than the library holds");
+      assign(tfs[k], tf.data() + 16 * (size_t)k);
+      found[k] = f[k] != 0;
+    }
+  }
+
+ private:
+  template <class Objects>
+  static void flatten(const Objects& objs, std::vector<double>& out) {
+    for (const auto& o : objs)
+      for (int c = 0; c < 7; ++c) out.push_back(o[c]);
+  }
+  template <class M4>
+  static void assign(M4& dst, const double tf[16]) {
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) dst(r, c) = tf[4 * r + c];
+  }
+};
+
 }  // namespace slide
 #endif  // SLIDE_SLOAM_ADAPTOR_HPP_

@@ -39,6 +39,7 @@ EXPORTS = [
     "slide_closest_stamp", "slide_clipper_default_params", "slide_clipper_dense_clique", "slide_match_triangles",
     "slide_estimate_tf2d", "slide_semantic_clipper", "slide_find_relative_meas_match", "slide_delaunay_2d", "slide_run_semantic_clipper",
     "slide_pick_next_measurement", "slide_in_loop_closure_region",
+    "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
 ]
 
 
@@ -1117,6 +1118,85 @@ def run_semantic_clipper(ref7, qry7, sigma=0.01, epsilon=0.06, min_num_pairs=4, 
                                             _p(u0a) if u0a is not None else None, C.c_int(len(u0a) if u0a is not None else 0),
                                             _p(tf), _p(counts), C.byref(found)))
     return dict(found=bool(found.value), tf=tf.reshape(4, 4), n_putative=int(counts[0]), n_inliers=int(counts[1]))
+
+
+class SlidegraphParams(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("epsilon", C.c_double), ("num_inliers_threshold", C.c_int), ("matching_threshold", C.c_double),
+                ("min_num_map_objects_to_start", C.c_int)]
+
+
+def slidegraph_params(**kw) -> SlidegraphParams:
+    """PlaceRecognition's SlideGraph parameters with the reference's defaults (place_recognition.cpp:65-75)."""
+    p = SlidegraphParams()
+    lib().slide_slidegraph_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"slidegraph_params: no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _closure_dict(tf, counts, found):
+    return dict(found=bool(found), tf=np.array(tf, dtype=np.float64).reshape(4, 4), n_putative=int(counts[2]), n_inliers=int(counts[3]),
+                n_ref_used=int(counts[0]), n_qry_used=int(counts[1]))
+
+
+def find_inter_loop_closure_clipper(ref7, qry7, params=None, u0=None):
+    """PlaceRecognition::findInterLoopClosureWithClipper (place_recognition.cpp:541-629) on two object maps (rows [label, x, y, z, d1,
+    d2, d3]): rows with x == y == 0 dropped, the gate on the kept counts, run_semantic_clipper, and tf = the INVERSE of its estimate
+    (identity when nothing is found).  Returns dict(found, tf, n_putative, n_inliers, n_ref_used, n_qry_used)."""
+    r, q = _d(ref7).reshape(-1, 7), _d(qry7).reshape(-1, 7)
+    p = params or slidegraph_params()
+    tf = np.zeros(16)
+    counts = np.zeros(4, np.int32)
+    found = C.c_int(0)
+    u0a = _d(u0) if u0 is not None else None
+    _check(lib().slide_find_inter_loop_closure_clipper(_p(r), C.c_int(len(r)), _p(q), C.c_int(len(q)), C.byref(p),
+                                                       _p(u0a) if u0a is not None else None, C.c_int(len(u0a) if u0a is not None else 0),
+                                                       _p(tf), _p(counts), C.byref(found)))
+    return _closure_dict(tf, counts, found.value)
+
+
+def find_inter_loop_closures_clipper(maps, pairs, params=None, u0s=None):
+    """The loop of SLOAMNode::interLoopClosureThread_ (sloamNode.cpp:587-694) in one call: maps = list of (n_i, 7) object maps, pairs =
+    list of (reference map, query map) indices, u0s = None or a list with None / start weights per pair.  Every pair is evaluated by
+    itself and gets exactly find_inter_loop_closure_clipper's result for that pair alone.  Returns a list of dicts as the single call's,
+    each with `status` added (0, or the pair's own SLIDE_ERR_INVALID / SLIDE_ERR_CAPACITY)."""
+    ms = [_d(m).reshape(-1, 7) for m in maps]
+    off = np.zeros(len(ms) + 1, np.int32)
+    off[1:] = np.cumsum([len(m) for m in ms])
+    flat = np.ascontiguousarray(np.concatenate(ms, axis=0)) if ms else np.zeros((0, 7))
+    if len(flat) == 0:
+        flat = np.zeros((1, 7))
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n = len(pr)
+    p = params or slidegraph_params()
+    tf = np.zeros((max(n, 1), 16))
+    counts = np.zeros((max(n, 1), 4), np.int32)
+    found = np.zeros(max(n, 1), np.int32)
+    status = np.zeros(max(n, 1), np.int32)
+    u0_ptrs = n_u0 = None
+    keep = []
+    if u0s is not None:
+        if len(u0s) != n:
+            raise ValueError("u0s needs one entry (or None) per pair")
+        u0_ptrs = (C.c_void_p * max(n, 1))()
+        n_u0 = np.zeros(max(n, 1), np.int32)
+        for k, u in enumerate(u0s):
+            if u is not None:
+                a = _d(u).reshape(-1)
+                keep.append(a)
+                u0_ptrs[k] = a.ctypes.data
+                n_u0[k] = len(a)
+    _check(lib().slide_find_inter_loop_closures_clipper(_p(flat), _p(off), C.c_int(len(ms)), _p(pr if n else np.zeros((1, 2), np.int32)), C.c_int(n),
+                                                        C.byref(p), u0_ptrs, _p(n_u0) if n_u0 is not None else None, _p(tf), _p(counts),
+                                                        _p(found), _p(status)))
+    out = []
+    for k in range(n):
+        d = _closure_dict(tf[k], counts[k], found[k])
+        d["status"] = int(status[k])
+        out.append(d)
+    return out
 
 
 def pick_next_measurement(odom, obs, rel, latest, current_time, msg_delay_tolerance, min_odom_distance):

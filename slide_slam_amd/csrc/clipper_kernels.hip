@@ -105,6 +105,77 @@ __global__ __launch_bounds__(256) void k_affinity_csr(const double* __restrict__
   }
   if (!EMIT && lane == 0) rowcnt[i] = base;
 }
+// The same for a LIST of problems in one launch (the robot pairs of sloamNode.cpp:600-694), dim 2, identity association list
+// (semantic_clipper.cpp:207-211: association a names point a of both sets): the rows of all pairs flattened behind aoff[0 .. n_seg],
+// the columns of a row run over ITS pair only, in chunks of 64 counted from the pair's first association, every entry one
+// clipper_pair_score<2> with the smaller association index first — so the CSR of a pair is k_affinity_csr's for that pair alone, bit
+// for bit.  EMIT = false: rowcnt[row].  EMIT = true: row i of pair s at nnz0[s] + rowptr[aoff[s] + s + i] (rowptr: the segmented scan,
+// n + 1 entries per pair; col / val: the pairs' arrays one after the other, indexed in 64 bits; nnz0[s] < 0: the pair was dropped).
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_affinity_csr_seg(const double* __restrict__ P1, const double* __restrict__ P2, const int* __restrict__ aoff,
+                                                          int n_seg, int n_rows, double sigma, double eps, double mindist, double affinityeps,
+                                                          int* __restrict__ rowcnt, const int* __restrict__ rowptr,
+                                                          const long long* __restrict__ nnz0, int* __restrict__ col, double* __restrict__ val) {
+  const int row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))), lane = threadIdx.x & 63;
+  if (row >= n_rows) return;
+  const int s = seg_of_row(aoff, n_seg, row);
+  const int a0 = aoff[s], m = aoff[s + 1] - a0, i = row - a0;
+  const double* X1 = P1 + 2 * (size_t)a0;
+  const double* X2 = P2 + 2 * (size_t)a0;
+  long long base = 0;
+  if (EMIT) {
+    if (nnz0[s] < 0) return;
+    base = nnz0[s] + rowptr[(size_t)row + s];
+  }
+  const double a1[2] = {X1[2 * (size_t)i], X1[2 * (size_t)i + 1]}, a2[2] = {X2[2 * (size_t)i], X2[2 * (size_t)i + 1]};
+  int cnt = 0;
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    const int j = c0 + lane;
+    double v = 0.0;
+    if (j < m && j != i) {
+      const bool up = j > i;          // the row is the smaller index
+      double lo1[2], hi1[2], lo2[2], hi2[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const double b1 = X1[2 * (size_t)j + k], b2 = X2[2 * (size_t)j + k];
+        lo1[k] = up ? a1[k] : b1; hi1[k] = up ? b1 : a1[k];
+        lo2[k] = up ? a2[k] : b2; hi2[k] = up ? b2 : a2[k];
+      }
+      const int lo = up ? i : j, hi = up ? j : i;
+      v = clipper_pair_score<2>(lo, lo, hi, hi, lo1, hi1, lo2, hi2, 2, sigma, eps, mindist, affinityeps);
+    }
+    const unsigned long long hit = __ballot(v != 0.0);
+    if (EMIT && v != 0.0) {
+      const long long k = base + __popcll(hit & ((1ull << lane) - 1ull));
+      col[k] = j;
+      val[k] = v;
+    }
+    base += __popcll(hit);
+    cnt += __popcll(hit);
+  }
+  if (!EMIT && lane == 0) rowcnt[row] = cnt;
+}
+void launch_affinity_csr_seg(bool emit, const double* P1, const double* P2, const int* aoff, int n_seg, int n_rows, double sigma, double eps,
+                             double mindist, double affinityeps, int* rowcnt, const int* rowptr, const long long* nnz0, int* col, double* val,
+                             hipStream_t s) {
+  if (n_rows <= 0) return;
+  const dim3 grid((n_rows + 3) / 4), block(256);
+  if (emit)
+    hipLaunchKernelGGL(k_affinity_csr_seg<true>, grid, block, 0, s, P1, P2, aoff, n_seg, n_rows, sigma, eps, mindist, affinityeps, rowcnt, rowptr, nnz0, col, val);
+  else
+    hipLaunchKernelGGL(k_affinity_csr_seg<false>, grid, block, 0, s, P1, P2, aoff, n_seg, n_rows, sigma, eps, mindist, affinityeps, rowcnt, rowptr, nnz0, col, val);
+}
+// the solves' results side by side for ONE read-back: u of pair s (the first n of its 6 n work doubles) to U[aoff[s] ...]
+__global__ __launch_bounds__(256) void k_clq_pack_u(const double* __restrict__ work, const int* __restrict__ aoff, int n_seg, int n_rows,
+                                                    double* __restrict__ U) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  const int a0 = aoff[seg_of_row(aoff, n_seg, row)];
+  U[row] = work[6 * (size_t)a0 + (size_t)(row - a0)];
+}
+void launch_clq_pack_u(const double* work, const int* aoff, int n_seg, int n_rows, double* U, hipStream_t s) {
+  if (n_rows > 0) hipLaunchKernelGGL(k_clq_pack_u, dim3((n_rows + 255) / 256), dim3(256), 0, s, work, aoff, n_seg, n_rows, U);
+}
 void launch_affinity_gather(const double* D1, const double* D2, int dim, const int32_t* A, int m, double* P1, double* P2, hipStream_t s) {
   const size_t n = (size_t)m * dim;
   if (n > 0) hipLaunchKernelGGL(k_affinity_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, D1, D2, dim, A, m, P1, P2);

@@ -235,6 +235,24 @@ void launch_place_argmax(const int32_t* inliers, long long n, long long* best_id
 void launch_tri_prepare(const double* tri, int n, double* sdist, double* sxy, hipStream_t s);
 void launch_tri_match(bool emit, const double* dm, const double* xm, int ntm, const double* dd, const double* xd, int ntd, double thr,
                       int* counts, const long long* offs, double* pts, double* diffs, hipStream_t s);
+// A list of map pairs in one launch (slide_find_inter_loop_closures_clipper): the rows of all pairs flattened behind a row-offset
+// table off[0 .. n_seg]; the segment of a row is the LAST s with off[s] <= row (empty segments are passed over).  Called with a
+// wave-uniform row, so the search is scalar code.
+__device__ __forceinline__ int seg_of_row(const int* __restrict__ off, int n_seg, int row) {
+  int lo = 0, hi = n_seg;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= row) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+struct TriSeg { int tm0, td0, ntd; };      // a pair's model / data triangles in the prepared arrays of all maps: first model, first data, data count
+void launch_tri_match_seg(bool emit, const double* sd, const double* sx, const int* rowoff, const TriSeg* segs, int n_seg, int n_rows, double thr,
+                          int* counts, const long long* offs, const long long* base, double* P1, double* P2, hipStream_t s);
+// exclusive scans of per-row counts restarting at every segment, totals[s] = the segment's sum (64 bits); the rowptr form writes the
+// n + 1 row pointers of segment s at rowptr[segoff[s] + s ...]
+void launch_seg_scan64(const int* cnt, const int* segoff, int n_seg, long long* out, long long* totals, hipStream_t s);
+void launch_seg_scan_rowptr(const int* cnt, const int* segoff, int n_seg, int* rowptr, long long* totals, hipStream_t s);
 // clipper_kernels.hip — CLIPPER dense clique on the device: CSR of the symmetric affinity matrix from its dense upper triangle (count,
 // host prefix sum, fill), then the whole projected-gradient solve in one persistent workgroup.  work6n: 6 n doubles (u comes back in the
 // first n), out4: {F, d, gradient evaluations, outer iterations}
@@ -288,5 +306,13 @@ void launch_affinity_gather(const double* D1, const double* D2, int dim, const i
 void launch_affinity_csr(bool emit, const double* D1, const double* D2, const double* P1, const double* P2, int dim, const int32_t* A, int m,
                          double sigma, double eps, double mindist, double affinityeps, int* rowcnt, const int* rowptr, int* col, double* val,
                          hipStream_t s);
+// The CSRs of a LIST of problems in one launch (dim 2, identity association list; clipper_kernels.hip): P1 / P2 the associations' points of
+// all pairs, aoff[0 .. n_seg] their association offsets.  count: rowcnt[row]; emit: pair s at nnz0[s] (< 0: skipped) + its own row
+// pointers rowptr[aoff[s] + s ...].  Each pair's CSR equals launch_affinity_csr's for that pair alone bit for bit.
+void launch_affinity_csr_seg(bool emit, const double* P1, const double* P2, const int* aoff, int n_seg, int n_rows, double sigma, double eps,
+                             double mindist, double affinityeps, int* rowcnt, const int* rowptr, const long long* nnz0, int* col, double* val,
+                             hipStream_t s);
+// U[aoff[s] + i] = work[6 aoff[s] + i]: the solved weights of all pairs side by side
+void launch_clq_pack_u(const double* work, const int* aoff, int n_seg, int n_rows, double* U, hipStream_t s);
 
 }  // namespace sl

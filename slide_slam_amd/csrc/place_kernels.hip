@@ -225,6 +225,14 @@ __global__ void k_tri_prepare(const double* __restrict__ tri, int n, double* __r
   double* o = sxy + 6 * (size_t)t;
   o[0] = ax; o[1] = ay; o[2] = bx; o[3] = by; o[4] = gx; o[5] = gy;
 }
+// compute_triangle_diff (semantic_clipper.cpp:49-66) of one (model, data) triangle pair from their sorted vertex-centroid distances:
+// THE one text k_tri_match and k_tri_match_seg evaluate (this source is compiled with -ffp-contract=off: the same bits in both).
+__device__ __forceinline__ double tri_pair_diff(double m0, double m1, double m2, const double* __restrict__ d3) {
+  const double e0 = m0 - d3[0], e1 = m1 - d3[1], e2 = m2 - d3[2];
+  double sacc = 0.0;
+  sacc += e0 * e0; sacc += e1 * e1; sacc += e2 * e2;
+  return sqrt(sacc);
+}
 // One wave per model triangle, lanes over the data triangles.  EMIT = false: counts[i] = matches of row i.
 // EMIT = true: rows are written at offs[i] in data order (ballot ranks keep the reference's loop order).
 template <bool EMIT>
@@ -242,10 +250,7 @@ __global__ __launch_bounds__(256) void k_tri_match(const double* __restrict__ dm
     bool hit = false;
     double diff = 0.0;
     if (j < ntd) {
-      const double e0 = m0 - dd[3 * (size_t)j], e1 = m1 - dd[3 * (size_t)j + 1], e2 = m2 - dd[3 * (size_t)j + 2];
-      double sacc = 0.0;
-      sacc += e0 * e0; sacc += e1 * e1; sacc += e2 * e2;
-      diff = sqrt(sacc);
+      diff = tri_pair_diff(m0, m1, m2, dd + 3 * (size_t)j);
       hit = diff < thr;
     }
     const unsigned long long mask = __ballot(hit);
@@ -263,6 +268,101 @@ __global__ __launch_bounds__(256) void k_tri_match(const double* __restrict__ dm
     cnt += __popcll(mask);
   }
   if (!EMIT && lane == 0) counts[i] = cnt;
+}
+// The same for a LIST of map pairs in one launch (the robot pairs of sloamNode.cpp:600-694): the rows of all pairs flattened, row =
+// one model triangle of one pair, one wave per row, four rows per workgroup.  The wave finds its pair in the row-offset table
+// (uniform per wave: scalar code) and scans the data triangles of ITS pair only, in chunks of 64 counted from the pair's first data
+// triangle — so the test, the ballot ranks and hence the order within a row are k_tri_match's for that pair alone.  sd / sx: the
+// prepared triangles of all maps, one after the other (one k_tri_prepare launch).  EMIT = false: counts[row].  EMIT = true: the
+// matched pair number base[s] + offs[row] + rank (offs: the segmented scan of counts, restarting at every pair; base[s] < 0: the
+// pair was dropped) writes its three associations' points straight into the layout k_affinity_csr_seg reads — P1[a] = model vertex,
+// P2[a] = data vertex, a = 3 * pair number + vertex, the identity association list of semantic_clipper.cpp:207-211.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_tri_match_seg(const double* __restrict__ sd, const double* __restrict__ sx,
+                                                       const int* __restrict__ rowoff, const TriSeg* __restrict__ segs, int n_seg, int n_rows,
+                                                       double thr, int* __restrict__ counts, const long long* __restrict__ offs,
+                                                       const long long* __restrict__ base, double* __restrict__ P1, double* __restrict__ P2) {
+  const int row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))), lane = threadIdx.x & 63;
+  if (row >= n_rows) return;
+  const int s = seg_of_row(rowoff, n_seg, row);
+  const TriSeg S = segs[s];
+  const size_t i = (size_t)S.tm0 + (size_t)(row - rowoff[s]);
+  const double* dd = sd + 3 * (size_t)S.td0;
+  const double* xd = sx + 6 * (size_t)S.td0;
+  const double m0 = sd[3 * i], m1 = sd[3 * i + 1], m2 = sd[3 * i + 2];
+  long long at = 0;
+  if (EMIT) {
+    if (base[s] < 0) return;
+    at = base[s] + offs[row];
+  }
+  int cnt = 0;
+  for (int j0 = 0; j0 < S.ntd; j0 += 64) {
+    const int j = j0 + lane;
+    bool hit = false;
+    if (j < S.ntd) hit = tri_pair_diff(m0, m1, m2, dd + 3 * (size_t)j) < thr;
+    const unsigned long long mask = __ballot(hit);
+    if (EMIT && hit) {
+      const long long a = 3 * (at + __popcll(mask & ((1ull << lane) - 1ull)));
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        P1[2 * (a + k)] = sx[6 * i + 2 * k]; P1[2 * (a + k) + 1] = sx[6 * i + 2 * k + 1];
+        P2[2 * (a + k)] = xd[6 * (size_t)j + 2 * k]; P2[2 * (a + k) + 1] = xd[6 * (size_t)j + 2 * k + 1];
+      }
+    }
+    at += __popcll(mask);
+    cnt += __popcll(mask);
+  }
+  if (!EMIT && lane == 0) counts[row] = cnt;
+}
+
+// Exclusive scan of per-row counts that restarts at every segment (pair), on the device: one workgroup per segment walks its rows
+// [segoff[s], segoff[s + 1]) in chunks of 256 (wave scans by shuffle, the four wave sums through LDS, a running carry), sums in 64
+// bits.  out[row + pad * s]; pad = 1 leaves room for the closing entry of every segment, which is written too: the n + 1 row
+// pointers of a CSR per segment (OUT = int: a segment whose total passes 2^31 - 1 shows in totals[s], its entries are not used).
+// totals[s]: the segment's sum — all the host reads back.
+template <class OUT>
+__global__ __launch_bounds__(256) void k_seg_scan(const int* __restrict__ cnt, const int* __restrict__ segoff, OUT* __restrict__ out, int pad,
+                                                  long long* __restrict__ totals) {
+  __shared__ long long wsum[4];
+  const int s = blockIdx.x, r0 = segoff[s], r1 = segoff[s + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long carry = 0;
+  for (int c0 = r0; c0 < r1; c0 += 256) {
+    const int r = c0 + (int)threadIdx.x;
+    const long long v = r < r1 ? (long long)cnt[r] : 0;
+    long long x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const long long y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    __syncthreads();                      // (wsum may still be read from the previous chunk)
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    long long before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { if (w < wave) before += wsum[w]; all += wsum[w]; }
+    if (r < r1) out[(size_t)r + (size_t)pad * s] = (OUT)(carry + before + x - v);
+    carry += all;
+  }
+  if (threadIdx.x == 0) {
+    totals[s] = carry;
+    if (pad) out[(size_t)r1 + (size_t)pad * s] = (OUT)carry;
+  }
+}
+
+void launch_tri_match_seg(bool emit, const double* sd, const double* sx, const int* rowoff, const TriSeg* segs, int n_seg, int n_rows, double thr,
+                          int* counts, const long long* offs, const long long* base, double* P1, double* P2, hipStream_t s) {
+  if (n_rows <= 0) return;
+  const dim3 grid((n_rows + 3) / 4), block(256);
+  if (emit) hipLaunchKernelGGL(k_tri_match_seg<true>, grid, block, 0, s, sd, sx, rowoff, segs, n_seg, n_rows, thr, counts, offs, base, P1, P2);
+  else hipLaunchKernelGGL(k_tri_match_seg<false>, grid, block, 0, s, sd, sx, rowoff, segs, n_seg, n_rows, thr, counts, offs, base, P1, P2);
+}
+void launch_seg_scan64(const int* cnt, const int* segoff, int n_seg, long long* out, long long* totals, hipStream_t s) {
+  if (n_seg > 0) hipLaunchKernelGGL(k_seg_scan<long long>, dim3(n_seg), dim3(256), 0, s, cnt, segoff, out, 0, totals);
+}
+void launch_seg_scan_rowptr(const int* cnt, const int* segoff, int n_seg, int* rowptr, long long* totals, hipStream_t s) {
+  if (n_seg > 0) hipLaunchKernelGGL(k_seg_scan<int>, dim3(n_seg), dim3(256), 0, s, cnt, segoff, rowptr, 1, totals);
 }
 
 void launch_tri_prepare(const double* tri, int n, double* sdist, double* sxy, hipStream_t s) {
