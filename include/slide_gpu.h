@@ -524,6 +524,30 @@ int slide_match_maps_sweep(const double* ref7, int nr, const double* qry7, int n
  * Returns 1 found / 0 not found / negative error.  tf16: 4x4 row-major query->reference. */
 int slide_find_inter_loop_closure(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t* p,
                                   double tf16[16], int* inliers, double xyzyaw[4]);
+/* The SlideMatch branch of SLOAMNode::interLoopClosureThread_ (sloamNode.cpp:600-694: one findInterLoopClosure,
+ * place_recognition.cpp:498-538, per robot without a loopClosureTf; 28 pairs in a central job over eight robots, 7 with one shared
+ * reference map on a host robot) as ONE call.  Map i = rows [map_off[i], map_off[i + 1]) of maps7; pair k = (reference map
+ * pairs[2 k], query map pairs[2 k + 1]) — the layout of slide_find_inter_loop_closures_clipper.  Every map is centred once and every
+ * distinct reference map bucketed once however many pairs name it; all tables go up in one buffer, k_place_sweep_seg sweeps the
+ * lattices of all pairs in one launch (workgroups shared out by candidates x distance tests) keeping only a running best per wave,
+ * k_place_best_seg reduces per pair, and ONE read-back fetches the winners: one allocation, one upload, two launches and one blocking
+ * read-back per call whatever n_pairs is, and no buffer per candidate.  Pair k is evaluated by itself: found[k], inliers[k],
+ * xyzyaw4n + 4 k and tf16n + 16 k are bit for bit what slide_find_inter_loop_closure returns and writes for that pair alone, whatever
+ * else is in the list, wherever the pair stands in it and however the workgroups are shared out; a pair that is not found has the
+ * identity in its tf16 and zeros in its xyzyaw.  n_candidates[k]: the pair's lattice size; best_index[k]: the winning candidate in
+ * lattice order (ring, x, y, then yaw), the first of the maximum, -1 when the pair has no lattice or did not run.  best_index,
+ * n_candidates, xyzyaw4n and status may be NULL.  The environment variable SLIDE_PLACE_PLAIN is ignored here: the plain kernel
+ * exists for comparison with the single call only.
+ * Refused as a whole on the host, before the device is touched and with nothing written (SLIDE_ERR_INVALID): n_pairs < 0, n_maps < 0,
+ * a NULL that is needed (pairs, map_off, tf16n, inliers, found; maps7 when a map has rows), a negative or decreasing map_off, a pair
+ * naming a map outside [0, n_maps).  n_pairs == 0: SLIDE_OK without a device.  Otherwise SLIDE_OK (SLIDE_ERR_HIP: no usable device)
+ * and a pair's own outcome in status[k]: a pair stopped by min_num_map_objects_to_start, by an empty map or by an empty lattice has
+ * found[k] = 0 and status 0 (the first two never reach the device; an empty lattice leaves inliers[k] = -10000 as the single call
+ * does); a pair whose bucketed LDS image exceeds the single call's 150 KiB rule has SLIDE_ERR_CAPACITY, found[k] = 0 and
+ * inliers[k] = 0, and its neighbours are unaffected. */
+int slide_find_inter_loop_closures(const double* maps7, const int32_t* map_off, int n_maps, const int32_t* pairs, int n_pairs,
+                                   const slide_place_params_t* p, double* tf16n, int32_t* inliers, double* xyzyaw4n, int32_t* found,
+                                   int64_t* best_index, int64_t* n_candidates, int32_t* status);
 
 /* PlaceRecognition::findIntraLoopClosure :389-496 (same-robot loop closure: the object detections around the query key pose against
  * the submap around an older candidate key pose).  meas7: detections in the query pose's LOCAL frame, submap7: map objects in the
@@ -593,7 +617,7 @@ void slide_clipper_last_solve_info(int* n_workgroups, double* grad_evals);
  * spent in its kernels — HIP events on the launch stream right around the launches; uploads, host prefix sums and read-backs excluded —
  * and the work those kernels were given. */
 enum {
-  SLIDE_MS_PLACE_SWEEP = 0,       /* ms: k_place_sweep + k_place_argmax of the last slide_match_maps / loop-closure search */
+  SLIDE_MS_PLACE_SWEEP = 0,       /* ms: k_place_sweep + k_place_argmax of the last slide_match_maps / loop-closure search (a list: the whole list) */
   SLIDE_MS_TRI_MATCH = 1,         /* ms: k_tri_prepare x 2 + k_tri_match count and emit passes */
   SLIDE_MS_CLQ_CSR = 2,           /* ms: k_clq_csr count + fill (CSR of the affinity matrix from its dense upper triangle) */
   SLIDE_MS_CLQ_SOLVE = 3,         /* ms: the projected-gradient solve (k_clq_solve or k_clq_solve_coop) */

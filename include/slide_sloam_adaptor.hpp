@@ -434,8 +434,56 @@ struct Mat4 {
 class PlaceRecognition {
  public:
   slide_slidegraph_params_t slidegraph;      // place_recognition.cpp:65-75: sigma, epsilon, num_inliners_threshold, descriptor_matching_threshold, min_num_map_objects_to_start
+  slide_place_params_t place;                // place_recognition.cpp:24-78: the SlideMatch parameters (slide_place_default_params)
   explicit PlaceRecognition(const slide_slidegraph_params_t* p = nullptr) {
     if (p) slidegraph = *p; else slide_slidegraph_default_params(&slidegraph);
+    slide_place_default_params(&place);
+  }
+
+  // PlaceRecognition::findInterLoopClosure place_recognition.cpp:498-538 (SlideMatch, the branch interLoopClosureThread_ takes when
+  // use_slidematch_ is set): centring, the lattice sweep, the inlier gate and the refinement happen inside the library;
+  // tfFromQueryToRef is the identity when nothing is found.
+  template <class Objects, class M4>
+  bool findInterLoopClosure(const Objects& reference_objects, const Objects& query_objects, M4& tfFromQueryToRef) const {
+    std::vector<double> ref, qry;
+    flatten(reference_objects, ref);
+    flatten(query_objects, qry);
+    double tf[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int inliers = 0;
+    const int rc = slide_find_inter_loop_closure(ref.data(), (int)(ref.size() / 7), qry.data(), (int)(qry.size() / 7), &place, tf, &inliers, nullptr);
+    if (rc < 0) detail::check(rc, "findInterLoopClosure");
+    assign(tfFromQueryToRef, tf);
+    return rc == 1;
+  }
+
+  // The SlideMatch loop of SLOAMNode::interLoopClosureThread_ (sloamNode.cpp:600-694) as one call, the reference map as map 0:
+  // tfs[k] / found[k] are what findInterLoopClosure(reference_objects, query_maps[k], ...) gives, bit for bit.
+  template <class Objects, class M4>
+  void findInterLoopClosures(const Objects& reference_objects, const std::vector<Objects>& query_maps, std::vector<M4>& tfs,
+                             std::vector<bool>& found) const {
+    const int n = (int)query_maps.size();
+    std::vector<double> flat;
+    std::vector<int32_t> off(1, 0), pairs;
+    flatten(reference_objects, flat);
+    off.push_back((int32_t)(flat.size() / 7));
+    for (int k = 0; k < n; ++k) {
+      flatten(query_maps[k], flat);
+      off.push_back((int32_t)(flat.size() / 7));
+      pairs.push_back(0);
+      pairs.push_back(k + 1);
+    }
+    std::vector<double> tf(16 * (size_t)n + 1);
+    std::vector<int32_t> inl(n + 1), f(n + 1), status(n + 1);
+    detail::check(slide_find_inter_loop_closures(flat.data(), off.data(), n + 1, pairs.data(), n, &place, tf.data(), inl.data(), nullptr, f.data(),
+                                                 nullptr, nullptr, status.data()),
+                  "findInterLoopClosures");
+    tfs.resize(n);
+    found.assign(n, false);
+    for (int k = 0; k < n; ++k) {
+      if (status[k] < 0) throw Error(status[k], "findInterLoopClosures: query map " + std::to_string(k) + ": the two maps exceed the sweep's on-chip image");
+      assign(tfs[k], tf.data() + 16 * (size_t)k);
+      found[k] = f[k] != 0;
+    }
   }
 
   template <class Objects, class M4>

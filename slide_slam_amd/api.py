@@ -34,7 +34,8 @@ EXPORTS = [
     "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
-    "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_intra_loop_closure",
+    "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_inter_loop_closures",
+    "slide_find_intra_loop_closure",
     "slide_loop_candidate_idx", "slide_clipper_affinity", "slide_clipper_affinity_csr", "slide_clipper_dense_clique_csr", "slide_clipper_match",
     "slide_closest_stamp", "slide_clipper_default_params", "slide_clipper_dense_clique", "slide_match_triangles",
     "slide_estimate_tf2d", "slide_semantic_clipper", "slide_find_relative_meas_match", "slide_delaunay_2d", "slide_run_semantic_clipper",
@@ -856,6 +857,30 @@ def find_inter_loop_closure(ref7, qry7, params: PlaceParams):
     if rc < 0:
         _check(rc)
     return dict(found=bool(rc), tf=tf.reshape(4, 4), inliers=inl.value, xyzyaw=xyzyaw)
+
+
+def find_inter_loop_closures(maps, pairs, params: PlaceParams):
+    """The SlideMatch branch of SLOAMNode::interLoopClosureThread_ (sloamNode.cpp:600-694) in one call: maps = list of (n_i, 7) object
+    maps, pairs = list of (reference map, query map) indices.  Every pair is evaluated by itself and gets exactly
+    find_inter_loop_closure's result for that pair alone (tf = identity when it is not found).  Returns one dict per pair with the
+    single call's keys plus `status` (0 or the pair's own SLIDE_ERR_CAPACITY), `best_index` (the winning candidate in lattice order, -1
+    for none) and `candidates` (the pair's lattice size)."""
+    ms = [_d(m).reshape(-1, 7) for m in maps]
+    off = np.zeros(len(ms) + 1, np.int32)
+    off[1:] = np.cumsum([len(m) for m in ms])
+    flat = np.ascontiguousarray(np.concatenate(ms, axis=0)) if ms else np.zeros((0, 7))
+    if len(flat) == 0:
+        flat = np.zeros((1, 7))
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n = len(pr)
+    tf = np.zeros((max(n, 1), 16))
+    xyzyaw = np.zeros((max(n, 1), 4))
+    inl, found, status = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+    best, cand = np.full(max(n, 1), -1, np.int64), np.zeros(max(n, 1), np.int64)
+    _check(lib().slide_find_inter_loop_closures(_p(flat), _p(off), C.c_int(len(ms)), _p(pr if n else np.zeros((1, 2), np.int32)), C.c_int(n),
+                                                C.byref(params), _p(tf), _p(inl), _p(xyzyaw), _p(found), _p(best), _p(cand), _p(status)))
+    return [dict(found=bool(found[k]), tf=tf[k].reshape(4, 4).copy(), inliers=int(inl[k]), xyzyaw=xyzyaw[k].copy(), status=int(status[k]),
+                 best_index=int(best[k]), candidates=int(cand[k])) for k in range(n)]
 
 
 def find_intra_loop_closure(meas7, submap7, query_pose7, candidate_pose7, params: PlaceParams, x_half=5.0, y_half=5.0,

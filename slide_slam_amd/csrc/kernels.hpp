@@ -231,6 +231,14 @@ struct PlaceDev {
   double v_crit;           // smallest double whose correctly rounded square root is >= thr_pos: sqrt(v) < thr_pos <=> v < v_crit
 };
 void launch_place_sweep(const PlaceDev& P, hipStream_t s);
+// A list of map pairs in one launch (slide_find_inter_loop_closures): one PlaceDev per live pair (ref7 / qry7 / inliers unused), a
+// workgroup table {pair, rank within the pair, workgroups of the pair}, one partial (first index of the best count) per workgroup and
+// one winner per pair; wg0[0 .. n_seg]: first workgroup of every pair.  lds_bytes: the largest pair's image (place_lds_bytes).
+struct PlaceWg { int pair, rank, n, pad; };
+struct PlaceBest { long long idx; int val, pad; };
+size_t place_lds_bytes(int nr, int nq, int ignore_dim);
+void launch_place_sweep_seg(const PlaceDev* segs, const PlaceWg* wgs, int n_wg, size_t lds_bytes, PlaceBest* part, const int* wg0, int n_seg,
+                            PlaceBest* best, hipStream_t s);
 void launch_place_argmax(const int32_t* inliers, long long n, long long* best_idx, int32_t* best_val, hipStream_t s);
 void launch_tri_prepare(const double* tri, int n, double* sdist, double* sxy, hipStream_t s);
 void launch_tri_match(bool emit, const double* dm, const double* xm, int ntm, const double* dd, const double* xd, int ntd, double thr,

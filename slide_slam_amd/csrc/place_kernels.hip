@@ -71,8 +71,10 @@ __global__ __launch_bounds__(256) void k_place_sweep(PlaceDev P, const double* _
 // sqrt(dx^2 + dy^2) < t as dx^2 + dy^2 < v_crit with v_crit = the smallest double whose correctly rounded root is >= t (the same
 // decision bit for bit: sqrt is monotone and correctly rounded on both sides) — the f64 square root was most of a pair test's cost.
 // Query objects live in LDS too (lane-contiguous), every candidate re-uses them.
-__global__ __launch_bounds__(256) void k_place_sweep_b(PlaceDev P, const double* __restrict__ cosv, const double* __restrict__ sinv) {
-  extern __shared__ __align__(16) double lds[];
+// The bucketed LDS image of one pair of maps and the count of ONE candidate on it: THE one text k_place_sweep_b and k_place_sweep_seg
+// evaluate (this source is compiled with -ffp-contract=off, and the count is an integer: the same value in both).
+struct PlaceLds { const double* rxy; const double* rdim; const double* qxy; const double* qdim; const int* qrange; };
+__device__ __forceinline__ PlaceLds place_stage_b(const PlaceDev& P, double* lds) {
   double* rxy = lds;                                   // 2 nr
   double* rdim = rxy + 2 * (size_t)P.nr;               // 3 nr (only when !ignore_dim)
   double* qxy = rdim + (P.ignore_dim ? 0 : 3 * (size_t)P.nr);      // 2 nq
@@ -85,6 +87,77 @@ __global__ __launch_bounds__(256) void k_place_sweep_b(PlaceDev P, const double*
     for (int e = threadIdx.x; e < 3 * P.nq; e += blockDim.x) qdim[e] = P.qdim[e];
   }
   __syncthreads();
+  return PlaceLds{rxy, rdim, qxy, qdim, qrange};
+}
+// inliers of the candidate (x, y, c = cos yaw, s = sin yaw), summed over the wavefront: every lane returns the count
+__device__ __forceinline__ int place_count_b(const PlaceLds& L, int nq, double x, double y, double c, double s, double v_crit, double thr_dim,
+                                             bool use_dim, int lane) {
+  const double* rxy = L.rxy; const double* rdim = L.rdim; const double* qxy = L.qxy; const double* qdim = L.qdim; const int* qrange = L.qrange;
+  int inl = 0;
+  for (int j0 = 0; j0 < nq; j0 += 64) {
+    const int j = j0 + lane;
+    const bool active = j < nq;
+    double tx = 0.0, ty = 0.0, q4 = 0.0, q5 = 0.0, q6 = 0.0;
+    int lo = 0, hi = 0;
+    if (active) {
+      const double q1 = qxy[2 * j], q2 = qxy[2 * j + 1];
+      tx = c * q1 + (-s) * q2 + x * 1.0;
+      ty = s * q1 + c * q2 + y * 1.0;
+      const double tw = 0.0 * q1 + 0.0 * q2 + 1.0 * 1.0;
+      tx = tx / tw; ty = ty / tw;
+      lo = qrange[2 * j]; hi = qrange[2 * j + 1];
+      if (use_dim) { q4 = qdim[3 * j]; q5 = qdim[3 * j + 1]; q6 = qdim[3 * j + 2]; }
+    }
+    bool hit = false;
+    unsigned long long todo = __ballot(active && hi > lo);
+    while (todo) {      // one bucket per chunk (the query objects are sorted by label), two or three where labels meet
+      const int first = __ffsll((long long)todo) - 1;
+      const int blo = __shfl(lo, first), bhi = __shfl(hi, first);
+      const bool mine = active && lo == blo && hi == bhi;
+      bool open_ = mine;                                  // still looking for its first hit
+      int k = blo;
+      if (!use_dim) {
+        // four reference objects per round: whether a query object has A hit does not depend on the order inside the bucket, and
+        // four independent distance tests hide each other's latencies (one test is a chain of five dependent f64 operations
+        // behind an LDS read: 128 cycles per object and wavefront when taken one by one)
+        for (; k + 4 <= bhi; k += 4) {
+          if (((k - blo) & 15) == 0 && __ballot(open_) == 0) { k = bhi; break; }
+          const double x0 = rxy[2 * k] - tx, y0 = rxy[2 * k + 1] - ty, x1 = rxy[2 * k + 2] - tx, y1 = rxy[2 * k + 3] - ty;
+          const double x2 = rxy[2 * k + 4] - tx, y2 = rxy[2 * k + 5] - ty, x3 = rxy[2 * k + 6] - tx, y3 = rxy[2 * k + 7] - ty;
+          const bool ok = (x0 * x0 + y0 * y0 < v_crit) | (x1 * x1 + y1 * y1 < v_crit) | (x2 * x2 + y2 * y2 < v_crit) | (x3 * x3 + y3 * y3 < v_crit);
+          if (open_ && ok) { hit = true; open_ = false; }
+        }
+      }
+      for (; k < bhi; ++k) {
+        if (((k - blo) & 15) == 0 && __ballot(open_) == 0) break;
+        const double xd = rxy[2 * k] - tx, yd = rxy[2 * k + 1] - ty;
+        bool ok = xd * xd + yd * yd < v_crit;
+        if (use_dim) {
+          const double m3 = rdim[3 * k], m4 = rdim[3 * k + 1], m5 = rdim[3 * k + 2];
+          double avg = 0;
+          if (m4 == 0 && m5 == 0) {
+            avg = fabs(m3 - q4);
+          } else {
+            avg += fabs(m3 - q4);
+            avg += fabs(m4 - q5);
+            avg += fabs(m5 - q6);
+            avg /= 3;
+          }
+          ok = ok && (avg < thr_dim);
+        }
+        if (open_ && ok) { hit = true; open_ = false; }
+      }
+      todo &= ~__ballot(mine);
+    }
+    inl += hit ? 1 : 0;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) inl += __shfl_xor(inl, off);
+  return inl;
+}
+__global__ __launch_bounds__(256) void k_place_sweep_b(PlaceDev P, const double* __restrict__ cosv, const double* __restrict__ sinv) {
+  extern __shared__ __align__(16) double lds[];
+  const PlaceLds L = place_stage_b(P, lds);
   const int lane = threadIdx.x & 63;
   const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
@@ -96,68 +169,76 @@ __global__ __launch_bounds__(256) void k_place_sweep_b(PlaceDev P, const double*
     const int iy = (int)(cand % P.n_yaw);
     const double x = P.xs[P.cell_x[cell]], y = P.ys[P.cell_y[cell]];
     const double c = cosv[iy], s = sinv[iy];
-    int inl = 0;
-    for (int j0 = 0; j0 < P.nq; j0 += 64) {
-      const int j = j0 + lane;
-      const bool active = j < P.nq;
-      double tx = 0.0, ty = 0.0, q4 = 0.0, q5 = 0.0, q6 = 0.0;
-      int lo = 0, hi = 0;
-      if (active) {
-        const double q1 = qxy[2 * j], q2 = qxy[2 * j + 1];
-        tx = c * q1 + (-s) * q2 + x * 1.0;
-        ty = s * q1 + c * q2 + y * 1.0;
-        const double tw = 0.0 * q1 + 0.0 * q2 + 1.0 * 1.0;
-        tx = tx / tw; ty = ty / tw;
-        lo = qrange[2 * j]; hi = qrange[2 * j + 1];
-        if (use_dim) { q4 = qdim[3 * j]; q5 = qdim[3 * j + 1]; q6 = qdim[3 * j + 2]; }
-      }
-      bool hit = false;
-      unsigned long long todo = __ballot(active && hi > lo);
-      while (todo) {      // one bucket per chunk (the query objects are sorted by label), two or three where labels meet
-        const int first = __ffsll((long long)todo) - 1;
-        const int blo = __shfl(lo, first), bhi = __shfl(hi, first);
-        const bool mine = active && lo == blo && hi == bhi;
-        bool open_ = mine;                                  // still looking for its first hit
-        int k = blo;
-        if (!use_dim) {
-          // four reference objects per round: whether a query object has A hit does not depend on the order inside the bucket, and
-          // four independent distance tests hide each other's latencies (one test is a chain of five dependent f64 operations
-          // behind an LDS read: 128 cycles per object and wavefront when taken one by one)
-          for (; k + 4 <= bhi; k += 4) {
-            if (((k - blo) & 15) == 0 && __ballot(open_) == 0) { k = bhi; break; }
-            const double x0 = rxy[2 * k] - tx, y0 = rxy[2 * k + 1] - ty, x1 = rxy[2 * k + 2] - tx, y1 = rxy[2 * k + 3] - ty;
-            const double x2 = rxy[2 * k + 4] - tx, y2 = rxy[2 * k + 5] - ty, x3 = rxy[2 * k + 6] - tx, y3 = rxy[2 * k + 7] - ty;
-            const bool ok = (x0 * x0 + y0 * y0 < v_crit) | (x1 * x1 + y1 * y1 < v_crit) | (x2 * x2 + y2 * y2 < v_crit) | (x3 * x3 + y3 * y3 < v_crit);
-            if (open_ && ok) { hit = true; open_ = false; }
-          }
-        }
-        for (; k < bhi; ++k) {
-          if (((k - blo) & 15) == 0 && __ballot(open_) == 0) break;
-          const double xd = rxy[2 * k] - tx, yd = rxy[2 * k + 1] - ty;
-          bool ok = xd * xd + yd * yd < v_crit;
-          if (use_dim) {
-            const double m3 = rdim[3 * k], m4 = rdim[3 * k + 1], m5 = rdim[3 * k + 2];
-            double avg = 0;
-            if (m4 == 0 && m5 == 0) {
-              avg = fabs(m3 - q4);
-            } else {
-              avg += fabs(m3 - q4);
-              avg += fabs(m4 - q5);
-              avg += fabs(m5 - q6);
-              avg /= 3;
-            }
-            ok = ok && (avg < thr_dim);
-          }
-          if (open_ && ok) { hit = true; open_ = false; }
-        }
-        todo &= ~__ballot(mine);
-      }
-      inl += hit ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) inl += __shfl_xor(inl, off);
+    const int inl = place_count_b(L, P.nq, x, y, c, s, v_crit, thr_dim, use_dim, lane);
     if (lane == 0) P.inliers[cand] = inl;
   }
+}
+
+// The sweep of a LIST of map pairs in one launch (slide_find_inter_loop_closures: the robot pairs of sloamNode.cpp:600-694).  segs: one
+// PlaceDev per live pair (bucketed tables and lattice in one arena); wgs: per workgroup {pair, rank within the pair, workgroups of the
+// pair}, built on the host with shares in proportion to candidates x distance tests.  A workgroup stages ITS pair's image and its four
+// waves stride that pair's candidates in ascending order, so a candidate's count is k_place_sweep_b's for that pair alone.  No count is
+// stored per candidate: a wave keeps (best count, first index) with strict `>`, the workgroup reduces its four waves (the smaller index
+// wins on equal counts) and writes one partial.  The same FP64 VALU / LDS bound as k_place_sweep_b; the dynamic LDS is the largest live
+// pair's image, so an image above 80 KiB leaves one workgroup per CU.
+__global__ __launch_bounds__(256) void k_place_sweep_seg(const PlaceDev* __restrict__ segs, const PlaceWg* __restrict__ wgs,
+                                                         PlaceBest* __restrict__ part) {
+  extern __shared__ __align__(16) double lds[];
+  __shared__ long long widx[4];
+  __shared__ int wval[4];
+  const PlaceWg W = wgs[blockIdx.x];
+  const PlaceDev P = segs[W.pair];
+  const PlaceLds L = place_stage_b(P, lds);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long ncand = P.n_cells * P.n_yaw, nwaves = 4LL * W.n;
+  const double* cosv = P.yaws + P.n_yaw;
+  const double* sinv = P.yaws + 2 * (size_t)P.n_yaw;
+  const double v_crit = P.v_crit, thr_dim = P.thr_dim;
+  const bool use_dim = !P.ignore_dim;
+  int bv = INT32_MIN;
+  long long bi = -1;
+  for (long long cand = 4LL * W.rank + wv; cand < ncand; cand += nwaves) {
+    const long long cell = cand / P.n_yaw;
+    const int iy = (int)(cand % P.n_yaw);
+    const double x = P.xs[P.cell_x[cell]], y = P.ys[P.cell_y[cell]];
+    const double c = cosv[iy], s = sinv[iy];
+    const int inl = place_count_b(L, P.nq, x, y, c, s, v_crit, thr_dim, use_dim, lane);
+    if (inl > bv) { bv = inl; bi = cand; }
+  }
+  if (lane == 0) { wval[wv] = bv; widx[wv] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (widx[w] >= 0 && (wval[w] > bv || (wval[w] == bv && (bi < 0 || widx[w] < bi)))) { bv = wval[w]; bi = widx[w]; }
+    part[blockIdx.x] = PlaceBest{bi, bv, 0};
+  }
+}
+// per pair: its workgroups' partials [wg0[s], wg0[s + 1]) reduced by the same rule (larger count, then smaller index)
+__global__ __launch_bounds__(256) void k_place_best_seg(const PlaceBest* __restrict__ part, const int* __restrict__ wg0, PlaceBest* __restrict__ best) {
+  __shared__ long long sidx[256];
+  __shared__ int sval[256];
+  const int s = blockIdx.x;
+  int bv = INT32_MIN;
+  long long bi = -1;
+  for (int i = wg0[s] + (int)threadIdx.x; i < wg0[s + 1]; i += 256) {
+    const PlaceBest b = part[i];
+    if (b.idx >= 0 && (b.val > bv || (b.val == bv && (bi < 0 || b.idx < bi)))) { bv = b.val; bi = b.idx; }
+  }
+  sval[threadIdx.x] = bv;
+  sidx[threadIdx.x] = bi;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) {
+      const int ov = sval[threadIdx.x + st];
+      const long long oi = sidx[threadIdx.x + st];
+      if (oi >= 0 && (ov > sval[threadIdx.x] || (ov == sval[threadIdx.x] && (sidx[threadIdx.x] < 0 || oi < sidx[threadIdx.x])))) {
+        sval[threadIdx.x] = ov;
+        sidx[threadIdx.x] = oi;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) best[s] = PlaceBest{sidx[0], sval[0], 0};
 }
 
 // first index of the maximum (the reference keeps a candidate only when it has STRICTLY more inliers)
@@ -386,7 +467,7 @@ void launch_place_sweep(const PlaceDev& P, hipStream_t s) {
   if (P.rxy) {
     static const bool attr = (hipFuncSetAttribute(reinterpret_cast<const void*>(k_place_sweep_b), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), true);
     (void)attr;
-    const size_t lds = ((size_t)(P.ignore_dim ? 2 : 5) * (P.nr + P.nq)) * sizeof(double) + 2 * (size_t)P.nq * sizeof(int) + 16;
+    const size_t lds = place_lds_bytes(P.nr, P.nq, P.ignore_dim);
     hipLaunchKernelGGL(k_place_sweep_b, dim3((unsigned)blocks), dim3(256), lds, s, P, cosv, sinv);
     return;
   }
@@ -394,6 +475,17 @@ void launch_place_sweep(const PlaceDev& P, hipStream_t s) {
   static const bool attr_plain = (hipFuncSetAttribute(reinterpret_cast<const void*>(k_place_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), true);
   (void)attr_plain;
   hipLaunchKernelGGL(k_place_sweep, dim3((unsigned)blocks), dim3(256), (size_t)P.nr * 6 * sizeof(double), s, P, cosv, sinv);
+}
+size_t place_lds_bytes(int nr, int nq, int ignore_dim) {
+  return ((size_t)(ignore_dim ? 2 : 5) * ((size_t)nr + (size_t)nq)) * sizeof(double) + 2 * (size_t)nq * sizeof(int) + 16;
+}
+void launch_place_sweep_seg(const PlaceDev* segs, const PlaceWg* wgs, int n_wg, size_t lds_bytes, PlaceBest* part, const int* wg0, int n_seg,
+                            PlaceBest* best, hipStream_t s) {
+  if (n_wg <= 0 || n_seg <= 0) return;
+  static const bool attr = (hipFuncSetAttribute(reinterpret_cast<const void*>(k_place_sweep_seg), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), true);
+  (void)attr;
+  hipLaunchKernelGGL(k_place_sweep_seg, dim3((unsigned)n_wg), dim3(256), lds_bytes, s, segs, wgs, part);
+  hipLaunchKernelGGL(k_place_best_seg, dim3((unsigned)n_seg), dim3(256), 0, s, part, wg0, best);
 }
 void launch_place_argmax(const int32_t* inliers, long long n, long long* best_idx, int32_t* best_val, hipStream_t s) {
   hipLaunchKernelGGL(k_place_argmax, dim3(256), dim3(256), 0, s, inliers, n, best_idx, best_val);
