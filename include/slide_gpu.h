@@ -560,6 +560,57 @@ int slide_find_intra_loop_closure(const double* meas7, int nm, const double* sub
                                   const double candidate_pose7[7], const slide_place_params_t* p, double x_half_range_intra,
                                   double y_half_range_intra, double yaw_half_range_intra, double tf16[16], int* inliers,
                                   double xyzyaw[4]);
+/* getkeyPoseSubmap of the three map managers (cylinderMapManager.cpp:186-211, cubeMapManager.cpp:77-101,
+ * ellipsoidMapManager.cpp:82-107) followed by SLOAMNode::prepareLCInput (sloamNode.cpp:544-576), for n_poses key poses at once, on the
+ * device: the submap the intra matcher needs around each candidate key pose.  Map tables: cylinders (root, ray — not normalised —,
+ * radius, label), cubes and ellipsoids (centre, scale, label).  pose_xyz3n: 3 doubles per pose.  The rule is the reference's: the pose
+ * position goes through pcl's PointT, i.e. float32, p = (float)pose.translation(); a model is kept iff model.distance(p) <=
+ * submap_radius (inclusive) and |model_z - pose_z| < max_dz (strict) with the DOUBLE pose z.  distance: |centre - p| for cubes and
+ * ellipsoids (cube.cpp:26-29, ellipsoid.cpp:28-31); for cylinders the distance from p to the axis through root along ray, minus radius
+ * (cylinder.cpp:226-234), and model_z = root z.  max_dz: the reference hard-codes 1.5 (and says so in a TODO); pass 1.5 for its
+ * behaviour.  Rows of pose k: rows7 [sub_off[k], sub_off[k + 1]), kept cylinders in map order, then cubes, then ellipsoids; cylinder
+ * rows [label, root, radius, 0, 0], cube / ellipsoid rows [label, centre, scale].  src_idx (may be NULL): the row's index in the
+ * concatenated table (cylinders, cubes, ellipsoids).  Capacity protocol of slide_match_maps_sweep: *n_rows and sub_off (n_poses + 1)
+ * are always filled; SLIDE_ERR_CAPACITY when *n_rows > capacity, and no row is written then.  k_keypose_submap counts per (pose,
+ * 256-object chunk) with a 64-lane ballot per wave, k_seg_scan turns the counts into offsets, the emit pass repeats the test and
+ * writes each kept row at its offset plus its rank inside the wave: a stable compaction without atomics.  The tables go up once;
+ * three launches and two blocking read-backs (the totals, then the rows) per call whatever n_poses is.  SLIDE_ERR_INVALID: a negative
+ * count or capacity, a NULL that is needed. */
+int slide_keypose_submaps(const double* cyl_root3, const double* cyl_ray3, const double* cyl_radius, const int32_t* cyl_label, int n_cyl,
+                          const double* cube_xyz3, const double* cube_scale3, const int32_t* cube_label, int n_cube,
+                          const double* ell_xyz3, const double* ell_scale3, const int32_t* ell_label, int n_ell,
+                          const double* pose_xyz3n, int n_poses, double submap_radius, double max_dz,
+                          int32_t* sub_off /* n_poses + 1 */, double* rows7, int32_t* src_idx, int64_t capacity, int64_t* n_rows);
+/* PlaceRecognition::findIntraLoopClosure place_recognition.cpp:389-496 for a LIST of candidate key poses — the attempt of
+ * SLOAMNode::intraLoopClosureThread_ (sloamNode.cpp:355-486) over every candidate instead of the one getLoopCandidateIdx returns — as
+ * ONE call.  meas7: one set of detections in the query pose's local frame, moved into the map frame once; candidate k: submap rows
+ * [sub_off[k], sub_off[k + 1]) of submaps7 with pose candidate_pose7n + 7 k; all candidates share the one intra lattice.  The host path
+ * and the launches are those of slide_find_inter_loop_closures (one allocation, one upload, k_place_sweep_seg + k_place_best_seg, one
+ * read-back), each submap bucketed once and the query re-bucketed against each submap's labels.  Candidate k is evaluated by itself:
+ * found[k], inliers[k], xyzyaw4n + 4 k and tf16n + 16 k are bit for bit what slide_find_intra_loop_closure returns and writes for that
+ * candidate alone, whatever else is in the list and wherever it stands in it; a candidate that is not found has the identity in its
+ * tf16 and zeros in its xyzyaw.  best_index / n_candidates as in the inter list; they, xyzyaw4n and status may be NULL.
+ * nm == 0 or nm < 4 (:396-405): every candidate found = 0, inliers = 0, status 0, no device touched.  An empty lattice:
+ * inliers[k] = -10000 as the single call leaves it.  An empty submap: found = 0, status 0, never reaches the device.  A submap whose
+ * bucketed image with these detections exceeds the single call's 150 KiB rule: status[k] = SLIDE_ERR_CAPACITY, found = 0, inliers = 0,
+ * neighbours unaffected.  Refused as a whole (SLIDE_ERR_INVALID) before the device is touched and with nothing written: negative
+ * counts, a NULL that is needed (sub_off, candidate_pose7n, query_pose7, tf16n, inliers, found; meas7 when nm > 0; submaps7 when a
+ * submap has rows), a negative or decreasing sub_off.  n_cand == 0: SLIDE_OK without a device. */
+int slide_find_intra_loop_closures(const double* meas7, int nm, const double query_pose7[7], const double* submaps7, const int32_t* sub_off,
+                                   int n_cand, const double* candidate_pose7n, const slide_place_params_t* p, double x_half_range_intra,
+                                   double y_half_range_intra, double yaw_half_range_intra, double* tf16n, int32_t* inliers,
+                                   double* xyzyaw4n, int32_t* found, int64_t* best_index, int64_t* n_candidates, int32_t* status);
+/* One attempt of SLOAMNode::intraLoopClosureThread_ (sloamNode.cpp:355-486: getkeyPoseSubmap x 3, prepareLCInput :544-576,
+ * findIntraLoopClosure) over n_cand candidate key poses in one call: slide_keypose_submaps around the candidates' positions (the first
+ * three entries of each candidate_pose7n row), then slide_find_intra_loop_closures on what it produced.  Every output is bit for bit
+ * that of the two calls made one after the other; submap_sizes[k] (n_cand, needed) = the rows of candidate k's submap. */
+int slide_intra_loop_closure_attempt(const double* cyl_root3, const double* cyl_ray3, const double* cyl_radius, const int32_t* cyl_label, int n_cyl,
+                                     const double* cube_xyz3, const double* cube_scale3, const int32_t* cube_label, int n_cube,
+                                     const double* ell_xyz3, const double* ell_scale3, const int32_t* ell_label, int n_ell, const double* meas7,
+                                     int nm, const double query_pose7[7], const double* candidate_pose7n, int n_cand, double submap_radius,
+                                     double max_dz, const slide_place_params_t* p, double x_half_range_intra, double y_half_range_intra,
+                                     double yaw_half_range_intra, double* tf16n, int32_t* inliers, double* xyzyaw4n, int32_t* found,
+                                     int64_t* best_index, int64_t* n_candidates, int32_t* status, int32_t* submap_sizes);
 
 /* CLIPPER pairwise-consistency affinity (clipper_semantic_object/src/clipper.cpp:21-65 with the
  * EuclideanDistance invariant src/invariants/euclidean_distance.cpp:13-31).  D1: n1 points of `dim`
@@ -676,6 +727,11 @@ int slide_in_loop_closure_region(const float* cloud_xyz, int n, const double pos
  * Host bookkeeping. */
 int slide_loop_candidate_idx(const float* cloud_xyz, int n, double max_dist, uint64_t pose_idx, uint64_t at_least_num_of_poses_old,
                              uint64_t* candidate_idx, int* found);
+/* The same test (cylinderMapManager.cpp:160-184) for EVERY key pose that passes it, not only the first FLANN returns: cand_idx in
+ * slide_loop_candidate_idx's order (float32 squared distance ascending, then index), so entry 0 is exactly that function's result.
+ * *n_found is the full count even when it exceeds cap; at most cap entries are written.  Host bookkeeping. */
+int slide_loop_candidate_list(const float* cloud_xyz, int n, double max_dist, uint64_t pose_idx, uint64_t at_least_num_of_poses_old,
+                              uint64_t* cand_idx, int cap, int* n_found);
 
 /* 2-D Delaunay triangulation (replaces the qhull call of DelaunayTriangulation::Observation, triangulation/observation.cpp:13-88,
  * options "Qt Qbb Qc Qz Q12 d").  Host code (sweep-hull + Lawson flips, long double predicates).  tri_out: vertex-index triples,

@@ -486,6 +486,60 @@ class PlaceRecognition {
     }
   }
 
+  // PlaceRecognition::findIntraLoopClosure place_recognition.cpp:389-496 with the reference's argument list (place_recognition.h:88-91;
+  // the caller has inter_loop_closure == false): reference_objects = the submap around the candidate key pose (map frame),
+  // query_objects = the detections in the query pose's local frame.  The intra window is the three rosparams of :53-63 (yaw in
+  // radians here).  tfFromQueryToCandidate is left alone when nothing is found, as in the reference.
+  double match_x_half_range_intra = 5.0, match_y_half_range_intra = 5.0, match_yaw_half_range_intra = 10.0 * 3.14159265358979323846 / 180.0;
+  template <class Objects, class SE3, class M4>
+  bool findIntraLoopClosure(const Objects& reference_objects, const Objects& query_objects, const SE3& query_pose, const SE3& reference_pose,
+                            M4& tfFromQueryToCandidate) const {
+    std::vector<double> sub, meas;
+    flatten(reference_objects, sub);
+    flatten(query_objects, meas);
+    double q7[7], c7[7], tf[16];
+    detail::to7(query_pose, q7);
+    detail::to7(reference_pose, c7);
+    int inliers = 0;
+    const int rc = slide_find_intra_loop_closure(meas.data(), (int)(meas.size() / 7), sub.data(), (int)(sub.size() / 7), q7, c7, &place,
+                                                 match_x_half_range_intra, match_y_half_range_intra, match_yaw_half_range_intra, tf, &inliers, nullptr);
+    if (rc < 0) detail::check(rc, "findIntraLoopClosure");
+    if (rc == 1) assign(tfFromQueryToCandidate, tf);
+    return rc == 1;
+  }
+  // One attempt of SLOAMNode::intraLoopClosureThread_ (sloamNode.cpp:355-486) over a LIST of candidate key poses in one call:
+  // tfs[k] / found[k] are what findIntraLoopClosure(submaps[k], query_objects, query_pose, reference_poses[k], ...) gives, bit for
+  // bit; tfs[k] is the identity when candidate k is not found.
+  template <class Objects, class SE3, class M4>
+  void findIntraLoopClosures(const std::vector<Objects>& submaps, const Objects& query_objects, const SE3& query_pose,
+                             const std::vector<SE3>& reference_poses, std::vector<M4>& tfs, std::vector<bool>& found) const {
+    const int n = (int)submaps.size();
+    if (reference_poses.size() != submaps.size()) throw Error(SLIDE_ERR_INVALID, "findIntraLoopClosures: one reference pose per submap");
+    std::vector<double> flat, meas, c7(7 * (size_t)n + 1);
+    std::vector<int32_t> off(1, 0);
+    flatten(query_objects, meas);
+    for (int k = 0; k < n; ++k) {
+      flatten(submaps[k], flat);
+      off.push_back((int32_t)(flat.size() / 7));
+      detail::to7(reference_poses[k], c7.data() + 7 * (size_t)k);
+    }
+    double q7[7];
+    detail::to7(query_pose, q7);
+    std::vector<double> tf(16 * (size_t)n + 1);
+    std::vector<int32_t> inl(n + 1), f(n + 1), status(n + 1);
+    detail::check(slide_find_intra_loop_closures(meas.data(), (int)(meas.size() / 7), q7, flat.data(), off.data(), n, c7.data(), &place,
+                                                 match_x_half_range_intra, match_y_half_range_intra, match_yaw_half_range_intra, tf.data(),
+                                                 inl.data(), nullptr, f.data(), nullptr, nullptr, status.data()),
+                  "findIntraLoopClosures");
+    tfs.resize(n);
+    found.assign(n, false);
+    for (int k = 0; k < n; ++k) {
+      if (status[k] < 0) throw Error(status[k], "findIntraLoopClosures: candidate " + std::to_string(k) + ": the submap and the detections exceed the sweep's on-chip image");
+      assign(tfs[k], tf.data() + 16 * (size_t)k);
+      found[k] = f[k] != 0;
+    }
+  }
+
   template <class Objects, class M4>
   bool findInterLoopClosureWithClipper(const Objects& reference_objects, const Objects& query_objects, M4& tfFromQueryToRef) const {
     std::vector<double> ref, qry;
@@ -542,6 +596,58 @@ class PlaceRecognition {
       for (int c = 0; c < 4; ++c) dst(r, c) = tf[4 * r + c];
   }
 };
+
+// getkeyPoseSubmap of the three map managers (cylinderMapManager.cpp:186-211, cubeMapManager.cpp:77-101, ellipsoidMapManager.cpp:82-107)
+// followed by SLOAMNode::prepareLCInput (sloamNode.cpp:544-576) around a list of key poses, on the device (slide_keypose_submaps):
+// submaps[k] = the Vector7d rows the intra matcher takes for key pose k.  Objects as the reference has them: cylinder.model.{root,
+// ray, radius, semantic_label}, cube / ellipsoid .model.{pose, scale, semantic_label}.  max_dz: the reference hard-codes 1.5.
+template <class Cylinders, class Cubes, class Ellipsoids, class SE3>
+std::vector<std::vector<std::array<double, 7>>> getkeyPoseSubmaps(const Cylinders& cylinders, const Cubes& cubes, const Ellipsoids& ellipsoids,
+                                                                  const std::vector<SE3>& poses, double submap_radius, double max_dz = 1.5) {
+  std::vector<double> cr, ca, crad, bx, bs, ex, es, px;
+  std::vector<int32_t> cl, bl, el;
+  for (const auto& c : cylinders) {
+    for (int k = 0; k < 3; ++k) { cr.push_back(c.model.root[k]); ca.push_back(c.model.ray[k]); }
+    crad.push_back(c.model.radius);
+    cl.push_back((int32_t)c.model.semantic_label);
+  }
+  for (const auto& c : cubes) {
+    const auto t = c.model.pose.translation();
+    for (int k = 0; k < 3; ++k) { bx.push_back(t[k]); bs.push_back(c.model.scale[k]); }
+    bl.push_back((int32_t)c.model.semantic_label);
+  }
+  for (const auto& c : ellipsoids) {
+    const auto t = c.model.pose.translation();
+    for (int k = 0; k < 3; ++k) { ex.push_back(t[k]); es.push_back(c.model.scale[k]); }
+    el.push_back((int32_t)c.model.semantic_label);
+  }
+  for (const auto& p : poses) {
+    const auto t = p.translation();
+    for (int k = 0; k < 3; ++k) px.push_back(t[k]);
+  }
+  const int n = (int)poses.size();
+  std::vector<int32_t> off((size_t)n + 1, 0);
+  std::vector<double> rows;
+  int64_t n_rows = 0;
+  auto call = [&](int64_t cap) {
+    return slide_keypose_submaps(cr.data(), ca.data(), crad.data(), cl.data(), (int)cl.size(), bx.data(), bs.data(), bl.data(), (int)bl.size(), ex.data(),
+                                 es.data(), el.data(), (int)el.size(), px.data(), n, submap_radius, max_dz, off.data(), rows.data(), nullptr, cap, &n_rows);
+  };
+  int rc = call(0);                                   // sizes only
+  if (rc == SLIDE_ERR_CAPACITY && n_rows > 0) {
+    rows.resize(7 * (size_t)n_rows);
+    rc = call(n_rows);
+  }
+  detail::check(rc, "getkeyPoseSubmaps");
+  std::vector<std::vector<std::array<double, 7>>> out((size_t)n);
+  for (int k = 0; k < n; ++k)
+    for (int32_t r = off[k]; r < off[k + 1]; ++r) {
+      std::array<double, 7> row;
+      for (int c = 0; c < 7; ++c) row[c] = rows[7 * (size_t)r + c];
+      out[k].push_back(row);
+    }
+  return out;
+}
 
 }  // namespace slide
 #endif  // SLIDE_SLOAM_ADAPTOR_HPP_

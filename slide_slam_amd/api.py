@@ -35,8 +35,8 @@ EXPORTS = [
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
     "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_inter_loop_closures",
-    "slide_find_intra_loop_closure",
-    "slide_loop_candidate_idx", "slide_clipper_affinity", "slide_clipper_affinity_csr", "slide_clipper_dense_clique_csr", "slide_clipper_match",
+    "slide_find_intra_loop_closure", "slide_keypose_submaps", "slide_find_intra_loop_closures", "slide_intra_loop_closure_attempt",
+    "slide_loop_candidate_idx", "slide_loop_candidate_list", "slide_clipper_affinity", "slide_clipper_affinity_csr", "slide_clipper_dense_clique_csr", "slide_clipper_match",
     "slide_closest_stamp", "slide_clipper_default_params", "slide_clipper_dense_clique", "slide_match_triangles",
     "slide_estimate_tf2d", "slide_semantic_clipper", "slide_find_relative_meas_match", "slide_delaunay_2d", "slide_run_semantic_clipper",
     "slide_pick_next_measurement", "slide_in_loop_closure_region",
@@ -905,6 +905,114 @@ def loop_candidate_idx(cloud_xyz, max_dist, pose_idx, at_least_num_of_poses_old)
     _check(lib().slide_loop_candidate_idx(_p(cloud), C.c_int(len(cloud)), C.c_double(max_dist), C.c_uint64(pose_idx),
                                           C.c_uint64(at_least_num_of_poses_old), C.byref(cand), C.byref(found)))
     return int(cand.value) if found.value else None
+
+
+def loop_candidate_list(cloud_xyz, max_dist, pose_idx, at_least_num_of_poses_old, cap=None):
+    """slide_loop_candidate_list: EVERY key pose that passes getLoopCandidateIdx's test, in loop_candidate_idx's order (entry 0 is its
+    result).  Returns (indices as an int64 array of at most `cap` entries — all of them when cap is None —, the full count)."""
+    cloud = np.ascontiguousarray(cloud_xyz, dtype=np.float32).reshape(-1, 3)
+    size = len(cloud) if cap is None else int(cap)
+    out, n = np.zeros(max(size, 1), np.uint64), C.c_int(0)
+    _check(lib().slide_loop_candidate_list(_p(cloud), C.c_int(len(cloud)), C.c_double(max_dist), C.c_uint64(pose_idx),
+                                           C.c_uint64(at_least_num_of_poses_old), _p(out), C.c_int(size), C.byref(n)))
+    return out[:min(n.value, size)].astype(np.int64), int(n.value)
+
+
+def _map_tables(cylinders, cubes, ellipsoids):
+    """The three map tables as the C arguments of slide_keypose_submaps.  cylinders: (root (n, 3), ray (n, 3), radius (n,), label (n,)),
+    cubes / ellipsoids: (centre (n, 3), scale (n, 3), label (n,)); None: an empty class."""
+    keep, args = [], []
+    for cls, widths in ((cylinders, (3, 3, 1)), (cubes, (3, 3)), (ellipsoids, (3, 3))):
+        if cls is None:
+            cls = [np.zeros((0, w)) for w in widths] + [np.zeros(0, np.int32)]
+        arrs = [_d(a).reshape(-1, w) if w > 1 else _d(a).reshape(-1) for a, w in zip(cls[:-1], widths)] + [_i(cls[-1]).reshape(-1)]
+        n = len(arrs[-1])
+        assert all(len(a) == n for a in arrs), "a map table's columns differ in length"
+        keep += arrs
+        args += [_p(a) if n else None for a in arrs] + [C.c_int(n)]
+    return keep, args
+
+
+def keypose_submaps(cylinders, cubes, ellipsoids, pose_xyz, submap_radius, max_dz=1.5, capacity=None, with_src=True):
+    """slide_keypose_submaps: getkeyPoseSubmap of the three map managers + prepareLCInput around a list of key-pose positions, on the
+    device.  Returns dict(status, n_rows, sub_off (n_poses + 1), rows (n_rows, 7), src_idx (n_rows,)); status SLIDE_ERR_CAPACITY
+    (n_rows and sub_off still filled, no rows) when `capacity` is too small.  capacity=None: sized by a first call that writes
+    nothing.  max_dz: the reference hard-codes 1.5."""
+    keep, targs = _map_tables(cylinders, cubes, ellipsoids)
+    pos = _d(pose_xyz).reshape(-1, 3)
+    n = len(pos)
+    off, nr = np.zeros(n + 1, np.int32), C.c_int64(0)
+
+    def call(cap):
+        rows, src = np.zeros((max(cap, 1), 7)), np.full(max(cap, 1), -1, np.int32)
+        rc = lib().slide_keypose_submaps(*targs, _p(pos) if n else None, C.c_int(n), C.c_double(submap_radius), C.c_double(max_dz), _p(off),
+                                         _p(rows), _p(src) if with_src else None, C.c_int64(cap), C.byref(nr))
+        return rc, rows, src
+    if capacity is None:
+        rc, rows, src = call(0)
+        if rc == SLIDE_ERR_CAPACITY and nr.value > 0:
+            rc, rows, src = call(nr.value)
+    else:
+        rc, rows, src = call(int(capacity))
+    if rc not in (SLIDE_OK, SLIDE_ERR_CAPACITY):
+        _check(rc)
+    k = nr.value if rc == SLIDE_OK else 0
+    return dict(status=int(rc), n_rows=int(nr.value), sub_off=off, rows=rows[:k], src_idx=src[:k] if with_src else None)
+
+
+def _intra_outputs(n):
+    tf, xyzyaw = np.zeros((max(n, 1), 16)), np.zeros((max(n, 1), 4))
+    inl, found, status = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+    best, cand = np.full(max(n, 1), -1, np.int64), np.zeros(max(n, 1), np.int64)
+    return tf, inl, xyzyaw, found, best, cand, status
+
+
+def _intra_dicts(n, tf, inl, xyzyaw, found, best, cand, status):
+    return [dict(found=bool(found[k]), tf=tf[k].reshape(4, 4).copy(), inliers=int(inl[k]), xyzyaw=xyzyaw[k].copy(), status=int(status[k]),
+                 best_index=int(best[k]), candidates=int(cand[k])) for k in range(n)]
+
+
+def find_intra_loop_closures(meas7, query_pose7, submaps, candidate_poses7, params: PlaceParams, x_half=5.0, y_half=5.0,
+                             yaw_half=10.0 * np.pi / 180.0):
+    """slide_find_intra_loop_closures: one set of detections (local frame of the query pose) against a LIST of candidate key poses in
+    one call; submaps = list of (n_k, 7) submaps, candidate_poses7 = (n, 7).  Every candidate gets exactly find_intra_loop_closure's
+    result for that candidate alone (tf = identity when it is not found).  Returns one dict per candidate in the shape
+    find_inter_loop_closures returns."""
+    m = _d(meas7).reshape(-1, 7)
+    sm = [_d(x).reshape(-1, 7) for x in submaps]
+    n = len(sm)
+    cp = _d(candidate_poses7).reshape(-1, 7)
+    assert len(cp) == n, "one candidate pose per submap"
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in sm])
+    flat = np.ascontiguousarray(np.concatenate(sm, axis=0)) if sm else np.zeros((0, 7))
+    if len(flat) == 0:
+        flat = np.zeros((1, 7))
+    out = _intra_outputs(n)
+    _check(lib().slide_find_intra_loop_closures(_p(m) if len(m) else None, C.c_int(len(m)), _p(_d(query_pose7)), _p(flat), _p(off), C.c_int(n),
+                                                _p(cp if n else np.zeros((1, 7))), C.byref(params), C.c_double(x_half), C.c_double(y_half),
+                                                C.c_double(yaw_half), *[_p(a) for a in out]))
+    return _intra_dicts(n, *out)
+
+
+def intra_loop_closure_attempt(cylinders, cubes, ellipsoids, meas7, query_pose7, candidate_poses7, submap_radius, params: PlaceParams,
+                               max_dz=1.5, x_half=5.0, y_half=5.0, yaw_half=10.0 * np.pi / 180.0):
+    """slide_intra_loop_closure_attempt: keypose_submaps around the candidates' positions followed by find_intra_loop_closures on what
+    it produced, in one call.  Returns find_intra_loop_closures' dicts, each with `submap_size` added."""
+    keep, targs = _map_tables(cylinders, cubes, ellipsoids)
+    m = _d(meas7).reshape(-1, 7)
+    cp = _d(candidate_poses7).reshape(-1, 7)
+    n = len(cp)
+    out = _intra_outputs(n)
+    sizes = np.zeros(max(n, 1), np.int32)
+    _check(lib().slide_intra_loop_closure_attempt(*targs, _p(m) if len(m) else None, C.c_int(len(m)), _p(_d(query_pose7)),
+                                                  _p(cp if n else np.zeros((1, 7))), C.c_int(n), C.c_double(submap_radius), C.c_double(max_dz),
+                                                  C.byref(params), C.c_double(x_half), C.c_double(y_half), C.c_double(yaw_half),
+                                                  *[_p(a) for a in out], _p(sizes)))
+    res = _intra_dicts(n, *out)
+    for k, r in enumerate(res):
+        r["submap_size"] = int(sizes[k])
+    return res
 
 
 def clipper_affinity(D1, D2, A, sigma=0.01, epsilon=0.06, mindist=0.0, affinityeps=1e-4):

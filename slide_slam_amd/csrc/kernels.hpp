@@ -239,6 +239,18 @@ struct PlaceBest { long long idx; int val, pad; };
 size_t place_lds_bytes(int nr, int nq, int ignore_dim);
 void launch_place_sweep_seg(const PlaceDev* segs, const PlaceWg* wgs, int n_wg, size_t lds_bytes, PlaceBest* part, const int* wg0, int n_seg,
                             PlaceBest* best, hipStream_t s);
+// Submaps around a list of key poses (slide_keypose_submaps): the three map tables, the poses (xyz at pose_xyz + pose_stride * k:
+// stride 3 for a position list, 7 for a pose list) and the two thresholds.  blockIdx.x = pose * n_chunk + chunk of 256 objects of the
+// concatenated table; count pass: cnt per workgroup; emit pass: rows at base[pose] + chunkoff[workgroup] + rank (src_idx may be null).
+struct SubmapDev {
+  const double* cyl_root; const double* cyl_ray; const double* cyl_radius; const int32_t* cyl_label; int n_cyl;
+  const double* cube_xyz; const double* cube_scale; const int32_t* cube_label; int n_cube;
+  const double* ell_xyz; const double* ell_scale; const int32_t* ell_label; int n_ell;
+  const double* pose_xyz; int pose_stride;
+  double radius, max_dz;
+};
+void launch_keypose_submap(bool emit, const SubmapDev& S, int n_poses, int n_chunk, int* cnt, const long long* chunkoff, const long long* base,
+                           double* rows7, int32_t* src_idx, hipStream_t s);
 void launch_place_argmax(const int32_t* inliers, long long n, long long* best_idx, int32_t* best_val, hipStream_t s);
 void launch_tri_prepare(const double* tri, int n, double* sdist, double* sxy, hipStream_t s);
 void launch_tri_match(bool emit, const double* dm, const double* xm, int ntm, const double* dd, const double* xd, int ntd, double thr,

@@ -432,6 +432,84 @@ __global__ __launch_bounds__(256) void k_seg_scan(const int* __restrict__ cnt, c
   }
 }
 
+// ---- Submaps around a list of key poses (getkeyPoseSubmap of the three map managers, then prepareLCInput) --------------------------
+// cylinderMapManager.cpp:186-211, cubeMapManager.cpp:77-101, ellipsoidMapManager.cpp:82-107, sloamNode.cpp:544-576.  THE one test the
+// count and the emit pass evaluate for object i of the concatenated table (cylinders, cubes, ellipsoids) and one key pose: the pose
+// goes through pcl's PointT, i.e. float32 (px, py, pz), the height test uses the double pose z; kept iff distance(p) <= radius
+// (inclusive) and |model z - pose z| < max_dz (strict).  Cubes and ellipsoids: |centre - p| (cube.cpp:26-29, ellipsoid.cpp:28-31);
+// cylinders: the distance from p to the axis through root along the un-normalised ray, minus the radius (cylinder.cpp:226-234), model
+// z = root z.  A NaN anywhere fails a comparison: dropped, as in the reference.
+__device__ __forceinline__ bool submap_keeps(const SubmapDev& S, int i, double px, double py, double pz, double pose_z) {
+  double d, mz;
+  if (i < S.n_cyl) {
+    const double* r = S.cyl_root + 3 * (size_t)i;
+    const double* a = S.cyl_ray + 3 * (size_t)i;
+    const double ex = px - r[0], ey = py - r[1], ez = pz - r[2];
+    const double t = (ex * a[0] + ey * a[1] + ez * a[2]) / (a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    const double qx = r[0] + t * a[0], qy = r[1] + t * a[1], qz = r[2] + t * a[2];
+    const double dx = px - qx, dy = py - qy, dz = pz - qz;
+    d = sqrt(dx * dx + dy * dy + dz * dz) - S.cyl_radius[i];
+    mz = r[2];
+  } else {
+    const double* c = i < S.n_cyl + S.n_cube ? S.cube_xyz + 3 * (size_t)(i - S.n_cyl) : S.ell_xyz + 3 * (size_t)(i - S.n_cyl - S.n_cube);
+    const double dx = c[0] - px, dy = c[1] - py, dz = c[2] - pz;
+    d = sqrt(dx * dx + dy * dy + dz * dz);
+    mz = c[2];
+  }
+  return d <= S.radius && fabs(mz - pose_z) < S.max_dz;
+}
+// One workgroup per (pose, chunk of 256 objects): blockIdx.x = pose * n_chunk + chunk.  EMIT = false: cnt[blockIdx.x] = kept objects
+// of the chunk (a 64-lane ballot per wave, the four wave counts through LDS).  EMIT = true: the test again, and every kept object
+// writes its row at base[pose] + chunkoff[blockIdx.x] (k_seg_scan of cnt, restarting at every pose) + the counts of the waves before
+// its own + its rank inside the wave (the popcount of the lanes below it): a stable compaction, no atomic decides the order.
+// Rows (prepareLCInput): cylinder [label, root, radius, 0, 0]; cube / ellipsoid [label, centre, scale].  Launch-latency bound at the
+// sizes of a key-pose list: a 10 000-object map is 0.5 MB, read once per pose out of L2.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_keypose_submap(SubmapDev S, int n_chunk, int* __restrict__ cnt, const long long* __restrict__ chunkoff,
+                                                        const long long* __restrict__ base, double* __restrict__ rows7,
+                                                        int32_t* __restrict__ src_idx) {
+  __shared__ int wcnt[4];
+  const int pose = (int)(blockIdx.x / (unsigned)n_chunk), chunk = (int)(blockIdx.x % (unsigned)n_chunk);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_all = S.n_cyl + S.n_cube + S.n_ell;
+  const int i = chunk * 256 + (int)threadIdx.x;
+  const double* pp = S.pose_xyz + (size_t)S.pose_stride * pose;
+  const double px = (double)(float)pp[0], py = (double)(float)pp[1], pz = (double)(float)pp[2];
+  const bool keep = i < n_all && submap_keeps(S, i, px, py, pz, pp[2]);
+  const unsigned long long mask = __ballot(keep);
+  if (lane == 0) wcnt[wave] = __popcll(mask);
+  __syncthreads();
+  if (!EMIT) {
+    if (threadIdx.x == 0) cnt[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    return;
+  }
+  if (!keep) return;
+  long long row = base[pose] + chunkoff[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; ++w) row += wcnt[w];
+  double* o = rows7 + 7 * (size_t)row;
+  if (i < S.n_cyl) {
+    o[0] = (double)S.cyl_label[i];
+    o[1] = S.cyl_root[3 * (size_t)i]; o[2] = S.cyl_root[3 * (size_t)i + 1]; o[3] = S.cyl_root[3 * (size_t)i + 2];
+    o[4] = S.cyl_radius[i]; o[5] = 0.0; o[6] = 0.0;
+  } else {
+    const bool cube = i < S.n_cyl + S.n_cube;
+    const int j = cube ? i - S.n_cyl : i - S.n_cyl - S.n_cube;
+    const double* c = (cube ? S.cube_xyz : S.ell_xyz) + 3 * (size_t)j;
+    const double* sc = (cube ? S.cube_scale : S.ell_scale) + 3 * (size_t)j;
+    o[0] = (double)(cube ? S.cube_label : S.ell_label)[j];
+    o[1] = c[0]; o[2] = c[1]; o[3] = c[2];
+    o[4] = sc[0]; o[5] = sc[1]; o[6] = sc[2];
+  }
+  if (src_idx) src_idx[row] = i;
+}
+void launch_keypose_submap(bool emit, const SubmapDev& S, int n_poses, int n_chunk, int* cnt, const long long* chunkoff, const long long* base,
+                           double* rows7, int32_t* src_idx, hipStream_t s) {
+  if (n_poses <= 0 || n_chunk <= 0) return;
+  const dim3 grid((unsigned)n_poses * (unsigned)n_chunk), block(256);
+  if (emit) hipLaunchKernelGGL(k_keypose_submap<true>, grid, block, 0, s, S, n_chunk, cnt, chunkoff, base, rows7, src_idx);
+  else hipLaunchKernelGGL(k_keypose_submap<false>, grid, block, 0, s, S, n_chunk, cnt, chunkoff, base, rows7, src_idx);
+}
+
 void launch_tri_match_seg(bool emit, const double* sd, const double* sx, const int* rowoff, const TriSeg* segs, int n_seg, int n_rows, double thr,
                           int* counts, const long long* offs, const long long* base, double* P1, double* P2, hipStream_t s) {
   if (n_rows <= 0) return;
