@@ -657,6 +657,77 @@ int slide_clipper_dense_clique_csr(const int32_t* rowptr, const int32_t* col, co
  * exists anywhere, on the host or the device.  sigma / epsilon / mindist / affinityeps from p.  nodes_out: m entries. */
 int slide_clipper_match(const double* D1, int n1, const double* D2, int n2, int dim, const int32_t* A, int m, const double* u0,
                         const slide_clipper_params_t* p, int32_t* nodes_out, int* n_nodes, double* u_out, double* score);
+/* ---- Selecting the mutually consistent subset of a list of loop closures ------------------------------------------------------
+ * Pairwise-consistency maximisation (PCM; Mangelson, Dominic, Eustice, Vasudevan, ICRA 2018) on the clique solver above.  It has NO
+ * counterpart in the reference: there every closure is accepted on an inlier count alone (place_recognition.cpp:845-856), the first
+ * that passes goes straight into the graph (sloamNode.cpp:448-476) with a noise of 0.01 x the odometry sigmas (graphWrapper.cpp:55),
+ * and one false closure at that weight bends the whole trajectory.
+ * A closure k: from_robot, from_idx, to_robot, to_idx, rel7 (the project's 7-double pose layout: x y z, qx qy qz qw) and sigma6, its
+ * own six sigmas.  Its meaning is exactly that of slide_graph_add_loop_closure, a Between factor on (X(from), X(to)): rel measures
+ * X_from^-1 X_to.  With the current estimates F_k = X(from_k), T_k = X(to_k), two closures i < j of one ordered robot pair close a
+ * cycle whose error is  e_ij = se3_log(z_i T_i^-1 T_j z_j^-1 F_j^-1 F_i)  in the tangent order [rot(3), trans(3)] — the order of
+ * sigma6, of odom_sigma6 and of every noise vector of slide_params_t.  Only within-robot relative poses (T_i^-1 T_j, F_j^-1 F_i)
+ * appear, so the formula holds when the two robots' world frames are unrelated.  Per component
+ * s2[c] = sigma6_i[c]^2 + sigma6_j[c]^2 + (|from_idx_i - from_idx_j| + |to_idx_i - to_idx_j|) odom_sigma6[c]^2 (the odometry legs of
+ * the cycle), d = sqrt(sum_c e[c]^2 / s2[c]), and the score is d < gate ? exp(-0.5 d^2 / sigma^2) : 0, kept if > affinityeps.  e_ij
+ * is not symmetric in (i, j): every entry is evaluated with the smaller closure index as i, so the matrix is symmetric bit for bit.
+ * gate = sqrt(16.81) = 4.1, the 0.99 quantile of chi-square with 6 degrees of freedom; sigma = gate / 2, a convention (the score at the
+ * gate is exp(-2)); affinityeps = 1e-4, CLIPPER's default; min_set = 1: a group whose selected set is smaller keeps nothing, and with 1
+ * a lone closure is kept, the reference's behaviour.  odom_sigma6: per odometry step; slide_graph_select_closures takes it from the
+ * graph's noise_model_odom_vec instead. */
+typedef struct {
+  double gate;            /* 4.1 */
+  double sigma;           /* gate / 2 */
+  double affinityeps;     /* 1e-4 */
+  double odom_sigma6[6];  /* 0.1 (slide_params_t::noise_model_odom_vec's default) */
+  int min_set;            /* 1 */
+} slide_closure_params_t;
+void slide_closure_default_params(slide_closure_params_t* p);
+/* Host bookkeeping, no kernel: closures of different unordered robot pairs are different problems ("groups").  Every closure with
+ * from_robot > to_robot is canonicalised by swapping its ends and inverting rel (flipped[k] = 1); same-robot closures are not
+ * reordered, either orientation closes a valid cycle.  Groups are numbered by ascending (from_robot, to_robot) and filled stably:
+ * group[k], and order[k] = the row of closure k in the list of all groups' closures one group after the other.  Every output but
+ * n_groups may be NULL. */
+int slide_closure_canonicalize(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
+                               const double* rel7, int32_t* from_robot_out, uint64_t* from_idx_out, int32_t* to_robot_out,
+                               uint64_t* to_idx_out, double* rel7_out, int32_t* flipped, int32_t* group, int32_t* order, int* n_groups);
+/* The consistency matrix of ONE group (the caller's closures as they are, nothing canonicalised), poses given per closure
+ * (from_pose7 / to_pose7: L x 7): the symmetric CSR without its diagonal, columns ascending, built on the device (k_closure_prepare,
+ * k_closure_csr_seg count, k_seg_scan, emit).  The two-call protocol of slide_clipper_affinity_csr: *nnz is always set, cap < *nnz
+ * returns SLIDE_ERR_CAPACITY with col_out / val_out untouched (rowptr_out, L + 1 ints, still filled). */
+int slide_closure_consistency_csr(const double* from_pose7, const double* to_pose7, const double* rel7, const double* sigma6,
+                                  const uint64_t* from_idx, const uint64_t* to_idx, int L, const slide_closure_params_t* p,
+                                  int32_t* rowptr_out, int32_t* col_out, double* val_out, long long cap, long long* nnz);
+/* A list of closures over any robot pairs, poses given per closure: canonicalise, group, ONE k_closure_prepare, k_closure_csr_seg
+ * count, k_seg_scan, emit, then ONE k_clq_solve_b launch for every group below 1024 closures; larger groups go one after another
+ * through the single problem's multi-workgroup route on their slice.  DSD_HEU rounding.  A group of one closure never reaches the
+ * device (selected 1, score 1, u 1); the single-group case is this path with one group.  A group's bits do not depend on what else is
+ * in the list or where it stands.  Blocking read-backs: 2 per call whatever the number of groups (the groups' non-zero counts; the
+ * solves' results in one buffer), + 2 for every group of 1024 or more, + 3 when the CSR is asked for.
+ * Per closure: keep[k] (0 / 1), group[k], status[k] (SLIDE_OK; SLIDE_ERR_CAPACITY: its group's matrix exceeds 2^31 - 1 non-zeros, keep
+ * 0) — group / status may be NULL.  Per group g (arrays of L entries, may be NULL): n_selected[g], score[g]; *n_groups.
+ * cp: the solver's parameters (NULL: slide_clipper_default_params; its sigma / epsilon / mindist / affinityeps are not read).
+ * u0 (NULL, or one pointer per closure group in group order, each NULL or that group's start weights in row order): NULL draws the
+ * fixed-seed start per group.  u_out (NULL or L): the solved weight of each closure.  csr_*: NULL, or the matrices of all groups one
+ * after the other for inspection — rowcnt_out[k] the non-zeros of closure k's row, col / val (columns counted within the group) copied
+ * when *csr_nnz <= csr_cap.
+ * Whole-call refusals (SLIDE_ERR_INVALID, decided on the host before the device is touched, nothing written): a needed pointer NULL,
+ * L < 0, a robot outside [0, SLIDE_MAX_ROBOTS), non-finite input, a zero quaternion, a sigma <= 0, gate / sigma <= 0, affinityeps < 0
+ * or non-finite, min_set < 0.  L == 0: SLIDE_OK, *n_groups = 0. */
+int slide_select_consistent_closures(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
+                                     const uint64_t* to_idx, const double* rel7, const double* sigma6, const double* from_pose7,
+                                     const double* to_pose7, const slide_closure_params_t* p, const slide_clipper_params_t* cp,
+                                     const double* const* u0, int32_t* keep, int32_t* group, int32_t* status, int32_t* n_selected,
+                                     double* score, int* n_groups, double* u_out, int32_t* rowcnt_out, int32_t* col_out, double* val_out,
+                                     long long csr_cap, long long* csr_nnz);
+/* The same with the endpoints resolved against the graph's current estimate (read from the device-resident estimate by slot, nothing
+ * is downloaded) and odom_sigma6 = the graph's noise_model_odom_vec (p's own is not read): call it after a solve and before the
+ * closures are added.  A closure naming a pose the graph does not hold (or has not taken in by a solve yet): status[k] =
+ * SLIDE_MISSING, keep 0, group -1; the others proceed.  It reads the graph and changes nothing in it. */
+int slide_graph_select_closures(slide_graph_t* g, int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
+                                const uint64_t* to_idx, const double* rel7, const double* sigma6, const slide_closure_params_t* p,
+                                const slide_clipper_params_t* cp, int32_t* keep, int32_t* group, int32_t* status, int32_t* n_selected,
+                                double* score, int* n_groups);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the

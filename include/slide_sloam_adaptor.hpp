@@ -234,6 +234,37 @@ class SemanticFactorGraph {
   // graph.h:115 (never set in the reference): empty = the graph's own noise_model_odom_vec, else six sigmas per metre
   std::vector<double> noise_model_pose_vec_per_m;
 
+  // The mutually consistent subset of a list of loop closures (slide_graph_select_closures; no counterpart in the reference, which
+  // adds the first closure that passes straight into the graph, sloamNode.cpp:448-476): what addLoopClosureFactor takes, as vectors,
+  // plus each closure's own six sigmas [rot, trans]; keep[k] = closure k belongs to the consistent set of its robot pair.  Call it
+  // after solve() and before the closures are added; the graph is only read.  A closure naming a pose the graph does not hold is
+  // not kept (status, when given, holds SLIDE_MISSING for it).  params = nullptr: slide_closure_default_params.
+  template <class Pose>
+  std::vector<bool> selectConsistentClosures(const std::vector<Pose>& posesRelative, const std::vector<size_t>& fromIdx,
+                                             const std::vector<size_t>& fromRobot, const std::vector<size_t>& toIdx,
+                                             const std::vector<size_t>& toRobot, const std::vector<std::array<double, 6>>& sigmas,
+                                             const slide_closure_params_t* params = nullptr, std::vector<int32_t>* status = nullptr) const {
+    const size_t n = posesRelative.size();
+    if (fromIdx.size() != n || fromRobot.size() != n || toIdx.size() != n || toRobot.size() != n || sigmas.size() != n)
+      throw Error(SLIDE_ERR_INVALID, std::string("selectConsistentClosures: one entry per closure in every vector"));
+    std::vector<double> rel(7 * n + 1), sg(6 * n + 1);
+    std::vector<int32_t> fr(n + 1), tr(n + 1), keep(n + 1, 0), st(n + 1, 0);
+    std::vector<uint64_t> fi(n + 1), ti(n + 1);
+    for (size_t k = 0; k < n; ++k) {
+      detail::to7(posesRelative[k], rel.data() + 7 * k);
+      for (int c = 0; c < 6; ++c) sg[6 * k + c] = sigmas[k][c];
+      fr[k] = (int32_t)fromRobot[k]; tr[k] = (int32_t)toRobot[k]; fi[k] = fromIdx[k]; ti[k] = toIdx[k];
+    }
+    int n_groups = 0;
+    detail::check(slide_graph_select_closures(g_, (int)n, fr.data(), fi.data(), tr.data(), ti.data(), rel.data(), sg.data(), params, nullptr,
+                                              keep.data(), nullptr, st.data(), nullptr, nullptr, &n_groups),
+                  "selectConsistentClosures");
+    if (status) status->assign(st.begin(), st.begin() + n);
+    std::vector<bool> out(n);
+    for (size_t k = 0; k < n; ++k) out[k] = keep[k] != 0;
+    return out;
+  }
+
   slide_graph_t* handle() const { return g_; }
 
  protected:

@@ -41,6 +41,8 @@ EXPORTS = [
     "slide_estimate_tf2d", "slide_semantic_clipper", "slide_find_relative_meas_match", "slide_delaunay_2d", "slide_run_semantic_clipper",
     "slide_pick_next_measurement", "slide_in_loop_closure_region",
     "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
+    "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
+    "slide_graph_select_closures",
 ]
 
 
@@ -349,6 +351,23 @@ class SlideGraph:
             self.h, C.c_int(robot), C.c_int(len(trajs)), off.ctypes.data_as(vp), traj.ctypes.data_as(vp), travel.ctypes.data_as(vp),
             sg.ctypes.data_as(vp) if sg is not None else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
         return out, status
+
+    def select_closures(self, closures, params=None, clipper=None):
+        """slide_graph_select_closures: the mutually consistent subset of a list of loop closures, their endpoints resolved against
+        the graph's current estimate (call it after a solve and before the closures are added; the graph is only read).  closures:
+        dicts or tuples (from_robot, from_idx, to_robot, to_idx, rel7, sigma6) — the arguments of add_loop_closure plus the closure's
+        own six sigmas [rot, trans].  Returns a dict: keep (bool per closure), group, status (SLIDE_MISSING: an endpoint the graph
+        does not hold), n_selected / score per group."""
+        fr, fi, tr, ti, rel, sg = _closure_arrays(closures)
+        L = len(fr)
+        p = params or closure_params()
+        cp = clipper or clipper_params()
+        keep, group, status = np.zeros(max(L, 1), np.int32), np.full(max(L, 1), -1, np.int32), np.zeros(max(L, 1), np.int32)
+        nsel, score, ng = np.zeros(max(L, 1), np.int32), np.zeros(max(L, 1)), C.c_int(0)
+        _check(self.L.slide_graph_select_closures(self.h, C.c_int(L), _p(fr), _p(fi), _p(tr), _p(ti), _p(rel), _p(sg), C.byref(p),
+                                                  C.byref(cp), _p(keep), _p(group), _p(status), _p(nsel), _p(score), C.byref(ng)))
+        return {"keep": keep[:L].astype(bool), "group": group[:L].copy(), "status": status[:L].copy(),
+                "n_selected": nsel[:ng.value].copy(), "score": score[:ng.value].copy()}
 
     def set_ghosts(self, own_robot, own_idx):
         r = _i(own_robot)
@@ -1112,6 +1131,135 @@ def clipper_match(D1, D2, A, u0=None, params=None):
     _check(lib().slide_clipper_match(_p(D1), C.c_int(D1.shape[0]), _p(D2), C.c_int(D2.shape[0]), C.c_int(D1.shape[1]), _p(A), C.c_int(m),
                                      _p(u0a) if u0a is not None else None, C.byref(p), _p(nodes), C.byref(nn), _p(u), C.byref(sc)))
     return nodes[:nn.value].copy(), u[:m].copy(), sc.value
+
+
+class ClosureParams(C.Structure):
+    """slide_closure_params_t: the gate, the score's width and the odometry sigmas of the loop-closure consistency test."""
+    _fields_ = [("gate", C.c_double), ("sigma", C.c_double), ("affinityeps", C.c_double), ("odom_sigma6", C.c_double * 6),
+                ("min_set", C.c_int)]
+
+
+def closure_params(**kw) -> ClosureParams:
+    p = ClosureParams()
+    lib().slide_closure_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "odom_sigma6":
+            for i, x in enumerate(np.broadcast_to(np.asarray(v, float), (6,))):
+                p.odom_sigma6[i] = float(x)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _closure_arrays(closures):
+    """closures: dicts with from_robot, from_idx, to_robot, to_idx, rel7, sigma6 (or tuples in that order) -> the flat arrays."""
+    rows = [(c["from_robot"], c["from_idx"], c["to_robot"], c["to_idx"], c["rel7"], c["sigma6"]) if isinstance(c, dict) else tuple(c)
+            for c in closures]
+    L = len(rows)
+    fr = np.array([r[0] for r in rows] + [0], np.int32)
+    fi = np.array([r[1] for r in rows] + [0], np.uint64)
+    tr = np.array([r[2] for r in rows] + [0], np.int32)
+    ti = np.array([r[3] for r in rows] + [0], np.uint64)
+    rel = np.zeros((L + 1, 7))
+    sg = np.ones((L + 1, 6))
+    for k, r in enumerate(rows):
+        rel[k] = np.asarray(r[4], float).reshape(7)
+        sg[k] = np.broadcast_to(np.asarray(r[5], float), (6,))
+    return fr[:L], fi[:L], tr[:L], ti[:L], rel[:L], sg[:L]
+
+
+def closure_canonicalize(closures):
+    """slide_closure_canonicalize (host bookkeeping, no device): closures with from_robot > to_robot get their ends swapped and rel
+    inverted; groups by ascending (from_robot, to_robot), filled stably.  Returns a dict of arrays: from_robot, from_idx, to_robot,
+    to_idx, rel7, flipped, group, order (row in the grouped list) and n_groups."""
+    fr, fi, tr, ti, rel, _ = _closure_arrays(closures)
+    L = len(fr)
+    n = max(L, 1)
+    o = {"from_robot": np.zeros(n, np.int32), "from_idx": np.zeros(n, np.uint64), "to_robot": np.zeros(n, np.int32),
+         "to_idx": np.zeros(n, np.uint64), "rel7": np.zeros((n, 7)), "flipped": np.zeros(n, np.int32), "group": np.zeros(n, np.int32),
+         "order": np.zeros(n, np.int32)}
+    ng = C.c_int(0)
+    _check(lib().slide_closure_canonicalize(C.c_int(L), _p(fr), _p(fi), _p(tr), _p(ti), _p(rel), _p(o["from_robot"]), _p(o["from_idx"]),
+                                            _p(o["to_robot"]), _p(o["to_idx"]), _p(o["rel7"]), _p(o["flipped"]), _p(o["group"]),
+                                            _p(o["order"]), C.byref(ng)))
+    o = {k: v[:L] for k, v in o.items()}
+    o["n_groups"] = ng.value
+    return o
+
+
+def closure_consistency_csr(from_pose7, to_pose7, rel7, sigma6, from_idx, to_idx, params=None):
+    """slide_closure_consistency_csr: the loop-closure consistency matrix of ONE group (the closures as given), poses per closure, as
+    the symmetric CSR without its diagonal, built on the device.  Returns (rowptr (L + 1), col, val), columns ascending."""
+    fp, tp, rel, sg = _d(from_pose7).reshape(-1, 7), _d(to_pose7).reshape(-1, 7), _d(rel7).reshape(-1, 7), _d(sigma6).reshape(-1, 6)
+    fi, ti = np.ascontiguousarray(from_idx, np.uint64), np.ascontiguousarray(to_idx, np.uint64)
+    L = rel.shape[0]
+    if not (len(fp) == len(tp) == len(sg) == len(fi) == len(ti) == L):
+        raise ValueError("one pose pair, sigma6 and index pair per closure")
+    p = params or closure_params()
+    rowptr = np.zeros(L + 1, np.int32)
+    nnz = C.c_longlong(0)
+
+    def call(col, val, cap):
+        return lib().slide_closure_consistency_csr(_p(fp), _p(tp), _p(rel), _p(sg), _p(fi), _p(ti), C.c_int(L), C.byref(p), _p(rowptr),
+                                                   col, val, C.c_longlong(cap), C.byref(nnz))
+    rc = call(None, None, 0)
+    if rc == SLIDE_OK:                       # nothing to fetch
+        return rowptr, np.zeros(0, np.int32), np.zeros(0)
+    if rc != SLIDE_ERR_CAPACITY or nnz.value <= 0:
+        _check(rc)
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+    _check(call(_p(col), _p(val), nnz.value))
+    return rowptr, col, val
+
+
+def select_consistent_closures(closures, from_pose7, to_pose7, params=None, clipper=None, u0=None, with_csr=False):
+    """slide_select_consistent_closures: the mutually consistent subset of a list of loop closures over any robot pairs
+    (pairwise-consistency maximisation on the clique solver), the endpoints' poses given per closure.  closures as in
+    SlideGraph.select_closures; u0: None, or a dict {group: start weights in the group's row order}.  Returns a dict: keep (bool),
+    group, status, u per closure; n_selected, score per group; with_csr: also csr = one (rowptr, col, val) per group (None for a
+    group of one closure)."""
+    fr, fi, tr, ti, rel, sg = _closure_arrays(closures)
+    L = len(fr)
+    fp, tp = _d(from_pose7).reshape(-1, 7), _d(to_pose7).reshape(-1, 7)
+    if len(fp) != L or len(tp) != L:
+        raise ValueError("one pose pair per closure")
+    p = params or closure_params()
+    cp = clipper or clipper_params()
+    n = max(L, 1)
+    keep, group, status = np.zeros(n, np.int32), np.full(n, -1, np.int32), np.zeros(n, np.int32)
+    nsel, score, ng, u = np.zeros(n, np.int32), np.zeros(n), C.c_int(0), np.zeros(n)
+    u0p, held = None, []
+    if u0:
+        arr = (C.c_void_p * n)()
+        for g, w in u0.items():
+            held.append(_d(w))
+            arr[int(g)] = held[-1].ctypes.data
+        u0p = arr
+    rowcnt = col = val = None
+    cap, nnz = 0, C.c_longlong(0)
+    if with_csr:
+        cap = L * max(L - 1, 0)
+        rowcnt, col, val = np.zeros(n, np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1))
+    _check(lib().slide_select_consistent_closures(C.c_int(L), _p(fr), _p(fi), _p(tr), _p(ti), _p(rel), _p(sg), _p(fp), _p(tp), C.byref(p),
+                                                  C.byref(cp), u0p, _p(keep), _p(group), _p(status), _p(nsel), _p(score), C.byref(ng),
+                                                  _p(u), _p(rowcnt) if with_csr else None, _p(col) if with_csr else None,
+                                                  _p(val) if with_csr else None, C.c_longlong(cap), C.byref(nnz)))
+    out = {"keep": keep[:L].astype(bool), "group": group[:L].copy(), "status": status[:L].copy(), "u": u[:L].copy(),
+           "n_selected": nsel[:ng.value].copy(), "score": score[:ng.value].copy()}
+    if with_csr:
+        # rows of a group in list order (the stable grouping), its slice of col / val behind the groups of two or more before it
+        csr, at = [], 0
+        for g in range(ng.value):
+            rows = np.nonzero(group[:L] == g)[0]
+            if len(rows) < 2:
+                csr.append(None)
+                continue
+            rp = np.concatenate([[0], np.cumsum(rowcnt[rows])]).astype(np.int32)
+            csr.append((rp, col[at:at + rp[-1]].copy(), val[at:at + rp[-1]].copy()))
+            at += int(rp[-1])
+        assert at == nnz.value
+        out["csr"] = csr
+    return out
 
 
 def clipper_last_solve_info():

@@ -28,6 +28,7 @@ SOURCES = [
     ("assoc_kernels.hip", ["-ffp-contract=off"]),
     ("place_kernels.hip", ["-ffp-contract=off"]),
     ("clipper_kernels.hip", ["-ffp-contract=off"]),
+    ("closure_kernels.hip", ["-ffp-contract=off"]),     # loop-closure consistency scores compared against a gate
     ("host_graph.hip", ["-ffp-contract=off"]),
     ("host_marginals.hip", ["-ffp-contract=off"]),     # (its Woodbury step runs on the host: same rounding as host_graph.hip)
     ("host_backend.hip", ["-ffp-contract=off"]),

@@ -393,6 +393,12 @@ class HostGraph {
   int gauss_newton(int iterations);  // batch GN iterations (threshold 0)
   int get_pose12(int robot, uint64_t idx, double* out12);   // SLIDE_MISSING + identity when absent
   int get_landmark(int cls, uint64_t idx, double* out);
+  // slide_graph_select_closures: slot[k] = row of pose (robot[k], idx[k]) in the device-resident estimate, -1 when the graph does
+  // not hold it (or has not uploaded it yet); the estimate itself, 12 doubles per row.  Nothing is changed.
+  void pose_slots(const int32_t* robot, const uint64_t* idx, int n, int32_t* slot) const {
+    for (int k = 0; k < n; ++k) slot[k] = robot_ok(robot[k]) ? pose_id(robot[k], idx[k]) : -1;
+  }
+  const double* pose_est_dev() const { return d_pose_est.d; }
   int lm_lid(int cls, uint64_t idx) const;                   // -1 when not merged yet
   // one-robot-per-GPU mode: shared-landmark slots + the three phases of a distributed GN pass
   int set_shared(const int32_t* cls, const int64_t* idx, const int32_t* owner, int n_slots);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "graph_dev.hpp"
+#include "sl_math.hpp"
 
 namespace sl {
 
@@ -334,5 +335,50 @@ void launch_affinity_csr_seg(bool emit, const double* P1, const double* P2, cons
                              hipStream_t s);
 // U[aoff[s] + i] = work[6 aoff[s] + i]: the solved weights of all pairs side by side
 void launch_clq_pack_u(const double* work, const int* aoff, int n_seg, int n_rows, double* U, hipStream_t s);
+
+// closure_kernels.hip — pairwise-consistency maximisation (PCM; Mangelson et al., ICRA 2018) over a list of loop closures: the
+// consistency matrix as CSR on the device, solved by the clique kernels above.  No counterpart in the reference, which adds the first
+// closure that passes its inlier test straight into the graph (sloamNode.cpp:448-476).
+// A closure k measures z_k = X(from_k)^-1 X(to_k) (the meaning of slide_graph_add_loop_closure).  With the current estimates
+// F_k = X(from_k), T_k = X(to_k), two closures i < j of one ordered robot pair close the cycle
+//     e_ij = se3_log(z_i T_i^-1 T_j z_j^-1 F_j^-1 F_i) = se3_log(U_i G_j^-1 F_i),   U_k = z_k T_k^-1,  G_k = F_k U_k,
+// in se3_log's tangent order [rot(3), trans(3)].  Only T_i^-1 T_j and F_j^-1 F_i — poses of ONE robot each — enter, so the two
+// robots' world frames need not be related.  k_closure_prepare writes per closure the 36 doubles [U | G^-1 | F] (R row-major, t).
+constexpr int CLOSURE_PRE = 36;
+struct ClosureScore { double gate, sigma, affinityeps, odom2[6]; };      // odom2: odom_sigma6 squared
+// THE one text of the pair score, called with the smaller closure index as (i) — on the device by k_closure_csr_seg and, being plain
+// host + device code, by a stand-alone CPU check: pre_i / pre_j the closures' prepared 36 doubles, s2i / s2j their squared sigmas,
+// legs = |from_idx_i - from_idx_j| + |to_idx_i - to_idx_j| odometry steps.  Variance per component s2i + s2j + legs odom2;
+// d = sqrt(sum e^2 / s2); d < gate ? exp(-0.5 d^2 / sigma^2) : 0, kept above affinityeps.  closure_kernels.hip is compiled with
+// -ffp-contract=off: correctly rounded operations in one fixed order plus the math library's acos / sin / tan / sqrt / exp.
+__host__ __device__ __forceinline__ double closure_pair_score(const double* __restrict__ pre_i, const double* __restrict__ pre_j, const double* __restrict__ s2i,
+                                                              const double* __restrict__ s2j, double legs, const ClosureScore& P) {
+  const SE3 E = compose(compose(from12(pre_i), from12(pre_j + 12)), from12(pre_i + 24));
+  double e[6];
+  se3_log(E, e);
+  double q = 0.0;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) q += e[c] * e[c] / (s2i[c] + s2j[c] + legs * P.odom2[c]);
+  const double d = sqrt(q);
+  const double scr = d < P.gate ? exp(-0.5 * d * d / (P.sigma * P.sigma)) : 0.0;
+  return scr > P.affinityeps ? scr : 0.0;
+}
+// what rows and columns of the matrix need of one closure, formed once (k_closure_prepare; host + device like the score)
+__host__ __device__ __forceinline__ void closure_prepare_one(const SE3& F, const SE3& T, const SE3& z, double* __restrict__ pre) {
+  const SE3 U = compose(z, inverse(T));
+  to12(U, pre);
+  to12(inverse(compose(F, U)), pre + 12);
+  to12(F, pre + 24);
+}
+// one thread per closure (rows of all groups flattened): F / T from the caller's pose12 arrays (fslot == null, row k at 12 k) or from a
+// graph's device-resident estimate by slot (pose12 = pose_est, rows fslot[k] / tslot[k]); z12: the measured relative poses
+void launch_closure_prepare(const double* fpose12, const double* tpose12, const int32_t* fslot, const int32_t* tslot, const double* z12, int n,
+                            double* pre, hipStream_t s);
+// The consistency CSRs of a LIST of groups in one launch, as launch_affinity_csr_seg: rows flattened behind goff[0 .. n_seg], the
+// columns of a row run over ITS group only.  sig2: 6 per row (squared sigmas), idx2: from_idx, to_idx per row.  count: rowcnt[row];
+// emit: group s at nnz0[s] (< 0: skipped) + its own row pointers rowptr[goff[s] + s ...].
+void launch_closure_csr_seg(bool emit, const double* pre, const double* sig2, const unsigned long long* idx2, const int* goff, int n_seg,
+                            int n_rows, const ClosureScore& P, int* rowcnt, const int* rowptr, const long long* nnz0, int* col, double* val,
+                            hipStream_t s);
 
 }  // namespace sl
