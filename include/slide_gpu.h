@@ -728,6 +728,38 @@ int slide_graph_select_closures(slide_graph_t* g, int L, const int32_t* from_rob
                                 const uint64_t* to_idx, const double* rel7, const double* sigma6, const slide_closure_params_t* p,
                                 const slide_clipper_params_t* cp, int32_t* keep, int32_t* group, int32_t* status, int32_t* n_selected,
                                 double* score, int* n_groups);
+/* ---- One closure against what the graph already knows: the individual-compatibility gate ----------------------------------------
+ * slide_graph_select_closures compares closures with each other; it cannot judge a lone closure, and a group of false closures that
+ * agree with each other (perceptual aliasing) forms a clique like a true one.  The complement measures a closure's residual against
+ * its own noise plus the joint marginal covariance of its two poses under the graph as it stands.  No counterpart in the reference
+ * (GTSAM users know the first query as Marginals::jointMarginalCovariance).
+ * Both calls use one identity: with S = L L^T the resident factor of the landmark-eliminated pose system and Sigma = S^-1,
+ * B^T Sigma B = W^T W where L W = B — a forward substitution only (T launches per sweep, not the 2 T of a solve) and symmetric
+ * positive semi-definite by construction.  Single-graph path only (one graph may hold several robots).  Candidates are cut into
+ * sweeps of whole candidates of at most SLIDE_INFO_GAIN_SWEEP_COLS columns of B (32 pairs or 64 closures); a sweep is one
+ * many-column forward substitution, the candidates' diagonal gram blocks and one read-back, and a candidate's bits do not depend on
+ * what else is in the list or where it stands.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written): those of slide_graph_get_pose_covariances (sharded or exact-joint mode,
+ * before the first solve, after slide_graph_chi2, once anything was merged after the last solve), and — decided on the host before
+ * the device is touched — a needed pointer NULL, n or L < 0, a robot outside [0, SLIDE_MAX_ROBOTS), non-finite input, a zero
+ * quaternion, a sigma <= 0.  n == 0 / L == 0 on a graph that would be served: SLIDE_OK.  Per candidate, into status[k] (may be NULL)
+ * with zeros in its outputs: SLIDE_MISSING for a pose the graph does not hold, SLIDE_ERR_INVALID when both ends are the same pose,
+ * SLIDE_ERR_NOT_SPD when I + A Sigma A^T has a pivot that is not positive.  The calls read the graph and change nothing in it.
+ *
+ * out144n: per pair the 12 x 12 row-major joint marginal [[Saa, Sab], [Sba, Sbb]]: pose a's six coordinates, then pose b's, tangent
+ * order [rot, trans] (B = the unit columns of the two poses' rows). */
+int slide_graph_get_pose_pair_covariances(slide_graph_t* g, int n, const int32_t* robot_a, const uint64_t* idx_a, const int32_t* robot_b,
+                                          const uint64_t* idx_b, double* out144n, int32_t* status);
+/* The endpoint arguments, rel7 and sigma6 mean exactly what they mean to slide_graph_select_closures (the same arrays can go to both
+ * calls): closure k is the Between factor slide_graph_add_loop_closure(rel7_k, from, to) would add with the sigmas sigma6_k.  r_k (6)
+ * is its whitened residual and A_k (6 x 12) its whitened Jacobian, linearised by the solver's own Between text under the graph's
+ * pose_chart at the current estimate of the two poses (what slide_graph_get_pose12 returns).  C_k = I + A_k Sigma A_k^T (B = A_k^T) is
+ * the innovation covariance in whitened units and d2[k] = r_k^T C_k^-1 r_k: chi-square with 6 degrees of freedom for a true closure
+ * that was not added yet.  Compare it with 16.81 (slide_closure_params_t::gate squared); the call itself applies no threshold.
+ * C36 (36 per closure, row-major) and r6 (6 per closure) may be NULL. */
+int slide_graph_closure_mahalanobis(slide_graph_t* g, int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
+                                    const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36 /* may be NULL */,
+                                    double* r6 /* may be NULL */, int32_t* status /* may be NULL */);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the

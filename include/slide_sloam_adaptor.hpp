@@ -265,6 +265,57 @@ class SemanticFactorGraph {
     return out;
   }
 
+  // Marginals::jointMarginalCovariance of two poses (slide_graph_get_pose_pair_covariances): the 12 x 12 block
+  // [[Saa, Sab], [Sba, Sbb]], pose a's six coordinates then pose b's, tangent order [rot, trans].  Mat12: anything written through
+  // m(r, c) that default-constructs to 12 x 12 (Eigen::Matrix<double, 12, 12>); the plain form returns it row-major.  Throws
+  // std::out_of_range for a pose the graph does not hold, Error for one pose named twice.
+  std::array<double, 144> jointPoseCovariance(const size_t idxA, const size_t robotA, const size_t idxB, const size_t robotB) const {
+    std::array<double, 144> c{};
+    const int32_t ra = (int32_t)robotA, rb = (int32_t)robotB;
+    const uint64_t ia = idxA, ib = idxB;
+    int32_t st = SLIDE_OK;
+    detail::check(slide_graph_get_pose_pair_covariances(g_, 1, &ra, &ia, &rb, &ib, c.data(), &st), "jointPoseCovariance");
+    if (st == SLIDE_MISSING) throw std::out_of_range("jointPoseCovariance: pose not in the graph");
+    if (st != SLIDE_OK) throw Error(st, std::string("jointPoseCovariance: both ends are the same pose"));
+    return c;
+  }
+  template <class Mat12>
+  Mat12 jointPoseCovariance(const size_t idxA, const size_t robotA, const size_t idxB, const size_t robotB) const {
+    const std::array<double, 144> c = jointPoseCovariance(idxA, robotA, idxB, robotB);
+    Mat12 m;
+    for (int r = 0; r < 12; ++r)
+      for (int q = 0; q < 12; ++q) m(r, q) = c[12 * r + q];
+    return m;
+  }
+  // The individual-compatibility gate of a list of loop closures (slide_graph_closure_mahalanobis), over the vectors
+  // selectConsistentClosures takes: d2[k] = r^T (I + A Sigma A^T)^-1 r of closure k against the graph as it stands, chi-square with 6
+  // degrees of freedom for a true closure — compare it with 16.81; no threshold is applied here.  Call it after solve() and before the
+  // closures are added; the graph is only read.  A closure with a fault of its own (status, when given: SLIDE_MISSING,
+  // SLIDE_ERR_INVALID for from == to, SLIDE_ERR_NOT_SPD) has d2 = 0: read the status before the value.
+  template <class Pose>
+  std::vector<double> closureMahalanobis(const std::vector<Pose>& posesRelative, const std::vector<size_t>& fromIdx,
+                                         const std::vector<size_t>& fromRobot, const std::vector<size_t>& toIdx,
+                                         const std::vector<size_t>& toRobot, const std::vector<std::array<double, 6>>& sigmas,
+                                         std::vector<int32_t>* status = nullptr) const {
+    const size_t n = posesRelative.size();
+    if (fromIdx.size() != n || fromRobot.size() != n || toIdx.size() != n || toRobot.size() != n || sigmas.size() != n)
+      throw Error(SLIDE_ERR_INVALID, std::string("closureMahalanobis: one entry per closure in every vector"));
+    std::vector<double> rel(7 * n + 1), sg(6 * n + 1), d2(n + 1, 0.0);
+    std::vector<int32_t> fr(n + 1), tr(n + 1), st(n + 1, 0);
+    std::vector<uint64_t> fi(n + 1), ti(n + 1);
+    for (size_t k = 0; k < n; ++k) {
+      detail::to7(posesRelative[k], rel.data() + 7 * k);
+      for (int c = 0; c < 6; ++c) sg[6 * k + c] = sigmas[k][c];
+      fr[k] = (int32_t)fromRobot[k]; tr[k] = (int32_t)toRobot[k]; fi[k] = fromIdx[k]; ti[k] = toIdx[k];
+    }
+    detail::check(slide_graph_closure_mahalanobis(g_, (int)n, fr.data(), fi.data(), tr.data(), ti.data(), rel.data(), sg.data(), d2.data(),
+                                                  nullptr, nullptr, st.data()),
+                  "closureMahalanobis");
+    if (status) status->assign(st.begin(), st.begin() + n);
+    d2.resize(n);
+    return d2;
+  }
+
   slide_graph_t* handle() const { return g_; }
 
  protected:

@@ -42,7 +42,7 @@ EXPORTS = [
     "slide_pick_next_measurement", "slide_in_loop_closure_region",
     "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
-    "slide_graph_select_closures",
+    "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
 ]
 
 
@@ -368,6 +368,33 @@ class SlideGraph:
                                                   C.byref(cp), _p(keep), _p(group), _p(status), _p(nsel), _p(score), C.byref(ng)))
         return {"keep": keep[:L].astype(bool), "group": group[:L].copy(), "status": status[:L].copy(),
                 "n_selected": nsel[:ng.value].copy(), "score": score[:ng.value].copy()}
+
+    def get_pose_pair_covariances(self, pairs):
+        """slide_graph_get_pose_pair_covariances (Marginals::jointMarginalCovariance): pairs = tuples (robot_a, idx_a, robot_b, idx_b).
+        Returns ((n, 12, 12), (n,) int32 status): block k = [[Saa, Sab], [Sba, Sbb]], pose a's six coordinates then pose b's, tangent
+        order [rot, trans]; a pair naming a pose the graph does not hold (SLIDE_MISSING) or one pose twice (SLIDE_ERR_INVALID) has
+        zeros and its code.  The graph is only read."""
+        rows = [tuple(p) for p in pairs]
+        n = len(rows)
+        ra, rb = (np.array([r[j] for r in rows] + [0], np.int32) for j in (0, 2))
+        ia, ib = (np.array([r[j] for r in rows] + [0], np.uint64) for j in (1, 3))
+        out, status = np.zeros((max(n, 1), 12, 12)), np.zeros(max(n, 1), np.int32)
+        _check(self.L.slide_graph_get_pose_pair_covariances(self.h, C.c_int(n), _p(ra), _p(ia), _p(rb), _p(ib), _p(out), _p(status)))
+        return out[:n], status[:n]
+
+    def closure_mahalanobis(self, closures):
+        """slide_graph_closure_mahalanobis: the individual-compatibility test of every closure of a list against the graph as it
+        stands (call it after a solve and before the closures are added; the graph is only read).  closures: what select_closures
+        takes.  Returns a dict: d2 (L) = r^T C^-1 r, chi-square with 6 degrees of freedom for a true closure — compare it with 16.81,
+        no threshold is applied here; status (SLIDE_MISSING, SLIDE_ERR_INVALID for from == to, SLIDE_ERR_NOT_SPD; zeros then);
+        C (L, 6, 6) = I + A Sigma A^T and r (L, 6), the whitened innovation covariance and residual."""
+        fr, fi, tr, ti, rel, sg = _closure_arrays(closures)
+        L = len(fr)
+        n = max(L, 1)
+        d2, Cm, r, status = np.zeros(n), np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros(n, np.int32)
+        _check(self.L.slide_graph_closure_mahalanobis(self.h, C.c_int(L), _p(fr), _p(fi), _p(tr), _p(ti), _p(rel), _p(sg), _p(d2), _p(Cm),
+                                                      _p(r), _p(status)))
+        return {"d2": d2[:L], "status": status[:L], "C": Cm[:L], "r": r[:L]}
 
     def set_ghosts(self, own_robot, own_idx):
         r = _i(own_robot)

@@ -74,4 +74,113 @@ void launch_closure_csr_seg(bool emit, const double* pre, const double* sig2, co
   else hipLaunchKernelGGL(k_closure_csr_seg<false>, grid, block, 0, s, pre, sig2, idx2, goff, n_seg, n_rows, P, rowcnt, rowptr, nnz0, col, val);
 }
 
+// ---- the individual-compatibility gate: one closure against what the graph already knows about its two poses ----------------------
+// d2 = r^T (I + A Sigma A^T)^-1 r, r (6) and A = [A_F | A_T] (6 x 12) the whitened residual and Jacobian of the Between factor
+// slide_graph_add_loop_closure(rel, from, to) would add, Sigma the inverse of the resident reduced pose system S = L L^T.  With
+// L W = A^T (a forward substitution only), A Sigma A^T = W^T W: the candidate's 6 x 6 diagonal block of the gram (k_gram_blocks).
+//
+// k_closure_gate_lin, one thread per candidate: the two poses from the device-resident estimate by slot, r and A by the text of
+// k_lin_pose_factors_body's Between branch (solver_kernels.hip): e = local(z, F^-1 T) in the graph's chart, H_F = -Ad(T^-1 F), H_T = I,
+// row a times 1 / sigma[a].  Column c0 + 6 k + a of B (nT rows, zero before the launch) gets row a of A: six entries at the from
+// pose's rows, six at the to pose's (prow: a pose's first row, null = 6 slot).  A candidate stores into its own six columns and its own
+// six residuals only, so candidates naming the same pose, or the same pair, need no atomics.
+__global__ __launch_bounds__(64) void k_closure_gate_lin(const double* __restrict__ pose_est, const int32_t* __restrict__ fslot,
+                                                         const int32_t* __restrict__ tslot, const double* __restrict__ z12,
+                                                         const double* __restrict__ sigma6, int n, int chart, const int* __restrict__ prow,
+                                                         double* __restrict__ B, int nT, double* __restrict__ r6) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  const SE3 X1 = from12(pose_est + 12 * (size_t)fslot[k]);
+  const SE3 X2 = from12(pose_est + 12 * (size_t)tslot[k]);
+  const SE3 Z = from12(z12 + 12 * (size_t)k);
+  double e[6];
+  local(Z, between(X1, X2), e, chart);
+  double Ad[36];
+  adjoint(between(X2, X1), Ad);
+  const size_t rf = prow ? (size_t)prow[fslot[k]] : 6 * (size_t)fslot[k], rt = prow ? (size_t)prow[tslot[k]] : 6 * (size_t)tslot[k];
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const double w = 1.0 / sigma6[6 * (size_t)k + a];
+    r6[6 * (size_t)k + a] = e[a] * w;
+    double* col = B + (size_t)(6 * k + a) * nT;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      col[rf + c] = -Ad[6 * a + c] * w;
+      col[rt + c] = a == c ? w : 0.0;
+    }
+  }
+}
+void launch_closure_gate_lin(const double* pose_est, const int32_t* fslot, const int32_t* tslot, const double* z12, const double* sigma6, int n,
+                             int chart, const int* prow, double* B, int nT, double* r6, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_closure_gate_lin, dim3((n + 63) / 64), dim3(64), 0, s, pose_est, fslot, tslot, z12, sigma6, n, chart, prow, B, nT, r6);
+}
+// The pair query's right-hand sides: pair k owns the columns 12 k .. 12 k + 11, the unit vectors of pose a's six rows, then pose b's
+// (B zero before the launch; one thread per column, each storing into its own column)
+__global__ __launch_bounds__(64) void k_pair_identity(const int32_t* __restrict__ aslot, const int32_t* __restrict__ bslot, int n,
+                                                      const int* __restrict__ prow, double* __restrict__ B, int nT) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= 12 * n) return;
+  const int k = e / 12, j = e - 12 * k;
+  const int p = j < 6 ? aslot[k] : bslot[k];
+  const size_t row = (prow ? (size_t)prow[p] : 6 * (size_t)p) + (j < 6 ? j : j - 6);
+  B[(size_t)e * nT + row] = 1.0;
+}
+void launch_pair_identity(const int32_t* aslot, const int32_t* bslot, int n, const int* prow, double* B, int nT, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_pair_identity, dim3((12 * n + 63) / 64), dim3(64), 0, s, aslot, bslot, n, prow, B, nT);
+}
+// k_closure_gate_finish, one wavefront per candidate (four to a workgroup): C = I + M (M: the candidate's 6 x 6 gram at 36 k),
+// symmetrised as the host's woodbury_drops symmetrises; lane 0 factors C = G G^T in registers, solves G y = r and writes
+// d2 = y^T y.  A pivot that is not > 0: flag[k] = 1 and zeros.  out: GATE_OUT doubles per candidate, [d2 | C row-major (36) | r (6)].
+__global__ __launch_bounds__(256) void k_closure_gate_finish(const double* __restrict__ M, const double* __restrict__ r6, int n,
+                                                             double* __restrict__ out, int* __restrict__ flag) {
+  __shared__ double Cs[4][36];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + wv;
+  if (k < n && lane < 36) {
+    const int a = lane / 6, b = lane - 6 * a;
+    const double* Mk = M + 36 * (size_t)k;
+    const double ab = (a == b ? 1.0 : 0.0) + Mk[6 * a + b], ba = (a == b ? 1.0 : 0.0) + Mk[6 * b + a];
+    Cs[wv][lane] = a == b ? ab : (a > b ? 0.5 * (ab + ba) : 0.5 * (ba + ab));
+  }
+  __syncthreads();
+  if (k >= n || lane != 0) return;
+  double G[6][6], y[6];
+  bool spd = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = Cs[wv][7 * j];
+#pragma unroll
+    for (int q = 0; q < j; ++q) d -= G[j][q] * G[j][q];
+    if (!(d > 0.0)) spd = false;
+    const double g = sqrt(spd ? d : 1.0);
+    G[j][j] = g;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double v = Cs[wv][6 * i + j];
+#pragma unroll
+      for (int q = 0; q < j; ++q) v -= G[i][q] * G[j][q];
+      G[i][j] = v / g;
+    }
+  }
+  double d2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double v = r6[6 * (size_t)k + i];
+#pragma unroll
+    for (int q = 0; q < i; ++q) v -= G[i][q] * y[q];
+    y[i] = v / G[i][i];
+    d2 += y[i] * y[i];
+  }
+  double* o = out + GATE_OUT * (size_t)k;
+  o[0] = spd ? d2 : 0.0;
+#pragma unroll
+  for (int e = 0; e < 36; ++e) o[1 + e] = spd ? Cs[wv][e] : 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) o[37 + e] = spd ? r6[6 * (size_t)k + e] : 0.0;
+  flag[k] = spd ? 0 : 1;
+}
+void launch_closure_gate_finish(const double* M, const double* r6, int n, double* out, int* flag, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_closure_gate_finish, dim3((n + 3) / 4), dim3(256), 0, s, M, r6, n, out, flag);
+}
+
 }  // namespace sl

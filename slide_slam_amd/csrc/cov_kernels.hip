@@ -368,6 +368,17 @@ void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const 
     hipLaunchKernelGGL(k_sub_bwd, dim3(nch), dim3(256), 0, s, S, ld, k, i1, Ld + (size_t)k * NB * NB, Winv + (size_t)k * 1024, X, nT, nrhs);
   }
 }
+// The forward launches alone: W = L^-1 B (B overwritten).  B^T S^-1 B = W^T W needs no backward pass: T launches, not 2 T.
+void launch_multi_fwd(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* W,
+                      int nrhs, hipStream_t s) {
+  const int nT = T * NB, nch = (nrhs + 15) / 16;
+  if (T <= 0 || nrhs <= 0) return;
+  for (int k = 0; k < T; ++k) {
+    const int i1 = prof ? prof[k] : T - 1;
+    hipLaunchKernelGGL(k_sub_fwd, dim3(i1 - k + 1, nch), dim3(256), 0, s, S, ld, k, Ld + (size_t)k * NB * NB, Winv + (size_t)k * 1024,
+                       B, W, nT, nrhs);
+  }
+}
 
 // M[a][b] = sum_q X[a ldx + row_q] X[b ldx + row_q] (a, b < ncol), rows = the list or (null) 0 .. nrows-1.  16x16 output tiles.
 __global__ __launch_bounds__(256) void k_gram(const double* __restrict__ X, size_t ldx, int ncol, const int* __restrict__ rows, int nrows,

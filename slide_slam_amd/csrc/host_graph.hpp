@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstring>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -381,6 +382,12 @@ class HostGraph {
   int closure_info_gain(int robot, const uint64_t* traj, int n, const double* travel, const double* sigma6, double* out3);
   int closure_info_gain_batch(int robot, int n_cand, const int32_t* off, const uint64_t* traj, const double* travel, const double* sigma6,
                               double* out3n, int32_t* status);      // candidate k = traj[off[k] .. off[k + 1]): out3n[3 k ..], status[k]
+  // the joint marginal of pose pairs and the Mahalanobis gate of a list of loop closures, both as B^T Sigma B = W^T W with L W = B
+  // (host_marginals.hip sigma_forms, closure_kernels.hip); the arguments are checked by the C ABI before these are called
+  int pose_pair_covariances(int n, const int32_t* robot_a, const uint64_t* idx_a, const int32_t* robot_b, const uint64_t* idx_b, double* out144n,
+                            int32_t* status);
+  int closure_mahalanobis(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
+                          const double* rel7, const double* sigma6, double* d2, double* C36, double* r6, int32_t* status);
   void join_batch(CholBatch* b, int slot);      // takes the graph's lock itself (never while the batch's is held the other way round)
   int dist_pass_local(double* d_buf);     // one distributed pass when every robot of the job is in this graph's batch (no host syncs inside)
   int add_point_landmark(uint64_t idx, const double* xyz);
@@ -572,6 +579,9 @@ class HostGraph {
   DevArr<int> d_midx, d_igrc;
   DevArr<double> d_igval;
   int marginal_state(const char* who) const;      // SLIDE_ERR_INVALID (+ message) unless a single-graph factorisation is resident
+  using FormFill = std::function<void(int k0, int nc, double* B, int nT)>;
+  using FormDone = std::function<int(int k0, int nc, const double* M)>;
+  int sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done);
   int ensure_sigma();
   int pose_id(int robot, uint64_t idx) const;     // the uploaded pose's index, or -1
   void robot_poses(int robot, std::vector<int>& out) const;

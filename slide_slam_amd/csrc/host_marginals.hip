@@ -629,6 +629,162 @@ int HostGraph::closure_info_gain_batch(int robot, int n_cand, const int32_t* off
   return SLIDE_OK;
 }
 
+// ---- quadratic forms B^T Sigma B of many candidates: the joint marginal of pose pairs and the closure gate -----------------------------
+// With S = L L^T the resident reduced pose system and Sigma = S^-1, B^T Sigma B = W^T W where L W = B: a forward substitution and a
+// gram, no backward pass — half the launch chain of launch_multi_solve — and symmetric positive semi-definite by construction.  The
+// ncand candidates own nk columns of B each and are cut into sweeps of whole candidates of at most SLIDE_INFO_GAIN_SWEEP_COLS
+// columns.  Per sweep: B zeroed, fill() queues the kernel that writes the candidates' columns, ONE launch_multi_fwd, the candidates'
+// nk x nk diagonal blocks of W^T W over all rows (k_gram_blocks + k_gram_reduce; nsplit from nk alone), then done() queues what
+// follows and reads back (M: nk x nk per candidate of the sweep, on the device).  As in gain_batch, a candidate's bits do not depend
+// on what else is in the list or where it stands: the substitution treats every column by itself.  (marginal_state first.)
+int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+  hipStream_t s = stream;
+  const int T = G.T, nT = T * NB, per = SLIDE_INFO_GAIN_SWEEP_COLS / nk, max_nc = std::min(ncand, per);
+  const int nsplit = gain_gram_splits(nk), nt = (nk + 15) / 16, jobs_per = nt * nt * nsplit;
+  const size_t nn = (size_t)nk * nk;
+  std::vector<GainCandDev> cd(max_nc);
+  std::vector<int4> jobs;
+  for (int i = 0; i < max_nc; ++i) {
+    cd[i] = GainCandDev{nk * i, nk, nsplit, 0, (long long)(nn * i), (long long)(nn * nsplit * i), 0};
+    for (int ta = 0; ta < nt; ++ta)
+      for (int tb = 0; tb < nt; ++tb)
+        for (int sp = 0; sp < nsplit; ++sp) jobs.push_back(make_int4(i, ta, tb, sp));
+  }
+  Scratch sc(s);
+  double* B = sc.alloc<double>((size_t)max_nc * nk * nT);
+  double* W = sc.alloc<double>((size_t)max_nc * nk * nT);
+  double* d_M = sc.alloc<double>(nn * max_nc);
+  double* d_part = sc.alloc<double>(nn * nsplit * max_nc);
+  GainCandDev* d_cd = sc.alloc<GainCandDev>(max_nc);
+  int4* d_jobs = sc.alloc<int4>(jobs.size());
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_cd, cd));
+  SL_HIP(sc.upload(d_jobs, jobs));
+  const bool dense = h_prof.size() != (size_t)T;
+  for (int k0 = 0; k0 < ncand; k0 += per) {
+    const int nc = std::min(per, ncand - k0), ncol = nc * nk;
+    SL_HIP(hipMemsetAsync(B, 0, (size_t)ncol * nT * sizeof(double), s));
+    fill(k0, nc, B, nT);
+    launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), B, W, ncol, s);
+    launch_gram_blocks(W, nT, nullptr, nT, d_cd, nc, d_jobs, nc * jobs_per, d_part, d_M, s);
+    SL_HIP(hipGetLastError());
+    const int rc = done(k0, nc, d_M);
+    if (rc != SLIDE_OK) return rc;
+  }
+  return SLIDE_OK;
+}
+// Marginals::jointMarginalCovariance of n pose pairs: out144n[144 k ..] the 12 x 12 row-major block [[Saa, Sab], [Sba, Sbb]] of pair k
+// (pose a's six coordinates, then b's; tangent order [rot, trans]).  B: the unit columns of the two poses' rows, so W^T W is the block
+// itself.  status[k] (or null): SLIDE_MISSING for a pose the graph does not hold, SLIDE_ERR_INVALID when a and b are one pose; zeros
+// then.  Whole-call refusals as pose_covariances, nothing written.  The arguments were checked by the caller (capi.hip).
+int HostGraph::pose_pair_covariances(int n, const int32_t* robot_a, const uint64_t* idx_a, const int32_t* robot_b, const uint64_t* idx_b,
+                                     double* out144n, int32_t* status) {
+  int rc = marginal_state("get_pose_pair_covariances");
+  if (rc != SLIDE_OK) return rc;
+  std::vector<int32_t> as, bs;
+  std::vector<int> ids;
+  for (int k = 0; k < n; ++k) {
+    for (int e = 0; e < 144; ++e) out144n[144 * (size_t)k + e] = 0.0;
+    const int a = pose_id(robot_a[k], idx_a[k]), b = pose_id(robot_b[k], idx_b[k]);
+    const int st = a < 0 || b < 0 ? SLIDE_MISSING : a == b ? SLIDE_ERR_INVALID : SLIDE_OK;
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    as.push_back(a); bs.push_back(b); ids.push_back(k);
+  }
+  if (ids.empty()) return SLIDE_OK;
+  hipStream_t s = stream;
+  Scratch sc(s);
+  int32_t* d_as = sc.alloc<int32_t>(as.size());
+  int32_t* d_bs = sc.alloc<int32_t>(bs.size());
+  if (!sc.ok()) { g_last_error = "get_pose_pair_covariances: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_as, as));
+  SL_HIP(sc.upload(d_bs, bs));
+  std::vector<double> h;
+  return sigma_forms(
+      "get_pose_pair_covariances", (int)ids.size(), 12,
+      [&](int k0, int nc, double* B, int nT) { launch_pair_identity(d_as + k0, d_bs + k0, nc, nullptr, B, nT, s); },
+      [&](int k0, int nc, const double* M) -> int {
+        h.resize(144 * (size_t)nc);
+        SL_HIP(hipMemcpyAsync(h.data(), M, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < nc; ++i) std::copy(h.begin() + 144 * (size_t)i, h.begin() + 144 * (size_t)(i + 1), out144n + 144 * (size_t)ids[k0 + i]);
+        return SLIDE_OK;
+      });
+}
+// The individual-compatibility test of L closures against the resident factor: closure k is the Between factor
+// add_loop_closure(rel7_k, from, to) with sigmas sigma6_k would add, r_k / A_k its whitened residual and Jacobian at the current
+// estimate of its two poses (k_closure_gate_lin: the solver's own Between text under the graph's chart), C_k = I + A_k Sigma A_k^T the
+// innovation covariance in whitened units (B = A_k^T in sigma_forms), d2_k = r_k^T C_k^-1 r_k (k_closure_gate_finish): chi-square
+// with 6 degrees of freedom for a true closure not yet added.  No threshold is applied here.  C36 / r6 / status may be null.
+// status[k]: SLIDE_MISSING (a pose the graph does not hold), SLIDE_ERR_INVALID (from and to are one pose), SLIDE_ERR_NOT_SPD (C_k);
+// zeros in its outputs then.  Per sweep of 64 closures: one linearisation launch, T substitution launches, two gram launches, one
+// finish launch, one read-back.  Whole-call refusals as pose_covariances, nothing written.  Arguments checked by the caller.
+int HostGraph::closure_mahalanobis(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
+                                   const double* rel7, const double* sigma6, double* d2, double* C36, double* r6, int32_t* status) {
+  int rc = marginal_state("closure_mahalanobis");
+  if (rc != SLIDE_OK) return rc;
+  std::vector<int32_t> fs, ts;
+  std::vector<double> z, sg;
+  std::vector<int> ids;
+  for (int k = 0; k < L; ++k) {
+    d2[k] = 0.0;
+    for (int e = 0; C36 && e < 36; ++e) C36[36 * (size_t)k + e] = 0.0;
+    for (int e = 0; r6 && e < 6; ++e) r6[6 * (size_t)k + e] = 0.0;
+    const int a = pose_id(from_robot[k], from_idx[k]), b = pose_id(to_robot[k], to_idx[k]);
+    const int st = a < 0 || b < 0 ? SLIDE_MISSING : a == b ? SLIDE_ERR_INVALID : SLIDE_OK;
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    double z12[12];
+    to12(from7(rel7 + 7 * (size_t)k), z12);
+    fs.push_back(a); ts.push_back(b); ids.push_back(k);
+    z.insert(z.end(), z12, z12 + 12);
+    sg.insert(sg.end(), sigma6 + 6 * (size_t)k, sigma6 + 6 * (size_t)k + 6);
+  }
+  if (ids.empty()) return SLIDE_OK;
+  hipStream_t s = stream;
+  const int m = (int)ids.size(), max_nc = std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / 6);
+  Scratch sc(s);
+  int32_t* d_fs = sc.alloc<int32_t>(m);
+  int32_t* d_ts = sc.alloc<int32_t>(m);
+  double* d_z = sc.alloc<double>(12 * (size_t)m);
+  double* d_sg = sc.alloc<double>(6 * (size_t)m);
+  double* d_r = sc.alloc<double>(6 * (size_t)m);
+  double* d_out = sc.alloc<double>(GATE_OUT * (size_t)max_nc);
+  int* d_flag = sc.alloc<int>(max_nc);
+  if (!sc.ok()) { g_last_error = "closure_mahalanobis: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_fs, fs));
+  SL_HIP(sc.upload(d_ts, ts));
+  SL_HIP(sc.upload(d_z, z));
+  SL_HIP(sc.upload(d_sg, sg));
+  std::vector<double> h(GATE_OUT * (size_t)max_nc);
+  std::vector<int> hflag(max_nc);
+  return sigma_forms(
+      "closure_mahalanobis", m, 6,
+      [&](int k0, int nc, double* B, int nT) {
+        launch_closure_gate_lin(d_pose_est.d, d_fs + k0, d_ts + k0, d_z + 12 * (size_t)k0, d_sg + 6 * (size_t)k0, nc, G.chart, nullptr, B, nT,
+                                d_r + 6 * (size_t)k0, s);
+      },
+      [&](int k0, int nc, const double* M) -> int {
+        launch_closure_gate_finish(M, d_r + 6 * (size_t)k0, nc, d_out, d_flag, s);
+        SL_HIP(hipGetLastError());
+        SL_HIP(hipMemcpyAsync(h.data(), d_out, GATE_OUT * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < nc; ++i) {
+          const size_t k = (size_t)ids[k0 + i];
+          if (hflag[i]) {
+            if (status) status[k] = SLIDE_ERR_NOT_SPD;
+            continue;
+          }
+          const double* o = h.data() + GATE_OUT * (size_t)i;
+          d2[k] = o[0];
+          if (C36) std::copy(o + 1, o + 37, C36 + 36 * k);
+          if (r6) std::copy(o + 37, o + 43, r6 + 6 * k);
+        }
+        return SLIDE_OK;
+      });
+}
+
 // ---- marginals on the joint graph: the selected inverse over the exact joint pass's factor (joint_cov_kernels.hip) -------
 // What the pass leaves behind and this reads (nothing of it is scratch of the pass): every robot's band factor in S (segments' diagonal
 // blocks in Ld / Winv, their border rows W^T below the band), the windows' second-level factor in bord (Ld2 / Winv2), the separator's

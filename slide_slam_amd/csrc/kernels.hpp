@@ -118,6 +118,9 @@ void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, co
                                  const int* prow = nullptr);      // out: 81 per landmark (d x d used)
 void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* X,
                         int nrhs, hipStream_t s);      // X = S^-1 B (B: nrhs columns of T * NB rows, overwritten)
+// the forward half of launch_multi_solve on its own: W = L^-1 B (S = L L^T; B overwritten), so that B^T S^-1 B = W^T W
+void launch_multi_fwd(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* W,
+                      int nrhs, hipStream_t s);
 void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nrows, double* M, hipStream_t s);
 void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s,
                        const int* prow = nullptr);      // prow: a pose's first row in U (null: 6 p)
@@ -380,5 +383,16 @@ void launch_closure_prepare(const double* fpose12, const double* tpose12, const 
 void launch_closure_csr_seg(bool emit, const double* pre, const double* sig2, const unsigned long long* idx2, const int* goff, int n_seg,
                             int n_rows, const ClosureScore& P, int* rowcnt, const int* rowptr, const long long* nnz0, int* col, double* val,
                             hipStream_t s);
+
+// The individual-compatibility gate of a list of closures and the joint marginal of pose pairs (closure_kernels.hip has the
+// invariant).  Candidate k of a sweep owns the columns 6 k .. 6 k + 5 (gate) or 12 k .. 12 k + 11 (pairs) of B (nT rows, zero before
+// the launch); fslot / tslot / aslot / bslot: rows of the device-resident estimate; prow: a pose's first row of the reduced system
+// (null: 6 slot); z12: the measured relative poses; r6: the whitened residuals (6 per candidate).
+constexpr int GATE_OUT = 43;      // per candidate: d2, C (36, row-major), r (6)
+void launch_closure_gate_lin(const double* pose_est, const int32_t* fslot, const int32_t* tslot, const double* z12, const double* sigma6, int n,
+                             int chart, const int* prow, double* B, int nT, double* r6, hipStream_t s);
+void launch_pair_identity(const int32_t* aslot, const int32_t* bslot, int n, const int* prow, double* B, int nT, hipStream_t s);
+// M: the candidates' 6 x 6 grams W_k^T W_k (36 each); out: GATE_OUT per candidate; flag[k] = 1 where I + M is not positive definite
+void launch_closure_gate_finish(const double* M, const double* r6, int n, double* out, int* flag, hipStream_t s);
 
 }  // namespace sl
