@@ -1234,14 +1234,7 @@ __global__ __launch_bounds__(256) void k_border_fill_b(const GraphDev* __restric
   if (o < 0) return;
   const int D = lm_dim(G.lm_type[l]);
   const int a = lane / D, k = lane - a * D;
-  if (lane < 6 * D) {
-    for (int q = G.lm_ptr[l]; q < G.lm_ptr[l + 1]; ++q) {
-      const int f = G.lm_fids[q];
-      const double e = G.ebuf[G.lf_eoff[f] + a * D + k];
-      double* dst = G.S + (size_t)(6 * G.lf_pose[f] + a) * G.ld + (size_t)G.T * NB + o + k;
-      *dst += e;
-    }
-  }
+  const int p0 = G.lm_ptr[l], p1 = G.lm_ptr[l + 1];
   const double* acc = G.lm_Hacc + 54 * (size_t)l;
   if (lane < D * (D + 1) / 2) {
     int r = 0;
@@ -1250,6 +1243,45 @@ __global__ __launch_bounds__(256) void k_border_fill_b(const GraphDev* __restric
     G.bord0[(size_t)(o + c) * G.ldb + o + r] = acc[lane];
   }
   if (lane < D) G.bord0[(size_t)(o + lane) * G.ldb + (size_t)G.nbr * NB] = -acc[45 + lane];
+  // The factor list 64 factors at a time: lane j resolves factor j's pose and E offset (two round trips for all of them, not three in
+  // front of every factor), the E values of eight factors are in flight together, and a factor that is the first of its pose in the
+  // list STORES 0 + e — k_border_clear_b left +0 there, so that is the very sum `+=` made — instead of reading the zero back first.
+  // Only a later factor of the same pose (or any factor past the first 64) reads, adds and writes, in list order.
+  const bool live = lane < 6 * D;
+  double* const col0 = G.S + (size_t)a * G.ld + (size_t)G.T * NB + o + k;      // + 6 * pose * ld
+  for (int base = p0; base < p1; base += 64) {
+    const int nq = min(64, p1 - base);
+    int pose = -1, eoff = 0;
+    if (lane < nq) {
+      const int f = G.lm_fids[base + lane];
+      pose = G.lf_pose[f];
+      eoff = G.lf_eoff[f];
+    }
+    bool again = base > p0;
+    for (int j = 0; j < nq; ++j) {
+      const int pj = __shfl(pose, j);
+      again = again || (j < lane && pj == pose);
+    }
+    const unsigned long long again_mask = __ballot(again);
+    for (int j0 = 0; j0 < nq; j0 += 8) {
+      double e[8];
+      int pj[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int ej = __shfl(eoff, j0 + u);
+        pj[u] = __shfl(pose, j0 + u);
+        e[u] = 0.0;
+        if (live && j0 + u < nq) e[u] = G.ebuf[ej + lane];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (!live || j0 + u >= nq) continue;
+        double* dst = col0 + (size_t)6 * pj[u] * G.ld;
+        if ((again_mask >> (j0 + u)) & 1ull) *dst += e[u];
+        else *dst = 0.0 + e[u];
+      }
+    }
+  }
 }
 // Separator poses out of the band (nested dissection of the robot's pose chain, graph_dev.hpp pose_sep).  The assembly wrote the
 // whole reduced system in pose order; for every separator pose q (one workgroup) its entries move to where a border variable lives:
@@ -1272,37 +1304,61 @@ __global__ __launch_bounds__(256) void k_sep_extract_b(const GraphDev* __restric
   const int q = s_q;
   if (q < 0) return;
   (void)max_sep;
-  const int tid = threadIdx.x, oq = G.pose_sep[q], NT = G.T * NB;
+  const int tid = threadIdx.x, oq = 6 * (int)blockIdx.x, NT = G.T * NB;      // (oq = pose_sep[q]: what the search above matched)
   const size_t ld = G.ld, ldb = G.ldb;
   const size_t brow = (size_t)G.T * NB;                      // first border row of S
   const int nb_rows = G.nbr * NB;                            // border rows (the separator poses' own rows among them: nothing there yet)
-  // (1) column strip: rows 6q .. end of the profile of q's last column's tile, plus the border rows and the right-hand side
+  // The strips of a cut pose on workgroups of their own (blockIdx.y: 0 the column strip, 1 the row strip, 2 .. the border rows in
+  // slices of 1024): every entry has one owner, so they need no order among them — one workgroup walking through all of them one
+  // after the other is a chain of global round trips.  Inside a strip a thread issues the loads of four entries before the first
+  // store (the stores may alias the next loads as far as the compiler knows: entry by entry every load waits for a round trip).
+  const int part = blockIdx.y;
+  if (part >= 2) {                                           // border rows at q's columns -> bord(row, o_c), four rows (32 bytes) per thread
+    const int n4 = nb_rows / 4, e = (part - 2) * 256 + tid;
+    if (e >= 6 * n4) return;
+    const int a = e / n4, b0 = 4 * (e - a * n4);
+    double* src = G.S + (size_t)(6 * q + a) * ld + brow + b0;
+    double* dst = G.bord0 + (size_t)(oq + a) * ldb + b0;
+    const double2 v01 = *reinterpret_cast<const double2*>(src), v23 = *reinterpret_cast<const double2*>(src + 2);
+    const double2 d01 = *reinterpret_cast<const double2*>(dst), d23 = *reinterpret_cast<const double2*>(dst + 2);
+    const double v[4] = {v01.x, v01.y, v23.x, v23.y}, d[4] = {d01.x, d01.y, d23.x, d23.y};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      // (bord0 is never cleared: an entry that was non-zero in an earlier pass is refreshed even when it is exactly zero now)
+      if (v[k] != 0.0) { dst[k] = v[k]; src[k] = 0.0; }
+      else if (b0 + k >= G.nsep * NB && d[k] != 0.0) dst[k] = 0.0;      // (rows below nsep * NB are the separator poses' own: part 0 writes them)
+    }
+    return;
+  }
+  // (1) column strip: rows 6q .. end of the profile of q's last column's tile, plus the right-hand side
   const int r_end = G.prof ? min(NT, (G.prof[(6 * q + 5) / NB] + 1) * NB) : NT;
   const int n_strip = r_end - 6 * q;
-  // the three strips of a cut pose on three workgroups (blockIdx.y): every entry has one owner, so they need no order among them —
-  // one workgroup walking through all of them one after the other is a chain of ~10 global round trips
-  const int part = blockIdx.y;
-  for (int e = tid; part == 0 && e < 6 * n_strip; e += 256) {             // (consecutive threads walk down one column of S)
-    const int a = e / n_strip, r = 6 * q + e % n_strip, c = 6 * q + a;
-    if (r < c) continue;
-    double* src = G.S + (size_t)c * ld + r;
-    const double v = *src;
-    const int pr = r / 6;
-    if (pr < G.P) {
-      const int orr = G.pose_sep[pr];
-      if (orr >= 0) G.bord0[(size_t)(oq + a) * ldb + orr + (r - 6 * pr)] = v;                     // separator x separator (o_r >= o_c: lower)
-      else G.S[(size_t)r * ld + brow + oq + a] = v;                                             // segment behind: border row of q, column r
+  for (int e0 = tid; part == 0 && e0 < 6 * n_strip; e0 += 4 * 256) {      // (consecutive threads walk down one column of S)
+    double v[4];
+    int orr[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 256 * u;
+      v[u] = 0.0; orr[u] = -1;
+      if (e >= 6 * n_strip) continue;
+      const int a = e / n_strip, r = 6 * q + e % n_strip, c = 6 * q + a;
+      if (r < c) continue;
+      v[u] = G.S[(size_t)c * ld + r];
+      if (r / 6 < G.P) orr[u] = G.pose_sep[r / 6];
     }
-    *src = (r == c) ? 1.0 : 0.0;
-  }
-  for (int e = tid; part == 1 && e < 6 * nb_rows; e += 256) {             // border rows at q's columns -> bord(row, o_c)
-    const int a = e / nb_rows, b = e % nb_rows;
-    double* src = G.S + (size_t)(6 * q + a) * ld + brow + b;
-    const double v = *src;
-    // (bord0 is never cleared: an entry that was non-zero in an earlier pass is refreshed even when it is exactly zero now)
-    double* dst = G.bord0 + (size_t)(oq + a) * ldb + b;
-    if (v != 0.0) { *dst = v; *src = 0.0; }
-    else if (b >= G.nsep * NB && *dst != 0.0) *dst = 0.0;      // (rows below nsep * NB are the separator poses' own: part 0 writes them)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 256 * u;
+      if (e >= 6 * n_strip) continue;
+      const int a = e / n_strip, r = 6 * q + e % n_strip, c = 6 * q + a;
+      if (r < c) continue;
+      const int pr = r / 6;
+      if (pr < G.P) {
+        if (orr[u] >= 0) G.bord0[(size_t)(oq + a) * ldb + orr[u] + (r - 6 * pr)] = v[u];          // separator x separator (o_r >= o_c: lower)
+        else G.S[(size_t)r * ld + brow + oq + a] = v[u];                                        // segment behind: border row of q, column r
+      }
+      G.S[(size_t)c * ld + r] = (r == c) ? 1.0 : 0.0;
+    }
   }
   if (part == 0 && tid < 6) {                                // right-hand side
     double* src = G.S + (size_t)(6 * q + tid) * ld + brow + (size_t)G.nbr * NB;
@@ -1313,13 +1369,28 @@ __global__ __launch_bounds__(256) void k_sep_extract_b(const GraphDev* __restric
     for (int p = G.nsep_dim + tid; p < G.nsep * NB; p += 256) G.bord0[(size_t)p * ldb + p] = 1.0;
   // (2) row strip: columns from the first column the profile lets reach q's rows, poses that are no separator poses only
   const int c_beg = G.first ? G.first[(6 * q) / NB] * NB : 0;
-  for (int e = tid; part == 2 && e < 6 * (6 * q - c_beg); e += 256) {
-    const int a = e % 6, c = c_beg + e / 6, r = 6 * q + a;
-    const int pc = c / 6;
-    if (pc >= G.P || G.pose_sep[pc] >= 0) continue;
-    double* src = G.S + (size_t)c * ld + r;
-    G.S[(size_t)c * ld + brow + oq + a] = *src;                                                  // border row of q, column c
-    *src = 0.0;
+  const int n_row = 6 * (6 * q - c_beg);
+  for (int e0 = tid; part == 1 && e0 < n_row; e0 += 4 * 256) {
+    double v[4];
+    int oc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 256 * u;
+      v[u] = 0.0; oc[u] = 0;                                 // (oc >= 0: nothing to move)
+      if (e >= n_row) continue;
+      const int a = e % 6, c = c_beg + e / 6;
+      if (c / 6 >= G.P) continue;
+      oc[u] = G.pose_sep[c / 6];
+      v[u] = G.S[(size_t)c * ld + 6 * q + a];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 256 * u;
+      if (e >= n_row || oc[u] >= 0) continue;
+      const int a = e % 6, c = c_beg + e / 6;
+      G.S[(size_t)c * ld + brow + oq + a] = v[u];                                               // border row of q, column c
+      G.S[(size_t)c * ld + 6 * q + a] = 0.0;
+    }
   }
 }
 // the separator poses' solution (the second level's) into the band's solution vector, which holds zeros there
@@ -1387,61 +1458,126 @@ struct SepGatherArgs {
   // added, exactly as two ranks owning a leaf each would (enqueue_arrow); split_col < 0: off
   int split_col; unsigned mask_b; double* sys2; int ld2; double* bord2;
 };
-constexpr int SEP_GATHER_COLS = 8;      // columns per workgroup (a workgroup per column: 62 000 workgroups, half of them above the diagonal)
+// One workgroup per (tile row, strip of SEP_GATHER_COLS columns) of the lower triangle; tile row Ts + nl is the right-hand-side row.
+//  - the rows' and columns' coordinates in every candidate robot's border block are resolved ONCE per workgroup into LDS (one round
+//    trip), the candidates from the two tiles' masks — a strip no robot holds both tiles of only stores zeros / the unit diagonal;
+//  - a thread owns one row and four columns and issues all of its value loads of a round (a pair of robots x four columns, both
+//    orders) before the first sum;
+//  - a robot's block holds its lower triangle only: where the robot's local order of a pair is the reverse of the separator's
+//    (lr < lc — the borders are ordered by first observing key frame, so about half of the pairs of different landmarks), the value is
+//    at lr * ldb + lc and lanes along the rows would read addresses ldb apart.  Those values are fetched with the lanes along the
+//    COLUMNS (16 lanes = one 128-byte line where the columns are neighbours in the robot's order too) and handed over through LDS.
+constexpr int SEP_GATHER_COLS = 16;      // columns per workgroup (divides NB: a strip lies in one tile column)
 __global__ __launch_bounds__(256) void k_sep_gather(SepGatherArgs A) {
   const SepLayout& Y = A.Y;
-  const int vr = blockIdx.x * 256 + threadIdx.x;
-  const int NL = Y.Ts * NB, NT = (Y.Ts + Y.nl) * NB;
-  if (vr > NT) return;
-  const bool rhs = vr == NT;
-  const int gr = rhs ? 0 : (vr < NL ? (vr < Y.ms ? vr : -1) : (vr - NL < Y.lam ? Y.ms + vr - NL : -1));
-  const unsigned rmask = A.tmask ? (rhs ? ~0u : (unsigned)A.tmask[vr / NB]) : ~0u;
-  // this row's coordinate in every robot's border block (the same for all columns of the workgroup: loaded once, not once per column
-  // in front of the value it addresses)
-  int lrow[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    lrow[r] = -1;
-    if (r < A.n && gr >= 0 && ((rmask >> r) & 1u) && ((A.robot_mask >> r) & 1u)) lrow[r] = rhs ? A.nbr[r] * NB : A.map[r][gr];
-  }
-#pragma unroll 2
-  for (int vc = blockIdx.y * SEP_GATHER_COLS; vc < (int)(blockIdx.y + 1) * SEP_GATHER_COLS && vc < NT; ++vc) {
-    if (!rhs && vr < vc) continue;
-    // (the block between the leaves of a dissected layout: nobody ever writes it, in either layout — zero since allocation)
-    if (sep_packed_hole(vr, vc, Y.hTa, Y.hTL)) continue;
-    // separator coordinate of a virtual index, or -1 on the padding
-    const int gc = vc < NL ? (vc < Y.ms ? vc : -1) : (vc - NL < Y.lam ? Y.ms + vc - NL : -1);
-    double s = 0.0, s2 = 0.0;
-    if (gc < 0 || gr < 0) {
-      s = (vr == vc && vc < NL) ? 1.0 : 0.0;      // unit diagonal on the landmark padding (the lambda padding is set by k_lam_prepare)
-    } else if (vr == vc && ((vc >= Y.gap[0] && vc < Y.gap[1]) || (vc >= Y.gap[2] && vc < Y.gap[3]))) {
-      s = A.packed ? 0.0 : 1.0;                   // padding between the blocks of a dissected layout (a packed partial sum gets it in k_sep_unpack)
-    } else {
-      // only the robots that hold coordinates of BOTH tiles can contribute (two or three of eight on a grid of robot cells)
-      // The robots' contributions are added along a BINARY TREE over the robot index — ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) — whatever
-      // the number of robots on this GPU: a rank that holds an aligned power-of-two range of the job's robots computes a subtree of the
-      // same tree, the pairwise exchanges between the ranks (distributed.py) its upper levels, and the job's sums are bit for bit the same
-      // at 1, 2, 4 and 8 ranks (an absent contribution is an exact zero; SURVEY 7, hard part 5).  A.first_robot masks the range to sum.
-      const unsigned cand = (A.tmask ? (unsigned)A.tmask[vc / NB] & rmask : ~0u) & A.robot_mask;
-      double v[8];
+  const int tr = blockIdx.x, c0 = blockIdx.y * SEP_GATHER_COLS, tc = c0 / NB;
+  const int Tt = Y.Ts + Y.nl, NL = Y.Ts * NB, NT = Tt * NB;
+  if (tr < tc) return;                                             // above the diagonal (the right-hand-side row tr == Tt never is)
+  // (the block between the leaves of a dissected layout: nobody ever writes it, in either layout — zero since allocation)
+  if (tc < Y.hTa && tr >= Y.hTa && tr < Y.hTL) return;
+  const bool rhs = tr == Tt;
+  const int tid = threadIdx.x;
+  __shared__ int s_l[8][NB + SEP_GATHER_COLS];                     // [robot][row of the tile | column of the strip] -> border coordinate or -1
+  __shared__ double s_t[2][SEP_GATHER_COLS][NB + 1];               // the reversed pairs' values of one pair of robots
+  // only the robots that hold coordinates of BOTH tiles can contribute (two or three of eight on a grid of robot cells)
+  unsigned cand = A.robot_mask & ((1u << A.n) - 1u);
+  if (A.tmask) cand &= (unsigned)A.tmask[tc] & (rhs ? ~0u : (unsigned)A.tmask[tr]);
+  // separator coordinate of a virtual index, or -1 on the padding
+  auto coord = [&](int v) { return v < NL ? (v < Y.ms ? v : -1) : (v - NL < Y.lam ? Y.ms + v - NL : -1); };
+  if (cand != 0) {
+    if (tid < NB + SEP_GATHER_COLS) {
+      const bool row = tid < NB;
+      const int g = row ? (rhs ? (tid == 0 ? 0 : -1) : coord(tr * NB + tid)) : coord(c0 + tid - NB);
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        v[r] = 0.0;
-        if (r < A.n && ((cand >> r) & 1u) && lrow[r] >= 0) {
-          const int lc = A.map[r][gc];
-          const int lr = lrow[r];
-          if (lc >= 0) v[r] = A.bord[r][(size_t)min(lr, lc) * A.ldb[r] + max(lr, lc)];      // (lower triangle of the robot's block)
+        int l = -1;
+        if (((cand >> r) & 1u) && g >= 0) l = (row && rhs) ? A.nbr[r] * NB : A.map[r][g];
+        s_l[r][tid] = l;
+      }
+    }
+    __syncthreads();
+  }
+  const int i = tid & (NB - 1), j0 = (tid >> 6) * 4;               // summing: row i, columns j0 .. j0 + 3 of the strip
+  const int jb = tid & (SEP_GATHER_COLS - 1), i0 = (tid >> 4) * 4; // fetching reversed pairs: column jb, rows i0 .. i0 + 3
+  const int vr = rhs ? NT : tr * NB + i;
+  const bool row_live = !rhs || i == 0;
+  // The robots' contributions are added along a BINARY TREE over the robot index — ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) — whatever
+  // the number of robots on this GPU: a rank that holds an aligned power-of-two range of the job's robots computes a subtree of the
+  // same tree, the pairwise exchanges between the ranks (distributed.py) its upper levels, and the job's sums are bit for bit the same
+  // at 1, 2, 4 and 8 ranks (an absent contribution is an exact zero; SURVEY 7, hard part 5).  A.robot_mask masks the range to sum.
+  // qa: a pair of the tree per column — (0 + 1), (2 + 3), (4 + 5), (6 + 7); qb: the same over the robots of mask_b (the split's
+  // second destination).  One pair of robots per round: with four, the hand-over buffer leaves room for four workgroups on a CU.
+  // ha, hb: the halves (0 .. 3), (4 .. 7), folded as soon as a half's second pair is there.
+  double ha[2][4], hb[2][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    double w[2][4], v[2][4];
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) v[rr][jj] = 0.0;
+    if (((cand >> (2 * p)) & 3u) != 0) {                           // (workgroup-uniform; an idle pair is 0 + 0 = 0)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const int r = 2 * p + rr;
+        const int lc = s_l[r][NB + jb];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+          const int lr = s_l[r][i0 + ii];
+          w[rr][ii] = 0.0;
+          if (lc >= 0 && lr >= 0 && lr < lc && tr * NB + i0 + ii >= c0 + jb) w[rr][ii] = A.bord[r][(size_t)lr * A.ldb[r] + lc];
         }
       }
-      if (A.split_col >= 0 && vc >= A.split_col) {
-        double va[8], vb[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { const bool b = (A.mask_b >> r) & 1u; va[r] = b ? 0.0 : v[r]; vb[r] = b ? v[r] : 0.0; }
-        s = ((va[0] + va[1]) + (va[2] + va[3])) + ((va[4] + va[5]) + (va[6] + va[7]));
-        s2 = ((vb[0] + vb[1]) + (vb[2] + vb[3])) + ((vb[4] + vb[5]) + (vb[6] + vb[7]));
-      } else {
-        s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+      for (int rr = 0; rr < 2; ++rr) {
+        const int r = 2 * p + rr;
+        const int lr = s_l[r][i];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int lc = s_l[r][NB + j0 + jj];
+          if (lc >= 0 && lr >= lc && (rhs || vr >= c0 + j0 + jj)) v[rr][jj] = A.bord[r][(size_t)lc * A.ldb[r] + lr];      // (lower triangle of the robot's block)
+        }
       }
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) s_t[rr][jb][i0 + ii] = w[rr][ii];
+      __syncthreads();
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const int r = 2 * p + rr;
+        const int lr = s_l[r][i];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int lc = s_l[r][NB + j0 + jj];
+          if (lc >= 0 && lr >= 0 && lr < lc) v[rr][jj] = s_t[rr][j0 + jj][i];
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const bool split = A.split_col >= 0 && c0 + j0 + jj >= A.split_col;
+      const bool b0 = split && ((A.mask_b >> (2 * p)) & 1u), b1 = split && ((A.mask_b >> (2 * p + 1)) & 1u);
+      const double qa = (b0 ? 0.0 : v[0][jj]) + (b1 ? 0.0 : v[1][jj]), qb = (b0 ? v[0][jj] : 0.0) + (b1 ? v[1][jj] : 0.0);
+      if (p & 1) { ha[p / 2][jj] += qa; hb[p / 2][jj] += qb; }      // (pair 2h) + (pair 2h + 1)
+      else { ha[p / 2][jj] = qa; hb[p / 2][jj] = qb; }
+    }
+  }
+  if (!row_live) return;
+  const int gr = rhs ? 0 : coord(vr);
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    const int vc = c0 + j0 + jj;
+    if (!rhs && vr < vc) continue;
+    const int gc = coord(vc);
+    double s = ha[0][jj] + ha[1][jj], s2 = hb[0][jj] + hb[1][jj];
+    if (gc < 0 || gr < 0) {
+      s = (vr == vc && vc < NL) ? 1.0 : 0.0;      // unit diagonal on the landmark padding (the lambda padding is set by k_lam_prepare)
+      s2 = 0.0;
+    } else if (vr == vc && ((vc >= Y.gap[0] && vc < Y.gap[1]) || (vc >= Y.gap[2] && vc < Y.gap[3]))) {
+      s = A.packed ? 0.0 : 1.0;                   // padding between the blocks of a dissected layout (a packed partial sum gets it in k_sep_unpack)
+      s2 = 0.0;
     }
     *sep_slot(Y, vr, vc, A.packed != 0) = s;
     if (A.split_col >= 0 && vc >= A.split_col) {      // the other half's partial sum (zero on the padding)
@@ -1817,9 +1953,11 @@ void launch_final_pack(const GraphDev& G, int pose, double* out16, hipStream_t s
 }
 
 void launch_sep_extract_batched(const GraphDev* d, const GraphDev* h, int n, const int* n_sep_poses, hipStream_t s) {
-  int mx = 0;
-  for (int i = 0; i < n; ++i) mx = std::max(mx, (h[i].arrow && h[i].pose_sep) ? n_sep_poses[i] : 0);
-  if (mx > 0) hipLaunchKernelGGL(k_sep_extract_b, dim3(mx, 3, n), dim3(256), 0, s, d, mx);
+  int mx = 0, nbr = 0;
+  for (int i = 0; i < n; ++i)
+    if (h[i].arrow && h[i].pose_sep && n_sep_poses[i] > 0) { mx = std::max(mx, n_sep_poses[i]); nbr = std::max(nbr, h[i].nbr); }
+  // blockIdx.y: the column strip, the row strip, then the six border-row strips of a cut pose in slices of 256 threads x 4 rows
+  if (mx > 0) hipLaunchKernelGGL(k_sep_extract_b, dim3(mx, 2 + (6 * nbr * (NB / 4) + 255) / 256, n), dim3(256), 0, s, d, mx);
 }
 void launch_sep_pose_scatter_batched(const GraphDev* d, const GraphDev* h, int n, double* const* xloc, hipStream_t s) {
   int P = 0;
@@ -1870,7 +2008,8 @@ void launch_sep_gather(const GraphDev* h, int n, const int* const* maps, const S
   A.robot_mask = ~0u; A.split_col = split_col; A.mask_b = mask_b; A.sys2 = sys2; A.ld2 = ld2; A.bord2 = bord2;
   for (int i = 0; i < n; ++i) { A.bord[i] = h[i].bord; A.ldb[i] = h[i].ldb; A.nbr[i] = h[i].nbr; A.map[i] = maps[i]; }
   const int NT = (Y.Ts + Y.nl) * NB;
-  if (NT > 0) hipLaunchKernelGGL(k_sep_gather, dim3((NT + 1 + 255) / 256, (NT + SEP_GATHER_COLS - 1) / SEP_GATHER_COLS), dim3(256), 0, s, A);
+  static_assert(NB % SEP_GATHER_COLS == 0 && SEP_GATHER_COLS == 16, "k_sep_gather: a strip lies in one tile column, four columns per thread");
+  if (NT > 0) hipLaunchKernelGGL(k_sep_gather, dim3(Y.Ts + Y.nl + 1, NT / SEP_GATHER_COLS), dim3(256), 0, s, A);
 }
 void launch_lam_prepare(const double* bord, int nl, int lam, double* out, hipStream_t s) {
   if (nl > 0) hipLaunchKernelGGL(k_lam_prepare, dim3((nl * NB + 1 + 255) / 256, nl * NB), dim3(256), 0, s, bord, nl, lam, out);
