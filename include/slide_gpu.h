@@ -231,6 +231,32 @@ int slide_chol_batch_closure_info_gain(slide_chol_batch_t* b, int slot, const in
 int slide_chol_batch_closure_info_gain_batch(slide_chol_batch_t* b, int slot, int n_cand, const int32_t* off, const int32_t* traj_slots,
                                              const uint64_t* traj, const double* travel, const double sigma_per_m[6], double* out4n,
                                              int32_t* status);
+/* slide_graph_get_pose_pair_covariances and slide_graph_closure_mahalanobis on the JOINT graph: the two queries those calls refuse for a
+ * graph joined to a batch, with a slot (a graph of the batch; its robot is the graph's own) where they take a robot.  The two poses may
+ * belong to different slots: the block between two robots is the one covariance the joint marginals above cannot give, and an
+ * inter-robot closure or a rendezvous candidate the one closure the single-graph gate cannot judge.  No counterpart in the reference.
+ * The pass leaves K = L D L^T with D = +I except on the lambda block of the inter-robot relative-pose factors (D = -I), so
+ * B^T K^-1 B = W^T D W with L W = B: the forward half of the substitution slide_chol_batch_closure_info_gain runs, and a signed gram
+ * that counts every coordinate of the joint system once.  Sigma is the inverse of the joint system the pass linearised; r_k and A_k are
+ * taken at the graphs' current estimates (slide_graph_get_pose12 after the pass) under the pose_chart of the from pose's graph: the
+ * linear-Gaussian model of slide_chol_batch_closure_info_gain.  Sweeps, outputs, C36 / r6 / status (each may be NULL) and a candidate's
+ * independence of the rest of the list are the single-graph calls'.
+ * Whole-call refusals (nothing written): the argument checks of the single-graph calls, made before the batch or the device is looked
+ * at (a slot outside [0, SLIDE_MAX_ROBOTS) among them), then those of slide_chol_batch_get_pose_covariances.  Per candidate, with zeros
+ * in its outputs: SLIDE_MISSING for a slot the batch does not have or a pose its graph does not hold, SLIDE_ERR_INVALID when both ends
+ * are the same pose of the same slot, SLIDE_ERR_NOT_SPD when I + A Sigma A^T has a pivot that is not positive.  n == 0 / L == 0 on a
+ * batch that would be served: SLIDE_OK.  Both run on the batch's stream outside any capture and write nothing a pass reads; the cached
+ * joint Sigma is neither used nor touched.
+ *
+ * Marginals::jointMarginalCovariance on the JOINT graph: block k = [[Saa, Sab], [Sba, Sbb]], row-major 12 x 12, pose a's six
+ * coordinates then pose b's, tangent order [rot, trans]. */
+int slide_chol_batch_get_pose_pair_covariances(slide_chol_batch_t* b, int n, const int32_t* slot_a, const uint64_t* idx_a, const int32_t* slot_b,
+                                               const uint64_t* idx_b, double* out144n, int32_t* status);
+/* Closure k is the Between factor with sigmas sigma6_k from pose (from_slot, from_idx) to (to_slot, to_idx);
+ * d2_k = r_k^T (I + A_k Sigma A_k^T)^-1 r_k, to be compared with 16.81; no threshold is applied. */
+int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot,
+                                         const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36 /* may be NULL */,
+                                         double* r6 /* may be NULL */, int32_t* status /* may be NULL */);
 /* The same pass for a job that spans GPUs, cut at its two exchanges (8 / N robots on each of N GPUs): every part is a captured
  * hipGraph replayed on the batch's stream.
  *   part 0: phase 0 of every robot + the local sum -> every local buffer holds this GPU's sum of the 54-doubles-per-slot blocks;

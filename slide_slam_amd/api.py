@@ -43,6 +43,7 @@ EXPORTS = [
     "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
     "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
+    "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis",
 ]
 
 
@@ -611,6 +612,33 @@ class CholBatch:
             slots.ctypes.data_as(vp) if slots is not None else None, traj.ctypes.data_as(vp), travel.ctypes.data_as(vp),
             sg.ctypes.data_as(vp) if sg is not None else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
         return out, status
+
+    def get_pose_pair_covariances(self, pairs):
+        """slide_chol_batch_get_pose_pair_covariances (Marginals::jointMarginalCovariance on the JOINT graph): pairs = tuples
+        (slot_a, idx_a, slot_b, idx_b); the two poses may belong to different slots.  Returns ((n, 12, 12), (n,) int32 status) as
+        SlideGraph.get_pose_pair_covariances: a pair naming a slot the batch does not have or a pose its graph does not hold
+        (SLIDE_MISSING) or one pose twice (SLIDE_ERR_INVALID) has zeros and its code.  The batch is only read."""
+        rows = [tuple(p) for p in pairs]
+        n = len(rows)
+        sa, sb = (np.array([r[j] for r in rows] + [0], np.int32) for j in (0, 2))
+        ia, ib = (np.array([r[j] for r in rows] + [0], np.uint64) for j in (1, 3))
+        out, status = np.zeros((max(n, 1), 12, 12)), np.zeros(max(n, 1), np.int32)
+        _check(self.L.slide_chol_batch_get_pose_pair_covariances(C.c_void_p(self.h), C.c_int(n), _p(sa), _p(ia), _p(sb), _p(ib), _p(out),
+                                                                 _p(status)))
+        return out[:n], status[:n]
+
+    def closure_mahalanobis(self, closures):
+        """slide_chol_batch_closure_mahalanobis: SlideGraph.closure_mahalanobis on the JOINT graph, for closures whose two ends may sit
+        in different robots' graphs.  closures: what select_closures takes, with from_robot / to_robot read as slots of the batch.
+        Returns the same dict: d2 (L) to compare with 16.81 (no threshold is applied), status (SLIDE_MISSING, SLIDE_ERR_INVALID for
+        from == to, SLIDE_ERR_NOT_SPD; zeros then), C (L, 6, 6) = I + A Sigma A^T and r (L, 6)."""
+        fs, fi, ts, ti, rel, sg = _closure_arrays(closures)
+        L = len(fs)
+        n = max(L, 1)
+        d2, Cm, r, status = np.zeros(n), np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros(n, np.int32)
+        _check(self.L.slide_chol_batch_closure_mahalanobis(C.c_void_p(self.h), C.c_int(L), _p(fs), _p(fi), _p(ts), _p(ti), _p(rel), _p(sg),
+                                                           _p(d2), _p(Cm), _p(r), _p(status)))
+        return {"d2": d2[:L], "status": status[:L], "C": Cm[:L], "r": r[:L]}
 
     def set_pcg(self, iterations, tol=0.0):
         """PCG iterations of the joint solve after the factorisations (0 = every robot's own block solve only); tol > 0: iterations

@@ -84,31 +84,39 @@ void launch_closure_csr_seg(bool emit, const double* pre, const double* sig2, co
 // row a times 1 / sigma[a].  Column c0 + 6 k + a of B (nT rows, zero before the launch) gets row a of A: six entries at the from
 // pose's rows, six at the to pose's (prow: a pose's first row, null = 6 slot).  A candidate stores into its own six columns and its own
 // six residuals only, so candidates naming the same pose, or the same pair, need no atomics.
-__global__ __launch_bounds__(64) void k_closure_gate_lin(const double* __restrict__ pose_est, const int32_t* __restrict__ fslot,
-                                                         const int32_t* __restrict__ tslot, const double* __restrict__ z12,
-                                                         const double* __restrict__ sigma6, int n, int chart, const int* __restrict__ prow,
-                                                         double* __restrict__ B, int nT, double* __restrict__ r6) {
-  const int k = blockIdx.x * 64 + threadIdx.x;
-  if (k >= n) return;
-  const SE3 X1 = from12(pose_est + 12 * (size_t)fslot[k]);
-  const SE3 X2 = from12(pose_est + 12 * (size_t)tslot[k]);
-  const SE3 Z = from12(z12 + 12 * (size_t)k);
+// (the body: candidate k's poses xf / xt, measurement z, sigmas sg; col: its first column of B, columns ld apart; rf / rt: the two poses'
+// first rows; r: its six residuals.  One text for the single-graph kernel and the joint one below.)
+__device__ __forceinline__ void closure_gate_lin_body(const double* __restrict__ xf, const double* __restrict__ xt,
+                                                      const double* __restrict__ z, const double* __restrict__ sg, int chart,
+                                                      double* __restrict__ col0, size_t ld, size_t rf, size_t rt, double* __restrict__ r) {
+  const SE3 X1 = from12(xf);
+  const SE3 X2 = from12(xt);
+  const SE3 Z = from12(z);
   double e[6];
   local(Z, between(X1, X2), e, chart);
   double Ad[36];
   adjoint(between(X2, X1), Ad);
-  const size_t rf = prow ? (size_t)prow[fslot[k]] : 6 * (size_t)fslot[k], rt = prow ? (size_t)prow[tslot[k]] : 6 * (size_t)tslot[k];
 #pragma unroll
   for (int a = 0; a < 6; ++a) {
-    const double w = 1.0 / sigma6[6 * (size_t)k + a];
-    r6[6 * (size_t)k + a] = e[a] * w;
-    double* col = B + (size_t)(6 * k + a) * nT;
+    const double w = 1.0 / sg[a];
+    r[a] = e[a] * w;
+    double* col = col0 + (size_t)a * ld;
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
       col[rf + c] = -Ad[6 * a + c] * w;
       col[rt + c] = a == c ? w : 0.0;
     }
   }
+}
+__global__ __launch_bounds__(64) void k_closure_gate_lin(const double* __restrict__ pose_est, const int32_t* __restrict__ fslot,
+                                                         const int32_t* __restrict__ tslot, const double* __restrict__ z12,
+                                                         const double* __restrict__ sigma6, int n, int chart, const int* __restrict__ prow,
+                                                         double* __restrict__ B, int nT, double* __restrict__ r6) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  const size_t rf = prow ? (size_t)prow[fslot[k]] : 6 * (size_t)fslot[k], rt = prow ? (size_t)prow[tslot[k]] : 6 * (size_t)tslot[k];
+  closure_gate_lin_body(pose_est + 12 * (size_t)fslot[k], pose_est + 12 * (size_t)tslot[k], z12 + 12 * (size_t)k, sigma6 + 6 * (size_t)k, chart,
+                        B + (size_t)(6 * k) * nT, (size_t)nT, rf, rt, r6 + 6 * (size_t)k);
 }
 void launch_closure_gate_lin(const double* pose_est, const int32_t* fslot, const int32_t* tslot, const double* z12, const double* sigma6, int n,
                              int chart, const int* prow, double* B, int nT, double* r6, hipStream_t s) {
@@ -127,6 +135,45 @@ __global__ __launch_bounds__(64) void k_pair_identity(const int32_t* __restrict_
 }
 void launch_pair_identity(const int32_t* aslot, const int32_t* bslot, int n, const int* prow, double* B, int nT, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_pair_identity, dim3((12 * n + 63) / 64), dim3(64), 0, s, aslot, bslot, n, prow, B, nT);
+}
+// The same two fills on the JOINT graph (CholBatch): the two ends of a candidate live in different graphs.  ends[k] = {graph of the
+// first pose, its pose id, graph of the second, its pose id}; tab (device memory): per graph its device-resident estimate, its prow
+// map and its system's first row in the one buffer of ld rows per column; the chart is the first pose's graph's.
+__global__ __launch_bounds__(64) void k_joint_closure_gate_lin(const JointPoseTab* __restrict__ tab, const int4* __restrict__ ends,
+                                                               const double* __restrict__ z12, const double* __restrict__ sigma6, int n,
+                                                               double* __restrict__ B, size_t ld, double* __restrict__ r6) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  const int4 e = ends[k];
+  const size_t rf = (size_t)tab->off[e.x] + tab->prow[e.x][e.y], rt = (size_t)tab->off[e.z] + tab->prow[e.z][e.w];
+  closure_gate_lin_body(tab->est[e.x] + 12 * (size_t)e.y, tab->est[e.z] + 12 * (size_t)e.w, z12 + 12 * (size_t)k, sigma6 + 6 * (size_t)k,
+                        tab->chart[e.x], B + (size_t)(6 * k) * ld, ld, rf, rt, r6 + 6 * (size_t)k);
+}
+void launch_joint_closure_gate_lin(const JointPoseTab* tab, const int4* ends, const double* z12, const double* sigma6, int n, double* B,
+                                   size_t ld, double* r6, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_joint_closure_gate_lin, dim3((n + 63) / 64), dim3(64), 0, s, tab, ends, z12, sigma6, n, B, ld, r6);
+}
+__global__ __launch_bounds__(64) void k_joint_pair_identity(const JointPoseTab* __restrict__ tab, const int4* __restrict__ ends, int n,
+                                                            double* __restrict__ B, size_t ld) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= 12 * n) return;
+  const int k = e / 12, j = e - 12 * k;
+  const int4 en = ends[k];
+  const int g = j < 6 ? en.x : en.z, p = j < 6 ? en.y : en.w;
+  const size_t row = (size_t)tab->off[g] + tab->prow[g][p] + (j < 6 ? j : j - 6);
+  B[(size_t)e * ld + row] = 1.0;
+}
+void launch_joint_pair_identity(const JointPoseTab* tab, const int4* ends, int n, double* B, size_t ld, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_joint_pair_identity, dim3((12 * n + 63) / 64), dim3(64), 0, s, tab, ends, n, B, ld);
+}
+// The signed gram of the joint factor K = L D L^T: M <- M - Mneg, M the candidates' grams over the rows with D = +I, Mneg over the
+// lambda rows (D = -I).  Entry by entry, so a block that is symmetric bit for bit stays so.
+__global__ __launch_bounds__(256) void k_gram_sub(double* __restrict__ M, const double* __restrict__ Mneg, size_t n) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) M[e] = M[e] - Mneg[e];
+}
+void launch_gram_sub(double* M, const double* Mneg, size_t n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_gram_sub, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, M, Mneg, n);
 }
 // k_closure_gate_finish, one wavefront per candidate (four to a workgroup): C = I + M (M: the candidate's 6 x 6 gram at 36 k),
 // symmetrised as the host's woodbury_drops symmetrises; lane 0 factors C = G G^T in registers, solves G y = r and writes

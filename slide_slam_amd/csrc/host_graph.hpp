@@ -149,6 +149,10 @@ struct PendFac {
 class HostGraph;
 // what an information-gain query reads back: the gram matrices, the rows of U at the trajectory's poses (for C = I + J U)
 struct GainFetched { std::vector<double> M, Urow; };
+// The callbacks of the quadratic-form queries (sigma_forms on one graph, joint_sigma_forms on a batch): fill queues the kernel that
+// writes the columns of candidates k0 .. k0 + nc - 1 into B (ld rows per column, zero before); done gets their grams on the device
+using FormFill = std::function<void(int k0, int nc, double* B, int ld)>;
+using FormDone = std::function<int(int k0, int nc, const double* M)>;
 class CholBatch {
  public:
   explicit CholBatch(int n);
@@ -208,6 +212,13 @@ class CholBatch {
   // a list of candidates in sweeps of one many-column solve each: candidate k = traj[off[k] .. off[k + 1]), out4n[4 k ..], status[k]
   int joint_closure_info_gain_batch(int slot, int n_cand, const int32_t* off, const int32_t* traj_slots, const uint64_t* traj,
                                     const double* travel, const double* sigma6, double* out4n, int32_t* status);
+  // the joint marginal of pose pairs and the Mahalanobis gate of a list of closures on the JOINT graph (HostGraph::pose_pair_covariances
+  // / closure_mahalanobis with a slot where those take a robot; the two ends may sit in different graphs): B^T K^-1 B = W^T D W with
+  // L W = B on the factor K = L D L^T of the last exact pass; the arguments are checked by the C ABI before these are called
+  int joint_pose_pair_covariances(int n, const int32_t* slot_a, const uint64_t* idx_a, const int32_t* slot_b, const uint64_t* idx_b,
+                                  double* out144n, int32_t* status);
+  int joint_closure_mahalanobis(int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot, const uint64_t* to_idx,
+                                const double* rel7, const double* sigma6, double* d2, double* C36, double* r6, int32_t* status);
 
  private:
   int n;
@@ -347,12 +358,15 @@ class CholBatch {
       std::vector<int> lst, sptr{0};
       std::vector<int2> sent;
       int max_gn = 0;
+      int n_fwd = 0;                                           // the launches before the backward half: W = L^-1 R on its own
     };
     void solve_plan(SolvePlan& p) const;
   };
   void joint_tree(JointTree& t) const;
   struct JointGain;                                // what the joint gain queries share: the tree, the solve's schedule, the grams' row lists
+  int joint_sigma_forms(const char* who, JointGain& jg, int ncand, int nk, const FormFill& fill, const FormDone& done);
   int joint_robot(int slot) const;                 // robot id of the graph's own poses
+  int joint_end(const JointGain& jg, int slot, uint64_t idx) const;      // one end of a pair or closure: its pose id in the graph of `slot`, or -1
   // the job's point landmarks: every graph's private ones (landmark ids), and of each shared slot that holds one, once, its offset in
   // the separator system
   void job_point_landmarks(std::vector<std::vector<int>>& priv, std::vector<int>& shared_off) const;
@@ -579,8 +593,6 @@ class HostGraph {
   DevArr<int> d_midx, d_igrc;
   DevArr<double> d_igval;
   int marginal_state(const char* who) const;      // SLIDE_ERR_INVALID (+ message) unless a single-graph factorisation is resident
-  using FormFill = std::function<void(int k0, int nc, double* B, int nT)>;
-  using FormDone = std::function<int(int k0, int nc, const double* M)>;
   int sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done);
   int ensure_sigma();
   int pose_id(int robot, uint64_t idx) const;     // the uploaded pose's index, or -1

@@ -637,9 +637,23 @@ int HostGraph::closure_info_gain_batch(int robot, int n_cand, const int32_t* off
 // nk x nk diagonal blocks of W^T W over all rows (k_gram_blocks + k_gram_reduce; nsplit from nk alone), then done() queues what
 // follows and reads back (M: nk x nk per candidate of the sweep, on the device).  As in gain_batch, a candidate's bits do not depend
 // on what else is in the list or where it stands: the substitution treats every column by itself.  (marginal_state first.)
-int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done) {
-  hipStream_t s = stream;
-  const int T = G.T, nT = T * NB, per = SLIDE_INFO_GAIN_SWEEP_COLS / nk, max_nc = std::min(ncand, per);
+// One driver serves this and the joint graph of a CholBatch (joint_sigma_forms) through a back end, as gain_batch does.
+//
+// What differs between one graph and the joint graph of a batch.  alloc: B and W (ld rows by the widest sweep's columns) and the back
+// end's own tables, from the query's scratch.  A sweep: B zeroed and filled by the driver, fwd (W = L^-1 B; B may be overwritten), then
+// the grams over the row list `rows` (null: 0 .. nrows - 1) and, where the factor has rows with D = -I, over rows_neg, subtracted.
+struct FormBackend {
+  hipStream_t s = nullptr;
+  size_t ld = 0;
+  double *B = nullptr, *W = nullptr;
+  const int *rows = nullptr, *rows_neg = nullptr;
+  int nrows = 0, nrows_neg = 0;
+  std::function<int(Scratch& sc, int max_ncol)> alloc;
+  std::function<void(int ncol)> fwd;
+};
+static int sigma_forms_core(const char* who, FormBackend& be, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+  hipStream_t s = be.s;
+  const int per = SLIDE_INFO_GAIN_SWEEP_COLS / nk, max_nc = std::min(ncand, per);
   const int nsplit = gain_gram_splits(nk), nt = (nk + 15) / 16, jobs_per = nt * nt * nsplit;
   const size_t nn = (size_t)nk * nk;
   std::vector<GainCandDev> cd(max_nc);
@@ -651,27 +665,45 @@ int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& f
         for (int sp = 0; sp < nsplit; ++sp) jobs.push_back(make_int4(i, ta, tb, sp));
   }
   Scratch sc(s);
-  double* B = sc.alloc<double>((size_t)max_nc * nk * nT);
-  double* W = sc.alloc<double>((size_t)max_nc * nk * nT);
+  int rc = be.alloc(sc, max_nc * nk);
   double* d_M = sc.alloc<double>(nn * max_nc);
+  double* d_Mneg = sc.alloc<double>(be.nrows_neg > 0 ? nn * max_nc : 0);
   double* d_part = sc.alloc<double>(nn * nsplit * max_nc);
   GainCandDev* d_cd = sc.alloc<GainCandDev>(max_nc);
   int4* d_jobs = sc.alloc<int4>(jobs.size());
   if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  if (rc != SLIDE_OK) return rc;
   SL_HIP(sc.upload(d_cd, cd));
   SL_HIP(sc.upload(d_jobs, jobs));
-  const bool dense = h_prof.size() != (size_t)T;
   for (int k0 = 0; k0 < ncand; k0 += per) {
     const int nc = std::min(per, ncand - k0), ncol = nc * nk;
-    SL_HIP(hipMemsetAsync(B, 0, (size_t)ncol * nT * sizeof(double), s));
-    fill(k0, nc, B, nT);
-    launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), B, W, ncol, s);
-    launch_gram_blocks(W, nT, nullptr, nT, d_cd, nc, d_jobs, nc * jobs_per, d_part, d_M, s);
+    SL_HIP(hipMemsetAsync(be.B, 0, (size_t)ncol * be.ld * sizeof(double), s));
+    fill(k0, nc, be.B, (int)be.ld);
+    be.fwd(ncol);
+    launch_gram_blocks(be.W, be.ld, be.rows, be.nrows, d_cd, nc, d_jobs, nc * jobs_per, d_part, d_M, s);
+    if (be.nrows_neg > 0) {
+      launch_gram_blocks(be.W, be.ld, be.rows_neg, be.nrows_neg, d_cd, nc, d_jobs, nc * jobs_per, d_part, d_Mneg, s);
+      launch_gram_sub(d_M, d_Mneg, nn * nc, s);
+    }
     SL_HIP(hipGetLastError());
-    const int rc = done(k0, nc, d_M);
+    rc = done(k0, nc, d_M);
     if (rc != SLIDE_OK) return rc;
   }
   return SLIDE_OK;
+}
+int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+  hipStream_t s = stream;
+  const int T = G.T, nT = T * NB;
+  const bool dense = h_prof.size() != (size_t)T;
+  FormBackend be;
+  be.s = s; be.ld = nT; be.nrows = nT;
+  be.alloc = [&](Scratch& sc, int max_ncol) -> int {
+    be.B = sc.alloc<double>((size_t)max_ncol * nT);
+    be.W = sc.alloc<double>((size_t)max_ncol * nT);
+    return SLIDE_OK;
+  };
+  be.fwd = [&](int ncol) { launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), be.B, be.W, ncol, s); };
+  return sigma_forms_core(who, be, ncand, nk, fill, done);
 }
 // Marginals::jointMarginalCovariance of n pose pairs: out144n[144 k ..] the 12 x 12 row-major block [[Saa, Sab], [Sba, Sbb]] of pair k
 // (pose a's six coordinates, then b's; tangent order [rot, trans]).  B: the unit columns of the two poses' rows, so W^T W is the block
@@ -1029,6 +1061,7 @@ void CholBatch::JointTree::solve_plan(SolvePlan& P) const {
   P.launches.push_back({2, 0, 0, 0, 0});
   leaf_steps(false);
   pull(4, false); top_steps(false);
+  P.n_fwd = (int)P.launches.size();      // (from here on: the backward half)
   pull(4, true); top_steps(true);
   pull(3, true); leaf_steps(true);
   P.launches.push_back({3, 0, 0, 0, 0});
@@ -1346,7 +1379,19 @@ struct CholBatch::JointGain {
     return SLIDE_OK;
   }
   // X = K^-1 R in S (R = J^T in Rb on entry)
-  void solve(double* X, double* Rb, int ncol, hipStream_t s) const {
+  void solve(double* X, double* Rb, int ncol, hipStream_t s) const { walk(X, Rb, ncol, s, plan.launches.size()); }
+  // The forward half alone: W = L^-1 R in the column tiles of X (a robot's rows of separator coordinates are not written: their
+  // partial sums went into the separator's R).  B^T K^-1 B = W^T D W.
+  void forward(double* X, double* Rb, int ncol, hipStream_t s) const { walk(X, Rb, ncol, s, (size_t)plan.n_fwd); }
+  // The rows of the signed gram, every coordinate of the joint system once: each robot's own columns' rows [0, Tc NB) and the
+  // separator's landmark rows (D = +I) into pos, the lambda rows (D = -I) into neg
+  void form_rows(std::vector<int>& pos, std::vector<int>& neg) const {
+    for (size_t i = 0; i < t.T.size(); ++i)
+      for (int r = 0; r < t.Tc[i] * NB; ++r) pos.push_back((int)off[1 + i] + r);
+    for (int r = 0; r < t.Tsep * NB; ++r) (r < t.Ts * NB ? pos : neg).push_back((int)off[0] + r);
+  }
+  JointPoseTab* d_tab = nullptr;             // (joint_sigma_forms: what the fill kernels address the poses by)
+  void walk(double* X, double* Rb, int ncol, hipStream_t s, size_t n_launch) const {
     const int n = (int)t.T.size();
     JMSum sA{};
     JSigGather gA{};
@@ -1356,7 +1401,8 @@ struct CholBatch::JointGain {
     }
     sA.dst = Rb + off[0]; sA.ld = (long long)N;
     gA.src = X + off[0]; gA.lds_src = (long long)N;
-    for (const JointTree::SolvePlan::Launch& L : plan.launches) {
+    for (size_t q = 0; q < n_launch; ++q) {
+      const JointTree::SolvePlan::Launch& L = plan.launches[q];
       if (L.kind == 0) launch_jms_push(d_sys, d_jobs + L.j0, L.nj, L.maxl, d_lst, ncol, L.bwd, s);
       else if (L.kind == 1) launch_jms_pull(d_sys, d_jobs + L.j0, L.nj, d_lst, ncol, L.bwd, s);
       else if (L.kind == 2) launch_jms_sum(sA, d_sptr, d_sent, t.Tsep * NB, ncol, s);
@@ -1512,5 +1558,154 @@ int CholBatch::joint_closure_info_gain_batch(int slot, int n_cand, const int32_t
     if (status) status[k] = cands[k].st;
   }
   return SLIDE_OK;
+}
+
+// ---- quadratic forms on the joint graph: the joint marginal of pose pairs and the closure gate across robots ---------------------------
+// The pass leaves K = L D L^T, D = +I but on the lambda block (factored as its negative: D = -I), so B^T K^-1 B = W^T D W with
+// L W = B: the FORWARD half of the many-right-hand-side solve (JointGain::forward — the plan's launches before the backward pull of
+// the top block) and a signed gram, every coordinate once (JointGain::form_rows).  The driver, the sweeps and the per-candidate grams
+// are sigma_forms' (sigma_forms_core): per sweep one memset of R, one fill launch, one walk of the forward half, the grams (a second
+// pair of launches and the subtraction only where the job has lambda rows), what done() queues, one read-back.  A candidate's bits
+// depend on its own columns and the row lists alone.  joint_state first, under pass_mtx; nothing the pass reads is written and the
+// cached joint Sigma is neither used nor touched.
+int CholBatch::joint_sigma_forms(const char* who, JointGain& jg, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+  hipStream_t s = master;
+  std::vector<int> pos, neg;
+  jg.form_rows(pos, neg);
+  FormBackend be;
+  be.s = s; be.ld = jg.N; be.nrows = (int)pos.size(); be.nrows_neg = (int)neg.size();
+  be.alloc = [&](Scratch& sc, int max_ncol) -> int {
+    be.W = sc.alloc<double>(jg.N * max_ncol);
+    be.B = sc.alloc<double>(jg.N * max_ncol);
+    int* d_rows = sc.alloc<int>(pos.size() + neg.size());
+    jg.d_tab = sc.alloc<JointPoseTab>(1);
+    const int rc = jg.upload(sc, be.W, be.B);
+    if (!sc.ok() || rc != SLIDE_OK) return rc;       // (the driver asks sc.ok() after its own allocations)
+    be.rows = d_rows; be.rows_neg = d_rows + pos.size();
+    SL_HIP(sc.upload(d_rows, pos));
+    SL_HIP(sc.upload(d_rows + pos.size(), neg));
+    std::vector<JointPoseTab> tab(1);
+    for (int i = 0; i < n; ++i) {
+      tab[0].est[i] = hG[i].pose_est; tab[0].prow[i] = jg.d_prow[i]; tab[0].off[i] = (long long)jg.off[1 + i]; tab[0].chart[i] = hG[i].chart;
+    }
+    SL_HIP(sc.upload(jg.d_tab, tab));
+    return SLIDE_OK;
+  };
+  be.fwd = [&](int ncol) { jg.forward(be.W, be.B, ncol, s); };
+  return sigma_forms_core(who, be, ncand, nk, fill, done);
+}
+// One end of a candidate: its pose id in the graph of `slot`, or -1 (a slot the batch does not have, a pose its graph does not hold)
+int CholBatch::joint_end(const JointGain& jg, int slot, uint64_t idx) const {
+  if (slot < 0 || slot >= n) return -1;
+  const int id = graphs[slot]->pose_id(joint_robot(slot), idx);
+  return id >= 0 && (size_t)id < jg.t.prow[slot].size() ? id : -1;
+}
+// Marginals::jointMarginalCovariance on the joint graph: HostGraph::pose_pair_covariances with (slot, pose index) for each end.  A
+// block between two robots is the one covariance the cached joint Sigma does not hold.  status[k] (or null): SLIDE_MISSING,
+// SLIDE_ERR_INVALID (one pose twice); zeros then.  Whole-call refusals: joint_state's, nothing written.
+int CholBatch::joint_pose_pair_covariances(int n_q, const int32_t* slot_a, const uint64_t* idx_a, const int32_t* slot_b, const uint64_t* idx_b,
+                                           double* out144n, int32_t* status) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("get_pose_pair_covariances", 0);
+  if (rc != SLIDE_OK) return rc;
+  JointGain jg;
+  jg.build(*this, 0);
+  std::vector<int4> ends;
+  std::vector<int> ids;
+  for (int k = 0; k < n_q; ++k) {
+    for (int e = 0; e < 144; ++e) out144n[144 * (size_t)k + e] = 0.0;
+    const int a = joint_end(jg, slot_a[k], idx_a[k]), b = joint_end(jg, slot_b[k], idx_b[k]);
+    const int st = a < 0 || b < 0 ? SLIDE_MISSING : (slot_a[k] == slot_b[k] && a == b) ? SLIDE_ERR_INVALID : SLIDE_OK;
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    ends.push_back(make_int4(slot_a[k], a, slot_b[k], b)); ids.push_back(k);
+  }
+  if (ids.empty()) return SLIDE_OK;
+  hipStream_t s = master;
+  Scratch sc(s);
+  int4* d_ends = sc.alloc<int4>(ends.size());
+  if (!sc.ok()) { g_last_error = "get_pose_pair_covariances: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_ends, ends));
+  std::vector<double> h;
+  return joint_sigma_forms(
+      "get_pose_pair_covariances", jg, (int)ids.size(), 12,
+      [&](int k0, int nc, double* B, int ld) { launch_joint_pair_identity(jg.d_tab, d_ends + k0, nc, B, (size_t)ld, s); },
+      [&](int k0, int nc, const double* M) -> int {
+        h.resize(144 * (size_t)nc);
+        SL_HIP(hipMemcpyAsync(h.data(), M, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < nc; ++i) std::copy(h.begin() + 144 * (size_t)i, h.begin() + 144 * (size_t)(i + 1), out144n + 144 * (size_t)ids[k0 + i]);
+        return SLIDE_OK;
+      });
+}
+// HostGraph::closure_mahalanobis on the joint graph: closure k is the Between factor with sigmas sigma6_k from pose (from_slot,
+// from_idx) to (to_slot, to_idx); r_k and A_k by the same device text (closure_gate_lin_body) at the two graphs' device-resident
+// estimates under the chart of the from pose's graph, Sigma the inverse of the joint system the pass linearised at pose_val — the
+// linear-Gaussian model of joint_closure_info_gain.  C_k = I + A_k Sigma A_k^T from the signed gram, d2_k by k_closure_gate_finish.
+// status[k] (or null): SLIDE_MISSING, SLIDE_ERR_INVALID (from and to are one pose), SLIDE_ERR_NOT_SPD; zeros then.
+int CholBatch::joint_closure_mahalanobis(int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot, const uint64_t* to_idx,
+                                         const double* rel7, const double* sigma6, double* d2, double* C36, double* r6, int32_t* status) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("closure_mahalanobis", 0);
+  if (rc != SLIDE_OK) return rc;
+  JointGain jg;
+  jg.build(*this, 0);
+  std::vector<int4> ends;
+  std::vector<double> z, sg;
+  std::vector<int> ids;
+  for (int k = 0; k < L; ++k) {
+    d2[k] = 0.0;
+    for (int e = 0; C36 && e < 36; ++e) C36[36 * (size_t)k + e] = 0.0;
+    for (int e = 0; r6 && e < 6; ++e) r6[6 * (size_t)k + e] = 0.0;
+    const int a = joint_end(jg, from_slot[k], from_idx[k]), b = joint_end(jg, to_slot[k], to_idx[k]);
+    const int st = a < 0 || b < 0 ? SLIDE_MISSING : (from_slot[k] == to_slot[k] && a == b) ? SLIDE_ERR_INVALID : SLIDE_OK;
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    double z12[12];
+    to12(from7(rel7 + 7 * (size_t)k), z12);
+    ends.push_back(make_int4(from_slot[k], a, to_slot[k], b)); ids.push_back(k);
+    z.insert(z.end(), z12, z12 + 12);
+    sg.insert(sg.end(), sigma6 + 6 * (size_t)k, sigma6 + 6 * (size_t)k + 6);
+  }
+  if (ids.empty()) return SLIDE_OK;
+  hipStream_t s = master;
+  const int m = (int)ids.size(), max_nc = std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / 6);
+  Scratch sc(s);
+  int4* d_ends = sc.alloc<int4>(m);
+  double* d_z = sc.alloc<double>(12 * (size_t)m);
+  double* d_sg = sc.alloc<double>(6 * (size_t)m);
+  double* d_r = sc.alloc<double>(6 * (size_t)m);
+  double* d_out = sc.alloc<double>(GATE_OUT * (size_t)max_nc);
+  int* d_flag = sc.alloc<int>(max_nc);
+  if (!sc.ok()) { g_last_error = "closure_mahalanobis: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_ends, ends));
+  SL_HIP(sc.upload(d_z, z));
+  SL_HIP(sc.upload(d_sg, sg));
+  std::vector<double> h(GATE_OUT * (size_t)max_nc);
+  std::vector<int> hflag(max_nc);
+  return joint_sigma_forms(
+      "closure_mahalanobis", jg, m, 6,
+      [&](int k0, int nc, double* B, int ld) {
+        launch_joint_closure_gate_lin(jg.d_tab, d_ends + k0, d_z + 12 * (size_t)k0, d_sg + 6 * (size_t)k0, nc, B, (size_t)ld, d_r + 6 * (size_t)k0, s);
+      },
+      [&](int k0, int nc, const double* M) -> int {
+        launch_closure_gate_finish(M, d_r + 6 * (size_t)k0, nc, d_out, d_flag, s);
+        SL_HIP(hipGetLastError());
+        SL_HIP(hipMemcpyAsync(h.data(), d_out, GATE_OUT * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < nc; ++i) {
+          const size_t k = (size_t)ids[k0 + i];
+          if (hflag[i]) {
+            if (status) status[k] = SLIDE_ERR_NOT_SPD;
+            continue;
+          }
+          const double* o = h.data() + GATE_OUT * (size_t)i;
+          d2[k] = o[0];
+          if (C36) std::copy(o + 1, o + 37, C36 + 36 * k);
+          if (r6) std::copy(o + 37, o + 43, r6 + 6 * k);
+        }
+        return SLIDE_OK;
+      });
 }
 }  // namespace sl

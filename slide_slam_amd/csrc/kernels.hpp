@@ -392,6 +392,13 @@ constexpr int GATE_OUT = 43;      // per candidate: d2, C (36, row-major), r (6)
 void launch_closure_gate_lin(const double* pose_est, const int32_t* fslot, const int32_t* tslot, const double* z12, const double* sigma6, int n,
                              int chart, const int* prow, double* B, int nT, double* r6, hipStream_t s);
 void launch_pair_identity(const int32_t* aslot, const int32_t* bslot, int n, const int* prow, double* B, int nT, hipStream_t s);
+// the same fills on the joint graph of a CholBatch: ends[k] = {graph of pose a / from, its pose id, graph of pose b / to, its pose id};
+// tab (in device memory): per graph its estimate, its prow map, its system's first row in the one buffer (ld rows per column), its chart
+struct JointPoseTab { const double* est[JSIG_ROBOTS_MAX]; const int* prow[JSIG_ROBOTS_MAX]; long long off[JSIG_ROBOTS_MAX]; int chart[JSIG_ROBOTS_MAX]; };
+void launch_joint_closure_gate_lin(const JointPoseTab* tab, const int4* ends, const double* z12, const double* sigma6, int n, double* B,
+                                   size_t ld, double* r6, hipStream_t s);
+void launch_joint_pair_identity(const JointPoseTab* tab, const int4* ends, int n, double* B, size_t ld, hipStream_t s);
+void launch_gram_sub(double* M, const double* Mneg, size_t n, hipStream_t s);      // M <- M - Mneg (the lambda rows' gram: D = -I there)
 // M: the candidates' 6 x 6 grams W_k^T W_k (36 each); out: GATE_OUT per candidate; flag[k] = 1 where I + M is not positive definite
 void launch_closure_gate_finish(const double* M, const double* r6, int n, double* out, int* flag, hipStream_t s);
 

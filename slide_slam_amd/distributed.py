@@ -691,6 +691,18 @@ class PassDriver:
         self._joint_ok()
         return self.batch.closure_info_gain_batch(robot, trajs, travels, sigma_per_m, traj_robots)
 
+    def get_pose_pair_covariances(self, pairs):
+        """((n, 12, 12), (n,) status) joint-graph marginals of pose pairs (robot_a, idx_a, robot_b, idx_b), the two poses of any two
+        robots of the job (a robot = its shard's slot): CholBatch.get_pose_pair_covariances."""
+        self._joint_ok()
+        return self.batch.get_pose_pair_covariances(pairs)
+
+    def closure_mahalanobis(self, closures):
+        """The Mahalanobis gate of a list of closures on the joint graph, from_robot / to_robot naming any two robots of the job:
+        CholBatch.closure_mahalanobis (d2 to compare with 16.81, status, C, r)."""
+        self._joint_ok()
+        return self.batch.closure_mahalanobis(closures)
+
     def one_pass(self):
         n54, n9, K = 54 * self.n_slots, 9 * self.n_slots, self.pcg_iters
         if self.batch is not None:
