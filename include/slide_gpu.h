@@ -149,8 +149,40 @@ int slide_graph_closure_info_gain_batch(slide_graph_t* g, int robot, int n_cand,
 int slide_graph_stats(slide_graph_t* g, int64_t out5[5]);
 /* Sum of squared whitened residuals of every factor at the current estimate (= 2 x gtsam::NonlinearFactorGraph::error of the graph
  * ISAM2 holds): out4 = {total, prior factors, Between factors, landmark factors}.  Commits delta into the linearisation point and
- * relinearises (the estimate itself does not move); pending factors are merged first. */
+ * relinearises (the estimate itself does not move); pending factors are merged first.  The sum is that of the system as
+ * linearised: while a robust loss is set (slide_graph_set_robust_loss) that is the reweighted system, a selected factor entering
+ * with w(s) s^2. */
 int slide_graph_chi2(slide_graph_t* g, double out4[4]);
+/* ---- Robust loss on the loop-closure and relative-measurement factors: iteratively reweighted least squares ---------------------
+ * No counterpart in the reference, whose closures are plain Between factors with sigmas of noise_model_odom_vec * 0.01
+ * (graphWrapper.cpp:55): one false closure that passed the vetting bends the whole trajectory.  GTSAM users know this as
+ * noiseModel::Robust::Create(mEstimator::{Huber, Cauchy, GemanMcClure, DCS}::Create(param), base) on exactly these factors.
+ * For a selected factor with base sigmas sigma0 (what slide_graph_add_loop_closure / _add_relative_meas chose), e its residual
+ * Local(measured, x1^-1 x2) and s = |e / sigma0|_2 at the linearisation point, the factor is linearised with sigma0 / sqrt(w(s))
+ * (Robust::WhitenSystem), w = mEstimator::weight:
+ *     kind 1 Huber          k   (default 1.345)   1 if s <= k, else k / s
+ *     kind 2 Cauchy         k   (default 0.1)     k^2 / (k^2 + s^2)
+ *     kind 3 Geman-McClure  c   (default 1.0)     (c^2 / (c^2 + s^2))^2
+ *     kind 4 DCS            Phi (default 1.0)     1 if s^2 <= Phi, else (2 Phi / (Phi + s^2))^2
+ * with w >= 1e-12.  A factor's weight is taken exactly when the factor is relinearised: an incremental slide_graph_solve that
+ * keeps a factor's linearisation keeps its weight.  Odometry factors are never reweighted.
+ * kind 0 switches the loss off (the default: launches and results are then what they are without this call); param <= 0 takes the
+ * default; class_mask bit 0 selects the loop closures, bit 1 the relative measurements.  The setting covers the factors already
+ * added and those added later, in slide_graph_gauss_newton, slide_graph_solve (incremental updates included) and so the streaming
+ * back-end (slide_backend_graph).  Every call restores the base sigmas and drops the resident factor, as slide_graph_chi2 does: the
+ * next solve relinearises everything.  Marginals, the information gain and the Mahalanobis gate read the resident factor and so
+ * describe the reweighted system.
+ * SLIDE_ERR_INVALID: kind outside 0 .. 4, a class_mask bit other than 0 and 1, a graph that has joined a batch.  Single-graph path
+ * only: while a loss is set, slide_graph_join_chol_batch, slide_graph_dist_phase and slide_graph_dist_pass_local return
+ * SLIDE_ERR_INVALID (their inter-rank relative-pose factors and captured passes do not carry the loss). */
+int slide_graph_set_robust_loss(slide_graph_t* g, int kind, double param, int class_mask);
+/* What the graph has come to think of its closures (no counterpart in the reference; in GTSAM: mEstimator::weight of each
+ * factor's whitened error): every loop-closure (kind 1) and relative-measurement (kind 2) factor in insertion order, with its keys,
+ * the weight w and the squared whitened norm s^2 of its last linearisation.  w = 1 when no loss was set then or the factor's class
+ * was not selected.  One read-back.  Any output pointer may be NULL; at most cap entries are written, *n_out is the full count.
+ * Factors added after the last solve are not listed yet.  SLIDE_ERR_INVALID before the first solve. */
+int slide_graph_get_closure_weights(slide_graph_t* g, int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx,
+                                    int32_t* kind, double* weight, double* s2, int* n_out);
 /* isam->update(fgraph, fvalues) (graph.cpp:262) throws when a factor names a key that is in neither the graph nor fvalues, and when a
  * value is inserted under a key that exists already.  Here such an entry is refused, the rest of the update is merged, and the call
  * that consumed it (solve, gauss_newton, dist_phase 0 / 20, set_shared, set_ghosts, chol_batch_pass) returns SLIDE_ERR_INVALID with the

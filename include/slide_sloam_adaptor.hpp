@@ -316,6 +316,30 @@ class SemanticFactorGraph {
     return d2;
   }
 
+  // Robust loss on the loop-closure / relative-measurement factors (slide_graph_set_robust_loss; no counterpart in the reference —
+  // GTSAM's noiseModel::Robust with mEstimator::Huber / Cauchy / GemanMcClure / DCS): kind 0 none, 1 .. 4 in that order; param <= 0:
+  // the loss's default.  Covers the factors already added and those added later.
+  void setRobustLoss(int kind, double param = 0.0, bool closures = true, bool relativeMeas = true) {
+    detail::check(slide_graph_set_robust_loss(g_, kind, param, (closures ? 1 : 0) | (relativeMeas ? 2 : 0)), "setRobustLoss");
+  }
+  // slide_graph_get_closure_weights: every loop-closure (kind 1) and relative-measurement (kind 2) factor in insertion order with
+  // the weight and squared whitened norm of its last linearisation.  Call it after solve().
+  struct ClosureWeight { size_t fromIdx, fromRobot, toIdx, toRobot; int kind; double weight, s2; };
+  std::vector<ClosureWeight> closureWeights() const {
+    int n = 0;
+    detail::check(slide_graph_get_closure_weights(g_, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n), "closureWeights");
+    std::vector<int32_t> fr(n + 1), tr(n + 1), kd(n + 1);
+    std::vector<uint64_t> fi(n + 1), ti(n + 1);
+    std::vector<double> w(n + 1), s2(n + 1);
+    int m = 0;
+    detail::check(slide_graph_get_closure_weights(g_, n, fr.data(), fi.data(), tr.data(), ti.data(), kd.data(), w.data(), s2.data(), &m),
+                  "closureWeights");
+    std::vector<ClosureWeight> out((size_t)(m < n ? m : n));
+    for (size_t k = 0; k < out.size(); ++k)
+      out[k] = ClosureWeight{(size_t)fi[k], (size_t)fr[k], (size_t)ti[k], (size_t)tr[k], (int)kd[k], w[k], s2[k]};
+    return out;
+  }
+
   slide_graph_t* handle() const { return g_; }
 
  protected:

@@ -43,6 +43,7 @@ EXPORTS = [
     "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
     "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
+    "slide_graph_set_robust_loss", "slide_graph_get_closure_weights",
     "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis",
 ]
 
@@ -426,8 +427,40 @@ class SlideGraph:
         off = np.ascontiguousarray(offsets, dtype=np.int32)
         _check(self.L.slide_graph_set_separator(self.h, _p(off), C.c_int(len(off))))
 
+    ROBUST_KINDS = {None: 0, "none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "dcs": 4}
+
+    def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
+        """slide_graph_set_robust_loss (GTSAM's noiseModel::Robust on the loop-closure / relative-measurement factors, iteratively
+        reweighted): kind = 0 / None (off), 1 / "huber", 2 / "cauchy", 3 / "geman_mcclure", 4 / "dcs"; param <= 0: the loss's default
+        (1.345, 0.1, 1.0, 1.0).  Covers factors already added and added later; the next solve relinearises everything."""
+        if kind is None or isinstance(kind, str):
+            if kind not in self.ROBUST_KINDS:
+                raise ValueError(f"robust loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
+            kind = self.ROBUST_KINDS[kind]
+        mask = (1 if closures else 0) | (2 if relative_meas else 0)
+        _check(self.L.slide_graph_set_robust_loss(self.h, C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+
+    def closure_weights(self, cap=None):
+        """slide_graph_get_closure_weights: every loop-closure (kind 1) and relative-measurement (kind 2) factor in insertion order.
+        Returns a dict of arrays: from_robot, from_idx, to_robot, to_idx, kind, weight, s2 (weight and squared whitened norm of the
+        factor's last linearisation; weight 1 where no loss applied) and n, the full count (cap: write at most that many)."""
+        n = C.c_int(0)
+        if cap is None:
+            _check(self.L.slide_graph_get_closure_weights(self.h, C.c_int(0), None, None, None, None, None, None, None, C.byref(n)))
+            cap = n.value
+        m = max(int(cap), 1)
+        fr, tr, kd = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        fi, ti = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+        w, s2 = np.zeros(m), np.zeros(m)
+        _check(self.L.slide_graph_get_closure_weights(self.h, C.c_int(int(cap)), _p(fr), _p(fi), _p(tr), _p(ti), _p(kd), _p(w), _p(s2),
+                                                      C.byref(n)))
+        k = min(int(cap), n.value)
+        return {"from_robot": fr[:k].copy(), "from_idx": fi[:k].copy(), "to_robot": tr[:k].copy(), "to_idx": ti[:k].copy(),
+                "kind": kd[:k].copy(), "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
+
     def chi2(self):
-        """Sum of squared whitened residuals at the current estimate: dict(total, prior, between, landmark)."""
+        """Sum of squared whitened residuals at the current estimate: dict(total, prior, between, landmark).  While a robust loss
+        is set: of the reweighted system."""
         out = np.zeros(4)
         _check(self.L.slide_graph_chi2(self.h, _p(out)))
         return dict(total=out[0], prior=out[1], between=out[2], landmark=out[3])

@@ -137,4 +137,16 @@ struct GraphDev {
   double bearing_sigma, cyl_sigma, numdiff_delta;
 };
 
+// Robust loss on the loop-closure / relative-measurement factors (k_robust_reweight): GraphDev::bt_sigma of a selected factor is
+// bt_sigma0 / sqrt(w), w the loss's weight at the whitened norm s of the factor's residual at its linearisation point.  A view of
+// its own, passed to the two kernels that need it: GraphDev, which every other kernel takes, stays as it is for a graph without a loss.
+struct RobustDev {
+  double* bt_sigma0;                // 6 per between factor: the sigmas the graph chose (what bt_sigma holds while no loss is set)
+  double* bt_w; double* bt_s2;      // 1 ; 1   weight and s^2 of the factor's last linearisation (selected factors only)
+  int* bt_kind;                     // 0 odometry, 1 loop closure, 2 relative measurement
+  int kind;                         // 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 DCS
+  int mask;                         // bit 0: loop closures, bit 1: relative measurements
+  double param;                     // k, k, c, Phi
+};
+
 }  // namespace sl

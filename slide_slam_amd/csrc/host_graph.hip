@@ -91,6 +91,13 @@ void Profiler::reset() {
   for (auto& m : ms) m = 0.0;
   for (auto& c : count) c = 0;
 }
+void Profiler::forget(const char* name) {
+  for (size_t i = 0; i < names.size(); ++i)
+    if (names[i] == name && recs.empty()) {
+      names.erase(names.begin() + i); ms.erase(ms.begin() + i); count.erase(count.begin() + i);
+      return;
+    }
+}
 Profiler::~Profiler() {
   for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : pool) (void)hipEventDestroy(e);
@@ -160,9 +167,10 @@ int HostGraph::set_prior(int robot, const double* pose7) {
   pend_vars.push_back(v);
   return SLIDE_OK;
 }
-int HostGraph::add_between_sigma(uint64_t k0, uint64_t k1, const SE3& rel, const double* sigma6) {
+int HostGraph::add_between_sigma(uint64_t k0, uint64_t k1, const SE3& rel, const double* sigma6, int origin) {
   PendFac f{};
   f.type = 1;
+  f.origin = origin;
   f.k0 = k0;
   f.k1 = k1;
   put12(rel, f.z);
@@ -189,7 +197,7 @@ int HostGraph::add_loop_closure(const double* rel7, uint64_t i1, int r1, uint64_
   if (!robot_ok(r1) || !robot_ok(r2)) return SLIDE_ERR_INVALID;
   double s[6];
   for (int i = 0; i < 6; ++i) s[i] = P.noise_model_odom_vec[i] * 0.01;   // noise_model_closure graphWrapper.cpp:55
-  return add_between_sigma(pose_key(r1, i1), pose_key(r2, i2), from7(rel7), s);
+  return add_between_sigma(pose_key(r1, i1), pose_key(r2, i2), from7(rel7), s, 1);
 }
 int HostGraph::add_relative_meas(const double* rel7, uint64_t i1, int r1, uint64_t i2, int r2) {
   if (!robot_ok(r1) || !robot_ok(r2)) return SLIDE_ERR_INVALID;
@@ -197,7 +205,7 @@ int HostGraph::add_relative_meas(const double* rel7, uint64_t i1, int r1, uint64
   const double dist = std::max(norm(rel.t), P.noise_floor);   // graph.cpp:251-252
   double s[6];
   for (int i = 0; i < 6; ++i) s[i] = P.noise_model_rel_meas_vec[i] * dist;
-  return add_between_sigma(pose_key(r1, i1), pose_key(r2, i2), rel, s);
+  return add_between_sigma(pose_key(r1, i1), pose_key(r2, i2), rel, s, 2);
 }
 // addRelativeMeasFactor (graph.cpp:247-258) in sharded mode: the other pose is owned by another rank and enters as the
 // constant value of ghost slot `slot` (refreshed every pass by dist_phase 20 / 21)
@@ -364,6 +372,8 @@ int HostGraph::merge_pending() {
       h_bt_j.push_back(b->second);
       h_bt_z.insert(h_bt_z.end(), f.z, f.z + 12);
       h_bt_sigma.insert(h_bt_sigma.end(), f.sigma, f.sigma + 6);
+      h_bt_kind.push_back(f.origin);
+      if (f.origin != 0) h_closures.push_back(ClosureRec{bi, f.k0, f.k1});
       pose_bt[a->second].push_back(bi << 1);
       pose_bt[b->second].push_back((bi << 1) | 1);
       csr_bt.touch(std::min(a->second, b->second));
@@ -1925,6 +1935,12 @@ int HostGraph::upload_new() {
   UP(d_bt_j, h_bt_j, up_bt, 1);
   UP(d_bt_z, h_bt_z, up_bt, 12);
   UP(d_bt_sigma, h_bt_sigma, up_bt, 6);
+  if (rb_arrays) {      // (a robust loss was set at some time: the base sigmas, the factors' origins, room for the weights)
+    UP(d_bt_sigma0, h_bt_sigma, up_rb, 6);
+    UP(d_bt_kind, h_bt_kind, up_rb, 1);
+    if (d_bt_w.ensure(std::max<size_t>(nbt, 1), up_rb, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+    if (d_bt_s2.ensure(std::max<size_t>(nbt, 1), up_rb, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  }
   if (d_bt_r.ensure(std::max<size_t>(6 * nbt, 1), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   if (d_bt_J0.ensure(std::max<size_t>(36 * nbt, 1), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   const size_t ngh = h_gh_pose.size();
@@ -2279,6 +2295,7 @@ int HostGraph::upload_new() {
   uploaded_once = true;
   up_P = Pn; up_L = Ln; up_pr = npr; up_bt = nbt; up_lf = nlf; up_gh = ngh;
   up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7;
+  if (rb_arrays) up_rb = nbt;
 
   G.P = (int)Pn; G.L = (int)Ln;
   G.pose_val = d_pose_val.d; G.pose_delta = d_pose_delta.d; G.pose_est = d_pose_est.d;
@@ -2286,6 +2303,8 @@ int HostGraph::upload_new() {
   G.n_prior = (int)npr; G.pr_pose = d_pr_pose.d; G.pr_z = d_pr_z.d; G.pr_sigma = d_pr_sigma.d; G.pr_r = d_pr_r.d;
   G.n_between = (int)nbt; G.bt_i = d_bt_i.d; G.bt_j = d_bt_j.d; G.bt_z = d_bt_z.d; G.bt_sigma = d_bt_sigma.d;
   G.bt_r = d_bt_r.d; G.bt_J0 = d_bt_J0.d;
+  RB.bt_sigma0 = d_bt_sigma0.d; RB.bt_w = d_bt_w.d; RB.bt_s2 = d_bt_s2.d; RB.bt_kind = d_bt_kind.d;      // (null until a robust loss is set)
+  RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
   G.n_ghost = (int)ngh; G.gh_pose = d_gh_pose.d; G.gh_slot = d_gh_slot.d; G.gh_first = d_gh_first.d; G.gh_z = d_gh_z.d;
   G.gh_sigma = d_gh_sigma.d; G.gh_r = d_gh_r.d; G.gh_J = d_gh_J.d;
   G.n_gslots = (int)h_gslot_pose.size(); G.ghost_val = d_ghost_val.d; G.gslot_pose = d_gslot_pose.d;
@@ -2426,6 +2445,10 @@ int HostGraph::enqueue_iteration(bool lookahead, bool skip_relin, int c_d, int w
   for (int i = 0; i < 11; ++i) id[i] = prof.id_of(kNames[i]);
 #define STAGE(i, call) do { prof.begin(id[i], s); call; prof.end(s); } while (0)
   if (!skip_relin) STAGE(0, launch_relin(G, s));
+  if (RB.kind != 0) {      // (only while a loss is set: the stage is not even named otherwise)
+    const int idr = prof.id_of("k_robust_reweight");
+    prof.begin(idr, s); launch_robust_reweight(G, RB, s); prof.end(s);
+  }
   STAGE(1, launch_linearize(G, s));
   STAGE(2, launch_landmark(G, 0, s));
   STAGE(3, launch_pose(G, s));
@@ -2488,21 +2511,24 @@ int HostGraph::run_update(double relin_thr, int iterations) {
     ~WfReset() { if (!keep) T = 0; }
   } wf_reset{wf_T};
   G.relin_thr = relin_thr;
+  note_linearisation();
   if (!status_clean) SL_HIP(hipMemsetAsync(d_status.d, 0, 8 * sizeof(int), s));      // (k_final_pack of the last update left them at zero otherwise)
   status_clean = false;
   cache_pose = -1;
   // Replaying a captured hipGraph removes the host launch cost (~250 launches + event traffic per pass) once the
   // SAME resident graph is solved again (batch Gauss-Newton, repeated solve() without new factors).
-  const bool same_as_prev = have_prev && std::memcmp(&G_prev, &G, sizeof(GraphDev)) == 0;
+  const bool same_as_prev = have_prev && std::memcmp(&G_prev, &G, sizeof(GraphDev)) == 0 && std::memcmp(&RB_prev, &RB, sizeof(RobustDev)) == 0;
+  const bool cap_ok = gexec && std::memcmp(&G_cap, &G, sizeof(GraphDev)) == 0 && std::memcmp(&RB_cap, &RB, sizeof(RobustDev)) == 0;
   static const bool env_graph = !(getenv("SLIDE_NO_GRAPH") && getenv("SLIDE_NO_GRAPH")[0] == '1');
   // two-stream look-ahead is implemented and parity-tested but measured SLOWER than the linear graph on MI355X
   // (the latency-critical diag+panel blocks queue behind the flood of update workgroups): opt-in only.
   static const bool env_look = getenv("SLIDE_LOOKAHEAD") && getenv("SLIDE_LOOKAHEAD")[0] == '1';
   const bool graph_ok = env_graph && !prof.on && G.T > 4;
-  bool use_graph = graph_ok && (iterations > 1 || same_as_prev || (gexec && std::memcmp(&G_cap, &G, sizeof(GraphDev)) == 0));
+  bool use_graph = graph_ok && (iterations > 1 || same_as_prev || cap_ok);
   G_prev = G;
+  RB_prev = RB;
   have_prev = true;
-  if (use_graph && !(gexec && std::memcmp(&G_cap, &G, sizeof(GraphDev)) == 0)) {
+  if (use_graph && !cap_ok) {
     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
     hipGraph_t graph = nullptr;
     std::lock_guard<std::mutex> cap(g_capture_mtx);
@@ -2516,7 +2542,7 @@ int HostGraph::run_update(double relin_thr, int iterations) {
       const hipError_t ei = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
       (void)hipGraphDestroy(graph);
       if (ei != hipSuccess) { gexec = nullptr; (void)hipGetLastError(); use_graph = false; }
-      else G_cap = G;
+      else { G_cap = G; RB_cap = RB; }
     }
   }
   // Incremental re-factorisation (the streaming path: one update after a few new factors).  iSAM2 re-eliminates only the part of the
@@ -2799,7 +2825,12 @@ int HostGraph::launch_phase(int phase, double* d_buf) {
   return SLIDE_OK;
 }
 
+static int refuse_robust(const char* who) {
+  g_last_error = std::string(who) + ": a robust loss is set on this graph; the sharded and joint paths do not carry it (slide_graph_set_robust_loss(g, 0, 0, 0) first)";
+  return SLIDE_ERR_INVALID;
+}
 int HostGraph::dist_phase(int phase, double* d_buf) {
+  if (rb_kind != 0) return refuse_robust("dist_phase");
   pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   hipStream_t s = stream;
   factor_valid = false;      // (the phases move linearisation points and factor into S on their own schedule)
@@ -2860,6 +2891,7 @@ int HostGraph::dist_phase(int phase, double* d_buf) {
 // One distributed Gauss-Newton pass of a graph whose batch holds EVERY robot of the job (all on this GPU): phases 0 / 1 / 2 with
 // the two exchanges as device-side sums between the batch's buffers — stream-ordered, one host synchronisation at the end.
 int HostGraph::dist_pass_local(double* d_buf) {
+  if (rb_kind != 0) return refuse_robust("dist_pass_local");
   pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   if (!batch) { g_last_error = "dist_pass_local: the graph is in no batch"; return SLIDE_ERR_INVALID; }
   wf_T = 0;      // (the pass moves the linearisation points: the last streaming solve's dp is no previous solution of the next)
@@ -2968,7 +3000,9 @@ int HostGraph::chi2(double* out4) {
   SL_HIP(hipMemsetAsync(G.pose_delta, 0, 6 * (size_t)G.P * sizeof(double), s));      // ... and delta <- 0: the next update must not apply it again
   wf_T = 0;                           // (nor may the bounded back-substitution keep a block of the last solve's dp: it is folded in now)
   if (G.L) SL_HIP(hipMemsetAsync(G.lm_delta, 0, 9 * (size_t)G.L * sizeof(double), s));
+  launch_robust_reweight(G, RB, s);       // (while a robust loss is set: the residuals summed below are the reweighted system's)
   launch_linearize(G, s);
+  note_linearisation();
   launch_estimate(G, s);
   if (d_covY.ensure(8, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   launch_chi2(G, d_covY.d, s);
@@ -2976,6 +3010,67 @@ int HostGraph::chi2(double* out4) {
   SL_HIP(hipStreamSynchronize(s));
   SL_HIP(hipGetLastError());
   factor_valid = false;
+  return SLIDE_OK;
+}
+// ---- robust loss (IRLS) on the loop-closure / relative-measurement factors ----------------------------------------------------
+int HostGraph::set_robust_loss(int kind, double param, int class_mask) {
+  if (kind < 0 || kind > 4) { g_last_error = "set_robust_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
+  if (class_mask & ~3) { g_last_error = "set_robust_loss: class_mask has bit 0 (loop closures) and bit 1 (relative measurements) only"; return SLIDE_ERR_INVALID; }
+  if (batch) { g_last_error = "set_robust_loss: the graph has joined a batch; the sharded and joint paths do not carry a robust loss"; return SLIDE_ERR_INVALID; }
+  if (!(param == param)) { g_last_error = "set_robust_loss: param is not a number"; return SLIDE_ERR_INVALID; }
+  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
+  rb_kind = kind;
+  rb_mask = kind ? class_mask : 0;
+  rb_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
+  RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
+  if (kind != 0 && !rb_arrays) { rb_arrays = true; topo_dirty = true; }      // (upload_new creates and fills the robust arrays)
+  // every sigma back to its base value; the next solve takes the weights of the new setting everywhere
+  if (up_rb > 0) SL_HIP(hipMemcpyAsync(d_bt_sigma.d, d_bt_sigma0.d, 6 * std::min(up_rb, up_bt) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  // the resident factor and the last solution belong to the system as it was weighted: as after chi2(), the next solve relinearises
+  // and re-factors everything and keeps no block of dp
+  factor_valid = false;
+  wf_T = 0;
+  pred_valid = false; status_clean = false; cache_pose = -1;
+  if (kind == 0) prof.forget("k_robust_reweight");
+  return SLIDE_OK;
+}
+static int key_robot(uint64_t key) {
+  for (int r = 0; r < SLIDE_MAX_ROBOTS; ++r)
+    if ((HostGraph::pose_key(r, 0) >> 56) == (key >> 56)) return r;
+  return -1;
+}
+int HostGraph::get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind,
+                                   double* weight, double* s2, int* n_out) {
+  if (!lin_done) { g_last_error = "get_closure_weights: nothing was linearised yet (call solve first)"; return SLIDE_ERR_INVALID; }
+  std::vector<int> idx;
+  for (const ClosureRec& c : h_closures)
+    if ((size_t)c.bt < lin_bt) idx.push_back(c.bt);      // (a factor added after the last solve has no linearisation to report)
+  const int n = (int)idx.size();
+  *n_out = n;
+  const int m = std::min(n, std::max(cap, 0));
+  if (m == 0) return SLIDE_OK;
+  hipStream_t s = stream;
+  if (d_rb_idx.ensure(m, 0, s) != SLIDE_OK || d_rb_out.ensure(2 * (size_t)m, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  SL_HIP(hipMemcpyAsync(d_rb_idx.d, idx.data(), m * sizeof(int), hipMemcpyHostToDevice, s));
+  RobustDev Rq = RB;
+  Rq.kind = lin_rb_kind; Rq.mask = lin_rb_mask;
+  launch_closure_weights(G, Rq, d_rb_idx.d, m, d_rb_out.d, s);
+  std::vector<double> out(2 * (size_t)m);
+  SL_HIP(hipMemcpyAsync(out.data(), d_rb_out.d, out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  const uint64_t low = 0x00ffffffffffffffull;
+  for (int k = 0, q = 0; k < m; ++k, ++q) {
+    while (h_closures[q].bt != idx[k]) ++q;
+    const ClosureRec& c = h_closures[q];
+    if (from_robot) from_robot[k] = key_robot(c.k0);
+    if (from_idx) from_idx[k] = c.k0 & low;
+    if (to_robot) to_robot[k] = key_robot(c.k1);
+    if (to_idx) to_idx[k] = c.k1 & low;
+    if (kind) kind[k] = h_bt_kind[c.bt];
+    if (weight) weight[k] = out[2 * (size_t)k];
+    if (s2) s2[k] = out[2 * (size_t)k + 1];
+  }
   return SLIDE_OK;
 }
 int HostGraph::get_tile_profile(int* out, int cap) {

@@ -126,6 +126,7 @@ struct Profiler {
   void end(hipStream_t s);
   void collect();     // after a stream sync
   void reset();
+  void forget(const char* name);     // drops a stage from the table (between solves: no record may be pending)
   ~Profiler();
 };
 
@@ -140,6 +141,7 @@ struct PendFac {
   uint64_t k0, k1;
   double z[15];
   double sigma[9];
+  int origin;        // between factors: 0 odometry, 1 loop closure, 2 relative measurement (GraphDev::bt_kind)
 };
 
 // The dense factor + solve of several graphs that share a GPU as ONE launch sequence (launch_chol_batch): every graph's thread
@@ -382,7 +384,7 @@ class HostGraph {
   // SemanticFactorGraph API (graph.cpp)
   int set_prior(int robot, const double* pose7);
   int add_keypose_between(int robot, uint64_t from, uint64_t to, const double* rel7, const double* est7);
-  int add_between_sigma(uint64_t k0, uint64_t k1, const SE3& rel, const double* sigma6);
+  int add_between_sigma(uint64_t k0, uint64_t k1, const SE3& rel, const double* sigma6, int origin = 0);
   int add_loop_closure(const double* rel7, uint64_t i1, int r1, uint64_t i2, int r2);
   int add_relative_meas(const double* rel7, uint64_t i1, int r1, uint64_t i2, int r2);
   int add_relative_meas_ghost(const double* rel7, uint64_t idx, int robot, int slot, bool local_first);
@@ -436,6 +438,13 @@ class HostGraph {
   void stats(int64_t* out5) const;
   int64_t rejected() const;
   int chi2(double* out4);                 // sum of squared whitened residuals at the current estimate: total, priors, betweens, landmark factors
+  // Robust loss on the loop-closure / relative-measurement factors (iteratively reweighted least squares; k_robust_reweight).
+  // kind 0: off; param <= 0: the loss's default; mask bit 0: loop closures, bit 1: relative measurements.  Single-graph path only.
+  int set_robust_loss(int kind, double param, int class_mask);
+  bool robust_on() const { return rb_kind != 0; }
+  // weight and squared whitened norm of every loop-closure / relative-measurement factor at its last linearisation, insertion order
+  int get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind, double* weight,
+                          double* s2, int* n_out);
   void set_incremental(bool on) { inc_enabled = on; }
   void incremental_stats(int64_t* out4) const { out4[0] = n_inc; out4[1] = n_full; out4[2] = last_cd; out4[3] = G.T; }
   // iSAM2's wildfire threshold on the back-substitution of a streaming update (ISAM2GaussNewtonParams::wildfireThreshold, 1e-3 in the
@@ -459,6 +468,7 @@ class HostGraph {
   std::mutex mtx;
   Profiler prof;
   GraphDev G{};
+  RobustDev RB{};                    // the robust loss's arrays and setting (null / 0 until a loss is set)
 
  private:
   int merge_pending();
@@ -498,6 +508,21 @@ class HostGraph {
   std::vector<int> h_lm_type;
   std::vector<int> h_pr_pose; std::vector<double> h_pr_z, h_pr_sigma;
   std::vector<int> h_bt_i, h_bt_j; std::vector<double> h_bt_z, h_bt_sigma;
+  // robust loss.  The device arrays it needs (bt_sigma0, bt_kind, bt_w, bt_s2) exist from the first time a loss is set on (rb_arrays):
+  // a graph that never sets one uploads and launches exactly what it did before.  h_bt_sigma is the mirror of bt_sigma0.
+  std::vector<int> h_bt_kind;
+  struct ClosureRec { int bt; uint64_t k0, k1; };
+  std::vector<ClosureRec> h_closures;          // the between factors with bt_kind != 0, insertion order
+  int rb_kind = 0, rb_mask = 0;
+  double rb_param = 0.0;
+  bool rb_arrays = false;
+  size_t up_rb = 0;                            // between factors the robust arrays hold
+  bool lin_done = false;                       // a linearisation ran; it covered lin_bt between factors under the loss lin_rb_kind / lin_rb_mask
+  size_t lin_bt = 0;
+  int lin_rb_kind = 0, lin_rb_mask = 0;
+  void note_linearisation() { lin_done = true; lin_bt = up_bt; lin_rb_kind = RB.kind; lin_rb_mask = RB.mask; }
+  DevArr<double> d_bt_sigma0, d_bt_w, d_bt_s2, d_rb_out;
+  DevArr<int> d_bt_kind, d_rb_idx;
   std::vector<int> h_gh_pose, h_gh_slot, h_gh_first; std::vector<double> h_gh_z, h_gh_sigma;   // ghost-between factors
   std::vector<int> h_gslot_pose;
   std::vector<int> h_lf_type, h_lf_pose, h_lf_lm, h_lf_slot;
@@ -609,6 +634,7 @@ class HostGraph {
   hipGraphExec_t gexec = nullptr;
   GraphDev G_cap{};
   GraphDev G_prev{};
+  RobustDev RB_cap{}, RB_prev{};      // (the captured pass bakes the robust view in as well)
   struct PhaseGraph { hipGraphExec_t exec = nullptr; GraphDev G{}; double* buf = nullptr; };
   PhaseGraph phase_graph[5];             // captured launch sequences of dist_phase 0 / 1 / 2 and of phase 1's halves (3, 4)
   int enqueue_phase(int phase, double* d_buf);

@@ -12,6 +12,8 @@ namespace sl {
 void init_solver_kernels();   // one-time kernel attributes (call outside stream capture)
 void launch_relin(const GraphDev& G, hipStream_t s);
 void launch_linearize(const GraphDev& G, hipStream_t s);
+void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s);      // ahead of launch_linearize while a robust loss is set (no launch otherwise)
+void launch_closure_weights(const GraphDev& G, const RobustDev& R, const int* idx, int n, double* out2n, hipStream_t s);   // (weight, s^2) of the listed between factors
 void launch_landmark(const GraphDev& G, int mode, hipStream_t s);      // mode: 0 fused, 1 accumulate, 2 finish from sums
 void launch_pose(const GraphDev& G, hipStream_t s);
 void launch_schur(const GraphDev& G, hipStream_t s);

@@ -2033,4 +2033,76 @@ void launch_arrow_finish_batched(const GraphDev* d, const GraphDev* h, int n, co
   hipLaunchKernelGGL(k_estimate_b, dim3(blocks_for(P + L, 256), 1, n), dim3(256), 0, s, d);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// robust loss on loop-closure / relative-measurement factors   [GTSAM noiseModel::Robust, mEstimator::{Huber, Cauchy,
+// GemanMcClure, DCS}::weight; no counterpart in the reference, whose closures are plain Between factors]
+// ------------------------------------------------------------------------------------------------
+// Iteratively reweighted least squares: one thread per between factor, ahead of the linearisation and under its skip rule, so a
+// factor's weight is taken exactly when (and at the point where) the factor is linearised.  s = |e / sigma0|_2 with e the residual
+// of k_lin_pose_factors_body; the factor is then linearised with sigma0 / sqrt(w(s)) (Robust::WhitenSystem), which is all the
+// consumers of bt_sigma (the linearisation, k_pose, k_schur) need to know.  w = 1 leaves sigma0's bits (x / 1.0 == x).  The loss
+// is uniform over the launch: the switch does not diverge.
+__device__ __forceinline__ double robust_weight(int kind, double c, double s2) {
+  switch (kind) {
+    case 1: { const double s = sqrt(s2); return s <= c ? 1.0 : c / s; }                                  // Huber
+    case 2: return (c * c) / (c * c + s2);                                                               // Cauchy
+    case 3: { const double q = (c * c) / (c * c + s2); return q * q; }                                   // Geman-McClure
+    case 4: { if (s2 <= c) return 1.0; const double q = (2.0 * c) / (c + s2); return q * q; }            // DCS
+    default: return 1.0;
+  }
+}
+__global__ __launch_bounds__(128) void k_robust_reweight(GraphDev G, RobustDev R) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= G.n_between) return;
+  const int origin = R.bt_kind[b];
+  if (origin < 1 || origin > 2 || !((R.mask >> (origin - 1)) & 1)) return;      // odometry, or a class the caller did not select
+  if (min(G.bt_i[b], G.bt_j[b]) < G.pose0) return;      // (k_lin_pose_factors_body's rule: a kept linearisation keeps its weight)
+  const SE3 X1 = from12(G.pose_val + 12 * (size_t)G.bt_i[b]);
+  const SE3 X2 = from12(G.pose_val + 12 * (size_t)G.bt_j[b]);
+  const SE3 Z = from12(G.bt_z + 12 * (size_t)b);
+  double e[6];
+  local(Z, between(X1, X2), e, G.chart);
+  double sg[6];
+  double s2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    sg[r] = R.bt_sigma0[6 * (size_t)b + r];
+    const double q = e[r] / sg[r];
+    s2 += q * q;
+  }
+  const double w = fmax(robust_weight(R.kind, R.param, s2), 1e-12);      // (the floor keeps every sigma finite)
+  const double d = sqrt(w);
+  R.bt_w[b] = w;
+  R.bt_s2[b] = s2;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) G.bt_sigma[6 * (size_t)b + r] = sg[r] / d;
+}
+// slide_graph_get_closure_weights: (weight, s^2) of the listed between factors at their last linearisation.  A factor the loss of
+// that linearisation (R.kind / R.mask as the host passes them) did not select has weight 1, and s^2 = |bt_r|^2 (its sigma is sigma0).
+__global__ __launch_bounds__(128) void k_closure_weights(GraphDev G, RobustDev R, const int* __restrict__ idx, int n, double* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int b = idx[k];
+  const int origin = R.kind != 0 ? R.bt_kind[b] : 0;      // (bt_kind exists once a loss was set)
+  if (origin >= 1 && origin <= 2 && ((R.mask >> (origin - 1)) & 1)) {
+    out[2 * k] = R.bt_w[b];
+    out[2 * k + 1] = R.bt_s2[b];
+  } else {
+    double s2 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) { const double q = G.bt_r[6 * (size_t)b + r]; s2 += q * q; }
+    out[2 * k] = 1.0;
+    out[2 * k + 1] = s2;
+  }
+}
+
+void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s) {
+  if (R.kind == 0 || G.n_between == 0) return;
+  hipLaunchKernelGGL(k_robust_reweight, dim3(blocks_for(G.n_between, 128)), dim3(128), 0, s, G, R);
+}
+void launch_closure_weights(const GraphDev& G, const RobustDev& R, const int* idx, int n, double* out2n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_closure_weights, dim3(blocks_for(n, 128)), dim3(128), 0, s, G, R, idx, n, out2n);
+}
+
 }  // namespace sl
