@@ -174,7 +174,7 @@ int slide_graph_chi2(slide_graph_t* g, double out4[4]);
  * describe the reweighted system.
  * SLIDE_ERR_INVALID: kind outside 0 .. 4, a class_mask bit other than 0 and 1, a graph that has joined a batch.  Single-graph path
  * only: while a loss is set, slide_graph_join_chol_batch, slide_graph_dist_phase and slide_graph_dist_pass_local return
- * SLIDE_ERR_INVALID (their inter-rank relative-pose factors and captured passes do not carry the loss). */
+ * SLIDE_ERR_INVALID (the un-batched sharded passes do not carry a loss; a batch carries its own: slide_chol_batch_set_robust_loss). */
 int slide_graph_set_robust_loss(slide_graph_t* g, int kind, double param, int class_mask);
 /* What the graph has come to think of its closures (no counterpart in the reference; in GTSAM: mEstimator::weight of each
  * factor's whitened error): every loop-closure (kind 1) and relative-measurement (kind 2) factor in insertion order, with its keys,
@@ -289,6 +289,36 @@ int slide_chol_batch_get_pose_pair_covariances(slide_chol_batch_t* b, int n, con
 int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot,
                                          const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36 /* may be NULL */,
                                          double* r6 /* may be NULL */, int32_t* status /* may be NULL */);
+/* ---- Robust loss on the exact joint multi-robot pass ------------------------------------------------------------------------------
+ * No counterpart in the reference (its inter-robot factors are plain Between factors, graph.cpp:247-258); GTSAM users know it as
+ * noiseModel::Robust on the closures of the joint graph.  slide_graph_set_robust_loss's rule, kinds, defaults and class_mask, as a
+ * property of the BATCH, uniform over its member graphs: before every linearisation of slide_chol_batch_pass and of a cut pass
+ * (part 0, after the ghosts are adopted) each member's loop-closure and relative-measurement Between factors are reweighted as on one
+ * graph, and so is every inter-robot relative-pose factor (slide_graph_add_relative_meas_ghost; class bit 1) at BOTH robots that
+ * hold it: both see the same two poses as bits, compute the same w, and the factor's six lambda rows enter the joint system scaled
+ * by sqrt(w) as a whole.  The step is the Gauss-Newton step of the reweighted joint graph.  kind 0 clears the loss: the pass then has
+ * the launches and gives the bits it gives without this call.  Every call restores the members' base sigmas, drops their resident
+ * factors and the batch's cached joint Sigma and captures the passes again; the joint marginals, information gain, gate and
+ * pose-pair marginals need a pass after it and then describe the reweighted system.  A graph that joins later takes the loss at the
+ * next pass; one that leaves gets its base sigmas back and carries no loss.  The per-graph calls keep refusing (a graph with a loss
+ * of its own cannot join; slide_graph_set_robust_loss refuses a member).
+ * SLIDE_ERR_INVALID: kind outside 0 .. 4, a class_mask bit other than 0 and 1, a batch with PCG passes (slide_chol_batch_set_pcg > 0;
+ * likewise slide_chol_batch_set_pcg > 0 while a loss is set: their step leaves the factors' cross block out). */
+int slide_chol_batch_set_robust_loss(slide_chol_batch_t* b, int kind, double param, int class_mask);
+/* slide_graph_get_closure_weights for the batch, after a pass (SLIDE_ERR_INVALID "pass first" before one, and after a change of the
+ * loss or of a member until the next pass): slot by slot, the member's loop-closure (kind 1) and relative-measurement (kind 2)
+ * Between factors in insertion order with ghost_id -1, then its ghost factors (kind 2) with ghost_id = their index in the job's
+ * list (slide_graph_set_ghost_ids; -1 if unnamed): the local pose stands in from_* when it is the factor's first key and in to_*
+ * otherwise, the other end as robot -1 and idx = its ghost slot.  A factor between two robots is listed once by each; the two rows
+ * carry the same w and s2 bit for bit.  w = 1 and s2 = |r|^2 where the last pass's loss did not select the factor.  One gather and
+ * one read-back for all members.  Any output pointer may be NULL; at most cap rows are written, *n_out is the full count. */
+int slide_chol_batch_get_closure_weights(slide_chol_batch_t* b, int cap, int32_t* slot, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot,
+                                         uint64_t* to_idx, int32_t* kind, int32_t* ghost_id, double* weight, double* s2, int* n_out);
+/* Measurement (no counterpart in the reference): the reweighting launch of the batch's loss alone between two events on the batch's
+ * stream; *ms: milliseconds.  The weights it writes belong to no pass (it sees the last pass's ghost values beside that pass's
+ * results): slide_chol_batch_get_closure_weights is refused until the next pass, which writes them all again.  SLIDE_ERR_INVALID
+ * without a loss. */
+int slide_chol_batch_profile_robust_reweight(slide_chol_batch_t* b, double* const* d_bufs, double* ms);
 /* The same pass for a job that spans GPUs, cut at its two exchanges (8 / N robots on each of N GPUs): every part is a captured
  * hipGraph replayed on the batch's stream.
  *   part 0: phase 0 of every robot + the local sum -> every local buffer holds this GPU's sum of the 54-doubles-per-slot blocks;

@@ -44,6 +44,7 @@ EXPORTS = [
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
     "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
     "slide_graph_set_robust_loss", "slide_graph_get_closure_weights",
+    "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
     "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis",
 ]
 
@@ -672,6 +673,46 @@ class CholBatch:
         _check(self.L.slide_chol_batch_closure_mahalanobis(C.c_void_p(self.h), C.c_int(L), _p(fs), _p(fi), _p(ts), _p(ti), _p(rel), _p(sg),
                                                            _p(d2), _p(Cm), _p(r), _p(status)))
         return {"d2": d2[:L], "status": status[:L], "C": Cm[:L], "r": r[:L]}
+
+    def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
+        """slide_chol_batch_set_robust_loss: SlideGraph.set_robust_loss's loss (same kinds, names and defaults) on the exact joint
+        pass, uniform over the member graphs: their loop closures (closures) and relative measurements, the inter-robot relative-pose
+        factors included (relative_meas).  kind 0 / None clears it.  Not with PCG passes."""
+        if kind is None or isinstance(kind, str):
+            if kind not in SlideGraph.ROBUST_KINDS:
+                raise ValueError(f"robust loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
+            kind = SlideGraph.ROBUST_KINDS[kind]
+        mask = (1 if closures else 0) | (2 if relative_meas else 0)
+        _check(self.L.slide_chol_batch_set_robust_loss(C.c_void_p(self.h), C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+
+    def closure_weights(self, cap=None):
+        """slide_chol_batch_get_closure_weights after a pass: slot by slot the member's loop-closure / relative-measurement between
+        factors in insertion order (ghost_id -1), then its ghost factors (the inter-robot relative-pose factors: ghost_id = index in
+        the job's list, the other end as robot -1 / idx = ghost slot).  Returns a dict of arrays: slot, from_robot, from_idx,
+        to_robot, to_idx, kind, ghost_id, weight, s2, and n, the full count (cap: write at most that many rows)."""
+        n = C.c_int(0)
+        h = C.c_void_p(self.h)
+        if cap is None:
+            _check(self.L.slide_chol_batch_get_closure_weights(h, C.c_int(0), None, None, None, None, None, None, None, None, None, C.byref(n)))
+            cap = n.value
+        m = max(int(cap), 1)
+        sl, fr, tr, kd, gi = (np.zeros(m, np.int32) for _ in range(5))
+        fi, ti = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+        w, s2 = np.zeros(m), np.zeros(m)
+        _check(self.L.slide_chol_batch_get_closure_weights(h, C.c_int(int(cap)), _p(sl), _p(fr), _p(fi), _p(tr), _p(ti), _p(kd), _p(gi), _p(w),
+                                                           _p(s2), C.byref(n)))
+        k = min(int(cap), n.value)
+        return {"slot": sl[:k].copy(), "from_robot": fr[:k].copy(), "from_idx": fi[:k].copy(), "to_robot": tr[:k].copy(),
+                "to_idx": ti[:k].copy(), "kind": kd[:k].copy(), "ghost_id": gi[:k].copy(), "weight": w[:k].copy(), "s2": s2[:k].copy(),
+                "n": n.value}
+
+    def profile_robust_reweight(self, buf_ptrs):
+        """slide_chol_batch_profile_robust_reweight: milliseconds of the loss's reweighting launch alone, between two events (closure_weights then
+        wants a pass first)."""
+        arr = (C.c_void_p * len(buf_ptrs))(*[int(p) for p in buf_ptrs])
+        ms = C.c_double(0.0)
+        _check(self.L.slide_chol_batch_profile_robust_reweight(C.c_void_p(self.h), arr, C.byref(ms)))
+        return ms.value
 
     def set_pcg(self, iterations, tol=0.0):
         """PCG iterations of the joint solve after the factorisations (0 = every robot's own block solve only); tol > 0: iterations

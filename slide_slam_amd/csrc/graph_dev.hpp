@@ -144,6 +144,8 @@ struct RobustDev {
   double* bt_sigma0;                // 6 per between factor: the sigmas the graph chose (what bt_sigma holds while no loss is set)
   double* bt_w; double* bt_s2;      // 1 ; 1   weight and s^2 of the factor's last linearisation (selected factors only)
   int* bt_kind;                     // 0 odometry, 1 loop closure, 2 relative measurement
+  double* gh_sigma0;                // 6 per ghost factor (batched passes: the inter-robot relative-pose factors, origin 2); GraphDev::gh_sigma
+  double* gh_w; double* gh_s2;      // 1 ; 1   is gh_sigma0 / sqrt(w) at both robots that hold the factor (k_robust_reweight_b)
   int kind;                         // 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 DCS
   int mask;                         // bit 0: loop closures, bit 1: relative measurements
   double param;                     // k, k, c, Phi

@@ -363,6 +363,7 @@ int HostGraph::merge_pending() {
       h_gh_first.push_back(f.z[12] != 0.0 ? 1 : 0);
       h_gh_z.insert(h_gh_z.end(), f.z, f.z + 12);
       h_gh_sigma.insert(h_gh_sigma.end(), f.sigma, f.sigma + 6);
+      h_gh_key.push_back(f.k0);
     } else if (f.type == 1) {
       auto b = key2pose.find(f.k1);
       if (b == key2pose.end()) { refuse("factor on a pose that is not in the graph:", f.k1); continue; }
@@ -471,6 +472,9 @@ void HostGraph::join_batch(CholBatch* b, int slot) {
     old = batch;
     batch = b;
     batch_slot = slot;
+    // (a batch's robust loss stays with the batch: the graph takes its base sigmas along, and the loss of the batch it joins — if
+    // any — at that batch's next pass)
+    if (old && old != b && rb_kind == 0) (void)restore_base_sigmas();
     factor_valid = false;   // (batched passes factor into the same S: a factor left by one is not the streaming path's)
     wf_T = 0;               // (nor is its dp the last streaming solve's solution)
     topo_dirty = true;      // (the joint-solve buffers depend on the batch's setting: upload_new looks again)
@@ -483,7 +487,7 @@ CholBatch::~CholBatch() {
   for (hipStream_t a : aux) if (a) (void)hipStreamSynchronize(a);
   for (auto& e : part_exec) if (e) (void)hipGraphExecDestroy(e);
   for (HostGraph* g : graphs)
-    if (g) { std::lock_guard<std::mutex> gl(g->mtx); if (g->batch == this) g->batch = nullptr; }
+    if (g) { std::lock_guard<std::mutex> gl(g->mtx); if (g->batch == this) { g->batch = nullptr; if (rb_kind != 0) (void)g->restore_base_sigmas(); } }
   for (hipEvent_t e : ev_in) if (e) (void)hipEventDestroy(e);
   if (ev_out) (void)hipEventDestroy(ev_out);
   if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -496,6 +500,9 @@ CholBatch::~CholBatch() {
   if (d_syrk_jobs) (void)hipFree(d_syrk_jobs);
   if (d_l2_jobs) (void)hipFree(d_l2_jobs);
   if (d_Gs) (void)hipFree(d_Gs);
+  if (d_Rs) (void)hipFree(d_Rs);
+  if (d_rb_ent) (void)hipFree(d_rb_ent);
+  if (d_rb_out) (void)hipFree(d_rb_out);
   if (d_status_all) (void)hipFree(d_status_all);
   if (ev_aux0) (void)hipEventDestroy(ev_aux0);
 
@@ -598,6 +605,12 @@ int CholBatch::prepare_pass() {
   if (!d_Gs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Gs), CHOL_BATCH_HOST_MAX * sizeof(GraphDev)));
   if (!d_status_all) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_status_all), CHOL_BATCH_HOST_MAX * 8 * sizeof(int)));
   SL_HIP(hipMemcpyAsync(d_Gs, hG.data(), n * sizeof(GraphDev), hipMemcpyHostToDevice, master));      // (not the legacy stream: other host threads may be capturing)
+  if (rb_kind != 0) {      // (the robust views beside them, only while the batch has a loss)
+    hR.resize(n);
+    for (int i = 0; i < n; ++i) hR[i] = member_view(graphs[i]);
+    if (!d_Rs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Rs), CHOL_BATCH_HOST_MAX * sizeof(RobustDev)));
+    SL_HIP(hipMemcpyAsync(d_Rs, hR.data(), n * sizeof(RobustDev), hipMemcpyHostToDevice, master));
+  }
   SL_HIP(hipStreamSynchronize(master));
   // exact joint passes: the systems the steps run on — every graph's segments (views of its S; the whole band when it is not cut) — and
   // the second-level systems of the graphs that are cut (the separator poses' block inside the border block, the rest of the border
@@ -1163,7 +1176,7 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
     launch_status_clear(d_Gs, n, master, sep_status, sep_nl > 0 ? lam_status : nullptr);
     const int rg = enqueue_ghost_refresh(d_bufs, part);
     if (rg != SLIDE_OK) return rg;
-    launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, false);      // relinearise, linearise, the robots' own per-landmark sums (nothing to pack: no exchange of them)
+    launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, false, rb_kind != 0 ? d_Rs : nullptr);      // relinearise, [reweight,] linearise, the robots' own per-landmark sums (nothing to pack: no exchange of them)
     launch_phase3_arrow_batched(d_Gs, hG.data(), n, master);         // private landmarks eliminated, reduced pose systems, borders
     {
       int nq[CHOL_BATCH_HOST_MAX];
@@ -1395,7 +1408,8 @@ int CholBatch::enqueue_pass(double* const* d_bufs, hipEvent_t e0, hipEvent_t e1,
   if (whole || part == 0) {
     launch_status_clear(d_Gs, n, master);      // (a kernel node: a captured hipMemsetAsync did not clear on replay, DESIGN §4 finding 6)
     if ((rc = enqueue_ghost_refresh(d_bufs, part)) != SLIDE_OK) return rc;
-    if (batch_p3) launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master);      // (all robots in one launch sequence: no fork / join)
+    if (!batch_p3 && rb_kind != 0) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's robust loss"; return SLIDE_ERR_INVALID; }
+    if (batch_p3) launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, true, rb_kind != 0 ? d_Rs : nullptr);      // (all robots in one launch sequence: no fork / join)
     else each(0);
     if (rc == SLIDE_OK) launch_sum_bcast(d_bufs, n, 54 * n_slots, master);
   }
@@ -1488,6 +1502,7 @@ int CholBatch::profile_pass(double* const* d_bufs, double* ms_steps, int* n_laun
     HostGraph* g = graphs[i];
     std::lock_guard<std::mutex> gl(g->mtx);
     g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;      // (a batched pass rewrites the status words, deltas and estimates)
+    if (rb_kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }
     int rc = g->merge_pending();
     if (rc == SLIDE_OK) rc = g->upload_new();
     if (rc != SLIDE_OK) return rc;
@@ -1536,6 +1551,7 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
     HostGraph* g = graphs[i];
     std::lock_guard<std::mutex> gl(g->mtx);
     g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;      // (a batched pass rewrites the status words, deltas and estimates)
+    if (rb_kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }      // (a member new to the batch's loss: upload_new creates its robust arrays)
     int rc = g->merge_pending();
     if (rc == SLIDE_OK) rc = g->upload_new();
     if (rc != SLIDE_OK) return rc;
@@ -1543,6 +1559,10 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
     if (g->G.n_slots != graphs[0]->G.n_slots) { g_last_error = "batched pass: the graphs disagree on the shared slots"; return SLIDE_ERR_INVALID; }
     SL_HIP(hipStreamSynchronize(g->stream));                       // (uploads of a changed graph; idle otherwise)
     *same = *same && std::memcmp(&pass_G[i], &g->G, sizeof(GraphDev)) == 0 && pass_bufs[i] == d_bufs[i];
+    if (rb_kind != 0 && *same) {
+      const RobustDev Rv = member_view(g);
+      *same = (int)pass_R.size() == n && std::memcmp(&pass_R[i], &Rv, sizeof(RobustDev)) == 0;
+    }
   }
   if (!*same) {
     // every captured sequence is stale: drop them, refresh the device-side tables once
@@ -1553,8 +1573,18 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
     pass_G.resize(n);
     pass_bufs.assign(d_bufs, d_bufs + n);
     for (int i = 0; i < n; ++i) pass_G[i] = graphs[i]->G;
+    pass_R.clear();
+    if (rb_kind != 0) pass_R = hR;
   }
+  note_pass();
   return SLIDE_OK;
+}
+// what the pass that starts now linearises: the read-back reports these factors under this loss
+void CholBatch::note_pass() {
+  rb_pass_done = true;
+  lin_rb_kind = rb_kind; lin_rb_mask = rb_mask;
+  lin_bt.resize(n); lin_gh.resize(n);
+  for (int i = 0; i < n; ++i) { lin_bt[i] = (size_t)graphs[i]->G.n_between; lin_gh[i] = (size_t)graphs[i]->G.n_ghost; }
 }
 int CholBatch::end_pass() {
   int st[CHOL_BATCH_HOST_MAX][8];
@@ -1636,6 +1666,150 @@ void CholBatch::set_pcg(int iters, double tol) {
   for (HostGraph* g : gs)              // the joined graphs (re)build their device view: the joint-solve buffers are allocated on demand
     if (g) { std::lock_guard<std::mutex> gl(g->mtx); g->topo_dirty = true; }
 }
+static int key_robot(uint64_t key);
+// ---- robust loss of the batch (k_robust_reweight_b) --------------------------------------------------------------------------------
+// The setting lives here, not in the members: a member's own RobustDev carries its arrays (kind 0: its own solves stay unweighted,
+// the per-graph refusals hold), the batch's views add the batch's loss.
+RobustDev CholBatch::member_view(const HostGraph* g) const {
+  RobustDev R = g->RB;
+  R.kind = rb_kind; R.mask = rb_mask; R.param = rb_param;
+  return R;
+}
+int CholBatch::set_robust_loss(int kind, double param, int class_mask) {
+  if (kind < 0 || kind > 4) { g_last_error = "chol_batch_set_robust_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
+  if (class_mask & ~3) { g_last_error = "chol_batch_set_robust_loss: class_mask has bit 0 (loop closures) and bit 1 (relative measurements) only"; return SLIDE_ERR_INVALID; }
+  if (!(param == param)) { g_last_error = "chol_batch_set_robust_loss: param is not a number"; return SLIDE_ERR_INVALID; }
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  if (kind != 0 && pcg_iters > 0) {
+    g_last_error = "chol_batch_set_robust_loss: the batch runs PCG passes (pcg_iters > 0), whose step leaves the inter-robot factors' cross block out; they do not carry a robust loss";
+    return SLIDE_ERR_INVALID;
+  }
+  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
+  std::vector<HostGraph*> gs;
+  {
+    std::lock_guard<std::mutex> lk(mtx);
+    rb_kind = kind;
+    rb_mask = kind ? class_mask : 0;
+    rb_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
+    pass_dirty = true;
+    gs.assign(graphs.begin(), graphs.end());
+  }
+  exact_serial = 0;           // (the joint queries wait for the next pass: the factor and the cached joint Sigma are the old weighting's)
+  rb_pass_done = false;
+  int rc = SLIDE_OK;
+  for (HostGraph* g : gs) {
+    if (!g) continue;
+    std::lock_guard<std::mutex> gl(g->mtx);
+    if (g->restore_base_sigmas() != SLIDE_OK) rc = SLIDE_ERR_HIP;      // every sigma back to its base value: the next pass weights under the new setting
+    g->factor_valid = false;
+    g->wf_T = 0;
+    g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;
+    if (kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }
+  }
+  return rc;
+}
+int CholBatch::get_closure_weights(int cap, int32_t* slot, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind,
+                                   int32_t* ghost_id, double* weight, double* s2, int* n_out) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  if (!rb_pass_done || (int)lin_bt.size() != n || !master) { g_last_error = "chol_batch_get_closure_weights: nothing was linearised under the current setting yet (pass first)"; return SLIDE_ERR_INVALID; }
+  struct Row { int slot, fac, bt, gh; };      // fac: the kernel's factor number; bt: index in h_closures, or -1; gh: ghost factor, or -1
+  std::vector<Row> rows;
+  std::vector<HostGraph*> gs;
+  {
+    std::lock_guard<std::mutex> lk(mtx);
+    // (a member joined, left or was replaced, or the batch's configuration changed: the device tables are the last pass's, not these graphs')
+    if (pass_dirty) { g_last_error = "chol_batch_get_closure_weights: the batch changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
+    gs.assign(graphs.begin(), graphs.end());
+  }
+  for (int i = 0; i < n; ++i) {
+    HostGraph* g = gs[i];
+    if (!g) { g_last_error = "chol_batch_get_closure_weights: a slot of the batch is empty"; return SLIDE_ERR_INVALID; }
+    std::lock_guard<std::mutex> gl(g->mtx);
+    if ((size_t)g->G.n_between != lin_bt[i] || (size_t)g->G.n_ghost != lin_gh[i]) { g_last_error = "chol_batch_get_closure_weights: a member changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
+    for (size_t c = 0; c < g->h_closures.size(); ++c)
+      if ((size_t)g->h_closures[c].bt < lin_bt[i]) rows.push_back(Row{i, g->h_closures[c].bt, (int)c, -1});
+    for (size_t q = 0; q < lin_gh[i]; ++q) rows.push_back(Row{i, (int)(lin_bt[i] + q), -1, (int)q});
+  }
+  const int total = (int)rows.size();
+  *n_out = total;
+  const int m = std::min(total, std::max(cap, 0));
+  if (m == 0) return SLIDE_OK;
+  if ((size_t)m > rb_ent_cap) {
+    if (d_rb_ent) { (void)hipFree(d_rb_ent); d_rb_ent = nullptr; }
+    if (d_rb_out) { (void)hipFree(d_rb_out); d_rb_out = nullptr; }
+    rb_ent_cap = 0;
+    SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_rb_ent), 2 * (size_t)m * sizeof(int)));
+    SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_rb_out), 2 * (size_t)m * sizeof(double)));
+    rb_ent_cap = (size_t)m;
+  }
+  std::vector<int> ent(2 * (size_t)m);
+  for (int k = 0; k < m; ++k) { ent[2 * (size_t)k] = rows[k].slot; ent[2 * (size_t)k + 1] = rows[k].fac; }
+  // the views of the last pass under the loss it ran with (no loss then: every weight 1, s^2 from the residuals)
+  std::vector<RobustDev> Rq(n);
+  for (int i = 0; i < n; ++i) { Rq[i] = member_view(gs[i]); Rq[i].kind = lin_rb_kind; Rq[i].mask = lin_rb_mask; }
+  if (!d_Rs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Rs), CHOL_BATCH_HOST_MAX * sizeof(RobustDev)));
+  SL_HIP(hipMemcpyAsync(d_Rs, Rq.data(), n * sizeof(RobustDev), hipMemcpyHostToDevice, master));      // (what the captured pass reads as well: the same bytes while a loss is set)
+  SL_HIP(hipMemcpyAsync(d_rb_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice, master));
+  launch_closure_weights_batched(d_Gs, d_Rs, d_rb_ent, m, d_rb_out, master);
+  std::vector<double> out(2 * (size_t)m);
+  SL_HIP(hipMemcpyAsync(out.data(), d_rb_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, master));
+  SL_HIP(hipStreamSynchronize(master));
+  SL_HIP(hipGetLastError());
+  const uint64_t low = 0x00ffffffffffffffull;
+  for (int k = 0; k < m; ++k) {
+    const Row& r = rows[k];
+    HostGraph* g = gs[r.slot];
+    std::lock_guard<std::mutex> gl(g->mtx);
+    uint64_t k0 = 0, k1 = 0;
+    int r0 = -1, r1 = -1, kd = 2, gid = -1;
+    if (r.bt >= 0) {
+      const HostGraph::ClosureRec& c = g->h_closures[r.bt];
+      k0 = c.k0 & low; k1 = c.k1 & low; r0 = key_robot(c.k0); r1 = key_robot(c.k1); kd = g->h_bt_kind[c.bt];
+    } else {
+      const uint64_t key = g->h_gh_key[r.gh];
+      const bool first = g->h_gh_first[r.gh] != 0;
+      (first ? k0 : k1) = key & low; (first ? r0 : r1) = key_robot(key);
+      (first ? k1 : k0) = (uint64_t)g->h_gh_slot[r.gh];
+      if ((size_t)r.gh < g->h_gh_gid.size()) gid = g->h_gh_gid[r.gh];
+    }
+    if (slot) slot[k] = r.slot;
+    if (from_robot) from_robot[k] = r0;
+    if (from_idx) from_idx[k] = k0;
+    if (to_robot) to_robot[k] = r1;
+    if (to_idx) to_idx[k] = k1;
+    if (kind) kind[k] = kd;
+    if (ghost_id) ghost_id[k] = gid;
+    if (weight) weight[k] = out[2 * (size_t)k];
+    if (s2) s2[k] = out[2 * (size_t)k + 1];
+  }
+  return SLIDE_OK;
+}
+// Measurement: k_robust_reweight_b alone between two events on the pass's stream.  It runs on what the last pass left - the ghost
+// values of that pass's start beside the estimates of its end - so the weights it writes belong to no pass: the read-back is
+// refused until the next pass, whose own launch writes every weight and sigma again before anything reads them.  An event pair
+// around one short launch mostly measures the launch.
+int CholBatch::profile_robust_reweight(double* const* d_bufs, double* ms) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  if (rb_kind == 0) { g_last_error = "profile_robust_reweight: the batch has no robust loss"; return SLIDE_ERR_INVALID; }
+  bool same = false;
+  int rc = begin_pass(d_bufs, &same);
+  if (rc != SLIDE_OK) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SL_HIP(hipEventCreate(&e0));
+  SL_HIP(hipEventCreate(&e1));
+  (void)hipEventRecord(e0, master);
+  launch_robust_reweight_batched(d_Gs, d_Rs, hG.data(), n, master);
+  (void)hipEventRecord(e1, master);
+  const hipError_t es = hipStreamSynchronize(master);
+  float t = 0.f;
+  if (es != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) rc = SLIDE_ERR_HIP;
+  *ms = t;
+  rb_pass_done = false;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return rc;
+}
+
 // S -> S0 for every joined graph (the factorisation works in place; the joint solve multiplies with the original blocks)
 int CholBatch::save_systems() {
   for (int i = 0; i < n; ++i) {
@@ -1949,6 +2123,11 @@ int HostGraph::upload_new() {
   UP(d_gh_first, h_gh_first, up_gh, 1);
   UP(d_gh_z, h_gh_z, up_gh, 12);
   UP(d_gh_sigma, h_gh_sigma, up_gh, 6);
+  if (rb_arrays) {      // (the ghost factors' share of the robust arrays: a batch's loss covers them)
+    UP(d_gh_sigma0, h_gh_sigma, up_rbg, 6);
+    if (d_gh_w.ensure(std::max<size_t>(ngh, 1), up_rbg, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+    if (d_gh_s2.ensure(std::max<size_t>(ngh, 1), up_rbg, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  }
   if (d_gh_r.ensure(std::max<size_t>(6 * ngh, 1), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   if (d_gh_J.ensure(std::max<size_t>(36 * ngh, 1), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   UP(d_lf_type, h_lf_type, up_lf, 1);
@@ -2295,7 +2474,7 @@ int HostGraph::upload_new() {
   uploaded_once = true;
   up_P = Pn; up_L = Ln; up_pr = npr; up_bt = nbt; up_lf = nlf; up_gh = ngh;
   up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7;
-  if (rb_arrays) up_rb = nbt;
+  if (rb_arrays) { up_rb = nbt; up_rbg = ngh; }
 
   G.P = (int)Pn; G.L = (int)Ln;
   G.pose_val = d_pose_val.d; G.pose_delta = d_pose_delta.d; G.pose_est = d_pose_est.d;
@@ -2304,6 +2483,7 @@ int HostGraph::upload_new() {
   G.n_between = (int)nbt; G.bt_i = d_bt_i.d; G.bt_j = d_bt_j.d; G.bt_z = d_bt_z.d; G.bt_sigma = d_bt_sigma.d;
   G.bt_r = d_bt_r.d; G.bt_J0 = d_bt_J0.d;
   RB.bt_sigma0 = d_bt_sigma0.d; RB.bt_w = d_bt_w.d; RB.bt_s2 = d_bt_s2.d; RB.bt_kind = d_bt_kind.d;      // (null until a robust loss is set)
+  RB.gh_sigma0 = d_gh_sigma0.d; RB.gh_w = d_gh_w.d; RB.gh_s2 = d_gh_s2.d;
   RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
   G.n_ghost = (int)ngh; G.gh_pose = d_gh_pose.d; G.gh_slot = d_gh_slot.d; G.gh_first = d_gh_first.d; G.gh_z = d_gh_z.d;
   G.gh_sigma = d_gh_sigma.d; G.gh_r = d_gh_r.d; G.gh_J = d_gh_J.d;
@@ -3025,13 +3205,18 @@ int HostGraph::set_robust_loss(int kind, double param, int class_mask) {
   RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
   if (kind != 0 && !rb_arrays) { rb_arrays = true; topo_dirty = true; }      // (upload_new creates and fills the robust arrays)
   // every sigma back to its base value; the next solve takes the weights of the new setting everywhere
-  if (up_rb > 0) SL_HIP(hipMemcpyAsync(d_bt_sigma.d, d_bt_sigma0.d, 6 * std::min(up_rb, up_bt) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  if (restore_base_sigmas() != SLIDE_OK) return SLIDE_ERR_HIP;
   // the resident factor and the last solution belong to the system as it was weighted: as after chi2(), the next solve relinearises
   // and re-factors everything and keeps no block of dp
   factor_valid = false;
   wf_T = 0;
   pred_valid = false; status_clean = false; cache_pose = -1;
   if (kind == 0) prof.forget("k_robust_reweight");
+  return SLIDE_OK;
+}
+int HostGraph::restore_base_sigmas() {
+  if (up_rb > 0) SL_HIP(hipMemcpyAsync(d_bt_sigma.d, d_bt_sigma0.d, 6 * std::min(up_rb, up_bt) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  if (up_rbg > 0) SL_HIP(hipMemcpyAsync(d_gh_sigma.d, d_gh_sigma0.d, 6 * std::min(up_rbg, up_gh) * sizeof(double), hipMemcpyDeviceToDevice, stream));
   return SLIDE_OK;
 }
 static int key_robot(uint64_t key) {

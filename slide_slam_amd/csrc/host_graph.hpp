@@ -174,6 +174,17 @@ class CholBatch {
   // Joint solve: after the factorisations, `iters` PCG iterations on the global reduced system (pcg_kernels.hip); 0 = each robot's own
   // block solve only (block-Jacobi over robots).  Changing it invalidates the captured launch sequences.
   void set_pcg(int iters, double tol = 0.0);
+  // Robust loss (iteratively reweighted least squares) on the members' loop-closure / relative-measurement between factors and on
+  // the inter-robot relative-pose (ghost) factors, uniform over the batch (HostGraph::set_robust_loss's arguments and defaults):
+  // k_robust_reweight_b ahead of the linearisation of every whole or cut pass.  Not with PCG passes (pcg_iters > 0).
+  int set_robust_loss(int kind, double param, int class_mask);
+  bool robust_on() const { return rb_kind != 0; }
+  // per member slot: its loop-closure / relative-measurement between factors in insertion order, then its ghost factors (kind 2;
+  // the local pose in from_* when it is the factor's first key, else in to_*; the other end: robot -1, idx = its ghost slot;
+  // ghost_id: slide_graph_set_ghost_ids' index, -1 for between factors and unnamed ghosts), with w and s^2 of the last pass
+  int get_closure_weights(int cap, int32_t* slot, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind,
+                          int32_t* ghost_id, double* weight, double* s2, int* n_out);
+  int profile_robust_reweight(double* const* d_bufs, double* ms);      // k_robust_reweight_b alone between two events (measurement)
   int pcg() const { return pcg_iters; }
   double pcg_tolerance() const { return pcg_tol; }
   // Exact joint step ("arrow"): the shared landmarks stay as the separator of the joint graph (graph_dev.hpp).  sep_buf: the caller's
@@ -310,6 +321,18 @@ class CholBatch {
   std::vector<double*> pass_bufs;
   hipEvent_t ev_fork = nullptr;
   GraphDev* d_Gs = nullptr;              // the joined graphs' device views, for the kernels batched over blockIdx.z
+  // robust loss of the batch: the members' RobustDev views beside d_Gs (their arrays, the batch's setting), compared by begin_pass
+  // like the GraphDev views; what the last pass linearised under and how many factors of each member it covered (the read-back)
+  int rb_kind = 0, rb_mask = 0;
+  double rb_param = 0.0;
+  RobustDev* d_Rs = nullptr;
+  std::vector<RobustDev> hR, pass_R;
+  RobustDev member_view(const HostGraph* g) const;
+  bool rb_pass_done = false;
+  int lin_rb_kind = 0, lin_rb_mask = 0;
+  std::vector<size_t> lin_bt, lin_gh;
+  int* d_rb_ent = nullptr; double* d_rb_out = nullptr; size_t rb_ent_cap = 0;
+  void note_pass();
   int capture_pass(double* const* d_bufs, int part, hipGraphExec_t* exec);
   int prepare_pass();
   int begin_pass(double* const* d_bufs, bool* same);
@@ -521,6 +544,10 @@ class HostGraph {
   size_t lin_bt = 0;
   int lin_rb_kind = 0, lin_rb_mask = 0;
   void note_linearisation() { lin_done = true; lin_bt = up_bt; lin_rb_kind = RB.kind; lin_rb_mask = RB.mask; }
+  std::vector<uint64_t> h_gh_key;              // ghost factor -> key of its local pose
+  size_t up_rbg = 0;                           // ghost factors the robust arrays hold (a batch's loss covers them)
+  DevArr<double> d_gh_sigma0, d_gh_w, d_gh_s2;
+  int restore_base_sigmas();                   // bt_sigma / gh_sigma <- sigma0 (a loss was set, cleared or left behind with a batch)
   DevArr<double> d_bt_sigma0, d_bt_w, d_bt_s2, d_rb_out;
   DevArr<int> d_bt_kind, d_rb_idx;
   std::vector<int> h_gh_pose, h_gh_slot, h_gh_first; std::vector<double> h_gh_z, h_gh_sigma;   // ghost-between factors

@@ -14,6 +14,11 @@ void launch_relin(const GraphDev& G, hipStream_t s);
 void launch_linearize(const GraphDev& G, hipStream_t s);
 void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s);      // ahead of launch_linearize while a robust loss is set (no launch otherwise)
 void launch_closure_weights(const GraphDev& G, const RobustDev& R, const int* idx, int n, double* out2n, hipStream_t s);   // (weight, s^2) of the listed between factors
+// the batch's robust loss (dR: the members' RobustDev table beside d): k_robust_reweight_b between k_relin_b and the linearisation
+// of launch_phase0_batched (its dR argument; null: no launch); (weight, s^2) of the listed (member, factor) pairs, a member's ghost
+// factors numbered behind its between factors
+void launch_robust_reweight_batched(const GraphDev* d, const RobustDev* dR, const GraphDev* h, int n, hipStream_t s);
+void launch_closure_weights_batched(const GraphDev* d, const RobustDev* dR, const int* ent2, int n, double* out2n, hipStream_t s);
 void launch_landmark(const GraphDev& G, int mode, hipStream_t s);      // mode: 0 fused, 1 accumulate, 2 finish from sums
 void launch_pose(const GraphDev& G, hipStream_t s);
 void launch_schur(const GraphDev& G, hipStream_t s);
@@ -30,7 +35,7 @@ void launch_gather(void* stage, unsigned desc_off, int nseg, hipStream_t s);
 void launch_gather_args(void* stage, const void* segs, int nseg, hipStream_t s);      // the same, up to 16 descriptors as kernel arguments
 void launch_sum_bcast(double* const* bufs, int n, int count, hipStream_t s);   // local all-reduce(sum) of up to 8 buffers
 void launch_bcast(double* const* bufs, int n, int count, hipStream_t s);       // bufs[0] -> the others
-void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack = true);   // the per-robot phases 0 / 4 / 2 of a batched pass,
+void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack = true, const RobustDev* dR = nullptr);   // the per-robot phases 0 / 4 / 2 of a batched pass,
 void launch_phase4_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s);   // blockIdx.z = robot
 void launch_phase2_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s);
 void launch_phase3_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s);   // blockIdx.z = robot               // local all-reduce(sum) of up to 8 buffers             // device arrays -> one staging buffer (DownloadBatch)   // staged upload -> destinations (UploadBatch)

@@ -1890,7 +1890,7 @@ __global__ void k_shared_pack_b(const GraphDev* __restrict__ Gs, int what, BufPt
 // The per-robot phases of a batched pass in ONE launch sequence for all robots (blockIdx.z = robot, grids sized for the largest graph):
 // forking every robot's phase onto its own stream and joining again cost three cross-stream joins of ~15 us per pass.
 // phase 0: relinearise, linearise, per-landmark partial sums, pack H_ll / g_l of the shared slots
-void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack) {
+void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack, const RobustDev* dR) {
   int L = 0, P = 0, slots = 0, npf = 0;
   long long nlf = 0;
   for (int i = 0; i < n; ++i) {
@@ -1901,6 +1901,7 @@ void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* 
   BufPtrs B{};
   for (int i = 0; i < n; ++i) B.p[i] = bufs[i];
   if (P + L > 0) hipLaunchKernelGGL(k_relin_b, dim3(blocks_for(P + L, 256), 1, n), dim3(256), 0, s, d);
+  if (dR) launch_robust_reweight_batched(d, dR, h, n, s);      // (only while the batch has a robust loss: the weights at the point the factors are linearised at)
   if (nlf > 0) {
     const int nb0 = npf > 0 ? (int)blocks_for(npf, 256) : 0;
     hipLaunchKernelGGL(k_lin_lf_b, dim3(nb0 + blocks_for(nlf, 256) + blocks_for(32LL * nlf, 256), 1, n), dim3(256), 0, s, d, nb0, (int)blocks_for(nlf, 256));
@@ -2052,9 +2053,25 @@ __device__ __forceinline__ double robust_weight(int kind, double c, double s2) {
     default: return 1.0;
   }
 }
-__global__ __launch_bounds__(128) void k_robust_reweight(GraphDev G, RobustDev R) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= G.n_between) return;
+// w, s^2 and sigma0 / sqrt(w) of one selected factor with residual e (what both the between and the ghost factors do with it)
+__device__ __forceinline__ void robust_apply(const RobustDev& R, const double* e, const double* __restrict__ sigma0, double* __restrict__ sigma,
+                                             double* __restrict__ w_out, double* __restrict__ s2_out) {
+  double sg[6];
+  double s2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    sg[r] = sigma0[r];
+    const double q = e[r] / sg[r];
+    s2 += q * q;
+  }
+  const double w = fmax(robust_weight(R.kind, R.param, s2), 1e-12);      // (the floor keeps every sigma finite)
+  const double d = sqrt(w);
+  *w_out = w;
+  *s2_out = s2;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) sigma[r] = sg[r] / d;
+}
+__device__ __forceinline__ void robust_reweight_between(const GraphDev& G, const RobustDev& R, int b) {
   const int origin = R.bt_kind[b];
   if (origin < 1 || origin > 2 || !((R.mask >> (origin - 1)) & 1)) return;      // odometry, or a class the caller did not select
   if (min(G.bt_i[b], G.bt_j[b]) < G.pose0) return;      // (k_lin_pose_factors_body's rule: a kept linearisation keeps its weight)
@@ -2063,20 +2080,46 @@ __global__ __launch_bounds__(128) void k_robust_reweight(GraphDev G, RobustDev R
   const SE3 Z = from12(G.bt_z + 12 * (size_t)b);
   double e[6];
   local(Z, between(X1, X2), e, G.chart);
-  double sg[6];
-  double s2 = 0.0;
+  robust_apply(R, e, R.bt_sigma0 + 6 * (size_t)b, G.bt_sigma + 6 * (size_t)b, R.bt_w + b, R.bt_s2 + b);
+}
+__global__ __launch_bounds__(128) void k_robust_reweight(GraphDev G, RobustDev R) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= G.n_between) return;
+  robust_reweight_between(G, R, b);
+}
+// The batched pass (blockIdx.z = robot, the grid sized for the largest member): the between factors as above, then the robot's
+// ghost factors - its ends of the inter-robot relative-pose factors, origin 2.  Both robots that hold a factor must take the same
+// weight: its lambda rows (k_border_fill_lam_b: J of both ends, -I and -r of the first-key end) are then scaled as a whole.  So e
+// is taken from what both ends hold as the same bits - the two poses' ESTIMATES as the ghost refresh hands them round: the other
+// pose's ghost value, and the own pose's pose_est through the same sum with zeros (x + 0.0: a -0.0 arrives as +0.0 there too) -
+// and through one instruction sequence, between(first, second) on selected operands.  The own pose_est is the own linearisation
+// point pose_val (k_relin_b at threshold 0 retracts the same inputs) up to the last bit: the two inlined copies of pose_retract12
+// were seen to differ in the last bits of one pose, which is why pose_val itself does not serve here.
+__global__ __launch_bounds__(128) void k_robust_reweight_b(const GraphDev* __restrict__ Gs, const RobustDev* __restrict__ Rs) {
+  const GraphDev& G = Gs[blockIdx.z];
+  const RobustDev& R = Rs[blockIdx.z];
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < G.n_between) {
+    robust_reweight_between(G, R, t);
+  } else if (t < G.n_between + G.n_ghost) {
+    if (!(R.mask & 2)) return;
+    // (no pose0 rule here, as in the ghost branch of k_lin_pose_factors_body: batched passes relinearise every factor)
+    const int q = t - G.n_between;
+    const bool first = G.gh_first[q] != 0;
+    const double* pl = G.pose_est + 12 * (size_t)G.gh_pose[q];
+    const double* po = G.ghost_val + 12 * (size_t)G.gh_slot[q];
+    double a[12], b[12];
 #pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    sg[r] = R.bt_sigma0[6 * (size_t)b + r];
-    const double q = e[r] / sg[r];
-    s2 += q * q;
+    for (int k = 0; k < 12; ++k) {
+      const double l = pl[k] + 0.0, o = po[k];
+      a[k] = first ? l : o;
+      b[k] = first ? o : l;
+    }
+    const SE3 Z = from12(G.gh_z + 12 * (size_t)q);
+    double e[6];
+    local(Z, between(from12(a), from12(b)), e, G.chart);
+    robust_apply(R, e, R.gh_sigma0 + 6 * (size_t)q, G.gh_sigma + 6 * (size_t)q, R.gh_w + q, R.gh_s2 + q);
   }
-  const double w = fmax(robust_weight(R.kind, R.param, s2), 1e-12);      // (the floor keeps every sigma finite)
-  const double d = sqrt(w);
-  R.bt_w[b] = w;
-  R.bt_s2[b] = s2;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) G.bt_sigma[6 * (size_t)b + r] = sg[r] / d;
 }
 // slide_graph_get_closure_weights: (weight, s^2) of the listed between factors at their last linearisation.  A factor the loss of
 // that linearisation (R.kind / R.mask as the host passes them) did not select has weight 1, and s^2 = |bt_r|^2 (its sigma is sigma0).
@@ -2097,12 +2140,46 @@ __global__ __launch_bounds__(128) void k_closure_weights(GraphDev G, RobustDev R
   }
 }
 
+// slide_chol_batch_get_closure_weights: the same over all members of a batch in one gather.  ent[k] = (member, factor): a between
+// factor of that member, or (factor >= its n_between) its ghost factor factor - n_between.
+__global__ __launch_bounds__(128) void k_closure_weights_b(const GraphDev* __restrict__ Gs, const RobustDev* __restrict__ Rs, const int2* __restrict__ ent,
+                                                           int n, double* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const GraphDev& G = Gs[ent[k].x];
+  const RobustDev& R = Rs[ent[k].x];
+  const int b = ent[k].y;
+  const bool ghost = b >= G.n_between;
+  const int q = b - G.n_between;
+  const int origin = R.kind == 0 ? 0 : (ghost ? 2 : R.bt_kind[b]);
+  if (origin >= 1 && origin <= 2 && ((R.mask >> (origin - 1)) & 1)) {
+    out[2 * k] = ghost ? R.gh_w[q] : R.bt_w[b];
+    out[2 * k + 1] = ghost ? R.gh_s2[q] : R.bt_s2[b];
+  } else {
+    const double* r6 = ghost ? G.gh_r + 6 * (size_t)q : G.bt_r + 6 * (size_t)b;
+    double s2 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) { const double v = r6[r]; s2 += v * v; }
+    out[2 * k] = 1.0;
+    out[2 * k + 1] = s2;
+  }
+}
+
 void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s) {
   if (R.kind == 0 || G.n_between == 0) return;
   hipLaunchKernelGGL(k_robust_reweight, dim3(blocks_for(G.n_between, 128)), dim3(128), 0, s, G, R);
 }
 void launch_closure_weights(const GraphDev& G, const RobustDev& R, const int* idx, int n, double* out2n, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_closure_weights, dim3(blocks_for(n, 128)), dim3(128), 0, s, G, R, idx, n, out2n);
+}
+
+void launch_robust_reweight_batched(const GraphDev* d, const RobustDev* dR, const GraphDev* h, int n, hipStream_t s) {
+  int nf = 0;
+  for (int i = 0; i < n; ++i) nf = std::max(nf, h[i].n_between + h[i].n_ghost);
+  if (nf > 0) hipLaunchKernelGGL(k_robust_reweight_b, dim3(blocks_for(nf, 128), 1, n), dim3(128), 0, s, d, dR);
+}
+void launch_closure_weights_batched(const GraphDev* d, const RobustDev* dR, const int* ent2, int n, double* out2n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_closure_weights_b, dim3(blocks_for(n, 128)), dim3(128), 0, s, d, dR, reinterpret_cast<const int2*>(ent2), n, out2n);
 }
 
 }  // namespace sl

@@ -531,6 +531,8 @@ class PassDriver:
         slot = {key: i for i, key in enumerate(keys)}
         self.n_gslots = len(keys)
         self.n_relmeas = len(rm)
+        self.relmeas_keys = [(a, ka, b, kb) for (ka, a, kb, b, _) in rm]      # (closure_weights: the job's list in virtual robot indices)
+        self.rank = rank
         for t, sh in enumerate(self.shards):
             v = rank * R + t
             sh.graph.set_ghosts(np.array([0 if r == v else -1 for (r, _) in keys], np.int32), np.array([k for (_, k) in keys], np.int64))
@@ -702,6 +704,61 @@ class PassDriver:
         CholBatch.closure_mahalanobis (d2 to compare with 16.81, status, C, r)."""
         self._joint_ok()
         return self.batch.closure_mahalanobis(closures)
+
+    # ---- robust loss on the exact joint pass (CholBatch.set_robust_loss, slide_gpu.h) --------------------------------------------------
+    def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
+        """The batch's robust loss for this driver's passes, whole or cut: every robot's loop closures (closures), its relative
+        measurements and the job's inter-robot relative-pose factors (relative_meas).  Batched exact-joint drivers only: the
+        un-batched and CPU-rehearsal passes and the PCG passes do not carry a loss.  Every rank of a job must set the same loss."""
+        if self.batch is None or not self.arrow:
+            raise ValueError("set_robust_loss needs a CholBatch running exact joint passes (arrow=True): the un-batched, CPU and PCG passes do not carry a robust loss")
+        if self.world > 1 and self.base is not None:
+            from .api import SlideGraph
+            k = SlideGraph.ROBUST_KINDS.get(kind, kind) if (kind is None or isinstance(kind, str)) else int(kind)
+            on = k not in (0, None)      # (compared as resolved: "huber" and 1 are one loss, param <= 0 is the default, off is off)
+            mine = (k if on else 0, max(float(param), 0.0) if on else 0.0, bool(closures) and on, bool(relative_meas) and on)
+            seen = self.base.all_gather_object(mine)
+            if len(set(seen)) != 1:
+                raise RuntimeError(f"set_robust_loss: the ranks disagree on the loss: {sorted(set(seen))}")
+        self.batch.set_robust_loss(kind, param, closures, relative_meas)
+
+    def closure_weights(self):
+        """After a pass: {"between": the robots' own loop-closure / relative-measurement factors (robot = virtual robot index
+        rank * R + slot with setup_ghosts' rank, from_idx, to_idx, kind, weight, s2; slot by slot in insertion order), "relmeas": one
+        row per entry of setup_ghosts' list (from_robot, from_idx, to_robot, to_idx in virtual robot indices, weight, s2; NaN where
+        no end of the factor lives in this job's processes)}.  A factor's two ends are merged; differing weights raise."""
+        if self.batch is None or not self.arrow:
+            raise ValueError("closure_weights needs a CholBatch running exact joint passes (arrow=True)")
+        cw = self.batch.closure_weights()
+        R = len(self.shards)
+        gh = (cw["from_robot"] < 0) | (cw["to_robot"] < 0)          # (a ghost factor's other end is robot -1)
+        bt = ~gh
+        if (cw["ghost_id"][gh] < 0).any():
+            raise RuntimeError("closure_weights: a ghost factor is not named in the job's list (set_ghost_ids; setup_ghosts does it for exact joint passes)")
+        between = {"robot": getattr(self, "rank", 0) * R + cw["slot"][bt], "from_idx": cw["from_idx"][bt], "to_idx": cw["to_idx"][bt],
+                   "kind": cw["kind"][bt], "weight": cw["weight"][bt], "s2": cw["s2"][bt]}
+        ends = {}
+        for g, w, s2 in zip(cw["ghost_id"][gh], cw["weight"][gh], cw["s2"][gh]):
+            ends.setdefault(int(g), []).append((float(w), float(s2)))
+        if self.world > 1 and self.base is not None:
+            merged = {}
+            for part in self.base.all_gather_object(ends):
+                for g, lst in part.items():
+                    merged.setdefault(g, []).extend(lst)
+            ends = merged
+        keys = getattr(self, "relmeas_keys", [])
+        n = len(keys)
+        w, s2 = np.full(n, np.nan), np.full(n, np.nan)
+        for g, lst in ends.items():
+            if not 0 <= g < n:
+                raise RuntimeError(f"closure_weights: ghost factor {g} is not in setup_ghosts' list")
+            if any(e != lst[0] for e in lst[1:]):
+                raise RuntimeError(f"closure_weights: the two ends of inter-robot factor {g} disagree: {lst}")
+            w[g], s2[g] = lst[0]
+        relmeas = {"from_robot": np.array([k[0] for k in keys], np.int32), "from_idx": np.array([k[1] for k in keys], np.uint64),
+                   "to_robot": np.array([k[2] for k in keys], np.int32), "to_idx": np.array([k[3] for k in keys], np.uint64),
+                   "weight": w, "s2": s2}
+        return {"between": between, "relmeas": relmeas}
 
     def one_pass(self):
         n54, n9, K = 54 * self.n_slots, 9 * self.n_slots, self.pcg_iters
