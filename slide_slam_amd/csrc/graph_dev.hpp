@@ -46,7 +46,9 @@ struct GraphDev {
   double* gh_r; double* gh_J;                     // 6 whitened residual ; 36 whitened Jacobian w.r.t. the local pose
   int n_gslots; double* ghost_val; int* gslot_pose;   // 12 per slot (R row-major, t) ; local pose owning the slot or -1
   int n_lf;                                       // landmark factors, unified id space
+  int n_nbr;                                      // ... of which are NOT bearing-range (cubes, cylinders: linearised by central differences)
   int* lf_type; int* lf_pose; int* lf_lm; int* lf_slot;   // slot = index into the per-type z arrays
+  int* lf_nbr;                                    // their ids, ascending (a factor's type never changes: appended as factors arrive)
   int64_t* lf_joff; int64_t* lf_eoff;             // offsets (doubles) into jbuf / ebuf
   double* br_z;                                   // 4 per BR factor: bearing(3), range
   double* cu_z; double* cu_sigma;                 // 15 ; 9

@@ -390,6 +390,7 @@ int HostGraph::merge_pending() {
       dirty_min_pose = std::min(dirty_min_pose, h_lm_first[b->second]);
       h_lm_first[b->second] = std::min(h_lm_first[b->second], a->second);
       h_lf_type.push_back(f.type);
+      if (f.type != FT_BR) h_lf_nbr.push_back(fid);
       h_lf_pose.push_back(a->second);
       h_lf_lm.push_back(b->second);
       if (f.type == FT_BR) {
@@ -2136,6 +2137,7 @@ int HostGraph::upload_new() {
   UP(d_lf_slot, h_lf_slot, up_lf, 1);
   UP(d_lf_joff, h_lf_joff, up_lf, 1);
   UP(d_lf_eoff, h_lf_eoff, up_lf, 1);
+  UP(d_lf_nbr, h_lf_nbr, up_nbr, 1);
   UP(d_br_z, h_br_z, up_br, 4);
   UP(d_cu_z, h_cu_z, up_cu, 15);
   UP(d_cu_sigma, h_cu_sigma, up_cu, 9);
@@ -2473,7 +2475,7 @@ int HostGraph::upload_new() {
   topo_dirty = false;
   uploaded_once = true;
   up_P = Pn; up_L = Ln; up_pr = npr; up_bt = nbt; up_lf = nlf; up_gh = ngh;
-  up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7;
+  up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7; up_nbr = h_lf_nbr.size();
   if (rb_arrays) { up_rb = nbt; up_rbg = ngh; }
 
   G.P = (int)Pn; G.L = (int)Ln;
@@ -2488,6 +2490,7 @@ int HostGraph::upload_new() {
   G.n_ghost = (int)ngh; G.gh_pose = d_gh_pose.d; G.gh_slot = d_gh_slot.d; G.gh_first = d_gh_first.d; G.gh_z = d_gh_z.d;
   G.gh_sigma = d_gh_sigma.d; G.gh_r = d_gh_r.d; G.gh_J = d_gh_J.d;
   G.n_gslots = (int)h_gslot_pose.size(); G.ghost_val = d_ghost_val.d; G.gslot_pose = d_gslot_pose.d;
+  G.n_nbr = (int)h_lf_nbr.size(); G.lf_nbr = d_lf_nbr.d;
   G.n_lf = (int)nlf; G.lf_type = d_lf_type.d; G.lf_pose = d_lf_pose.d; G.lf_lm = d_lf_lm.d; G.lf_slot = d_lf_slot.d;
   G.lf_joff = d_lf_joff.d; G.lf_eoff = d_lf_eoff.d;
   G.br_z = d_br_z.d; G.cu_z = d_cu_z.d; G.cu_sigma = d_cu_sigma.d; G.cy_z = d_cy_z.d;
@@ -2557,6 +2560,9 @@ int HostGraph::build_schur_pairs(hipStream_t s) {
   int W = 1;
   for (int pj = 0; pj < Pn; ++pj) W = std::max(W, p_end(pj) - pj);
   if (W > 256) return SLIDE_OK;
+  // k_schur_lb addresses the E / F records by 32-bit byte offsets into ebuf — it truncates a pair entry's record offset to
+  // (unsigned)(entry >> 4) and multiplies by eight — so every record has to end below 4 GB = 2^29 doubles; past that the walk runs
+  if (ebuf_used >= (1LL << 29)) return SLIDE_OK;
   std::vector<int> idx((size_t)2 * Pn * W, 0);
   std::vector<long long> pairs;
   auto ed_of = [&](int f) {

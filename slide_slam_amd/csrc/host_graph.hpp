@@ -553,6 +553,7 @@ class HostGraph {
   std::vector<int> h_gh_pose, h_gh_slot, h_gh_first; std::vector<double> h_gh_z, h_gh_sigma;   // ghost-between factors
   std::vector<int> h_gslot_pose;
   std::vector<int> h_lf_type, h_lf_pose, h_lf_lm, h_lf_slot;
+  std::vector<int> h_lf_nbr;              // ids of the factors that are not bearing-range (GraphDev::lf_nbr)
   std::vector<int64_t> h_lf_joff, h_lf_eoff;
   std::vector<double> h_br_z, h_cu_z, h_cu_sigma, h_cy_z;
   int64_t jbuf_used = 0, ebuf_used = 0;
@@ -567,7 +568,7 @@ class HostGraph {
   std::vector<long long> hc_pose_ed;      // ... and its E record (offset << 4 | tangent dimension)
   int lm_first_from = 0;                  // h_lm_first changed from this landmark on since the last upload
   std::vector<int> h_lm_last, h_reach;    // per landmark the last observing pose; per pose the last pose it couples to (the profile's input)
-  size_t up_P = 0, up_L = 0, up_pr = 0, up_bt = 0, up_lf = 0, up_br = 0, up_cu = 0, up_cy = 0;
+  size_t up_P = 0, up_L = 0, up_pr = 0, up_bt = 0, up_lf = 0, up_br = 0, up_cu = 0, up_cy = 0, up_nbr = 0;
   int last_relin = 0;
   bool topo_dirty = true, uploaded_once = false;      // upload_new has work only after merge_pending consumed something
 
@@ -577,7 +578,7 @@ class HostGraph {
   DevArr<int> d_bt_i, d_bt_j; DevArr<double> d_bt_z, d_bt_sigma, d_bt_r, d_bt_J0;
   DevArr<int> d_gh_pose, d_gh_slot, d_gh_first, d_gslot_pose; DevArr<double> d_gh_z, d_gh_sigma, d_gh_r, d_gh_J, d_ghost_val;
   size_t up_gh = 0;
-  DevArr<int> d_lf_type, d_lf_pose, d_lf_lm, d_lf_slot;
+  DevArr<int> d_lf_type, d_lf_pose, d_lf_lm, d_lf_slot, d_lf_nbr;
   DevArr<int64_t> d_lf_joff, d_lf_eoff;
   DevArr<long long> d_pose_ed, d_sp_pairs;
   DevArr<int> d_sp_idx;                   // pair lists of the Schur assembly (GraphDev::sp_idx), rebuilt by upload_new for graphs in an exact joint batch

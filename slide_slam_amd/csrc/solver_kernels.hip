@@ -206,11 +206,17 @@ __device__ inline void cyl_err(const SE3& X, const double* q, const double* z, d
 // Thread map (round 4): the first nb1 workgroups give every factor ONE thread and linearise the bearing-range factors (analytic
 // Jacobians: one lane's work — with 32 lanes per factor a wavefront held two of them, 2 of 64 lanes active, and bearing-range
 // factors are most of a SLAM graph); the workgroups behind them give every factor 32 lanes and linearise cubes / cylinders by the
-// reference's central differences (one error evaluation per lane) — wavefronts whose two factors are bearing-range leave at once.
+// reference's central differences (one error evaluation per lane).  That region is launched over the graph's list of those factors
+// (GraphDev::lf_nbr, kept by the host as factors arrive): over all factors, seven of ten 32-lane groups of a SLAM graph loaded a type
+// and left, and only wavefronts whose two factors were both bearing-range left whole.
 __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bid) {
   const bool br_region = bid < nb1;
-  const int f = br_region ? (int)(bid * 256 + threadIdx.x) : (int)(((bid - nb1) * 256 + threadIdx.x) >> 5);
+  int f = br_region ? (int)(bid * 256 + threadIdx.x) : (int)(((bid - nb1) * 256 + threadIdx.x) >> 5);
   const int j = br_region ? 0 : (threadIdx.x & 31);
+  if (!br_region) {      // the 32-lane region runs over the list of the cubes and cylinders (lf_nbr), not over all factors
+    if (f >= G.n_nbr) return;
+    f = G.lf_nbr[f];
+  }
   if (f >= G.n_lf) return;
   const int type = G.lf_type[f];
   if ((type == FT_BR) != br_region) return;
@@ -730,7 +736,6 @@ void launch_pose_adj(const GraphDev& G, hipStream_t s) {
   if (G.P > 0) hipLaunchKernelGGL(k_pose_adj, dim3(G.P), dim3(256), (size_t)G.adj_words * sizeof(unsigned), s, G);
 }
 
-template <bool LISTED>
 __device__ __forceinline__ void k_schur_body(const GraphDev& G, int pj, int yb) {
   __shared__ double schur_tile[6][192];
   __shared__ long long pj_ed[SCHUR_PJ_CAP];
@@ -742,20 +747,16 @@ __device__ __forceinline__ void k_schur_body(const GraphDev& G, int pj, int yb) 
   // relative-pose factor with pose j — only those blocks of the strip are non-zero, all others are written as zeros unseen
   unsigned* adj = reinterpret_cast<unsigned*>(schur_slot + (G.L + 7) / 8 * 8);
   const int adj_words = (G.P + 31) / 32 + 1;
-  constexpr bool listed = LISTED;               // pair lists (HostGraph::build_schur_pairs): nothing to look up
-  if (!listed) {
-    for (int t = tid; t < G.L; t += 256) schur_slot[t] = -1;
-    __syncthreads();
-  }
+  for (int t = tid; t < G.L; t += 256) schur_slot[t] = -1;
+  __syncthreads();
   // (the bitmap depends on the topology only: k_pose_adj builds it once per change of the graph, not in every pass)
   for (int t = tid; t < adj_words; t += 256) adj[t] = G.pose_adj[(size_t)pj * G.adj_words + t];
   const int b0 = G.pose_ptr[pj], nb = G.pose_ptr[pj + 1] - b0;
-  if (!listed)
-    for (int q = tid; q < nb; q += 256) {
-      const int l = G.pose_lms[b0 + q];
-      if (q == 0 || G.pose_lms[b0 + q - 1] != l) schur_slot[l] = (short)q;
-      if (q < SCHUR_PJ_CAP) { pj_lm[q] = l; pj_ed[q] = G.pose_ed[b0 + q]; }
-    }
+  for (int q = tid; q < nb; q += 256) {
+    const int l = G.pose_lms[b0 + q];
+    if (q == 0 || G.pose_lms[b0 + q - 1] != l) schur_slot[l] = (short)q;
+    if (q < SCHUR_PJ_CAP) { pj_lm[q] = l; pj_ed[q] = G.pose_ed[b0 + q]; }
+  }
   __syncthreads();
   const int sub = tid & 7;
   // rows below the profile of this column's tile are structurally zero and stay untouched (zero since the last change of profile)
@@ -816,29 +817,8 @@ __device__ __forceinline__ void k_schur_body(const GraphDev& G, int pj, int yb) 
         }
       }
     }
-    if (listed) {
-      // own share of the block's pair list, two pairs at a time: F_x E_y^T
-      const int q0 = G.sp_idx[2 * ((size_t)pj * G.sp_w + (pi - pj))], q1 = q0 + G.sp_idx[2 * ((size_t)pj * G.sp_w + (pi - pj)) + 1];
-      for (int x = q0 + sub; x < q1; x += 8) {
-        const long long ex = G.sp_pairs[2 * (size_t)x], ey = G.sp_pairs[2 * (size_t)x + 1];
-        const int D = (int)(ex & 15);
-        const double* F = G.ebuf + (ex >> 4) + 6 * D;
-        const double* E = G.ebuf + (ey >> 4);
-        {
-          for (int k = 0; k < D; ++k) {
-            double fk[6], ek[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) { fk[a] = F[a * D + k]; ek[a] = E[a * D + k]; }
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-              for (int c = 0; c < 6; ++c) acc[6 * a + c] -= fk[a] * ek[c];
-          }
-        }
-      }
-    }
     // own share of pose i's list, three entries at a time: first all index loads and LDS look-ups, then the records
-    const int a0 = listed ? 0 : G.pose_ptr[pi], a1 = listed ? 0 : G.pose_ptr[pi + 1];
+    const int a0 = G.pose_ptr[pi], a1 = G.pose_ptr[pi + 1];
     for (int x0 = a0 + sub; x0 < a1; x0 += 24) {
       int sl[3];
       long long ed[3];
@@ -925,14 +905,157 @@ __global__ __launch_bounds__(256) void k_schur(GraphDev G, int p_first) {
     if (blockIdx.y == 0) k_pad_rhs_body(G, x - G.P);
     return;
   }
-  k_schur_body<false>(G, x, blockIdx.y);
+  k_schur_body(G, x, blockIdx.y);
 }
 __global__ __launch_bounds__(256) void k_schur_b(const GraphDev* __restrict__ Gs) {
   const GraphDev G = Gs[blockIdx.z];
-  k_schur_body<false>(G, blockIdx.x, blockIdx.y);
+  k_schur_body(G, blockIdx.x, blockIdx.y);
 }
-// the same from pair lists (every graph of the launch has them: launch_phase3_arrow_batched) — a kernel of its own: the walk's tables and
-// its three-deep staging would set this one's register budget too
+// the same from pair lists (every graph of the launch has them: launch_phase3_arrow_batched) — a kernel and a body of its own: the walk's
+// tables and its three-deep staging would set this one's register budget too, and nothing of them is read here.  No LDS table and no
+// barrier stands before the first load: the adjacency words of a chunk are two wave-uniform loads straight from pose_adj, so a workgroup
+// whose chunk is empty (on a strip that fits one chunk, every workgroup y >= 1) goes from its GraphDev to the zero fill in two round
+// trips.  A lane's dependent chain is (start, count) of its block -> its pair entries -> the records: the two index words come in one
+// 8-byte load, up to three pair entries (24 pairs per block) in three 16-byte loads issued together, and the records two columns at a
+// time.  The arithmetic is the walk's and the parent pair loop's: pairs in list order, columns k ascending, acc -= f e as one fma.
+constexpr int SCHUR_KC = 2;         // record columns loaded together: 2 x 12 loads in flight per lane at 162 VGPRs (3 columns spill at three waves per SIMD)
+
+// KC columns of one pair's F and E: all their loads first, then the products column by column.  The records are addressed by 32-bit byte
+// offsets off the one (uniform) base of ebuf — twelve row offsets in twelve registers instead of twenty-four; build_schur_pairs lists
+// pairs only while every record lies below 4 GB.
+template <int KC>
+__device__ __forceinline__ void schur_pair_cols(const char* __restrict__ ebase, unsigned fb, unsigned eb, int D, int k0, double (&acc)[36]) {
+  double fk[KC][6], ek[KC][6];
+#pragma unroll
+  for (int u = 0; u < KC; ++u)
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      const unsigned o = (unsigned)(a * D + k0) * 8u;
+      fk[u][a] = *reinterpret_cast<const double*>(ebase + (fb + o) + 8 * u);
+      ek[u][a] = *reinterpret_cast<const double*>(ebase + (eb + o) + 8 * u);
+    }
+#pragma unroll
+  for (int u = 0; u < KC; ++u)
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc[6 * a + c] = fma(-fk[u][a], ek[u][c], acc[6 * a + c]);
+}
+__device__ __forceinline__ void k_schur_listed_body(const GraphDev& G, int pj, int yb) {
+  __shared__ double schur_tile[6][192];
+  if (pj >= G.P) return;            // (a batched launch covers the largest graph)
+  if (6 * pj + 5 < G.col0) return;  // incremental re-factorisation: this pose's columns hold the factor of the last solve
+  const int tid = threadIdx.x;
+  const int sub = tid & 7;
+  const unsigned* __restrict__ adj = G.pose_adj + (size_t)pj * G.adj_words;      // (k_pose_adj: topology only)
+  // rows below the profile of this column's tile are structurally zero and stay untouched (zero since the last change of profile)
+  int p_end = G.P;
+  if (G.prof) {
+    const int rows = (G.prof[(6 * pj + 5) / NB] + 1) * NB;      // (the profile is monotone: the later of the column's two tiles)
+    p_end = min(G.P, (rows + 5) / 6);
+  }
+  for (int pi0 = pj + 32 * yb; pi0 < p_end; pi0 += 32 * (int)gridDim.y) {
+    const int nval = 6 * min(32, G.P - pi0);
+    double* Sb = G.S + (size_t)(6 * pj) * G.ld + 6 * (size_t)pi0;
+    double* S0b = G.S0 + (size_t)(6 * pj) * G.ld + 6 * (size_t)pi0;      // second copy for the joint solve (save_S0)
+    const int w = pi0 >> 5, sh = pi0 & 31;
+    const unsigned aw0 = adj[w], aw1 = adj[w + 1];      // (w + 1 < adj_words: the row has one word of slack)
+    const unsigned m = sh ? ((aw0 >> sh) | (aw1 << (32 - sh))) : aw0;      // poses pi0 .. pi0 + 31
+    if (m == 0u) {
+      for (int e = tid; e < 6 * 192; e += 256) {
+        const int c = e / 192, r = e % 192;
+        if (r < nval && 6 * pj + c >= G.col0) {
+          Sb[(size_t)c * G.ld + r] = 0.0;
+          if (G.save_S0) S0b[(size_t)c * G.ld + r] = 0.0;
+        }
+      }
+      continue;
+    }
+    const int pi = pi0 + (tid >> 3);
+    const bool live = pi < G.P && ((m >> (tid >> 3)) & 1u);
+    double acc[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) acc[k] = 0.0;
+    if (live) {
+      // (start, count) of the block's pair list first: the chain behind it is the long one
+      const int2 qc = *reinterpret_cast<const int2*>(G.sp_idx + 2 * ((size_t)pj * G.sp_w + (pi - pj)));
+      if (sub == 0) {
+        if (pi == pj) {
+#pragma unroll
+          for (int k = 0; k < 36; ++k) acc[k] = G.pose_H[36 * (size_t)pi + k];
+        } else {
+          for (int q = G.pose_bt_ptr[pi]; q < G.pose_bt_ptr[pi + 1]; ++q) {
+            const int ent = G.pose_bt[q];
+            const int b = ent >> 1, role = ent & 1;
+            const int other = role ? G.bt_i[b] : G.bt_j[b];
+            if (other != pj) continue;
+            const double* J = G.bt_J0 + 36 * (size_t)b;
+            if (role == 1) {   // pose i is the second key: J_i = diag(w), J_j = J0
+#pragma unroll
+              for (int a = 0; a < 6; ++a) {
+                const double w = 1.0 / G.bt_sigma[6 * b + a];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) acc[6 * a + c] += w * J[6 * a + c];
+              }
+            } else {           // pose i is the first key: J_i = J0, J_j = diag(w)
+#pragma unroll
+              for (int c = 0; c < 6; ++c) {
+                const double w = 1.0 / G.bt_sigma[6 * b + c];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[6 * a + c] += J[6 * c + a] * w;
+              }
+            }
+          }
+        }
+      }
+      // own share of the block's pair list (x = q0 + sub, + 8, ...), three entries at a time: F_x E_y^T
+      const int q0 = qc.x, q1 = qc.x + qc.y;
+      const longlong2* __restrict__ prs = reinterpret_cast<const longlong2*>(G.sp_pairs);
+      const char* __restrict__ ebase = reinterpret_cast<const char*>(G.ebuf);
+      for (int x0 = q0 + sub; x0 < q1; x0 += 24) {
+        const longlong2 z2 = longlong2{0, 0};
+        const longlong2 e0 = prs[x0];
+        const longlong2 e1 = x0 + 8 < q1 ? prs[x0 + 8] : z2;
+        const longlong2 e2 = x0 + 16 < q1 ? prs[x0 + 16] : z2;
+#pragma unroll 1
+        for (int u = 0; u < 3 && x0 + 8 * u < q1; ++u) {
+          const longlong2 e = u == 0 ? e0 : (u == 1 ? e1 : e2);
+          const int D = (int)(e.x & 15);
+          const unsigned fb = ((unsigned)(e.x >> 4) + 6u * D) * 8u, eb = (unsigned)(e.y >> 4) * 8u;
+          int k = 0;
+#pragma unroll 1
+          for (; k + SCHUR_KC <= D; k += SCHUR_KC) schur_pair_cols<SCHUR_KC>(ebase, fb, eb, D, k, acc);
+#pragma unroll 1
+          for (; k < D; ++k) schur_pair_cols<1>(ebase, fb, eb, D, k, acc);
+        }
+      }
+    }
+    // sum over the eight lanes of the group on the vector ALU (DPP: quad butterflies, then the mirrored half row)
+#pragma unroll
+    for (int k = 0; k < 36; ++k) {
+      acc[k] += dpp_f64<0xB1>(acc[k]);     // quad_perm [1,0,3,2]
+      acc[k] += dpp_f64<0x4E>(acc[k]);     // quad_perm [2,3,0,1]
+      acc[k] += dpp_f64<0x141>(acc[k]);    // row_half_mirror: lane i <-> 7 - i of each eight
+    }
+    // through an LDS tile to full-line stores: 192 consecutive doubles per S column and workgroup
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+      if (sub == c) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) schur_tile[c][6 * (tid >> 3) + a] = acc[6 * a + c];
+      }
+    __syncthreads();
+    for (int e = tid; e < 6 * 192; e += 256) {
+      const int c = e / 192, r = e % 192;
+      if (r < nval && 6 * pj + c >= G.col0) {      // (a pose straddling the first dirty tile column: only its columns inside it)
+        Sb[(size_t)c * G.ld + r] = schur_tile[c][r];
+        if (G.save_S0) S0b[(size_t)c * G.ld + r] = schur_tile[c][r];
+      }
+    }
+    __syncthreads();      // the tile is reused by the next chunk
+  }
+}
+// k_schur_lb: k_schur_listed_body for every robot of a batched exact pass.
 // xcd != 0: the workgroups are renumbered so that the ones the hardware deals to one XCD (linear id mod 8) cover a CONTIGUOUS range of
 // (robot, chunk, pose column) — with eight robots, one robot per XCD: a landmark's E / F records are read by every pose column that
 // observes it, and with consecutive columns dealt round-robin every XCD's L2 fetched every record (PMC: 182 MB fetched per launch for
@@ -951,7 +1074,7 @@ __global__ __launch_bounds__(256) void k_schur_lb(const GraphDev* __restrict__ G
     z = (int)(l2 / ((long long)gridDim.x * gridDim.y));
   }
   const GraphDev G = Gs[z];
-  k_schur_body<true>(G, x, y);
+  k_schur_listed_body(G, x, y);
 }
 
 // padding (identity) between 6P and T*NB, and the RHS row (-g) at row T*NB
@@ -1784,7 +1907,6 @@ static inline unsigned blocks_for(long long n, int bs) { return (unsigned)((n + 
 
 void init_solver_kernels() {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_b), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_lb), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);   // 60000 landmarks (the capacity check in HostGraph::upload_new) beside 12 KB of static LDS
 }
 void launch_relin(const GraphDev& G, hipStream_t s) {
@@ -1795,7 +1917,7 @@ void launch_linearize(const GraphDev& G, hipStream_t s) {
   const int npf = G.n_prior + G.n_between + G.n_ghost;
   if (G.n_lf > 0) {
     const int nb0 = npf > 0 ? (int)blocks_for(npf, 256) : 0;
-    hipLaunchKernelGGL(k_lin_lf, dim3(nb0 + blocks_for(G.n_lf, 256) + blocks_for(32LL * G.n_lf, 256)), dim3(256), 0, s, G, nb0, (int)blocks_for(G.n_lf, 256));
+    hipLaunchKernelGGL(k_lin_lf, dim3(nb0 + blocks_for(G.n_lf, 256) + blocks_for(32LL * G.n_nbr, 256)), dim3(256), 0, s, G, nb0, (int)blocks_for(G.n_lf, 256));
   } else if (npf > 0) {
     hipLaunchKernelGGL(k_lin_pose_factors, dim3(blocks_for(npf, 128)), dim3(128), 0, s, G);
   }
@@ -1878,10 +2000,10 @@ void launch_phase3_arrow_batched(const GraphDev* d, const GraphDev* h, int n, hi
     int split = 1;
     bool listed = true;
     for (int i = 0; i < n; ++i) { split = std::max(split, h[i].schur_split > 0 ? h[i].schur_split : 2); listed = listed && h[i].sp_idx != nullptr; }
-    const size_t lds = (size_t)((L + 7) / 8 * 8) * sizeof(short) + (size_t)((P + 31) / 32 + 1) * sizeof(unsigned);
     static const int schur_xcd = getenv("SLIDE_SCHUR_XCD") ? atoi(getenv("SLIDE_SCHUR_XCD")) : 0;
-    if (listed) hipLaunchKernelGGL(k_schur_lb, dim3(P, split > 0 ? split : 1, n), dim3(256), lds, s, d, schur_xcd);
-    else hipLaunchKernelGGL(k_schur_b, dim3(P, split > 0 ? split : 1, n), dim3(256), lds, s, d);
+    if (listed) hipLaunchKernelGGL(k_schur_lb, dim3(P, split > 0 ? split : 1, n), dim3(256), 0, s, d, schur_xcd);      // (no table in LDS)
+    else hipLaunchKernelGGL(k_schur_b, dim3(P, split > 0 ? split : 1, n), dim3(256),
+                            (size_t)((L + 7) / 8 * 8) * sizeof(short) + (size_t)((P + 31) / 32 + 1) * sizeof(unsigned), s, d);
     hipLaunchKernelGGL(k_pad_rhs_b, dim3(blocks_for(pad, 256), 1, n), dim3(256), 0, s, d);
   }
   launch_border_assemble_batched(d, h, n, s);
@@ -1892,11 +2014,12 @@ __global__ void k_shared_pack_b(const GraphDev* __restrict__ Gs, int what, BufPt
 // phase 0: relinearise, linearise, per-landmark partial sums, pack H_ll / g_l of the shared slots
 void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack, const RobustDev* dR) {
   int L = 0, P = 0, slots = 0, npf = 0;
-  long long nlf = 0;
+  long long nlf = 0, nnbr = 0;
   for (int i = 0; i < n; ++i) {
     L = std::max(L, h[i].L); P = std::max(P, h[i].P); slots = std::max(slots, h[i].n_slots);
     npf = std::max(npf, h[i].n_prior + h[i].n_between + h[i].n_ghost);
     nlf = std::max<long long>(nlf, h[i].n_lf);
+    nnbr = std::max<long long>(nnbr, h[i].n_nbr);
   }
   BufPtrs B{};
   for (int i = 0; i < n; ++i) B.p[i] = bufs[i];
@@ -1904,7 +2027,7 @@ void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* 
   if (dR) launch_robust_reweight_batched(d, dR, h, n, s);      // (only while the batch has a robust loss: the weights at the point the factors are linearised at)
   if (nlf > 0) {
     const int nb0 = npf > 0 ? (int)blocks_for(npf, 256) : 0;
-    hipLaunchKernelGGL(k_lin_lf_b, dim3(nb0 + blocks_for(nlf, 256) + blocks_for(32LL * nlf, 256), 1, n), dim3(256), 0, s, d, nb0, (int)blocks_for(nlf, 256));
+    hipLaunchKernelGGL(k_lin_lf_b, dim3(nb0 + blocks_for(nlf, 256) + blocks_for(32LL * nnbr, 256), 1, n), dim3(256), 0, s, d, nb0, (int)blocks_for(nlf, 256));
   } else if (npf > 0) {
     hipLaunchKernelGGL(k_lin_pose_factors_b, dim3(blocks_for(npf, 128), 1, n), dim3(128), 0, s, d);
   }
