@@ -342,6 +342,16 @@ void* orc_backend_create(const OrcParams* p, int num_robots) {
   return b;
 }
 void orc_backend_destroy(void* h) { delete (Backend*)h; }
+// K of the three getSubmap gates (the reference hard-codes 50 / 30 / 1000: cylinderMapManager.cpp:230, cubeMapManager.cpp:61,
+// ellipsoidMapManager.cpp:65; the product takes them as knn_cylinder / knn_cube / knn_ellipsoid) — for tests of the gate at other K
+void orc_backend_set_knn(void* h, int k_cyl, int k_cube, int k_ell) {
+  Backend* b = (Backend*)h;
+  b->cylMap.K = k_cyl; b->cubeMap.K = k_cube; b->ellMap.K = k_ell;
+}
+void orc_backend_get_knn(void* h, int* out3) {
+  Backend* b = (Backend*)h;
+  out3[0] = b->cylMap.K; out3[1] = b->cubeMap.K; out3[2] = b->ellMap.K;
+}
 
 static void emit(const FrameResult& r, double* out7, int* cm, int* bm, int* em, int* cid, int* bid, int* eid,
                  double* timers) {

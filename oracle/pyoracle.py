@@ -288,6 +288,15 @@ class OracleBackend:
         return dict(status=int(st), pose7=out7, cyl_match=cm, cube_match=bm, ell_match=em, cyl_id=cid, cube_id=bid,
                     ell_id=eid, t_assoc=tm[0], t_graph=tm[1])
 
+    def set_knn(self, k_cyl, k_cube, k_ell):
+        """K of the three submap gates (defaults 50 / 30 / 1000, the reference's constants)."""
+        self.L.orc_backend_set_knn(self.h, C.c_int(int(k_cyl)), C.c_int(int(k_cube)), C.c_int(int(k_ell)))
+
+    def knn(self):
+        out = np.zeros(3, np.int32)
+        self.L.orc_backend_get_knn(self.h, _p(out))
+        return tuple(int(k) for k in out)
+
     def ingest_solve(self):
         return int(self.L.orc_backend_ingest_solve(self.h))
 
