@@ -150,8 +150,8 @@ int slide_graph_stats(slide_graph_t* g, int64_t out5[5]);
 /* Sum of squared whitened residuals of every factor at the current estimate (= 2 x gtsam::NonlinearFactorGraph::error of the graph
  * ISAM2 holds): out4 = {total, prior factors, Between factors, landmark factors}.  Commits delta into the linearisation point and
  * relinearises (the estimate itself does not move); pending factors are merged first.  The sum is that of the system as
- * linearised: while a robust loss is set (slide_graph_set_robust_loss) that is the reweighted system, a selected factor entering
- * with w(s) s^2. */
+ * linearised: while a robust loss is set (slide_graph_set_robust_loss, slide_graph_set_observation_loss) that is the reweighted
+ * system, a selected factor entering with w(s) s^2. */
 int slide_graph_chi2(slide_graph_t* g, double out4[4]);
 /* ---- Robust loss on the loop-closure and relative-measurement factors: iteratively reweighted least squares ---------------------
  * No counterpart in the reference, whose closures are plain Between factors with sigmas of noise_model_odom_vec * 0.01
@@ -183,6 +183,34 @@ int slide_graph_set_robust_loss(slide_graph_t* g, int kind, double param, int cl
  * Factors added after the last solve are not listed yet.  SLIDE_ERR_INVALID before the first solve. */
 int slide_graph_get_closure_weights(slide_graph_t* g, int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx,
                                     int32_t* kind, double* weight, double* s2, int* n_out);
+/* ---- Robust loss on the landmark observation factors: iteratively reweighted least squares -------------------------------------
+ * No counterpart in the reference, which adds every match of the per-frame data association as a plain factor: a false match
+ * inside the association's gate pulls its pose and its landmark with the full weight of a true one.  In GTSAM:
+ * noiseModel::Robust::Create(mEstimator::...::Create(param), base) on the BearingRange / Cube / Cylinder factors.
+ * For a selected factor with whitened residual r at the linearisation point (3 rows under bearing_range_sigma, a cube's 9 under its
+ * own sigmas, a cylinder's 7 under cylinder_sigma), s^2 = |r|^2 and w = mEstimator::weight(s) as listed above (same kinds, default
+ * parameters and floor w >= 1e-12); the factor enters the step as sqrt(w) [r | J] (Robust::WhitenSystem).  The scaling is fused
+ * into the linearisation kernel: no further launch, and w = 1 leaves the factor's linearisation bit for bit.
+ * kind 0 switches the loss off (the default: launches and results are then what they are without this call); param <= 0 takes the
+ * default; class_mask bit 0 selects the bearing-range factors (point / ellipsoid landmarks), bit 1 the cube, bit 2 the cylinder
+ * factors.  Independent of slide_graph_set_robust_loss; both may be set.  A factor's weight is taken exactly when the factor is
+ * relinearised: an incremental slide_graph_solve that keeps a factor's linearisation keeps the weight inside it.  Covers the factors
+ * already added and those added later, in slide_graph_gauss_newton, slide_graph_solve and so the streaming back-end.  Every call
+ * (kind 0 included) drops the resident factor, as slide_graph_chi2 does: the next solve relinearises everything.  slide_graph_chi2,
+ * the marginals, the information gain and the Mahalanobis gate describe the reweighted system.
+ * A landmark all of whose observations are down-weighted to the floor has an H_ll of order 1e-12: there is no guard of its own for
+ * it, the solve reports it as it reports any near-singular landmark block.
+ * SLIDE_ERR_INVALID: kind outside 0 .. 4, a class_mask bit other than 0 .. 2, a param that is not a number, a graph that has joined
+ * a batch.  Single-graph path only: while a loss is set, slide_graph_join_chol_batch, slide_graph_dist_phase and
+ * slide_graph_dist_pass_local return SLIDE_ERR_INVALID (the sharded and joint passes do not carry an observation loss). */
+int slide_graph_set_observation_loss(slide_graph_t* g, int kind, double param, int class_mask);
+/* What the graph has come to think of its observations: every landmark factor in insertion order with its pose (robot, pose_idx),
+ * its landmark (cls: SLIDE_CLS_*, lm_idx), the weight w and the squared whitened norm s^2 (taken before the scaling) of its last
+ * linearisation.  w = 1 when no loss was set then or the factor's class was not selected; s^2 is reported all the same.  One
+ * read-back.  Any output pointer may be NULL; at most cap entries are written, *n_out is the full count.  Factors added after the
+ * last solve are not listed yet.  SLIDE_ERR_INVALID before the first solve. */
+int slide_graph_get_observation_weights(slide_graph_t* g, int cap, int32_t* robot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx,
+                                        double* weight, double* s2, int* n_out);
 /* isam->update(fgraph, fvalues) (graph.cpp:262) throws when a factor names a key that is in neither the graph nor fvalues, and when a
  * value is inserted under a key that exists already.  Here such an entry is refused, the rest of the update is merged, and the call
  * that consumed it (solve, gauss_newton, dist_phase 0 / 20, set_shared, set_ghosts, chol_batch_pass) returns SLIDE_ERR_INVALID with the

@@ -340,6 +340,27 @@ class SemanticFactorGraph {
     return out;
   }
 
+  // Robust loss on the landmark observation factors (slide_graph_set_observation_loss; no counterpart in the reference — GTSAM's
+  // noiseModel::Robust on the BearingRange / Cube / Cylinder factors): kinds and defaults as setRobustLoss, independent of it.
+  void setObservationLoss(int kind, double param = 0.0, bool points = true, bool cubes = true, bool cylinders = true) {
+    detail::check(slide_graph_set_observation_loss(g_, kind, param, (points ? 1 : 0) | (cubes ? 2 : 0) | (cylinders ? 4 : 0)), "setObservationLoss");
+  }
+  // slide_graph_get_observation_weights: every landmark factor in insertion order with the weight and (unscaled) squared whitened
+  // norm of its last linearisation.  cls: SLIDE_CLS_*.  Call it after solve().
+  struct ObservationWeight { size_t poseIdx, robot; int cls; size_t lmIdx; double weight, s2; };
+  std::vector<ObservationWeight> observationWeights() const {
+    int n = 0;
+    detail::check(slide_graph_get_observation_weights(g_, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n), "observationWeights");
+    std::vector<int32_t> rb(n + 1), cl(n + 1);
+    std::vector<uint64_t> pi(n + 1), li(n + 1);
+    std::vector<double> w(n + 1), s2(n + 1);
+    int m = 0;
+    detail::check(slide_graph_get_observation_weights(g_, n, rb.data(), pi.data(), cl.data(), li.data(), w.data(), s2.data(), &m), "observationWeights");
+    std::vector<ObservationWeight> out((size_t)(m < n ? m : n));
+    for (size_t k = 0; k < out.size(); ++k) out[k] = ObservationWeight{(size_t)pi[k], (size_t)rb[k], (int)cl[k], (size_t)li[k], w[k], s2[k]};
+    return out;
+  }
+
   slide_graph_t* handle() const { return g_; }
 
  protected:

@@ -44,6 +44,7 @@ EXPORTS = [
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
     "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
     "slide_graph_set_robust_loss", "slide_graph_get_closure_weights",
+    "slide_graph_set_observation_loss", "slide_graph_get_observation_weights",
     "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
     "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis",
 ]
@@ -459,9 +460,37 @@ class SlideGraph:
         return {"from_robot": fr[:k].copy(), "from_idx": fi[:k].copy(), "to_robot": tr[:k].copy(), "to_idx": ti[:k].copy(),
                 "kind": kd[:k].copy(), "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
 
+    def set_observation_loss(self, kind, param=0.0, points=True, cubes=True, cylinders=True):
+        """slide_graph_set_observation_loss (GTSAM's noiseModel::Robust on the bearing-range / cube / cylinder factors, iteratively
+        reweighted inside the linearisation kernel): kinds, names and defaults as set_robust_loss; independent of it.  Covers
+        factors already added and added later; the next solve relinearises everything."""
+        if kind is None or isinstance(kind, str):
+            if kind not in self.ROBUST_KINDS:
+                raise ValueError(f"observation loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
+            kind = self.ROBUST_KINDS[kind]
+        mask = (1 if points else 0) | (2 if cubes else 0) | (4 if cylinders else 0)
+        _check(self.L.slide_graph_set_observation_loss(self.h, C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+
+    def observation_weights(self, cap=None):
+        """slide_graph_get_observation_weights: every landmark factor in insertion order.  Returns a dict of arrays: robot, pose_idx,
+        cls (SLIDE_CLS_*), lm_idx, weight, s2 (weight and unscaled squared whitened norm of the factor's last linearisation; weight 1
+        where no loss applied) and n, the full count (cap: write at most that many)."""
+        n = C.c_int(0)
+        if cap is None:
+            _check(self.L.slide_graph_get_observation_weights(self.h, C.c_int(0), None, None, None, None, None, None, C.byref(n)))
+            cap = n.value
+        m = max(int(cap), 1)
+        rb, cl = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        pi, li = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+        w, s2 = np.zeros(m), np.zeros(m)
+        _check(self.L.slide_graph_get_observation_weights(self.h, C.c_int(int(cap)), _p(rb), _p(pi), _p(cl), _p(li), _p(w), _p(s2), C.byref(n)))
+        k = min(int(cap), n.value)
+        return {"robot": rb[:k].copy(), "pose_idx": pi[:k].copy(), "cls": cl[:k].copy(), "lm_idx": li[:k].copy(),
+                "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
+
     def chi2(self):
         """Sum of squared whitened residuals at the current estimate: dict(total, prior, between, landmark).  While a robust loss
-        is set: of the reweighted system."""
+        is set (on the closures or on the observations): of the reweighted system."""
         out = np.zeros(4)
         _check(self.L.slide_graph_chi2(self.h, _p(out)))
         return dict(total=out[0], prior=out[1], between=out[2], landmark=out[3])

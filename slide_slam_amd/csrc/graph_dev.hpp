@@ -153,4 +153,14 @@ struct RobustDev {
   double param;                     // k, k, c, Phi
 };
 
+// Robust loss on the landmark observation factors (k_lin_lf<true>): the record [r | Jp | Jl] of a selected factor enters jbuf as
+// sqrt(w) [r | Jp | Jl], w the loss's weight at s = |r|_2 of the factor's whitened residual at its linearisation point.  Like
+// RobustDev a view of its own beside GraphDev, which keeps its layout: only the linearisation of a graph with a loss takes it.
+struct ObsLossDev {
+  double* lf_w; double* lf_s2;      // 1 ; 1 per landmark factor: weight and (unscaled) s^2 of the factor's last linearisation under a loss
+  int kind;                         // 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure, 4 DCS
+  int mask;                         // bit 0: bearing-range, bit 1: cube, bit 2: cylinder factors
+  double param;                     // k, k, c, Phi
+};
+
 }  // namespace sl

@@ -2138,6 +2138,10 @@ int HostGraph::upload_new() {
   UP(d_lf_joff, h_lf_joff, up_lf, 1);
   UP(d_lf_eoff, h_lf_eoff, up_lf, 1);
   UP(d_lf_nbr, h_lf_nbr, up_nbr, 1);
+  if (ol_arrays) {      // (an observation loss was set at some time: room for the factors' weights; a kept record keeps its entry)
+    if (d_lf_w.ensure(std::max<size_t>(nlf, 1), up_ol, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+    if (d_lf_s2.ensure(std::max<size_t>(nlf, 1), up_ol, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+  }
   UP(d_br_z, h_br_z, up_br, 4);
   UP(d_cu_z, h_cu_z, up_cu, 15);
   UP(d_cu_sigma, h_cu_sigma, up_cu, 9);
@@ -2477,6 +2481,7 @@ int HostGraph::upload_new() {
   up_P = Pn; up_L = Ln; up_pr = npr; up_bt = nbt; up_lf = nlf; up_gh = ngh;
   up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7; up_nbr = h_lf_nbr.size();
   if (rb_arrays) { up_rb = nbt; up_rbg = ngh; }
+  if (ol_arrays) up_ol = nlf;
 
   G.P = (int)Pn; G.L = (int)Ln;
   G.pose_val = d_pose_val.d; G.pose_delta = d_pose_delta.d; G.pose_est = d_pose_est.d;
@@ -2487,6 +2492,8 @@ int HostGraph::upload_new() {
   RB.bt_sigma0 = d_bt_sigma0.d; RB.bt_w = d_bt_w.d; RB.bt_s2 = d_bt_s2.d; RB.bt_kind = d_bt_kind.d;      // (null until a robust loss is set)
   RB.gh_sigma0 = d_gh_sigma0.d; RB.gh_w = d_gh_w.d; RB.gh_s2 = d_gh_s2.d;
   RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
+  OB.lf_w = d_lf_w.d; OB.lf_s2 = d_lf_s2.d;      // (null until an observation loss is set)
+  OB.kind = ol_kind; OB.mask = ol_mask; OB.param = ol_param;
   G.n_ghost = (int)ngh; G.gh_pose = d_gh_pose.d; G.gh_slot = d_gh_slot.d; G.gh_first = d_gh_first.d; G.gh_z = d_gh_z.d;
   G.gh_sigma = d_gh_sigma.d; G.gh_r = d_gh_r.d; G.gh_J = d_gh_J.d;
   G.n_gslots = (int)h_gslot_pose.size(); G.ghost_val = d_ghost_val.d; G.gslot_pose = d_gslot_pose.d;
@@ -2635,7 +2642,7 @@ int HostGraph::enqueue_iteration(bool lookahead, bool skip_relin, int c_d, int w
     const int idr = prof.id_of("k_robust_reweight");
     prof.begin(idr, s); launch_robust_reweight(G, RB, s); prof.end(s);
   }
-  STAGE(1, launch_linearize(G, s));
+  STAGE(1, launch_linearize(G, OB, s));
   STAGE(2, launch_landmark(G, 0, s));
   STAGE(3, launch_pose(G, s));
   STAGE(4, launch_schur(G, s));
@@ -2703,8 +2710,10 @@ int HostGraph::run_update(double relin_thr, int iterations) {
   cache_pose = -1;
   // Replaying a captured hipGraph removes the host launch cost (~250 launches + event traffic per pass) once the
   // SAME resident graph is solved again (batch Gauss-Newton, repeated solve() without new factors).
-  const bool same_as_prev = have_prev && std::memcmp(&G_prev, &G, sizeof(GraphDev)) == 0 && std::memcmp(&RB_prev, &RB, sizeof(RobustDev)) == 0;
-  const bool cap_ok = gexec && std::memcmp(&G_cap, &G, sizeof(GraphDev)) == 0 && std::memcmp(&RB_cap, &RB, sizeof(RobustDev)) == 0;
+  const bool same_as_prev = have_prev && std::memcmp(&G_prev, &G, sizeof(GraphDev)) == 0 && std::memcmp(&RB_prev, &RB, sizeof(RobustDev)) == 0 &&
+                            std::memcmp(&OB_prev, &OB, sizeof(ObsLossDev)) == 0;
+  const bool cap_ok = gexec && std::memcmp(&G_cap, &G, sizeof(GraphDev)) == 0 && std::memcmp(&RB_cap, &RB, sizeof(RobustDev)) == 0 &&
+                      std::memcmp(&OB_cap, &OB, sizeof(ObsLossDev)) == 0;
   static const bool env_graph = !(getenv("SLIDE_NO_GRAPH") && getenv("SLIDE_NO_GRAPH")[0] == '1');
   // two-stream look-ahead is implemented and parity-tested but measured SLOWER than the linear graph on MI355X
   // (the latency-critical diag+panel blocks queue behind the flood of update workgroups): opt-in only.
@@ -2713,6 +2722,7 @@ int HostGraph::run_update(double relin_thr, int iterations) {
   bool use_graph = graph_ok && (iterations > 1 || same_as_prev || cap_ok);
   G_prev = G;
   RB_prev = RB;
+  OB_prev = OB;
   have_prev = true;
   if (use_graph && !cap_ok) {
     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
@@ -2728,7 +2738,7 @@ int HostGraph::run_update(double relin_thr, int iterations) {
       const hipError_t ei = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
       (void)hipGraphDestroy(graph);
       if (ei != hipSuccess) { gexec = nullptr; (void)hipGetLastError(); use_graph = false; }
-      else { G_cap = G; RB_cap = RB; }
+      else { G_cap = G; RB_cap = RB; OB_cap = OB; }
     }
   }
   // Incremental re-factorisation (the streaming path: one update after a few new factors).  iSAM2 re-eliminates only the part of the
@@ -2925,7 +2935,7 @@ int HostGraph::enqueue_phase(int phase, double* d_buf) {
   const bool joint = pcg_iters > 0 && G.n_slots > 0 && !batch;      // un-batched joint solve: phases 31 / 32 / 33 follow phase 1
   if (phase == 0) {
     launch_relin(G, s);
-    launch_linearize(G, s);
+    launch_linearize(G, OB, s);      // (dist_phase refuses while an observation loss is set: OB.kind is 0 here)
     launch_landmark(G, 1, s);
     launch_shared_pack(G, 0, d_buf, s);
   } else if (phase == 1 || phase == 3 || phase == 4) {      // 3 / 4: the parts of phase 1 before / after the factor + solve
@@ -3011,12 +3021,17 @@ int HostGraph::launch_phase(int phase, double* d_buf) {
   return SLIDE_OK;
 }
 
+static int refuse_observation_loss(const char* who) {
+  g_last_error = std::string(who) + ": an observation loss is set on this graph; the sharded and joint paths do not carry it (slide_graph_set_observation_loss(g, 0, 0, 0) first)";
+  return SLIDE_ERR_INVALID;
+}
 static int refuse_robust(const char* who) {
   g_last_error = std::string(who) + ": a robust loss is set on this graph; the sharded and joint paths do not carry it (slide_graph_set_robust_loss(g, 0, 0, 0) first)";
   return SLIDE_ERR_INVALID;
 }
 int HostGraph::dist_phase(int phase, double* d_buf) {
   if (rb_kind != 0) return refuse_robust("dist_phase");
+  if (ol_kind != 0) return refuse_observation_loss("dist_phase");
   pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   hipStream_t s = stream;
   factor_valid = false;      // (the phases move linearisation points and factor into S on their own schedule)
@@ -3078,6 +3093,7 @@ int HostGraph::dist_phase(int phase, double* d_buf) {
 // the two exchanges as device-side sums between the batch's buffers — stream-ordered, one host synchronisation at the end.
 int HostGraph::dist_pass_local(double* d_buf) {
   if (rb_kind != 0) return refuse_robust("dist_pass_local");
+  if (ol_kind != 0) return refuse_observation_loss("dist_pass_local");
   pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   if (!batch) { g_last_error = "dist_pass_local: the graph is in no batch"; return SLIDE_ERR_INVALID; }
   wf_T = 0;      // (the pass moves the linearisation points: the last streaming solve's dp is no previous solution of the next)
@@ -3187,7 +3203,7 @@ int HostGraph::chi2(double* out4) {
   wf_T = 0;                           // (nor may the bounded back-substitution keep a block of the last solve's dp: it is folded in now)
   if (G.L) SL_HIP(hipMemsetAsync(G.lm_delta, 0, 9 * (size_t)G.L * sizeof(double), s));
   launch_robust_reweight(G, RB, s);       // (while a robust loss is set: the residuals summed below are the reweighted system's)
-  launch_linearize(G, s);
+  launch_linearize(G, OB, s);             // (likewise under an observation loss: its factors enter with w(s) s^2)
   note_linearisation();
   launch_estimate(G, s);
   if (d_covY.ensure(8, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
@@ -3259,6 +3275,56 @@ int HostGraph::get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_
     if (to_robot) to_robot[k] = key_robot(c.k1);
     if (to_idx) to_idx[k] = c.k1 & low;
     if (kind) kind[k] = h_bt_kind[c.bt];
+    if (weight) weight[k] = out[2 * (size_t)k];
+    if (s2) s2[k] = out[2 * (size_t)k + 1];
+  }
+  return SLIDE_OK;
+}
+// ---- robust loss (IRLS) on the landmark observation factors, fused into their linearisation ------------------------------------
+int HostGraph::set_observation_loss(int kind, double param, int class_mask) {
+  if (kind < 0 || kind > 4) { g_last_error = "set_observation_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
+  if (class_mask & ~7) { g_last_error = "set_observation_loss: class_mask has bit 0 (bearing-range), bit 1 (cube) and bit 2 (cylinder) only"; return SLIDE_ERR_INVALID; }
+  if (batch) { g_last_error = "set_observation_loss: the graph has joined a batch; the sharded and joint paths do not carry an observation loss"; return SLIDE_ERR_INVALID; }
+  if (!(param == param)) { g_last_error = "set_observation_loss: param is not a number"; return SLIDE_ERR_INVALID; }
+  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
+  ol_kind = kind;
+  ol_mask = kind ? class_mask : 0;
+  ol_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
+  OB.kind = ol_kind; OB.mask = ol_mask; OB.param = ol_param;
+  if (kind != 0 && !ol_arrays) { ol_arrays = true; topo_dirty = true; }      // (upload_new creates the weight arrays)
+  // the resident factor, the kept records and the last solution belong to the system as it was weighted: as after chi2(), the next
+  // solve relinearises and re-factors everything and keeps no block of dp
+  factor_valid = false;
+  wf_T = 0;
+  pred_valid = false; status_clean = false; cache_pose = -1;
+  return SLIDE_OK;
+}
+int HostGraph::get_observation_weights(int cap, int32_t* robot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2,
+                                       int* n_out) {
+  if (!lin_done) { g_last_error = "get_observation_weights: nothing was linearised yet (call solve first)"; return SLIDE_ERR_INVALID; }
+  const int n = (int)std::min(lin_lf, up_lf);      // (a factor added after the last solve has no linearisation to report)
+  *n_out = n;
+  const int m = std::min(n, std::max(cap, 0));
+  if (m == 0) return SLIDE_OK;
+  hipStream_t s = stream;
+  std::vector<double> out;
+  if (weight || s2) {
+    if (d_ol_out.ensure(2 * (size_t)m, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+    launch_observation_weights(G, OB, lin_ol_kind != 0, m, d_ol_out.d, s);
+    out.resize(2 * (size_t)m);
+    SL_HIP(hipMemcpyAsync(out.data(), d_ol_out.d, out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    SL_HIP(hipGetLastError());
+  }
+  std::vector<uint64_t> pkey, lkey;      // ids -> keys (the graph keeps the maps the other way round)
+  if (robot || pose_idx) { pkey.assign(h_pose_val.size() / 12, 0); for (const auto& kv : key2pose) pkey[kv.second] = kv.first; }
+  if (lm_idx) { lkey.assign(h_lm_type.size(), 0); for (const auto& kv : key2lm) lkey[kv.second] = kv.first; }
+  const uint64_t low = 0x00ffffffffffffffull;
+  for (int k = 0; k < m; ++k) {
+    if (robot) robot[k] = key_robot(pkey[h_lf_pose[k]]);
+    if (pose_idx) pose_idx[k] = pkey[h_lf_pose[k]] & low;
+    if (cls) cls[k] = h_lf_type[k] == FT_CYL ? SLIDE_CLS_CYLINDER : (h_lf_type[k] == FT_CUBE ? SLIDE_CLS_CUBE : SLIDE_CLS_ELLIPSOID);
+    if (lm_idx) lm_idx[k] = lkey[h_lf_lm[k]] & low;
     if (weight) weight[k] = out[2 * (size_t)k];
     if (s2) s2[k] = out[2 * (size_t)k + 1];
   }

@@ -468,6 +468,13 @@ class HostGraph {
   // weight and squared whitened norm of every loop-closure / relative-measurement factor at its last linearisation, insertion order
   int get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind, double* weight,
                           double* s2, int* n_out);
+  // Robust loss on the landmark observation factors (iteratively reweighted least squares, fused into the linearisation:
+  // k_lin_lf_robust).  kind 0: off; param <= 0: the loss's default; mask bit 0: bearing-range, bit 1: cube, bit 2: cylinder factors.
+  // Independent of set_robust_loss.  Single-graph path only.
+  int set_observation_loss(int kind, double param, int class_mask);
+  bool observation_loss_on() const { return ol_kind != 0; }
+  // weight and squared whitened norm of every landmark factor at its last linearisation, insertion order
+  int get_observation_weights(int cap, int32_t* robot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2, int* n_out);
   void set_incremental(bool on) { inc_enabled = on; }
   void incremental_stats(int64_t* out4) const { out4[0] = n_inc; out4[1] = n_full; out4[2] = last_cd; out4[3] = G.T; }
   // iSAM2's wildfire threshold on the back-substitution of a streaming update (ISAM2GaussNewtonParams::wildfireThreshold, 1e-3 in the
@@ -492,6 +499,7 @@ class HostGraph {
   Profiler prof;
   GraphDev G{};
   RobustDev RB{};                    // the robust loss's arrays and setting (null / 0 until a loss is set)
+  ObsLossDev OB{};                   // the observation loss's arrays and setting (null / 0 until one is set)
 
  private:
   int merge_pending();
@@ -543,7 +551,15 @@ class HostGraph {
   bool lin_done = false;                       // a linearisation ran; it covered lin_bt between factors under the loss lin_rb_kind / lin_rb_mask
   size_t lin_bt = 0;
   int lin_rb_kind = 0, lin_rb_mask = 0;
-  void note_linearisation() { lin_done = true; lin_bt = up_bt; lin_rb_kind = RB.kind; lin_rb_mask = RB.mask; }
+  void note_linearisation() { lin_done = true; lin_bt = up_bt; lin_rb_kind = RB.kind; lin_rb_mask = RB.mask; lin_lf = up_lf; lin_ol_kind = OB.kind; }
+  // observation loss.  lf_w / lf_s2 exist from the first time a loss is set on (ol_arrays) and grow with the landmark factors.
+  int ol_kind = 0, ol_mask = 0;
+  double ol_param = 0.0;
+  bool ol_arrays = false;
+  size_t up_ol = 0;                            // landmark factors the arrays hold
+  size_t lin_lf = 0;                           // the last linearisation covered lin_lf landmark factors, under the loss lin_ol_kind
+  int lin_ol_kind = 0;
+  DevArr<double> d_lf_w, d_lf_s2, d_ol_out;
   std::vector<uint64_t> h_gh_key;              // ghost factor -> key of its local pose
   size_t up_rbg = 0;                           // ghost factors the robust arrays hold (a batch's loss covers them)
   DevArr<double> d_gh_sigma0, d_gh_w, d_gh_s2;
@@ -663,6 +679,7 @@ class HostGraph {
   GraphDev G_cap{};
   GraphDev G_prev{};
   RobustDev RB_cap{}, RB_prev{};      // (the captured pass bakes the robust view in as well)
+  ObsLossDev OB_cap{}, OB_prev{};     // (and the observation loss's)
   struct PhaseGraph { hipGraphExec_t exec = nullptr; GraphDev G{}; double* buf = nullptr; };
   PhaseGraph phase_graph[5];             // captured launch sequences of dist_phase 0 / 1 / 2 and of phase 1's halves (3, 4)
   int enqueue_phase(int phase, double* d_buf);

@@ -11,7 +11,8 @@ namespace sl {
 // solver_kernels.hip
 void init_solver_kernels();   // one-time kernel attributes (call outside stream capture)
 void launch_relin(const GraphDev& G, hipStream_t s);
-void launch_linearize(const GraphDev& G, hipStream_t s);
+void launch_linearize(const GraphDev& G, const ObsLossDev& O, hipStream_t s);      // O.kind != 0: the landmark factors under the observation loss (same launch count)
+void launch_observation_weights(const GraphDev& G, const ObsLossDev& O, bool robust, int n, double* out2n, hipStream_t s);      // (weight, s^2) of landmark factors [0, n)
 void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s);      // ahead of launch_linearize while a robust loss is set (no launch otherwise)
 void launch_closure_weights(const GraphDev& G, const RobustDev& R, const int* idx, int n, double* out2n, hipStream_t s);   // (weight, s^2) of the listed between factors
 // the batch's robust loss (dR: the members' RobustDev table beside d): k_robust_reweight_b between k_relin_b and the linearisation

@@ -209,7 +209,24 @@ __device__ inline void cyl_err(const SE3& X, const double* q, const double* z, d
 // reference's central differences (one error evaluation per lane).  That region is launched over the graph's list of those factors
 // (GraphDev::lf_nbr, kept by the host as factors arrive): over all factors, seven of ten 32-lane groups of a SLAM graph loaded a type
 // and left, and only wavefronts whose two factors were both bearing-range left whole.
-__device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bid) {
+//
+// ROBUST (slide_graph_set_observation_loss; GTSAM's noiseModel::Robust on these factors, no counterpart in the reference): the record
+// is stored as sqrt(w) [r | Jp | Jl] (Robust::WhitenSystem), w = mEstimator::weight at s = |r|_2 of the whitened residual — all
+// k_landmark, k_pose, k_schur and k_chi2 ever read of the factor, so the fused scaling is the whole IRLS step.  The weight is taken
+// where the factor is linearised and under the same skip rule: a record an incremental update keeps keeps its weight.  A thread
+// of the bearing-range region holds its three residuals; in the 32-lane region every lane already receives lane 30's unperturbed
+// error, forms s^2 and w redundantly (no further cross-lane traffic) and scales what it stores, lane 30 records w and s^2.  w = 1
+// (a class the mask leaves out, or a residual inside the loss's quadratic part) leaves the record's bits: x * 1.0 == x.  The loss
+// is uniform over the launch: robust_weight's switch does not diverge.  ROBUST = false is the code as it was.
+__device__ __forceinline__ double robust_weight(int kind, double c, double s2);      // (with the closure loss, below)
+__device__ __forceinline__ double obs_loss_scale(const ObsLossDev& O, int type, int f, double s2, bool record) {
+  const bool sel = (O.mask >> (type - FT_BR)) & 1;
+  const double w = sel ? fmax(robust_weight(O.kind, O.param, s2), 1e-12) : 1.0;      // (the floor of the closure loss)
+  if (record) { O.lf_w[f] = w; O.lf_s2[f] = s2; }
+  return sqrt(w);
+}
+template <bool ROBUST>
+__device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, const ObsLossDev& O, int nb1, int bid) {
   const bool br_region = bid < nb1;
   int f = br_region ? (int)(bid * 256 + threadIdx.x) : (int)(((bid - nb1) * 256 + threadIdx.x) >> 5);
   const int j = br_region ? 0 : (threadIdx.x & 31);
@@ -228,6 +245,8 @@ __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bi
   const int col = j >> 1;                                // 0..14 perturbed tangent component, 15: none
   const double dl = G.numdiff_delta, fac = 1.0 / (2.0 * dl);
   const double d = (j & 1) ? -dl : dl;
+  double sq = 1.0;                                       // sqrt(w) of the factor (ROBUST)
+  auto sc = [&](double v) { if constexpr (ROBUST) return v * sq; else return v; };
   if (type == FT_BR) {
     // [GTSAM BearingRangeFactor<Pose3,Point3>] r = [sphere-local(z_b, b) ; rho - z_rho] / sigma
     const double* z = G.br_z + 4 * (size_t)slot;
@@ -237,7 +256,11 @@ __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bi
     const V3 b = (1.0 / rho) * q;
     double e2[2];
     sphere_local(V3{z[0], z[1], z[2]}, b, e2);
-    out[0] = e2[0] * w; out[1] = e2[1] * w; out[2] = (rho - z[3]) * w;
+    if constexpr (ROBUST) {
+      const double r0 = e2[0] * w, r1 = e2[1] * w, r2 = (rho - z[3]) * w;
+      sq = obs_loss_scale(O, FT_BR, f, r0 * r0 + r1 * r1 + r2 * r2, true);
+    }
+    out[0] = sc(e2[0] * w); out[1] = sc(e2[1] * w); out[2] = sc((rho - z[3]) * w);
     // D_q_pose = [hat(q), -I], D_q_point = R^T ; D_b_q = B(b)^T (I - b b^T)/rho ; D_rho_q = b^T
     V3 b1, b2;
     sphere_basis(b, b1, b2);
@@ -263,9 +286,9 @@ __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bi
         double s = 0, u = 0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) { s += Dm[3 * r + k] * Q.a[3 * k + j]; u += Dm[3 * r + k] * X.R.a[3 * j + k]; }
-        Jp[6 * r + j] = s * w;
-        Jp[6 * r + 3 + j] = -Dm[3 * r + j] * w;
-        Jl[3 * r + j] = u * w;
+        Jp[6 * r + j] = sc(s * w);
+        Jp[6 * r + 3 + j] = sc(-Dm[3 * r + j] * w);
+        Jl[3 * r + j] = sc(u * w);
       }
   } else if (type == FT_CUBE) {
     // cubeFactor.cpp:41-50; tangent: pose (6), cube pose (6), cube scale (3)
@@ -279,12 +302,18 @@ __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bi
     for (int k = 0; k < 3; ++k) cs[k] = lv[12 + k] + ((col == 12 + k) ? d : 0.0);
     double e[9];
     cube_err(retract(X, dX, G.chart), retract(C, dC, G.chart), cs, z, e);
+    if constexpr (ROBUST) {
+      double s2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) { const double q = __shfl(e[i], 30, 32) * (1.0 / sg[i]); s2 += q * q; }
+      sq = obs_loss_scale(O, FT_CUBE, f, s2, j == 30);
+    }
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
       const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
-      if (j == 30) out[i] = hx * w;
+      if (j == 30) out[i] = sc(hx * w);
       if ((j & 1) == 0 && col < 15) {
-        const double v = ((e[i] - hx) - (eo - hx)) * fac * w;
+        const double v = sc(((e[i] - hx) - (eo - hx)) * fac * w);
         if (col < 6) out[9 + 6 * i + col] = v;           // Jp
         else out[63 + 9 * i + col - 6] = v;               // Jl
       }
@@ -302,12 +331,18 @@ __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bi
     for (int k = 0; k < 7; ++k) q[k] = lv[k] + ((vi == k) ? d : 0.0);
     double e[7];
     cyl_err(retract(X, dX, G.chart), q, z, e);
+    if constexpr (ROBUST) {
+      double s2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < 7; ++i) { const double q = __shfl(e[i], 30, 32) * w; s2 += q * q; }
+      sq = obs_loss_scale(O, FT_CYL, f, s2, j == 30);
+    }
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32);
-      if (j == 30) out[i] = hx * w;
+      if (j == 30) out[i] = sc(hx * w);
       if ((j & 1) == 0 && col < 13) {
-        const double v = ((e[i] - hx) - (eo - hx)) * fac * w;
+        const double v = sc(((e[i] - hx) - (eo - hx)) * fac * w);
         if (col < 6) out[7 + 6 * i + col] = v;           // Jp
         else out[49 + 7 * i + jl] = v;                    // Jl
       }
@@ -318,11 +353,16 @@ __device__ __forceinline__ void k_lin_lf_body(const GraphDev& G, int nb1, int bi
 // not depend on each other, and a launch costs a streaming update ~8 us of its ~280)
 __global__ __launch_bounds__(256) void k_lin_lf(GraphDev G, int nb0, int nb1) {
   if ((int)blockIdx.x < nb0) k_lin_pose_factors_body(G, blockIdx.x * 256 + threadIdx.x);
-  else k_lin_lf_body(G, nb1, (int)blockIdx.x - nb0);
+  else k_lin_lf_body<false>(G, ObsLossDev{}, nb1, (int)blockIdx.x - nb0);
+}
+// the same launch while an observation loss is set (launch_linearize picks it from the setting; the pose factors are unchanged)
+__global__ __launch_bounds__(256) void k_lin_lf_robust(GraphDev G, ObsLossDev O, int nb0, int nb1) {
+  if ((int)blockIdx.x < nb0) k_lin_pose_factors_body(G, blockIdx.x * 256 + threadIdx.x);
+  else k_lin_lf_body<true>(G, O, nb1, (int)blockIdx.x - nb0);
 }
 __global__ __launch_bounds__(256) void k_lin_lf_b(const GraphDev* __restrict__ Gs, int nb0, int nb1) {
   if ((int)blockIdx.x < nb0) k_lin_pose_factors_body(Gs[blockIdx.z], blockIdx.x * 256 + threadIdx.x);
-  else k_lin_lf_body(Gs[blockIdx.z], nb1, (int)blockIdx.x - nb0);
+  else k_lin_lf_body<false>(Gs[blockIdx.z], ObsLossDev{}, nb1, (int)blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1913,11 +1953,13 @@ void launch_relin(const GraphDev& G, hipStream_t s) {
   if (G.P + G.L == 0) return;
   hipLaunchKernelGGL(k_relin, dim3(blocks_for(G.P + G.L, 256)), dim3(256), 0, s, G);
 }
-void launch_linearize(const GraphDev& G, hipStream_t s) {
+void launch_linearize(const GraphDev& G, const ObsLossDev& O, hipStream_t s) {
   const int npf = G.n_prior + G.n_between + G.n_ghost;
   if (G.n_lf > 0) {
     const int nb0 = npf > 0 ? (int)blocks_for(npf, 256) : 0;
-    hipLaunchKernelGGL(k_lin_lf, dim3(nb0 + blocks_for(G.n_lf, 256) + blocks_for(32LL * G.n_nbr, 256)), dim3(256), 0, s, G, nb0, (int)blocks_for(G.n_lf, 256));
+    if (O.kind != 0)
+      hipLaunchKernelGGL(k_lin_lf_robust, dim3(nb0 + blocks_for(G.n_lf, 256) + blocks_for(32LL * G.n_nbr, 256)), dim3(256), 0, s, G, O, nb0, (int)blocks_for(G.n_lf, 256));
+    else hipLaunchKernelGGL(k_lin_lf, dim3(nb0 + blocks_for(G.n_lf, 256) + blocks_for(32LL * G.n_nbr, 256)), dim3(256), 0, s, G, nb0, (int)blocks_for(G.n_lf, 256));
   } else if (npf > 0) {
     hipLaunchKernelGGL(k_lin_pose_factors, dim3(blocks_for(npf, 128)), dim3(128), 0, s, G);
   }
@@ -2288,6 +2330,28 @@ __global__ __launch_bounds__(128) void k_closure_weights_b(const GraphDev* __res
   }
 }
 
+// slide_graph_get_observation_weights: (weight, s^2) of the landmark factors [0, n) at their last linearisation.  robust: that
+// linearisation ran under a loss and recorded both (w = 1 for a class its mask left out); otherwise w = 1 and s^2 = |r|^2 of the
+// record, which is then unscaled.
+__global__ __launch_bounds__(128) void k_observation_weights(GraphDev G, ObsLossDev O, int robust, int n, double* __restrict__ out) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n || f >= G.n_lf) return;
+  if (robust) {
+    out[2 * (size_t)f] = O.lf_w[f];
+    out[2 * (size_t)f + 1] = O.lf_s2[f];
+  } else {
+    const double* r = G.jbuf + G.lf_joff[f];
+    const int m = lf_rows(G.lf_type[f]);
+    double s2 = 0.0;
+    for (int i = 0; i < m; ++i) s2 += r[i] * r[i];
+    out[2 * (size_t)f] = 1.0;
+    out[2 * (size_t)f + 1] = s2;
+  }
+}
+
+void launch_observation_weights(const GraphDev& G, const ObsLossDev& O, bool robust, int n, double* out2n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_observation_weights, dim3(blocks_for(n, 128)), dim3(128), 0, s, G, O, robust ? 1 : 0, n, out2n);
+}
 void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s) {
   if (R.kind == 0 || G.n_between == 0) return;
   hipLaunchKernelGGL(k_robust_reweight, dim3(blocks_for(G.n_between, 128)), dim3(128), 0, s, G, R);
