@@ -1345,7 +1345,9 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
     launch_border_apply(sys.data(), n, xloc, master);                // y -= W x_s
     launch_chol_bwd_batch(seg_sys.data(), (int)seg_sys.size(), master);      // L^T dp = y, all segments side by side
     launch_sep_pose_scatter_batched(d_Gs, hG.data(), n, xloc, master);
-    launch_arrow_finish_batched(d_Gs, hG.data(), n, sep_dp, d_sep_off, master);
+    bool slots_onto = true;
+    for (int i = 0; i < n; ++i) slots_onto = slots_onto && graphs[i]->lm_slot_onto;
+    launch_arrow_finish_batched(d_Gs, hG.data(), n, sep_dp, d_sep_off, master, slots_onto);
     launch_status_gather(d_Gs, n, d_status_all, master, sep_status, sep_nl > 0 ? lam_status : nullptr);      // (the separator's not-SPD / chain flags are reported with graph 0's)
     mark(5);
   }
@@ -2614,6 +2616,7 @@ int HostGraph::build_schur_pairs(hipStream_t s) {
   return SLIDE_OK;
 }
 int HostGraph::sync_lm_slot() {
+  lm_slot_onto = false;
   if (h_sh_lid.empty()) {            // no shared slots (single-robot graphs, replicas): nothing reads the table
     G.lm_slot = nullptr;
     return SLIDE_OK;
@@ -2622,6 +2625,11 @@ int HostGraph::sync_lm_slot() {
   std::vector<int> slot(std::max<size_t>(Ln, 1), -1);
   for (size_t i = 0; i < h_sh_lid.size(); ++i)
     if (h_sh_lid[i] >= 0 && (size_t)h_sh_lid[i] < Ln) slot[h_sh_lid[i]] = (int)i;
+  // every slot k_sep_lm_delta_b writes a delta for (sh_lid[i] >= 0) is the slot its landmark's entry leads back to: then the exact pass's
+  // back-substitution writes those deltas itself (launch_arrow_finish_batched)
+  lm_slot_onto = true;
+  for (size_t i = 0; i < h_sh_lid.size(); ++i)
+    if (h_sh_lid[i] >= 0 && ((size_t)h_sh_lid[i] >= Ln || slot[h_sh_lid[i]] != (int)i)) lm_slot_onto = false;
   if (d_lm_slot.ensure(slot.size(), 0, stream) != SLIDE_OK) return SLIDE_ERR_HIP;
   SL_HIP(hipMemcpyAsync(d_lm_slot.d, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, stream));
   SL_HIP(hipStreamSynchronize(stream));      // (a pageable temporary)

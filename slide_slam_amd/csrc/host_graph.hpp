@@ -609,6 +609,7 @@ class HostGraph {
   DevArr<double> d_S0, d_pcg, d_pcg_scal;              // joint solve (pcg_kernels.hip)
   DevArr<int> d_lm_slot;                               // landmark -> shared slot or -1
   int sync_lm_slot();                                  // rebuilds it from h_sh_lid (upload_new, set_shared)
+  bool lm_slot_onto = false;                           // sync_lm_slot: lm_slot[h_sh_lid[i]] == i for every slot i that names a landmark (no two slots on one landmark, none out of range)
   DevArr<int> d_prof, d_first;                         // tile-level profile of the reduced system (graph_dev.hpp), host copies h_prof / h_first
   std::vector<int> h_prof, h_first;
   int prof_ver = 0;

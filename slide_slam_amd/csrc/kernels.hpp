@@ -45,7 +45,7 @@ void launch_ghost_exchange_batched(const GraphDev* d, int n, int n_gslots, int w
 // exact joint step ("arrow", graph_dev.hpp): border rows + border block of every robot; the separator system of all shared landmarks
 // gathered from the robots' border blocks (maps[i]: m ints, global separator coordinate -> robot i's border coordinate or -1); its
 // solution handed back
-void launch_border_assemble_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s);
+void launch_border_assemble_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s, bool clear = true, bool fills = true);      // the separate launches: what launch_phase3_arrow_batched did not merge
 void launch_sep_extract_batched(const GraphDev* d, const GraphDev* h, int n, const int* n_sep_poses, hipStream_t s);      // separator poses out of the band (k_sep_extract_b)
 void launch_sep_pose_scatter_batched(const GraphDev* d, const GraphDev* h, int n, double* const* xloc, hipStream_t s);  // their solution into dp
 // Separator system: Ts tile columns of landmark coordinates (ms real) in sys (ld = (Ts + nl + 1) * NB: band, nl border row tiles = the
@@ -60,7 +60,9 @@ void launch_sep_top_add(const SepLayout& Y, int c0, const double* sys2, int ld2,
 void launch_sep_unpack(const SepLayout& Y, hipStream_t s, int c0 = 0, int c1 = -1, bool to_packed = false);      // tile columns [c0, c1) (virtual: lambda tiles behind the landmarks'); to_packed: the reverse copy
 void launch_lam_prepare(const double* bord, int nl, int lam, double* out, hipStream_t s);      // M = -(K22 - L21 L21^T), rhs = -(r2 - L21 z1)
 void launch_sep_xloc(int n, const int* const* maps, int ms, int lam, const double* xs, const double* xl, double* const* xloc, hipStream_t s);
-void launch_arrow_finish_batched(const GraphDev* d, const GraphDev* h, int n, const double* xs, const int* sep_off, hipStream_t s);
+void launch_arrow_finish_batched(const GraphDev* d, const GraphDev* h, int n, const double* xs, const int* sep_off, hipStream_t s, bool slots_onto);      // slots_onto: lm_slot reaches every slot of every graph (HostGraph::lm_slot_onto)
+struct AsmMerge { int mask; };                   // SLIDE_ASM_MERGE (default 6) — solver_kernels.hip, launch_phase3_arrow_batched
+AsmMerge asm_merge_env();                        // read on every call: the launch sequence of a pass takes them when it is built
 void launch_phase3_arrow_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s);   // phase 3 without the exchanged sums: the robots' own H_ll
 
 // chol_kernels.hip — blocked right-looking FP64 Cholesky of the (T*NB)^2 lower matrix S (column-major,

@@ -935,6 +935,8 @@ __device__ __forceinline__ void k_schur_body(const GraphDev& G, int pj, int yb) 
   }
 }
 __device__ __forceinline__ void k_pad_rhs_body(const GraphDev& G, int bid);
+__device__ __forceinline__ void k_border_fill_body(const GraphDev& G, int bid);
+__device__ __forceinline__ void k_border_fill_lam_body(const GraphDev& G, int bid);
 // workgroups x >= P (y = 0) of the launch write the right-hand-side row and the padding of the last tile (k_pad_rhs_body: they depend on
 // k_pose only, like the Schur blocks — round 5: one launch instead of two on the streaming path)
 // p_first: the first pose column the launch covers (an incremental update re-assembles from G.col0 on: the pose columns left of it
@@ -1101,7 +1103,20 @@ __device__ __forceinline__ void k_schur_listed_body(const GraphDev& G, int pj, i
 // observes it, and with consecutive columns dealt round-robin every XCD's L2 fetched every record (PMC: 182 MB fetched per launch for
 // 35 MB of records).  Experiment (SLIDE_SCHUR_XCD=1), measured on C4: assembly 0.507 - 0.510 ms either way — the kernel is bound by
 // the latency of its dependent loads per workgroup, not by where they are served from; off by default
-__global__ __launch_bounds__(256) void k_schur_lb(const GraphDev* __restrict__ Gs, int xcd) {
+//
+// Regions behind the pose columns (launch_phase3_arrow_batched): the workgroups x >= np of the grid, numbered r = (x - np) * gridDim.y + y,
+// run the launches that used to queue behind this one and read nothing it writes — npad workgroups of k_pad_rhs_body, nfill of
+// k_border_fill_body, nlam of k_border_fill_lam_body, each sized for the largest robot of the batch (np = the largest P; np = gridDim.x
+// and no regions: the separate launches).  No region depends on another one and nothing orders them:
+//   pose columns   read   pose_adj, prof, sp_idx, sp_pairs, ebuf, pose_H, pose_bt*, bt_*     write  S / S0 rows 6 pj .. 6 P - 1 (the band)
+//   pad region     reads  pose_g, yv, first                          writes S / S0 rows 6 P .. T NB - 1 (the padding) and S row (T + nbr) NB
+//   fill region    reads  sh_lid, lm_bord, lm_type, lm_ptr, lm_fids, lf_pose, lf_eoff, lm_Hacc, ebuf (E), and its OWN earlier stores
+//                  writes S rows T NB + o .. + D - 1 of the landmark's border coordinates o, bord0 (its block and right-hand-side entries)
+//   lambda region  reads  gh_bord, gh_pose, gh_first, gh_J, gh_r     writes S rows T NB + o .. + 5 of the factor's border coordinates, bord0
+// ebuf, lm_Hacc, pose_H, pose_g, gh_J and gh_r were written by earlier launches (k_landmark, k_pose, k_lin_lf) and are only read here; the
+// row ranges of S are disjoint (band < padding < border rows < right-hand-side row), and every border item (a shared landmark, a ghost
+// factor) has border coordinates of its own (upload_new hands them out one after the other), so the fills meet neither in S nor in bord0.
+__global__ __launch_bounds__(256) void k_schur_lb(const GraphDev* __restrict__ Gs, int xcd, int np, int npad, int nfill, int nlam) {
   int x = blockIdx.x, y = blockIdx.y, z = blockIdx.z;
   if (xcd) {
     const long long total = (long long)gridDim.x * gridDim.y * gridDim.z;
@@ -1114,6 +1129,15 @@ __global__ __launch_bounds__(256) void k_schur_lb(const GraphDev* __restrict__ G
     z = (int)(l2 / ((long long)gridDim.x * gridDim.y));
   }
   const GraphDev G = Gs[z];
+  if (x >= np) {
+    int r = (x - np) * (int)gridDim.y + y;
+    if (r < npad) { k_pad_rhs_body(G, r); return; }
+    r -= npad;
+    if (r < nfill) { k_border_fill_body(G, r); return; }
+    r -= nfill;
+    if (r < nlam) k_border_fill_lam_body(G, r);
+    return;
+  }
   k_schur_listed_body(G, x, y);
 }
 
@@ -1266,10 +1290,13 @@ __global__ __launch_bounds__(256) void k_pad_rhs_b(const GraphDev* __restrict__ 
 // landmark back-substitution  delta_l = -H_ll^-1 (g_l + sum_f E_f^T delta_p), and delta_p = dp.
 // MODE 0: everything.  MODE 1: only t_l = sum_f E_f^T delta_p -> lm_t (for the cross-robot all-reduce).
 // MODE 2: delta_l from the (all-reduced) t_l.
+// MODE 3: MODE 0 of an exact joint pass in which a separator landmark (lm_slot[l] >= 0) skips its factor sum — H_ll^-1 = 0 would
+// multiply it away — and takes its delta from the separator's solution, xs[sep_off[slot] + k]: the value k_sep_lm_delta_b stored
+// over that zero, so every lm_delta entry has one writer and that launch goes (launch_arrow_finish_batched).
 // One wave per landmark (lanes over its factors, butterfly sum of the <= 9 numbers), four landmarks per workgroup; the
 // pose part is a plain copy by the first blocks' threads.
 template <int MODE>
-__device__ __forceinline__ void k_backsub_body(const GraphDev& G) {
+__device__ __forceinline__ void k_backsub_body(const GraphDev& G, const double* __restrict__ xs = nullptr, const int* __restrict__ sep_off = nullptr) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (MODE != 2) {
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -1277,6 +1304,13 @@ __device__ __forceinline__ void k_backsub_body(const GraphDev& G) {
   }
   for (int l = blockIdx.x * 4 + wave; l < G.L; l += gridDim.x * 4) {
     const int D = lm_dim(G.lm_type[l]);
+    if (MODE == 3) {
+      const int sl = (G.arrow && G.lm_slot) ? G.lm_slot[l] : -1;      // (the condition under which k_landmark<3> zeroed H_ll^-1)
+      if (sl >= 0) {
+        if (lane < D) G.lm_delta[9 * (size_t)l + lane] = xs[sep_off[sl] + lane];
+        continue;
+      }
+    }
     double rhs[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) rhs[k] = 0.0;
@@ -1329,6 +1363,9 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_backsub(GraphDev G) { k_backsub_body<MODE>(G); }
 template <int MODE>
 __global__ __launch_bounds__(256) void k_backsub_b(const GraphDev* __restrict__ Gs) { k_backsub_body<MODE>(Gs[blockIdx.z]); }
+__global__ __launch_bounds__(256) void k_backsub_sep_b(const GraphDev* __restrict__ Gs, const double* __restrict__ xs, const int* __restrict__ sep_off) {
+  k_backsub_body<3>(Gs[blockIdx.z], xs, sep_off);
+}
 
 // ---- cross-robot exchange of shared landmarks (one robot per GPU) --------------------------
 // what 0: normal-equation partial sums (54 per slot: packed lower H_ll, g_l), what 1: t_l (9), what 2: the
@@ -1386,10 +1423,9 @@ __global__ __launch_bounds__(256) void k_border_clear_b(const GraphDev* __restri
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < nrow * ncol; t += (long long)gridDim.x * 256)
     G.S[(size_t)(t / nrow) * G.ld + (size_t)G.T * NB + (size_t)(t % nrow)] = 0.0;
 }
-__global__ __launch_bounds__(256) void k_border_fill_b(const GraphDev* __restrict__ Gs) {
-  const GraphDev G = Gs[blockIdx.z];
+__device__ __forceinline__ void k_border_fill_body(const GraphDev& G, int bid) {
   if (!G.arrow || G.nbr <= 0) return;
-  const int sidx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int sidx = bid * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (sidx >= G.n_slots) return;
   const int l = G.sh_lid[sidx];
   if (l < 0) return;
@@ -1445,6 +1481,10 @@ __global__ __launch_bounds__(256) void k_border_fill_b(const GraphDev* __restric
       }
     }
   }
+}
+__global__ __launch_bounds__(256) void k_border_fill_b(const GraphDev* __restrict__ Gs) {
+  const GraphDev G = Gs[blockIdx.z];
+  k_border_fill_body(G, blockIdx.x);
 }
 // Separator poses out of the band (nested dissection of the robot's pose chain, graph_dev.hpp pose_sep).  The assembly wrote the
 // whole reduced system in pose order; for every separator pose q (one workgroup) its entries move to where a border variable lives:
@@ -1567,10 +1607,9 @@ __global__ __launch_bounds__(256) void k_sep_pose_scatter_b(const GraphDev* __re
 }
 // lambda rows of the inter-robot relative-pose factors: 36 threads per ghost factor write J (6 x 6, whitened, w.r.t. the own pose) into
 // the border rows at the pose's columns; the first-key side also writes -I onto the border block's diagonal and -r into its RHS row
-__global__ __launch_bounds__(256) void k_border_fill_lam_b(const GraphDev* __restrict__ Gs) {
-  const GraphDev G = Gs[blockIdx.z];
+__device__ __forceinline__ void k_border_fill_lam_body(const GraphDev& G, int bid) {
   if (!G.arrow || !G.gh_bord || G.nbr <= 0) return;
-  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int t = bid * 256 + threadIdx.x;
   const int q = t / 36, e = t - 36 * q;
   if (q >= G.n_ghost) return;
   const int o = G.gh_bord[q];
@@ -1581,6 +1620,10 @@ __global__ __launch_bounds__(256) void k_border_fill_lam_b(const GraphDev* __res
     G.bord0[(size_t)(o + k) * G.ldb + o + k] = -1.0;
     G.bord0[(size_t)(o + k) * G.ldb + (size_t)G.nbr * NB] = -G.gh_r[6 * (size_t)q + k];
   }
+}
+__global__ __launch_bounds__(256) void k_border_fill_lam_b(const GraphDev* __restrict__ Gs) {
+  const GraphDev G = Gs[blockIdx.z];
+  k_border_fill_lam_body(G, blockIdx.x);
 }
 // separator system of all shared landmarks = sum over the robots of their border blocks after k_border_syrk, gathered through the
 // robots' global -> local coordinate maps into the layout the Cholesky kernels factor (column-major lower, ld = (Ts + 1) * NB, the
@@ -2027,28 +2070,53 @@ void launch_phase3_batched(const GraphDev* d, const GraphDev* h, int n, double* 
     hipLaunchKernelGGL(k_pad_rhs_b, dim3(blocks_for(pad, 256), 1, n), dim3(256), 0, s, d);
   }
 }
+// The short launches of an exact joint pass's assembly that read nothing the listed Schur launch writes run as regions of its grid (k_schur_lb) instead of
+// queueing behind it on the stream.  SLIDE_ASM_MERGE is a bit mask of what is merged, read every time a pass's launch sequence is built
+// (one process can take both sides): 2 = padding / right-hand-side row and the two border fills inside k_schur_lb (the border clear then
+// runs in front of that launch), 4 = the separator landmarks' deltas inside the back-substitution (launch_arrow_finish_batched).  Default
+// 6; 0 = the separate launches.  (Value 1 was the border clear as a region of the landmark launch: measured and taken out again,
+// profiles/assembly_regions_timing.txt.)
+AsmMerge asm_merge_env() {
+  AsmMerge M{6};
+  if (const char* e = getenv("SLIDE_ASM_MERGE")) M.mask = atoi(e);
+  return M;
+}
 // the same for an exact joint pass: no exchanged sums to unpack (a separator landmark keeps the robot's own H_ll / g_l), then the border
 void launch_phase3_arrow_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s) {
-  int L = 0, P = 0;
-  long long pad = 0;
+  const AsmMerge M = asm_merge_env();
+  int L = 0, P = 0, slots = 0, ngh = 0;
+  long long pad = 0, work = 0;
   for (int i = 0; i < n; ++i) {
     L = std::max(L, h[i].L); P = std::max(P, h[i].P);
     const long long NT = (long long)h[i].T * NB;
     pad = std::max(pad, NT + (NT - 6LL * h[i].P) * NT);
+    slots = std::max(slots, h[i].n_slots);
+    work = std::max(work, (long long)h[i].nbr * NB * h[i].T * NB);
+    ngh = std::max(ngh, h[i].gh_bord ? h[i].n_ghost : 0);
   }
+  const bool border = work > 0 && slots > 0;      // (launch_border_assemble_batched's own condition)
   if (L > 0) hipLaunchKernelGGL(k_landmark_b<3>, dim3(blocks_for(L, 4), 1, n), dim3(256), 0, s, d);
+  bool m_fill = false;
   if (P > 0) {
     hipLaunchKernelGGL(k_pose_b, dim3(blocks_for(P, 4), 1, n), dim3(256), 0, s, d);
     int split = 1;
     bool listed = true;
     for (int i = 0; i < n; ++i) { split = std::max(split, h[i].schur_split > 0 ? h[i].schur_split : 2); listed = listed && h[i].sp_idx != nullptr; }
     static const int schur_xcd = getenv("SLIDE_SCHUR_XCD") ? atoi(getenv("SLIDE_SCHUR_XCD")) : 0;
-    if (listed) hipLaunchKernelGGL(k_schur_lb, dim3(P, split > 0 ? split : 1, n), dim3(256), 0, s, d, schur_xcd);      // (no table in LDS)
-    else hipLaunchKernelGGL(k_schur_b, dim3(P, split > 0 ? split : 1, n), dim3(256),
-                            (size_t)((L + 7) / 8 * 8) * sizeof(short) + (size_t)((P + 31) / 32 + 1) * sizeof(unsigned), s, d);
-    hipLaunchKernelGGL(k_pad_rhs_b, dim3(blocks_for(pad, 256), 1, n), dim3(256), 0, s, d);
+    m_fill = listed && (M.mask & 2);      // (the walk, k_schur_b, keeps the separate launches)
+    if (m_fill) {
+      launch_border_assemble_batched(d, h, n, s, true, false);      // the fills need the clear: it runs in front of them
+      const int npad = (int)blocks_for(pad, 256), nfill = border ? (slots + 3) / 4 : 0, nlam = border && ngh > 0 ? (36 * ngh + 255) / 256 : 0;
+      hipLaunchKernelGGL(k_schur_lb, dim3(P + blocks_for((long long)npad + nfill + nlam, split), split, n), dim3(256), 0, s, d, schur_xcd, P, npad, nfill, nlam);
+    } else if (listed) {
+      hipLaunchKernelGGL(k_schur_lb, dim3(P, split, n), dim3(256), 0, s, d, schur_xcd, P, 0, 0, 0);      // (no table in LDS)
+    } else {
+      hipLaunchKernelGGL(k_schur_b, dim3(P, split, n), dim3(256),
+                         (size_t)((L + 7) / 8 * 8) * sizeof(short) + (size_t)((P + 31) / 32 + 1) * sizeof(unsigned), s, d);
+    }
+    if (!m_fill) hipLaunchKernelGGL(k_pad_rhs_b, dim3(blocks_for(pad, 256), 1, n), dim3(256), 0, s, d);
   }
-  launch_border_assemble_batched(d, h, n, s);
+  if (!m_fill) launch_border_assemble_batched(d, h, n, s);
 }
 __global__ void k_shared_pack_b(const GraphDev* __restrict__ Gs, int what, BufPtrs B) { k_shared_pack_body(Gs[blockIdx.z], what, B.p[blockIdx.z]); }
 // The per-robot phases of a batched pass in ONE launch sequence for all robots (blockIdx.z = robot, grids sized for the largest graph):
@@ -2134,7 +2202,8 @@ void launch_sep_pose_scatter_batched(const GraphDev* d, const GraphDev* h, int n
   for (int i = 0; i < n; ++i) X.p[i] = xloc[i];
   hipLaunchKernelGGL(k_sep_pose_scatter_b, dim3(blocks_for(6LL * P, 256), 1, n), dim3(256), 0, s, d, X);
 }
-void launch_border_assemble_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s) {
+// the border's separate launches (clear / fills: what launch_phase3_arrow_batched did not merge into the Schur launch)
+void launch_border_assemble_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s, bool clear, bool fills) {
   int slots = 0;
   long long work = 0;
   for (int i = 0; i < n; ++i) {
@@ -2142,7 +2211,8 @@ void launch_border_assemble_batched(const GraphDev* d, const GraphDev* h, int n,
     work = std::max(work, (long long)h[i].nbr * NB * h[i].T * NB);
   }
   if (work <= 0 || slots <= 0) return;
-  hipLaunchKernelGGL(k_border_clear_b, dim3((unsigned)std::min<long long>((work + 255) / 256, 4096), 1, n), dim3(256), 0, s, d);
+  if (clear) hipLaunchKernelGGL(k_border_clear_b, dim3((unsigned)std::min<long long>((work + 255) / 256, 4096), 1, n), dim3(256), 0, s, d);
+  if (!fills) return;
   hipLaunchKernelGGL(k_border_fill_b, dim3((slots + 3) / 4, 1, n), dim3(256), 0, s, d);
   int ngh = 0;
   for (int i = 0; i < n; ++i) ngh = std::max(ngh, h[i].gh_bord ? h[i].n_ghost : 0);
@@ -2188,14 +2258,22 @@ void launch_sep_xloc(int n, const int* const* maps, int ms, int lam, const doubl
 }
 // the last steps of an exact joint pass for all robots of the GPU: pose_delta = dp and the private landmarks' deltas (k_backsub<0>; a
 // separator landmark gets 0 there: H_ll^-1 = 0), the separator landmarks' deltas from the separator's solution, estimate
-void launch_arrow_finish_batched(const GraphDev* d, const GraphDev* h, int n, const double* xs, const int* sep_off, hipStream_t s) {
+// slots_onto: every graph's landmark -> slot table leads back to every slot that names a landmark (HostGraph::sync_lm_slot), so the
+// back-substitution reaches through lm_slot every entry k_sep_lm_delta_b would write; then (SLIDE_ASM_MERGE value 4) k_backsub_sep_b
+// writes the separator landmarks' deltas itself and that launch goes.
+void launch_arrow_finish_batched(const GraphDev* d, const GraphDev* h, int n, const double* xs, const int* sep_off, hipStream_t s, bool slots_onto) {
   int L = 0, P = 0, slots = 0;
   for (int i = 0; i < n; ++i) { L = std::max(L, h[i].L); P = std::max(P, h[i].P); slots = std::max(slots, h[i].n_slots); }
   if (P + L == 0) return;
-  hipLaunchKernelGGL(k_backsub_b<0>, dim3(std::max(blocks_for(L, 4), blocks_for(6 * P, 256)), 1, n), dim3(256), 0, s, d);
-  SepScatterArgs A{};
-  A.n = n; A.xs = xs;
-  if (slots > 0) hipLaunchKernelGGL(k_sep_lm_delta_b, dim3(blocks_for(9LL * slots, 256), 1, n), dim3(256), 0, s, d, A, sep_off);
+  const dim3 grid(std::max(blocks_for(L, 4), blocks_for(6 * P, 256)), 1, n);
+  if (slots > 0 && slots_onto && (asm_merge_env().mask & 4)) {
+    hipLaunchKernelGGL(k_backsub_sep_b, grid, dim3(256), 0, s, d, xs, sep_off);
+  } else {
+    hipLaunchKernelGGL(k_backsub_b<0>, grid, dim3(256), 0, s, d);
+    SepScatterArgs A{};
+    A.n = n; A.xs = xs;
+    if (slots > 0) hipLaunchKernelGGL(k_sep_lm_delta_b, dim3(blocks_for(9LL * slots, 256), 1, n), dim3(256), 0, s, d, A, sep_off);
+  }
   hipLaunchKernelGGL(k_estimate_b, dim3(blocks_for(P + L, 256), 1, n), dim3(256), 0, s, d);
 }
 
