@@ -202,7 +202,8 @@ int slide_graph_get_closure_weights(slide_graph_t* g, int cap, int32_t* from_rob
  * it, the solve reports it as it reports any near-singular landmark block.
  * SLIDE_ERR_INVALID: kind outside 0 .. 4, a class_mask bit other than 0 .. 2, a param that is not a number, a graph that has joined
  * a batch.  Single-graph path only: while a loss is set, slide_graph_join_chol_batch, slide_graph_dist_phase and
- * slide_graph_dist_pass_local return SLIDE_ERR_INVALID (the sharded and joint passes do not carry an observation loss). */
+ * slide_graph_dist_pass_local return SLIDE_ERR_INVALID (the un-batched sharded passes do not carry an observation loss; a batch carries
+ * its own: slide_chol_batch_set_observation_loss). */
 int slide_graph_set_observation_loss(slide_graph_t* g, int kind, double param, int class_mask);
 /* What the graph has come to think of its observations: every landmark factor in insertion order with its pose (robot, pose_idx),
  * its landmark (cls: SLIDE_CLS_*, lm_idx), the weight w and the squared whitened norm s^2 (taken before the scaling) of its last
@@ -347,6 +348,35 @@ int slide_chol_batch_get_closure_weights(slide_chol_batch_t* b, int cap, int32_t
  * results): slide_chol_batch_get_closure_weights is refused until the next pass, which writes them all again.  SLIDE_ERR_INVALID
  * without a loss. */
 int slide_chol_batch_profile_robust_reweight(slide_chol_batch_t* b, double* const* d_bufs, double* ms);
+/* ---- Observation loss on the exact joint multi-robot pass --------------------------------------------------------------------------
+ * No counterpart in the reference; GTSAM users know it as noiseModel::Robust on the BearingRange / Cube / Cylinder factors of the
+ * joint graph.  slide_graph_set_observation_loss's rule, kinds, defaults, floor and class_mask as a property of the BATCH, uniform
+ * over its member graphs: in every slide_chol_batch_pass and cut pass (part 0) each member's landmark factors are linearised by
+ * k_lin_lf_robust_b in k_lin_lf_b's place, a selected factor entering as sqrt(w) [r | J] - also into the shared landmarks' rows of
+ * the separator system, so a false match onto a shared landmark is down-weighted for every robot that sees the landmark.  The step
+ * is the Gauss-Newton step of the reweighted joint graph.  Same number of launches with and without; kind 0 clears the loss: the
+ * pass then has the launches and gives the bits it gives without this call.  Independent of slide_chol_batch_set_robust_loss; both
+ * may be set.  Every call (kind 0 included) drops the members' resident factors and the batch's cached joint Sigma and captures the
+ * passes again; the joint marginals, information gain, gate and pose-pair marginals need a pass after it and then describe the
+ * reweighted system.  A graph that joins later takes the loss at the next pass; nothing of a member is rewritten under the loss, so
+ * one that leaves has nothing to restore.  The per-graph calls keep refusing (a graph with an observation loss of its own cannot
+ * join; slide_graph_set_observation_loss refuses a member); slide_graph_get_observation_weights on a member reports w = 1 and the
+ * s^2 of the SCALED record: use slide_chol_batch_get_observation_weights.
+ * SLIDE_ERR_INVALID: kind outside 0 .. 4, a class_mask bit other than 0 .. 2, a param that is not a number, a batch with PCG passes
+ * (slide_chol_batch_set_pcg > 0; likewise slide_chol_batch_set_pcg > 0 while a loss is set). */
+int slide_chol_batch_set_observation_loss(slide_chol_batch_t* b, int kind, double param, int class_mask);
+/* slide_graph_get_observation_weights for the batch, after a pass (SLIDE_ERR_INVALID "pass first" before one, after a change of the
+ * observation loss, after a member joined, left or was replaced, and while a member holds another number of landmark factors than
+ * the last pass linearised): slot by slot, the member's landmark factors in insertion order with the member's slot, the factor's
+ * pose index, its landmark (cls: SLIDE_CLS_*, lm_idx: the member's own index), the weight w and the squared whitened norm s^2 (taken
+ * before the scaling) of the last pass.  w = 1 where that pass ran without a loss or its mask left the class out.  One launch and
+ * one read-back for all members.  Any output pointer may be NULL; at most cap rows are written, *n_out is the full count. */
+int slide_chol_batch_get_observation_weights(slide_chol_batch_t* b, int cap, int32_t* slot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx,
+                                             double* weight, double* s2, int* n_out);
+/* Measurement (no counterpart in the reference): the linearisation launch of a batched pass alone (k_lin_lf_b, or k_lin_lf_robust_b
+ * while an observation loss is set) between two events on the batch's stream; *ms: milliseconds.  It linearises at the point the
+ * last pass left; the read-backs and the joint queries are refused until the next pass. */
+int slide_chol_batch_profile_linearize(slide_chol_batch_t* b, double* const* d_bufs, double* ms);
 /* The same pass for a job that spans GPUs, cut at its two exchanges (8 / N robots on each of N GPUs): every part is a captured
  * hipGraph replayed on the batch's stream.
  *   part 0: phase 0 of every robot + the local sum -> every local buffer holds this GPU's sum of the 54-doubles-per-slot blocks;

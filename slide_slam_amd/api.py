@@ -47,6 +47,7 @@ EXPORTS = [
     "slide_graph_set_observation_loss", "slide_graph_get_observation_weights",
     "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
     "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis",
+    "slide_chol_batch_set_observation_loss", "slide_chol_batch_get_observation_weights", "slide_chol_batch_profile_linearize",
 ]
 
 
@@ -741,6 +742,46 @@ class CholBatch:
         arr = (C.c_void_p * len(buf_ptrs))(*[int(p) for p in buf_ptrs])
         ms = C.c_double(0.0)
         _check(self.L.slide_chol_batch_profile_robust_reweight(C.c_void_p(self.h), arr, C.byref(ms)))
+        return ms.value
+
+    def set_observation_loss(self, kind, param=0.0, points=True, cubes=True, cylinders=True):
+        """slide_chol_batch_set_observation_loss: SlideGraph.set_observation_loss's loss (same kinds, names and defaults) on the
+        batched passes, uniform over the member graphs: their bearing-range (points), cube and cylinder factors, the observations
+        of the shared landmarks included.  Fused into the passes' linearisation launch; independent of set_robust_loss.  kind 0 /
+        None clears it.  Not with PCG passes."""
+        if kind is None or isinstance(kind, str):
+            if kind not in SlideGraph.ROBUST_KINDS:
+                raise ValueError(f"observation loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
+            kind = SlideGraph.ROBUST_KINDS[kind]
+        mask = (1 if points else 0) | (2 if cubes else 0) | (4 if cylinders else 0)
+        _check(self.L.slide_chol_batch_set_observation_loss(C.c_void_p(self.h), C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+
+    def observation_weights(self, cap=None):
+        """slide_chol_batch_get_observation_weights after a pass: slot by slot the member's landmark factors in insertion order.
+        Returns a dict of arrays: slot, pose_idx, cls (SLIDE_CLS_*), lm_idx (the member's own landmark index), weight, s2 (weight and
+        unscaled squared whitened norm of the factor's linearisation in the last pass; weight 1 where no loss applied) and n, the
+        full count (cap: write at most that many rows).  The per-graph SlideGraph.observation_weights of a member does not know
+        the batch's loss (weight 1, s2 of the scaled record): use this one."""
+        n = C.c_int(0)
+        h = C.c_void_p(self.h)
+        if cap is None:
+            _check(self.L.slide_chol_batch_get_observation_weights(h, C.c_int(0), None, None, None, None, None, None, C.byref(n)))
+            cap = n.value
+        m = max(int(cap), 1)
+        sl, cl = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        pi, li = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+        w, s2 = np.zeros(m), np.zeros(m)
+        _check(self.L.slide_chol_batch_get_observation_weights(h, C.c_int(int(cap)), _p(sl), _p(pi), _p(cl), _p(li), _p(w), _p(s2), C.byref(n)))
+        k = min(int(cap), n.value)
+        return {"slot": sl[:k].copy(), "pose_idx": pi[:k].copy(), "cls": cl[:k].copy(), "lm_idx": li[:k].copy(),
+                "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
+
+    def profile_linearize(self, buf_ptrs):
+        """slide_chol_batch_profile_linearize: milliseconds of the passes' linearisation launch alone, between two events, under the
+        batch's current observation loss (the read-backs and joint queries then want a pass first)."""
+        arr = (C.c_void_p * len(buf_ptrs))(*[int(p) for p in buf_ptrs])
+        ms = C.c_double(0.0)
+        _check(self.L.slide_chol_batch_profile_linearize(C.c_void_p(self.h), arr, C.byref(ms)))
         return ms.value
 
     def set_pcg(self, iterations, tol=0.0):

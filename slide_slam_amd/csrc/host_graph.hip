@@ -504,6 +504,8 @@ CholBatch::~CholBatch() {
   if (d_Rs) (void)hipFree(d_Rs);
   if (d_rb_ent) (void)hipFree(d_rb_ent);
   if (d_rb_out) (void)hipFree(d_rb_out);
+  if (d_Os) (void)hipFree(d_Os);
+  if (d_ol_out) (void)hipFree(d_ol_out);
   if (d_status_all) (void)hipFree(d_status_all);
   if (ev_aux0) (void)hipEventDestroy(ev_aux0);
 
@@ -611,6 +613,12 @@ int CholBatch::prepare_pass() {
     for (int i = 0; i < n; ++i) hR[i] = member_view(graphs[i]);
     if (!d_Rs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Rs), CHOL_BATCH_HOST_MAX * sizeof(RobustDev)));
     SL_HIP(hipMemcpyAsync(d_Rs, hR.data(), n * sizeof(RobustDev), hipMemcpyHostToDevice, master));
+  }
+  if (ol_kind != 0) {      // (and the observation loss's, likewise)
+    hO.resize(n);
+    for (int i = 0; i < n; ++i) hO[i] = member_obs_view(graphs[i]);
+    if (!d_Os) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Os), CHOL_BATCH_HOST_MAX * sizeof(ObsLossDev)));
+    SL_HIP(hipMemcpyAsync(d_Os, hO.data(), n * sizeof(ObsLossDev), hipMemcpyHostToDevice, master));
   }
   SL_HIP(hipStreamSynchronize(master));
   // exact joint passes: the systems the steps run on — every graph's segments (views of its S; the whole band when it is not cut) — and
@@ -1177,7 +1185,7 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
     launch_status_clear(d_Gs, n, master, sep_status, sep_nl > 0 ? lam_status : nullptr);
     const int rg = enqueue_ghost_refresh(d_bufs, part);
     if (rg != SLIDE_OK) return rg;
-    launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, false, rb_kind != 0 ? d_Rs : nullptr);      // relinearise, [reweight,] linearise, the robots' own per-landmark sums (nothing to pack: no exchange of them)
+    launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, false, rb_kind != 0 ? d_Rs : nullptr, ol_kind != 0 ? d_Os : nullptr);      // relinearise, [reweight,] linearise, the robots' own per-landmark sums (nothing to pack: no exchange of them)
     launch_phase3_arrow_batched(d_Gs, hG.data(), n, master);         // private landmarks eliminated, reduced pose systems, borders
     {
       int nq[CHOL_BATCH_HOST_MAX];
@@ -1412,7 +1420,8 @@ int CholBatch::enqueue_pass(double* const* d_bufs, hipEvent_t e0, hipEvent_t e1,
     launch_status_clear(d_Gs, n, master);      // (a kernel node: a captured hipMemsetAsync did not clear on replay, DESIGN §4 finding 6)
     if ((rc = enqueue_ghost_refresh(d_bufs, part)) != SLIDE_OK) return rc;
     if (!batch_p3 && rb_kind != 0) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's robust loss"; return SLIDE_ERR_INVALID; }
-    if (batch_p3) launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, true, rb_kind != 0 ? d_Rs : nullptr);      // (all robots in one launch sequence: no fork / join)
+    if (!batch_p3 && ol_kind != 0) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's observation loss"; return SLIDE_ERR_INVALID; }
+    if (batch_p3) launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, true, rb_kind != 0 ? d_Rs : nullptr, ol_kind != 0 ? d_Os : nullptr);      // (all robots in one launch sequence: no fork / join)
     else each(0);
     if (rc == SLIDE_OK) launch_sum_bcast(d_bufs, n, 54 * n_slots, master);
   }
@@ -1506,6 +1515,7 @@ int CholBatch::profile_pass(double* const* d_bufs, double* ms_steps, int* n_laun
     std::lock_guard<std::mutex> gl(g->mtx);
     g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;      // (a batched pass rewrites the status words, deltas and estimates)
     if (rb_kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }
+    if (ol_kind != 0 && !g->ol_arrays) { g->ol_arrays = true; g->topo_dirty = true; }
     int rc = g->merge_pending();
     if (rc == SLIDE_OK) rc = g->upload_new();
     if (rc != SLIDE_OK) return rc;
@@ -1555,16 +1565,24 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
     std::lock_guard<std::mutex> gl(g->mtx);
     g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;      // (a batched pass rewrites the status words, deltas and estimates)
     if (rb_kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }      // (a member new to the batch's loss: upload_new creates its robust arrays)
+    if (ol_kind != 0 && !g->ol_arrays) { g->ol_arrays = true; g->topo_dirty = true; }      // (likewise lf_w / lf_s2 under the batch's observation loss)
     int rc = g->merge_pending();
     if (rc == SLIDE_OK) rc = g->upload_new();
     if (rc != SLIDE_OK) return rc;
     g->G.relin_thr = 0.0;
+    g->note_linearisation();      // (the pass linearises every factor of the member: its own read-backs, which know no loss of the batch, report w = 1 and the records' |r|^2)
     if (g->G.n_slots != graphs[0]->G.n_slots) { g_last_error = "batched pass: the graphs disagree on the shared slots"; return SLIDE_ERR_INVALID; }
     SL_HIP(hipStreamSynchronize(g->stream));                       // (uploads of a changed graph; idle otherwise)
     *same = *same && std::memcmp(&pass_G[i], &g->G, sizeof(GraphDev)) == 0 && pass_bufs[i] == d_bufs[i];
     if (rb_kind != 0 && *same) {
       const RobustDev Rv = member_view(g);
       *same = (int)pass_R.size() == n && std::memcmp(&pass_R[i], &Rv, sizeof(RobustDev)) == 0;
+    }
+    if (*same) {      // (the observation loss, or the address of a member's weight arrays, changed: the captured linearisation is stale)
+      if (ol_kind != 0) {
+        const ObsLossDev Ov = member_obs_view(g);
+        *same = (int)pass_O.size() == n && std::memcmp(&pass_O[i], &Ov, sizeof(ObsLossDev)) == 0;
+      } else *same = pass_O.empty();
     }
   }
   if (!*same) {
@@ -1578,6 +1596,8 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
     for (int i = 0; i < n; ++i) pass_G[i] = graphs[i]->G;
     pass_R.clear();
     if (rb_kind != 0) pass_R = hR;
+    pass_O.clear();
+    if (ol_kind != 0) pass_O = hO;
   }
   note_pass();
   return SLIDE_OK;
@@ -1588,6 +1608,10 @@ void CholBatch::note_pass() {
   lin_rb_kind = rb_kind; lin_rb_mask = rb_mask;
   lin_bt.resize(n); lin_gh.resize(n);
   for (int i = 0; i < n; ++i) { lin_bt[i] = (size_t)graphs[i]->G.n_between; lin_gh[i] = (size_t)graphs[i]->G.n_ghost; }
+  ol_pass_done = true;
+  lin_ol_kind = ol_kind;
+  lin_lf.resize(n);
+  for (int i = 0; i < n; ++i) lin_lf[i] = (size_t)graphs[i]->G.n_lf;
 }
 int CholBatch::end_pass() {
   int st[CHOL_BATCH_HOST_MAX][8];
@@ -1808,6 +1832,133 @@ int CholBatch::profile_robust_reweight(double* const* d_bufs, double* ms) {
   if (es != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) rc = SLIDE_ERR_HIP;
   *ms = t;
   rb_pass_done = false;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return rc;
+}
+
+// ---- observation loss of the batch (k_lin_lf_robust_b) -----------------------------------------------------------------------------
+// As with the closure loss the setting lives here: a member's own ObsLossDev carries its arrays under kind 0 (its own solves stay
+// unweighted, the per-graph refusals hold), the batch's views add the batch's loss.  Unlike the closure loss nothing of a member is
+// rewritten under it - the weight sits inside the records the next linearisation writes again - so a member that leaves, and the
+// batch's destructor, have nothing to restore.
+ObsLossDev CholBatch::member_obs_view(const HostGraph* g) const {
+  ObsLossDev O = g->OB;
+  O.kind = ol_kind; O.mask = ol_mask; O.param = ol_param;
+  return O;
+}
+int CholBatch::set_observation_loss(int kind, double param, int class_mask) {
+  if (kind < 0 || kind > 4) { g_last_error = "chol_batch_set_observation_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
+  if (class_mask & ~7) { g_last_error = "chol_batch_set_observation_loss: class_mask has bit 0 (bearing-range), bit 1 (cube) and bit 2 (cylinder) only"; return SLIDE_ERR_INVALID; }
+  if (!(param == param)) { g_last_error = "chol_batch_set_observation_loss: param is not a number"; return SLIDE_ERR_INVALID; }
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  if (kind != 0 && pcg_iters > 0) {
+    g_last_error = "chol_batch_set_observation_loss: the batch runs PCG passes (pcg_iters > 0), whose step leaves the inter-robot factors' cross block out; they do not carry an observation loss";
+    return SLIDE_ERR_INVALID;
+  }
+  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
+  std::vector<HostGraph*> gs;
+  {
+    std::lock_guard<std::mutex> lk(mtx);
+    ol_kind = kind;
+    ol_mask = kind ? class_mask : 0;
+    ol_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
+    pass_dirty = true;
+    gs.assign(graphs.begin(), graphs.end());
+  }
+  exact_serial = 0;           // (the joint queries wait for the next pass: the factor and the cached joint Sigma are the old weighting's)
+  ol_pass_done = false;
+  for (HostGraph* g : gs) {      // (the members' weight arrays come with the next pass: begin_pass, upload_new)
+    if (!g) continue;
+    std::lock_guard<std::mutex> gl(g->mtx);
+    g->factor_valid = false;
+    g->wf_T = 0;
+    g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;
+  }
+  return SLIDE_OK;
+}
+int CholBatch::get_observation_weights(int cap, int32_t* slot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2, int* n_out) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  if (!ol_pass_done || (int)lin_lf.size() != n || !master) { g_last_error = "chol_batch_get_observation_weights: nothing was linearised under the current setting yet (pass first)"; return SLIDE_ERR_INVALID; }
+  std::vector<HostGraph*> gs;
+  {
+    std::lock_guard<std::mutex> lk(mtx);
+    // (a member joined, left or was replaced, or the batch's configuration changed: the device tables are the last pass's, not these graphs')
+    if (pass_dirty) { g_last_error = "chol_batch_get_observation_weights: the batch changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
+    gs.assign(graphs.begin(), graphs.end());
+  }
+  int off[CHOL_BATCH_HOST_MAX] = {0}, cnt[CHOL_BATCH_HOST_MAX] = {0};
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    HostGraph* g = gs[i];
+    if (!g) { g_last_error = "chol_batch_get_observation_weights: a slot of the batch is empty"; return SLIDE_ERR_INVALID; }
+    std::lock_guard<std::mutex> gl(g->mtx);
+    if ((size_t)g->G.n_lf != lin_lf[i] || g->h_lf_type.size() != lin_lf[i]) { g_last_error = "chol_batch_get_observation_weights: a member changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
+    if (lin_ol_kind != 0 && lin_lf[i] > 0 && (!g->OB.lf_w || !g->OB.lf_s2 || g->up_ol < lin_lf[i])) { g_last_error = "chol_batch_get_observation_weights: a member changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
+    off[i] = (int)total;
+    total += (long long)lin_lf[i];
+  }
+  if (total > 0x7fffffffLL) { g_last_error = "chol_batch_get_observation_weights: too many factors"; return SLIDE_ERR_INVALID; }
+  *n_out = (int)total;
+  const int m = (int)std::min<long long>(total, std::max(cap, 0));
+  if (m == 0) return SLIDE_OK;
+  for (int i = 0; i < n; ++i) cnt[i] = std::max(0, std::min((int)lin_lf[i], m - off[i]));      // (rows past cap are not written)
+  std::vector<double> out;
+  if (weight || s2) {
+    if ((size_t)m > ol_out_cap) {
+      if (d_ol_out) { (void)hipFree(d_ol_out); d_ol_out = nullptr; }
+      ol_out_cap = 0;
+      SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_ol_out), 2 * (size_t)m * sizeof(double)));
+      ol_out_cap = (size_t)m;
+    }
+    // d_Gs and d_Os are the last pass's tables: with a loss then, d_Os holds the members' arrays that pass wrote
+    launch_observation_weights_batched(d_Gs, d_Os, lin_ol_kind != 0, off, cnt, n, d_ol_out, master);
+    out.resize(2 * (size_t)m);
+    SL_HIP(hipMemcpyAsync(out.data(), d_ol_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, master));
+    SL_HIP(hipStreamSynchronize(master));
+    SL_HIP(hipGetLastError());
+  }
+  const uint64_t low = 0x00ffffffffffffffull;
+  for (int i = 0; i < n; ++i) {
+    if (cnt[i] == 0) continue;
+    HostGraph* g = gs[i];
+    std::lock_guard<std::mutex> gl(g->mtx);
+    std::vector<uint64_t> pkey, lkey;      // ids -> keys (the graph keeps the maps the other way round)
+    if (pose_idx) { pkey.assign(g->h_pose_val.size() / 12, 0); for (const auto& kv : g->key2pose) pkey[kv.second] = kv.first; }
+    if (lm_idx) { lkey.assign(g->h_lm_type.size(), 0); for (const auto& kv : g->key2lm) lkey[kv.second] = kv.first; }
+    for (int f = 0; f < cnt[i]; ++f) {
+      const size_t k = (size_t)off[i] + f;
+      if (slot) slot[k] = i;
+      if (pose_idx) pose_idx[k] = pkey[g->h_lf_pose[f]] & low;
+      if (cls) cls[k] = g->h_lf_type[f] == FT_CYL ? SLIDE_CLS_CYLINDER : (g->h_lf_type[f] == FT_CUBE ? SLIDE_CLS_CUBE : SLIDE_CLS_ELLIPSOID);
+      if (lm_idx) lm_idx[k] = lkey[g->h_lf_lm[f]] & low;
+      if (weight) weight[k] = out[2 * k];
+      if (s2) s2[k] = out[2 * k + 1];
+    }
+  }
+  return SLIDE_OK;
+}
+// Measurement: the pass's linearisation launch alone between two events on the pass's stream, under the batch's current loss.  It
+// linearises at the point the last pass left, so what it writes belongs to no pass: the read-backs and the joint queries wait for
+// the next pass.  An event pair around one short launch mostly measures the launch.
+int CholBatch::profile_linearize(double* const* d_bufs, double* ms) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  bool same = false;
+  int rc = begin_pass(d_bufs, &same);
+  if (rc != SLIDE_OK) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SL_HIP(hipEventCreate(&e0));
+  SL_HIP(hipEventCreate(&e1));
+  (void)hipEventRecord(e0, master);
+  launch_linearize_batched(d_Gs, hG.data(), n, master, ol_kind != 0 ? d_Os : nullptr);
+  (void)hipEventRecord(e1, master);
+  const hipError_t es = hipStreamSynchronize(master);
+  float t = 0.f;
+  if (es != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) rc = SLIDE_ERR_HIP;
+  *ms = t;
+  exact_serial = 0;
+  rb_pass_done = false;
+  ol_pass_done = false;
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return rc;
@@ -3292,7 +3443,7 @@ int HostGraph::get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_
 int HostGraph::set_observation_loss(int kind, double param, int class_mask) {
   if (kind < 0 || kind > 4) { g_last_error = "set_observation_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
   if (class_mask & ~7) { g_last_error = "set_observation_loss: class_mask has bit 0 (bearing-range), bit 1 (cube) and bit 2 (cylinder) only"; return SLIDE_ERR_INVALID; }
-  if (batch) { g_last_error = "set_observation_loss: the graph has joined a batch; the sharded and joint paths do not carry an observation loss"; return SLIDE_ERR_INVALID; }
+  if (batch) { g_last_error = "set_observation_loss: the graph has joined a batch; a batch carries its own observation loss (slide_chol_batch_set_observation_loss), the un-batched sharded passes carry none"; return SLIDE_ERR_INVALID; }
   if (!(param == param)) { g_last_error = "set_observation_loss: param is not a number"; return SLIDE_ERR_INVALID; }
   static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
   ol_kind = kind;

@@ -185,6 +185,15 @@ class CholBatch {
   int get_closure_weights(int cap, int32_t* slot, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind,
                           int32_t* ghost_id, double* weight, double* s2, int* n_out);
   int profile_robust_reweight(double* const* d_bufs, double* ms);      // k_robust_reweight_b alone between two events (measurement)
+  // Robust loss on the members' landmark observation factors, uniform over the batch (HostGraph::set_observation_loss's arguments,
+  // defaults and validation): k_lin_lf_robust_b in k_lin_lf_b's place in every whole or cut pass.  Independent of set_robust_loss.
+  // Not with PCG passes (pcg_iters > 0).
+  int set_observation_loss(int kind, double param, int class_mask);
+  bool observation_loss_on() const { return ol_kind != 0; }
+  // slot by slot the member's landmark factors in insertion order: its slot, the factor's pose index, its landmark (cls: SLIDE_CLS_*,
+  // lm_idx: the member's local index), w and the unscaled s^2 of the last pass.  One launch, one read-back.
+  int get_observation_weights(int cap, int32_t* slot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2, int* n_out);
+  int profile_linearize(double* const* d_bufs, double* ms);      // the pass's linearisation launch alone between two events (measurement)
   int pcg() const { return pcg_iters; }
   double pcg_tolerance() const { return pcg_tol; }
   // Exact joint step ("arrow"): the shared landmarks stay as the separator of the joint graph (graph_dev.hpp).  sep_buf: the caller's
@@ -333,6 +342,19 @@ class CholBatch {
   std::vector<size_t> lin_bt, lin_gh;
   int* d_rb_ent = nullptr; double* d_rb_out = nullptr; size_t rb_ent_cap = 0;
   void note_pass();
+  // observation loss of the batch: the members' ObsLossDev views beside d_Gs and d_Rs (their lf_w / lf_s2, the batch's setting; a
+  // member's own OB.kind stays 0), compared by begin_pass like the other two; what the last pass linearised under and how many
+  // landmark factors of each member it covered (the read-back).  No array of a member is rewritten under the loss, so nothing is
+  // restored when a member leaves or the batch goes.
+  int ol_kind = 0, ol_mask = 0;
+  double ol_param = 0.0;
+  ObsLossDev* d_Os = nullptr;
+  std::vector<ObsLossDev> hO, pass_O;
+  ObsLossDev member_obs_view(const HostGraph* g) const;
+  bool ol_pass_done = false;
+  int lin_ol_kind = 0;
+  std::vector<size_t> lin_lf;
+  double* d_ol_out = nullptr; size_t ol_out_cap = 0;
   int capture_pass(double* const* d_bufs, int part, hipGraphExec_t* exec);
   int prepare_pass();
   int begin_pass(double* const* d_bufs, bool* same);

@@ -13,6 +13,10 @@ void init_solver_kernels();   // one-time kernel attributes (call outside stream
 void launch_relin(const GraphDev& G, hipStream_t s);
 void launch_linearize(const GraphDev& G, const ObsLossDev& O, hipStream_t s);      // O.kind != 0: the landmark factors under the observation loss (same launch count)
 void launch_observation_weights(const GraphDev& G, const ObsLossDev& O, bool robust, int n, double* out2n, hipStream_t s);      // (weight, s^2) of landmark factors [0, n)
+// the same for the members of a batch in one launch (dO: their ObsLossDev table beside d; off / cnt: host arrays, member i writes its
+// factors [0, cnt[i]) behind off[i] rows of out2n)
+void launch_observation_weights_batched(const GraphDev* d, const ObsLossDev* dO, bool robust, const int* off, const int* cnt, int n, double* out2n,
+                                        hipStream_t s);
 void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s);      // ahead of launch_linearize while a robust loss is set (no launch otherwise)
 void launch_closure_weights(const GraphDev& G, const RobustDev& R, const int* idx, int n, double* out2n, hipStream_t s);   // (weight, s^2) of the listed between factors
 // the batch's robust loss (dR: the members' RobustDev table beside d): k_robust_reweight_b between k_relin_b and the linearisation
@@ -36,7 +40,9 @@ void launch_gather(void* stage, unsigned desc_off, int nseg, hipStream_t s);
 void launch_gather_args(void* stage, const void* segs, int nseg, hipStream_t s);      // the same, up to 16 descriptors as kernel arguments
 void launch_sum_bcast(double* const* bufs, int n, int count, hipStream_t s);   // local all-reduce(sum) of up to 8 buffers
 void launch_bcast(double* const* bufs, int n, int count, hipStream_t s);       // bufs[0] -> the others
-void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack = true, const RobustDev* dR = nullptr);   // the per-robot phases 0 / 4 / 2 of a batched pass,
+void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack = true, const RobustDev* dR = nullptr,
+                           const ObsLossDev* dO = nullptr);   // the per-robot phases 0 / 4 / 2 of a batched pass (dO: the batch's observation loss, k_lin_lf_robust_b in k_lin_lf_b's place),
+void launch_linearize_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s, const ObsLossDev* dO = nullptr);      // phase 0's linearisation launch alone
 void launch_phase4_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s);   // blockIdx.z = robot
 void launch_phase2_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s);
 void launch_phase3_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s);   // blockIdx.z = robot               // local all-reduce(sum) of up to 8 buffers             // device arrays -> one staging buffer (DownloadBatch)   // staged upload -> destinations (UploadBatch)

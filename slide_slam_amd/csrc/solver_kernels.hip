@@ -364,6 +364,15 @@ __global__ __launch_bounds__(256) void k_lin_lf_b(const GraphDev* __restrict__ G
   if ((int)blockIdx.x < nb0) k_lin_pose_factors_body(Gs[blockIdx.z], blockIdx.x * 256 + threadIdx.x);
   else k_lin_lf_body<false>(Gs[blockIdx.z], ObsLossDev{}, nb1, (int)blockIdx.x - nb0);
 }
+// the batched launch while the batch has an observation loss (slide_chol_batch_set_observation_loss; launch_phase0_batched picks it):
+// Os is the members' table beside Gs, their own lf_w / lf_s2 under the batch's kind, mask and param.  pose0 is 0 in every batched
+// pass, so every factor of every member is linearised and weighted in every pass; the record is all k_landmark_b, k_pose_b, the Schur
+// kernels and the border / separator assembly read of a factor, so this is the whole reweighted joint step, the shared landmarks'
+// rows of the separator system included.  Os[z] is uniform over the workgroup, like Gs[z].
+__global__ __launch_bounds__(256) void k_lin_lf_robust_b(const GraphDev* __restrict__ Gs, const ObsLossDev* __restrict__ Os, int nb0, int nb1) {
+  if ((int)blockIdx.x < nb0) k_lin_pose_factors_body(Gs[blockIdx.z], blockIdx.x * 256 + threadIdx.x);
+  else k_lin_lf_body<true>(Gs[blockIdx.z], Os[blockIdx.z], nb1, (int)blockIdx.x - nb0);
+}
 
 // ------------------------------------------------------------------------------------------------
 // landmark reduce: H_ll = sum Jl^T Jl, g_l = sum Jl^T r, H_ll^-1, and per factor
@@ -2119,28 +2128,37 @@ void launch_phase3_arrow_batched(const GraphDev* d, const GraphDev* h, int n, hi
   if (!m_fill) launch_border_assemble_batched(d, h, n, s);
 }
 __global__ void k_shared_pack_b(const GraphDev* __restrict__ Gs, int what, BufPtrs B) { k_shared_pack_body(Gs[blockIdx.z], what, B.p[blockIdx.z]); }
-// The per-robot phases of a batched pass in ONE launch sequence for all robots (blockIdx.z = robot, grids sized for the largest graph):
-// forking every robot's phase onto its own stream and joining again cost three cross-stream joins of ~15 us per pass.
-// phase 0: relinearise, linearise, per-landmark partial sums, pack H_ll / g_l of the shared slots
-void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack, const RobustDev* dR) {
-  int L = 0, P = 0, slots = 0, npf = 0;
+// the linearisation of a batched pass: one launch for all members; dO (the batch's observation loss) picks k_lin_lf_robust_b, the
+// launch count is the same either way, and a batch none of whose members has a landmark factor takes the pose-factor kernel as before
+void launch_linearize_batched(const GraphDev* d, const GraphDev* h, int n, hipStream_t s, const ObsLossDev* dO) {
+  int npf = 0;
   long long nlf = 0, nnbr = 0;
   for (int i = 0; i < n; ++i) {
-    L = std::max(L, h[i].L); P = std::max(P, h[i].P); slots = std::max(slots, h[i].n_slots);
     npf = std::max(npf, h[i].n_prior + h[i].n_between + h[i].n_ghost);
     nlf = std::max<long long>(nlf, h[i].n_lf);
     nnbr = std::max<long long>(nnbr, h[i].n_nbr);
   }
+  if (nlf > 0) {
+    const int nb0 = npf > 0 ? (int)blocks_for(npf, 256) : 0;
+    const dim3 grid(nb0 + blocks_for(nlf, 256) + blocks_for(32LL * nnbr, 256), 1, n);
+    if (dO) hipLaunchKernelGGL(k_lin_lf_robust_b, grid, dim3(256), 0, s, d, dO, nb0, (int)blocks_for(nlf, 256));
+    else hipLaunchKernelGGL(k_lin_lf_b, grid, dim3(256), 0, s, d, nb0, (int)blocks_for(nlf, 256));
+  } else if (npf > 0) {
+    hipLaunchKernelGGL(k_lin_pose_factors_b, dim3(blocks_for(npf, 128), 1, n), dim3(128), 0, s, d);
+  }
+}
+// The per-robot phases of a batched pass in ONE launch sequence for all robots (blockIdx.z = robot, grids sized for the largest graph):
+// forking every robot's phase onto its own stream and joining again cost three cross-stream joins of ~15 us per pass.
+// phase 0: relinearise, linearise, per-landmark partial sums, pack H_ll / g_l of the shared slots
+void launch_phase0_batched(const GraphDev* d, const GraphDev* h, int n, double* const* bufs, hipStream_t s, bool pack, const RobustDev* dR,
+                           const ObsLossDev* dO) {
+  int L = 0, P = 0, slots = 0;
+  for (int i = 0; i < n; ++i) { L = std::max(L, h[i].L); P = std::max(P, h[i].P); slots = std::max(slots, h[i].n_slots); }
   BufPtrs B{};
   for (int i = 0; i < n; ++i) B.p[i] = bufs[i];
   if (P + L > 0) hipLaunchKernelGGL(k_relin_b, dim3(blocks_for(P + L, 256), 1, n), dim3(256), 0, s, d);
   if (dR) launch_robust_reweight_batched(d, dR, h, n, s);      // (only while the batch has a robust loss: the weights at the point the factors are linearised at)
-  if (nlf > 0) {
-    const int nb0 = npf > 0 ? (int)blocks_for(npf, 256) : 0;
-    hipLaunchKernelGGL(k_lin_lf_b, dim3(nb0 + blocks_for(nlf, 256) + blocks_for(32LL * nnbr, 256), 1, n), dim3(256), 0, s, d, nb0, (int)blocks_for(nlf, 256));
-  } else if (npf > 0) {
-    hipLaunchKernelGGL(k_lin_pose_factors_b, dim3(blocks_for(npf, 128), 1, n), dim3(128), 0, s, d);
-  }
+  launch_linearize_batched(d, h, n, s, dO);
   if (L > 0 && pack) hipLaunchKernelGGL(k_landmark_b<1>, dim3(blocks_for(L, 4), 1, n), dim3(256), 0, s, d);      // (!pack: the exact joint pass sums and finishes in one launch, k_landmark_b<3>)
   if (slots > 0 && pack) hipLaunchKernelGGL(k_shared_pack_b, dim3(blocks_for(54LL * slots, 128), 1, n), dim3(128), 0, s, d, 0, B);
 }
@@ -2427,8 +2445,38 @@ __global__ __launch_bounds__(128) void k_observation_weights(GraphDev G, ObsLoss
   }
 }
 
+// slide_chol_batch_get_observation_weights: the same for every member of a batch in one launch (blockIdx.z = member, the grid sized
+// for the largest): member z writes its factors [0, T.cnt[z]) behind T.off[z] rows of the one output array.
+struct ObsOutTab { int off[8]; int cnt[8]; };
+__global__ __launch_bounds__(128) void k_observation_weights_b(const GraphDev* __restrict__ Gs, const ObsLossDev* __restrict__ Os, int robust, ObsOutTab T,
+                                                               double* __restrict__ out) {
+  const GraphDev& G = Gs[blockIdx.z];
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= T.cnt[blockIdx.z] || f >= G.n_lf) return;
+  double* o = out + 2 * ((size_t)T.off[blockIdx.z] + f);
+  if (robust) {
+    const ObsLossDev& O = Os[blockIdx.z];
+    o[0] = O.lf_w[f];
+    o[1] = O.lf_s2[f];
+  } else {
+    const double* r = G.jbuf + G.lf_joff[f];
+    const int m = lf_rows(G.lf_type[f]);
+    double s2 = 0.0;
+    for (int i = 0; i < m; ++i) s2 += r[i] * r[i];
+    o[0] = 1.0;
+    o[1] = s2;
+  }
+}
+
 void launch_observation_weights(const GraphDev& G, const ObsLossDev& O, bool robust, int n, double* out2n, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_observation_weights, dim3(blocks_for(n, 128)), dim3(128), 0, s, G, O, robust ? 1 : 0, n, out2n);
+}
+void launch_observation_weights_batched(const GraphDev* d, const ObsLossDev* dO, bool robust, const int* off, const int* cnt, int n, double* out2n,
+                                        hipStream_t s) {
+  ObsOutTab T{};
+  int most = 0;
+  for (int i = 0; i < n && i < 8; ++i) { T.off[i] = off[i]; T.cnt[i] = cnt[i]; most = std::max(most, cnt[i]); }
+  if (most > 0) hipLaunchKernelGGL(k_observation_weights_b, dim3(blocks_for(most, 128), 1, std::min(n, 8)), dim3(128), 0, s, d, dO, robust ? 1 : 0, T, out2n);
 }
 void launch_robust_reweight(const GraphDev& G, const RobustDev& R, hipStream_t s) {
   if (R.kind == 0 || G.n_between == 0) return;

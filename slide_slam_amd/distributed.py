@@ -722,6 +722,33 @@ class PassDriver:
                 raise RuntimeError(f"set_robust_loss: the ranks disagree on the loss: {sorted(set(seen))}")
         self.batch.set_robust_loss(kind, param, closures, relative_meas)
 
+    # ---- observation loss on the exact joint pass (CholBatch.set_observation_loss, slide_gpu.h) ---------------------------------------
+    def set_observation_loss(self, kind, param=0.0, points=True, cubes=True, cylinders=True):
+        """The batch's observation loss for this driver's passes, whole or cut: every robot's bearing-range (points), cube and
+        cylinder factors, the observations of the shared landmarks included.  Batched exact-joint drivers only: the un-batched and
+        CPU-rehearsal passes and the PCG passes do not carry a loss.  Every rank of a job must set the same loss."""
+        if self.batch is None or not self.arrow:
+            raise ValueError("set_observation_loss needs a CholBatch running exact joint passes (arrow=True): the un-batched, CPU and PCG passes do not carry an observation loss")
+        if self.world > 1 and self.base is not None:
+            from .api import SlideGraph
+            k = SlideGraph.ROBUST_KINDS.get(kind, kind) if (kind is None or isinstance(kind, str)) else int(kind)
+            on = k not in (0, None)      # (compared as resolved, as in set_robust_loss)
+            mine = (k if on else 0, max(float(param), 0.0) if on else 0.0, bool(points) and on, bool(cubes) and on, bool(cylinders) and on)
+            seen = self.base.all_gather_object(mine)
+            if len(set(seen)) != 1:
+                raise RuntimeError(f"set_observation_loss: the ranks disagree on the loss: {sorted(set(seen))}")
+        self.batch.set_observation_loss(kind, param, points, cubes, cylinders)
+
+    def observation_weights(self):
+        """After a pass: CholBatch.observation_weights' rows of this process's robots (slot, pose_idx, cls, lm_idx, weight, s2, n)
+        with "robot", the job's virtual robot index rank * R + slot of every row (setup_ghosts' rank; 0 for a job of one process).
+        A shared landmark is listed by every robot that observes it, each row under that robot's own landmark index."""
+        if self.batch is None or not self.arrow:
+            raise ValueError("observation_weights needs a CholBatch running exact joint passes (arrow=True)")
+        ow = self.batch.observation_weights()
+        ow["robot"] = (getattr(self, "rank", 0) * len(self.shards) + ow["slot"]).astype(np.int32)
+        return ow
+
     def closure_weights(self):
         """After a pass: {"between": the robots' own loop-closure / relative-measurement factors (robot = virtual robot index
         rank * R + slot with setup_ghosts' rank, from_idx, to_idx, kind, weight, s2; slot by slot in insertion order), "relmeas": one
