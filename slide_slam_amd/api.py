@@ -196,6 +196,36 @@ def _sigma6(sigma_per_m):
     return sg
 
 
+ROBUST_KINDS = {None: 0, "none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "dcs": 4}
+# the columns of the weight read-backs, in the C ABI's argument order
+_I32, _U64, _F64 = np.int32, np.uint64, np.float64
+_CLOSURE_COLS = [("from_robot", _I32), ("from_idx", _U64), ("to_robot", _I32), ("to_idx", _U64), ("kind", _I32)]
+_OBSERVATION_COLS = [("pose_idx", _U64), ("cls", _I32), ("lm_idx", _U64)]
+_WEIGHT_COLS = [("weight", _F64), ("s2", _F64)]
+
+
+def _loss_kind(kind, what):
+    """The kind of a loss (`what`: "robust" / "observation") as the C ABI takes it: a name of ROBUST_KINDS resolved, a number passed on."""
+    if kind is None or isinstance(kind, str):
+        if kind not in ROBUST_KINDS:
+            raise ValueError(f"{what} loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
+        kind = ROBUST_KINDS[kind]
+    return C.c_int(int(kind))
+
+
+def _weights(fn, handle, columns, cap=None):
+    """The read-back of a *_get_*_weights call: the count first (cap None), then one array per (name, dtype) column filled up to
+    cap rows.  Returns the columns cut to the rows written, and n, the full count."""
+    n = C.c_int(0)
+    if cap is None:
+        _check(fn(handle, C.c_int(0), *[None] * len(columns), C.byref(n)))
+        cap = n.value
+    cols = {name: np.zeros(max(int(cap), 1), dt) for name, dt in columns}
+    _check(fn(handle, C.c_int(int(cap)), *[_p(a) for a in cols.values()], C.byref(n)))
+    k = min(int(cap), n.value)
+    return {**{name: a[:k].copy() for name, a in cols.items()}, "n": n.value}
+
+
 class SlideGraph:
     """SemanticFactorGraph seam (reference include/factorgraph/graph.h:70-121) on the MI355X."""
 
@@ -430,64 +460,33 @@ class SlideGraph:
         off = np.ascontiguousarray(offsets, dtype=np.int32)
         _check(self.L.slide_graph_set_separator(self.h, _p(off), C.c_int(len(off))))
 
-    ROBUST_KINDS = {None: 0, "none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "dcs": 4}
+    ROBUST_KINDS = ROBUST_KINDS
 
     def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
         """slide_graph_set_robust_loss (GTSAM's noiseModel::Robust on the loop-closure / relative-measurement factors, iteratively
         reweighted): kind = 0 / None (off), 1 / "huber", 2 / "cauchy", 3 / "geman_mcclure", 4 / "dcs"; param <= 0: the loss's default
         (1.345, 0.1, 1.0, 1.0).  Covers factors already added and added later; the next solve relinearises everything."""
-        if kind is None or isinstance(kind, str):
-            if kind not in self.ROBUST_KINDS:
-                raise ValueError(f"robust loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
-            kind = self.ROBUST_KINDS[kind]
         mask = (1 if closures else 0) | (2 if relative_meas else 0)
-        _check(self.L.slide_graph_set_robust_loss(self.h, C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+        _check(self.L.slide_graph_set_robust_loss(self.h, _loss_kind(kind, "robust"), C.c_double(float(param)), C.c_int(mask)))
 
     def closure_weights(self, cap=None):
         """slide_graph_get_closure_weights: every loop-closure (kind 1) and relative-measurement (kind 2) factor in insertion order.
         Returns a dict of arrays: from_robot, from_idx, to_robot, to_idx, kind, weight, s2 (weight and squared whitened norm of the
         factor's last linearisation; weight 1 where no loss applied) and n, the full count (cap: write at most that many)."""
-        n = C.c_int(0)
-        if cap is None:
-            _check(self.L.slide_graph_get_closure_weights(self.h, C.c_int(0), None, None, None, None, None, None, None, C.byref(n)))
-            cap = n.value
-        m = max(int(cap), 1)
-        fr, tr, kd = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
-        fi, ti = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
-        w, s2 = np.zeros(m), np.zeros(m)
-        _check(self.L.slide_graph_get_closure_weights(self.h, C.c_int(int(cap)), _p(fr), _p(fi), _p(tr), _p(ti), _p(kd), _p(w), _p(s2),
-                                                      C.byref(n)))
-        k = min(int(cap), n.value)
-        return {"from_robot": fr[:k].copy(), "from_idx": fi[:k].copy(), "to_robot": tr[:k].copy(), "to_idx": ti[:k].copy(),
-                "kind": kd[:k].copy(), "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
+        return _weights(self.L.slide_graph_get_closure_weights, self.h, _CLOSURE_COLS + _WEIGHT_COLS, cap)
 
     def set_observation_loss(self, kind, param=0.0, points=True, cubes=True, cylinders=True):
         """slide_graph_set_observation_loss (GTSAM's noiseModel::Robust on the bearing-range / cube / cylinder factors, iteratively
         reweighted inside the linearisation kernel): kinds, names and defaults as set_robust_loss; independent of it.  Covers
         factors already added and added later; the next solve relinearises everything."""
-        if kind is None or isinstance(kind, str):
-            if kind not in self.ROBUST_KINDS:
-                raise ValueError(f"observation loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
-            kind = self.ROBUST_KINDS[kind]
         mask = (1 if points else 0) | (2 if cubes else 0) | (4 if cylinders else 0)
-        _check(self.L.slide_graph_set_observation_loss(self.h, C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+        _check(self.L.slide_graph_set_observation_loss(self.h, _loss_kind(kind, "observation"), C.c_double(float(param)), C.c_int(mask)))
 
     def observation_weights(self, cap=None):
         """slide_graph_get_observation_weights: every landmark factor in insertion order.  Returns a dict of arrays: robot, pose_idx,
         cls (SLIDE_CLS_*), lm_idx, weight, s2 (weight and unscaled squared whitened norm of the factor's last linearisation; weight 1
         where no loss applied) and n, the full count (cap: write at most that many)."""
-        n = C.c_int(0)
-        if cap is None:
-            _check(self.L.slide_graph_get_observation_weights(self.h, C.c_int(0), None, None, None, None, None, None, C.byref(n)))
-            cap = n.value
-        m = max(int(cap), 1)
-        rb, cl = np.zeros(m, np.int32), np.zeros(m, np.int32)
-        pi, li = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
-        w, s2 = np.zeros(m), np.zeros(m)
-        _check(self.L.slide_graph_get_observation_weights(self.h, C.c_int(int(cap)), _p(rb), _p(pi), _p(cl), _p(li), _p(w), _p(s2), C.byref(n)))
-        k = min(int(cap), n.value)
-        return {"robot": rb[:k].copy(), "pose_idx": pi[:k].copy(), "cls": cl[:k].copy(), "lm_idx": li[:k].copy(),
-                "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
+        return _weights(self.L.slide_graph_get_observation_weights, self.h, [("robot", _I32)] + _OBSERVATION_COLS + _WEIGHT_COLS, cap)
 
     def chi2(self):
         """Sum of squared whitened residuals at the current estimate: dict(total, prior, between, landmark).  While a robust loss
@@ -708,33 +707,16 @@ class CholBatch:
         """slide_chol_batch_set_robust_loss: SlideGraph.set_robust_loss's loss (same kinds, names and defaults) on the exact joint
         pass, uniform over the member graphs: their loop closures (closures) and relative measurements, the inter-robot relative-pose
         factors included (relative_meas).  kind 0 / None clears it.  Not with PCG passes."""
-        if kind is None or isinstance(kind, str):
-            if kind not in SlideGraph.ROBUST_KINDS:
-                raise ValueError(f"robust loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
-            kind = SlideGraph.ROBUST_KINDS[kind]
         mask = (1 if closures else 0) | (2 if relative_meas else 0)
-        _check(self.L.slide_chol_batch_set_robust_loss(C.c_void_p(self.h), C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+        _check(self.L.slide_chol_batch_set_robust_loss(C.c_void_p(self.h), _loss_kind(kind, "robust"), C.c_double(float(param)), C.c_int(mask)))
 
     def closure_weights(self, cap=None):
         """slide_chol_batch_get_closure_weights after a pass: slot by slot the member's loop-closure / relative-measurement between
         factors in insertion order (ghost_id -1), then its ghost factors (the inter-robot relative-pose factors: ghost_id = index in
         the job's list, the other end as robot -1 / idx = ghost slot).  Returns a dict of arrays: slot, from_robot, from_idx,
         to_robot, to_idx, kind, ghost_id, weight, s2, and n, the full count (cap: write at most that many rows)."""
-        n = C.c_int(0)
-        h = C.c_void_p(self.h)
-        if cap is None:
-            _check(self.L.slide_chol_batch_get_closure_weights(h, C.c_int(0), None, None, None, None, None, None, None, None, None, C.byref(n)))
-            cap = n.value
-        m = max(int(cap), 1)
-        sl, fr, tr, kd, gi = (np.zeros(m, np.int32) for _ in range(5))
-        fi, ti = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
-        w, s2 = np.zeros(m), np.zeros(m)
-        _check(self.L.slide_chol_batch_get_closure_weights(h, C.c_int(int(cap)), _p(sl), _p(fr), _p(fi), _p(tr), _p(ti), _p(kd), _p(gi), _p(w),
-                                                           _p(s2), C.byref(n)))
-        k = min(int(cap), n.value)
-        return {"slot": sl[:k].copy(), "from_robot": fr[:k].copy(), "from_idx": fi[:k].copy(), "to_robot": tr[:k].copy(),
-                "to_idx": ti[:k].copy(), "kind": kd[:k].copy(), "ghost_id": gi[:k].copy(), "weight": w[:k].copy(), "s2": s2[:k].copy(),
-                "n": n.value}
+        cols = [("slot", _I32)] + _CLOSURE_COLS + [("ghost_id", _I32)] + _WEIGHT_COLS
+        return _weights(self.L.slide_chol_batch_get_closure_weights, C.c_void_p(self.h), cols, cap)
 
     def profile_robust_reweight(self, buf_ptrs):
         """slide_chol_batch_profile_robust_reweight: milliseconds of the loss's reweighting launch alone, between two events (closure_weights then
@@ -749,12 +731,9 @@ class CholBatch:
         batched passes, uniform over the member graphs: their bearing-range (points), cube and cylinder factors, the observations
         of the shared landmarks included.  Fused into the passes' linearisation launch; independent of set_robust_loss.  kind 0 /
         None clears it.  Not with PCG passes."""
-        if kind is None or isinstance(kind, str):
-            if kind not in SlideGraph.ROBUST_KINDS:
-                raise ValueError(f"observation loss {kind!r}: one of huber, cauchy, geman_mcclure, dcs, None")
-            kind = SlideGraph.ROBUST_KINDS[kind]
         mask = (1 if points else 0) | (2 if cubes else 0) | (4 if cylinders else 0)
-        _check(self.L.slide_chol_batch_set_observation_loss(C.c_void_p(self.h), C.c_int(int(kind)), C.c_double(float(param)), C.c_int(mask)))
+        _check(self.L.slide_chol_batch_set_observation_loss(C.c_void_p(self.h), _loss_kind(kind, "observation"), C.c_double(float(param)),
+                                                            C.c_int(mask)))
 
     def observation_weights(self, cap=None):
         """slide_chol_batch_get_observation_weights after a pass: slot by slot the member's landmark factors in insertion order.
@@ -762,19 +741,8 @@ class CholBatch:
         unscaled squared whitened norm of the factor's linearisation in the last pass; weight 1 where no loss applied) and n, the
         full count (cap: write at most that many rows).  The per-graph SlideGraph.observation_weights of a member does not know
         the batch's loss (weight 1, s2 of the scaled record): use this one."""
-        n = C.c_int(0)
-        h = C.c_void_p(self.h)
-        if cap is None:
-            _check(self.L.slide_chol_batch_get_observation_weights(h, C.c_int(0), None, None, None, None, None, None, C.byref(n)))
-            cap = n.value
-        m = max(int(cap), 1)
-        sl, cl = np.zeros(m, np.int32), np.zeros(m, np.int32)
-        pi, li = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
-        w, s2 = np.zeros(m), np.zeros(m)
-        _check(self.L.slide_chol_batch_get_observation_weights(h, C.c_int(int(cap)), _p(sl), _p(pi), _p(cl), _p(li), _p(w), _p(s2), C.byref(n)))
-        k = min(int(cap), n.value)
-        return {"slot": sl[:k].copy(), "pose_idx": pi[:k].copy(), "cls": cl[:k].copy(), "lm_idx": li[:k].copy(),
-                "weight": w[:k].copy(), "s2": s2[:k].copy(), "n": n.value}
+        cols = [("slot", _I32)] + _OBSERVATION_COLS + _WEIGHT_COLS
+        return _weights(self.L.slide_chol_batch_get_observation_weights, C.c_void_p(self.h), cols, cap)
 
     def profile_linearize(self, buf_ptrs):
         """slide_chol_batch_profile_linearize: milliseconds of the passes' linearisation launch alone, between two events, under the

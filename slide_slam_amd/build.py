@@ -31,6 +31,7 @@ SOURCES = [
     ("closure_kernels.hip", ["-ffp-contract=off"]),     # loop-closure consistency scores compared against a gate
     ("host_graph.hip", ["-ffp-contract=off"]),
     ("host_marginals.hip", ["-ffp-contract=off"]),     # (its Woodbury step runs on the host: same rounding as host_graph.hip)
+    ("host_loss.hip", ["-ffp-contract=off"]),          # (the robust losses' host side, split off host_graph.hip the same way)
     ("host_backend.hip", ["-ffp-contract=off"]),
     ("capi.hip", ["-ffp-contract=off"]),
     ("wire.hip", ["-ffp-contract=off"]),     # host code only: sloam_msgs wire codec + rosbag reader (include/slide_wire.h)

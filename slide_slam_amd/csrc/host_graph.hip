@@ -438,7 +438,6 @@ int HostGraph::merge_pending() {
   return SLIDE_OK;
 }
 
-constexpr int CHOL_BATCH_HOST_MAX = 8;
 // the Cholesky view of a graph's reduced system (joint: with the f32 factor copy of the PCG preconditioner)
 static CholSystem chol_system_of(const GraphDev& G, bool joint, float* L32, const int* h_prof, double* ctab, const int* bfirst, const int* h_bfirst) {
   CholSystem c{};
@@ -466,18 +465,17 @@ void CholBatch::detach(HostGraph* g) {
     if (p == g) { p = nullptr; pass_dirty = true; }
 }
 void HostGraph::join_batch(CholBatch* b, int slot) {
-  pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
   CholBatch* old = nullptr;
   {
     std::lock_guard<std::mutex> lk(mtx);
+    drop_stream_state();
     old = batch;
     batch = b;
     batch_slot = slot;
     // (a batch's robust loss stays with the batch: the graph takes its base sigmas along, and the loss of the batch it joins — if
     // any — at that batch's next pass)
-    if (old && old != b && rb_kind == 0) (void)restore_base_sigmas();
-    factor_valid = false;   // (batched passes factor into the same S: a factor left by one is not the streaming path's)
-    wf_T = 0;               // (nor is its dp the last streaming solve's solution)
+    if (old && old != b && RB.kind == 0) (void)restore_base_sigmas();
+    drop_factor();          // (batched passes factor into the same S: a factor left by one is not the streaming path's, nor its dp the last streaming solve's solution)
     topo_dirty = true;      // (the joint-solve buffers depend on the batch's setting: upload_new looks again)
   }
   if (old && old != b) old->detach(this);
@@ -488,7 +486,7 @@ CholBatch::~CholBatch() {
   for (hipStream_t a : aux) if (a) (void)hipStreamSynchronize(a);
   for (auto& e : part_exec) if (e) (void)hipGraphExecDestroy(e);
   for (HostGraph* g : graphs)
-    if (g) { std::lock_guard<std::mutex> gl(g->mtx); if (g->batch == this) { g->batch = nullptr; if (rb_kind != 0) (void)g->restore_base_sigmas(); } }
+    if (g) { std::lock_guard<std::mutex> gl(g->mtx); if (g->batch == this) { g->batch = nullptr; if (rb.on()) (void)g->restore_base_sigmas(); } }
   for (hipEvent_t e : ev_in) if (e) (void)hipEventDestroy(e);
   if (ev_out) (void)hipEventDestroy(ev_out);
   if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -608,13 +606,13 @@ int CholBatch::prepare_pass() {
   if (!d_Gs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Gs), CHOL_BATCH_HOST_MAX * sizeof(GraphDev)));
   if (!d_status_all) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_status_all), CHOL_BATCH_HOST_MAX * 8 * sizeof(int)));
   SL_HIP(hipMemcpyAsync(d_Gs, hG.data(), n * sizeof(GraphDev), hipMemcpyHostToDevice, master));      // (not the legacy stream: other host threads may be capturing)
-  if (rb_kind != 0) {      // (the robust views beside them, only while the batch has a loss)
+  if (rb.on()) {      // (the robust views beside them, only while the batch has a loss)
     hR.resize(n);
     for (int i = 0; i < n; ++i) hR[i] = member_view(graphs[i]);
     if (!d_Rs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Rs), CHOL_BATCH_HOST_MAX * sizeof(RobustDev)));
     SL_HIP(hipMemcpyAsync(d_Rs, hR.data(), n * sizeof(RobustDev), hipMemcpyHostToDevice, master));
   }
-  if (ol_kind != 0) {      // (and the observation loss's, likewise)
+  if (ol.on()) {      // (and the observation loss's, likewise)
     hO.resize(n);
     for (int i = 0; i < n; ++i) hO[i] = member_obs_view(graphs[i]);
     if (!d_Os) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Os), CHOL_BATCH_HOST_MAX * sizeof(ObsLossDev)));
@@ -1185,7 +1183,7 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
     launch_status_clear(d_Gs, n, master, sep_status, sep_nl > 0 ? lam_status : nullptr);
     const int rg = enqueue_ghost_refresh(d_bufs, part);
     if (rg != SLIDE_OK) return rg;
-    launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, false, rb_kind != 0 ? d_Rs : nullptr, ol_kind != 0 ? d_Os : nullptr);      // relinearise, [reweight,] linearise, the robots' own per-landmark sums (nothing to pack: no exchange of them)
+    launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, false, rb.on() ? d_Rs : nullptr, ol.on() ? d_Os : nullptr);      // relinearise, [reweight,] linearise, the robots' own per-landmark sums (nothing to pack: no exchange of them)
     launch_phase3_arrow_batched(d_Gs, hG.data(), n, master);         // private landmarks eliminated, reduced pose systems, borders
     {
       int nq[CHOL_BATCH_HOST_MAX];
@@ -1419,9 +1417,9 @@ int CholBatch::enqueue_pass(double* const* d_bufs, hipEvent_t e0, hipEvent_t e1,
   if (whole || part == 0) {
     launch_status_clear(d_Gs, n, master);      // (a kernel node: a captured hipMemsetAsync did not clear on replay, DESIGN §4 finding 6)
     if ((rc = enqueue_ghost_refresh(d_bufs, part)) != SLIDE_OK) return rc;
-    if (!batch_p3 && rb_kind != 0) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's robust loss"; return SLIDE_ERR_INVALID; }
-    if (!batch_p3 && ol_kind != 0) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's observation loss"; return SLIDE_ERR_INVALID; }
-    if (batch_p3) launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, true, rb_kind != 0 ? d_Rs : nullptr, ol_kind != 0 ? d_Os : nullptr);      // (all robots in one launch sequence: no fork / join)
+    if (!batch_p3 && rb.on()) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's robust loss"; return SLIDE_ERR_INVALID; }
+    if (!batch_p3 && ol.on()) { g_last_error = "batched pass: SLIDE_BATCH_PHASE3=0 does not carry the batch's observation loss"; return SLIDE_ERR_INVALID; }
+    if (batch_p3) launch_phase0_batched(d_Gs, hG.data(), n, d_bufs, master, true, rb.on() ? d_Rs : nullptr, ol.on() ? d_Os : nullptr);      // (all robots in one launch sequence: no fork / join)
     else each(0);
     if (rc == SLIDE_OK) launch_sum_bcast(d_bufs, n, 54 * n_slots, master);
   }
@@ -1510,19 +1508,12 @@ int CholBatch::profile_pass(double* const* d_bufs, double* ms_steps, int* n_laun
     SL_HIP(hipStreamCreateWithFlags(&master, hipStreamNonBlocking));
     SL_HIP(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
   }
+  int rc = SLIDE_OK;
   for (int i = 0; i < n; ++i) {
-    HostGraph* g = graphs[i];
-    std::lock_guard<std::mutex> gl(g->mtx);
-    g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;      // (a batched pass rewrites the status words, deltas and estimates)
-    if (rb_kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }
-    if (ol_kind != 0 && !g->ol_arrays) { g->ol_arrays = true; g->topo_dirty = true; }
-    int rc = g->merge_pending();
-    if (rc == SLIDE_OK) rc = g->upload_new();
-    if (rc != SLIDE_OK) return rc;
-    g->G.relin_thr = 0.0;
-    SL_HIP(hipStreamSynchronize(g->stream));
+    std::lock_guard<std::mutex> gl(graphs[i]->mtx);
+    if ((rc = prepare_member(graphs[i], false)) != SLIDE_OK) return rc;
   }
-  int rc = prepare_pass();
+  rc = prepare_pass();
   if (rc != SLIDE_OK) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   SL_HIP(hipEventCreate(&e0));
@@ -1541,6 +1532,25 @@ int CholBatch::profile_pass(double* const* d_bufs, double* ms_steps, int* n_laun
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return rc;
+}
+
+// Brings one member up to date for a pass that starts now (the caller holds its lock).  for_pass: begin_pass's form, which also notes
+// what the pass linearises and refuses members that disagree on the shared slots.  profile_pass (for_pass false) has never done
+// either; the history records no reason, and the difference is kept as it is.
+int CholBatch::prepare_member(HostGraph* g, bool for_pass) {
+  g->drop_stream_state();      // (a batched pass rewrites the status words, deltas and estimates)
+  if (rb.on() && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }      // (a member new to the batch's loss: upload_new creates its robust arrays)
+  if (ol.on() && !g->ol_arrays) { g->ol_arrays = true; g->topo_dirty = true; }      // (likewise lf_w / lf_s2 under the batch's observation loss)
+  int rc = g->merge_pending();
+  if (rc == SLIDE_OK) rc = g->upload_new();
+  if (rc != SLIDE_OK) return rc;
+  g->G.relin_thr = 0.0;
+  if (for_pass) {
+    g->note_linearisation();      // (the pass linearises every factor of the member: its own read-backs, which know no loss of the batch, report w = 1 and the records' |r|^2)
+    if (g->G.n_slots != graphs[0]->G.n_slots) { g_last_error = "batched pass: the graphs disagree on the shared slots"; return SLIDE_ERR_INVALID; }
+  }
+  SL_HIP(hipStreamSynchronize(g->stream));      // (uploads of a changed graph; idle otherwise)
+  return SLIDE_OK;
 }
 
 // Brings every joined graph up to date, clears the status words and decides whether the captured launch sequences still fit
@@ -1563,23 +1573,15 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
   for (int i = 0; i < n; ++i) {
     HostGraph* g = graphs[i];
     std::lock_guard<std::mutex> gl(g->mtx);
-    g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;      // (a batched pass rewrites the status words, deltas and estimates)
-    if (rb_kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }      // (a member new to the batch's loss: upload_new creates its robust arrays)
-    if (ol_kind != 0 && !g->ol_arrays) { g->ol_arrays = true; g->topo_dirty = true; }      // (likewise lf_w / lf_s2 under the batch's observation loss)
-    int rc = g->merge_pending();
-    if (rc == SLIDE_OK) rc = g->upload_new();
+    const int rc = prepare_member(g, true);
     if (rc != SLIDE_OK) return rc;
-    g->G.relin_thr = 0.0;
-    g->note_linearisation();      // (the pass linearises every factor of the member: its own read-backs, which know no loss of the batch, report w = 1 and the records' |r|^2)
-    if (g->G.n_slots != graphs[0]->G.n_slots) { g_last_error = "batched pass: the graphs disagree on the shared slots"; return SLIDE_ERR_INVALID; }
-    SL_HIP(hipStreamSynchronize(g->stream));                       // (uploads of a changed graph; idle otherwise)
     *same = *same && std::memcmp(&pass_G[i], &g->G, sizeof(GraphDev)) == 0 && pass_bufs[i] == d_bufs[i];
-    if (rb_kind != 0 && *same) {
+    if (rb.on() && *same) {
       const RobustDev Rv = member_view(g);
       *same = (int)pass_R.size() == n && std::memcmp(&pass_R[i], &Rv, sizeof(RobustDev)) == 0;
     }
     if (*same) {      // (the observation loss, or the address of a member's weight arrays, changed: the captured linearisation is stale)
-      if (ol_kind != 0) {
+      if (ol.on()) {
         const ObsLossDev Ov = member_obs_view(g);
         *same = (int)pass_O.size() == n && std::memcmp(&pass_O[i], &Ov, sizeof(ObsLossDev)) == 0;
       } else *same = pass_O.empty();
@@ -1595,9 +1597,9 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
     pass_bufs.assign(d_bufs, d_bufs + n);
     for (int i = 0; i < n; ++i) pass_G[i] = graphs[i]->G;
     pass_R.clear();
-    if (rb_kind != 0) pass_R = hR;
+    if (rb.on()) pass_R = hR;
     pass_O.clear();
-    if (ol_kind != 0) pass_O = hO;
+    if (ol.on()) pass_O = hO;
   }
   note_pass();
   return SLIDE_OK;
@@ -1605,11 +1607,11 @@ int CholBatch::begin_pass(double* const* d_bufs, bool* same) {
 // what the pass that starts now linearises: the read-back reports these factors under this loss
 void CholBatch::note_pass() {
   rb_pass_done = true;
-  lin_rb_kind = rb_kind; lin_rb_mask = rb_mask;
+  lin_rb_kind = rb.kind; lin_rb_mask = rb.mask;
   lin_bt.resize(n); lin_gh.resize(n);
   for (int i = 0; i < n; ++i) { lin_bt[i] = (size_t)graphs[i]->G.n_between; lin_gh[i] = (size_t)graphs[i]->G.n_ghost; }
   ol_pass_done = true;
-  lin_ol_kind = ol_kind;
+  lin_ol_kind = ol.kind;
   lin_lf.resize(n);
   for (int i = 0; i < n; ++i) lin_lf[i] = (size_t)graphs[i]->G.n_lf;
 }
@@ -1693,277 +1695,6 @@ void CholBatch::set_pcg(int iters, double tol) {
   for (HostGraph* g : gs)              // the joined graphs (re)build their device view: the joint-solve buffers are allocated on demand
     if (g) { std::lock_guard<std::mutex> gl(g->mtx); g->topo_dirty = true; }
 }
-static int key_robot(uint64_t key);
-// ---- robust loss of the batch (k_robust_reweight_b) --------------------------------------------------------------------------------
-// The setting lives here, not in the members: a member's own RobustDev carries its arrays (kind 0: its own solves stay unweighted,
-// the per-graph refusals hold), the batch's views add the batch's loss.
-RobustDev CholBatch::member_view(const HostGraph* g) const {
-  RobustDev R = g->RB;
-  R.kind = rb_kind; R.mask = rb_mask; R.param = rb_param;
-  return R;
-}
-int CholBatch::set_robust_loss(int kind, double param, int class_mask) {
-  if (kind < 0 || kind > 4) { g_last_error = "chol_batch_set_robust_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
-  if (class_mask & ~3) { g_last_error = "chol_batch_set_robust_loss: class_mask has bit 0 (loop closures) and bit 1 (relative measurements) only"; return SLIDE_ERR_INVALID; }
-  if (!(param == param)) { g_last_error = "chol_batch_set_robust_loss: param is not a number"; return SLIDE_ERR_INVALID; }
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  if (kind != 0 && pcg_iters > 0) {
-    g_last_error = "chol_batch_set_robust_loss: the batch runs PCG passes (pcg_iters > 0), whose step leaves the inter-robot factors' cross block out; they do not carry a robust loss";
-    return SLIDE_ERR_INVALID;
-  }
-  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
-  std::vector<HostGraph*> gs;
-  {
-    std::lock_guard<std::mutex> lk(mtx);
-    rb_kind = kind;
-    rb_mask = kind ? class_mask : 0;
-    rb_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
-    pass_dirty = true;
-    gs.assign(graphs.begin(), graphs.end());
-  }
-  exact_serial = 0;           // (the joint queries wait for the next pass: the factor and the cached joint Sigma are the old weighting's)
-  rb_pass_done = false;
-  int rc = SLIDE_OK;
-  for (HostGraph* g : gs) {
-    if (!g) continue;
-    std::lock_guard<std::mutex> gl(g->mtx);
-    if (g->restore_base_sigmas() != SLIDE_OK) rc = SLIDE_ERR_HIP;      // every sigma back to its base value: the next pass weights under the new setting
-    g->factor_valid = false;
-    g->wf_T = 0;
-    g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;
-    if (kind != 0 && !g->rb_arrays) { g->rb_arrays = true; g->topo_dirty = true; }
-  }
-  return rc;
-}
-int CholBatch::get_closure_weights(int cap, int32_t* slot, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind,
-                                   int32_t* ghost_id, double* weight, double* s2, int* n_out) {
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  if (!rb_pass_done || (int)lin_bt.size() != n || !master) { g_last_error = "chol_batch_get_closure_weights: nothing was linearised under the current setting yet (pass first)"; return SLIDE_ERR_INVALID; }
-  struct Row { int slot, fac, bt, gh; };      // fac: the kernel's factor number; bt: index in h_closures, or -1; gh: ghost factor, or -1
-  std::vector<Row> rows;
-  std::vector<HostGraph*> gs;
-  {
-    std::lock_guard<std::mutex> lk(mtx);
-    // (a member joined, left or was replaced, or the batch's configuration changed: the device tables are the last pass's, not these graphs')
-    if (pass_dirty) { g_last_error = "chol_batch_get_closure_weights: the batch changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
-    gs.assign(graphs.begin(), graphs.end());
-  }
-  for (int i = 0; i < n; ++i) {
-    HostGraph* g = gs[i];
-    if (!g) { g_last_error = "chol_batch_get_closure_weights: a slot of the batch is empty"; return SLIDE_ERR_INVALID; }
-    std::lock_guard<std::mutex> gl(g->mtx);
-    if ((size_t)g->G.n_between != lin_bt[i] || (size_t)g->G.n_ghost != lin_gh[i]) { g_last_error = "chol_batch_get_closure_weights: a member changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
-    for (size_t c = 0; c < g->h_closures.size(); ++c)
-      if ((size_t)g->h_closures[c].bt < lin_bt[i]) rows.push_back(Row{i, g->h_closures[c].bt, (int)c, -1});
-    for (size_t q = 0; q < lin_gh[i]; ++q) rows.push_back(Row{i, (int)(lin_bt[i] + q), -1, (int)q});
-  }
-  const int total = (int)rows.size();
-  *n_out = total;
-  const int m = std::min(total, std::max(cap, 0));
-  if (m == 0) return SLIDE_OK;
-  if ((size_t)m > rb_ent_cap) {
-    if (d_rb_ent) { (void)hipFree(d_rb_ent); d_rb_ent = nullptr; }
-    if (d_rb_out) { (void)hipFree(d_rb_out); d_rb_out = nullptr; }
-    rb_ent_cap = 0;
-    SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_rb_ent), 2 * (size_t)m * sizeof(int)));
-    SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_rb_out), 2 * (size_t)m * sizeof(double)));
-    rb_ent_cap = (size_t)m;
-  }
-  std::vector<int> ent(2 * (size_t)m);
-  for (int k = 0; k < m; ++k) { ent[2 * (size_t)k] = rows[k].slot; ent[2 * (size_t)k + 1] = rows[k].fac; }
-  // the views of the last pass under the loss it ran with (no loss then: every weight 1, s^2 from the residuals)
-  std::vector<RobustDev> Rq(n);
-  for (int i = 0; i < n; ++i) { Rq[i] = member_view(gs[i]); Rq[i].kind = lin_rb_kind; Rq[i].mask = lin_rb_mask; }
-  if (!d_Rs) SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_Rs), CHOL_BATCH_HOST_MAX * sizeof(RobustDev)));
-  SL_HIP(hipMemcpyAsync(d_Rs, Rq.data(), n * sizeof(RobustDev), hipMemcpyHostToDevice, master));      // (what the captured pass reads as well: the same bytes while a loss is set)
-  SL_HIP(hipMemcpyAsync(d_rb_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice, master));
-  launch_closure_weights_batched(d_Gs, d_Rs, d_rb_ent, m, d_rb_out, master);
-  std::vector<double> out(2 * (size_t)m);
-  SL_HIP(hipMemcpyAsync(out.data(), d_rb_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, master));
-  SL_HIP(hipStreamSynchronize(master));
-  SL_HIP(hipGetLastError());
-  const uint64_t low = 0x00ffffffffffffffull;
-  for (int k = 0; k < m; ++k) {
-    const Row& r = rows[k];
-    HostGraph* g = gs[r.slot];
-    std::lock_guard<std::mutex> gl(g->mtx);
-    uint64_t k0 = 0, k1 = 0;
-    int r0 = -1, r1 = -1, kd = 2, gid = -1;
-    if (r.bt >= 0) {
-      const HostGraph::ClosureRec& c = g->h_closures[r.bt];
-      k0 = c.k0 & low; k1 = c.k1 & low; r0 = key_robot(c.k0); r1 = key_robot(c.k1); kd = g->h_bt_kind[c.bt];
-    } else {
-      const uint64_t key = g->h_gh_key[r.gh];
-      const bool first = g->h_gh_first[r.gh] != 0;
-      (first ? k0 : k1) = key & low; (first ? r0 : r1) = key_robot(key);
-      (first ? k1 : k0) = (uint64_t)g->h_gh_slot[r.gh];
-      if ((size_t)r.gh < g->h_gh_gid.size()) gid = g->h_gh_gid[r.gh];
-    }
-    if (slot) slot[k] = r.slot;
-    if (from_robot) from_robot[k] = r0;
-    if (from_idx) from_idx[k] = k0;
-    if (to_robot) to_robot[k] = r1;
-    if (to_idx) to_idx[k] = k1;
-    if (kind) kind[k] = kd;
-    if (ghost_id) ghost_id[k] = gid;
-    if (weight) weight[k] = out[2 * (size_t)k];
-    if (s2) s2[k] = out[2 * (size_t)k + 1];
-  }
-  return SLIDE_OK;
-}
-// Measurement: k_robust_reweight_b alone between two events on the pass's stream.  It runs on what the last pass left - the ghost
-// values of that pass's start beside the estimates of its end - so the weights it writes belong to no pass: the read-back is
-// refused until the next pass, whose own launch writes every weight and sigma again before anything reads them.  An event pair
-// around one short launch mostly measures the launch.
-int CholBatch::profile_robust_reweight(double* const* d_bufs, double* ms) {
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  if (rb_kind == 0) { g_last_error = "profile_robust_reweight: the batch has no robust loss"; return SLIDE_ERR_INVALID; }
-  bool same = false;
-  int rc = begin_pass(d_bufs, &same);
-  if (rc != SLIDE_OK) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SL_HIP(hipEventCreate(&e0));
-  SL_HIP(hipEventCreate(&e1));
-  (void)hipEventRecord(e0, master);
-  launch_robust_reweight_batched(d_Gs, d_Rs, hG.data(), n, master);
-  (void)hipEventRecord(e1, master);
-  const hipError_t es = hipStreamSynchronize(master);
-  float t = 0.f;
-  if (es != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) rc = SLIDE_ERR_HIP;
-  *ms = t;
-  rb_pass_done = false;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return rc;
-}
-
-// ---- observation loss of the batch (k_lin_lf_robust_b) -----------------------------------------------------------------------------
-// As with the closure loss the setting lives here: a member's own ObsLossDev carries its arrays under kind 0 (its own solves stay
-// unweighted, the per-graph refusals hold), the batch's views add the batch's loss.  Unlike the closure loss nothing of a member is
-// rewritten under it - the weight sits inside the records the next linearisation writes again - so a member that leaves, and the
-// batch's destructor, have nothing to restore.
-ObsLossDev CholBatch::member_obs_view(const HostGraph* g) const {
-  ObsLossDev O = g->OB;
-  O.kind = ol_kind; O.mask = ol_mask; O.param = ol_param;
-  return O;
-}
-int CholBatch::set_observation_loss(int kind, double param, int class_mask) {
-  if (kind < 0 || kind > 4) { g_last_error = "chol_batch_set_observation_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
-  if (class_mask & ~7) { g_last_error = "chol_batch_set_observation_loss: class_mask has bit 0 (bearing-range), bit 1 (cube) and bit 2 (cylinder) only"; return SLIDE_ERR_INVALID; }
-  if (!(param == param)) { g_last_error = "chol_batch_set_observation_loss: param is not a number"; return SLIDE_ERR_INVALID; }
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  if (kind != 0 && pcg_iters > 0) {
-    g_last_error = "chol_batch_set_observation_loss: the batch runs PCG passes (pcg_iters > 0), whose step leaves the inter-robot factors' cross block out; they do not carry an observation loss";
-    return SLIDE_ERR_INVALID;
-  }
-  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
-  std::vector<HostGraph*> gs;
-  {
-    std::lock_guard<std::mutex> lk(mtx);
-    ol_kind = kind;
-    ol_mask = kind ? class_mask : 0;
-    ol_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
-    pass_dirty = true;
-    gs.assign(graphs.begin(), graphs.end());
-  }
-  exact_serial = 0;           // (the joint queries wait for the next pass: the factor and the cached joint Sigma are the old weighting's)
-  ol_pass_done = false;
-  for (HostGraph* g : gs) {      // (the members' weight arrays come with the next pass: begin_pass, upload_new)
-    if (!g) continue;
-    std::lock_guard<std::mutex> gl(g->mtx);
-    g->factor_valid = false;
-    g->wf_T = 0;
-    g->pred_valid = false; g->status_clean = false; g->cache_pose = -1;
-  }
-  return SLIDE_OK;
-}
-int CholBatch::get_observation_weights(int cap, int32_t* slot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2, int* n_out) {
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  if (!ol_pass_done || (int)lin_lf.size() != n || !master) { g_last_error = "chol_batch_get_observation_weights: nothing was linearised under the current setting yet (pass first)"; return SLIDE_ERR_INVALID; }
-  std::vector<HostGraph*> gs;
-  {
-    std::lock_guard<std::mutex> lk(mtx);
-    // (a member joined, left or was replaced, or the batch's configuration changed: the device tables are the last pass's, not these graphs')
-    if (pass_dirty) { g_last_error = "chol_batch_get_observation_weights: the batch changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
-    gs.assign(graphs.begin(), graphs.end());
-  }
-  int off[CHOL_BATCH_HOST_MAX] = {0}, cnt[CHOL_BATCH_HOST_MAX] = {0};
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    HostGraph* g = gs[i];
-    if (!g) { g_last_error = "chol_batch_get_observation_weights: a slot of the batch is empty"; return SLIDE_ERR_INVALID; }
-    std::lock_guard<std::mutex> gl(g->mtx);
-    if ((size_t)g->G.n_lf != lin_lf[i] || g->h_lf_type.size() != lin_lf[i]) { g_last_error = "chol_batch_get_observation_weights: a member changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
-    if (lin_ol_kind != 0 && lin_lf[i] > 0 && (!g->OB.lf_w || !g->OB.lf_s2 || g->up_ol < lin_lf[i])) { g_last_error = "chol_batch_get_observation_weights: a member changed since the last pass (pass first)"; return SLIDE_ERR_INVALID; }
-    off[i] = (int)total;
-    total += (long long)lin_lf[i];
-  }
-  if (total > 0x7fffffffLL) { g_last_error = "chol_batch_get_observation_weights: too many factors"; return SLIDE_ERR_INVALID; }
-  *n_out = (int)total;
-  const int m = (int)std::min<long long>(total, std::max(cap, 0));
-  if (m == 0) return SLIDE_OK;
-  for (int i = 0; i < n; ++i) cnt[i] = std::max(0, std::min((int)lin_lf[i], m - off[i]));      // (rows past cap are not written)
-  std::vector<double> out;
-  if (weight || s2) {
-    if ((size_t)m > ol_out_cap) {
-      if (d_ol_out) { (void)hipFree(d_ol_out); d_ol_out = nullptr; }
-      ol_out_cap = 0;
-      SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_ol_out), 2 * (size_t)m * sizeof(double)));
-      ol_out_cap = (size_t)m;
-    }
-    // d_Gs and d_Os are the last pass's tables: with a loss then, d_Os holds the members' arrays that pass wrote
-    launch_observation_weights_batched(d_Gs, d_Os, lin_ol_kind != 0, off, cnt, n, d_ol_out, master);
-    out.resize(2 * (size_t)m);
-    SL_HIP(hipMemcpyAsync(out.data(), d_ol_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, master));
-    SL_HIP(hipStreamSynchronize(master));
-    SL_HIP(hipGetLastError());
-  }
-  const uint64_t low = 0x00ffffffffffffffull;
-  for (int i = 0; i < n; ++i) {
-    if (cnt[i] == 0) continue;
-    HostGraph* g = gs[i];
-    std::lock_guard<std::mutex> gl(g->mtx);
-    std::vector<uint64_t> pkey, lkey;      // ids -> keys (the graph keeps the maps the other way round)
-    if (pose_idx) { pkey.assign(g->h_pose_val.size() / 12, 0); for (const auto& kv : g->key2pose) pkey[kv.second] = kv.first; }
-    if (lm_idx) { lkey.assign(g->h_lm_type.size(), 0); for (const auto& kv : g->key2lm) lkey[kv.second] = kv.first; }
-    for (int f = 0; f < cnt[i]; ++f) {
-      const size_t k = (size_t)off[i] + f;
-      if (slot) slot[k] = i;
-      if (pose_idx) pose_idx[k] = pkey[g->h_lf_pose[f]] & low;
-      if (cls) cls[k] = g->h_lf_type[f] == FT_CYL ? SLIDE_CLS_CYLINDER : (g->h_lf_type[f] == FT_CUBE ? SLIDE_CLS_CUBE : SLIDE_CLS_ELLIPSOID);
-      if (lm_idx) lm_idx[k] = lkey[g->h_lf_lm[f]] & low;
-      if (weight) weight[k] = out[2 * k];
-      if (s2) s2[k] = out[2 * k + 1];
-    }
-  }
-  return SLIDE_OK;
-}
-// Measurement: the pass's linearisation launch alone between two events on the pass's stream, under the batch's current loss.  It
-// linearises at the point the last pass left, so what it writes belongs to no pass: the read-backs and the joint queries wait for
-// the next pass.  An event pair around one short launch mostly measures the launch.
-int CholBatch::profile_linearize(double* const* d_bufs, double* ms) {
-  std::lock_guard<std::mutex> pl(pass_mtx);
-  bool same = false;
-  int rc = begin_pass(d_bufs, &same);
-  if (rc != SLIDE_OK) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SL_HIP(hipEventCreate(&e0));
-  SL_HIP(hipEventCreate(&e1));
-  (void)hipEventRecord(e0, master);
-  launch_linearize_batched(d_Gs, hG.data(), n, master, ol_kind != 0 ? d_Os : nullptr);
-  (void)hipEventRecord(e1, master);
-  const hipError_t es = hipStreamSynchronize(master);
-  float t = 0.f;
-  if (es != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess) rc = SLIDE_ERR_HIP;
-  *ms = t;
-  exact_serial = 0;
-  rb_pass_done = false;
-  ol_pass_done = false;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return rc;
-}
-
 // S -> S0 for every joined graph (the factorisation works in place; the joint solve multiplies with the original blocks)
 int CholBatch::save_systems() {
   for (int i = 0; i < n; ++i) {
@@ -2644,9 +2375,7 @@ int HostGraph::upload_new() {
   G.bt_r = d_bt_r.d; G.bt_J0 = d_bt_J0.d;
   RB.bt_sigma0 = d_bt_sigma0.d; RB.bt_w = d_bt_w.d; RB.bt_s2 = d_bt_s2.d; RB.bt_kind = d_bt_kind.d;      // (null until a robust loss is set)
   RB.gh_sigma0 = d_gh_sigma0.d; RB.gh_w = d_gh_w.d; RB.gh_s2 = d_gh_s2.d;
-  RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
   OB.lf_w = d_lf_w.d; OB.lf_s2 = d_lf_s2.d;      // (null until an observation loss is set)
-  OB.kind = ol_kind; OB.mask = ol_mask; OB.param = ol_param;
   G.n_ghost = (int)ngh; G.gh_pose = d_gh_pose.d; G.gh_slot = d_gh_slot.d; G.gh_first = d_gh_first.d; G.gh_z = d_gh_z.d;
   G.gh_sigma = d_gh_sigma.d; G.gh_r = d_gh_r.d; G.gh_J = d_gh_J.d;
   G.n_gslots = (int)h_gslot_pose.size(); G.ghost_val = d_ghost_val.d; G.gslot_pose = d_gslot_pose.d;
@@ -3089,7 +2818,7 @@ int HostGraph::sync_self() {
 }
 
 int HostGraph::enqueue_phase(int phase, double* d_buf) {
-  pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
+  drop_stream_state();
   hipStream_t s = stream;
   const bool joint = pcg_iters > 0 && G.n_slots > 0 && !batch;      // un-batched joint solve: phases 31 / 32 / 33 follow phase 1
   if (phase == 0) {
@@ -3149,7 +2878,7 @@ int HostGraph::enqueue_phase(int phase, double* d_buf) {
 // The launch sequence of a phase (0, 1, 2; 3 / 4 = phase 1 before / after the factor + solve) is replayed as a hipGraph while the
 // resident graph and the exchange buffer stay the same (every pass of a distributed Gauss-Newton run): ~90 launches per pass otherwise
 int HostGraph::launch_phase(int phase, double* d_buf) {
-  pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
+  drop_stream_state();
   hipStream_t s = stream;
   static const bool env_graph = !(getenv("SLIDE_NO_GRAPH") && getenv("SLIDE_NO_GRAPH")[0] == '1');
   PhaseGraph& pg = phase_graph[phase];
@@ -3189,12 +2918,11 @@ static int refuse_robust(const char* who) {
   return SLIDE_ERR_INVALID;
 }
 int HostGraph::dist_phase(int phase, double* d_buf) {
-  if (rb_kind != 0) return refuse_robust("dist_phase");
-  if (ol_kind != 0) return refuse_observation_loss("dist_phase");
-  pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
+  if (RB.kind != 0) return refuse_robust("dist_phase");
+  if (OB.kind != 0) return refuse_observation_loss("dist_phase");
+  drop_stream_state();
   hipStream_t s = stream;
-  factor_valid = false;      // (the phases move linearisation points and factor into S on their own schedule)
-  wf_T = 0;                  // (and leave dp holding no streaming solve's solution)
+  drop_factor();             // (the phases move linearisation points and factor into S on their own schedule, and leave dp holding no streaming solve's solution)
   if (phase >= 0 && phase <= 2) {
     if (phase == 0) {
       int rc = merge_pending();
@@ -3251,9 +2979,9 @@ int HostGraph::dist_phase(int phase, double* d_buf) {
 // One distributed Gauss-Newton pass of a graph whose batch holds EVERY robot of the job (all on this GPU): phases 0 / 1 / 2 with
 // the two exchanges as device-side sums between the batch's buffers — stream-ordered, one host synchronisation at the end.
 int HostGraph::dist_pass_local(double* d_buf) {
-  if (rb_kind != 0) return refuse_robust("dist_pass_local");
-  if (ol_kind != 0) return refuse_observation_loss("dist_pass_local");
-  pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
+  if (RB.kind != 0) return refuse_robust("dist_pass_local");
+  if (OB.kind != 0) return refuse_observation_loss("dist_pass_local");
+  drop_stream_state();
   if (!batch) { g_last_error = "dist_pass_local: the graph is in no batch"; return SLIDE_ERR_INVALID; }
   wf_T = 0;      // (the pass moves the linearisation points: the last streaming solve's dp is no previous solution of the next)
   hipStream_t s = stream;
@@ -3348,7 +3076,7 @@ void HostGraph::stats(int64_t* o) const {
 int64_t HostGraph::rejected() const { return n_rejected; }
 // 2 x NonlinearFactorGraph::error at the CURRENT estimate: theta <- theta (+) delta, relinearise, sum r^T r
 int HostGraph::chi2(double* out4) {
-  pred_valid = false; status_clean = false; cache_pose = -1;      // (outside the streaming update: nothing it left behind can be relied on)
+  drop_stream_state();
   int rc = merge_pending();
   if (rc != SLIDE_OK) return rc;
   rc = upload_new();
@@ -3371,122 +3099,6 @@ int HostGraph::chi2(double* out4) {
   SL_HIP(hipStreamSynchronize(s));
   SL_HIP(hipGetLastError());
   factor_valid = false;
-  return SLIDE_OK;
-}
-// ---- robust loss (IRLS) on the loop-closure / relative-measurement factors ----------------------------------------------------
-int HostGraph::set_robust_loss(int kind, double param, int class_mask) {
-  if (kind < 0 || kind > 4) { g_last_error = "set_robust_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
-  if (class_mask & ~3) { g_last_error = "set_robust_loss: class_mask has bit 0 (loop closures) and bit 1 (relative measurements) only"; return SLIDE_ERR_INVALID; }
-  if (batch) { g_last_error = "set_robust_loss: the graph has joined a batch; the sharded and joint paths do not carry a robust loss"; return SLIDE_ERR_INVALID; }
-  if (!(param == param)) { g_last_error = "set_robust_loss: param is not a number"; return SLIDE_ERR_INVALID; }
-  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
-  rb_kind = kind;
-  rb_mask = kind ? class_mask : 0;
-  rb_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
-  RB.kind = rb_kind; RB.mask = rb_mask; RB.param = rb_param;
-  if (kind != 0 && !rb_arrays) { rb_arrays = true; topo_dirty = true; }      // (upload_new creates and fills the robust arrays)
-  // every sigma back to its base value; the next solve takes the weights of the new setting everywhere
-  if (restore_base_sigmas() != SLIDE_OK) return SLIDE_ERR_HIP;
-  // the resident factor and the last solution belong to the system as it was weighted: as after chi2(), the next solve relinearises
-  // and re-factors everything and keeps no block of dp
-  factor_valid = false;
-  wf_T = 0;
-  pred_valid = false; status_clean = false; cache_pose = -1;
-  if (kind == 0) prof.forget("k_robust_reweight");
-  return SLIDE_OK;
-}
-int HostGraph::restore_base_sigmas() {
-  if (up_rb > 0) SL_HIP(hipMemcpyAsync(d_bt_sigma.d, d_bt_sigma0.d, 6 * std::min(up_rb, up_bt) * sizeof(double), hipMemcpyDeviceToDevice, stream));
-  if (up_rbg > 0) SL_HIP(hipMemcpyAsync(d_gh_sigma.d, d_gh_sigma0.d, 6 * std::min(up_rbg, up_gh) * sizeof(double), hipMemcpyDeviceToDevice, stream));
-  return SLIDE_OK;
-}
-static int key_robot(uint64_t key) {
-  for (int r = 0; r < SLIDE_MAX_ROBOTS; ++r)
-    if ((HostGraph::pose_key(r, 0) >> 56) == (key >> 56)) return r;
-  return -1;
-}
-int HostGraph::get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind,
-                                   double* weight, double* s2, int* n_out) {
-  if (!lin_done) { g_last_error = "get_closure_weights: nothing was linearised yet (call solve first)"; return SLIDE_ERR_INVALID; }
-  std::vector<int> idx;
-  for (const ClosureRec& c : h_closures)
-    if ((size_t)c.bt < lin_bt) idx.push_back(c.bt);      // (a factor added after the last solve has no linearisation to report)
-  const int n = (int)idx.size();
-  *n_out = n;
-  const int m = std::min(n, std::max(cap, 0));
-  if (m == 0) return SLIDE_OK;
-  hipStream_t s = stream;
-  if (d_rb_idx.ensure(m, 0, s) != SLIDE_OK || d_rb_out.ensure(2 * (size_t)m, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-  SL_HIP(hipMemcpyAsync(d_rb_idx.d, idx.data(), m * sizeof(int), hipMemcpyHostToDevice, s));
-  RobustDev Rq = RB;
-  Rq.kind = lin_rb_kind; Rq.mask = lin_rb_mask;
-  launch_closure_weights(G, Rq, d_rb_idx.d, m, d_rb_out.d, s);
-  std::vector<double> out(2 * (size_t)m);
-  SL_HIP(hipMemcpyAsync(out.data(), d_rb_out.d, out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  SL_HIP(hipStreamSynchronize(s));
-  SL_HIP(hipGetLastError());
-  const uint64_t low = 0x00ffffffffffffffull;
-  for (int k = 0, q = 0; k < m; ++k, ++q) {
-    while (h_closures[q].bt != idx[k]) ++q;
-    const ClosureRec& c = h_closures[q];
-    if (from_robot) from_robot[k] = key_robot(c.k0);
-    if (from_idx) from_idx[k] = c.k0 & low;
-    if (to_robot) to_robot[k] = key_robot(c.k1);
-    if (to_idx) to_idx[k] = c.k1 & low;
-    if (kind) kind[k] = h_bt_kind[c.bt];
-    if (weight) weight[k] = out[2 * (size_t)k];
-    if (s2) s2[k] = out[2 * (size_t)k + 1];
-  }
-  return SLIDE_OK;
-}
-// ---- robust loss (IRLS) on the landmark observation factors, fused into their linearisation ------------------------------------
-int HostGraph::set_observation_loss(int kind, double param, int class_mask) {
-  if (kind < 0 || kind > 4) { g_last_error = "set_observation_loss: kind must be 0 (off), 1 Huber, 2 Cauchy, 3 Geman-McClure or 4 DCS"; return SLIDE_ERR_INVALID; }
-  if (class_mask & ~7) { g_last_error = "set_observation_loss: class_mask has bit 0 (bearing-range), bit 1 (cube) and bit 2 (cylinder) only"; return SLIDE_ERR_INVALID; }
-  if (batch) { g_last_error = "set_observation_loss: the graph has joined a batch; a batch carries its own observation loss (slide_chol_batch_set_observation_loss), the un-batched sharded passes carry none"; return SLIDE_ERR_INVALID; }
-  if (!(param == param)) { g_last_error = "set_observation_loss: param is not a number"; return SLIDE_ERR_INVALID; }
-  static const double kDefault[5] = {0.0, 1.345, 0.1, 1.0, 1.0};      // GTSAM's defaults of Huber, Cauchy, GemanMcClure, DCS
-  ol_kind = kind;
-  ol_mask = kind ? class_mask : 0;
-  ol_param = kind ? (param > 0.0 ? param : kDefault[kind]) : 0.0;
-  OB.kind = ol_kind; OB.mask = ol_mask; OB.param = ol_param;
-  if (kind != 0 && !ol_arrays) { ol_arrays = true; topo_dirty = true; }      // (upload_new creates the weight arrays)
-  // the resident factor, the kept records and the last solution belong to the system as it was weighted: as after chi2(), the next
-  // solve relinearises and re-factors everything and keeps no block of dp
-  factor_valid = false;
-  wf_T = 0;
-  pred_valid = false; status_clean = false; cache_pose = -1;
-  return SLIDE_OK;
-}
-int HostGraph::get_observation_weights(int cap, int32_t* robot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2,
-                                       int* n_out) {
-  if (!lin_done) { g_last_error = "get_observation_weights: nothing was linearised yet (call solve first)"; return SLIDE_ERR_INVALID; }
-  const int n = (int)std::min(lin_lf, up_lf);      // (a factor added after the last solve has no linearisation to report)
-  *n_out = n;
-  const int m = std::min(n, std::max(cap, 0));
-  if (m == 0) return SLIDE_OK;
-  hipStream_t s = stream;
-  std::vector<double> out;
-  if (weight || s2) {
-    if (d_ol_out.ensure(2 * (size_t)m, 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
-    launch_observation_weights(G, OB, lin_ol_kind != 0, m, d_ol_out.d, s);
-    out.resize(2 * (size_t)m);
-    SL_HIP(hipMemcpyAsync(out.data(), d_ol_out.d, out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    SL_HIP(hipGetLastError());
-  }
-  std::vector<uint64_t> pkey, lkey;      // ids -> keys (the graph keeps the maps the other way round)
-  if (robot || pose_idx) { pkey.assign(h_pose_val.size() / 12, 0); for (const auto& kv : key2pose) pkey[kv.second] = kv.first; }
-  if (lm_idx) { lkey.assign(h_lm_type.size(), 0); for (const auto& kv : key2lm) lkey[kv.second] = kv.first; }
-  const uint64_t low = 0x00ffffffffffffffull;
-  for (int k = 0; k < m; ++k) {
-    if (robot) robot[k] = key_robot(pkey[h_lf_pose[k]]);
-    if (pose_idx) pose_idx[k] = pkey[h_lf_pose[k]] & low;
-    if (cls) cls[k] = h_lf_type[k] == FT_CYL ? SLIDE_CLS_CYLINDER : (h_lf_type[k] == FT_CUBE ? SLIDE_CLS_CUBE : SLIDE_CLS_ELLIPSOID);
-    if (lm_idx) lm_idx[k] = lkey[h_lf_lm[k]] & low;
-    if (weight) weight[k] = out[2 * (size_t)k];
-    if (s2) s2[k] = out[2 * (size_t)k + 1];
-  }
   return SLIDE_OK;
 }
 int HostGraph::get_tile_profile(int* out, int cap) {

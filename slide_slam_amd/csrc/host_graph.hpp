@@ -26,6 +26,22 @@ void thread_capture_mode_local();      // (host_graph.hip) once per host thread:
 bool hip_ok(hipError_t e, const char* what);
 inline bool robot_ok(int r) { return r >= 0 && r < SLIDE_MAX_ROBOTS; }
 int decode_status(const int* st8);      // status words of a pass -> SLIDE_OK / SLIDE_ERR_NOT_SPD / SLIDE_ERR_RUNTIME (+ g_last_error)
+// A robust loss as its setter normalised it (host_loss.hip): kind 0 = off with mask and param 0, else GTSAM's Huber, Cauchy,
+// GemanMcClure or DCS (1 .. 4) on the factor classes of mask with param > 0.  A graph keeps its two in RB / OB, a batch in rb / ol.
+struct LossSetting {
+  int kind = 0, mask = 0;
+  double param = 0.0;
+  bool on() const { return kind != 0; }
+};
+// The one validator of the four setters.  who: the entry point's prefix of every message; mask_text: its sentence about the bits of
+// allowed_mask; refusal (null: none): the entry point's own refusal, reported after the kind and mask checks and before the
+// not-a-number check.  param <= 0 becomes the loss's default.  SLIDE_ERR_INVALID (+ g_last_error), *out untouched, or SLIDE_OK.
+int parse_loss(const char* who, int kind, double param, int class_mask, int allowed_mask, const char* mask_text, LossSetting* out,
+               const char* refusal = nullptr);
+int key_robot(uint64_t key);            // (host_loss.hip) the robot of a pose key, -1 for any other key
+// the output columns of the weight read-backs (null: not asked for); who: the robot on a graph, the slot on a batch
+struct ClosureCols { int32_t *slot, *from_robot; uint64_t* from_idx; int32_t* to_robot; uint64_t* to_idx; int32_t *kind, *ghost_id; double *weight, *s2; };
+struct ObsCols { int32_t* who; uint64_t* pose_idx; int32_t* cls; uint64_t* lm_idx; double *weight, *s2; };
 #define SL_HIP(x)                                     \
   do {                                                \
     if (!::sl::hip_ok((x), #x)) return SLIDE_ERR_HIP; \
@@ -149,6 +165,7 @@ struct PendFac {
 // all of them, and every graph's stream continues behind the batch.  All joined graphs must solve in lockstep (the distributed
 // pass does); a rendezvous that is not completed within 60 s returns SLIDE_ERR_RUNTIME.
 class HostGraph;
+constexpr int CHOL_BATCH_HOST_MAX = 8;      // graphs a batch holds at most
 // what an information-gain query reads back: the gram matrices, the rows of U at the trajectory's poses (for C = I + J U)
 struct GainFetched { std::vector<double> M, Urow; };
 // The callbacks of the quadratic-form queries (sigma_forms on one graph, joint_sigma_forms on a batch): fill queues the kernel that
@@ -177,8 +194,8 @@ class CholBatch {
   // Robust loss (iteratively reweighted least squares) on the members' loop-closure / relative-measurement between factors and on
   // the inter-robot relative-pose (ghost) factors, uniform over the batch (HostGraph::set_robust_loss's arguments and defaults):
   // k_robust_reweight_b ahead of the linearisation of every whole or cut pass.  Not with PCG passes (pcg_iters > 0).
-  int set_robust_loss(int kind, double param, int class_mask);
-  bool robust_on() const { return rb_kind != 0; }
+  int set_robust_loss(int kind, double param, int class_mask) { return set_loss(true, kind, param, class_mask); }
+  bool robust_on() const { return rb.on(); }
   // per member slot: its loop-closure / relative-measurement between factors in insertion order, then its ghost factors (kind 2;
   // the local pose in from_* when it is the factor's first key, else in to_*; the other end: robot -1, idx = its ghost slot;
   // ghost_id: slide_graph_set_ghost_ids' index, -1 for between factors and unnamed ghosts), with w and s^2 of the last pass
@@ -188,8 +205,8 @@ class CholBatch {
   // Robust loss on the members' landmark observation factors, uniform over the batch (HostGraph::set_observation_loss's arguments,
   // defaults and validation): k_lin_lf_robust_b in k_lin_lf_b's place in every whole or cut pass.  Independent of set_robust_loss.
   // Not with PCG passes (pcg_iters > 0).
-  int set_observation_loss(int kind, double param, int class_mask);
-  bool observation_loss_on() const { return ol_kind != 0; }
+  int set_observation_loss(int kind, double param, int class_mask) { return set_loss(false, kind, param, class_mask); }
+  bool observation_loss_on() const { return ol.on(); }
   // slot by slot the member's landmark factors in insertion order: its slot, the factor's pose index, its landmark (cls: SLIDE_CLS_*,
   // lm_idx: the member's local index), w and the unscaled s^2 of the last pass.  One launch, one read-back.
   int get_observation_weights(int cap, int32_t* slot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2, int* n_out);
@@ -332,8 +349,9 @@ class CholBatch {
   GraphDev* d_Gs = nullptr;              // the joined graphs' device views, for the kernels batched over blockIdx.z
   // robust loss of the batch: the members' RobustDev views beside d_Gs (their arrays, the batch's setting), compared by begin_pass
   // like the GraphDev views; what the last pass linearised under and how many factors of each member it covered (the read-back)
-  int rb_kind = 0, rb_mask = 0;
-  double rb_param = 0.0;
+  LossSetting rb;
+  int set_loss(bool closures, int kind, double param, int class_mask);      // both setters: rb (closures) or ol
+  int readback_members(const char* who, bool pass_done, size_t n_noted, std::vector<HostGraph*>& gs);
   RobustDev* d_Rs = nullptr;
   std::vector<RobustDev> hR, pass_R;
   RobustDev member_view(const HostGraph* g) const;
@@ -346,8 +364,7 @@ class CholBatch {
   // member's own OB.kind stays 0), compared by begin_pass like the other two; what the last pass linearised under and how many
   // landmark factors of each member it covered (the read-back).  No array of a member is rewritten under the loss, so nothing is
   // restored when a member leaves or the batch goes.
-  int ol_kind = 0, ol_mask = 0;
-  double ol_param = 0.0;
+  LossSetting ol;
   ObsLossDev* d_Os = nullptr;
   std::vector<ObsLossDev> hO, pass_O;
   ObsLossDev member_obs_view(const HostGraph* g) const;
@@ -357,6 +374,7 @@ class CholBatch {
   double* d_ol_out = nullptr; size_t ol_out_cap = 0;
   int capture_pass(double* const* d_bufs, int part, hipGraphExec_t* exec);
   int prepare_pass();
+  int prepare_member(HostGraph* g, bool for_pass);      // (the caller holds g->mtx)
   int begin_pass(double* const* d_bufs, bool* same);
   int end_pass();
   int enqueue_pass(double* const* d_bufs, hipEvent_t e0, hipEvent_t e1, int part);
@@ -486,7 +504,7 @@ class HostGraph {
   // Robust loss on the loop-closure / relative-measurement factors (iteratively reweighted least squares; k_robust_reweight).
   // kind 0: off; param <= 0: the loss's default; mask bit 0: loop closures, bit 1: relative measurements.  Single-graph path only.
   int set_robust_loss(int kind, double param, int class_mask);
-  bool robust_on() const { return rb_kind != 0; }
+  bool robust_on() const { return RB.kind != 0; }
   // weight and squared whitened norm of every loop-closure / relative-measurement factor at its last linearisation, insertion order
   int get_closure_weights(int cap, int32_t* from_robot, uint64_t* from_idx, int32_t* to_robot, uint64_t* to_idx, int32_t* kind, double* weight,
                           double* s2, int* n_out);
@@ -494,7 +512,7 @@ class HostGraph {
   // k_lin_lf_robust).  kind 0: off; param <= 0: the loss's default; mask bit 0: bearing-range, bit 1: cube, bit 2: cylinder factors.
   // Independent of set_robust_loss.  Single-graph path only.
   int set_observation_loss(int kind, double param, int class_mask);
-  bool observation_loss_on() const { return ol_kind != 0; }
+  bool observation_loss_on() const { return OB.kind != 0; }
   // weight and squared whitened norm of every landmark factor at its last linearisation, insertion order
   int get_observation_weights(int cap, int32_t* robot, uint64_t* pose_idx, int32_t* cls, uint64_t* lm_idx, double* weight, double* s2, int* n_out);
   void set_incremental(bool on) { inc_enabled = on; }
@@ -520,8 +538,8 @@ class HostGraph {
   std::mutex mtx;
   Profiler prof;
   GraphDev G{};
-  RobustDev RB{};                    // the robust loss's arrays and setting (null / 0 until a loss is set)
-  ObsLossDev OB{};                   // the observation loss's arrays and setting (null / 0 until one is set)
+  RobustDev RB{};                    // the robust loss's arrays and setting (null / 0 until a loss is set): kind / mask / param are the only store of it
+  ObsLossDev OB{};                   // the observation loss's arrays and setting (null / 0 until one is set), likewise
 
  private:
   int merge_pending();
@@ -566,8 +584,6 @@ class HostGraph {
   std::vector<int> h_bt_kind;
   struct ClosureRec { int bt; uint64_t k0, k1; };
   std::vector<ClosureRec> h_closures;          // the between factors with bt_kind != 0, insertion order
-  int rb_kind = 0, rb_mask = 0;
-  double rb_param = 0.0;
   bool rb_arrays = false;
   size_t up_rb = 0;                            // between factors the robust arrays hold
   bool lin_done = false;                       // a linearisation ran; it covered lin_bt between factors under the loss lin_rb_kind / lin_rb_mask
@@ -575,8 +591,6 @@ class HostGraph {
   int lin_rb_kind = 0, lin_rb_mask = 0;
   void note_linearisation() { lin_done = true; lin_bt = up_bt; lin_rb_kind = RB.kind; lin_rb_mask = RB.mask; lin_lf = up_lf; lin_ol_kind = OB.kind; }
   // observation loss.  lf_w / lf_s2 exist from the first time a loss is set on (ol_arrays) and grow with the landmark factors.
-  int ol_kind = 0, ol_mask = 0;
-  double ol_param = 0.0;
   bool ol_arrays = false;
   size_t up_ol = 0;                            // landmark factors the arrays hold
   size_t lin_lf = 0;                           // the last linearisation covered lin_lf landmark factors, under the loss lin_ol_kind
@@ -586,6 +600,13 @@ class HostGraph {
   size_t up_rbg = 0;                           // ghost factors the robust arrays hold (a batch's loss covers them)
   DevArr<double> d_gh_sigma0, d_gh_w, d_gh_s2;
   int restore_base_sigmas();                   // bt_sigma / gh_sigma <- sigma0 (a loss was set, cleared or left behind with a batch)
+  // the read-backs' rows (host_loss.hip): ids -> keys (the graph keeps the maps the other way round), one closure or ghost factor's
+  // row of the closure columns, the first `count` landmark factors' rows of the observation columns from row `at` on; ws: the
+  // (weight, s^2) pairs of all rows as the kernel left them
+  void inverse_keys(bool poses, bool lms, std::vector<uint64_t>& pkey, std::vector<uint64_t>& lkey) const;
+  void closure_row(const ClosureCols& c, size_t k, int slot, const ClosureRec& rec, const double* ws) const;
+  void ghost_row(const ClosureCols& c, size_t k, int slot, int gh, const double* ws) const;
+  void observation_rows(const ObsCols& c, size_t at, int count, int slot, const double* ws) const;      // slot < 0: who = the pose's robot
   DevArr<double> d_bt_sigma0, d_bt_w, d_bt_s2, d_rb_out;
   DevArr<int> d_bt_kind, d_rb_idx;
   std::vector<int> h_gh_pose, h_gh_slot, h_gh_first; std::vector<double> h_gh_z, h_gh_sigma;   // ghost-between factors
@@ -675,6 +696,15 @@ class HostGraph {
   DevArr<int> d_cctr;
   DevArr<double> d_covY;
   bool factor_valid = false;            // S / Ld / Winv hold the factor of the system of the last solve
+  // What a streaming update leaves for the next one besides the factor: its prediction of the next relinearisation, the zeroed status
+  // words and the cached newest pose.  They describe the device as that update left it, so whatever else writes deltas, estimates or
+  // status words (a pass of any other kind, chi2, a changed loss or batch) drops all three together.
+  void drop_stream_state() { pred_valid = false; status_clean = false; cache_pose = -1; }
+  // The resident factor and the solution kept for the bounded back-substitution are of one system: what makes the factor another
+  // system's (a changed weighting, batched or sharded passes factoring into the same S) makes dp no previous solution either.
+  // Outside a successful run_update the two are cleared together.  (Two sites clear them apart, as they always have: chi2 drops dp
+  // where it folds delta in and the factor only once it has succeeded, dist_pass_local drops dp alone.)
+  void drop_factor() { factor_valid = false; wf_T = 0; }
   unsigned long long fact_serial = 0;   // +1 whenever a solve leaves a new factorisation
   size_t fact_shape[8] = {};            // what that factorisation was of: T, ld, the uploaded counts (marginal_state compares)
   void fact_shape_now(size_t* out) const;

@@ -705,38 +705,32 @@ class PassDriver:
         self._joint_ok()
         return self.batch.closure_mahalanobis(closures)
 
-    # ---- robust loss on the exact joint pass (CholBatch.set_robust_loss, slide_gpu.h) --------------------------------------------------
+    # ---- robust loss and observation loss on the exact joint pass (CholBatch.set_robust_loss / set_observation_loss, slide_gpu.h) ------
+    def _loss_agreed(self, who, what, kind, param, *classes):
+        """What both loss setters check first: the driver carries losses at all, and the ranks of a job set the same one."""
+        if self.batch is None or not self.arrow:
+            raise ValueError(f"{who} needs a CholBatch running exact joint passes (arrow=True): the un-batched, CPU and PCG passes do not carry {what}")
+        if self.world > 1 and self.base is not None:
+            from .api import ROBUST_KINDS
+            k = ROBUST_KINDS.get(kind, kind) if (kind is None or isinstance(kind, str)) else int(kind)
+            on = k not in (0, None)      # (compared as resolved: "huber" and 1 are one loss, param <= 0 is the default, off is off)
+            mine = (k if on else 0, max(float(param), 0.0) if on else 0.0, *(bool(c) and on for c in classes))
+            seen = self.base.all_gather_object(mine)
+            if len(set(seen)) != 1:
+                raise RuntimeError(f"{who}: the ranks disagree on the loss: {sorted(set(seen))}")
+
     def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
         """The batch's robust loss for this driver's passes, whole or cut: every robot's loop closures (closures), its relative
         measurements and the job's inter-robot relative-pose factors (relative_meas).  Batched exact-joint drivers only: the
         un-batched and CPU-rehearsal passes and the PCG passes do not carry a loss.  Every rank of a job must set the same loss."""
-        if self.batch is None or not self.arrow:
-            raise ValueError("set_robust_loss needs a CholBatch running exact joint passes (arrow=True): the un-batched, CPU and PCG passes do not carry a robust loss")
-        if self.world > 1 and self.base is not None:
-            from .api import SlideGraph
-            k = SlideGraph.ROBUST_KINDS.get(kind, kind) if (kind is None or isinstance(kind, str)) else int(kind)
-            on = k not in (0, None)      # (compared as resolved: "huber" and 1 are one loss, param <= 0 is the default, off is off)
-            mine = (k if on else 0, max(float(param), 0.0) if on else 0.0, bool(closures) and on, bool(relative_meas) and on)
-            seen = self.base.all_gather_object(mine)
-            if len(set(seen)) != 1:
-                raise RuntimeError(f"set_robust_loss: the ranks disagree on the loss: {sorted(set(seen))}")
+        self._loss_agreed("set_robust_loss", "a robust loss", kind, param, closures, relative_meas)
         self.batch.set_robust_loss(kind, param, closures, relative_meas)
 
-    # ---- observation loss on the exact joint pass (CholBatch.set_observation_loss, slide_gpu.h) ---------------------------------------
     def set_observation_loss(self, kind, param=0.0, points=True, cubes=True, cylinders=True):
         """The batch's observation loss for this driver's passes, whole or cut: every robot's bearing-range (points), cube and
         cylinder factors, the observations of the shared landmarks included.  Batched exact-joint drivers only: the un-batched and
         CPU-rehearsal passes and the PCG passes do not carry a loss.  Every rank of a job must set the same loss."""
-        if self.batch is None or not self.arrow:
-            raise ValueError("set_observation_loss needs a CholBatch running exact joint passes (arrow=True): the un-batched, CPU and PCG passes do not carry an observation loss")
-        if self.world > 1 and self.base is not None:
-            from .api import SlideGraph
-            k = SlideGraph.ROBUST_KINDS.get(kind, kind) if (kind is None or isinstance(kind, str)) else int(kind)
-            on = k not in (0, None)      # (compared as resolved, as in set_robust_loss)
-            mine = (k if on else 0, max(float(param), 0.0) if on else 0.0, bool(points) and on, bool(cubes) and on, bool(cylinders) and on)
-            seen = self.base.all_gather_object(mine)
-            if len(set(seen)) != 1:
-                raise RuntimeError(f"set_observation_loss: the ranks disagree on the loss: {sorted(set(seen))}")
+        self._loss_agreed("set_observation_loss", "an observation loss", kind, param, points, cubes, cylinders)
         self.batch.set_observation_loss(kind, param, points, cubes, cylinders)
 
     def observation_weights(self):
