@@ -33,6 +33,10 @@ SOURCES = [
     ("host_marginals.hip", ["-ffp-contract=off"]),     # (its Woodbury step runs on the host: same rounding as host_graph.hip)
     ("host_loss.hip", ["-ffp-contract=off"]),          # (the robust losses' host side, split off host_graph.hip the same way)
     ("host_backend.hip", ["-ffp-contract=off"]),
+    ("host_clipper.hip", ["-ffp-contract=off"]),       # (the clique solver's host side, split off capi.hip: rounding of u against thresholds)
+    ("host_place.hip", ["-ffp-contract=off"]),         # (SlideMatch's host side: the lattice's repeated additions, pose compositions)
+    ("host_slidegraph.hip", ["-ffp-contract=off"]),    # (SlideGraph's host side: estimate_tf2d's sums and the inverse transform)
+    ("host_closure.hip", ["-ffp-contract=off"]),       # (closure selection's host side: pose compositions, sigma squares)
     ("capi.hip", ["-ffp-contract=off"]),
     ("wire.hip", ["-ffp-contract=off"]),     # host code only: sloam_msgs wire codec + rosbag reader (include/slide_wire.h)
 ]

@@ -1,6 +1,8 @@
-// extern "C" boundary (include/slide_gpu.h).  Every compute entry point drives HIP kernels; there is
-// no CPU fallback.  Host code here is limited to marshalling, the candidate lattice of SlideMatch
-// (generated by the reference's own repeated-addition loops) and O(1)-sized post-processing.
+// extern "C" boundary (include/slide_gpu.h) of the graph, the batch and the backend: thin wrappers that take the handle's lock and
+// forward to HostGraph / CholBatch / HostBackend.  Besides them: the stand-alone dense solve and bordered-factorisation hooks,
+// stand-alone association, and five small pure-host functions of the reference's bookkeeping.  The matchers live in files of their
+// own: host_place.hip (SlideMatch), host_clipper.hip (CLIPPER), host_slidegraph.hip (SlideGraph), host_closure.hip (closure selection).
+// Every compute entry point drives HIP kernels; there is no CPU fallback.
 #include <unistd.h>
 #include <algorithm>
 #include <cmath>
@@ -9,15 +11,13 @@
 #include <utility>
 #include <vector>
 
+#include "capi_handles.hpp"
 #include "delaunay.hpp"
 #include "host_backend.hpp"
+#include "host_clipper.hpp"
 
 using namespace sl;
 
-struct slide_graph {
-  HostGraph g;
-  explicit slide_graph(const slide_params_t& p) : g(p) {}
-};
 struct slide_backend {
   HostBackend b;
   slide_graph_t* gview = nullptr;
@@ -26,18 +26,23 @@ struct slide_backend {
 
 static thread_local std::string t_err;
 
-struct Tmp {
-  std::vector<void*> ptrs;
-  ~Tmp() { for (void* p : ptrs) (void)hipFree(p); }
-  template <class T>
-  T* up(const T* h, size_t n) {
-    T* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(d);
-    if (n && h && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
+// The gate of CylinderMapManager::getLoopCandidateIdx (cylinderMapManager.cpp:160-184), ONE text for the two functions below:
+// visit(d2, i) for every key pose i inside the radius that is old enough, in index order; d2 = its float32 squared distance.
+template <class Visit>
+static void loop_candidates(const float* cloud_xyz, int n, double max_dist, uint64_t pose_idx, uint64_t at_least_num_of_poses_old, Visit visit) {
+  const float qx = cloud_xyz[3 * pose_idx], qy = cloud_xyz[3 * pose_idx + 1], qz = cloud_xyz[3 * pose_idx + 2];
+  const float r2 = (float)(max_dist * max_dist);                 // pcl radiusSearch hands radius^2 to FLANN as float
+  for (int i = 0; i < n; ++i) {
+    const float dx = cloud_xyz[3 * i] - qx, dy = cloud_xyz[3 * i + 1] - qy, dz = cloud_xyz[3 * i + 2] - qz;
+    float d2 = dx * dx;
+    d2 += dy * dy;
+    d2 += dz * dz;
+    if (!(d2 < r2)) continue;
+    // "nnIdx != poseIdx && poseIdx - nnIdx > at_least_num_of_poses_old" with poseIdx a size_t: a LATER pose wraps around and passes
+    if ((uint64_t)i == pose_idx || !(pose_idx - (uint64_t)i > at_least_num_of_poses_old)) continue;
+    visit(d2, (uint64_t)i);
   }
-};
+}
 
 extern "C" {
 
@@ -98,8 +103,6 @@ slide_graph_t* slide_graph_create(const slide_params_t* p) {
   return g;
 }
 void slide_graph_destroy(slide_graph_t* g) { delete g; }
-
-#define LOCK(G) std::lock_guard<std::mutex> lk((G)->g.mtx)
 
 int slide_graph_set_prior(slide_graph_t* g, int robot, const double pose7[7]) { if (!g) return SLIDE_ERR_INVALID; LOCK(g); return g->g.set_prior(robot, pose7); }
 int slide_graph_add_keypose_between(slide_graph_t* g, int robot, uint64_t from_idx, uint64_t to_idx, const double rel7[7],
@@ -249,7 +252,6 @@ int slide_graph_dist_phase(slide_graph_t* g, int phase, double* d_buf) {
   return g->g.dist_phase(phase, d_buf);
 }
 
-struct slide_chol_batch { sl::CholBatch b; explicit slide_chol_batch(int n) : b(n) {} };
 slide_chol_batch_t* slide_chol_batch_create(int n_graphs) {
   if (n_graphs < 1 || n_graphs > 8) return nullptr;
   return new slide_chol_batch(n_graphs);
@@ -818,1489 +820,8 @@ int slide_backend_landmark_table(slide_backend_t* b, int cls, double* xyz, int32
   return n;
 }
 
-// graph access of a backend: thin views that forward to the backend's own graph (no second graph object)
-struct slide_graph_view;
-}  // extern "C"
-
-// The backend owns its HostGraph by value; the C-ABI graph functions take slide_graph*, whose only member is
-// a HostGraph at offset 0, so a pointer to the backend's graph is a valid slide_graph*.
-static_assert(offsetof(slide_graph, g) == 0, "slide_graph must start with its HostGraph");
-
-extern "C" {
+// graph access of a backend: thin views that forward to the backend's own graph (no second graph object; capi_handles.hpp)
 slide_graph_t* slide_backend_graph(slide_backend_t* b) { return b ? reinterpret_cast<slide_graph_t*>(&b->b.g) : nullptr; }
-
-// ---- SlideMatch ----------------------------------------------------------------------------------------
-void slide_place_default_params(slide_place_params_t* p) {
-  p->dilation_factor = 1.2; p->search_xy_step_size = 0.5; p->match_yaw_half_range = 180. * M_PI / 180.;
-  p->search_yaw_step_size = 2.0 * M_PI / 180.; p->match_threshold_position = 0.5; p->match_threshold_dimension = 1.0;
-  p->disable_yaw_search = 0; p->ignore_dimension = 0; p->min_num_inliers = 5; p->use_nonlinear_least_squares = 1;
-  p->min_num_map_objects_to_start = 1; p->max_rings = -1;
-}
-
-}  // extern "C"
-// Measurement aid (slide_last_device_ms): device time of the kernels of the LAST stand-alone SlideMatch / SlideGraph / CLIPPER call of
-// this process, HIP events on the stream those entry points launch on (the legacy stream) right around the launches — uploads, host
-// prefix sums and read-backs excluded.  Slots: include/slide_gpu.h.
-static double g_dev_ms[SLIDE_MS_COUNT];
-namespace {
-struct DevTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  int slot;
-  bool add;
-  explicit DevTimer(int slot_, bool add_ = false) : slot(slot_), add(add_) {
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
-    (void)hipEventRecord(a, nullptr);
-  }
-  ~DevTimer() {
-    if (!a || !b) return;
-    float ms = 0.f;
-    if (hipEventRecord(b, nullptr) == hipSuccess && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess)
-      g_dev_ms[slot] = (add ? g_dev_ms[slot] : 0.0) + (double)ms;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-  }
-};
-}  // namespace
-extern "C" {
-// Optional read-back of the whole sweep (slide_match_maps_sweep): what the kernels wrote for every candidate, not only the winner.
-struct SweepOut {
-  double* xyyaw;          // 3 per candidate
-  int32_t* inliers;       // 1 per candidate
-  int64_t capacity;       // candidates the two buffers hold
-  int64_t* n_candidates;  // filled as soon as the lattice is known
-  int64_t* best_index;    // the candidate the device arg-max chose, -1 when nothing was launched
-};
-// The candidate lattice exactly as the nested loops of place_recognition.cpp:136-241 generate it, by the reference's own repeated
-// additions: ONE text for the single call (match_maps_ranges) and the list form (find_inter_loop_closures), so every lattice value is
-// the same double in both.  Candidates in loop order: ring, x, y, then yaw.
-struct PlaceLattice {
-  std::vector<double> yaws, xs, ys;
-  std::vector<int32_t> cx, cy;      // per cell: indices into xs / ys
-  long long ncell() const { return (long long)cx.size(); }
-  int ny() const { return (int)yaws.size(); }
-  long long ncand() const { return ncell() * ny(); }
-  std::vector<double> yaw_table() const {      // [yaw | cos | sin], the layout launch_place_sweep reads
-    const int n = ny();
-    std::vector<double> t(3 * (size_t)n);
-    for (int i = 0; i < n; ++i) { t[i] = yaws[i]; t[n + i] = std::cos(yaws[i]); t[2 * n + i] = std::sin(yaws[i]); }
-    return t;
-  }
-};
-static void place_lattice(double x_half, double y_half, const slide_place_params_t& P, PlaceLattice& L) {
-  if (P.disable_yaw_search) L.yaws.push_back(0.0);
-  else for (double y = -P.match_yaw_half_range; y < P.match_yaw_half_range; y += P.search_yaw_step_size) L.yaws.push_back(y);
-  const double outer = 10 * P.search_xy_step_size;
-  const int steps = (int)std::ceil(std::min(x_half, y_half) / outer);
-  if (steps <= 0) return;
-  const double sx = x_half / (double)steps, sy = y_half / (double)steps;
-  if (sx < P.search_xy_step_size || sy < P.search_xy_step_size) return;
-  const int nrings = P.max_rings >= 0 ? std::min(P.max_rings, steps) : steps;
-  for (int cur = 0; cur < nrings; ++cur) {
-    const double cs = (double)cur;
-    const double x_pe = (cs + 1) * sx, x_ns = -(cs + 1) * sx, x_lb = -cs * sx, x_rb = cs * sx;
-    const double y_pe = (cs + 1) * sy, y_ns = -(cs + 1) * sy, y_lb = -cs * sy, y_rb = cs * sy;
-    const int xo = (int)L.xs.size(), yo = (int)L.ys.size();
-    for (double x = x_ns; x <= x_pe; x += P.search_xy_step_size) L.xs.push_back(x);
-    for (double y = y_ns; y <= y_pe; y += P.search_xy_step_size) L.ys.push_back(y);
-    for (int ix = xo; ix < (int)L.xs.size(); ++ix)
-      for (int iy = yo; iy < (int)L.ys.size(); ++iy) {
-        const double x = L.xs[ix], y = L.ys[iy];
-        if ((x >= x_lb && x <= x_rb) && (y >= y_lb && y <= y_rb)) continue;
-        L.cx.push_back(ix);
-        L.cy.push_back(iy);
-      }
-  }
-}
-// Both maps bucketed by label, stably (k_place_sweep_b): bucket b = the b-th distinct label in the reference's order.  The reference
-// side depends on the reference map alone (the list form buckets a map once however many pairs name it), the query side on both.
-struct PlaceRefBuckets {
-  std::vector<double> labels;
-  std::vector<int> start;            // bucket b = [start[b], start[b + 1])
-  std::vector<double> rxy, rdim;     // 2 / 3 per object, bucket after bucket
-};
-struct PlaceQryBuckets {
-  std::vector<double> qxy, qdim;     // 2 / 3 per object, ordered by the bucket of their label
-  std::vector<int32_t> qrange;       // 2 per object: the reference bucket it scans
-  double tests = 0.0;                // distance tests per candidate: the sum of the ranges
-};
-static void place_bucket_ref(const double* ref7, int nr, PlaceRefBuckets& B) {
-  std::vector<int> rb(nr);
-  for (int k = 0; k < nr; ++k) {
-    const double l = ref7[7 * (size_t)k];
-    int b = -1;
-    for (size_t t = 0; t < B.labels.size(); ++t) if (B.labels[t] == l) { b = (int)t; break; }
-    if (b < 0 && l == l) { b = (int)B.labels.size(); B.labels.push_back(l); }      // (a NaN label equals nothing: such an object is never scanned)
-    rb[k] = b;
-  }
-  const int NBK = (int)B.labels.size();
-  B.start.assign(NBK + 1, 0);
-  for (int k = 0; k < nr; ++k) if (rb[k] >= 0) ++B.start[rb[k] + 1];
-  for (int b = 0; b < NBK; ++b) B.start[b + 1] += B.start[b];
-  B.rxy.assign(2 * (size_t)std::max(nr, 1), 0.0); B.rdim.assign(3 * (size_t)std::max(nr, 1), 0.0);
-  std::vector<int> fill(B.start.begin(), B.start.end() - 1);
-  for (int k = 0; k < nr; ++k) {
-    if (rb[k] < 0) continue;
-    const int p = fill[rb[k]]++;
-    const double* m = ref7 + 7 * (size_t)k;
-    B.rxy[2 * (size_t)p] = m[1]; B.rxy[2 * (size_t)p + 1] = m[2];
-    B.rdim[3 * (size_t)p] = m[4]; B.rdim[3 * (size_t)p + 1] = m[5]; B.rdim[3 * (size_t)p + 2] = m[6];
-  }
-}
-static void place_bucket_qry(const PlaceRefBuckets& B, const double* qry7, int nq, PlaceQryBuckets& Q) {
-  const int NBK = (int)B.labels.size();
-  std::vector<int> qb(nq), qorder(nq);
-  for (int j = 0; j < nq; ++j) {
-    const double l = qry7[7 * (size_t)j];
-    int b = NBK;                                             // (no reference object carries this label: an empty range, sorted last)
-    for (int t = 0; t < NBK; ++t) if (B.labels[t] == l) { b = t; break; }
-    qb[j] = b; qorder[j] = j;
-  }
-  std::stable_sort(qorder.begin(), qorder.end(), [&](int a, int b) { return qb[a] < qb[b]; });
-  Q.qxy.resize(2 * (size_t)nq); Q.qdim.resize(3 * (size_t)nq); Q.qrange.resize(2 * (size_t)nq);
-  Q.tests = 0.0;
-  for (int p = 0; p < nq; ++p) {
-    const int j = qorder[p];
-    const double* q = qry7 + 7 * (size_t)j;
-    Q.qxy[2 * (size_t)p] = q[1]; Q.qxy[2 * (size_t)p + 1] = q[2];
-    Q.qdim[3 * (size_t)p] = q[4]; Q.qdim[3 * (size_t)p + 1] = q[5]; Q.qdim[3 * (size_t)p + 2] = q[6];
-    Q.qrange[2 * (size_t)p] = qb[j] < NBK ? B.start[qb[j]] : 0;
-    Q.qrange[2 * (size_t)p + 1] = qb[j] < NBK ? B.start[qb[j] + 1] : 0;
-    Q.tests += (double)(Q.qrange[2 * (size_t)p + 1] - Q.qrange[2 * (size_t)p]);
-  }
-}
-// sqrt(v) < t  <=>  v < v_crit, v_crit = the smallest double whose correctly rounded square root is >= t
-static double place_v_crit(double t) {
-  double vc = 0.0;
-  if (t > 0.0 && t == t) {
-    vc = t * t;
-    while (vc > 0.0 && std::sqrt(vc) >= t) vc = std::nextafter(vc, -INFINITY);
-    while (std::sqrt(vc) < t) vc = std::nextafter(vc, INFINITY);
-  }
-  return vc;
-}
-// on-chip capacity of the bucketed kernels: their LDS image (place_lds_bytes), 150 KiB of the CU's 160 KiB at the most
-static bool place_image_fits(int nr, int nq, int ignore_dim) { return place_lds_bytes(nr, nq, ignore_dim) <= 150 * 1024; }
-
-static int match_maps_ranges(const double* ref7, int nr, const double* qry7, int nq, double x_half, double y_half,
-                             const slide_place_params_t& P, double best[3], int* best_inl, int64_t* n_cand,
-                             const SweepOut* sweep = nullptr) {
-  *best_inl = -10000;
-  best[0] = best[1] = best[2] = 0;
-  if (n_cand) *n_cand = 0;
-  if (sweep) { *sweep->n_candidates = 0; *sweep->best_index = -1; }
-  PlaceLattice L;
-  place_lattice(x_half, y_half, P, L);
-  const std::vector<double>&xs = L.xs, &ys = L.ys, &yaws = L.yaws;
-  const std::vector<int32_t>&cx = L.cx, &cy = L.cy;
-  const long long ncell = L.ncell();
-  const int ny = L.ny();
-  if (ncell == 0 || ny == 0 || nq == 0) return SLIDE_OK;
-  if (sweep) {
-    *sweep->n_candidates = ncell * ny;
-    if (ncell * ny > sweep->capacity) { g_last_error = "sweep read-back: the candidate buffers are too small"; return SLIDE_ERR_CAPACITY; }
-  }
-  const std::vector<double> ytab = L.yaw_table();
-  Tmp T;
-  PlaceDev D;
-  D.ref7 = T.up(ref7, 7 * (size_t)nr); D.nr = nr;
-  D.qry7 = T.up(qry7, 7 * (size_t)nq); D.nq = nq;
-  D.xs = T.up(xs.data(), xs.size()); D.ys = T.up(ys.data(), ys.size()); D.yaws = T.up(ytab.data(), ytab.size());
-  D.cell_x = T.up(cx.data(), cx.size()); D.cell_y = T.up(cy.data(), cy.size());
-  D.n_cells = ncell; D.n_yaw = ny;
-  D.thr_pos = P.match_threshold_position; D.thr_dim = P.match_threshold_dimension; D.ignore_dim = P.ignore_dimension;
-  D.inliers = T.up<int32_t>(nullptr, (size_t)ncell * ny);
-  D.rxy = D.rdim = D.qxy = D.qdim = nullptr; D.qrange = nullptr; D.v_crit = 0.0;
-  static const bool plain_sweep = getenv("SLIDE_PLACE_PLAIN") && getenv("SLIDE_PLACE_PLAIN")[0] == '1';      // (comparison: round 1-4's kernel)
-  PlaceRefBuckets RB;
-  PlaceQryBuckets QB;
-  if (!plain_sweep) {
-    place_bucket_ref(ref7, nr, RB);
-    place_bucket_qry(RB, qry7, nq, QB);
-    D.v_crit = place_v_crit(P.match_threshold_position);
-    D.rxy = T.up(RB.rxy.data(), RB.rxy.size()); D.rdim = T.up(RB.rdim.data(), RB.rdim.size());
-    D.qxy = T.up(QB.qxy.data(), QB.qxy.size()); D.qdim = T.up(QB.qdim.data(), QB.qdim.size());
-    D.qrange = T.up(QB.qrange.data(), QB.qrange.size());
-    if (!D.rxy || !D.rdim || !D.qxy || !D.qdim || !D.qrange) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  }
-  long long* d_bi = T.up<long long>(nullptr, 256);
-  int32_t* d_bv = T.up<int32_t>(nullptr, 256);
-  if (!D.ref7 || !D.qry7 || !D.xs || !D.ys || !D.yaws || !D.cell_x || !D.cell_y || !D.inliers || !d_bi || !d_bv) {
-    g_last_error = "hipMalloc/hipMemcpy failed";
-    return SLIDE_ERR_HIP;
-  }
-  // on-chip capacity: each kernel keeps its own LDS image (launch_place_sweep), 150 KiB of the CU's 160 KiB at the most
-  if (!D.rxy && (size_t)nr * 6 * sizeof(double) > 150 * 1024) { g_last_error = "reference map exceeds the sweep's LDS image (plain kernel: 48 B per object, 150 KiB)"; return SLIDE_ERR_CAPACITY; }
-  if (D.rxy && !place_image_fits(nr, nq, P.ignore_dimension)) { g_last_error = "the two maps exceed the sweep's LDS image (150 KiB)"; return SLIDE_ERR_CAPACITY; }
-  {
-    DevTimer tm(SLIDE_MS_PLACE_SWEEP);
-    launch_place_sweep(D, nullptr);
-    launch_place_argmax(D.inliers, ncell * ny, d_bi, d_bv, nullptr);
-  }
-  g_dev_ms[SLIDE_MS_PLACE_PAIR_TESTS] = (double)ncell * (double)ny * (double)nq * (double)nr;
-  g_dev_ms[SLIDE_MS_PLACE_DIST_TESTS] = (double)ncell * (double)ny * (D.rxy ? QB.tests : (double)nq * (double)nr);
-  long long bi[256];
-  int32_t bv[256];
-  SL_HIP(hipMemcpy(bi, d_bi, sizeof(bi), hipMemcpyDeviceToHost));
-  SL_HIP(hipMemcpy(bv, d_bv, sizeof(bv), hipMemcpyDeviceToHost));
-  SL_HIP(hipGetLastError());
-  long long best_i = -1;
-  int best_v = INT32_MIN;
-  for (int k = 0; k < 256; ++k)
-    if (bi[k] >= 0 && (bv[k] > best_v || (bv[k] == best_v && bi[k] < best_i))) { best_v = bv[k]; best_i = bi[k]; }
-  if (sweep) {
-    SL_HIP(hipMemcpy(sweep->inliers, D.inliers, (size_t)ncell * ny * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (long long c = 0; c < ncell; ++c)
-      for (int i = 0; i < ny; ++i) {
-        double* o = sweep->xyyaw + 3 * (size_t)(c * ny + i);
-        o[0] = xs[cx[c]]; o[1] = ys[cy[c]]; o[2] = yaws[i];
-      }
-    *sweep->best_index = best_i;
-  }
-  if (best_i < 0) return SLIDE_OK;
-  const long long cell = best_i / ny;
-  best[0] = xs[cx[cell]]; best[1] = ys[cy[cell]]; best[2] = yaws[best_i % ny];
-  *best_inl = best_v;
-  if (n_cand) *n_cand = ncell * ny;
-  return SLIDE_OK;
-}
-
-// matched pairs of ONE transform (place_recognition.cpp:281-357), host side: nq * nr pair tests once
-static void pairs_of(const double* ref7, int nr, const double* qry7, int nq, const double best[3], const slide_place_params_t& P,
-                     std::vector<int>& ri, std::vector<int>& qi) {
-  const double c = std::cos(best[2]), s = std::sin(best[2]);
-  for (int j = 0; j < nq; ++j) {
-    const double* q = qry7 + 7 * (size_t)j;
-    double tx = c * q[1] + (-s) * q[2] + best[0] * 1.0;
-    double ty = s * q[1] + c * q[2] + best[1] * 1.0;
-    const double tw = 0.0 * q[1] + 0.0 * q[2] + 1.0 * 1.0;
-    tx = tx / tw; ty = ty / tw;
-    for (int k = 0; k < nr; ++k) {
-      const double* m = ref7 + 7 * (size_t)k;
-      if (m[0] != q[0]) continue;
-      const double xd = m[1] - tx, yd = m[2] - ty;
-      double avg = 0;
-      if (m[5] == 0 && m[6] == 0) avg = std::fabs(m[4] - q[4]);
-      else { avg += std::fabs(m[4] - q[4]); avg += std::fabs(m[5] - q[5]); avg += std::fabs(m[6] - q[6]); avg /= 3; }
-      const bool dist_ok = std::sqrt(xd * xd + yd * yd) < P.match_threshold_position;
-      const bool dim_ok = P.ignore_dimension ? true : (avg < P.match_threshold_dimension);
-      if (dist_ok && dim_ok) { ri.push_back(k); qi.push_back(j); break; }
-    }
-  }
-}
-
-static void half_ranges(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t& P, double* xh, double* yh) {
-  double mx = 0, my = 0;
-  for (int i = 0; i < nr; ++i) { mx = std::max(mx, std::fabs(ref7[7 * i + 1])); my = std::max(my, std::fabs(ref7[7 * i + 2])); }
-  for (int i = 0; i < nq; ++i) { mx = std::max(mx, std::fabs(qry7[7 * i + 1])); my = std::max(my, std::fabs(qry7[7 * i + 2])); }
-  if (!P.disable_yaw_search) mx = my = std::max(mx, my);
-  *xh = mx * P.dilation_factor;
-  *yh = my * P.dilation_factor;
-}
-
-int slide_match_maps(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t* p, double best_xyyaw[3],
-                     int32_t* pair_ref_idx, int32_t* pair_qry_idx, int64_t* n_candidates) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  slide_place_params_t P;
-  if (p) P = *p; else slide_place_default_params(&P);
-  double xh, yh;
-  half_ranges(ref7, nr, qry7, nq, P, &xh, &yh);
-  int inl;
-  const int rc = match_maps_ranges(ref7, nr, qry7, nq, xh, yh, P, best_xyyaw, &inl, n_candidates);
-  if (rc != SLIDE_OK) return rc;
-  if (inl > -10000 && pair_ref_idx && pair_qry_idx) {
-    std::vector<int> ri, qi;
-    pairs_of(ref7, nr, qry7, nq, best_xyyaw, P, ri, qi);
-    for (size_t i = 0; i < ri.size(); ++i) { pair_ref_idx[i] = ri[i]; pair_qry_idx[i] = qi[i]; }
-  }
-  return inl;
-}
-
-int slide_match_maps_sweep(const double* ref7, int nr, const double* qry7, int nq, const slide_place_params_t* p, double* cand_xyyaw,
-                           int32_t* cand_inliers, int64_t capacity, int64_t* n_candidates, int64_t* best_index) {
-  if (!cand_xyyaw || !cand_inliers || !n_candidates || !best_index || capacity < 0) return SLIDE_ERR_INVALID;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  slide_place_params_t P;
-  if (p) P = *p; else slide_place_default_params(&P);
-  double xh, yh;
-  half_ranges(ref7, nr, qry7, nq, P, &xh, &yh);
-  const SweepOut out{cand_xyyaw, cand_inliers, capacity, n_candidates, best_index};
-  double best[3];
-  int inl;
-  return match_maps_ranges(ref7, nr, qry7, nq, xh, yh, P, best, &inl, nullptr, &out);
-}
-
-// Horn's closed-form absolute orientation (unit quaternion = dominant eigenvector of a 4x4 symmetric
-// matrix, Jacobi sweeps): the proper rotation maximising the correlation — what solveLSQ's SVD +
-// reflection fix (place_recognition.cpp:670-686) yields.
-static void horn_rotation(const double H[9] /* sum src * tgt^T */, double R[9]) {
-  const double Sxx = H[0], Sxy = H[1], Sxz = H[2], Syx = H[3], Syy = H[4], Syz = H[5], Szx = H[6], Szy = H[7], Szz = H[8];
-  double N[16] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
-                  Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
-                  Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy,
-                  Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz};
-  double V[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0;
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) off += N[4 * p + q] * N[4 * p + q];
-    if (off < 1e-300) break;
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) {
-        if (std::fabs(N[4 * p + q]) < 1e-300) continue;
-        const double th = (N[4 * q + q] - N[4 * p + p]) / (2.0 * N[4 * p + q]);
-        const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {
-          const double a = N[4 * k + p], b = N[4 * k + q];
-          N[4 * k + p] = c * a - s * b; N[4 * k + q] = s * a + c * b;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double a = N[4 * p + k], b = N[4 * q + k];
-          N[4 * p + k] = c * a - s * b; N[4 * q + k] = s * a + c * b;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double a = V[4 * k + p], b = V[4 * k + q];
-          V[4 * k + p] = c * a - s * b; V[4 * k + q] = s * a + c * b;
-        }
-      }
-  }
-  int best = 0;
-  for (int i = 1; i < 4; ++i) if (N[5 * i] > N[5 * best]) best = i;
-  const double w = V[best], x = V[4 + best], y = V[8 + best], z = V[12 + best];
-  const double q[4] = {x, y, z, w};
-  const M3 Rm = quat_to_R(q);
-  for (int i = 0; i < 9; ++i) R[i] = Rm.a[i];
-}
-
-// What findTransformation does with the sweep's winner (place_recognition.cpp:818-945): the inlier gate, then either the lattice point
-// with the centroid shift reverted or the closed-form refinement over the matched pairs.  ref / qry: the maps the sweep saw (centred
-// for inter), cr / cq: their centroids (zero for intra).  ONE text for the single calls and the list form.  Returns 1 found / 0 not.
-static int finish_transformation(const double* ref, int nr, const double* qry, int nq, const double cr[2], const double cq[2],
-                                 const slide_place_params_t& P, const double best[3], int inl, double xyzyaw[4]) {
-  if (inl < P.min_num_inliers) return 0;
-  if (!P.use_nonlinear_least_squares) {
-    const double c = std::cos(best[2]), s = std::sin(best[2]);   // revertCentroidShift :947-967 (the centroids are zero for intra)
-    xyzyaw[0] = cr[0] + best[0] + (c * (-cq[0]) - s * (-cq[1]));
-    xyzyaw[1] = cr[1] + best[1] + (s * (-cq[0]) + c * (-cq[1]));
-    xyzyaw[2] = 0.0;
-    xyzyaw[3] = std::atan2(s, c);
-  } else {
-    std::vector<int> ri, qi;
-    pairs_of(ref, nr, qry, nq, best, P, ri, qi);
-    const int n = (int)ri.size();
-    double cs[3] = {0, 0, 0}, ct[3] = {0, 0, 0};
-    std::vector<double> src(3 * (size_t)n), tgt(3 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-      const double* m = &ref[7 * (size_t)ri[i]];
-      const double* q = &qry[7 * (size_t)qi[i]];
-      tgt[3 * i] = m[1] + cr[0]; tgt[3 * i + 1] = m[2] + cr[1]; tgt[3 * i + 2] = m[3];
-      src[3 * i] = q[1] + cq[0]; src[3 * i + 1] = q[2] + cq[1]; src[3 * i + 2] = q[3];
-      for (int k = 0; k < 3; ++k) { cs[k] += src[3 * i + k]; ct[k] += tgt[3 * i + k]; }
-    }
-    for (int k = 0; k < 3; ++k) { cs[k] /= n; ct[k] /= n; }
-    double H[9] = {0};
-    for (int i = 0; i < n; ++i)
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) H[3 * a + b] += (src[3 * i + a] - cs[a]) * (tgt[3 * i + b] - ct[b]);
-    double R[9];
-    horn_rotation(H, R);
-    for (int a = 0; a < 3; ++a) xyzyaw[a] = ct[a] - (R[3 * a] * cs[0] + R[3 * a + 1] * cs[1] + R[3 * a + 2] * cs[2]);
-    xyzyaw[3] = std::atan2(R[3], R[0]);   // getxyzYawfromTF :697-711
-  }
-  return 1;
-}
-
-
-// PlaceRecognition::findTransformation place_recognition.cpp:736-945.  inter: centre both maps on their XY centroids, search ranges
-// from the map extents (:745-800); intra (inter_loop_closure == false, :801-816): maps as they are, the three intra half ranges.
-// Returns 1 found / 0 not found / negative error; xyzyaw = getxyzYawfromTF of the result.
-static int find_transformation(const double* ref7_in, int nr, const double* qry7_in, int nq, slide_place_params_t P, bool inter,
-                               double x_half_intra, double y_half_intra, double yaw_half_intra, int* inliers, double xyzyaw[4]) {
-  std::vector<double> ref(ref7_in, ref7_in + 7 * (size_t)nr), qry(qry7_in, qry7_in + 7 * (size_t)nq);
-  double cr[2] = {0, 0}, cq[2] = {0, 0};
-  double xh, yh;
-  if (inter) {
-    for (int i = 0; i < nr; ++i) { cr[0] += ref[7 * i + 1]; cr[1] += ref[7 * i + 2]; }
-    for (int i = 0; i < nq; ++i) { cq[0] += qry[7 * i + 1]; cq[1] += qry[7 * i + 2]; }
-    cr[0] /= nr; cr[1] /= nr; cq[0] /= nq; cq[1] /= nq;
-    for (int i = 0; i < nr; ++i) { ref[7 * i + 1] -= cr[0]; ref[7 * i + 2] -= cr[1]; }
-    for (int i = 0; i < nq; ++i) { qry[7 * i + 1] -= cq[0]; qry[7 * i + 2] -= cq[1]; }
-    half_ranges(ref.data(), nr, qry.data(), nq, P, &xh, &yh);
-  } else {
-    xh = x_half_intra; yh = y_half_intra;
-    P.match_yaw_half_range = yaw_half_intra;
-  }
-  double best[3];
-  int inl;
-  const int rc = match_maps_ranges(ref.data(), nr, qry.data(), nq, xh, yh, P, best, &inl, nullptr);
-  if (rc != SLIDE_OK) return rc;
-  if (inliers) *inliers = inl;
-  return finish_transformation(ref.data(), nr, qry.data(), nq, cr, cq, P, best, inl, xyzyaw);
-}
-
-static void inter_tf16(const double xyzyaw[4], double tf16[16]) {      // findInterLoopClosure :528-535
-  for (int i = 0; i < 16; ++i) tf16[i] = 0;
-  tf16[0] = std::cos(xyzyaw[3]); tf16[1] = -std::sin(xyzyaw[3]);
-  tf16[4] = std::sin(xyzyaw[3]); tf16[5] = std::cos(xyzyaw[3]);
-  tf16[10] = 1; tf16[15] = 1;
-  tf16[3] = xyzyaw[0]; tf16[7] = xyzyaw[1]; tf16[11] = xyzyaw[2];
-}
-int slide_find_inter_loop_closure(const double* ref7_in, int nr, const double* qry7_in, int nq, const slide_place_params_t* p,
-                                  double tf16[16], int* inliers, double xyzyaw_out[4]) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  slide_place_params_t P;
-  if (p) P = *p; else slide_place_default_params(&P);
-  if (inliers) *inliers = 0;
-  if (nr < P.min_num_map_objects_to_start || nq < P.min_num_map_objects_to_start || nr == 0 || nq == 0) return 0;
-  double xyzyaw[4];
-  const int rc = find_transformation(ref7_in, nr, qry7_in, nq, P, true, 0, 0, 0, inliers, xyzyaw);
-  if (rc != 1) return rc;
-  inter_tf16(xyzyaw, tf16);
-  if (xyzyaw_out) for (int i = 0; i < 4; ++i) xyzyaw_out[i] = xyzyaw[i];
-  return 1;
-}
-
-}  // extern "C"
-// ---- PlaceRecognition::findInterLoopClosure place_recognition.cpp:498-538 for a list of map pairs (sloamNode.cpp:600-694) -------------
-namespace {
-struct PlaceMap {                      // one map of the list: centred ONCE (row-order sums, as find_transformation does), bucketed ONCE as a reference
-  const double* rows7 = nullptr;
-  int n = 0;
-  bool centred = false, bucketed = false;
-  double c[2] = {0, 0};
-  std::vector<double> rows;            // the centred copy
-  const double* data() const { return centred ? rows.data() : rows7; }      // the map as the sweep sees it
-  PlaceRefBuckets B;
-  size_t at_rxy = 0, at_rdim = 0;      // its bucketed tables in the arena (0: not there yet)
-};
-struct PlacePair {                     // a live pair: one that reaches the device
-  int k;                               // position in the core's job list
-  int lat;                             // its lattice among the call's distinct lattices
-  PlaceQryBuckets Q;
-  double weight;                       // candidates x distance tests per candidate
-};
-// the host image of the ONE device buffer of a call: tables appended at 16-byte boundaries
-struct PlaceArena {
-  std::vector<unsigned char> h;
-  size_t reserve(size_t bytes) {
-    const size_t at = (h.size() + 15) & ~(size_t)15;
-    h.resize(at + bytes);
-    return at;
-  }
-  template <class T>
-  size_t put(const T* v, size_t n) {
-    const size_t at = reserve(std::max<size_t>(n, 1) * sizeof(T));
-    if (n) std::memcpy(h.data() + at, v, n * sizeof(T));
-    return at;
-  }
-};
-constexpr int PLACE_LIST_WGS = 256 * 8;      // launch_place_sweep's grid for one pair: the list's total
-struct PlaceJob { int k; PlaceMap* R; PlaceMap* Q; double xh, yh; };      // a pair past its caller's gates: position in the caller's list, prepared maps, half ranges
-}  // namespace
-
-// The shared core of the list forms (slide_find_inter_loop_closures, slide_find_intra_loop_closures).  jobs: the pairs that passed
-// their caller's gates, each with its two PREPARED maps (PlaceMap::data(): centred for inter, as they are for intra) and its half
-// ranges; P carries the yaw half range of the call.  Outputs are initialised by the caller.  Host: lattice (place_lattice, one per
-// distinct pair of half ranges), bucketing (place_bucket_ref once per distinct reference map, place_bucket_qry per pair), the workgroup
-// shares.  Device: ONE allocation, ONE upload (every table of every live pair, the PlaceDev and workgroup tables), k_place_sweep_seg +
-// k_place_best_seg, ONE read-back (a winner per live pair) — whatever the number of jobs is.  Then finish(job, best, inl) per live pair
-// on the host: the caller's own end of findTransformation (finish_transformation and what its single call does with the result).
-template <class Finish>
-static int place_list_core(const std::vector<PlaceJob>& jobs, const slide_place_params_t& P, int32_t* inliers, int64_t* best_index,
-                           int64_t* n_candidates, int32_t* status, Finish finish) {
-  std::vector<PlaceLattice> lats;
-  std::vector<std::pair<double, double>> lat_key;      // (x_half, y_half): pairs with equal half ranges share one lattice
-  std::vector<PlacePair> live;
-  double sum_pair_tests = 0.0, sum_dist_tests = 0.0;
-  for (size_t j = 0; j < jobs.size(); ++j) {
-    PlaceMap& R = *jobs[j].R;
-    PlaceMap& Q = *jobs[j].Q;
-    const int k = jobs[j].k, nr = R.n, nq = Q.n;
-    const double xh = jobs[j].xh, yh = jobs[j].yh;
-    int li = -1;
-    for (size_t t = 0; t < lat_key.size(); ++t) if (lat_key[t].first == xh && lat_key[t].second == yh) { li = (int)t; break; }
-    if (li < 0) {
-      li = (int)lats.size();
-      lats.emplace_back();
-      place_lattice(xh, yh, P, lats.back());
-      lat_key.emplace_back(xh, yh);
-    }
-    const PlaceLattice& L = lats[li];
-    if (L.ncell() == 0 || L.ny() == 0) { inliers[k] = -10000; continue; }      // (what the single call's sweep reports for no candidate)
-    if (n_candidates) n_candidates[k] = L.ncand();
-    if (!place_image_fits(nr, nq, P.ignore_dimension)) { if (status) status[k] = SLIDE_ERR_CAPACITY; continue; }
-    if (!R.bucketed) { R.bucketed = true; place_bucket_ref(R.data(), nr, R.B); }
-    live.emplace_back();
-    PlacePair& pr = live.back();
-    pr.k = (int)j; pr.lat = li;
-    place_bucket_qry(R.B, Q.data(), nq, pr.Q);
-    pr.weight = (double)L.ncand() * std::max(pr.Q.tests, 1.0);
-    sum_pair_tests += (double)L.ncand() * (double)nq * (double)nr;
-    sum_dist_tests += (double)L.ncand() * pr.Q.tests;
-  }
-  const int n_live = (int)live.size();
-  if (n_live == 0) return SLIDE_OK;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  // workgroups in proportion to candidates x distance tests: every live pair one, the rest of the single launch's 2048 by weight,
-  // no pair more than one wave per candidate can use
-  double wsum = 0.0;
-  for (const PlacePair& pr : live) wsum += pr.weight;
-  const int spare = std::max(0, PLACE_LIST_WGS - n_live);
-  std::vector<int> wg0(n_live + 1, 0);
-  for (int s = 0; s < n_live; ++s) {
-    const long long useful = (lats[live[s].lat].ncand() + 3) / 4;
-    long long n = 1 + (long long)std::floor((double)spare * (live[s].weight / wsum));
-    n = std::max(1LL, std::min(n, useful));
-    wg0[s + 1] = wg0[s] + (int)n;
-  }
-  const int n_wg = wg0[n_live];
-  std::vector<PlaceWg> wgs((size_t)n_wg);
-  for (int s = 0; s < n_live; ++s)
-    for (int r = 0; r < wg0[s + 1] - wg0[s]; ++r) wgs[(size_t)wg0[s] + r] = PlaceWg{s, r, wg0[s + 1] - wg0[s], 0};
-  // the arena: lattices, bucketed reference maps (once each), per-pair query tables, then the tables of pointers
-  PlaceArena A;
-  A.reserve(16);                                        // (offset 0 means "not there yet")
-  struct LatAt { size_t xs, ys, yaws, cx, cy; };
-  std::vector<LatAt> lat_at(lats.size(), LatAt{0, 0, 0, 0, 0});
-  struct PairAt { size_t qxy, qdim, qrange; };
-  std::vector<PairAt> pair_at(n_live);
-  size_t lds_bytes = 0;
-  for (int s = 0; s < n_live; ++s) {
-    const PlacePair& pr = live[s];
-    const PlaceLattice& L = lats[pr.lat];
-    LatAt& la = lat_at[pr.lat];
-    if (!la.xs) {
-      const std::vector<double> ytab = L.yaw_table();
-      la.xs = A.put(L.xs.data(), L.xs.size()); la.ys = A.put(L.ys.data(), L.ys.size()); la.yaws = A.put(ytab.data(), ytab.size());
-      la.cx = A.put(L.cx.data(), L.cx.size()); la.cy = A.put(L.cy.data(), L.cy.size());
-    }
-    PlaceMap& R = *jobs[pr.k].R;
-    if (!R.at_rxy) { R.at_rxy = A.put(R.B.rxy.data(), R.B.rxy.size()); R.at_rdim = A.put(R.B.rdim.data(), R.B.rdim.size()); }
-    pair_at[s] = PairAt{A.put(pr.Q.qxy.data(), pr.Q.qxy.size()), A.put(pr.Q.qdim.data(), pr.Q.qdim.size()), A.put(pr.Q.qrange.data(), pr.Q.qrange.size())};
-    lds_bytes = std::max(lds_bytes, place_lds_bytes(R.n, jobs[pr.k].Q->n, P.ignore_dimension));
-  }
-  const size_t at_segs = A.reserve(sizeof(PlaceDev) * (size_t)n_live);
-  const size_t at_wgs = A.put(wgs.data(), wgs.size());
-  const size_t at_wg0 = A.put(wg0.data(), wg0.size());
-  const size_t up_bytes = A.h.size();
-  const size_t at_part = (up_bytes + 15) & ~(size_t)15;                  // results behind the upload: written by the kernels only
-  const size_t at_best = at_part + sizeof(PlaceBest) * (size_t)n_wg;
-  const size_t all_bytes = at_best + sizeof(PlaceBest) * (size_t)n_live;
-  Tmp T;
-  unsigned char* d = T.up<unsigned char>(nullptr, all_bytes);
-  if (!d) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  const double v_crit = place_v_crit(P.match_threshold_position);
-  for (int s = 0; s < n_live; ++s) {
-    const PlacePair& pr = live[s];
-    const PlaceLattice& L = lats[pr.lat];
-    const LatAt& la = lat_at[pr.lat];
-    const PlaceMap& R = *jobs[pr.k].R;
-    PlaceDev D;
-    D.ref7 = D.qry7 = nullptr; D.inliers = nullptr;
-    D.nr = R.n; D.nq = jobs[pr.k].Q->n;
-    D.xs = reinterpret_cast<const double*>(d + la.xs); D.ys = reinterpret_cast<const double*>(d + la.ys);
-    D.yaws = reinterpret_cast<const double*>(d + la.yaws);
-    D.cell_x = reinterpret_cast<const int32_t*>(d + la.cx); D.cell_y = reinterpret_cast<const int32_t*>(d + la.cy);
-    D.n_cells = L.ncell(); D.n_yaw = L.ny();
-    D.thr_pos = P.match_threshold_position; D.thr_dim = P.match_threshold_dimension; D.ignore_dim = P.ignore_dimension;
-    D.rxy = reinterpret_cast<const double*>(d + R.at_rxy); D.rdim = reinterpret_cast<const double*>(d + R.at_rdim);
-    D.qxy = reinterpret_cast<const double*>(d + pair_at[s].qxy); D.qdim = reinterpret_cast<const double*>(d + pair_at[s].qdim);
-    D.qrange = reinterpret_cast<const int32_t*>(d + pair_at[s].qrange);
-    D.v_crit = v_crit;
-    std::memcpy(A.h.data() + at_segs + sizeof(PlaceDev) * (size_t)s, &D, sizeof(PlaceDev));
-  }
-  SL_HIP(hipMemcpy(d, A.h.data(), up_bytes, hipMemcpyHostToDevice));                                   // the one upload
-  {
-    DevTimer tm(SLIDE_MS_PLACE_SWEEP);
-    launch_place_sweep_seg(reinterpret_cast<const PlaceDev*>(d + at_segs), reinterpret_cast<const PlaceWg*>(d + at_wgs), n_wg, lds_bytes,
-                           reinterpret_cast<PlaceBest*>(d + at_part), reinterpret_cast<const int*>(d + at_wg0), n_live,
-                           reinterpret_cast<PlaceBest*>(d + at_best), nullptr);
-  }
-  g_dev_ms[SLIDE_MS_PLACE_PAIR_TESTS] = sum_pair_tests;
-  g_dev_ms[SLIDE_MS_PLACE_DIST_TESTS] = sum_dist_tests;
-  std::vector<PlaceBest> win(n_live);
-  SL_HIP(hipMemcpy(win.data(), d + at_best, sizeof(PlaceBest) * (size_t)n_live, hipMemcpyDeviceToHost));     // the one read-back
-  SL_HIP(hipGetLastError());
-  for (int s = 0; s < n_live; ++s) {
-    const PlacePair& pr = live[s];
-    const PlaceLattice& L = lats[pr.lat];
-    const int k = jobs[pr.k].k;
-    double best[3] = {0, 0, 0};
-    int inl = -10000;
-    if (win[s].idx >= 0) {
-      const long long cell = win[s].idx / L.ny();
-      best[0] = L.xs[L.cx[cell]]; best[1] = L.ys[L.cy[cell]]; best[2] = L.yaws[win[s].idx % L.ny()];
-      inl = win[s].val;
-    }
-    if (best_index) best_index[k] = win[s].idx;
-    inliers[k] = inl;
-    finish(jobs[pr.k], best, inl);
-  }
-  return SLIDE_OK;
-}
-
-// PlaceRecognition::findInterLoopClosure for a list of pairs: the gate (:507-515), every map centred ONCE (row-order sums, as
-// find_transformation does), the half ranges from the centred extents, then the shared core; per pair finish_transformation with the
-// two centroids and findInterLoopClosure's tf (:528-535), as the single call does.
-static int find_inter_loop_closures(std::vector<PlaceMap>& M, const int32_t* pairs, int n_pairs, const slide_place_params_t& P, double* tf16n,
-                                    int32_t* inliers, double* xyzyaw4n, int32_t* found, int64_t* best_index, int64_t* n_candidates,
-                                    int32_t* status) {
-  auto centre = [&](PlaceMap& m) {
-    if (m.centred) return;
-    m.centred = true;
-    m.rows.assign(m.rows7, m.rows7 + 7 * (size_t)m.n);
-    for (int i = 0; i < m.n; ++i) { m.c[0] += m.rows[7 * (size_t)i + 1]; m.c[1] += m.rows[7 * (size_t)i + 2]; }
-    m.c[0] /= m.n; m.c[1] /= m.n;
-    for (int i = 0; i < m.n; ++i) { m.rows[7 * (size_t)i + 1] -= m.c[0]; m.rows[7 * (size_t)i + 2] -= m.c[1]; }
-  };
-  std::vector<PlaceJob> jobs;
-  for (int k = 0; k < n_pairs; ++k) {
-    PlaceMap& R = M[pairs[2 * k]];
-    PlaceMap& Q = M[pairs[2 * k + 1]];
-    const int nr = R.n, nq = Q.n;
-    if (nr < P.min_num_map_objects_to_start || nq < P.min_num_map_objects_to_start || nr == 0 || nq == 0) continue;      // :507-515
-    centre(R); centre(Q);
-    double xh, yh;
-    half_ranges(R.rows.data(), nr, Q.rows.data(), nq, P, &xh, &yh);
-    jobs.push_back(PlaceJob{k, &R, &Q, xh, yh});
-  }
-  return place_list_core(jobs, P, inliers, best_index, n_candidates, status, [&](const PlaceJob& J, const double best[3], int inl) {
-    const PlaceMap& R = *J.R;
-    const PlaceMap& Q = *J.Q;
-    double xyzyaw[4];
-    if (finish_transformation(R.rows.data(), R.n, Q.rows.data(), Q.n, R.c, Q.c, P, best, inl, xyzyaw) != 1) return;
-    inter_tf16(xyzyaw, tf16n + 16 * (size_t)J.k);
-    if (xyzyaw4n) for (int i = 0; i < 4; ++i) xyzyaw4n[4 * (size_t)J.k + i] = xyzyaw[i];
-    found[J.k] = 1;
-  });
-}
-
-extern "C" {
-int slide_find_inter_loop_closures(const double* maps7, const int32_t* map_off, int n_maps, const int32_t* pairs, int n_pairs,
-                                   const slide_place_params_t* p, double* tf16n, int32_t* inliers, double* xyzyaw4n, int32_t* found,
-                                   int64_t* best_index, int64_t* n_candidates, int32_t* status) {
-  if (n_pairs < 0 || n_maps < 0) return SLIDE_ERR_INVALID;
-  if (n_pairs == 0) return SLIDE_OK;
-  if (!map_off || !pairs || !tf16n || !inliers || !found) { g_last_error = "find_inter_loop_closures: a needed pointer is NULL"; return SLIDE_ERR_INVALID; }
-  if (n_maps > 0 && map_off[0] < 0) { g_last_error = "find_inter_loop_closures: map_off[0] is negative"; return SLIDE_ERR_INVALID; }
-  for (int i = 0; i < n_maps; ++i)
-    if (map_off[i + 1] < map_off[i]) { g_last_error = "find_inter_loop_closures: map_off decreases at map " + std::to_string(i); return SLIDE_ERR_INVALID; }
-  if (n_maps > 0 && map_off[n_maps] > map_off[0] && !maps7) { g_last_error = "find_inter_loop_closures: maps7 is NULL"; return SLIDE_ERR_INVALID; }
-  for (int k = 0; k < n_pairs; ++k)
-    if (pairs[2 * k] < 0 || pairs[2 * k] >= n_maps || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= n_maps) {
-      g_last_error = "find_inter_loop_closures: pair " + std::to_string(k) + " names a map outside [0, n_maps)";
-      return SLIDE_ERR_INVALID;
-    }
-  slide_place_params_t P;
-  if (p) P = *p; else slide_place_default_params(&P);
-  std::vector<PlaceMap> M(n_maps);
-  for (int i = 0; i < n_maps; ++i) { M[i].rows7 = maps7 ? maps7 + 7 * (size_t)map_off[i] : nullptr; M[i].n = map_off[i + 1] - map_off[i]; }
-  for (int k = 0; k < n_pairs; ++k) {
-    double* tf = tf16n + 16 * (size_t)k;
-    for (int i = 0; i < 16; ++i) tf[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    inliers[k] = 0;
-    found[k] = 0;
-    if (xyzyaw4n) for (int i = 0; i < 4; ++i) xyzyaw4n[4 * (size_t)k + i] = 0.0;
-    if (best_index) best_index[k] = -1;
-    if (n_candidates) n_candidates[k] = 0;
-    if (status) status[k] = SLIDE_OK;
-  }
-  return find_inter_loop_closures(M, pairs, n_pairs, P, tf16n, inliers, xyzyaw4n, found, best_index, n_candidates, status);
-}
-
-}  // extern "C"
-// loop_closure_transform = [Rz(yaw) | (x, y, 0)] :456-471 ; tf = candidate^-1 * query * loop_closure_transform :479-492.  ONE text
-// for the single call and the list form.
-static void intra_tf16(const SE3& Cn, const SE3& Q, const double xyzyaw[4], double tf16[16]) {
-  SE3 Lc;
-  const double c = std::cos(xyzyaw[3]), s = std::sin(xyzyaw[3]);
-  Lc.R = M3{{c, -s, 0, s, c, 0, 0, 0, 1}};
-  Lc.t = V3{xyzyaw[0], xyzyaw[1], 0.0};
-  const SE3 out = compose(compose(inverse(Cn), Q), Lc);
-  for (int r = 0; r < 3; ++r) {
-    for (int k = 0; k < 3; ++k) tf16[4 * r + k] = out.R.a[3 * r + k];
-    tf16[12 + r] = 0.0;
-  }
-  tf16[3] = out.t.x; tf16[7] = out.t.y; tf16[11] = out.t.z; tf16[15] = 1.0;
-}
-extern "C" {
-// PlaceRecognition::findIntraLoopClosure place_recognition.cpp:389-496
-int slide_find_intra_loop_closure(const double* meas7, int nm, const double* submap7, int ns, const double query_pose7[7],
-                                  const double candidate_pose7[7], const slide_place_params_t* p, double x_half_range_intra,
-                                  double y_half_range_intra, double yaw_half_range_intra, double tf16[16], int* inliers,
-                                  double xyzyaw_out[4]) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (!query_pose7 || !candidate_pose7 || !tf16) return SLIDE_ERR_INVALID;
-  slide_place_params_t P;
-  if (p) P = *p; else slide_place_default_params(&P);
-  if (inliers) *inliers = 0;
-  if (nm == 0 || ns == 0) return 0;      // :396-399
-  if (nm < 4) return 0;                  // :400-405
-  const SE3 Q = from7(query_pose7), Cn = from7(candidate_pose7);
-  // measurements are in the local frame: into the map frame with the (drifted) query pose :418-440
-  std::vector<double> mw(meas7, meas7 + 7 * (size_t)nm);
-  for (int i = 0; i < nm; ++i) {
-    const V3 w = transform_from(Q, V3{meas7[7 * i + 1], meas7[7 * i + 2], meas7[7 * i + 3]});
-    mw[7 * (size_t)i + 1] = w.x; mw[7 * (size_t)i + 2] = w.y; mw[7 * (size_t)i + 3] = w.z;
-  }
-  double xyzyaw[4];
-  const int rc = find_transformation(submap7, ns, mw.data(), nm, P, false, x_half_range_intra, y_half_range_intra, yaw_half_range_intra,
-                                     inliers, xyzyaw);
-  if (rc != 1) return rc;
-  intra_tf16(Cn, Q, xyzyaw, tf16);
-  if (xyzyaw_out) for (int i = 0; i < 4; ++i) xyzyaw_out[i] = xyzyaw[i];
-  return 1;
-}
-
-// findIntraLoopClosure for a list of candidate key poses (the attempts of SLOAMNode::intraLoopClosureThread_, sloamNode.cpp:355-486,
-// over every candidate instead of the first): the detections go into the map frame ONCE, candidate k's submap is the reference map of
-// pair k, the one transformed query is re-bucketed against each submap's labels, all candidates share the one intra lattice; the
-// shared core of the inter list sweeps them.
-int slide_find_intra_loop_closures(const double* meas7, int nm, const double query_pose7[7], const double* submaps7, const int32_t* sub_off,
-                                   int n_cand, const double* candidate_pose7n, const slide_place_params_t* p, double x_half_range_intra,
-                                   double y_half_range_intra, double yaw_half_range_intra, double* tf16n, int32_t* inliers,
-                                   double* xyzyaw4n, int32_t* found, int64_t* best_index, int64_t* n_candidates, int32_t* status) {
-  if (n_cand < 0 || nm < 0) return SLIDE_ERR_INVALID;
-  if (n_cand == 0) return SLIDE_OK;
-  if (!sub_off || !candidate_pose7n || !query_pose7 || !tf16n || !inliers || !found || (nm > 0 && !meas7)) {
-    g_last_error = "find_intra_loop_closures: a needed pointer is NULL";
-    return SLIDE_ERR_INVALID;
-  }
-  if (sub_off[0] < 0) { g_last_error = "find_intra_loop_closures: sub_off[0] is negative"; return SLIDE_ERR_INVALID; }
-  for (int k = 0; k < n_cand; ++k)
-    if (sub_off[k + 1] < sub_off[k]) { g_last_error = "find_intra_loop_closures: sub_off decreases at candidate " + std::to_string(k); return SLIDE_ERR_INVALID; }
-  if (sub_off[n_cand] > sub_off[0] && !submaps7) { g_last_error = "find_intra_loop_closures: submaps7 is NULL"; return SLIDE_ERR_INVALID; }
-  slide_place_params_t P;
-  if (p) P = *p; else slide_place_default_params(&P);
-  for (int k = 0; k < n_cand; ++k) {
-    double* tf = tf16n + 16 * (size_t)k;
-    for (int i = 0; i < 16; ++i) tf[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    inliers[k] = 0;
-    found[k] = 0;
-    if (xyzyaw4n) for (int i = 0; i < 4; ++i) xyzyaw4n[4 * (size_t)k + i] = 0.0;
-    if (best_index) best_index[k] = -1;
-    if (n_candidates) n_candidates[k] = 0;
-    if (status) status[k] = SLIDE_OK;
-  }
-  if (nm == 0 || nm < 4) return SLIDE_OK;      // :396-405
-  const SE3 Q = from7(query_pose7);
-  std::vector<double> mw(meas7, meas7 + 7 * (size_t)nm);      // :418-440, as the single call
-  for (int i = 0; i < nm; ++i) {
-    const V3 w = transform_from(Q, V3{meas7[7 * i + 1], meas7[7 * i + 2], meas7[7 * i + 3]});
-    mw[7 * (size_t)i + 1] = w.x; mw[7 * (size_t)i + 2] = w.y; mw[7 * (size_t)i + 3] = w.z;
-  }
-  P.match_yaw_half_range = yaw_half_range_intra;      // findTransformation :801-816
-  std::vector<PlaceMap> M((size_t)n_cand + 1);
-  PlaceMap& Qm = M[n_cand];
-  Qm.rows7 = mw.data(); Qm.n = nm;
-  std::vector<PlaceJob> jobs;
-  for (int k = 0; k < n_cand; ++k) {
-    M[k].n = sub_off[k + 1] - sub_off[k];
-    if (M[k].n == 0) continue;                 // :396-399
-    M[k].rows7 = submaps7 + 7 * (size_t)sub_off[k];
-    jobs.push_back(PlaceJob{k, &M[k], &Qm, x_half_range_intra, y_half_range_intra});
-  }
-  const double zero[2] = {0, 0};
-  return place_list_core(jobs, P, inliers, best_index, n_candidates, status, [&](const PlaceJob& J, const double best[3], int inl) {
-    double xyzyaw[4];
-    if (finish_transformation(J.R->rows7, J.R->n, mw.data(), nm, zero, zero, P, best, inl, xyzyaw) != 1) return;
-    intra_tf16(from7(candidate_pose7n + 7 * (size_t)J.k), Q, xyzyaw, tf16n + 16 * (size_t)J.k);
-    if (xyzyaw4n) for (int i = 0; i < 4; ++i) xyzyaw4n[4 * (size_t)J.k + i] = xyzyaw[i];
-    found[J.k] = 1;
-  });
-}
-
-}  // extern "C"
-// ---- getkeyPoseSubmap x 3 + prepareLCInput for a list of key poses (k_keypose_submap) ----------------------------------------------------
-// rows / src filled when the total fits `capacity` (capacity < 0: own_rows / own_src are sized to the total instead).  The map tables
-// go up once; launches: count, k_seg_scan, emit; blocking read-backs: the per-pose totals, then the rows (and their source indices).
-namespace {
-struct SubmapTables {
-  const double *cyl_root3, *cyl_ray3, *cyl_radius; const int32_t* cyl_label; int n_cyl;
-  const double *cube_xyz3, *cube_scale3; const int32_t* cube_label; int n_cube;
-  const double *ell_xyz3, *ell_scale3; const int32_t* ell_label; int n_ell;
-};
-bool submap_tables_valid(const SubmapTables& t) {
-  if (t.n_cyl < 0 || t.n_cube < 0 || t.n_ell < 0) return false;
-  if (t.n_cyl > 0 && (!t.cyl_root3 || !t.cyl_ray3 || !t.cyl_radius || !t.cyl_label)) return false;
-  if (t.n_cube > 0 && (!t.cube_xyz3 || !t.cube_scale3 || !t.cube_label)) return false;
-  if (t.n_ell > 0 && (!t.ell_xyz3 || !t.ell_scale3 || !t.ell_label)) return false;
-  return (long long)t.n_cyl + t.n_cube + t.n_ell <= (long long)INT32_MAX - 256;
-}
-int keypose_submaps(const SubmapTables& t, const double* pose_xyz, int pose_stride, int n_poses, double submap_radius, double max_dz,
-                    int32_t* sub_off, double* rows7, int32_t* src_idx, int64_t capacity, int64_t* n_rows, std::vector<double>* own_rows) {
-  *n_rows = 0;
-  for (int k = 0; k <= n_poses; ++k) sub_off[k] = 0;
-  const int n_all = t.n_cyl + t.n_cube + t.n_ell;
-  if (n_poses == 0 || n_all == 0) return SLIDE_OK;
-  const int n_chunk = (n_all + 255) / 256;
-  if ((long long)n_chunk * n_poses > (long long)INT32_MAX) { g_last_error = "keypose_submaps: poses x 256-object chunks exceed 2^31 - 1"; return SLIDE_ERR_CAPACITY; }
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  const int n_wg = n_chunk * n_poses;
-  Tmp T;
-  SubmapDev S;
-  S.cyl_root = T.up(t.cyl_root3, 3 * (size_t)t.n_cyl); S.cyl_ray = T.up(t.cyl_ray3, 3 * (size_t)t.n_cyl);
-  S.cyl_radius = T.up(t.cyl_radius, (size_t)t.n_cyl); S.cyl_label = T.up(t.cyl_label, (size_t)t.n_cyl); S.n_cyl = t.n_cyl;
-  S.cube_xyz = T.up(t.cube_xyz3, 3 * (size_t)t.n_cube); S.cube_scale = T.up(t.cube_scale3, 3 * (size_t)t.n_cube);
-  S.cube_label = T.up(t.cube_label, (size_t)t.n_cube); S.n_cube = t.n_cube;
-  S.ell_xyz = T.up(t.ell_xyz3, 3 * (size_t)t.n_ell); S.ell_scale = T.up(t.ell_scale3, 3 * (size_t)t.n_ell);
-  S.ell_label = T.up(t.ell_label, (size_t)t.n_ell); S.n_ell = t.n_ell;
-  std::vector<double> pos(3 * (size_t)n_poses);
-  for (int k = 0; k < n_poses; ++k) for (int a = 0; a < 3; ++a) pos[3 * (size_t)k + a] = pose_xyz[(size_t)pose_stride * k + a];
-  S.pose_xyz = T.up(pos.data(), pos.size()); S.pose_stride = 3;
-  S.radius = submap_radius; S.max_dz = max_dz;
-  std::vector<int> segoff((size_t)n_poses + 1);
-  for (int k = 0; k <= n_poses; ++k) segoff[k] = k * n_chunk;
-  int* d_segoff = T.up(segoff.data(), segoff.size());
-  int* d_cnt = T.up<int>(nullptr, (size_t)n_wg);
-  long long* d_chunkoff = T.up<long long>(nullptr, (size_t)n_wg);
-  long long* d_tot = T.up<long long>(nullptr, (size_t)n_poses);
-  long long* d_base = T.up<long long>(nullptr, (size_t)n_poses);
-  if (!S.cyl_root || !S.cyl_ray || !S.cyl_radius || !S.cyl_label || !S.cube_xyz || !S.cube_scale || !S.cube_label || !S.ell_xyz || !S.ell_scale ||
-      !S.ell_label || !S.pose_xyz || !d_segoff || !d_cnt || !d_chunkoff || !d_tot || !d_base) {
-    g_last_error = "hipMalloc/hipMemcpy failed";
-    return SLIDE_ERR_HIP;
-  }
-  launch_keypose_submap(false, S, n_poses, n_chunk, d_cnt, nullptr, nullptr, nullptr, nullptr, nullptr);
-  launch_seg_scan64(d_cnt, d_segoff, n_poses, d_chunkoff, d_tot, nullptr);
-  std::vector<long long> tot((size_t)n_poses), base((size_t)n_poses);
-  SL_HIP(hipMemcpy(tot.data(), d_tot, sizeof(long long) * (size_t)n_poses, hipMemcpyDeviceToHost));      // read-back 1: the totals
-  SL_HIP(hipGetLastError());
-  long long total = 0;
-  for (int k = 0; k < n_poses; ++k) { base[k] = total; total += tot[k]; }
-  *n_rows = total;
-  if (total > (long long)INT32_MAX) { g_last_error = "keypose_submaps: more than 2^31 - 1 rows"; return SLIDE_ERR_CAPACITY; }
-  for (int k = 0; k < n_poses; ++k) sub_off[k] = (int32_t)base[k];
-  sub_off[n_poses] = (int32_t)total;
-  if (own_rows) { own_rows->assign(7 * (size_t)total, 0.0); rows7 = own_rows->data(); }
-  else if (total > capacity) { g_last_error = "keypose_submaps: the row buffers are too small"; return SLIDE_ERR_CAPACITY; }
-  if (total == 0) return SLIDE_OK;
-  double* d_rows = T.up<double>(nullptr, 7 * (size_t)total);
-  int32_t* d_src = src_idx ? T.up<int32_t>(nullptr, (size_t)total) : nullptr;
-  if (!d_rows || (src_idx && !d_src)) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  SL_HIP(hipMemcpy(d_base, base.data(), sizeof(long long) * (size_t)n_poses, hipMemcpyHostToDevice));
-  launch_keypose_submap(true, S, n_poses, n_chunk, nullptr, d_chunkoff, d_base, d_rows, d_src, nullptr);
-  SL_HIP(hipMemcpy(rows7, d_rows, sizeof(double) * 7 * (size_t)total, hipMemcpyDeviceToHost));             // read-back 2: the rows
-  if (src_idx) SL_HIP(hipMemcpy(src_idx, d_src, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost));
-  SL_HIP(hipGetLastError());
-  return SLIDE_OK;
-}
-}  // namespace
-extern "C" {
-int slide_keypose_submaps(const double* cyl_root3, const double* cyl_ray3, const double* cyl_radius, const int32_t* cyl_label, int n_cyl,
-                          const double* cube_xyz3, const double* cube_scale3, const int32_t* cube_label, int n_cube, const double* ell_xyz3,
-                          const double* ell_scale3, const int32_t* ell_label, int n_ell, const double* pose_xyz3n, int n_poses,
-                          double submap_radius, double max_dz, int32_t* sub_off, double* rows7, int32_t* src_idx, int64_t capacity,
-                          int64_t* n_rows) {
-  const SubmapTables t{cyl_root3, cyl_ray3, cyl_radius, cyl_label, n_cyl, cube_xyz3, cube_scale3, cube_label, n_cube, ell_xyz3, ell_scale3, ell_label, n_ell};
-  if (n_poses < 0 || capacity < 0 || !sub_off || !n_rows || (n_poses > 0 && !pose_xyz3n) || (capacity > 0 && !rows7) || !submap_tables_valid(t)) {
-    g_last_error = "keypose_submaps: a negative count or a needed pointer is NULL";
-    return SLIDE_ERR_INVALID;
-  }
-  return keypose_submaps(t, pose_xyz3n, 3, n_poses, submap_radius, max_dz, sub_off, rows7, src_idx, capacity, n_rows, nullptr);
-}
-
-// One attempt of SLOAMNode::intraLoopClosureThread_ (sloamNode.cpp:355-486) over a list of candidate key poses: slide_keypose_submaps
-// around the candidates' positions, then slide_find_intra_loop_closures on what it produced.
-int slide_intra_loop_closure_attempt(const double* cyl_root3, const double* cyl_ray3, const double* cyl_radius, const int32_t* cyl_label, int n_cyl,
-                                     const double* cube_xyz3, const double* cube_scale3, const int32_t* cube_label, int n_cube,
-                                     const double* ell_xyz3, const double* ell_scale3, const int32_t* ell_label, int n_ell, const double* meas7,
-                                     int nm, const double query_pose7[7], const double* candidate_pose7n, int n_cand, double submap_radius,
-                                     double max_dz, const slide_place_params_t* p, double x_half_range_intra, double y_half_range_intra,
-                                     double yaw_half_range_intra, double* tf16n, int32_t* inliers, double* xyzyaw4n, int32_t* found,
-                                     int64_t* best_index, int64_t* n_candidates, int32_t* status, int32_t* submap_sizes) {
-  const SubmapTables t{cyl_root3, cyl_ray3, cyl_radius, cyl_label, n_cyl, cube_xyz3, cube_scale3, cube_label, n_cube, ell_xyz3, ell_scale3, ell_label, n_ell};
-  if (n_cand < 0 || nm < 0 || !submap_tables_valid(t)) return SLIDE_ERR_INVALID;
-  if (n_cand == 0) return SLIDE_OK;
-  if (!candidate_pose7n || !query_pose7 || !tf16n || !inliers || !found || !submap_sizes || (nm > 0 && !meas7)) {
-    g_last_error = "intra_loop_closure_attempt: a needed pointer is NULL";
-    return SLIDE_ERR_INVALID;
-  }
-  std::vector<int32_t> off((size_t)n_cand + 1);
-  std::vector<double> rows;
-  int64_t n_rows = 0;
-  const int rc = keypose_submaps(t, candidate_pose7n, 7, n_cand, submap_radius, max_dz, off.data(), nullptr, nullptr, -1, &n_rows, &rows);
-  if (rc != SLIDE_OK) return rc;
-  for (int k = 0; k < n_cand; ++k) submap_sizes[k] = off[k + 1] - off[k];
-  return slide_find_intra_loop_closures(meas7, nm, query_pose7, rows.data(), off.data(), n_cand, candidate_pose7n, p, x_half_range_intra,
-                                        y_half_range_intra, yaw_half_range_intra, tf16n, inliers, xyzyaw4n, found, best_index, n_candidates,
-                                        status);
-}
-
-int slide_clipper_affinity(const double* D1, int n1, const double* D2, int n2, int dim, const int32_t* A, int m, double sigma,
-                           double epsilon, double mindist, double affinityeps, double* M_out) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (m <= 0) return SLIDE_OK;
-  Tmp T;
-  double* d1 = T.up(D1, (size_t)n1 * dim);
-  double* d2 = T.up(D2, (size_t)n2 * dim);
-  int32_t* dA = T.up(A, 2 * (size_t)m);
-  double* dM = T.up<double>(nullptr, (size_t)m * m);
-  if (!d1 || !d2 || !dA || !dM) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  {
-    DevTimer tm(SLIDE_MS_AFFINITY);
-    launch_clipper_affinity(d1, d2, dim, dA, m, sigma, epsilon, mindist, affinityeps, dM, nullptr);
-  }
-  SL_HIP(hipMemcpy(M_out, dM, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost));
-  SL_HIP(hipGetLastError());
-  return SLIDE_OK;
-}
-
-void slide_clipper_default_params(slide_clipper_params_t* p) {
-  p->tol_u = 1e-8; p->tol_F = 1e-9; p->maxiniters = 200; p->maxoliters = 1000; p->beta = 0.25; p->maxlsiters = 99;
-  p->eps = 1e-9; p->affinityeps = 1e-4; p->rescale_u0 = 1; p->sigma = 0.01; p->epsilon = 0.06; p->mindist = 0.0;
-}
-
-// ---- CLIPPER::findDenseClique clipper.cpp:172-323 (DSD_HEU rounding) -------------------------------------------------
-// The solve runs entirely on the device (clipper_kernels.hip): CSR of the symmetric affinity matrix built from its dense upper
-// triangle, then ONE persistent workgroup for the whole projected-gradient iteration.  The host only draws the start weights,
-// sizes the CSR (one prefix sum over the row counts) and rounds the result.
-}  // extern "C"
-namespace {
-// DSD_HEU rounding (clipper.cpp:302-310 with utils.cpp:33-55): the omega entries of u the reference's bounded min-heap scan keeps —
-// an entry replaces the heap's smallest (value, index) pair only when its value is strictly larger — largest pair first.
-std::vector<int> top_entries(const std::vector<double>& x, int k) {
-  std::vector<int> heap;                                   // indices, min-heap on (x[i], i)
-  if (k < 1) return heap;
-  auto greater = [&](int a, int b) { return x[a] > x[b] || (x[a] == x[b] && a > b); };
-  for (int i = 0; i < (int)x.size(); ++i) {
-    if ((int)heap.size() < k) { heap.push_back(i); std::push_heap(heap.begin(), heap.end(), greater); }
-    else if (x[heap.front()] < x[i]) { std::pop_heap(heap.begin(), heap.end(), greater); heap.back() = i; std::push_heap(heap.begin(), heap.end(), greater); }
-  }
-  std::sort_heap(heap.begin(), heap.end(), greater);      // descending in the heap's order = largest pair first
-  return heap;
-}
-void default_u0(std::vector<double>& u) {             // fixed-seed splitmix64 -> U[0, 1)
-  uint64_t x = 0x9E3779B97F4A7C15ull;
-  for (double& v : u) {
-    x += 0x9E3779B97F4A7C15ull;
-    uint64_t z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    v = (double)(z >> 11) * (1.0 / 9007199254740992.0);
-  }
-}
-
-// A CSR of the symmetric affinity matrix on the device (in the caller's Tmp), its row pointers on the host as well.  Three builders
-// feed the one solve below: from a dense upper triangle, from the associations, from the caller's own arrays.
-struct DevCsr {
-  int* ptr = nullptr;
-  int* col = nullptr;
-  double* val = nullptr;
-  long long nnz = -1;          // set once the scan of the row counts has finished
-  std::vector<int> h_ptr;
-};
-// row counts (device) -> row pointers on both sides + col / val allocated; nnz summed in 64 bits
-// cap >= 0: more non-zeros than cap end the build with SLIDE_ERR_CAPACITY before col / val exist (h_ptr and nnz are set)
-int csr_scan_alloc(Tmp& T, const int* d_cnt, int n, DevCsr& S, long long cap = -1) {
-  std::vector<int> cnt(n);
-  S.h_ptr.assign((size_t)n + 1, 0);
-  SL_HIP(hipMemcpy(cnt.data(), d_cnt, sizeof(int) * n, hipMemcpyDeviceToHost));
-  long long nnz = 0;
-  for (int i = 0; i < n; ++i) {
-    nnz += cnt[i];
-    if (nnz > INT32_MAX) { g_last_error = "affinity matrix has more than 2^31 non-zeros"; return SLIDE_ERR_CAPACITY; }
-    S.h_ptr[i + 1] = (int)nnz;
-  }
-  S.nnz = nnz;
-  if (cap >= 0 && nnz > cap) { g_last_error = "the CSR has " + std::to_string(nnz) + " non-zeros, the caller's buffers hold " + std::to_string(cap); return SLIDE_ERR_CAPACITY; }
-  S.ptr = T.up(S.h_ptr.data(), (size_t)n + 1);
-  S.col = T.up<int>(nullptr, (size_t)std::max<long long>(nnz, 1));
-  S.val = T.up<double>(nullptr, (size_t)std::max<long long>(nnz, 1));
-  if (!S.ptr || !S.col || !S.val) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  return SLIDE_OK;
-}
-// dM: device, n x n row-major upper-filled (n > 0)
-int csr_from_dense_device(Tmp& T, const double* dM, int n, DevCsr& S) {
-  int* d_cnt = T.up<int>(nullptr, n);
-  if (!d_cnt) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  {
-    DevTimer tm(SLIDE_MS_CLQ_CSR);
-    launch_clq_csr_count(dM, n, d_cnt, nullptr);
-  }
-  const int rc = csr_scan_alloc(T, d_cnt, n, S);
-  if (rc != SLIDE_OK) return rc;
-  {
-    DevTimer tm(SLIDE_MS_CLQ_CSR, true);
-    launch_clq_csr_fill(dM, n, S.ptr, S.col, S.val, nullptr);
-  }
-  g_dev_ms[SLIDE_MS_CLQ_NNZ] = (double)S.nnz;
-  return SLIDE_OK;
-}
-// scorePairwiseConsistency clipper.cpp:21-65 ending in M_ = M.sparseView(): k_affinity_csr count, host scan, emit — nothing of size
-// m^2.  d1 / d2 / dA: device copies of D1 / D2 / A (m > 0).  The points are gathered per association first (k_affinity_gather: 2 m dim
-// doubles); SLIDE_AFFINITY_CSR_GATHER=0 in the environment reads them through A instead (the variant DESIGN.md 7 measures against;
-// the same bits).
-int csr_from_assoc_device(Tmp& T, const double* d1, const double* d2, int dim, const int32_t* dA, int m, double sigma, double epsilon,
-                          double mindist, double affinityeps, DevCsr& S, long long cap = -1) {
-  int* d_cnt = T.up<int>(nullptr, m);
-  double *p1 = nullptr, *p2 = nullptr;
-  const char* e = getenv("SLIDE_AFFINITY_CSR_GATHER");
-  if (!(e && e[0] == '0' && e[1] == 0)) {
-    p1 = T.up<double>(nullptr, (size_t)m * dim);
-    p2 = T.up<double>(nullptr, (size_t)m * dim);
-    if (!p1 || !p2) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  }
-  if (!d_cnt) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  {
-    DevTimer tm(SLIDE_MS_AFFINITY_CSR);
-    if (p1) launch_affinity_gather(d1, d2, dim, dA, m, p1, p2, nullptr);
-    launch_affinity_csr(false, d1, d2, p1, p2, dim, dA, m, sigma, epsilon, mindist, affinityeps, d_cnt, nullptr, nullptr, nullptr, nullptr);
-  }
-  SL_HIP(hipGetLastError());
-  const int rc = csr_scan_alloc(T, d_cnt, m, S, cap);
-  if (rc != SLIDE_OK) return rc;
-  {
-    DevTimer tm(SLIDE_MS_AFFINITY_CSR, true);
-    launch_affinity_csr(true, d1, d2, p1, p2, dim, dA, m, sigma, epsilon, mindist, affinityeps, nullptr, S.ptr, S.col, S.val, nullptr);
-  }
-  SL_HIP(hipGetLastError());
-  g_dev_ms[SLIDE_MS_CLQ_NNZ] = (double)S.nnz;
-  return SLIDE_OK;
-}
-// A (m x 2) names points of D1 (n1) and D2 (n2)
-int check_associations(const int32_t* A, int m, int n1, int n2) {
-  for (int j = 0; j < m; ++j)
-    if (A[2 * (size_t)j] < 0 || A[2 * (size_t)j] >= n1 || A[2 * (size_t)j + 1] < 0 || A[2 * (size_t)j + 1] >= n2) {
-      g_last_error = "association " + std::to_string(j) + " names a point outside D1 / D2";
-      return SLIDE_ERR_INVALID;
-    }
-  return SLIDE_OK;
-}
-
-// findDenseClique on a device CSR (n > 0): ClqSolve set-up, the cooperative or the one-workgroup kernel, read-back, DSD_HEU rounding
-static int g_clq_last_wgs = 1;          // workgroups the last single-problem solve ran on, and its gradient evaluations
-static double g_clq_last_evals = 0.0;
-int solve_csr_device(Tmp& T, const DevCsr& S, int n, const double* u0, const slide_clipper_params_t& P, std::vector<int>& nodes,
-                     std::vector<double>& u, double& score) {
-  nodes.clear();
-  u.assign(n, 0.0);
-  score = 0.0;
-  std::vector<double> start(n);
-  if (u0) start.assign(u0, u0 + n); else default_u0(start);
-  int* d_ptr = S.ptr; int* d_col = S.col; double* d_val = S.val;
-  double* d_u0 = T.up(start.data(), n);
-  double* d_work = T.up<double>(nullptr, 6 * (size_t)n);
-  double* d_out = T.up<double>(nullptr, 4);
-  if (!d_u0 || !d_work || !d_out) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  // one large problem: the product's rows over several workgroups (4 rows per wave and product, at most 128 workgroups; below 1024
-  // associations one CU is quicker than a grid barrier per evaluation).  SLIDE_CLIPPER_WGS forces a count (1 = the one-workgroup kernel).
-  int n_wg = n >= 1024 ? std::min(128, (n + 63) / 64) : 1;
-  if (const char* e = getenv("SLIDE_CLIPPER_WGS")) { const int v = atoi(e); if (v >= 1) n_wg = std::min(v, 256); }
-  g_clq_last_wgs = 1;
-  bool done = false;
-  DevTimer* solve_tm = nullptr;
-  if (n_wg > 1) {
-    double* d_priv = T.up<double>(nullptr, (size_t)n_wg * 4 * n);
-    double* d_mc = T.up<double>(nullptr, 4 * (size_t)n);
-    int* d_bar = T.up<int>(nullptr, 2);
-    if (!d_priv || !d_mc || !d_bar) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-    ClqSolve A{};
-    A.rowptr = d_ptr; A.col = d_col; A.val = d_val; A.n = n; A.u0 = d_u0;
-    A.u = d_work; A.unew = A.g = A.gnew = nullptr; A.Mu = d_mc; A.Cu = d_mc + n;
-    A.tol_u = P.tol_u; A.tol_F = P.tol_F; A.beta = P.beta; A.eps = P.eps;
-    A.maxin = P.maxiniters; A.maxol = P.maxoliters; A.maxls = P.maxlsiters; A.rescale = P.rescale_u0;
-    A.out = d_out;
-    solve_tm = new DevTimer(SLIDE_MS_CLQ_SOLVE);
-    done = launch_clq_solve_coop(A, d_priv, d_bar, n_wg, nullptr);
-    if (done) g_clq_last_wgs = n_wg;
-    else { delete solve_tm; solve_tm = nullptr; }
-  }
-  if (!done) {
-    solve_tm = new DevTimer(SLIDE_MS_CLQ_SOLVE);
-    launch_clq_solve(d_ptr, d_col, d_val, n, d_u0, d_work, P.tol_u, P.tol_F, P.beta, P.eps, P.maxiniters, P.maxoliters, P.maxlsiters,
-                     P.rescale_u0, d_out, nullptr);
-  }
-  delete solve_tm;
-  double out4[4];
-  SL_HIP(hipMemcpy(out4, d_out, sizeof(out4), hipMemcpyDeviceToHost));
-  if (out4[2] < 0.0) { g_last_error = "clipper: a grid barrier of the multi-workgroup solve timed out"; return SLIDE_ERR_HIP; }
-  g_clq_last_evals = out4[2];
-  SL_HIP(hipMemcpy(u.data(), d_work, sizeof(double) * n, hipMemcpyDeviceToHost));
-  SL_HIP(hipGetLastError());
-  score = out4[0];
-  nodes = top_entries(u, (int)std::round(score));
-  return SLIDE_OK;
-}
-// dM: device, n x n row-major upper-filled.  Returns SLIDE_OK and fills nodes / u / score.
-int dense_clique_device(const double* dM, int n, const double* u0, const slide_clipper_params_t& P, std::vector<int>& nodes,
-                        std::vector<double>& u, double& score) {
-  nodes.clear();
-  u.assign(n, 0.0);
-  score = 0.0;
-  if (n == 0) return SLIDE_OK;
-  Tmp T;
-  DevCsr S;
-  const int rc = csr_from_dense_device(T, dM, n, S);
-  if (rc != SLIDE_OK) return rc;
-  return solve_csr_device(T, S, n, u0, P, nodes, u, score);
-}
-
-// semantic_clipper.cpp:122-138; see the oracle's note on the reflection branch
-void estimate_tf2d(const double* a, const double* b, int n, double* tf3) {
-  double ca[2] = {0, 0}, cb[2] = {0, 0};
-  for (int i = 0; i < n; ++i) { ca[0] += a[2 * i]; ca[1] += a[2 * i + 1]; cb[0] += b[2 * i]; cb[1] += b[2 * i + 1]; }
-  for (int k = 0; k < 2; ++k) { ca[k] /= n; cb[k] /= n; }
-  double H[4] = {0, 0, 0, 0};
-  for (int i = 0; i < n; ++i) {
-    const double ax = a[2 * i] - ca[0], ay = a[2 * i + 1] - ca[1], bx = b[2 * i] - cb[0], by = b[2 * i + 1] - cb[1];
-    H[0] += ax * bx; H[1] += ax * by; H[2] += ay * bx; H[3] += ay * by;
-  }
-  // V U^T of H = U S V^T maximises trace(R H) over orthogonal R: a rotation when det H >= 0, else a reflection whose
-  // column 1 the reference negates (:130-132) — which yields the rotation by the reflection's own angle.
-  const double detH = H[0] * H[3] - H[1] * H[2];
-  const double th = detH >= 0.0 ? std::atan2(H[1] - H[2], H[0] + H[3]) : std::atan2(H[1] + H[2], H[0] - H[3]);
-  const double c = std::cos(th), s = std::sin(th);
-  tf3[0] = c; tf3[1] = -s; tf3[2] = cb[0] - (c * ca[0] - s * ca[1]);
-  tf3[3] = s; tf3[4] = c; tf3[5] = cb[1] - (s * ca[0] + c * ca[1]);
-  tf3[6] = 0; tf3[7] = 0; tf3[8] = 1;
-}
-
-// device-side triangle matching: returns pairs in d_pts (12 doubles per pair) / d_diffs, count in np
-int match_triangles_device(Tmp& T, const double* tri_model, int ntm, const double* tri_data, int ntd, double thr, double** d_pts,
-                           double** d_diffs, long long* np) {
-  *np = 0; *d_pts = nullptr; *d_diffs = nullptr;
-  if (ntm <= 0 || ntd <= 0) return SLIDE_OK;
-  double* dtm = T.up(tri_model, 6 * (size_t)ntm);
-  double* dtd = T.up(tri_data, 6 * (size_t)ntd);
-  double* sdm = T.up<double>(nullptr, 3 * (size_t)ntm);
-  double* sxm = T.up<double>(nullptr, 6 * (size_t)ntm);
-  double* sdd = T.up<double>(nullptr, 3 * (size_t)ntd);
-  double* sxd = T.up<double>(nullptr, 6 * (size_t)ntd);
-  int* dcnt = T.up<int>(nullptr, ntm);
-  long long* doff = T.up<long long>(nullptr, ntm);
-  if (!dtm || !dtd || !sdm || !sxm || !sdd || !sxd || !dcnt || !doff) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  {
-    DevTimer tm(SLIDE_MS_TRI_MATCH);
-    launch_tri_prepare(dtm, ntm, sdm, sxm, nullptr);
-    launch_tri_prepare(dtd, ntd, sdd, sxd, nullptr);
-    launch_tri_match(false, sdm, sxm, ntm, sdd, sxd, ntd, thr, dcnt, nullptr, nullptr, nullptr, nullptr);
-  }
-  g_dev_ms[SLIDE_MS_TRI_PAIRS] = (double)ntm * (double)ntd;
-  std::vector<int> cnt(ntm);
-  SL_HIP(hipMemcpy(cnt.data(), dcnt, sizeof(int) * ntm, hipMemcpyDeviceToHost));
-  std::vector<long long> off(ntm);
-  long long tot = 0;
-  for (int i = 0; i < ntm; ++i) { off[i] = tot; tot += cnt[i]; }
-  *np = tot;
-  if (tot == 0) return SLIDE_OK;
-  SL_HIP(hipMemcpy(doff, off.data(), sizeof(long long) * ntm, hipMemcpyHostToDevice));
-  *d_pts = T.up<double>(nullptr, 12 * (size_t)tot);
-  *d_diffs = T.up<double>(nullptr, (size_t)tot);
-  if (!*d_pts || !*d_diffs) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  {
-    DevTimer tm(SLIDE_MS_TRI_MATCH, true);
-    launch_tri_match(true, sdm, sxm, ntm, sdd, sxd, ntd, thr, dcnt, doff, *d_pts, *d_diffs, nullptr);
-  }
-  SL_HIP(hipGetLastError());
-  return SLIDE_OK;
-}
-}  // namespace
-extern "C" {
-
-int slide_clipper_dense_clique(const double* M_upper, int n, const double* u0, const slide_clipper_params_t* p,
-                               int32_t* nodes_out, int* n_nodes, double* u_out, double* score) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (n < 0 || !n_nodes) return SLIDE_ERR_INVALID;
-  slide_clipper_params_t P;
-  if (p) P = *p; else slide_clipper_default_params(&P);
-  Tmp T;
-  double* dM = T.up(M_upper, (size_t)n * n);
-  if (n > 0 && !dM) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  std::vector<int> nodes;
-  std::vector<double> u;
-  double sc = 0;
-  const int rc = dense_clique_device(dM, n, u0, P, nodes, u, sc);
-  if (rc != SLIDE_OK) return rc;
-  *n_nodes = (int)nodes.size();
-  for (size_t i = 0; i < nodes.size(); ++i) nodes_out[i] = nodes[i];
-  if (u_out) for (int i = 0; i < n; ++i) u_out[i] = u[i];
-  if (score) *score = sc;
-  return SLIDE_OK;
-}
-
-// host-side check of a caller's CSR (before anything touches the device): rowptr from 0 and non-decreasing, columns inside [0, n),
-// strictly ascending within a row and off the diagonal, every (i, j, v) with its (j, i, v)
-static int check_symmetric_csr(const int32_t* rowptr, const int32_t* col, const double* val, int n) {
-  auto bad = [](int row, const char* what) { g_last_error = "clipper CSR, row " + std::to_string(row) + ": " + what; return SLIDE_ERR_INVALID; };
-  if (rowptr[0] != 0) return bad(0, "rowptr[0] is not 0");
-  for (int i = 0; i < n; ++i)
-    if (rowptr[i + 1] < rowptr[i]) return bad(i, "rowptr decreases");
-  if (rowptr[n] > 0 && (!col || !val)) return bad(0, "col / val missing");
-  for (int i = 0; i < n; ++i)
-    for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-      if (col[k] < 0 || col[k] >= n) return bad(i, "a column outside [0, n)");
-      if (col[k] == i) return bad(i, "an entry on the diagonal");
-      if (k > rowptr[i] && col[k] <= col[k - 1]) return bad(i, "columns not strictly ascending");
-    }
-  for (int i = 0; i < n; ++i)
-    for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-      const int j = col[k];
-      const int32_t* lo = col + rowptr[j];
-      const int32_t* hi = col + rowptr[j + 1];
-      const int32_t* q = std::lower_bound(lo, hi, (int32_t)i);
-      if (q == hi || *q != i) return bad(i, "an entry without its transpose");
-      if (!(val[q - col] == val[k])) return bad(i, "an entry whose transpose holds another value");
-    }
-  return SLIDE_OK;
-}
-
-int slide_clipper_affinity_csr(const double* D1, int n1, const double* D2, int n2, int dim, const int32_t* A, int m, double sigma,
-                               double epsilon, double mindist, double affinityeps, int32_t* rowptr_out, int32_t* col_out, double* val_out,
-                               long long cap, long long* nnz) {
-  if (m < 0 || dim < 1 || n1 < 0 || n2 < 0 || cap < 0 || !nnz || !rowptr_out || (m > 0 && (!A || !D1 || !D2))) return SLIDE_ERR_INVALID;
-  *nnz = 0;
-  if (m > (1 << 30)) { g_last_error = "more than 2^30 associations"; return SLIDE_ERR_CAPACITY; }
-  int rc = check_associations(A, m, n1, n2);
-  if (rc != SLIDE_OK) return rc;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  rowptr_out[0] = 0;
-  if (m == 0) return SLIDE_OK;
-  Tmp T;
-  double* d1 = T.up(D1, (size_t)n1 * dim);
-  double* d2 = T.up(D2, (size_t)n2 * dim);
-  int32_t* dA = T.up(A, 2 * (size_t)m);
-  if (!d1 || !d2 || !dA) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  DevCsr S;
-  rc = csr_from_assoc_device(T, d1, d2, dim, dA, m, sigma, epsilon, mindist, affinityeps, S, cap);
-  if (S.nnz >= 0) {          // the scan finished: counts and pointers are valid
-    *nnz = S.nnz;
-    for (int i = 0; i <= m; ++i) rowptr_out[i] = S.h_ptr[i];
-  }
-  if (rc != SLIDE_OK) return rc;
-  if (S.nnz > 0) {
-    if (!col_out || !val_out) return SLIDE_ERR_INVALID;
-    SL_HIP(hipMemcpy(col_out, S.col, sizeof(int32_t) * (size_t)S.nnz, hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(val_out, S.val, sizeof(double) * (size_t)S.nnz, hipMemcpyDeviceToHost));
-  }
-  return SLIDE_OK;
-}
-
-static int clique_out(int rc, int n, const std::vector<int>& nodes, const std::vector<double>& u, double sc, int32_t* nodes_out, int* n_nodes,
-                      double* u_out, double* score) {
-  if (rc != SLIDE_OK) return rc;
-  *n_nodes = (int)nodes.size();
-  for (size_t i = 0; i < nodes.size(); ++i) nodes_out[i] = nodes[i];
-  if (u_out) for (int i = 0; i < n; ++i) u_out[i] = u[i];
-  if (score) *score = sc;
-  return SLIDE_OK;
-}
-
-int slide_clipper_dense_clique_csr(const int32_t* rowptr, const int32_t* col, const double* val, int n, const double* u0,
-                                   const slide_clipper_params_t* p, int32_t* nodes_out, int* n_nodes, double* u_out, double* score) {
-  if (n < 0 || !n_nodes || !rowptr || (n > 0 && !nodes_out)) return SLIDE_ERR_INVALID;
-  int rc = check_symmetric_csr(rowptr, col, val, n);
-  if (rc != SLIDE_OK) return rc;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  slide_clipper_params_t P;
-  if (p) P = *p; else slide_clipper_default_params(&P);
-  std::vector<int> nodes;
-  std::vector<double> u;
-  double sc = 0;
-  if (n > 0) {
-    Tmp T;
-    DevCsr S;
-    S.nnz = rowptr[n];
-    S.ptr = T.up(rowptr, (size_t)n + 1);
-    S.col = T.up(col, (size_t)S.nnz);
-    S.val = T.up(val, (size_t)S.nnz);
-    if (!S.ptr || !S.col || !S.val) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    g_dev_ms[SLIDE_MS_CLQ_NNZ] = (double)S.nnz;
-    rc = solve_csr_device(T, S, n, u0, P, nodes, u, sc);
-  }
-  return clique_out(rc, n, nodes, u, sc, nodes_out, n_nodes, u_out, score);
-}
-
-int slide_clipper_match(const double* D1, int n1, const double* D2, int n2, int dim, const int32_t* A, int m, const double* u0,
-                        const slide_clipper_params_t* p, int32_t* nodes_out, int* n_nodes, double* u_out, double* score) {
-  if (m < 0 || dim < 1 || n1 < 0 || n2 < 0 || !n_nodes || (m > 0 && (!A || !D1 || !D2 || !nodes_out))) return SLIDE_ERR_INVALID;
-  if (m > (1 << 30)) { g_last_error = "more than 2^30 associations"; return SLIDE_ERR_CAPACITY; }
-  int rc = check_associations(A, m, n1, n2);
-  if (rc != SLIDE_OK) return rc;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  slide_clipper_params_t P;
-  if (p) P = *p; else slide_clipper_default_params(&P);
-  std::vector<int> nodes;
-  std::vector<double> u;
-  double sc = 0;
-  if (m > 0) {
-    Tmp T;
-    double* d1 = T.up(D1, (size_t)n1 * dim);
-    double* d2 = T.up(D2, (size_t)n2 * dim);
-    int32_t* dA = T.up(A, 2 * (size_t)m);
-    if (!d1 || !d2 || !dA) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    DevCsr S;
-    rc = csr_from_assoc_device(T, d1, d2, dim, dA, m, P.sigma, P.epsilon, P.mindist, P.affinityeps, S);
-    if (rc == SLIDE_OK) rc = solve_csr_device(T, S, m, u0, P, nodes, u, sc);
-  }
-  return clique_out(rc, m, nodes, u, sc, nodes_out, n_nodes, u_out, score);
-}
-
-int slide_last_device_ms(int what, double* out) {
-  if (what < 0 || what >= SLIDE_MS_COUNT || !out) return SLIDE_ERR_INVALID;
-  *out = g_dev_ms[what];
-  return SLIDE_OK;
-}
-void slide_clipper_last_solve_info(int* n_workgroups, double* grad_evals) {
-  if (n_workgroups) *n_workgroups = g_clq_last_wgs;
-  if (grad_evals) *grad_evals = g_clq_last_evals;
-}
-
-// Several dense-clique problems at once (the robot pairs of a multi-robot job: 28 at eight robots; semantic_clipper.cpp:227-235
-// once per pair): the CSR builds are issued one after the other, the projected-gradient solves run as ONE launch, a persistent
-// workgroup per job.  Job j: M_upper[j] (n[j] x n[j], row-major, upper triangle used), u0[j] or NULL (the default start);
-// nodes_out[j] (>= n[j] ints), u_out[j] (n[j] doubles, may be NULL), n_nodes[j], score[j].  Results equal n_jobs single calls.
-int slide_clipper_dense_clique_batch(int n_jobs, const double* const* M_upper, const int* n, const double* const* u0, const slide_clipper_params_t* p,
-                                     int32_t* const* nodes_out, int* n_nodes, double* const* u_out, double* score) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (n_jobs < 0 || (n_jobs > 0 && (!M_upper || !n || !nodes_out || !n_nodes))) return SLIDE_ERR_INVALID;
-  slide_clipper_params_t P;
-  if (p) P = *p; else slide_clipper_default_params(&P);
-  Tmp T;
-  std::vector<ClqSolve> jobs(n_jobs);
-  std::vector<double*> d_work(n_jobs, nullptr), d_out(n_jobs, nullptr);
-  for (int j = 0; j < n_jobs; ++j) {
-    ClqSolve& A = jobs[j];
-    A = ClqSolve{};
-    const int nj = n[j];
-    if (nj < 0) return SLIDE_ERR_INVALID;
-    n_nodes[j] = 0;
-    if (score) score[j] = 0.0;
-    if (nj == 0) continue;
-    double* dM = T.up(M_upper[j], (size_t)nj * nj);
-    std::vector<double> start(nj);
-    if (u0 && u0[j]) start.assign(u0[j], u0[j] + nj); else default_u0(start);
-    int* d_cnt = T.up<int>(nullptr, nj);
-    int* d_ptr = T.up<int>(nullptr, (size_t)nj + 1);
-    double* d_u0 = T.up(start.data(), nj);
-    d_work[j] = T.up<double>(nullptr, 6 * (size_t)nj);
-    d_out[j] = T.up<double>(nullptr, 4);
-    if (!dM || !d_cnt || !d_ptr || !d_u0 || !d_work[j] || !d_out[j]) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    launch_clq_csr_count(dM, nj, d_cnt, nullptr);
-    std::vector<int> cnt(nj), ptr((size_t)nj + 1, 0);
-    SL_HIP(hipMemcpy(cnt.data(), d_cnt, sizeof(int) * nj, hipMemcpyDeviceToHost));
-    long long nnz = 0;
-    for (int i = 0; i < nj; ++i) { ptr[i] = (int)nnz; nnz += cnt[i]; }
-    if (nnz > INT32_MAX) { g_last_error = "affinity matrix has more than 2^31 non-zeros"; return SLIDE_ERR_CAPACITY; }
-    ptr[nj] = (int)nnz;
-    SL_HIP(hipMemcpy(d_ptr, ptr.data(), sizeof(int) * ((size_t)nj + 1), hipMemcpyHostToDevice));
-    int* d_col = T.up<int>(nullptr, (size_t)std::max<long long>(nnz, 1));
-    double* d_val = T.up<double>(nullptr, (size_t)std::max<long long>(nnz, 1));
-    if (!d_col || !d_val) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-    launch_clq_csr_fill(dM, nj, d_ptr, d_col, d_val, nullptr);
-    A.rowptr = d_ptr; A.col = d_col; A.val = d_val; A.n = nj; A.u0 = d_u0;
-    double* w = d_work[j];
-    A.u = w; A.unew = w + nj; A.g = w + 2 * (size_t)nj; A.gnew = w + 3 * (size_t)nj; A.Mu = w + 4 * (size_t)nj; A.Cu = w + 5 * (size_t)nj;
-    A.tol_u = P.tol_u; A.tol_F = P.tol_F; A.beta = P.beta; A.eps = P.eps;
-    A.maxin = P.maxiniters; A.maxol = P.maxoliters; A.maxls = P.maxlsiters; A.rescale = P.rescale_u0;
-    A.out = d_out[j];
-  }
-  if (n_jobs > 0) {
-    ClqSolve* d_jobs = T.up(jobs.data(), (size_t)n_jobs);
-    if (!d_jobs) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    launch_clq_solve_batch(d_jobs, n_jobs, nullptr);
-    SL_HIP(hipDeviceSynchronize());
-    SL_HIP(hipGetLastError());
-  }
-  for (int j = 0; j < n_jobs; ++j) {
-    const int nj = n[j];
-    if (nj == 0) continue;
-    double out4[4];
-    std::vector<double> u(nj);
-    SL_HIP(hipMemcpy(out4, d_out[j], sizeof(out4), hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(u.data(), d_work[j], sizeof(double) * nj, hipMemcpyDeviceToHost));
-    const std::vector<int> nodes = top_entries(u, (int)std::round(out4[0]));
-    n_nodes[j] = (int)nodes.size();
-    for (size_t i = 0; i < nodes.size(); ++i) nodes_out[j][i] = nodes[i];
-    if (u_out && u_out[j]) for (int i = 0; i < nj; ++i) u_out[j][i] = u[i];
-    if (score) score[j] = out4[0];
-  }
-  return SLIDE_OK;
-}
-
-int slide_match_triangles(const double* tri_model, int ntm, const double* tri_data, int ntd, double threshold, double* pts_out,
-                          double* diffs_out, int cap_pairs, int* n_pairs) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (!n_pairs || ntm < 0 || ntd < 0) return SLIDE_ERR_INVALID;
-  Tmp T;
-  double *dp = nullptr, *dd = nullptr;
-  long long np = 0;
-  const int rc = match_triangles_device(T, tri_model, ntm, tri_data, ntd, threshold, &dp, &dd, &np);
-  if (rc != SLIDE_OK) return rc;
-  if (np > 2147483647LL) { g_last_error = "more than 2^31 matched triangle pairs"; return SLIDE_ERR_CAPACITY; }
-  *n_pairs = (int)np;
-  const long long w = std::min<long long>(np, cap_pairs);
-  if (w > 0 && pts_out) SL_HIP(hipMemcpy(pts_out, dp, sizeof(double) * 12 * (size_t)w, hipMemcpyDeviceToHost));
-  if (w > 0 && diffs_out) SL_HIP(hipMemcpy(diffs_out, dd, sizeof(double) * (size_t)w, hipMemcpyDeviceToHost));
-  return SLIDE_OK;
-}
-
-int slide_estimate_tf2d(const double* a_xy, const double* b_xy, int n, double tf3[9]) {
-  if (n <= 0) return SLIDE_ERR_INVALID;
-  estimate_tf2d(a_xy, b_xy, n, tf3);
-  return SLIDE_OK;
-}
-
-int slide_semantic_clipper(const double* tri_model, int ntm, const double* tri_data, int ntd, const slide_clipper_params_t* p,
-                           int min_num_pairs, double matching_threshold, const double* u0, int n_u0, double tf16[16], int counts[2],
-                           int32_t* inliers_out, int cap_inliers, int* found) {
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  if (!found || !counts) return SLIDE_ERR_INVALID;
-  slide_clipper_params_t P;
-  if (p) P = *p; else slide_clipper_default_params(&P);
-  for (int i = 0; i < 16; ++i) tf16[i] = (i % 5 == 0) ? 1.0 : 0.0;
-  *found = 0;
-  counts[0] = counts[1] = 0;
-  Tmp T;
-  double *dp = nullptr, *dd = nullptr;
-  long long np = 0;
-  int rc = match_triangles_device(T, tri_model, ntm, tri_data, ntd, matching_threshold, &dp, &dd, &np);
-  if (rc != SLIDE_OK) return rc;
-  const long long m = 3 * np;
-  if (m > (1 << 30)) { g_last_error = "more than 2^30 putative associations"; return SLIDE_ERR_CAPACITY; }
-  counts[0] = (int)m;
-  if (m == 0) return SLIDE_OK;
-  if (u0 && n_u0 != (int)m) { g_last_error = "u0 length does not match the number of putative associations"; return SLIDE_ERR_INVALID; }
-  // matched points back to the host (inlier gather, estimate_tf), split model / data for the affinity kernel
-  std::vector<double> pts(4 * (size_t)m);
-  SL_HIP(hipMemcpy(pts.data(), dp, sizeof(double) * 4 * (size_t)m, hipMemcpyDeviceToHost));
-  std::vector<double> D1(2 * (size_t)m), D2(2 * (size_t)m);
-  std::vector<int32_t> A(2 * (size_t)m);
-  for (long long i = 0; i < m; ++i) {
-    D1[2 * i] = pts[4 * i]; D1[2 * i + 1] = pts[4 * i + 1]; D2[2 * i] = pts[4 * i + 2]; D2[2 * i + 1] = pts[4 * i + 3];
-    A[2 * i] = (int32_t)i; A[2 * i + 1] = (int32_t)i;          // identity association list, semantic_clipper.cpp:207-211
-  }
-  double* d1 = T.up(D1.data(), D1.size());
-  double* d2 = T.up(D2.data(), D2.size());
-  int32_t* dA = T.up(A.data(), A.size());
-  if (!d1 || !d2 || !dA) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  // the affinity matrix as CSR straight from the associations (M_ = M.sparseView(), clipper.cpp:64): no m x m matrix, so no m is
-  // refused for its dense size; the CSR is the one k_clipper_affinity + k_clq_csr gave, bit for bit
-  DevCsr S;
-  rc = csr_from_assoc_device(T, d1, d2, 2, dA, (int)m, P.sigma, P.epsilon, P.mindist, P.affinityeps, S);
-  if (rc != SLIDE_OK) return rc;
-  std::vector<int> nodes;
-  std::vector<double> u;
-  double sc = 0;
-  rc = solve_csr_device(T, S, (int)m, u0, P, nodes, u, sc);
-  if (rc != SLIDE_OK) return rc;
-  counts[1] = (int)nodes.size();
-  if (inliers_out) for (size_t i = 0; i < nodes.size() && (int)i < cap_inliers; ++i) inliers_out[i] = nodes[i];
-  if ((int)nodes.size() < min_num_pairs) return SLIDE_OK;
-  std::vector<double> a(2 * nodes.size()), b(2 * nodes.size());
-  for (size_t k = 0; k < nodes.size(); ++k) {
-    const int i = nodes[k];
-    a[2 * k] = D1[2 * i]; a[2 * k + 1] = D1[2 * i + 1]; b[2 * k] = D2[2 * i]; b[2 * k + 1] = D2[2 * i + 1];
-  }
-  double tf3[9];
-  estimate_tf2d(a.data(), b.data(), (int)nodes.size(), tf3);
-  const double yaw = std::atan2(tf3[3], tf3[0]);
-  tf16[0] = std::cos(yaw); tf16[1] = -std::sin(yaw); tf16[4] = std::sin(yaw); tf16[5] = std::cos(yaw);
-  tf16[3] = tf3[2]; tf16[7] = tf3[5];
-  *found = 1;
-  return SLIDE_OK;
-}
 
 // GetIndexClosestPoseMstPair sloam.cpp:428-440 (strict '<': first index wins ties)
 int slide_closest_stamp(const int64_t* sec, const int64_t* nsec, int n, int64_t qsec, int64_t qnsec, int* idx, double* diff) {
@@ -2374,23 +895,14 @@ int slide_loop_candidate_idx(const float* cloud_xyz, int n, double max_dist, uin
   *found = 0;
   if (n < 50) return SLIDE_OK;                                   // :163
   if (pose_idx >= (uint64_t)n) return SLIDE_ERR_INVALID;         // (the reference would index out of bounds)
-  const float qx = cloud_xyz[3 * pose_idx], qy = cloud_xyz[3 * pose_idx + 1], qz = cloud_xyz[3 * pose_idx + 2];
-  const float r2 = (float)(max_dist * max_dist);                 // pcl radiusSearch hands radius^2 to FLANN as float
   // FLANN returns the neighbours nearest first; the first one that qualifies wins = the nearest qualifying one
   // (equidistant neighbours: by index, as in the K-NN gate)
   bool have = false;
   float bd = 0.f;
   uint64_t bi = 0;
-  for (int i = 0; i < n; ++i) {
-    const float dx = cloud_xyz[3 * i] - qx, dy = cloud_xyz[3 * i + 1] - qy, dz = cloud_xyz[3 * i + 2] - qz;
-    float d2 = dx * dx;
-    d2 += dy * dy;
-    d2 += dz * dz;
-    if (!(d2 < r2)) continue;
-    // "nnIdx != poseIdx && poseIdx - nnIdx > at_least_num_of_poses_old" with poseIdx a size_t: a LATER pose wraps around and passes
-    if ((uint64_t)i == pose_idx || !(pose_idx - (uint64_t)i > at_least_num_of_poses_old)) continue;
-    if (!have || d2 < bd) { have = true; bd = d2; bi = (uint64_t)i; }
-  }
+  loop_candidates(cloud_xyz, n, max_dist, pose_idx, at_least_num_of_poses_old, [&](float d2, uint64_t i) {
+    if (!have || d2 < bd) { have = true; bd = d2; bi = i; }
+  });
   if (have) { *candidate_idx = bi; *found = 1; }
   return SLIDE_OK;
 }
@@ -2402,18 +914,8 @@ int slide_loop_candidate_list(const float* cloud_xyz, int n, double max_dist, ui
   *n_found = 0;
   if (n < 50) return SLIDE_OK;                                   // :163
   if (pose_idx >= (uint64_t)n) return SLIDE_ERR_INVALID;
-  const float qx = cloud_xyz[3 * pose_idx], qy = cloud_xyz[3 * pose_idx + 1], qz = cloud_xyz[3 * pose_idx + 2];
-  const float r2 = (float)(max_dist * max_dist);
   std::vector<std::pair<float, uint64_t>> hits;                  // (float32 squared distance, index): the sibling's order is this pair's order
-  for (int i = 0; i < n; ++i) {
-    const float dx = cloud_xyz[3 * i] - qx, dy = cloud_xyz[3 * i + 1] - qy, dz = cloud_xyz[3 * i + 2] - qz;
-    float d2 = dx * dx;
-    d2 += dy * dy;
-    d2 += dz * dz;
-    if (!(d2 < r2)) continue;
-    if ((uint64_t)i == pose_idx || !(pose_idx - (uint64_t)i > at_least_num_of_poses_old)) continue;
-    hits.emplace_back(d2, (uint64_t)i);
-  }
+  loop_candidates(cloud_xyz, n, max_dist, pose_idx, at_least_num_of_poses_old, [&](float d2, uint64_t i) { hits.emplace_back(d2, i); });
   std::stable_sort(hits.begin(), hits.end(), [](const std::pair<float, uint64_t>& a, const std::pair<float, uint64_t>& b) { return a.first < b.first; });
   *n_found = (int)hits.size();
   for (size_t i = 0; i < hits.size() && (int)i < cap; ++i) cand_idx[i] = hits[i].second;
@@ -2426,823 +928,6 @@ int slide_delaunay_2d(const double* xy, int n, int32_t* tri_out, int cap, int* n
   *n_tri = (int)t.size();
   for (size_t i = 0; i < t.size() && (int)i < cap; ++i)
     for (int k = 0; k < 3; ++k) tri_out[3 * i + k] = t[i][k];
-  return SLIDE_OK;
-}
-
-int slide_run_semantic_clipper(const double* ref7, int nr, const double* qry7, int nq, double sigma, double epsilon,
-                               int min_num_pairs, double matching_threshold, const double* u0, int n_u0, double tf16[16], int counts[2],
-                               int* found) {
-  if (nr < 0 || nq < 0) return SLIDE_ERR_INVALID;
-  auto tris = [](const double* rows7, int n) {
-    std::vector<double> xy(2 * (size_t)std::max(n, 1));
-    for (int i = 0; i < n; ++i) { xy[2 * i] = rows7[7 * (size_t)i + 1]; xy[2 * i + 1] = rows7[7 * (size_t)i + 2]; }   // semantic_clipper.cpp:150-165
-    const std::vector<std::array<int32_t, 3>> t = delaunay::triangulate(xy.data(), n);
-    std::vector<double> out(6 * t.size());
-    for (size_t k = 0; k < t.size(); ++k)
-      for (int v = 0; v < 3; ++v) { out[6 * k + 2 * v] = xy[2 * t[k][v]]; out[6 * k + 2 * v + 1] = xy[2 * t[k][v] + 1]; }
-    return out;
-  };
-  const std::vector<double> tm = tris(ref7, nr), td = tris(qry7, nq);
-  slide_clipper_params_t P;
-  slide_clipper_default_params(&P);
-  P.sigma = sigma;
-  P.epsilon = epsilon;
-  return slide_semantic_clipper(tm.data(), (int)(tm.size() / 6), td.data(), (int)(td.size() / 6), &P, min_num_pairs, matching_threshold,
-                                u0, n_u0, tf16, counts, nullptr, 0, found);
-}
-
-void slide_slidegraph_default_params(slide_slidegraph_params_t* p) {      // place_recognition.cpp:65-75
-  p->sigma = 0.1; p->epsilon = 0.1; p->num_inliers_threshold = 10; p->matching_threshold = 0.1; p->min_num_map_objects_to_start = 20;
-}
-}  // extern "C"
-namespace {
-// ---- PlaceRecognition::findInterLoopClosureWithClipper place_recognition.cpp:541-629 for a list of map pairs ----------------------------
-struct MapView { const double* rows7; int n; };
-struct MapTris {                       // one map, filtered (:584, :601) and triangulated ONCE however many pairs name it
-  bool filtered = false, triangulated = false;
-  std::vector<double> xy;              // the kept rows' (x, y)
-  std::vector<double> tri;             // 6 doubles per Delaunay triangle (semantic_clipper.cpp:150-165)
-  int kept = 0, ntri = 0, tri0 = -1;   // tri0: first triangle in the prepared arrays of all maps
-};
-void identity16(double* tf) { for (int i = 0; i < 16; ++i) tf[i] = (i % 5 == 0) ? 1.0 : 0.0; }
-
-// Outputs are initialised by the caller; every pair is evaluated by itself.  Stages: host filter + gate + Delaunay; ONE k_tri_prepare;
-// k_tri_match_seg count, segmented scan, read-back 1 (matched pairs per map pair); k_tri_match_seg emit straight into P1 / P2;
-// k_affinity_csr_seg count, segmented scan into per-pair row pointers, read-back 2 (non-zeros per pair); emit; ONE k_clq_solve_b for
-// the pairs below the cooperative threshold; read-back 3 (out4, u, P1, P2 of all pairs, one buffer); the pairs at or above the
-// threshold one after another through solve_csr_device on their slice; rounding, estimate_tf and the inverse on the host.
-int inter_loop_closures_clipper(const std::vector<MapView>& maps, const int32_t* pairs, int n_pairs, const slide_slidegraph_params_t& G,
-                                const double* const* u0, const int* n_u0, double* tf16n, int32_t* counts4n, int32_t* found,
-                                int32_t* status) {
-  std::vector<MapTris> M(maps.size());
-  auto filter = [&](int i) {
-    MapTris& m = M[i];
-    if (m.filtered) return;
-    m.filtered = true;
-    for (int r = 0; r < maps[i].n; ++r) {
-      const double x = maps[i].rows7[7 * (size_t)r + 1], y = maps[i].rows7[7 * (size_t)r + 2];
-      if (x == 0.0 && y == 0.0) continue;
-      m.xy.push_back(x); m.xy.push_back(y);
-    }
-    m.kept = (int)(m.xy.size() / 2);
-  };
-  auto triangulate = [&](int i) {
-    MapTris& m = M[i];
-    if (m.triangulated) return;
-    m.triangulated = true;
-    const std::vector<std::array<int32_t, 3>> t = delaunay::triangulate(m.xy.data(), m.kept);
-    m.tri.resize(6 * t.size());
-    for (size_t k = 0; k < t.size(); ++k)
-      for (int v = 0; v < 3; ++v) { m.tri[6 * k + 2 * v] = m.xy[2 * t[k][v]]; m.tri[6 * k + 2 * v + 1] = m.xy[2 * t[k][v] + 1]; }
-    m.ntri = (int)t.size();
-  };
-  auto fail = [&](int k, int rc) { if (status) status[k] = rc; };
-  // the segments: pairs that pass the gate (:618) and have triangles on both sides
-  std::vector<int> seg_pair;
-  std::vector<int> rowoff(1, 0);
-  for (int k = 0; k < n_pairs; ++k) {
-    const int a = pairs[2 * k], b = pairs[2 * k + 1];
-    filter(a); filter(b);
-    counts4n[4 * k] = M[a].kept; counts4n[4 * k + 1] = M[b].kept;
-    if (M[a].kept < G.min_num_map_objects_to_start || M[b].kept < G.min_num_map_objects_to_start) continue;
-    triangulate(a); triangulate(b);
-    if (M[a].ntri == 0 || M[b].ntri == 0) continue;
-    if ((long long)rowoff.back() + M[a].ntri > INT32_MAX) { fail(k, SLIDE_ERR_CAPACITY); continue; }
-    seg_pair.push_back(k);
-    rowoff.push_back(rowoff.back() + M[a].ntri);
-  }
-  const int n_seg = (int)seg_pair.size(), n_rows = rowoff.back();
-  if (n_seg == 0) return SLIDE_OK;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  slide_clipper_params_t P;
-  slide_clipper_default_params(&P);
-  P.sigma = G.sigma;
-  P.epsilon = G.epsilon;
-  // the triangles of every map a segment names, one after the other
-  std::vector<double> tri_all;
-  std::vector<TriSeg> segs(n_seg);
-  for (int s = 0; s < n_seg; ++s) {
-    const int k = seg_pair[s];
-    for (int side = 0; side < 2; ++side) {
-      MapTris& m = M[pairs[2 * k + side]];
-      if (m.tri0 >= 0) continue;
-      if (tri_all.size() / 6 + (size_t)m.ntri > (size_t)INT32_MAX) { g_last_error = "more than 2^31 triangles in the list's maps"; return SLIDE_ERR_CAPACITY; }
-      m.tri0 = (int)(tri_all.size() / 6);
-      tri_all.insert(tri_all.end(), m.tri.begin(), m.tri.end());
-    }
-    segs[s] = TriSeg{M[pairs[2 * k]].tri0, M[pairs[2 * k + 1]].tri0, M[pairs[2 * k + 1]].ntri};
-  }
-  const int n_tri = (int)(tri_all.size() / 6);
-  Tmp T;
-  double* d_tri = T.up(tri_all.data(), tri_all.size());
-  double* d_sd = T.up<double>(nullptr, 3 * (size_t)n_tri);
-  double* d_sx = T.up<double>(nullptr, 6 * (size_t)n_tri);
-  int* d_rowoff = T.up(rowoff.data(), rowoff.size());
-  TriSeg* d_segs = T.up(segs.data(), segs.size());
-  int* d_tcnt = T.up<int>(nullptr, n_rows);
-  long long* d_toff = T.up<long long>(nullptr, n_rows);
-  long long* d_tot = T.up<long long>(nullptr, n_seg);
-  if (!d_tri || !d_sd || !d_sx || !d_rowoff || !d_segs || !d_tcnt || !d_toff || !d_tot) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  launch_tri_prepare(d_tri, n_tri, d_sd, d_sx, nullptr);
-  launch_tri_match_seg(false, d_sd, d_sx, d_rowoff, d_segs, n_seg, n_rows, G.matching_threshold, d_tcnt, nullptr, nullptr, nullptr, nullptr, nullptr);
-  launch_seg_scan64(d_tcnt, d_rowoff, n_seg, d_toff, d_tot, nullptr);
-  SL_HIP(hipGetLastError());
-  std::vector<long long> tot(n_seg);
-  SL_HIP(hipMemcpy(tot.data(), d_tot, sizeof(long long) * n_seg, hipMemcpyDeviceToHost));                 // read-back 1
-  // associations per pair; a pair's own faults drop it here (base < 0: nothing of it is emitted)
-  std::vector<long long> base(n_seg, -1);
-  std::vector<int> aoff(n_seg + 1, 0);
-  for (int s = 0; s < n_seg; ++s) {
-    const int k = seg_pair[s];
-    aoff[s + 1] = aoff[s];
-    if (tot[s] > (1LL << 30) / 3 || (long long)aoff[s] + 3 * tot[s] > (1LL << 30)) { fail(k, SLIDE_ERR_CAPACITY); continue; }
-    const int m = (int)(3 * tot[s]);
-    counts4n[4 * k + 2] = m;
-    if (m == 0) continue;
-    if (u0 && u0[k] && n_u0[k] != m) { fail(k, SLIDE_ERR_INVALID); continue; }
-    base[s] = aoff[s] / 3;
-    aoff[s + 1] = aoff[s] + m;
-  }
-  const int n_assoc = aoff[n_seg];
-  if (n_assoc == 0) return SLIDE_OK;
-  // one result buffer for the one read-back at the end: [out4 per segment | u | P1 | P2]
-  const size_t res_len = 4 * (size_t)n_seg + 5 * (size_t)n_assoc;
-  double* d_res = T.up<double>(nullptr, res_len);
-  long long* d_base = T.up(base.data(), base.size());
-  int* d_aoff = T.up(aoff.data(), aoff.size());
-  int* d_rcnt = T.up<int>(nullptr, n_assoc);
-  int* d_rptr = T.up<int>(nullptr, (size_t)n_assoc + n_seg);
-  if (!d_res || !d_base || !d_aoff || !d_rcnt || !d_rptr) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  double* d_out = d_res;
-  double* d_u = d_res + 4 * (size_t)n_seg;
-  double* d_p1 = d_u + n_assoc;
-  double* d_p2 = d_p1 + 2 * (size_t)n_assoc;
-  SL_HIP(hipMemsetAsync(d_res, 0, (4 * (size_t)n_seg + (size_t)n_assoc) * sizeof(double), nullptr));
-  launch_tri_match_seg(true, d_sd, d_sx, d_rowoff, d_segs, n_seg, n_rows, G.matching_threshold, nullptr, d_toff, d_base, d_p1, d_p2, nullptr);
-  launch_affinity_csr_seg(false, d_p1, d_p2, d_aoff, n_seg, n_assoc, P.sigma, P.epsilon, P.mindist, P.affinityeps, d_rcnt, nullptr, nullptr, nullptr,
-                          nullptr, nullptr);
-  launch_seg_scan_rowptr(d_rcnt, d_aoff, n_seg, d_rptr, d_tot, nullptr);
-  SL_HIP(hipGetLastError());
-  SL_HIP(hipMemcpy(tot.data(), d_tot, sizeof(long long) * n_seg, hipMemcpyDeviceToHost));                 // read-back 2
-  std::vector<long long> nnz0(n_seg, -1);
-  long long nnz_all = 0;
-  for (int s = 0; s < n_seg; ++s) {
-    if (aoff[s + 1] == aoff[s]) continue;
-    if (tot[s] > INT32_MAX) { fail(seg_pair[s], SLIDE_ERR_CAPACITY); continue; }      // ClqSolve::rowptr is per problem, 32 bits
-    nnz0[s] = nnz_all;
-    nnz_all += tot[s];
-  }
-  long long* d_nnz0 = T.up(nnz0.data(), nnz0.size());
-  int* d_col = T.up<int>(nullptr, (size_t)std::max<long long>(nnz_all, 1));
-  double* d_val = T.up<double>(nullptr, (size_t)std::max<long long>(nnz_all, 1));
-  if (!d_nnz0 || !d_col || !d_val) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  launch_affinity_csr_seg(true, d_p1, d_p2, d_aoff, n_seg, n_assoc, P.sigma, P.epsilon, P.mindist, P.affinityeps, nullptr, d_rptr, d_nnz0, d_col, d_val,
-                          nullptr);
-  // the solves: one launch for every pair below the single call's cooperative threshold
-  constexpr int COOP_N = 1024;
-  std::vector<double> start(n_assoc, 0.0);
-  std::vector<ClqSolve> jobs;
-  double* d_work = T.up<double>(nullptr, 6 * (size_t)n_assoc);
-  if (!d_work) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  for (int s = 0; s < n_seg; ++s) {
-    const int m = aoff[s + 1] - aoff[s], k = seg_pair[s];
-    if (m == 0 || nnz0[s] < 0 || m >= COOP_N) continue;
-    if (u0 && u0[k]) std::copy(u0[k], u0[k] + m, start.begin() + aoff[s]);
-    else { std::vector<double> d(m); default_u0(d); std::copy(d.begin(), d.end(), start.begin() + aoff[s]); }
-    ClqSolve A{};
-    A.rowptr = d_rptr + aoff[s] + s; A.col = d_col + nnz0[s]; A.val = d_val + nnz0[s]; A.n = m;
-    double* w = d_work + 6 * (size_t)aoff[s];
-    A.u = w; A.unew = w + m; A.g = w + 2 * (size_t)m; A.gnew = w + 3 * (size_t)m; A.Mu = w + 4 * (size_t)m; A.Cu = w + 5 * (size_t)m;
-    A.tol_u = P.tol_u; A.tol_F = P.tol_F; A.beta = P.beta; A.eps = P.eps;
-    A.maxin = P.maxiniters; A.maxol = P.maxoliters; A.maxls = P.maxlsiters; A.rescale = P.rescale_u0;
-    A.out = d_out + 4 * (size_t)s;
-    jobs.push_back(A);
-  }
-  if (!jobs.empty()) {
-    double* d_start = T.up(start.data(), start.size());
-    if (!d_start) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    for (ClqSolve& A : jobs) A.u0 = d_start + (A.u - d_work) / 6;       // (A.u = d_work + 6 aoff[s]: the start weights of its pair)
-    ClqSolve* d_jobs = T.up(jobs.data(), jobs.size());
-    if (!d_jobs) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    launch_clq_solve_batch(d_jobs, (int)jobs.size(), nullptr);
-    launch_clq_pack_u(d_work, d_aoff, n_seg, n_assoc, d_u, nullptr);
-  }
-  SL_HIP(hipGetLastError());
-  std::vector<double> res(res_len);
-  SL_HIP(hipMemcpy(res.data(), d_res, sizeof(double) * res_len, hipMemcpyDeviceToHost));                  // read-back 3
-  const double* h_u = res.data() + 4 * (size_t)n_seg;
-  const double* h_p1 = h_u + n_assoc;
-  const double* h_p2 = h_p1 + 2 * (size_t)n_assoc;
-  for (int s = 0; s < n_seg; ++s) {
-    const int m = aoff[s + 1] - aoff[s], k = seg_pair[s];
-    if (m == 0 || nnz0[s] < 0) continue;
-    std::vector<int> nodes;
-    if (m >= COOP_N) {        // the single call's route for one large problem, on this pair's slice of the shared buffers
-      DevCsr S;
-      S.ptr = d_rptr + aoff[s] + s; S.col = d_col + nnz0[s]; S.val = d_val + nnz0[s]; S.nnz = tot[s];
-      std::vector<double> u;
-      double sc = 0;
-      const int rc = solve_csr_device(T, S, m, (u0 && u0[k]) ? u0[k] : nullptr, P, nodes, u, sc);
-      if (rc != SLIDE_OK) return rc;
-    } else {
-      const std::vector<double> u(h_u + aoff[s], h_u + aoff[s + 1]);
-      nodes = top_entries(u, (int)std::round(res[4 * (size_t)s]));
-    }
-    counts4n[4 * k + 3] = (int)nodes.size();
-    if ((int)nodes.size() < G.num_inliers_threshold) continue;
-    std::vector<double> a(2 * nodes.size()), b(2 * nodes.size());
-    for (size_t i = 0; i < nodes.size(); ++i) {
-      const size_t j = (size_t)aoff[s] + nodes[i];
-      a[2 * i] = h_p1[2 * j]; a[2 * i + 1] = h_p1[2 * j + 1]; b[2 * i] = h_p2[2 * j]; b[2 * i + 1] = h_p2[2 * j + 1];
-    }
-    double tf3[9];
-    estimate_tf2d(a.data(), b.data(), (int)nodes.size(), tf3);
-    // run_semantic_clipper's 4x4 (yaw + xy, semantic_clipper.cpp:255-268) and its inverse (place_recognition.cpp:624): R^T, -R^T t
-    const double yaw = std::atan2(tf3[3], tf3[0]), c = std::cos(yaw), sn = std::sin(yaw), tx = tf3[2], ty = tf3[5];
-    double* tf = tf16n + 16 * (size_t)k;
-    tf[0] = c; tf[1] = sn; tf[4] = -sn; tf[5] = c;
-    tf[3] = -(c * tx + sn * ty); tf[7] = -(-sn * tx + c * ty);
-    found[k] = 1;
-  }
-  return SLIDE_OK;
-}
-}  // namespace
-extern "C" {
-
-int slide_find_inter_loop_closures_clipper(const double* maps7, const int32_t* map_off, int n_maps, const int32_t* pairs, int n_pairs,
-                                           const slide_slidegraph_params_t* p, const double* const* u0, const int* n_u0, double* tf16n,
-                                           int32_t* counts4n, int32_t* found, int32_t* status) {
-  if (n_pairs < 0 || n_maps < 0) return SLIDE_ERR_INVALID;
-  if (n_pairs == 0) return SLIDE_OK;
-  if (!map_off || !pairs || !tf16n || !counts4n || !found) { g_last_error = "find_inter_loop_closures_clipper: a needed pointer is NULL"; return SLIDE_ERR_INVALID; }
-  if (n_maps > 0 && map_off[0] < 0) { g_last_error = "find_inter_loop_closures_clipper: map_off[0] is negative"; return SLIDE_ERR_INVALID; }
-  for (int i = 0; i < n_maps; ++i)
-    if (map_off[i + 1] < map_off[i]) { g_last_error = "find_inter_loop_closures_clipper: map_off decreases at map " + std::to_string(i); return SLIDE_ERR_INVALID; }
-  if (n_maps > 0 && map_off[n_maps] > map_off[0] && !maps7) { g_last_error = "find_inter_loop_closures_clipper: maps7 is NULL"; return SLIDE_ERR_INVALID; }
-  for (int k = 0; k < n_pairs; ++k) {
-    if (pairs[2 * k] < 0 || pairs[2 * k] >= n_maps || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= n_maps) {
-      g_last_error = "find_inter_loop_closures_clipper: pair " + std::to_string(k) + " names a map outside [0, n_maps)";
-      return SLIDE_ERR_INVALID;
-    }
-    if (u0 && u0[k] && !n_u0) { g_last_error = "find_inter_loop_closures_clipper: u0 given without n_u0"; return SLIDE_ERR_INVALID; }
-  }
-  slide_slidegraph_params_t G;
-  if (p) G = *p; else slide_slidegraph_default_params(&G);
-  std::vector<MapView> maps(n_maps);
-  for (int i = 0; i < n_maps; ++i) maps[i] = MapView{maps7 ? maps7 + 7 * (size_t)map_off[i] : nullptr, map_off[i + 1] - map_off[i]};
-  for (int k = 0; k < n_pairs; ++k) {
-    identity16(tf16n + 16 * (size_t)k);
-    for (int c = 0; c < 4; ++c) counts4n[4 * k + c] = 0;
-    found[k] = 0;
-    if (status) status[k] = SLIDE_OK;
-  }
-  return inter_loop_closures_clipper(maps, pairs, n_pairs, G, u0, n_u0, tf16n, counts4n, found, status);
-}
-
-int slide_find_inter_loop_closure_clipper(const double* ref7, int nr, const double* qry7, int nq, const slide_slidegraph_params_t* p,
-                                          const double* u0, int n_u0, double tf16[16], int counts[4], int* found) {
-  if (nr < 0 || nq < 0 || !tf16 || !counts || !found || (nr > 0 && !ref7) || (nq > 0 && !qry7)) return SLIDE_ERR_INVALID;
-  slide_slidegraph_params_t G;
-  if (p) G = *p; else slide_slidegraph_default_params(&G);
-  const std::vector<MapView> maps = {MapView{ref7, nr}, MapView{qry7, nq}};
-  const int32_t pair[2] = {0, 1};
-  identity16(tf16);
-  int32_t c4[4] = {0, 0, 0, 0}, f = 0, st = SLIDE_OK;
-  const double* const u0s[1] = {u0};
-  const int rc = inter_loop_closures_clipper(maps, pair, 1, G, u0s, &n_u0, tf16, c4, &f, &st);
-  for (int c = 0; c < 4; ++c) counts[c] = c4[c];
-  *found = f;
-  if (rc == SLIDE_OK && st == SLIDE_ERR_INVALID) g_last_error = "u0 length does not match the number of putative associations";
-  if (rc == SLIDE_OK && st == SLIDE_ERR_CAPACITY) g_last_error = "more than 2^30 putative associations or 2^31 - 1 non-zeros in the affinity matrix";
-  return rc != SLIDE_OK ? rc : st;
-}
-
-// ---- Selecting the mutually consistent subset of a list of loop closures (PCM on the clique solver; no counterpart in the reference,
-// which adds the first closure that passes straight into the graph: sloamNode.cpp:448-476, graphWrapper.cpp:55) -----------------------
-}  // extern "C"
-namespace {
-struct ClosureCanon {
-  std::vector<int32_t> fr, tr, flipped, group, order;      // per closure; group / order -1 for a skipped closure
-  std::vector<uint64_t> fi, ti;
-  std::vector<SE3> z;
-  std::vector<int> goff;                                   // rows of group g: goff[g] .. goff[g + 1]
-  int n_groups = 0;
-};
-// from_robot > to_robot: ends swapped, rel inverted.  Groups by ascending (from_robot, to_robot), filled in list order.
-void closure_canonicalize(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
-                          const double* rel7, const int32_t* skip, ClosureCanon& C) {
-  C.fr.assign(from_robot, from_robot + L); C.tr.assign(to_robot, to_robot + L);
-  C.fi.assign(from_idx, from_idx + L); C.ti.assign(to_idx, to_idx + L);
-  C.flipped.assign(L, 0); C.group.assign(L, -1); C.order.assign(L, -1);
-  C.z.resize(L);
-  std::vector<int> keys;
-  for (int k = 0; k < L; ++k) {
-    C.z[k] = from7(rel7 + 7 * (size_t)k);
-    if (C.fr[k] > C.tr[k]) {
-      std::swap(C.fr[k], C.tr[k]); std::swap(C.fi[k], C.ti[k]);
-      C.z[k] = inverse(C.z[k]);
-      C.flipped[k] = 1;
-    }
-    if (!(skip && skip[k])) keys.push_back(C.fr[k] * (SLIDE_MAX_ROBOTS + 1) + C.tr[k]);
-  }
-  std::sort(keys.begin(), keys.end());
-  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  C.n_groups = (int)keys.size();
-  C.goff.assign(C.n_groups + 1, 0);
-  for (int k = 0; k < L; ++k) {
-    if (skip && skip[k]) continue;
-    C.group[k] = (int)(std::lower_bound(keys.begin(), keys.end(), C.fr[k] * (SLIDE_MAX_ROBOTS + 1) + C.tr[k]) - keys.begin());
-    C.goff[C.group[k] + 1] += 1;
-  }
-  for (int g = 0; g < C.n_groups; ++g) C.goff[g + 1] += C.goff[g];
-  std::vector<int> fill(C.goff.begin(), C.goff.end() - 1);
-  for (int k = 0; k < L; ++k)
-    if (C.group[k] >= 0) C.order[k] = fill[C.group[k]]++;
-}
-bool closure_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-bool closure_quats_ok(const double* p7, int L) {
-  for (int k = 0; k < L; ++k) {
-    const double* q = p7 + 7 * (size_t)k + 3;
-    if (!(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0)) return false;
-  }
-  return true;
-}
-int closure_bad(const char* what) { g_last_error = std::string("closure selection: ") + what; return SLIDE_ERR_INVALID; }
-int closure_check_params(const slide_closure_params_t& P, bool odom) {
-  if (!(P.gate > 0.0) || !std::isfinite(P.gate) || !(P.sigma > 0.0) || !std::isfinite(P.sigma)) return closure_bad("gate and sigma must be > 0");
-  if (!(P.affinityeps >= 0.0) || !std::isfinite(P.affinityeps)) return closure_bad("affinityeps must be >= 0");
-  if (P.min_set < 0) return closure_bad("min_set must be >= 0");
-  for (int c = 0; odom && c < 6; ++c)
-    if (!(P.odom_sigma6[c] > 0.0) || !std::isfinite(P.odom_sigma6[c])) return closure_bad("odom_sigma6 must be > 0");
-  return SLIDE_OK;
-}
-// rel7 / sigma6 (and the poses when given) of L closures: finite, quaternions not zero, sigmas > 0
-int closure_check_values(int L, const double* rel7, const double* sigma6, const double* from_pose7, const double* to_pose7) {
-  if (!closure_finite(rel7, 7 * (size_t)L) || !closure_quats_ok(rel7, L)) return closure_bad("rel7 holds a non-finite value or a zero quaternion");
-  if (!closure_finite(sigma6, 6 * (size_t)L)) return closure_bad("sigma6 holds a non-finite value");
-  for (size_t i = 0; i < 6 * (size_t)L; ++i)
-    if (!(sigma6[i] > 0.0)) return closure_bad("a sigma <= 0");
-  for (const double* p : {from_pose7, to_pose7})
-    if (p && (!closure_finite(p, 7 * (size_t)L) || !closure_quats_ok(p, L))) return closure_bad("a pose holds a non-finite value or a zero quaternion");
-  return SLIDE_OK;
-}
-ClosureScore closure_score_params(const slide_closure_params_t& P) {
-  ClosureScore S;
-  S.gate = P.gate; S.sigma = P.sigma; S.affinityeps = P.affinityeps;
-  for (int c = 0; c < 6; ++c) S.odom2[c] = P.odom_sigma6[c] * P.odom_sigma6[c];
-  return S;
-}
-
-// The device side of one list: its rows (closures of the groups of two or more, group after group) prepared, counted, scanned, emitted.
-struct ClosureRows {
-  int n_seg = 0, n_rows = 0;
-  std::vector<int> goff;                  // n_seg + 1
-  std::vector<double> z12, sig2, fpose12, tpose12;
-  std::vector<unsigned long long> idx2;
-  std::vector<int32_t> fslot, tslot;      // graph form: rows of pose_est
-  // device
-  int* d_goff = nullptr; int* d_rcnt = nullptr; int* d_rptr = nullptr; long long* d_tot = nullptr; long long* d_nnz0 = nullptr;
-  int* d_col = nullptr; double* d_val = nullptr;
-  std::vector<long long> tot, nnz0;
-  long long nnz_all = 0;
-};
-// d_pose_est: null = the rows' own pose arrays.  After it: the CSR of every segment on the device (nnz0[s] < 0: more than 2^31 - 1
-// non-zeros, dropped).  ONE blocking read-back (the segments' totals).
-int closure_build_csr(Tmp& T, ClosureRows& R, const double* d_pose_est, const ClosureScore& S) {
-  const int n = R.n_rows;
-  double* d_z = T.up(R.z12.data(), R.z12.size());
-  double* d_sig2 = T.up(R.sig2.data(), R.sig2.size());
-  unsigned long long* d_idx2 = T.up(R.idx2.data(), R.idx2.size());
-  double* d_pre = T.up<double>(nullptr, CLOSURE_PRE * (size_t)n);
-  R.d_goff = T.up(R.goff.data(), R.goff.size());
-  R.d_rcnt = T.up<int>(nullptr, n);
-  R.d_rptr = T.up<int>(nullptr, (size_t)n + R.n_seg);
-  R.d_tot = T.up<long long>(nullptr, R.n_seg);
-  if (!d_z || !d_sig2 || !d_idx2 || !d_pre || !R.d_goff || !R.d_rcnt || !R.d_rptr || !R.d_tot) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  if (d_pose_est) {
-    int32_t* d_fs = T.up(R.fslot.data(), R.fslot.size());
-    int32_t* d_ts = T.up(R.tslot.data(), R.tslot.size());
-    if (!d_fs || !d_ts) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    launch_closure_prepare(d_pose_est, d_pose_est, d_fs, d_ts, d_z, n, d_pre, nullptr);
-  } else {
-    double* d_f = T.up(R.fpose12.data(), R.fpose12.size());
-    double* d_t = T.up(R.tpose12.data(), R.tpose12.size());
-    if (!d_f || !d_t) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    launch_closure_prepare(d_f, d_t, nullptr, nullptr, d_z, n, d_pre, nullptr);
-  }
-  launch_closure_csr_seg(false, d_pre, d_sig2, d_idx2, R.d_goff, R.n_seg, n, S, R.d_rcnt, nullptr, nullptr, nullptr, nullptr, nullptr);
-  launch_seg_scan_rowptr(R.d_rcnt, R.d_goff, R.n_seg, R.d_rptr, R.d_tot, nullptr);
-  SL_HIP(hipGetLastError());
-  R.tot.assign(R.n_seg, 0);
-  SL_HIP(hipMemcpy(R.tot.data(), R.d_tot, sizeof(long long) * R.n_seg, hipMemcpyDeviceToHost));           // read-back 1
-  R.nnz0.assign(R.n_seg, -1);
-  R.nnz_all = 0;
-  for (int s = 0; s < R.n_seg; ++s) {
-    if (R.tot[s] > INT32_MAX) continue;      // ClqSolve::rowptr is per problem, 32 bits
-    R.nnz0[s] = R.nnz_all;
-    R.nnz_all += R.tot[s];
-  }
-  R.d_nnz0 = T.up(R.nnz0.data(), R.nnz0.size());
-  R.d_col = T.up<int>(nullptr, (size_t)std::max<long long>(R.nnz_all, 1));
-  R.d_val = T.up<double>(nullptr, (size_t)std::max<long long>(R.nnz_all, 1));
-  if (!R.d_nnz0 || !R.d_col || !R.d_val) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-  launch_closure_csr_seg(true, d_pre, d_sig2, d_idx2, R.d_goff, R.n_seg, n, S, nullptr, R.d_rptr, R.d_nnz0, R.d_col, R.d_val, nullptr);
-  SL_HIP(hipGetLastError());
-  return SLIDE_OK;
-}
-void closure_row_values(ClosureRows& R, const SE3& z, const double* sigma6, uint64_t fi, uint64_t ti) {
-  double z12[12];
-  to12(z, z12);
-  R.z12.insert(R.z12.end(), z12, z12 + 12);
-  for (int c = 0; c < 6; ++c) R.sig2.push_back(sigma6[c] * sigma6[c]);
-  R.idx2.push_back(fi); R.idx2.push_back(ti);
-}
-void closure_row_pose(std::vector<double>& dst, const double* pose7) {
-  double p12[12];
-  to12(from7(pose7), p12);
-  dst.insert(dst.end(), p12, p12 + 12);
-}
-
-struct ClosureOut {
-  int32_t* keep; int32_t* group; int32_t* status; int32_t* n_selected; double* score; int* n_groups; double* u_out;
-  int32_t* rowcnt_out; int32_t* col_out; double* val_out; long long csr_cap; long long* csr_nnz;
-};
-// C: the canonical list (status of its skipped closures already written by the caller).  Poses: per closure on the host (input
-// order, as given: a flipped closure's ends are swapped here), or the graph's device estimate with per-closure slots.
-int select_closures_core(int L, const ClosureCanon& C, const double* sigma6, const double* from_pose7, const double* to_pose7,
-                         const double* d_pose_est, const int32_t* fslot, const int32_t* tslot, const slide_closure_params_t& P,
-                         const slide_clipper_params_t& CP, const double* const* u0, const ClosureOut& O) {
-  const int NG = C.n_groups;
-  *O.n_groups = NG;
-  if (O.csr_nnz) *O.csr_nnz = 0;
-  for (int k = 0; k < L; ++k) {
-    O.keep[k] = 0;
-    if (O.group) O.group[k] = C.group[k];
-    if (O.status && C.group[k] >= 0) O.status[k] = SLIDE_OK;
-    if (O.u_out) O.u_out[k] = 0.0;
-    if (O.rowcnt_out) O.rowcnt_out[k] = 0;
-  }
-  for (int g = 0; g < NG; ++g) {
-    if (O.n_selected) O.n_selected[g] = 0;
-    if (O.score) O.score[g] = 0.0;
-  }
-  std::vector<int> by_row(C.goff[NG], -1);      // closure of every row
-  for (int k = 0; k < L; ++k)
-    if (C.order[k] >= 0) by_row[C.order[k]] = k;
-  // a lone closure never reaches the device: the clique of a 1 x 1 problem is that closure (u = 1, F = u (M + I) u = 1)
-  ClosureRows R;
-  std::vector<int> seg_group;
-  R.goff.push_back(0);
-  for (int g = 0; g < NG; ++g) {
-    const int m = C.goff[g + 1] - C.goff[g];
-    if (m == 1) {
-      const int k = by_row[C.goff[g]];
-      if (O.n_selected) O.n_selected[g] = 1;
-      if (O.score) O.score[g] = 1.0;
-      if (O.u_out) O.u_out[k] = 1.0;
-      O.keep[k] = 1 >= P.min_set ? 1 : 0;
-      continue;
-    }
-    seg_group.push_back(g);
-    for (int r = C.goff[g]; r < C.goff[g + 1]; ++r) {
-      const int k = by_row[r];
-      closure_row_values(R, C.z[k], sigma6 + 6 * (size_t)k, C.fi[k], C.ti[k]);
-      const bool fl = C.flipped[k] != 0;
-      if (d_pose_est) {
-        R.fslot.push_back(fl ? tslot[k] : fslot[k]);
-        R.tslot.push_back(fl ? fslot[k] : tslot[k]);
-      } else {
-        closure_row_pose(R.fpose12, (fl ? to_pose7 : from_pose7) + 7 * (size_t)k);
-        closure_row_pose(R.tpose12, (fl ? from_pose7 : to_pose7) + 7 * (size_t)k);
-      }
-    }
-    R.goff.push_back(R.goff.back() + m);
-  }
-  R.n_seg = (int)seg_group.size();
-  R.n_rows = R.goff.back();
-  if (R.n_seg == 0) return SLIDE_OK;
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  Tmp T;
-  int rc = closure_build_csr(T, R, d_pose_est, closure_score_params(P));
-  if (rc != SLIDE_OK) return rc;
-  const int n_seg = R.n_seg, n_rows = R.n_rows;
-  const std::vector<int>& goff = R.goff;
-  auto row_closure = [&](int s, int i) { return by_row[C.goff[seg_group[s]] + i]; };
-  // the solves: one launch for every group below the single problem's multi-workgroup threshold; results [out4 per group | u]
-  constexpr int COOP_N = 1024;
-  const size_t res_len = 4 * (size_t)n_seg + (size_t)n_rows;
-  double* d_res = T.up<double>(nullptr, res_len);
-  double* d_work = T.up<double>(nullptr, 6 * (size_t)n_rows);
-  if (!d_res || !d_work) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
-  SL_HIP(hipMemsetAsync(d_res, 0, res_len * sizeof(double), nullptr));
-  double* d_out = d_res;
-  double* d_u = d_res + 4 * (size_t)n_seg;
-  std::vector<double> start(n_rows, 0.0);
-  std::vector<ClqSolve> jobs;
-  for (int s = 0; s < n_seg; ++s) {
-    const int m = goff[s + 1] - goff[s], g = seg_group[s];
-    if (R.nnz0[s] < 0) {
-      for (int i = 0; i < m; ++i)
-        if (O.status) O.status[row_closure(s, i)] = SLIDE_ERR_CAPACITY;
-      continue;
-    }
-    if (m >= COOP_N) continue;
-    if (u0 && u0[g]) std::copy(u0[g], u0[g] + m, start.begin() + goff[s]);
-    else { std::vector<double> d(m); default_u0(d); std::copy(d.begin(), d.end(), start.begin() + goff[s]); }
-    ClqSolve A{};
-    A.rowptr = R.d_rptr + goff[s] + s; A.col = R.d_col + R.nnz0[s]; A.val = R.d_val + R.nnz0[s]; A.n = m;
-    double* w = d_work + 6 * (size_t)goff[s];
-    A.u = w; A.unew = w + m; A.g = w + 2 * (size_t)m; A.gnew = w + 3 * (size_t)m; A.Mu = w + 4 * (size_t)m; A.Cu = w + 5 * (size_t)m;
-    A.tol_u = CP.tol_u; A.tol_F = CP.tol_F; A.beta = CP.beta; A.eps = CP.eps;
-    A.maxin = CP.maxiniters; A.maxol = CP.maxoliters; A.maxls = CP.maxlsiters; A.rescale = CP.rescale_u0;
-    A.out = d_out + 4 * (size_t)s;
-    jobs.push_back(A);
-  }
-  if (!jobs.empty()) {
-    double* d_start = T.up(start.data(), start.size());
-    if (!d_start) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    for (ClqSolve& A : jobs) A.u0 = d_start + (A.u - d_work) / 6;       // (A.u = d_work + 6 goff[s]: the start weights of its group)
-    ClqSolve* d_jobs = T.up(jobs.data(), jobs.size());
-    if (!d_jobs) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
-    launch_clq_solve_batch(d_jobs, (int)jobs.size(), nullptr);
-    launch_clq_pack_u(d_work, R.d_goff, n_seg, n_rows, d_u, nullptr);
-  }
-  SL_HIP(hipGetLastError());
-  std::vector<double> res(res_len);
-  SL_HIP(hipMemcpy(res.data(), d_res, sizeof(double) * res_len, hipMemcpyDeviceToHost));                  // read-back 2
-  const double* h_u = res.data() + 4 * (size_t)n_seg;
-  for (int s = 0; s < n_seg; ++s) {
-    const int m = goff[s + 1] - goff[s], g = seg_group[s];
-    if (R.nnz0[s] < 0) continue;
-    std::vector<int> nodes;
-    std::vector<double> u;
-    double sc = 0.0;
-    if (m >= COOP_N) {        // the single problem's route for one large group, on this group's slice of the shared buffers
-      DevCsr S;
-      S.ptr = R.d_rptr + goff[s] + s; S.col = R.d_col + R.nnz0[s]; S.val = R.d_val + R.nnz0[s]; S.nnz = R.tot[s];
-      rc = solve_csr_device(T, S, m, (u0 && u0[g]) ? u0[g] : nullptr, CP, nodes, u, sc);
-      if (rc != SLIDE_OK) return rc;
-    } else {
-      u.assign(h_u + goff[s], h_u + goff[s + 1]);
-      sc = res[4 * (size_t)s];
-      nodes = top_entries(u, (int)std::round(sc));
-    }
-    if (O.n_selected) O.n_selected[g] = (int)nodes.size();
-    if (O.score) O.score[g] = sc;
-    if (O.u_out) for (int i = 0; i < m; ++i) O.u_out[row_closure(s, i)] = u[i];
-    if ((int)nodes.size() >= P.min_set && !nodes.empty())
-      for (int i : nodes) O.keep[row_closure(s, i)] = 1;
-  }
-  // the matrices themselves, for inspection (three more blocking copies)
-  if (O.csr_nnz) *O.csr_nnz = R.nnz_all;
-  if (O.rowcnt_out) {
-    std::vector<int> cnt(n_rows);
-    SL_HIP(hipMemcpy(cnt.data(), R.d_rcnt, sizeof(int) * n_rows, hipMemcpyDeviceToHost));
-    for (int s = 0; s < n_seg; ++s)
-      for (int i = 0; i < goff[s + 1] - goff[s]; ++i)
-        if (R.nnz0[s] >= 0) O.rowcnt_out[row_closure(s, i)] = cnt[goff[s] + i];
-  }
-  if (O.col_out && O.val_out && R.nnz_all > 0 && R.nnz_all <= O.csr_cap) {
-    SL_HIP(hipMemcpy(O.col_out, R.d_col, sizeof(int32_t) * (size_t)R.nnz_all, hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(O.val_out, R.d_val, sizeof(double) * (size_t)R.nnz_all, hipMemcpyDeviceToHost));
-  }
-  return SLIDE_OK;
-}
-int closure_check_list(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
-                       const double* rel7, const double* sigma6, const void* keep, const void* n_groups) {
-  if (L < 0) return closure_bad("L < 0");
-  if (!n_groups) return closure_bad("n_groups is NULL");
-  if (L > 0 && (!from_robot || !from_idx || !to_robot || !to_idx || !rel7 || !sigma6 || !keep)) return closure_bad("a needed pointer is NULL");
-  for (int k = 0; k < L; ++k)
-    if (!robot_ok(from_robot[k]) || !robot_ok(to_robot[k])) return closure_bad("a robot outside [0, SLIDE_MAX_ROBOTS)");
-  return SLIDE_OK;
-}
-}  // namespace
-extern "C" {
-
-void slide_closure_default_params(slide_closure_params_t* p) {
-  p->gate = 4.1;                 // sqrt(16.81): the 0.99 quantile of chi-square with 6 degrees of freedom
-  p->sigma = p->gate / 2;        // a convention: the score at the gate is exp(-2)
-  p->affinityeps = 1e-4;         // CLIPPER's default
-  for (int c = 0; c < 6; ++c) p->odom_sigma6[c] = 0.1;
-  p->min_set = 1;
-}
-
-int slide_closure_canonicalize(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
-                               const double* rel7, int32_t* from_robot_out, uint64_t* from_idx_out, int32_t* to_robot_out,
-                               uint64_t* to_idx_out, double* rel7_out, int32_t* flipped, int32_t* group, int32_t* order, int* n_groups) {
-  int dummy = 0;
-  int rc = closure_check_list(L, from_robot, from_idx, to_robot, to_idx, rel7, rel7, &dummy, n_groups);
-  if (rc != SLIDE_OK) return rc;
-  if (L > 0 && (!closure_finite(rel7, 7 * (size_t)L) || !closure_quats_ok(rel7, L))) return closure_bad("rel7 holds a non-finite value or a zero quaternion");
-  ClosureCanon C;
-  closure_canonicalize(L, from_robot, from_idx, to_robot, to_idx, rel7, nullptr, C);
-  *n_groups = C.n_groups;
-  for (int k = 0; k < L; ++k) {
-    if (from_robot_out) from_robot_out[k] = C.fr[k];
-    if (from_idx_out) from_idx_out[k] = C.fi[k];
-    if (to_robot_out) to_robot_out[k] = C.tr[k];
-    if (to_idx_out) to_idx_out[k] = C.ti[k];
-    if (rel7_out) {
-      if (C.flipped[k]) to7(C.z[k], rel7_out + 7 * (size_t)k);
-      else std::memcpy(rel7_out + 7 * (size_t)k, rel7 + 7 * (size_t)k, 7 * sizeof(double));      // untouched closures keep their bits
-    }
-    if (flipped) flipped[k] = C.flipped[k];
-    if (group) group[k] = C.group[k];
-    if (order) order[k] = C.order[k];
-  }
-  return SLIDE_OK;
-}
-
-int slide_closure_consistency_csr(const double* from_pose7, const double* to_pose7, const double* rel7, const double* sigma6,
-                                  const uint64_t* from_idx, const uint64_t* to_idx, int L, const slide_closure_params_t* p,
-                                  int32_t* rowptr_out, int32_t* col_out, double* val_out, long long cap, long long* nnz) {
-  if (L < 0) return closure_bad("L < 0");
-  if (cap < 0 || !nnz || !rowptr_out) return closure_bad("cap < 0, or nnz / rowptr_out is NULL");
-  if (L > 0 && (!from_pose7 || !to_pose7 || !rel7 || !sigma6 || !from_idx || !to_idx)) return closure_bad("a needed pointer is NULL");
-  slide_closure_params_t P;
-  if (p) P = *p; else slide_closure_default_params(&P);
-  int rc = closure_check_params(P, true);
-  if (rc == SLIDE_OK && L > 0) rc = closure_check_values(L, rel7, sigma6, from_pose7, to_pose7);
-  if (rc != SLIDE_OK) return rc;
-  *nnz = 0;
-  if (L <= 1) {          // no pair: the empty matrix, no device
-    for (int i = 0; i <= L; ++i) rowptr_out[i] = 0;
-    return SLIDE_OK;
-  }
-  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
-  ClosureRows R;
-  R.n_seg = 1; R.n_rows = L; R.goff = {0, L};
-  for (int k = 0; k < L; ++k) {
-    closure_row_values(R, from7(rel7 + 7 * (size_t)k), sigma6 + 6 * (size_t)k, from_idx[k], to_idx[k]);
-    closure_row_pose(R.fpose12, from_pose7 + 7 * (size_t)k);
-    closure_row_pose(R.tpose12, to_pose7 + 7 * (size_t)k);
-  }
-  Tmp T;
-  rc = closure_build_csr(T, R, nullptr, closure_score_params(P));
-  if (rc != SLIDE_OK) return rc;
-  if (R.nnz0[0] < 0) { g_last_error = "the consistency matrix has more than 2^31 - 1 non-zeros"; return SLIDE_ERR_CAPACITY; }
-  *nnz = R.tot[0];
-  SL_HIP(hipMemcpy(rowptr_out, R.d_rptr, sizeof(int32_t) * ((size_t)L + 1), hipMemcpyDeviceToHost));
-  if (*nnz > cap) { g_last_error = "the CSR has " + std::to_string(*nnz) + " non-zeros, the caller's buffers hold " + std::to_string(cap); return SLIDE_ERR_CAPACITY; }
-  if (*nnz > 0) {
-    if (!col_out || !val_out) return closure_bad("col_out / val_out is NULL");
-    SL_HIP(hipMemcpy(col_out, R.d_col, sizeof(int32_t) * (size_t)*nnz, hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(val_out, R.d_val, sizeof(double) * (size_t)*nnz, hipMemcpyDeviceToHost));
-  }
-  return SLIDE_OK;
-}
-
-int slide_select_consistent_closures(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
-                                     const uint64_t* to_idx, const double* rel7, const double* sigma6, const double* from_pose7,
-                                     const double* to_pose7, const slide_closure_params_t* p, const slide_clipper_params_t* cp,
-                                     const double* const* u0, int32_t* keep, int32_t* group, int32_t* status, int32_t* n_selected,
-                                     double* score, int* n_groups, double* u_out, int32_t* rowcnt_out, int32_t* col_out, double* val_out,
-                                     long long csr_cap, long long* csr_nnz) {
-  int rc = closure_check_list(L, from_robot, from_idx, to_robot, to_idx, rel7, sigma6, keep, n_groups);
-  if (rc != SLIDE_OK) return rc;
-  if (L > 0 && (!from_pose7 || !to_pose7)) return closure_bad("a needed pointer is NULL");
-  if (csr_cap < 0) return closure_bad("csr_cap < 0");
-  slide_closure_params_t P;
-  if (p) P = *p; else slide_closure_default_params(&P);
-  rc = closure_check_params(P, true);
-  if (rc == SLIDE_OK && L > 0) rc = closure_check_values(L, rel7, sigma6, from_pose7, to_pose7);
-  if (rc != SLIDE_OK) return rc;
-  slide_clipper_params_t CP;
-  if (cp) CP = *cp; else slide_clipper_default_params(&CP);
-  if (L == 0) { *n_groups = 0; if (csr_nnz) *csr_nnz = 0; return SLIDE_OK; }
-  ClosureCanon C;
-  closure_canonicalize(L, from_robot, from_idx, to_robot, to_idx, rel7, nullptr, C);
-  const ClosureOut O{keep, group, status, n_selected, score, n_groups, u_out, rowcnt_out, col_out, val_out, csr_cap, csr_nnz};
-  return select_closures_core(L, C, sigma6, from_pose7, to_pose7, nullptr, nullptr, nullptr, P, CP, u0, O);
-}
-
-int slide_graph_select_closures(slide_graph_t* g, int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
-                                const uint64_t* to_idx, const double* rel7, const double* sigma6, const slide_closure_params_t* p,
-                                const slide_clipper_params_t* cp, int32_t* keep, int32_t* group, int32_t* status, int32_t* n_selected,
-                                double* score, int* n_groups) {
-  if (!g) return closure_bad("the graph is NULL");
-  int rc = closure_check_list(L, from_robot, from_idx, to_robot, to_idx, rel7, sigma6, keep, n_groups);
-  if (rc != SLIDE_OK) return rc;
-  slide_closure_params_t P;
-  if (p) P = *p; else slide_closure_default_params(&P);
-  rc = closure_check_params(P, false);
-  if (rc == SLIDE_OK && L > 0) rc = closure_check_values(L, rel7, sigma6, nullptr, nullptr);
-  if (rc != SLIDE_OK) return rc;
-  slide_clipper_params_t CP;
-  if (cp) CP = *cp; else slide_clipper_default_params(&CP);
-  if (L == 0) { *n_groups = 0; return SLIDE_OK; }
-  LOCK(g);
-  for (int c = 0; c < 6; ++c) P.odom_sigma6[c] = g->g.P.noise_model_odom_vec[c];
-  rc = closure_check_params(P, true);
-  if (rc != SLIDE_OK) return rc;
-  std::vector<int32_t> fslot(L), tslot(L), skip(L, 0);
-  g->g.pose_slots(from_robot, from_idx, L, fslot.data());
-  g->g.pose_slots(to_robot, to_idx, L, tslot.data());
-  for (int k = 0; k < L; ++k)
-    if (fslot[k] < 0 || tslot[k] < 0) { skip[k] = 1; if (status) status[k] = SLIDE_MISSING; }
-  ClosureCanon C;
-  closure_canonicalize(L, from_robot, from_idx, to_robot, to_idx, rel7, skip.data(), C);
-  SL_HIP(hipStreamSynchronize(g->g.stream));      // the estimate of the last solve is in place; this call only reads it
-  const ClosureOut O{keep, group, status, n_selected, score, n_groups, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-  return select_closures_core(L, C, sigma6, nullptr, nullptr, g->g.pose_est_dev(), fslot.data(), tslot.data(), P, CP, nullptr, O);
-}
-
-// Marginals::jointMarginalCovariance for a list of pose pairs.  The argument checks come first and need neither graph nor device.
-int slide_graph_get_pose_pair_covariances(slide_graph_t* g, int n, const int32_t* robot_a, const uint64_t* idx_a, const int32_t* robot_b,
-                                          const uint64_t* idx_b, double* out144n, int32_t* status) {
-  if (n < 0) { g_last_error = "get_pose_pair_covariances: n < 0"; return SLIDE_ERR_INVALID; }
-  if (n > 0 && (!robot_a || !idx_a || !robot_b || !idx_b || !out144n)) { g_last_error = "get_pose_pair_covariances: a needed pointer is NULL"; return SLIDE_ERR_INVALID; }
-  for (int k = 0; k < n; ++k)
-    if (!robot_ok(robot_a[k]) || !robot_ok(robot_b[k])) { g_last_error = "get_pose_pair_covariances: a robot outside [0, SLIDE_MAX_ROBOTS)"; return SLIDE_ERR_INVALID; }
-  if (!g) { g_last_error = "get_pose_pair_covariances: the graph is NULL"; return SLIDE_ERR_INVALID; }
-  LOCK(g);
-  return g->g.pose_pair_covariances(n, robot_a, idx_a, robot_b, idx_b, out144n, status);
-}
-
-// The individual-compatibility gate of a list of loop closures (the complement of slide_graph_select_closures, same arrays)
-int slide_graph_closure_mahalanobis(slide_graph_t* g, int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
-                                    const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36, double* r6,
-                                    int32_t* status) {
-  int dummy = 0;
-  int rc = closure_check_list(L, from_robot, from_idx, to_robot, to_idx, rel7, sigma6, d2, &dummy);
-  if (rc == SLIDE_OK && L > 0) rc = closure_check_values(L, rel7, sigma6, nullptr, nullptr);
-  if (rc != SLIDE_OK) { g_last_error = "closure_mahalanobis: " + g_last_error; return rc; }
-  if (!g) { g_last_error = "closure_mahalanobis: the graph is NULL"; return SLIDE_ERR_INVALID; }
-  LOCK(g);
-  return g->g.closure_mahalanobis(L, from_robot, from_idx, to_robot, to_idx, rel7, sigma6, d2, C36, r6, status);
-}
-
-// The same two queries on the joint graph of a CholBatch (a slot where the calls above take a robot).  The argument checks are the
-// single-graph calls' own and come before the batch or the device is looked at.
-int slide_chol_batch_get_pose_pair_covariances(slide_chol_batch_t* b, int n, const int32_t* slot_a, const uint64_t* idx_a, const int32_t* slot_b,
-                                               const uint64_t* idx_b, double* out144n, int32_t* status) {
-  if (n < 0) { g_last_error = "get_pose_pair_covariances: n < 0"; return SLIDE_ERR_INVALID; }
-  if (n > 0 && (!slot_a || !idx_a || !slot_b || !idx_b || !out144n)) { g_last_error = "get_pose_pair_covariances: a needed pointer is NULL"; return SLIDE_ERR_INVALID; }
-  for (int k = 0; k < n; ++k)
-    if (!robot_ok(slot_a[k]) || !robot_ok(slot_b[k])) { g_last_error = "get_pose_pair_covariances: a slot outside [0, SLIDE_MAX_ROBOTS)"; return SLIDE_ERR_INVALID; }
-  if (!b) { g_last_error = "get_pose_pair_covariances: the batch is NULL"; return SLIDE_ERR_INVALID; }
-  return b->b.joint_pose_pair_covariances(n, slot_a, idx_a, slot_b, idx_b, out144n, status);
-}
-int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot,
-                                         const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36, double* r6,
-                                         int32_t* status) {
-  int dummy = 0;
-  int rc = closure_check_list(L, from_slot, from_idx, to_slot, to_idx, rel7, sigma6, d2, &dummy);
-  if (rc == SLIDE_OK && L > 0) rc = closure_check_values(L, rel7, sigma6, nullptr, nullptr);
-  if (rc != SLIDE_OK) { g_last_error = "closure_mahalanobis: " + g_last_error; return rc; }
-  if (!b) { g_last_error = "closure_mahalanobis: the batch is NULL"; return SLIDE_ERR_INVALID; }
-  return b->b.joint_closure_mahalanobis(L, from_slot, from_idx, to_slot, to_idx, rel7, sigma6, d2, C36, r6, status);
-}
-
-// sloam::FindRelativeMeasurementMatch sloam.cpp:321-412 (host-side bookkeeping: a few dozen stamps per call)
-int slide_find_relative_meas_match(int n_robots, const int64_t* pk_sec, const int64_t* pk_nsec, const int32_t* offsets,
-                                   const uint64_t* pose_counter, int host, int* n_pending_io, int64_t* m_sec, int64_t* m_nsec,
-                                   int32_t* m_robot, int32_t* m_only_odom, int32_t* m_tag, int32_t* match_out, int* n_matches) {
-  if (!n_pending_io || !n_matches || host < 0 || host >= n_robots) return SLIDE_ERR_INVALID;
-  *n_matches = 0;
-  int np = *n_pending_io;
-  if (np <= 0) return SLIDE_OK;
-  const double max_dt = 0.001;                                        // sloam.cpp:324
-  auto closest = [&](int robot, int64_t qs, int64_t qn, int& idx, double& diff) {
-    slide_closest_stamp(pk_sec + offsets[robot], pk_nsec + offsets[robot], offsets[robot + 1] - offsets[robot], qs, qn, &idx, &diff);
-  };
-  auto erase = [&](int i) {
-    for (int k = i; k + 1 < np; ++k) {
-      m_sec[k] = m_sec[k + 1]; m_nsec[k] = m_nsec[k + 1]; m_robot[k] = m_robot[k + 1]; m_only_odom[k] = m_only_odom[k + 1];
-      m_tag[k] = m_tag[k + 1];
-    }
-    --np;
-  };
-  for (int i = 0; i < np; ++i) {
-    const int r = m_robot[i];
-    if (r == host || r < 0 || r >= n_robots || m_only_odom[i]) { *n_pending_io = np; return SLIDE_ERR_INVALID; }
-    int io, ih;
-    double dt;
-    closest(r, m_sec[i], m_nsec[i], io, dt);
-    if (io == -1 || dt > max_dt || (uint64_t)io >= pose_counter[r]) continue;
-    closest(host, m_sec[i], m_nsec[i], ih, dt);
-    if (ih == -1 || dt > max_dt || (uint64_t)ih >= pose_counter[host]) continue;
-    int32_t* mo = match_out + 4 * (size_t)(*n_matches);
-    mo[0] = m_tag[i]; mo[1] = i; mo[2] = ih; mo[3] = io;
-    ++*n_matches;
-    erase(i);
-    --i;
-  }
-  // prune measurements both robots have already passed (sloam.cpp:388-410)
-  auto later = [](int64_t as, int64_t an, int64_t bs, int64_t bn) { return as > bs || (as == bs && an > bn); };
-  for (int i = 0; i < np; ++i) {
-    const int r = m_robot[i];
-    int64_t os = 0, on = 0, hs = 0, hn = 0;
-    if (pose_counter[r] > 0) { os = pk_sec[offsets[r] + pose_counter[r] - 1]; on = pk_nsec[offsets[r] + pose_counter[r] - 1]; }
-    if (pose_counter[host] > 0) { hs = pk_sec[offsets[host] + pose_counter[host] - 1]; hn = pk_nsec[offsets[host] + pose_counter[host] - 1]; }
-    if (later(os, on, m_sec[i], m_nsec[i]) && later(hs, hn, m_sec[i], m_nsec[i])) { erase(i); --i; }
-  }
-  *n_pending_io = np;
   return SLIDE_OK;
 }
 

@@ -119,6 +119,25 @@ def test_batch_equals_single_solves(gpu):
         assert bF == F and np.array_equal(bu, u) and np.array_equal(bn, nodes), (c["name"], bF - F)
 
 
+def test_batch_equals_single_dense_calls(gpu):
+    """The job set-up of clipper_dense_clique_batch against the single call's, from the dense matrices both entry points take:
+    n = 0, 1, 3, 64, 65 and 130 in ONE call, the n = 65 job with a caller's u0 and every other job with the default start.  nodes, u
+    and score of every job equal clipper_dense_clique's bit for bit ("Results equal n_jobs single calls", include/slide_gpu.h)."""
+    mats = {0: (np.zeros((0, 0)), None), 1: cc.noise(1, 0.5, 0.2, 1.0, 411)[:2], 3: cc.chunk_boundary_matrix(3, 413),
+            64: cc.planted(64, 8, 0.1, 464)[:2], 65: cc.chunk_boundary_matrix(65, 465), 130: cc.planted(130, 12, 0.08, 530)[:2]}
+    ns = [0, 1, 3, 64, 65, 130]
+    Ms = [np.ascontiguousarray(np.triu(mats[n][0], 1)) for n in ns]
+    u0s = [mats[n][1] if n == 65 else None for n in ns]
+    assert np.count_nonzero(Ms[2]) and np.count_nonzero(Ms[3]) and np.count_nonzero(Ms[5])
+    res = gpu.clipper_dense_clique_batch(Ms, u0s, gpu.clipper_params())
+    assert len(res) == len(ns)
+    for n, M, u0, (bn, bu, bF) in zip(ns, Ms, u0s, res):
+        nodes, u, F = gpu.clipper_dense_clique(M, u0, gpu.clipper_params())
+        print(f"n = {n}: {len(nodes)} nodes, F = {F!r} (batch {bF!r})")
+        assert len(bu) == n
+        assert bF == F and np.array_equal(bu, u) and np.array_equal(bn, nodes), (n, bF - F)
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 129, 257])
 def test_dense_entry_equals_csr_entry(gpu, n):
     """k_clq_csr (one wave per row, the columns in chunks of 64, ballot ranks) with entries on both sides of every chunk boundary:

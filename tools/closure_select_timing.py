@@ -5,6 +5,7 @@ synchronised around the timed region: the median of REPS repetitions after WARM 
 takes minutes).  No threshold is set on these times: there is no earlier path to compare against.
 
     timeout -k 10 1100 python tools/closure_select_timing.py > profiles/closure_select_timing.txt
+    python tools/closure_select_timing.py --device-only      # the device times alone (seconds): for comparing two builds of the library
 """
 import os
 import sys
@@ -66,7 +67,7 @@ def restate_rows(c, cc):
     return M
 
 
-def main():
+def main(device_only=False):
     import torch
     torch.zeros(1, device=torch.device("cuda", 0))      # (torch initialises the device before the library's HIP runtime is loaded)
     import closure_cases as cc
@@ -103,6 +104,9 @@ def main():
         for _ in range(WARM):
             out = device()
         t_dev = [timed(device) for _ in range(REPS)]
+        if device_only:
+            print(f"({name}) device {np.median(t_dev):9.3f} ms ({min(t_dev):.3f} - {max(t_dev):.3f}); kept {int(np.sum(out['keep']))} of {len(cl)}", flush=True)
+            continue
         t_host = [timed(host)] if big else [timed(host) for _ in range(WARM + REPS)][WARM:]
         sel = host()
         at, agree = 0, 0
@@ -114,4 +118,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main("--device-only" in sys.argv)
