@@ -906,6 +906,43 @@ int slide_graph_get_pose_pair_covariances(slide_graph_t* g, int n, const int32_t
 int slide_graph_closure_mahalanobis(slide_graph_t* g, int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot,
                                     const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36 /* may be NULL */,
                                     double* r6 /* may be NULL */, int32_t* status /* may be NULL */);
+/* ---- One landmark observation against what the graph already knows: the gate's counterpart for observation factors ----------------
+ * Most factors of a graph are landmark observations, and the association that produces them tests a Euclidean distance only (0.75 m
+ * for ellipsoids, 2 m for cubes and cylinders: sloam.cpp:73-203), whatever the pose's drift and the landmark's own uncertainty.  This
+ * is the individual-compatibility (innovation) gate of a candidate match before it becomes a factor: nearest-neighbour association
+ * with a chi-square gate.  No counterpart in the reference; GTSAM users would assemble it from
+ * Marginals::jointMarginalCovariance({X(i), L(j)}).
+ * Candidate k is the factor slide_graph_add_range_bearing / _add_cube / _add_cylinder would add between pose (robot[k], pose_idx[k])
+ * and the EXISTING landmark (cls[k], lm_idx[k]) of dimension D = 3 / 9 / 7; it has m = D rows.  meas17[17 k ..] holds the remaining
+ * arguments of the class's add call in its order, zero padded: SLIDE_CLS_ELLIPSOID bearing[3], range; SLIDE_CLS_CUBE pose_world7,
+ * cube_world7, scale[3]; SLIDE_CLS_CYLINDER pose_world7, root[3], ray[3], radius.  r (m) is its whitened residual and A = [Ap | Al]
+ * (m x 6, m x D) its whitened Jacobian, linearised by the solver's own text for the class (analytic for bearing-range, central
+ * differences of numdiff_delta for cubes and cylinders) under the graph's pose_chart, with the noise the add call would choose
+ * (bearing_range_sigma; noise_model_cube_vec x max(|loc.t|, 0.1); cylinder_sigma) and NO robust weight, whatever
+ * slide_graph_set_observation_loss says.  With H the full system as last linearised (reweighted, if a loss is set) and S = L L^T its
+ * landmark-eliminated pose system,
+ *     C = I + A H^-1 A^T = I + Al H_ll^-1 Al^T + B^T S^-1 B,    B = P_p^T Ap^T - sum_{f in factors(l)} P_{p_f}^T F_f Al^T,
+ *     d2[k] = r^T C^-1 r,
+ * P_q selecting pose q's six rows and F_f = E_f H_ll^-1 the factor's resident Schur block: the pose-landmark cross block of the
+ * marginal is never formed, and B^T S^-1 B = W^T W with L W = B is the forward substitution of the two calls above.  Sigma belongs to
+ * the LAST LINEARISATION POINT (the resident factor), r and A to the CURRENT ESTIMATE (what slide_graph_get_pose12 /
+ * slide_graph_get_landmark return).  d2 is chi-square with m degrees of freedom for a true match that was not added yet: compare it
+ * with the 0.99 quantile, 11.345 (m = 3), 18.475 (m = 7), 21.666 (m = 9); no threshold is applied by the call.  The graph is only
+ * read: nothing in it changes.
+ * Outputs: dof[k] = 3 / 9 / 7; C81 (81 per candidate) row-major with leading dimension 9, zero outside the m x m block; r9 (9 per
+ * candidate).  dof, C81, r9 and status may be NULL.  Candidates are grouped by class and cut into sweeps of at most
+ * SLIDE_INFO_GAIN_SWEEP_COLS columns (128 points, 42 cubes, 54 cylinders); a sweep starts its substitution at the block column of the
+ * lowest pose it touches (the candidates' poses and their landmarks' first observers), and a candidate's bits do not depend on what
+ * else is in the list or where it stands.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written, the message names observation_mahalanobis and the reason): decided on the
+ * host before the graph or the device is looked at — the graph is NULL, a needed pointer NULL, n < 0, a robot outside
+ * [0, SLIDE_MAX_ROBOTS), a class that is none of the three, non-finite input, a zero quaternion, a zero bearing, a range <= 0, a zero
+ * ray; then those of slide_graph_get_pose_covariances.  n == 0 on a graph that would be served: SLIDE_OK.  Per candidate, into
+ * status[k] with zeros in its outputs: SLIDE_MISSING for a pose or landmark the graph does not hold, SLIDE_ERR_NOT_SPD when C has a
+ * pivot that is not positive. */
+int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
+                                        const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof /* may be NULL */,
+                                        double* C81 /* may be NULL */, double* r9 /* may be NULL */, int32_t* status /* may be NULL */);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the

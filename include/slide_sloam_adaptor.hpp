@@ -315,6 +315,62 @@ class SemanticFactorGraph {
     d2.resize(n);
     return d2;
   }
+  // The individual-compatibility gate of candidate landmark observations (slide_graph_observation_mahalanobis; no counterpart in the
+  // reference, whose association tests a Euclidean distance only, sloam.cpp:73-203).  A candidate holds what addRangeBearingFactor /
+  // addCubeFactor / addCylinderFactor would be given for an EXISTING landmark; build it with the three makers.  d2[k] = r^T C^-1 r of
+  // candidate k against the graph as it stands, chi-square with dof[k] = 3 / 9 / 7 degrees of freedom for a true match — compare it
+  // with 11.345 / 21.666 / 18.475; no threshold is applied here.  Call it after solve() and before the observations are added; the
+  // graph is only read.  A candidate with a fault of its own (status, when given: SLIDE_MISSING, SLIDE_ERR_NOT_SPD) has d2 = 0: read
+  // the status before the value.
+  struct ObservationCandidate { int cls = SLIDE_CLS_ELLIPSOID; size_t robot = 0, poseIdx = 0, lmIdx = 0; std::array<double, 17> meas{}; };
+  template <class Point>
+  static ObservationCandidate pointCandidate(const size_t poseIdx, const size_t ugvIdx, const Point& bearing_measurement,
+                                             const double& range_measurement, const int& robotID) {
+    ObservationCandidate c;
+    c.cls = SLIDE_CLS_ELLIPSOID; c.robot = (size_t)robotID; c.poseIdx = poseIdx; c.lmIdx = ugvIdx;
+    detail::to3(bearing_measurement, c.meas.data());
+    c.meas[3] = range_measurement;
+    return c;
+  }
+  template <class Pose>
+  static ObservationCandidate cubeCandidate(const size_t poseIdx, const size_t cubeIdx, const Pose& pose, const CubeMeasurement& cube_global_meas,
+                                            const int& robotID) {
+    ObservationCandidate c;
+    c.cls = SLIDE_CLS_CUBE; c.robot = (size_t)robotID; c.poseIdx = poseIdx; c.lmIdx = cubeIdx;
+    detail::to7(pose, c.meas.data());
+    detail::to7(cube_global_meas.pose, c.meas.data() + 7);
+    for (int i = 0; i < 3; ++i) c.meas[14 + i] = cube_global_meas.scale[i];
+    return c;
+  }
+  template <class Pose>
+  static ObservationCandidate cylinderCandidate(const size_t poseIdx, const size_t cylIdx, const Pose& pose, const CylinderMeasurement& cylinder,
+                                                const int& robotID) {
+    ObservationCandidate c;
+    c.cls = SLIDE_CLS_CYLINDER; c.robot = (size_t)robotID; c.poseIdx = poseIdx; c.lmIdx = cylIdx;
+    detail::to7(pose, c.meas.data());
+    for (int i = 0; i < 3; ++i) { c.meas[7 + i] = cylinder.root[i]; c.meas[10 + i] = cylinder.ray[i]; }
+    c.meas[13] = cylinder.radius;
+    return c;
+  }
+  std::vector<double> observationMahalanobis(const std::vector<ObservationCandidate>& candidates, std::vector<int32_t>* dof = nullptr,
+                                             std::vector<int32_t>* status = nullptr) const {
+    const size_t n = candidates.size();
+    std::vector<double> meas(17 * n + 1), d2(n + 1, 0.0);
+    std::vector<int32_t> rb(n + 1), cls(n + 1), df(n + 1, 0), st(n + 1, 0);
+    std::vector<uint64_t> pi(n + 1), li(n + 1);
+    for (size_t k = 0; k < n; ++k) {
+      const ObservationCandidate& c = candidates[k];
+      rb[k] = (int32_t)c.robot; cls[k] = (int32_t)c.cls; pi[k] = c.poseIdx; li[k] = c.lmIdx;
+      for (int i = 0; i < 17; ++i) meas[17 * k + i] = c.meas[i];
+    }
+    detail::check(slide_graph_observation_mahalanobis(g_, (int)n, rb.data(), pi.data(), cls.data(), li.data(), meas.data(), d2.data(), df.data(),
+                                                      nullptr, nullptr, st.data()),
+                  "observationMahalanobis");
+    if (dof) dof->assign(df.begin(), df.begin() + n);
+    if (status) status->assign(st.begin(), st.begin() + n);
+    d2.resize(n);
+    return d2;
+  }
 
   // Robust loss on the loop-closure / relative-measurement factors (slide_graph_set_robust_loss; no counterpart in the reference —
   // GTSAM's noiseModel::Robust with mEstimator::Huber / Cauchy / GemanMcClure / DCS): kind 0 none, 1 .. 4 in that order; param <= 0:

@@ -2,7 +2,7 @@
 per-frame semantic data association + factor-graph linearise-and-solve, behind the C-ABI of
 include/slide_gpu.h.  See DESIGN.md.  There is no CPU fallback."""
 from .api import (assoc_sweep_batch, CHART_CAYLEY, CHART_EXPMAP, CLS_CUBE, CLS_CYLINDER, CLS_ELLIPSOID, FRAME_FOREIGN, FRAME_HOST,  # noqa: F401
-                  FRAME_HOST_DEFERRED, LIB_PATH, CholBatch, ClipperParams, Params, PlaceParams, SlideBackend, SlideError, SlideGraph,
+                  FRAME_HOST_DEFERRED, LIB_PATH, OBSERVATION_GATE_CHI2_99, CholBatch, ClipperParams, Params, PlaceParams, SlideBackend, SlideError, SlideGraph,
                   MS_AFFINITY_CSR, clipper_affinity, clipper_affinity_csr, clipper_dense_clique, clipper_dense_clique_batch, clipper_dense_clique_csr, clipper_match, clipper_last_solve_info, clipper_params, ClosureParams, closure_params, closure_canonicalize, closure_consistency_csr, select_consistent_closures, closest_stamp, delaunay_2d, estimate_tf2d, find_relative_meas_match, in_loop_closure_region, match_triangles,
                   pick_next_measurement, run_semantic_clipper, SlidegraphParams, slidegraph_params, find_inter_loop_closure_clipper,
                   find_inter_loop_closures_clipper,

@@ -43,6 +43,7 @@ EXPORTS = [
     "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
     "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
+    "slide_graph_observation_mahalanobis",
     "slide_graph_set_robust_loss", "slide_graph_get_closure_weights",
     "slide_graph_set_observation_loss", "slide_graph_get_observation_weights",
     "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
@@ -53,6 +54,13 @@ EXPORTS = [
 
 class SlideError(RuntimeError):
     pass
+
+
+# the 0.99 quantiles of chi-square by degrees of freedom: what SlideGraph.observation_mahalanobis's d2 is compared with (points 3,
+# cylinders 7, cubes 9)
+OBSERVATION_GATE_CHI2_99 = {3: 11.345, 7: 18.475, 9: 21.666}
+_OBS_CLASSES = {"cylinder": 0, "cube": 1, "point": 2}      # SLIDE_CLS_*
+_OBS_NARGS = {"point": 4, "cube": 17, "cylinder": 14}
 
 
 class Params(C.Structure):
@@ -430,6 +438,34 @@ class SlideGraph:
         _check(self.L.slide_graph_closure_mahalanobis(self.h, C.c_int(L), _p(fr), _p(fi), _p(tr), _p(ti), _p(rel), _p(sg), _p(d2), _p(Cm),
                                                       _p(r), _p(status)))
         return {"d2": d2[:L], "status": status[:L], "C": Cm[:L], "r": r[:L]}
+
+    def observation_mahalanobis(self, candidates):
+        """slide_graph_observation_mahalanobis: the individual-compatibility test of candidate landmark observations against the
+        graph as it stands (call it after a solve and before the observations are added; the graph is only read).  candidates: tuples
+        ("point", robot, pose_idx, lm_idx, bearing, range), ("cube", robot, pose_idx, idx, pose7, cube7, scale) or
+        ("cylinder", robot, pose_idx, idx, pose7, root, ray, radius): the arguments of add_range_bearing / add_cube / add_cylinder
+        for an existing landmark.  Returns a dict: d2 (n) = r^T C^-1 r, chi-square with dof (n) = 3 / 9 / 7 degrees of freedom for a
+        true match — compare it with OBSERVATION_GATE_CHI2_99[dof], no threshold is applied here; status (SLIDE_MISSING,
+        SLIDE_ERR_NOT_SPD; zeros then); C (n, 9, 9) = I + A H^-1 A^T, zero outside the dof x dof block, and r (n, 9), the whitened
+        innovation covariance and residual."""
+        rows = [tuple(c) for c in candidates]
+        n = len(rows)
+        k = max(n, 1)
+        robot, cls = np.zeros(k, np.int32), np.zeros(k, np.int32)
+        pidx, lidx, meas = np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.zeros((k, 17))
+        for i, c in enumerate(rows):
+            if c[0] not in _OBS_CLASSES:
+                raise SlideError(f"observation_mahalanobis: unknown candidate kind {c[0]!r}")
+            cls[i], robot[i], pidx[i], lidx[i] = _OBS_CLASSES[c[0]], c[1], c[2], c[3]
+            parts = [np.atleast_1d(_d(x)).ravel() for x in c[4:]]
+            v = np.concatenate(parts)
+            if len(v) != _OBS_NARGS[c[0]]:
+                raise SlideError(f"observation_mahalanobis: a {c[0]} candidate takes {_OBS_NARGS[c[0]]} measurement values, got {len(v)}")
+            meas[i, :len(v)] = v
+        d2, dof, Cm, r, status = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9)), np.zeros(k, np.int32)
+        _check(self.L.slide_graph_observation_mahalanobis(self.h, C.c_int(n), _p(robot), _p(pidx), _p(cls), _p(lidx), _p(meas), _p(d2),
+                                                          _p(dof), _p(Cm), _p(r), _p(status)))
+        return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
 
     def set_ghosts(self, own_robot, own_idx):
         r = _i(own_robot)

@@ -369,11 +369,14 @@ void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const 
   }
 }
 // The forward launches alone: W = L^-1 B (B overwritten).  B^T S^-1 B = W^T W needs no backward pass: T launches, not 2 T.
+// k0 > 0 (the short walk): B is zero above row k0 * NB, so W is zero there too and the launches of the block columns before k0 would
+// subtract zeros from the rows below; the caller has zeroed those rows of W, and the rows from k0 * NB on come out with the bits of
+// the walk from column 0 (y - 0 = y).
 void launch_multi_fwd(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* W,
-                      int nrhs, hipStream_t s) {
+                      int nrhs, hipStream_t s, int k0) {
   const int nT = T * NB, nch = (nrhs + 15) / 16;
   if (T <= 0 || nrhs <= 0) return;
-  for (int k = 0; k < T; ++k) {
+  for (int k = k0 < 0 ? 0 : k0; k < T; ++k) {
     const int i1 = prof ? prof[k] : T - 1;
     hipLaunchKernelGGL(k_sub_fwd, dim3(i1 - k + 1, nch), dim3(256), 0, s, S, ld, k, Ld + (size_t)k * NB * NB, Winv + (size_t)k * 1024,
                        B, W, nT, nrhs);

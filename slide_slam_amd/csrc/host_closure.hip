@@ -1,7 +1,8 @@
 // Host side of loop-closure selection: the mutually consistent subset of a list of loop closures (PCM on the clique solver through
 // host_clipper.hpp's solve_csr_segments; no counterpart in the reference, which adds the first closure that passes straight into the
 // graph: sloamNode.cpp:448-476, graphWrapper.cpp:55), and behind it the entry points that share its argument checks (pose-pair
-// covariances, the closures' Mahalanobis gate) and slide_find_relative_meas_match.
+// covariances, the closures' Mahalanobis gate), the observations' Mahalanobis gate with checks of its own in the same style, and
+// slide_find_relative_meas_match.
 #include <cmath>
 
 #include "capi_handles.hpp"
@@ -442,6 +443,38 @@ int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int
   if (rc != SLIDE_OK) { g_last_error = "closure_mahalanobis: " + g_last_error; return rc; }
   if (!b) { g_last_error = "closure_mahalanobis: the batch is NULL"; return SLIDE_ERR_INVALID; }
   return b->b.joint_closure_mahalanobis(L, from_slot, from_idx, to_slot, to_idx, rel7, sigma6, d2, C36, r6, status);
+}
+
+// The individual-compatibility gate of a list of candidate landmark observations (the closure gate's counterpart for the factors the
+// association produces).  The argument checks come first and need neither graph nor device; nothing is written on a refusal.
+int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
+                                        const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
+                                        int32_t* status) {
+  auto bad = [](const char* what) { g_last_error = std::string("observation_mahalanobis: ") + what; return SLIDE_ERR_INVALID; };
+  auto zero3 = [](const double* v) { return !(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0); };
+  auto zero_quat = [](const double* p7) { return !(p7[3] * p7[3] + p7[4] * p7[4] + p7[5] * p7[5] + p7[6] * p7[6] > 0.0); };
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!robot || !pose_idx || !cls || !lm_idx || !meas17 || !d2)) return bad("a needed pointer is NULL");
+  for (int k = 0; k < n; ++k)
+    if (!robot_ok(robot[k])) return bad("a robot outside [0, SLIDE_MAX_ROBOTS)");
+  for (int k = 0; k < n; ++k)
+    if (cls[k] != SLIDE_CLS_ELLIPSOID && cls[k] != SLIDE_CLS_CUBE && cls[k] != SLIDE_CLS_CYLINDER) return bad("a class that is not a landmark class");
+  if (n > 0 && !closure_finite(meas17, 17 * (size_t)n)) return bad("meas17 holds a non-finite value");
+  for (int k = 0; k < n; ++k) {
+    const double* a = meas17 + 17 * (size_t)k;
+    if (cls[k] == SLIDE_CLS_ELLIPSOID) {
+      if (zero3(a)) return bad("a zero bearing");
+      if (!(a[3] > 0.0)) return bad("a range <= 0");
+    } else if (cls[k] == SLIDE_CLS_CUBE) {
+      if (zero_quat(a) || zero_quat(a + 7)) return bad("a zero quaternion");
+    } else {
+      if (zero_quat(a)) return bad("a zero quaternion");
+      if (zero3(a + 10)) return bad("a zero ray");
+    }
+  }
+  if (!g) return bad("the graph is NULL");
+  LOCK(g);
+  return g->g.observation_mahalanobis(n, robot, pose_idx, cls, lm_idx, meas17, d2, dof, C81, r9, status);
 }
 
 // sloam::FindRelativeMeasurementMatch sloam.cpp:321-412 (host-side bookkeeping: a few dozen stamps per call)

@@ -257,30 +257,43 @@ int HostGraph::add_point_landmark(uint64_t idx, const double* xyz) {
   pend_vars.push_back(v);
   return SLIDE_OK;
 }
+// (the measurement as the three add calls store it — and as observation_mahalanobis evaluates a candidate: one text for both)
+void HostGraph::br_meas(const double* bearing, double range, double* z4) {
+  const double n = std::sqrt(bearing[0] * bearing[0] + bearing[1] * bearing[1] + bearing[2] * bearing[2]);
+  for (int i = 0; i < 3; ++i) z4[i] = bearing[i] / n;   // Pose3().bearing(p) = Unit3(p)  (graph.cpp:163)
+  z4[3] = range;
+}
+void HostGraph::cube_meas(const SE3& pose, const SE3& cube_world, const double* scale, double* z15, double* sigma9) const {
+  const SE3 loc = compose(inverse(pose), cube_world);             // cube_global_meas.project(pose.inverse()) graph.cpp:211
+  const double dist = std::max(norm(loc.t), 0.1);                 // graph.cpp:214
+  put12(loc, z15);
+  for (int i = 0; i < 3; ++i) z15[12 + i] = scale[i];
+  for (int i = 0; i < 9; ++i) sigma9[i] = P.noise_model_cube_vec[i] * dist;
+}
+void HostGraph::cyl_meas(const SE3& pose, const double* root, const double* ray, double radius, double* z7) {
+  const SE3 inv = inverse(pose);                                  // cylinder.project(pose.inverse()) graph.cpp:190
+  const V3 lr = transform_from(inv, V3{root[0], root[1], root[2]});
+  const V3 la = mul(inv.R, V3{ray[0], ray[1], ray[2]});
+  z7[0] = lr.x; z7[1] = lr.y; z7[2] = lr.z; z7[3] = la.x; z7[4] = la.y; z7[5] = la.z; z7[6] = radius;
+}
 int HostGraph::add_range_bearing(int robot, uint64_t pose_idx, uint64_t lm_idx, const double* bearing, double range) {
   if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
   PendFac f{};
   f.type = FT_BR;
   f.k0 = pose_key(robot, pose_idx);
   f.k1 = lm_key(SLIDE_CLS_ELLIPSOID, lm_idx);
-  const double n = std::sqrt(bearing[0] * bearing[0] + bearing[1] * bearing[1] + bearing[2] * bearing[2]);
-  for (int i = 0; i < 3; ++i) f.z[i] = bearing[i] / n;   // Pose3().bearing(p) = Unit3(p)  (graph.cpp:163)
-  f.z[3] = range;
+  br_meas(bearing, range, f.z);
   pend_facs.push_back(f);
   return SLIDE_OK;
 }
 int HostGraph::add_cube(int robot, uint64_t pose_idx, uint64_t cube_idx, const SE3& pose, const SE3& cube_world,
                         const double* scale, bool exists) {
   if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
-  const SE3 loc = compose(inverse(pose), cube_world);             // cube_global_meas.project(pose.inverse()) graph.cpp:211
-  const double dist = std::max(norm(loc.t), 0.1);                 // graph.cpp:214
   PendFac f{};
   f.type = FT_CUBE;
   f.k0 = pose_key(robot, pose_idx);
   f.k1 = lm_key(SLIDE_CLS_CUBE, cube_idx);
-  put12(loc, f.z);
-  for (int i = 0; i < 3; ++i) f.z[12 + i] = scale[i];
-  for (int i = 0; i < 9; ++i) f.sigma[i] = P.noise_model_cube_vec[i] * dist;
+  cube_meas(pose, cube_world, scale, f.z, f.sigma);
   pend_facs.push_back(f);
   if (!exists) {
     PendVar v{};
@@ -295,14 +308,11 @@ int HostGraph::add_cube(int robot, uint64_t pose_idx, uint64_t cube_idx, const S
 int HostGraph::add_cylinder(int robot, uint64_t pose_idx, uint64_t cyl_idx, const SE3& pose, const double* root,
                             const double* ray, double radius, bool exists) {
   if (!robot_ok(robot)) return SLIDE_ERR_INVALID;
-  const SE3 inv = inverse(pose);                                  // cylinder.project(pose.inverse()) graph.cpp:190
-  const V3 lr = transform_from(inv, V3{root[0], root[1], root[2]});
-  const V3 la = mul(inv.R, V3{ray[0], ray[1], ray[2]});
   PendFac f{};
   f.type = FT_CYL;
   f.k0 = pose_key(robot, pose_idx);
   f.k1 = lm_key(SLIDE_CLS_CYLINDER, cyl_idx);
-  f.z[0] = lr.x; f.z[1] = lr.y; f.z[2] = lr.z; f.z[3] = la.x; f.z[4] = la.y; f.z[5] = la.z; f.z[6] = radius;
+  cyl_meas(pose, root, ray, radius, f.z);
   pend_facs.push_back(f);
   if (!exists) {
     PendVar v{};

@@ -172,6 +172,8 @@ struct GainFetched { std::vector<double> M, Urow; };
 // writes the columns of candidates k0 .. k0 + nc - 1 into B (ld rows per column, zero before); done gets their grams on the device
 using FormFill = std::function<void(int k0, int nc, double* B, int ld)>;
 using FormDone = std::function<int(int k0, int nc, const double* M)>;
+// (optional, single graph only) the first block column the sweep's forward substitution has to walk: B is zero above row NB * it
+using FormStart = std::function<int(int k0, int nc)>;
 class CholBatch {
  public:
   explicit CholBatch(int n);
@@ -467,6 +469,15 @@ class HostGraph {
                             int32_t* status);
   int closure_mahalanobis(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
                           const double* rel7, const double* sigma6, double* d2, double* C36, double* r6, int32_t* status);
+  // the Mahalanobis gate of a list of candidate landmark observations (obs_gate_kernels.hip has the invariant): candidate k is the
+  // factor add_range_bearing / add_cube / add_cylinder would add between pose (robot, pose_idx) and the existing landmark (cls, lm_idx)
+  // from meas17[17 k ..], the class's remaining arguments in the add call's order; arguments checked by the C ABI
+  int observation_mahalanobis(int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
+                              const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status);
+  // what the three add calls store of their arguments (and the gate evaluates): z as br_z / cu_z / cy_z hold it, the cube's sigmas
+  static void br_meas(const double* bearing, double range, double* z4);
+  void cube_meas(const SE3& pose, const SE3& cube_world, const double* scale, double* z15, double* sigma9) const;
+  static void cyl_meas(const SE3& pose, const double* root, const double* ray, double radius, double* z7);
   void join_batch(CholBatch* b, int slot);      // takes the graph's lock itself (never while the batch's is held the other way round)
   int dist_pass_local(double* d_buf);     // one distributed pass when every robot of the job is in this graph's batch (no host syncs inside)
   int add_point_landmark(uint64_t idx, const double* xyz);
@@ -715,7 +726,7 @@ class HostGraph {
   DevArr<int> d_midx, d_igrc;
   DevArr<double> d_igval;
   int marginal_state(const char* who) const;      // SLIDE_ERR_INVALID (+ message) unless a single-graph factorisation is resident
-  int sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done);
+  int sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done, const FormStart& start = nullptr);
   int ensure_sigma();
   int pose_id(int robot, uint64_t idx) const;     // the uploaded pose's index, or -1
   void robot_poses(int robot, std::vector<int>& out) const;

@@ -650,6 +650,11 @@ struct FormBackend {
   int nrows = 0, nrows_neg = 0;
   std::function<int(Scratch& sc, int max_ncol)> alloc;
   std::function<void(int ncol)> fwd;
+  // the short walk (single graph, optional): start(k0, nc) = the first block column whose rows of B the sweep's candidates touch; the
+  // driver zeroes the rows of W above it and fwd walks from kb on.  The gram keeps its row range and split, so the bits are those of
+  // the walk from column 0.
+  FormStart start;
+  int kb = 0;
 };
 static int sigma_forms_core(const char* who, FormBackend& be, int ncand, int nk, const FormFill& fill, const FormDone& done) {
   hipStream_t s = be.s;
@@ -679,6 +684,8 @@ static int sigma_forms_core(const char* who, FormBackend& be, int ncand, int nk,
     const int nc = std::min(per, ncand - k0), ncol = nc * nk;
     SL_HIP(hipMemsetAsync(be.B, 0, (size_t)ncol * be.ld * sizeof(double), s));
     fill(k0, nc, be.B, (int)be.ld);
+    be.kb = be.start ? std::max(0, be.start(k0, nc)) : 0;
+    if (be.kb > 0) SL_HIP(hipMemset2DAsync(be.W, be.ld * sizeof(double), 0, (size_t)be.kb * NB * sizeof(double), (size_t)ncol, s));
     be.fwd(ncol);
     launch_gram_blocks(be.W, be.ld, be.rows, be.nrows, d_cd, nc, d_jobs, nc * jobs_per, d_part, d_M, s);
     if (be.nrows_neg > 0) {
@@ -691,7 +698,7 @@ static int sigma_forms_core(const char* who, FormBackend& be, int ncand, int nk,
   }
   return SLIDE_OK;
 }
-int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done, const FormStart& start) {
   hipStream_t s = stream;
   const int T = G.T, nT = T * NB;
   const bool dense = h_prof.size() != (size_t)T;
@@ -702,7 +709,8 @@ int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& f
     be.W = sc.alloc<double>((size_t)max_ncol * nT);
     return SLIDE_OK;
   };
-  be.fwd = [&](int ncol) { launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), be.B, be.W, ncol, s); };
+  be.start = start;
+  be.fwd = [&](int ncol) { launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), be.B, be.W, ncol, s, std::min(be.kb, T - 1)); };
   return sigma_forms_core(who, be, ncand, nk, fill, done);
 }
 // Marginals::jointMarginalCovariance of n pose pairs: out144n[144 k ..] the 12 x 12 row-major block [[Saa, Sab], [Sba, Sbb]] of pair k
@@ -815,6 +823,106 @@ int HostGraph::closure_mahalanobis(int L, const int32_t* from_robot, const uint6
         }
         return SLIDE_OK;
       });
+}
+// The individual-compatibility test of n candidate landmark observations against the resident factor — the closure gate's counterpart
+// for the factors that make up most of a graph (obs_gate_kernels.hip has the invariant).  Candidate k is the factor
+// add_range_bearing / add_cube / add_cylinder would add between pose (robot, pose_idx) and the EXISTING landmark (cls, lm_idx): z and
+// the sigmas by the add calls' own text (br_meas / cube_meas / cyl_meas; bearing_range_sigma, noise_model_cube_vec x max(|loc.t|, 0.1),
+// cylinder_sigma), r and A = [Ap | Al] at the current estimate by k_obs_gate_lin, no robust weight.  C = I + Al H_ll^-1 Al^T + W^T W
+// with L W = B, d2 = r^T C^-1 r (k_obs_gate_finish): chi-square with dof = 3 / 9 / 7 for a true match not yet added; no threshold is
+// applied.  The candidates are grouped by class and run through sigma_forms with nk = 3, 9, 7 (128, 42, 54 candidates per sweep);
+// results go back in the caller's order.  A sweep starts its forward substitution at the block column of the lowest pose it touches
+// (the candidates' poses and their landmarks' first observers): a frame's detections sit at the newest pose and see recent landmarks.
+// Per sweep: one linearise-and-fill launch, T - k0 substitution launches, two gram launches, one finish launch, one read-back.
+// status[k]: SLIDE_MISSING (a pose or landmark the graph does not hold), SLIDE_ERR_NOT_SPD (C_k); zeros in its outputs then.
+// Whole-call refusals as pose_covariances, nothing written.  Arguments checked by the caller.
+int HostGraph::observation_mahalanobis(int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
+                                       const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status) {
+  int rc = marginal_state("observation_mahalanobis");
+  if (rc != SLIDE_OK) return rc;
+  struct Group { int type = 0; std::vector<int32_t> pid, lid; std::vector<double> z, sg; std::vector<int> ids; };
+  Group groups[3];
+  groups[0].type = FT_BR; groups[1].type = FT_CUBE; groups[2].type = FT_CYL;
+  for (int k = 0; k < n; ++k) {
+    d2[k] = 0.0;
+    for (int e = 0; C81 && e < 81; ++e) C81[81 * (size_t)k + e] = 0.0;
+    for (int e = 0; r9 && e < 9; ++e) r9[9 * (size_t)k + e] = 0.0;
+    if (dof) dof[k] = landmark_dim(cls[k]);
+    const int p = pose_id(robot[k], pose_idx[k]), l = lm_lid(cls[k], lm_idx[k]);
+    const int st = p < 0 || l < 0 || lm_fids[l].empty() ? SLIDE_MISSING : SLIDE_OK;
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    const double* a = meas17 + 17 * (size_t)k;
+    double z[15] = {}, sg[9] = {};
+    Group& g = groups[cls[k] == SLIDE_CLS_ELLIPSOID ? 0 : cls[k] == SLIDE_CLS_CUBE ? 1 : 2];
+    if (g.type == FT_BR) {
+      br_meas(a, a[3], z);
+      for (int i = 0; i < 3; ++i) sg[i] = P.bearing_range_sigma;
+    } else if (g.type == FT_CUBE) {
+      cube_meas(from7(a), from7(a + 7), a + 14, z, sg);
+    } else {
+      cyl_meas(from7(a), a + 7, a + 10, a[13], z);
+      for (int i = 0; i < 7; ++i) sg[i] = P.cylinder_sigma;
+    }
+    g.pid.push_back(p); g.lid.push_back(l); g.ids.push_back(k);
+    g.z.insert(g.z.end(), z, z + 15);
+    g.sg.insert(g.sg.end(), sg, sg + 9);
+  }
+  hipStream_t s = stream;
+  const char* fw = std::getenv("SLIDE_OBS_GATE_FULL_WALK");      // (measurement aid: every sweep walks from block column 0)
+  const bool full_walk = fw && fw[0] == '1';
+  for (Group& g : groups) {
+    if (g.ids.empty()) continue;
+    const int m = (int)g.ids.size(), nk = lf_rows(g.type), max_nc = std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / nk);
+    Scratch sc(s);
+    int32_t* d_pid = sc.alloc<int32_t>(m);
+    int32_t* d_lid = sc.alloc<int32_t>(m);
+    double* d_z = sc.alloc<double>(15 * (size_t)m);
+    double* d_sg = sc.alloc<double>(9 * (size_t)m);
+    double* d_r = sc.alloc<double>(9 * (size_t)max_nc);
+    double* d_G0 = sc.alloc<double>(81 * (size_t)max_nc);
+    double* d_out = sc.alloc<double>(OBS_GATE_OUT * (size_t)max_nc);
+    int* d_flag = sc.alloc<int>(max_nc);
+    if (!sc.ok()) { g_last_error = "observation_mahalanobis: out of device memory"; return SLIDE_ERR_HIP; }
+    SL_HIP(sc.upload(d_pid, g.pid));
+    SL_HIP(sc.upload(d_lid, g.lid));
+    SL_HIP(sc.upload(d_z, g.z));
+    SL_HIP(sc.upload(d_sg, g.sg));
+    std::vector<double> h(OBS_GATE_OUT * (size_t)max_nc);
+    std::vector<int> hflag(max_nc);
+    rc = sigma_forms(
+        "observation_mahalanobis", m, nk,
+        [&](int k0, int nc, double* B, int nT) {
+          launch_obs_gate_lin(G, g.type, d_pid + k0, d_lid + k0, d_z + 15 * (size_t)k0, d_sg + 9 * (size_t)k0, nc, B, nT, d_r, d_G0, s);
+        },
+        [&](int k0, int nc, const double* M) -> int {
+          launch_obs_gate_finish(nk, M, d_G0, d_r, nc, d_out, d_flag, s);
+          SL_HIP(hipGetLastError());
+          SL_HIP(hipMemcpyAsync(h.data(), d_out, OBS_GATE_OUT * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+          SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+          SL_HIP(hipStreamSynchronize(s));
+          for (int i = 0; i < nc; ++i) {
+            const size_t k = (size_t)g.ids[k0 + i];
+            if (hflag[i]) {
+              if (status) status[k] = SLIDE_ERR_NOT_SPD;
+              continue;
+            }
+            const double* o = h.data() + OBS_GATE_OUT * (size_t)i;
+            d2[k] = o[0];
+            if (C81) std::copy(o + 1, o + 82, C81 + 81 * k);
+            if (r9) std::copy(o + 82, o + 91, r9 + 9 * k);
+          }
+          return SLIDE_OK;
+        },
+        [&](int k0, int nc) -> int {
+          if (full_walk) return 0;
+          int lo = 1 << 30;
+          for (int i = k0; i < k0 + nc; ++i) lo = std::min(lo, std::min((int)g.pid[i], h_lm_first[g.lid[i]]));
+          return std::min((6 * lo) / NB, G.T - 1);
+        });
+    if (rc != SLIDE_OK) return rc;
+  }
+  return SLIDE_OK;
 }
 
 // ---- marginals on the joint graph: the selected inverse over the exact joint pass's factor (joint_cov_kernels.hip) -------

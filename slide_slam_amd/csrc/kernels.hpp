@@ -135,8 +135,9 @@ void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, co
 void launch_multi_solve(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* X,
                         int nrhs, hipStream_t s);      // X = S^-1 B (B: nrhs columns of T * NB rows, overwritten)
 // the forward half of launch_multi_solve on its own: W = L^-1 B (S = L L^T; B overwritten), so that B^T S^-1 B = W^T W
+// (k0: the first block column walked — the caller knows B is zero above row k0 * NB and has zeroed those rows of W)
 void launch_multi_fwd(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, double* B, double* W,
-                      int nrhs, hipStream_t s);
+                      int nrhs, hipStream_t s, int k0 = 0);
 void launch_gram(const double* X, size_t ldx, int ncol, const int* rows, int nrows, double* M, hipStream_t s);
 void launch_landmark_V(const GraphDev& G, const double* U, int nT, int ncol, const int* lids, int n, double* V, size_t ldv, hipStream_t s,
                        const int* prow = nullptr);      // prow: a pose's first row in U (null: 6 p)
@@ -417,5 +418,15 @@ void launch_joint_pair_identity(const JointPoseTab* tab, const int4* ends, int n
 void launch_gram_sub(double* M, const double* Mneg, size_t n, hipStream_t s);      // M <- M - Mneg (the lambda rows' gram: D = -I there)
 // M: the candidates' 6 x 6 grams W_k^T W_k (36 each); out: GATE_OUT per candidate; flag[k] = 1 where I + M is not positive definite
 void launch_closure_gate_finish(const double* M, const double* r6, int n, double* out, int* flag, hipStream_t s);
+
+// The individual-compatibility gate of landmark observations (obs_gate_kernels.hip has the invariant).  One launch serves candidates of
+// one class (type: FT_BR / FT_CUBE / FT_CYL, m = lf_rows(type) rows and columns each); candidate k of a sweep owns the columns
+// m k .. m k + m - 1 of B (nT rows, zero before the launch).  pid / lid: its pose and landmark ids; z15 / sg9: its measurement as the
+// class's z array holds it and its sigmas (15 / 9 per candidate); r9: the whitened residuals; G0: Al H_ll^-1 Al^T (81 per candidate,
+// m x m packed).  M: the candidates' m x m grams; out: OBS_GATE_OUT per candidate; flag[k] = 1 where C is not positive definite.
+constexpr int OBS_GATE_OUT = 91;      // per candidate: d2, C (81, row-major, leading dimension 9), r (9)
+void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const int32_t* lid, const double* z15, const double* sg9, int n,
+                         double* B, int nT, double* r9, double* G0, hipStream_t s);
+void launch_obs_gate_finish(int m, const double* M, const double* G0, const double* r9, int n, double* out, int* flag, hipStream_t s);
 
 }  // namespace sl

@@ -1,0 +1,250 @@
+// The individual-compatibility gate of landmark observations: one candidate observation against what the graph already knows about its
+// pose AND its landmark (slide_graph_observation_mahalanobis).  No counterpart in the reference, whose association accepts a match on
+// a Euclidean threshold alone (sloam.cpp:73-203); GTSAM users would assemble it from Marginals::jointMarginalCovariance({X(i), L(j)}).
+//
+// A candidate is the factor slide_graph_add_range_bearing / _add_cube / _add_cylinder would add between pose p and the EXISTING landmark
+// l of dimension D (3 / 9 / 7); it has m = D rows.  r (m) and A = [Ap | Al] (m x 6, m x D) are its whitened residual and Jacobian at
+// the current estimate (pose_est, lm_est), no robust weight applied.  With H the full system as last linearised and S = L L^T its
+// landmark-eliminated pose system,
+//     C  = I + A H^-1 A^T = I + Al H_ll^-1 Al^T + B^T S^-1 B,      B = P_p^T Ap^T - sum_{f in factors(l)} P_{p_f}^T F_f Al^T,
+//     d2 = r^T C^-1 r,
+// F_f = E_f H_ll^-1 the 6 x D block of the factor's Schur record (ebuf + lf_eoff[f] + 6 D, as k_lm_cov and k_lm_V read it) and
+// H_ll^-1 the landmark's block of lm_Hinv: the pose-landmark cross block of the marginal is never formed.  B^T S^-1 B = W^T W with
+// L W = B is the forward substitution and gram of sigma_forms (host_marginals.hip); candidate k of a sweep owns the columns
+// m k .. m k + m - 1 of B.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+
+namespace sl {
+
+// (the error functions of the cube and cylinder factors, restated from solver_kernels.hip: cubeFactor.cpp:35, cylinderFactor.cpp:35)
+__device__ __forceinline__ void og_cube_err(const SE3& X, const SE3& C, const double* cs, const double* z, double* e) {
+  const SE3 M = from12(z);
+  const SE3 err = compose(inverse(C), compose(X, M));
+  se3_log(err, e);
+  e[6] = z[12] - cs[0]; e[7] = z[13] - cs[1]; e[8] = z[14] - cs[2];
+}
+__device__ __forceinline__ void og_cyl_err(const SE3& X, const double* q, const double* z, double* e) {
+  const V3 root = transform_from(X, V3{z[0], z[1], z[2]});
+  const V3 ray = mul(X.R, V3{z[3], z[4], z[5]});
+  e[0] = q[3] - ray.x; e[1] = q[4] - ray.y; e[2] = q[5] - ray.z;
+  e[3] = q[0] - root.x; e[4] = q[1] - root.y; e[5] = q[2] - root.z;
+  e[6] = z[6] - q[6];
+}
+
+// k_obs_gate_lin, one wavefront per candidate.  `type` (FT_BR / FT_CUBE / FT_CYL) is the launch's: the host groups candidates by class.
+// pid / lid: the candidate's pose and landmark ids; z15: its measurement as br_z / cu_z / cy_z hold it (4 / 15 / 7 used of 15); sg9: its
+// sigmas (m used of 9).  The three branches restate k_lin_lf_body's (solver_kernels.hip) at pose_est / lm_est: analytic for
+// bearing-range (lane 0), central differences through the variables' own retract for cubes and cylinders (lane = 2 column + sign
+// within 32 lanes, lanes 30 / 31 the unperturbed error; the upper 32 lanes repeat the lower ones and store nothing).  The record
+// [r | Ap | Al] is staged in LDS in jbuf's layout.  Then lane 6 j + a owns the entries (row 6 q + a, column m k + j) of B for every pose
+// q: Ap[j][a] at the candidate's pose, minus sum_c F_f[a][c] Al[j][c] at the pose of every factor f of the landmark, in the order of
+// lm_fids — the same lane reads and writes the same entry every time, so a pose met twice (the candidate's own pose observing l, a
+// pose holding two factors on l) is an ordered read-modify-write, and no atomics are needed.  B is zero before the launch and the
+// candidates own disjoint columns.  Stored for the finish: r (9 per candidate) and G0 = Al H_ll^-1 Al^T (81 per candidate, m x m
+// packed), one triangle computed and mirrored.
+__global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const int32_t* __restrict__ pid, const int32_t* __restrict__ lid,
+                                                     const double* __restrict__ z15, const double* __restrict__ sg9, int n,
+                                                     double* __restrict__ B, int nT, double* __restrict__ r9, double* __restrict__ G0) {
+  __shared__ double rec[144];
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int p = pid[k], l = lid[k];
+  const int m = lf_rows(type), D = m;
+  const SE3 X = from12(G.pose_est + 12 * (size_t)p);
+  const double* lv = G.lm_est + 15 * (size_t)l;
+  const double* z = z15 + 15 * (size_t)k;
+  const double* sg = sg9 + 9 * (size_t)k;
+  double* Jp = rec + m;
+  double* Jl = rec + 7 * m;
+  const int j = lane & 31, col = j >> 1;
+  const bool st = lane < 32;
+  const double dl = G.numdiff_delta, fac = 1.0 / (2.0 * dl);
+  const double d = (j & 1) ? -dl : dl;
+  if (type == FT_BR) {
+    const double w = 1.0 / sg[0];
+    const V3 q = transform_to(X, V3{lv[0], lv[1], lv[2]});
+    const double rho = norm(q);
+    const V3 b = (1.0 / rho) * q;
+    double e2[2];
+    sphere_local(V3{z[0], z[1], z[2]}, b, e2);
+    V3 b1, b2;
+    sphere_basis(b, b1, b2);
+    double Dm[9];
+    const double bb[3] = {b.x, b.y, b.z}, c1[3] = {b1.x, b1.y, b1.z}, c2[3] = {b2.x, b2.y, b2.z};
+#pragma unroll
+    for (int jj = 0; jj < 3; ++jj) {
+      double s1 = 0, s2 = 0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double dn = ((i == jj ? 1.0 : 0.0) - bb[i] * bb[jj]) / rho;
+        s1 += c1[i] * dn; s2 += c2[i] * dn;
+      }
+      Dm[jj] = s1; Dm[3 + jj] = s2; Dm[6 + jj] = bb[jj];
+    }
+    const M3 Q = hat(q);
+    if (lane == 0) {
+      rec[0] = e2[0] * w; rec[1] = e2[1] * w; rec[2] = (rho - z[3]) * w;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) {
+          double s = 0, u = 0;
+#pragma unroll
+          for (int kk = 0; kk < 3; ++kk) { s += Dm[3 * r + kk] * Q.a[3 * kk + jj]; u += Dm[3 * r + kk] * X.R.a[3 * jj + kk]; }
+          Jp[6 * r + jj] = s * w;
+          Jp[6 * r + 3 + jj] = -Dm[3 * r + jj] * w;
+          Jl[3 * r + jj] = u * w;
+        }
+    }
+  } else if (type == FT_CUBE) {
+    const SE3 C = from12(lv);
+    double dX[6], dC[6], cs[3];
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk) { dX[kk] = (col == kk) ? d : 0.0; dC[kk] = (col == 6 + kk) ? d : 0.0; }
+#pragma unroll
+    for (int kk = 0; kk < 3; ++kk) cs[kk] = lv[12 + kk] + ((col == 12 + kk) ? d : 0.0);
+    double e[9];
+    og_cube_err(retract(X, dX, G.chart), retract(C, dC, G.chart), cs, z, e);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
+      if (st && j == 30) rec[i] = hx * w;
+      if (st && (j & 1) == 0 && col < 15) {
+        const double v = ((e[i] - hx) - (eo - hx)) * fac * w;
+        if (col < 6) Jp[6 * i + col] = v;
+        else Jl[9 * i + col - 6] = v;
+      }
+    }
+  } else {
+    const int jl = col - 6;
+    const int vi = jl < 0 ? -1 : (jl < 3 ? jl + 3 : (jl < 6 ? jl - 3 : (jl == 6 ? 6 : -1)));      // tangent [ray, root, radius] onto [root, ray, radius]
+    double dX[6], q[7];
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk) dX[kk] = (col == kk) ? d : 0.0;
+#pragma unroll
+    for (int kk = 0; kk < 7; ++kk) q[kk] = lv[kk] + ((vi == kk) ? d : 0.0);
+    double e[7];
+    og_cyl_err(retract(X, dX, G.chart), q, z, e);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
+      if (st && j == 30) rec[i] = hx * w;
+      if (st && (j & 1) == 0 && col < 13) {
+        const double v = ((e[i] - hx) - (eo - hx)) * fac * w;
+        if (col < 6) Jp[6 * i + col] = v;
+        else Jl[7 * i + jl] = v;
+      }
+    }
+  }
+  __syncthreads();
+  const int f0 = G.lm_ptr[l], f1 = G.lm_ptr[l + 1];
+  if (lane < 6 * m) {
+    const int jc = lane / 6, a = lane - 6 * jc;
+    double* colB = B + (size_t)(m * k + jc) * nT;
+    colB[6 * (size_t)p + a] = Jp[6 * jc + a];
+    for (int qf = f0; qf < f1; ++qf) {
+      const int f = G.lm_fids[qf];
+      const double* F = G.ebuf + G.lf_eoff[f] + 6 * D + a * D;
+      double s = 0.0;
+      for (int c = 0; c < D; ++c) s += F[c] * Jl[jc * D + c];
+      double* at = colB + 6 * (size_t)G.lf_pose[f] + a;
+      *at = *at - s;
+    }
+  }
+  if (lane < m * (m + 1) / 2) {
+    int i = 0;
+    while ((i + 1) * (i + 2) / 2 <= lane) ++i;
+    const int jc = lane - i * (i + 1) / 2;      // (i >= jc)
+    const double* Hi = G.lm_Hinv + 81 * (size_t)l;
+    double s = 0.0;
+    for (int c = 0; c < D; ++c) {
+      double t = 0.0;
+      for (int dd = 0; dd < D; ++dd) t += Hi[c * D + dd] * Jl[jc * D + dd];
+      s += Jl[i * D + c] * t;
+    }
+    G0[81 * (size_t)k + m * i + jc] = s;
+    G0[81 * (size_t)k + m * jc + i] = s;
+  }
+  if (lane < m) r9[9 * (size_t)k + lane] = rec[lane];
+}
+void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const int32_t* lid, const double* z15, const double* sg9, int n,
+                         double* B, int nT, double* r9, double* G0, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_obs_gate_lin, dim3(n), dim3(64), 0, s, G, type, pid, lid, z15, sg9, n, B, nT, r9, G0);
+}
+
+// k_obs_gate_finish, one wavefront per candidate (four to a workgroup): C = (I + G0) + M, M the candidate's m x m gram W_k^T W_k at
+// m m k; entries (a, b) and (b, a) are one sum of the same operands, so C is symmetric bit for bit.  Lane 0 factors C = G G^T in
+// registers, solves G y = r and forms d2 = y^T y.  A pivot that is not > 0: flag[k] = 1 and zeros.  out: OBS_GATE_OUT doubles per
+// candidate, [d2 | C row-major, leading dimension 9, zero outside the m x m block (81) | r (9)].
+template <int M>
+__global__ __launch_bounds__(256) void k_obs_gate_finish(const double* __restrict__ Mg, const double* __restrict__ G0,
+                                                         const double* __restrict__ r9, int n, double* __restrict__ out,
+                                                         int* __restrict__ flag) {
+  __shared__ double Cs[4][M * M];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + wv;
+  if (k < n)
+    for (int e = lane; e < M * M; e += 64) {
+      const int a = e / M, b = e - M * a, hi = a > b ? a : b, lo = a > b ? b : a;
+      Cs[wv][e] = ((a == b ? 1.0 : 0.0) + G0[81 * (size_t)k + M * hi + lo]) + Mg[(size_t)(M * M) * k + M * hi + lo];
+    }
+  __syncthreads();
+  if (k >= n) return;
+  double d2 = 0.0;
+  int bad = 0;
+  if (lane == 0) {
+    double Gm[M][M], y[M];
+    bool spd = true;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double d = Cs[wv][(M + 1) * j];
+#pragma unroll
+      for (int q = 0; q < j; ++q) d -= Gm[j][q] * Gm[j][q];
+      if (!(d > 0.0)) spd = false;
+      const double g = sqrt(spd ? d : 1.0);
+      Gm[j][j] = g;
+#pragma unroll
+      for (int i = j + 1; i < M; ++i) {
+        double v = Cs[wv][M * i + j];
+#pragma unroll
+        for (int q = 0; q < j; ++q) v -= Gm[i][q] * Gm[j][q];
+        Gm[i][j] = v / g;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double v = r9[9 * (size_t)k + i];
+#pragma unroll
+      for (int q = 0; q < i; ++q) v -= Gm[i][q] * y[q];
+      y[i] = v / Gm[i][i];
+      d2 += y[i] * y[i];
+    }
+    bad = spd ? 0 : 1;
+    flag[k] = bad;
+  }
+  d2 = __shfl(d2, 0);
+  bad = __shfl(bad, 0);
+  double* o = out + OBS_GATE_OUT * (size_t)k;
+  for (int e = lane; e < OBS_GATE_OUT; e += 64) {
+    double v = 0.0;
+    if (!bad) {
+      if (e == 0) v = d2;
+      else if (e < 82) {
+        const int a = (e - 1) / 9, b = (e - 1) - 9 * a;
+        if (a < M && b < M) v = Cs[wv][M * a + b];
+      } else if (e - 82 < M) v = r9[9 * (size_t)k + e - 82];
+    }
+    o[e] = v;
+  }
+}
+void launch_obs_gate_finish(int m, const double* Mg, const double* G0, const double* r9, int n, double* out, int* flag, hipStream_t s) {
+  if (n <= 0) return;
+  const dim3 grid((n + 3) / 4), block(256);
+  if (m == 3) hipLaunchKernelGGL(k_obs_gate_finish<3>, grid, block, 0, s, Mg, G0, r9, n, out, flag);
+  else if (m == 7) hipLaunchKernelGGL(k_obs_gate_finish<7>, grid, block, 0, s, Mg, G0, r9, n, out, flag);
+  else hipLaunchKernelGGL(k_obs_gate_finish<9>, grid, block, 0, s, Mg, G0, r9, n, out, flag);
+}
+
+}  // namespace sl
