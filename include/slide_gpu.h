@@ -318,6 +318,34 @@ int slide_chol_batch_get_pose_pair_covariances(slide_chol_batch_t* b, int n, con
 int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot,
                                          const uint64_t* to_idx, const double* rel7, const double* sigma6, double* d2, double* C36 /* may be NULL */,
                                          double* r6 /* may be NULL */, int32_t* status /* may be NULL */);
+/* slide_graph_observation_mahalanobis on the JOINT graph: the individual-compatibility gate of candidate landmark observations that
+ * call refuses for a graph joined to a batch.  The robots of an exact pass are coupled almost entirely through shared landmarks, so a
+ * false match onto one of them lands in the separator and pulls every robot that sees it; and one kind of candidate has no
+ * single-graph form at all: robot a's pose against a landmark only robot b has mapped, the would-be new shared landmark.  No
+ * counterpart in the reference.
+ * Candidate k names a pose (pose_slot[k], pose_idx[k]) and an existing landmark (lm_slot[k], cls[k], lm_idx[k]), lm_idx the
+ * landmark's index in the graph of lm_slot; the two slots may differ, and lm_slot == NULL means the pose's slot throughout.  meas17,
+ * r, A = [Ap | Al], the outputs and the sweeps are the single-graph call's: the noise the POSE's graph would choose, no robust weight,
+ * the device-resident estimates (the pose of its graph, the landmark of its own), the pose retracted under its graph's pose_chart and
+ * the landmark under its own graph's.  K = L D L^T is the joint system the last whole exact pass factored, and
+ *     C = I + G0 + B^T K^-1 B = I + G0 + W^T D W,   L W = B,   d2[k] = r^T C^-1 r.
+ * A private landmark (no shared slot in its graph) is eliminated, as on one graph: G0 = Al H_ll^-1 Al^T and
+ * B = P_p^T Ap^T - sum_{f in factors(l)} P_{p_f}^T F_f Al^T in joint rows, the factors' poses being poses of the LANDMARK's graph.  A
+ * shared landmark is a separator variable the pass does not eliminate: G0 = 0 and B = P_p^T Ap^T + P_l^T Al^T, P_l selecting the
+ * landmark's rows of the separator system (entered once, whichever replica names it, so any robot's replica gives the same bits).  The signed gram counts every
+ * coordinate once, the lambda rows of the inter-robot relative-pose factors with D = -I (slide_chol_batch_closure_mahalanobis above).
+ * Every sweep walks the whole forward half of the joint substitution; a candidate's bits do not depend on the rest of the list.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written): the argument checks of slide_graph_observation_mahalanobis in its own
+ * words, made before the batch or the device is looked at (lm_slot, where given, is checked like pose_slot; the batch is NULL), then
+ * those of slide_chol_batch_get_pose_covariances (no whole exact pass yet, the graphs changed since, PCG passes).  Per candidate, with
+ * zeros in its outputs: SLIDE_MISSING for a slot the batch does not have, a pose or landmark its graph does not hold, or a landmark
+ * with neither a factor nor a shared slot; SLIDE_ERR_NOT_SPD when C has a pivot that is not positive.  n == 0 on a batch that would be
+ * served: SLIDE_OK.  Runs on the batch's stream outside any capture and writes nothing a pass reads; the cached joint Sigma is neither
+ * used nor touched. */
+int slide_chol_batch_observation_mahalanobis(slide_chol_batch_t* b, int n, const int32_t* pose_slot, const uint64_t* pose_idx,
+                                             const int32_t* lm_slot /* may be NULL */, const int32_t* cls, const uint64_t* lm_idx,
+                                             const double* meas17, double* d2, int32_t* dof /* may be NULL */, double* C81 /* may be NULL */,
+                                             double* r9 /* may be NULL */, int32_t* status /* may be NULL */);
 /* ---- Robust loss on the exact joint multi-robot pass ------------------------------------------------------------------------------
  * No counterpart in the reference (its inter-robot factors are plain Between factors, graph.cpp:247-258); GTSAM users know it as
  * noiseModel::Robust on the closures of the joint graph.  slide_graph_set_robust_loss's rule, kinds, defaults and class_mask, as a

@@ -47,7 +47,7 @@ EXPORTS = [
     "slide_graph_set_robust_loss", "slide_graph_get_closure_weights",
     "slide_graph_set_observation_loss", "slide_graph_get_observation_weights",
     "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
-    "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis",
+    "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis", "slide_chol_batch_observation_mahalanobis",
     "slide_chol_batch_set_observation_loss", "slide_chol_batch_get_observation_weights", "slide_chol_batch_profile_linearize",
 ]
 
@@ -61,6 +61,31 @@ class SlideError(RuntimeError):
 OBSERVATION_GATE_CHI2_99 = {3: 11.345, 7: 18.475, 9: 21.666}
 _OBS_CLASSES = {"cylinder": 0, "cube": 1, "point": 2}      # SLIDE_CLS_*
 _OBS_NARGS = {"point": 4, "cube": 17, "cylinder": 14}
+_OBS_NPARTS = {"point": 2, "cube": 3, "cylinder": 4}      # measurement arguments of a candidate tuple
+
+
+def _observation_arrays(candidates, with_lm_slot):
+    """The candidate tuples of observation_mahalanobis as the C call's arrays (one spare row for an empty list).  with_lm_slot: a
+    tuple may carry one more trailing value, the landmark's slot (CholBatch); the last array is then the landmarks' slots."""
+    rows = [tuple(c) for c in candidates]
+    n = len(rows)
+    k = max(n, 1)
+    robot, cls, lslot = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+    pidx, lidx, meas = np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.zeros((k, 17))
+    for i, c in enumerate(rows):
+        if c[0] not in _OBS_CLASSES:
+            raise SlideError(f"observation_mahalanobis: unknown candidate kind {c[0]!r}")
+        cls[i], robot[i], pidx[i], lidx[i] = _OBS_CLASSES[c[0]], c[1], c[2], c[3]
+        rest = c[4:]
+        lslot[i] = robot[i]
+        if with_lm_slot and len(rest) == _OBS_NPARTS[c[0]] + 1:
+            lslot[i], rest = int(rest[-1]), rest[:-1]
+        parts = [np.atleast_1d(_d(x)).ravel() for x in rest]
+        v = np.concatenate(parts)
+        if len(v) != _OBS_NARGS[c[0]]:
+            raise SlideError(f"observation_mahalanobis: a {c[0]} candidate takes {_OBS_NARGS[c[0]]} measurement values, got {len(v)}")
+        meas[i, :len(v)] = v
+    return n, k, robot, pidx, cls, lidx, meas, lslot
 
 
 class Params(C.Structure):
@@ -448,20 +473,7 @@ class SlideGraph:
         true match — compare it with OBSERVATION_GATE_CHI2_99[dof], no threshold is applied here; status (SLIDE_MISSING,
         SLIDE_ERR_NOT_SPD; zeros then); C (n, 9, 9) = I + A H^-1 A^T, zero outside the dof x dof block, and r (n, 9), the whitened
         innovation covariance and residual."""
-        rows = [tuple(c) for c in candidates]
-        n = len(rows)
-        k = max(n, 1)
-        robot, cls = np.zeros(k, np.int32), np.zeros(k, np.int32)
-        pidx, lidx, meas = np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.zeros((k, 17))
-        for i, c in enumerate(rows):
-            if c[0] not in _OBS_CLASSES:
-                raise SlideError(f"observation_mahalanobis: unknown candidate kind {c[0]!r}")
-            cls[i], robot[i], pidx[i], lidx[i] = _OBS_CLASSES[c[0]], c[1], c[2], c[3]
-            parts = [np.atleast_1d(_d(x)).ravel() for x in c[4:]]
-            v = np.concatenate(parts)
-            if len(v) != _OBS_NARGS[c[0]]:
-                raise SlideError(f"observation_mahalanobis: a {c[0]} candidate takes {_OBS_NARGS[c[0]]} measurement values, got {len(v)}")
-            meas[i, :len(v)] = v
+        n, k, robot, pidx, cls, lidx, meas, _ = _observation_arrays(candidates, False)
         d2, dof, Cm, r, status = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9)), np.zeros(k, np.int32)
         _check(self.L.slide_graph_observation_mahalanobis(self.h, C.c_int(n), _p(robot), _p(pidx), _p(cls), _p(lidx), _p(meas), _p(d2),
                                                           _p(dof), _p(Cm), _p(r), _p(status)))
@@ -738,6 +750,19 @@ class CholBatch:
         _check(self.L.slide_chol_batch_closure_mahalanobis(C.c_void_p(self.h), C.c_int(L), _p(fs), _p(fi), _p(ts), _p(ti), _p(rel), _p(sg),
                                                            _p(d2), _p(Cm), _p(r), _p(status)))
         return {"d2": d2[:L], "status": status[:L], "C": Cm[:L], "r": r[:L]}
+
+    def observation_mahalanobis(self, candidates):
+        """slide_chol_batch_observation_mahalanobis: SlideGraph.observation_mahalanobis on the JOINT graph.  candidates: that call's
+        tuples with a slot of the batch where they name a robot — ("point", slot, pose_idx, lm_idx, bearing, range), ("cube", slot,
+        pose_idx, idx, pose7, cube7, scale), ("cylinder", slot, pose_idx, idx, pose7, root, ray, radius) — and optionally one more
+        trailing value, lm_slot: the slot whose graph holds the landmark (idx is then its index THERE), for robot a's pose against a
+        landmark of robot b.  Returns the same dict: d2 to compare with OBSERVATION_GATE_CHI2_99[dof] (no threshold is applied), dof,
+        status (SLIDE_MISSING, SLIDE_ERR_NOT_SPD; zeros then), C (n, 9, 9) and r (n, 9).  The batch is only read."""
+        n, k, slot, pidx, cls, lidx, meas, lslot = _observation_arrays(candidates, True)
+        d2, dof, Cm, r, status = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9)), np.zeros(k, np.int32)
+        _check(self.L.slide_chol_batch_observation_mahalanobis(C.c_void_p(self.h), C.c_int(n), _p(slot), _p(pidx), _p(lslot), _p(cls), _p(lidx),
+                                                               _p(meas), _p(d2), _p(dof), _p(Cm), _p(r), _p(status)))
+        return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
 
     def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
         """slide_chol_batch_set_robust_loss: SlideGraph.set_robust_loss's loss (same kinds, names and defaults) on the exact joint

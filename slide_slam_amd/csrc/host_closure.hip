@@ -447,16 +447,17 @@ int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int
 
 // The individual-compatibility gate of a list of candidate landmark observations (the closure gate's counterpart for the factors the
 // association produces).  The argument checks come first and need neither graph nor device; nothing is written on a refusal.
-int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
-                                        const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
-                                        int32_t* status) {
-  auto bad = [](const char* what) { g_last_error = std::string("observation_mahalanobis: ") + what; return SLIDE_ERR_INVALID; };
+static int obs_gate_bad(const char* what) { g_last_error = std::string("observation_mahalanobis: ") + what; return SLIDE_ERR_INVALID; }
+// (the list's own checks, shared with the batch's call: robot2, or null, is its second list of slots)
+static int obs_gate_check_list(int n, const int32_t* robot, const int32_t* robot2, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
+                               const double* meas17, const double* d2) {
+  auto bad = obs_gate_bad;
   auto zero3 = [](const double* v) { return !(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0); };
   auto zero_quat = [](const double* p7) { return !(p7[3] * p7[3] + p7[4] * p7[4] + p7[5] * p7[5] + p7[6] * p7[6] > 0.0); };
   if (n < 0) return bad("n < 0");
   if (n > 0 && (!robot || !pose_idx || !cls || !lm_idx || !meas17 || !d2)) return bad("a needed pointer is NULL");
   for (int k = 0; k < n; ++k)
-    if (!robot_ok(robot[k])) return bad("a robot outside [0, SLIDE_MAX_ROBOTS)");
+    if (!robot_ok(robot[k]) || (robot2 && !robot_ok(robot2[k]))) return bad("a robot outside [0, SLIDE_MAX_ROBOTS)");
   for (int k = 0; k < n; ++k)
     if (cls[k] != SLIDE_CLS_ELLIPSOID && cls[k] != SLIDE_CLS_CUBE && cls[k] != SLIDE_CLS_CYLINDER) return bad("a class that is not a landmark class");
   if (n > 0 && !closure_finite(meas17, 17 * (size_t)n)) return bad("meas17 holds a non-finite value");
@@ -472,9 +473,26 @@ int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* 
       if (zero3(a + 10)) return bad("a zero ray");
     }
   }
-  if (!g) return bad("the graph is NULL");
+  return SLIDE_OK;
+}
+int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
+                                        const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
+                                        int32_t* status) {
+  const int rc = obs_gate_check_list(n, robot, nullptr, pose_idx, cls, lm_idx, meas17, d2);
+  if (rc != SLIDE_OK) return rc;
+  if (!g) return obs_gate_bad("the graph is NULL");
   LOCK(g);
   return g->g.observation_mahalanobis(n, robot, pose_idx, cls, lm_idx, meas17, d2, dof, C81, r9, status);
+}
+// The same on the joint graph of a CholBatch: slots where the call above takes robots, the landmark's slot of its own (NULL: the
+// pose's).  The argument checks are the single-graph call's and come before the batch or the device is looked at.
+int slide_chol_batch_observation_mahalanobis(slide_chol_batch_t* b, int n, const int32_t* pose_slot, const uint64_t* pose_idx, const int32_t* lm_slot,
+                                             const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81,
+                                             double* r9, int32_t* status) {
+  const int rc = obs_gate_check_list(n, pose_slot, lm_slot, pose_idx, cls, lm_idx, meas17, d2);
+  if (rc != SLIDE_OK) return rc;
+  if (!b) return obs_gate_bad("the batch is NULL");
+  return b->b.joint_observation_mahalanobis(n, pose_slot, pose_idx, lm_slot, cls, lm_idx, meas17, d2, dof, C81, r9, status);
 }
 
 // sloam::FindRelativeMeasurementMatch sloam.cpp:321-412 (host-side bookkeeping: a few dozen stamps per call)

@@ -260,6 +260,11 @@ class CholBatch {
                                   double* out144n, int32_t* status);
   int joint_closure_mahalanobis(int L, const int32_t* from_slot, const uint64_t* from_idx, const int32_t* to_slot, const uint64_t* to_idx,
                                 const double* rel7, const double* sigma6, double* d2, double* C36, double* r6, int32_t* status);
+  // the Mahalanobis gate of candidate landmark observations on the JOINT graph (HostGraph::observation_mahalanobis with slots; lm_slot
+  // null: the landmark is the pose's graph's, else it may be another robot's): a private landmark through its graph's Schur records, a
+  // shared one at its separator rows
+  int joint_observation_mahalanobis(int n, const int32_t* pose_slot, const uint64_t* pose_idx, const int32_t* lm_slot, const int32_t* cls,
+                                    const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status);
 
  private:
   int n;

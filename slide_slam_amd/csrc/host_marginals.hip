@@ -1816,4 +1816,135 @@ int CholBatch::joint_closure_mahalanobis(int L, const int32_t* from_slot, const 
         return SLIDE_OK;
       });
 }
+// HostGraph::observation_mahalanobis on the joint graph (obs_gate_kernels.hip has the invariant): candidate k is the factor
+// add_range_bearing / add_cube / add_cylinder would add between pose (pose_slot, pose_idx) and the EXISTING landmark (cls, lm_idx) of
+// the graph in lm_slot (null: the pose's slot) — the two may differ: robot a's pose against a landmark only robot b has mapped.  z and
+// the sigmas by the add calls' own text with the parameters of the POSE's graph, r and A = [Ap | Al] at the two graphs' device-resident
+// estimates by k_joint_obs_gate_lin, no robust weight.  A private landmark enters as on one graph, with joint rows and the factors'
+// poses taken in the landmark's graph; a shared one is a separator variable the pass does not eliminate: Al^T is a right-hand side
+// on its separator coordinates (h_sep_off of its slot, the coordinates JointGain::build lists in rows_sh) and G0 = 0.  The walk forms
+// the separator's rows of R as the sum of the robots' rows of separator coordinates, so Al^T is written into those rows of the lowest
+// robot that holds the landmark (sep_entry_row): one place whichever replica names it.  C = I + G0 + W^T D W from the signed gram, d2 by
+// k_obs_gate_finish on M - Mneg.  Grouped by class, nk = 3 / 9 / 7 (128 / 42 / 54 candidates per sweep); every sweep walks the whole
+// forward half of the joint plan (the single graph's short walk from a late block column has no counterpart there).  status[k] (or
+// null): SLIDE_MISSING (a slot the batch lacks, a pose or landmark its graph does not hold, a landmark with neither a factor nor a
+// shared slot), SLIDE_ERR_NOT_SPD; zeros then.  Whole-call refusals: joint_state's, nothing written.
+int CholBatch::joint_observation_mahalanobis(int n_q, const int32_t* pose_slot, const uint64_t* pose_idx, const int32_t* lm_slot, const int32_t* cls,
+                                             const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
+                                             int32_t* status) {
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state("observation_mahalanobis", 0);
+  if (rc != SLIDE_OK) return rc;
+  JointGain jg;
+  jg.build(*this, 0);
+  // Where a right-hand side on the separator coordinates [so, so + d) enters the walk: the separator's own rows of R are WRITTEN by
+  // the walk (k_jms_sum: the sum of the robots' rows of separator coordinates), so the entry goes to those rows of the LOWEST robot
+  // whose border holds them — one place whichever replica names the landmark, and 0 + x = x in the sum.  -1: no robot holds them.
+  std::vector<long long> sep_first;                  // per separator row: its joint row in the lowest robot that maps it (-1: none), built on first use
+  auto sep_entry_row = [&](int so, int d) -> long long {
+    if (sep_first.empty()) {
+      sep_first.assign((size_t)jg.t.Tsep * NB + 1, -1);
+      for (int i = n - 1; i >= 0; --i)
+        for (int o = 0; o < jg.t.gn[i]; ++o)
+          if (jg.t.map[i][o] >= 0) sep_first[jg.t.map[i][o]] = (long long)jg.off[1 + i] + (long long)jg.t.Tc[i] * NB + o;
+    }
+    if (so < 0 || (size_t)(so + d) >= sep_first.size() || sep_first[so] < 0) return -1;
+    for (int c = 1; c < d; ++c)
+      if (sep_first[so + c] != sep_first[so] + c) return -1;      // (a landmark's coordinates are one run of its robot's border)
+    return sep_first[so];
+  };
+  struct Group { int type = 0; std::vector<int4> ends; std::vector<long long> sep; std::vector<double> z, sg; std::vector<int> ids; };
+  Group groups[3];
+  groups[0].type = FT_BR; groups[1].type = FT_CUBE; groups[2].type = FT_CYL;
+  for (int k = 0; k < n_q; ++k) {
+    d2[k] = 0.0;
+    for (int e = 0; C81 && e < 81; ++e) C81[81 * (size_t)k + e] = 0.0;
+    for (int e = 0; r9 && e < 9; ++e) r9[9 * (size_t)k + e] = 0.0;
+    if (dof) dof[k] = landmark_dim(cls[k]);
+    const int ps = pose_slot[k], ls = lm_slot ? lm_slot[k] : ps;
+    const int p = joint_end(jg, ps, pose_idx[k]);
+    int l = -1;
+    long long sep = -1;
+    if (ls >= 0 && ls < n) {
+      const HostGraph* gl = graphs[ls];
+      l = gl->lm_lid(cls[k], lm_idx[k]);
+      if (l >= 0 && (size_t)l >= gl->up_L) l = -1;
+      if (l >= 0 && (size_t)l < gl->h_lm_bord.size() && gl->h_lm_bord[l] >= 0) {
+        int so = -1;
+        for (size_t q = 0; q < gl->h_sh_lid.size(); ++q)
+          if (gl->h_sh_lid[q] == l) { so = gl->h_sep_off[q]; break; }
+        sep = so >= 0 ? sep_entry_row(so, landmark_dim(cls[k])) : -1;
+        if (sep < 0) l = -1;
+      }
+      if (l >= 0 && sep < 0 && gl->lm_fids[l].empty()) l = -1;
+    }
+    const int st = p < 0 || l < 0 ? SLIDE_MISSING : SLIDE_OK;
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    const HostGraph* gp = graphs[ps];
+    const double* a = meas17 + 17 * (size_t)k;
+    double z[15] = {}, sg[9] = {};
+    Group& g = groups[cls[k] == SLIDE_CLS_ELLIPSOID ? 0 : cls[k] == SLIDE_CLS_CUBE ? 1 : 2];
+    if (g.type == FT_BR) {
+      HostGraph::br_meas(a, a[3], z);
+      for (int i = 0; i < 3; ++i) sg[i] = gp->P.bearing_range_sigma;
+    } else if (g.type == FT_CUBE) {
+      gp->cube_meas(from7(a), from7(a + 7), a + 14, z, sg);
+    } else {
+      HostGraph::cyl_meas(from7(a), a + 7, a + 10, a[13], z);
+      for (int i = 0; i < 7; ++i) sg[i] = gp->P.cylinder_sigma;
+    }
+    g.ends.push_back(make_int4(ps, p, ls, l)); g.sep.push_back(sep); g.ids.push_back(k);
+    g.z.insert(g.z.end(), z, z + 15);
+    g.sg.insert(g.sg.end(), sg, sg + 9);
+  }
+  hipStream_t s = master;
+  for (Group& g : groups) {
+    if (g.ids.empty()) continue;
+    const int m = (int)g.ids.size(), nk = lf_rows(g.type), max_nc = std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / nk);
+    Scratch sc(s);
+    int4* d_ends = sc.alloc<int4>(m);
+    long long* d_sep = sc.alloc<long long>(m);
+    double* d_z = sc.alloc<double>(15 * (size_t)m);
+    double* d_sg = sc.alloc<double>(9 * (size_t)m);
+    double* d_r = sc.alloc<double>(9 * (size_t)max_nc);
+    double* d_G0 = sc.alloc<double>(81 * (size_t)max_nc);
+    double* d_out = sc.alloc<double>(OBS_GATE_OUT * (size_t)max_nc);
+    int* d_flag = sc.alloc<int>(max_nc);
+    if (!sc.ok()) { g_last_error = "observation_mahalanobis: out of device memory"; return SLIDE_ERR_HIP; }
+    SL_HIP(sc.upload(d_ends, g.ends));
+    SL_HIP(sc.upload(d_sep, g.sep));
+    SL_HIP(sc.upload(d_z, g.z));
+    SL_HIP(sc.upload(d_sg, g.sg));
+    std::vector<double> h(OBS_GATE_OUT * (size_t)max_nc);
+    std::vector<int> hflag(max_nc);
+    rc = joint_sigma_forms(
+        "observation_mahalanobis", jg, m, nk,
+        [&](int k0, int nc, double* B, int ld) {
+          launch_joint_obs_gate_lin(d_Gs, jg.d_tab, g.type, d_ends + k0, d_sep + k0, d_z + 15 * (size_t)k0, d_sg + 9 * (size_t)k0, nc, B, (size_t)ld,
+                                    d_r, d_G0, s);
+        },
+        [&](int k0, int nc, const double* M) -> int {
+          launch_obs_gate_finish(nk, M, d_G0, d_r, nc, d_out, d_flag, s);
+          SL_HIP(hipGetLastError());
+          SL_HIP(hipMemcpyAsync(h.data(), d_out, OBS_GATE_OUT * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+          SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+          SL_HIP(hipStreamSynchronize(s));
+          for (int i = 0; i < nc; ++i) {
+            const size_t k = (size_t)g.ids[k0 + i];
+            if (hflag[i]) {
+              if (status) status[k] = SLIDE_ERR_NOT_SPD;
+              continue;
+            }
+            const double* o = h.data() + OBS_GATE_OUT * (size_t)i;
+            d2[k] = o[0];
+            if (C81) std::copy(o + 1, o + 82, C81 + 81 * k);
+            if (r9) std::copy(o + 82, o + 91, r9 + 9 * k);
+          }
+          return SLIDE_OK;
+        });
+    if (rc != SLIDE_OK) return rc;
+  }
+  return SLIDE_OK;
+}
 }  // namespace sl

@@ -427,6 +427,11 @@ void launch_closure_gate_finish(const double* M, const double* r6, int n, double
 constexpr int OBS_GATE_OUT = 91;      // per candidate: d2, C (81, row-major, leading dimension 9), r (9)
 void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const int32_t* lid, const double* z15, const double* sg9, int n,
                          double* B, int nT, double* r9, double* G0, hipStream_t s);
+// the same fill on the joint graph of a CholBatch: Gs the members' views (device), tab as the joint closure gate's, ends[k] = {graph of
+// the pose, its pose id, graph of the landmark, its landmark id}, sep_row[k] the joint row at which a separator landmark's first
+// coordinate enters the walk, or -1 (a private landmark: its factors' poses are rows of the landmark's graph)
+void launch_joint_obs_gate_lin(const GraphDev* Gs, const JointPoseTab* tab, int type, const int4* ends, const long long* sep_row, const double* z15,
+                               const double* sg9, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s);
 void launch_obs_gate_finish(int m, const double* M, const double* G0, const double* r9, int n, double* out, int* flag, hipStream_t s);
 
 }  // namespace sl

@@ -12,6 +12,13 @@
 // H_ll^-1 the landmark's block of lm_Hinv: the pose-landmark cross block of the marginal is never formed.  B^T S^-1 B = W^T W with
 // L W = B is the forward substitution and gram of sigma_forms (host_marginals.hip); candidate k of a sweep owns the columns
 // m k .. m k + m - 1 of B.
+//
+// On the JOINT graph of a CholBatch (slide_chol_batch_observation_mahalanobis) K = L D L^T is the exact joint pass's system and
+//     C = I + G0 + W^T D W,   L W = B,
+// for a PRIVATE landmark with G0 = Al H_ll^-1 Al^T and the B above in joint rows, the factors' poses being poses of the landmark's
+// graph (which need not be the candidate pose's); for a SHARED landmark — a separator variable the pass does not eliminate: its
+// H_ll^-1 and F are zero — with G0 = 0, no factor sum and Al^T as a right-hand side on the landmark's separator coordinates.  The
+// signed gram (D = -I on the lambda rows) is the joint closure gate's (closure_kernels.hip, host_marginals.hip's joint_sigma_forms).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -33,34 +40,35 @@ __device__ __forceinline__ void og_cyl_err(const SE3& X, const double* q, const 
   e[6] = z[6] - q[6];
 }
 
-// k_obs_gate_lin, one wavefront per candidate.  `type` (FT_BR / FT_CUBE / FT_CYL) is the launch's: the host groups candidates by class.
-// pid / lid: the candidate's pose and landmark ids; z15: its measurement as br_z / cu_z / cy_z hold it (4 / 15 / 7 used of 15); sg9: its
-// sigmas (m used of 9).  The three branches restate k_lin_lf_body's (solver_kernels.hip) at pose_est / lm_est: analytic for
-// bearing-range (lane 0), central differences through the variables' own retract for cubes and cylinders (lane = 2 column + sign
-// within 32 lanes, lanes 30 / 31 the unperturbed error; the upper 32 lanes repeat the lower ones and store nothing).  The record
-// [r | Ap | Al] is staged in LDS in jbuf's layout.  Then lane 6 j + a owns the entries (row 6 q + a, column m k + j) of B for every pose
-// q: Ap[j][a] at the candidate's pose, minus sum_c F_f[a][c] Al[j][c] at the pose of every factor f of the landmark, in the order of
-// lm_fids — the same lane reads and writes the same entry every time, so a pose met twice (the candidate's own pose observing l, a
-// pose holding two factors on l) is an ordered read-modify-write, and no atomics are needed.  B is zero before the launch and the
-// candidates own disjoint columns.  Stored for the finish: r (9 per candidate) and G0 = Al H_ll^-1 Al^T (81 per candidate, m x m
-// packed), one triangle computed and mirrored.
-__global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const int32_t* __restrict__ pid, const int32_t* __restrict__ lid,
-                                                     const double* __restrict__ z15, const double* __restrict__ sg9, int n,
-                                                     double* __restrict__ B, int nT, double* __restrict__ r9, double* __restrict__ G0) {
-  __shared__ double rec[144];
-  const int k = blockIdx.x, lane = threadIdx.x;
-  if (k >= n) return;
-  const int p = pid[k], l = lid[k];
+// The linearise-and-fill body of one candidate, one wavefront, shared by k_obs_gate_lin (one graph) and k_joint_obs_gate_lin (the joint
+// graph of a CholBatch), as closure_gate_lin_body serves both closure gate kernels.  `type` (FT_BR / FT_CUBE / FT_CYL) is the launch's:
+// the host groups candidates by class.  Gp: the graph of the candidate's pose p (its pose_est, numdiff_delta and chart); Gl: the graph
+// of its landmark l (its lm_est, chart, Schur records and lm_Hinv) — one and the same on one graph.  z: the measurement as br_z / cu_z /
+// cy_z hold it (4 / 15 / 7 used of 15); sg: the sigmas (m used of 9).  The three branches restate k_lin_lf_body's (solver_kernels.hip) at
+// pose_est / lm_est: analytic for bearing-range (lane 0), central differences through the variables' own retract for cubes and cylinders
+// (lane = 2 column + sign within 32 lanes, lanes 30 / 31 the unperturbed error; the upper 32 lanes repeat the lower ones and store
+// nothing).  The record [r | Ap | Al] is staged in LDS (rec, 144 doubles) in jbuf's layout.  colB: the candidate's first column of B
+// (ld rows per column).  Rows: row_p the first row of the candidate's pose; pose q of the LANDMARK's graph starts at
+// off_l + (prow_l ? prow_l[q] : 6 q); sep_row < 0: a private landmark, else the first row of a separator landmark's coordinates.
+// Private: lane 6 j + a owns the entries (row a of a pose, column j) of B for every pose: Ap[j][a] at the candidate's pose, minus
+// sum_c F_f[a][c] Al[j][c] at the pose of every factor f of the landmark, in the order of lm_fids — the same lane reads and writes the
+// same entry every time, so a pose met twice (the candidate's own pose observing l, a pose holding two factors on l) is an ordered
+// read-modify-write, and no atomics are needed; G0 = Al H_ll^-1 Al^T, one triangle computed and mirrored.  Separator landmark (an
+// exact pass leaves its H_ll^-1 and F zero: it is not eliminated): Al^T goes to its own rows, no factor sum, G0 = 0.  B is zero before
+// the launch and the candidates own disjoint columns.  Stored for the finish: r (r9k, 9) and G0 (G0k, 81, m x m packed).
+__device__ __forceinline__ void obs_gate_lin_body(const GraphDev& Gp, const GraphDev& Gl, int type, int p, int l, const double* __restrict__ z,
+                                                  const double* __restrict__ sg, double* __restrict__ rec, double* __restrict__ colB,
+                                                  size_t ld, size_t row_p, size_t off_l, const int* __restrict__ prow_l, long long sep_row,
+                                                  double* __restrict__ r9k, double* __restrict__ G0k) {
+  const int lane = threadIdx.x;
   const int m = lf_rows(type), D = m;
-  const SE3 X = from12(G.pose_est + 12 * (size_t)p);
-  const double* lv = G.lm_est + 15 * (size_t)l;
-  const double* z = z15 + 15 * (size_t)k;
-  const double* sg = sg9 + 9 * (size_t)k;
+  const SE3 X = from12(Gp.pose_est + 12 * (size_t)p);
+  const double* lv = Gl.lm_est + 15 * (size_t)l;
   double* Jp = rec + m;
   double* Jl = rec + 7 * m;
   const int j = lane & 31, col = j >> 1;
   const bool st = lane < 32;
-  const double dl = G.numdiff_delta, fac = 1.0 / (2.0 * dl);
+  const double dl = Gp.numdiff_delta, fac = 1.0 / (2.0 * dl);
   const double d = (j & 1) ? -dl : dl;
   if (type == FT_BR) {
     const double w = 1.0 / sg[0];
@@ -106,7 +114,7 @@ __global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) cs[kk] = lv[12 + kk] + ((col == 12 + kk) ? d : 0.0);
     double e[9];
-    og_cube_err(retract(X, dX, G.chart), retract(C, dC, G.chart), cs, z, e);
+    og_cube_err(retract(X, dX, Gp.chart), retract(C, dC, Gl.chart), cs, z, e);
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
       const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const
 #pragma unroll
     for (int kk = 0; kk < 7; ++kk) q[kk] = lv[kk] + ((vi == kk) ? d : 0.0);
     double e[7];
-    og_cyl_err(retract(X, dX, G.chart), q, z, e);
+    og_cyl_err(retract(X, dX, Gp.chart), q, z, e);
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
@@ -139,39 +147,89 @@ __global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const
     }
   }
   __syncthreads();
-  const int f0 = G.lm_ptr[l], f1 = G.lm_ptr[l + 1];
-  if (lane < 6 * m) {
-    const int jc = lane / 6, a = lane - 6 * jc;
-    double* colB = B + (size_t)(m * k + jc) * nT;
-    colB[6 * (size_t)p + a] = Jp[6 * jc + a];
-    for (int qf = f0; qf < f1; ++qf) {
-      const int f = G.lm_fids[qf];
-      const double* F = G.ebuf + G.lf_eoff[f] + 6 * D + a * D;
+  if (sep_row >= 0) {
+    if (lane < 6 * m) {
+      const int jc = lane / 6, a = lane - 6 * jc;
+      colB[(size_t)jc * ld + row_p + a] = Jp[6 * jc + a];
+    }
+    for (int e = lane; e < m * D; e += 64) {
+      const int jc = e / D, c = e - D * jc;
+      colB[(size_t)jc * ld + (size_t)sep_row + c] = Jl[jc * D + c];
+    }
+    for (int e = lane; e < m * m; e += 64) G0k[e] = 0.0;
+  } else {
+    const int f0 = Gl.lm_ptr[l], f1 = Gl.lm_ptr[l + 1];
+    if (lane < 6 * m) {
+      const int jc = lane / 6, a = lane - 6 * jc;
+      double* cB = colB + (size_t)jc * ld;
+      cB[row_p + a] = Jp[6 * jc + a];
+      for (int qf = f0; qf < f1; ++qf) {
+        const int f = Gl.lm_fids[qf];
+        const double* F = Gl.ebuf + Gl.lf_eoff[f] + 6 * D + a * D;
+        double s = 0.0;
+        for (int c = 0; c < D; ++c) s += F[c] * Jl[jc * D + c];
+        const int q = Gl.lf_pose[f];
+        double* at = cB + off_l + (prow_l ? (size_t)prow_l[q] : 6 * (size_t)q) + a;
+        *at = *at - s;
+      }
+    }
+    if (lane < m * (m + 1) / 2) {
+      int i = 0;
+      while ((i + 1) * (i + 2) / 2 <= lane) ++i;
+      const int jc = lane - i * (i + 1) / 2;      // (i >= jc)
+      const double* Hi = Gl.lm_Hinv + 81 * (size_t)l;
       double s = 0.0;
-      for (int c = 0; c < D; ++c) s += F[c] * Jl[jc * D + c];
-      double* at = colB + 6 * (size_t)G.lf_pose[f] + a;
-      *at = *at - s;
+      for (int c = 0; c < D; ++c) {
+        double t = 0.0;
+        for (int dd = 0; dd < D; ++dd) t += Hi[c * D + dd] * Jl[jc * D + dd];
+        s += Jl[i * D + c] * t;
+      }
+      G0k[m * i + jc] = s;
+      G0k[m * jc + i] = s;
     }
   }
-  if (lane < m * (m + 1) / 2) {
-    int i = 0;
-    while ((i + 1) * (i + 2) / 2 <= lane) ++i;
-    const int jc = lane - i * (i + 1) / 2;      // (i >= jc)
-    const double* Hi = G.lm_Hinv + 81 * (size_t)l;
-    double s = 0.0;
-    for (int c = 0; c < D; ++c) {
-      double t = 0.0;
-      for (int dd = 0; dd < D; ++dd) t += Hi[c * D + dd] * Jl[jc * D + dd];
-      s += Jl[i * D + c] * t;
-    }
-    G0[81 * (size_t)k + m * i + jc] = s;
-    G0[81 * (size_t)k + m * jc + i] = s;
-  }
-  if (lane < m) r9[9 * (size_t)k + lane] = rec[lane];
+  if (lane < m) r9k[lane] = rec[lane];
+}
+// k_obs_gate_lin, one wavefront per candidate of one graph.  pid / lid: the candidate's pose and landmark ids; z15 / sg9: 15 / 9 per
+// candidate; candidate k owns the columns m k .. m k + m - 1 of B (nT rows); a pose's rows are 6 p .. 6 p + 5.
+__global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const int32_t* __restrict__ pid, const int32_t* __restrict__ lid,
+                                                     const double* __restrict__ z15, const double* __restrict__ sg9, int n,
+                                                     double* __restrict__ B, int nT, double* __restrict__ r9, double* __restrict__ G0) {
+  __shared__ double rec[144];
+  const int k = blockIdx.x;
+  if (k >= n) return;
+  const int p = pid[k], m = lf_rows(type);
+  obs_gate_lin_body(G, G, type, p, lid[k], z15 + 15 * (size_t)k, sg9 + 9 * (size_t)k, rec, B + (size_t)(m * k) * nT, (size_t)nT, 6 * (size_t)p, 0,
+                    nullptr, -1, r9 + 9 * (size_t)k, G0 + 81 * (size_t)k);
 }
 void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const int32_t* lid, const double* z15, const double* sg9, int n,
                          double* B, int nT, double* r9, double* G0, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_obs_gate_lin, dim3(n), dim3(64), 0, s, G, type, pid, lid, z15, sg9, n, B, nT, r9, G0);
+}
+
+// The same fill on the JOINT graph of a CholBatch (slide_chol_batch_observation_mahalanobis), one wavefront per candidate.  ends[k] =
+// {graph of the pose, its pose id, graph of the landmark, its landmark id}: the two graphs may differ (robot a's pose against a landmark
+// only robot b has mapped).  Gs: the batch's table of its members' views; tab: per graph its prow map and its system's first row in
+// the one buffer of ld rows per column (JointPoseTab); sep_row[k]: -1 for a private landmark, else the joint row at which a separator
+// landmark's first coordinate enters the walk (its rows in the border of the lowest robot that holds it: the substitution sums the
+// robots' rows of separator coordinates into the separator's own).  The factors of a private landmark sit at poses of the LANDMARK's graph; a window pose has its rows in
+// its robot's border, which prow already says.
+__global__ __launch_bounds__(64) void k_joint_obs_gate_lin(const GraphDev* __restrict__ Gs, const JointPoseTab* __restrict__ tab, int type,
+                                                           const int4* __restrict__ ends, const long long* __restrict__ sep_row,
+                                                           const double* __restrict__ z15, const double* __restrict__ sg9, int n,
+                                                           double* __restrict__ B, size_t ld, double* __restrict__ r9, double* __restrict__ G0) {
+  __shared__ double rec[144];
+  const int k = blockIdx.x;
+  if (k >= n) return;
+  const int4 e = ends[k];
+  const int m = lf_rows(type);
+  obs_gate_lin_body(Gs[e.x], Gs[e.z], type, e.y, e.w, z15 + 15 * (size_t)k, sg9 + 9 * (size_t)k, rec, B + (size_t)(m * k) * ld, ld,
+                    (size_t)tab->off[e.x] + tab->prow[e.x][e.y], (size_t)tab->off[e.z], tab->prow[e.z], sep_row[k], r9 + 9 * (size_t)k,
+                    G0 + 81 * (size_t)k);
+}
+void launch_joint_obs_gate_lin(const GraphDev* Gs, const JointPoseTab* tab, int type, const int4* ends, const long long* sep_row, const double* z15,
+                               const double* sg9, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_joint_obs_gate_lin, dim3(n), dim3(64), 0, s, Gs, tab, type, ends, sep_row, z15, sg9, n, B, ld, r9, G0);
 }
 
 // k_obs_gate_finish, one wavefront per candidate (four to a workgroup): C = (I + G0) + M, M the candidate's m x m gram W_k^T W_k at

@@ -705,6 +705,13 @@ class PassDriver:
         self._joint_ok()
         return self.batch.closure_mahalanobis(closures)
 
+    def observation_mahalanobis(self, candidates):
+        """The Mahalanobis gate of candidate landmark observations on the joint graph: CholBatch.observation_mahalanobis (a robot = its
+        shard's slot; an optional trailing lm_slot names the robot whose graph holds the landmark).  d2 to compare with
+        OBSERVATION_GATE_CHI2_99[dof], dof, status, C, r."""
+        self._joint_ok()
+        return self.batch.observation_mahalanobis(candidates)
+
     # ---- robust loss and observation loss on the exact joint pass (CholBatch.set_robust_loss / set_observation_loss, slide_gpu.h) ------
     def _loss_agreed(self, who, what, kind, param, *classes):
         """What both loss setters check first: the driver carries losses at all, and the ranks of a job set the same one."""
