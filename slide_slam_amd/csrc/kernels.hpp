@@ -411,7 +411,8 @@ void launch_closure_gate_lin(const double* pose_est, const int32_t* fslot, const
 void launch_pair_identity(const int32_t* aslot, const int32_t* bslot, int n, const int* prow, double* B, int nT, hipStream_t s);
 // the same fills on the joint graph of a CholBatch: ends[k] = {graph of pose a / from, its pose id, graph of pose b / to, its pose id};
 // tab (in device memory): per graph its estimate, its prow map, its system's first row in the one buffer (ld rows per column), its chart
-struct JointPoseTab { const double* est[JSIG_ROBOTS_MAX]; const int* prow[JSIG_ROBOTS_MAX]; long long off[JSIG_ROBOTS_MAX]; int chart[JSIG_ROBOTS_MAX]; };
+struct JointPoseTab { SL_GPTR(const double) est[JSIG_ROBOTS_MAX]; SL_GPTR(const int) prow[JSIG_ROBOTS_MAX]; long long off[JSIG_ROBOTS_MAX]; int chart[JSIG_ROBOTS_MAX]; };
+static_assert(sizeof(JointPoseTab) == (2 * sizeof(void*) + sizeof(long long) + sizeof(int)) * JSIG_ROBOTS_MAX, "host and device passes see the same bytes");
 void launch_joint_closure_gate_lin(const JointPoseTab* tab, const int4* ends, const double* z12, const double* sigma6, int n, double* B,
                                    size_t ld, double* r6, hipStream_t s);
 void launch_joint_pair_identity(const JointPoseTab* tab, const int4* ends, int n, double* B, size_t ld, hipStream_t s);

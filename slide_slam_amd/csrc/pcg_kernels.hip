@@ -92,7 +92,9 @@ __device__ __forceinline__ void pcg_tl_body(const GraphDev& G, const PcgBufs& B,
 // out = S0 * in for the symmetric S0 held as its lower triangle (column-major, leading dimension ld): one workgroup per block row
 // i of 64: tiles (i, j <= i) as they lie, tiles (j > i, i) transposed.  Deterministic (no atomics): every block row is summed by
 // one workgroup in a fixed order.
-__device__ __forceinline__ void pcg_symv_body(const GraphDev& G, int bi, int vin, int vout, int in_lds) {
+// IN_LDS a template parameter: chosen at run time, the vector's pointer is LDS or global, and every read of it a flat load
+template <bool IN_LDS>
+__device__ __forceinline__ void pcg_symv_body(const GraphDev& G, int bi, int vin, int vout) {
   if (bi >= G.T) return;
   extern __shared__ double xs_lds[];      // the whole input vector (T * 64 doubles) when it fits: no barrier inside the tile loops
   __shared__ double red[4][NB];
@@ -101,11 +103,11 @@ __device__ __forceinline__ void pcg_symv_body(const GraphDev& G, int bi, int vin
   const double* x = pvec(G, vin);
   const double* S0 = G.S0;
   const int ld = G.ld, nT = G.T * NB;
-  if (in_lds) {
+  if (IN_LDS) {
     for (int i = tid; i < nT; i += 256) xs_lds[i] = x[i];
     __syncthreads();
   }
-  const double* xs = in_lds ? xs_lds : x;
+  const double* xs = IN_LDS ? xs_lds : x;
   double acc = 0.0;
   // tiles (bi, j), j < bi: y[row] += sum_c tile[row][c] x_j[c]; thread (row, cp) takes columns 16 cp ..; the next tile's sixteen
   // loads are issued before this tile's products (two register sets): the loop is a pure stream, latency is all there is to hide
@@ -198,7 +200,10 @@ __device__ __forceinline__ void pcg_symv_body(const GraphDev& G, int bi, int vin
 // workgroups of a robot take the block rows of the product, the others four shared slots each
 __global__ __launch_bounds__(256) void k_pcg_tl_symv(const GraphDev* __restrict__ Gs, PcgBufs B, int vec, int vout, int n_row_blocks, int in_lds) {
   const GraphDev G = Gs[blockIdx.z];
-  if ((int)blockIdx.x < n_row_blocks) pcg_symv_body(G, blockIdx.x, vec, vout, in_lds);
+  if ((int)blockIdx.x < n_row_blocks) {
+    if (in_lds) pcg_symv_body<true>(G, blockIdx.x, vec, vout);
+    else pcg_symv_body<false>(G, blockIdx.x, vec, vout);
+  }
   else pcg_tl_body(G, B, (int)blockIdx.x - n_row_blocks, vec);
 }
 

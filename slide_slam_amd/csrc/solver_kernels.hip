@@ -386,6 +386,7 @@ __global__ __launch_bounds__(256) void k_lin_lf_robust_b(const GraphDev* __restr
 __shared__ double lm_hs[4][96];   // per wave of k_landmark: H_ll^-1 (81) + g_l (9)
 constexpr int LM_RED_MAX = 24;    // k_landmark<3>: landmarks with at most that many factors reduce their partial sums through LDS
 __shared__ double lm_red[4][54 * LM_RED_MAX];
+constexpr int LM_KR = 2;          // landmark_wave's second loop: rows of a factor's record loaded together
 
 template <int D, int MODE>
 __device__ inline void landmark_wave(const GraphDev& G, int l, int lane) {
@@ -562,11 +563,36 @@ __device__ inline void landmark_wave(const GraphDev& G, int l, int lane) {
     double Ea[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) Ea[c] = 0.0;
+    // the record's rows LM_KR at a time, the next group's loads issued before this group's products (two register sets).  The
+    // scheduling barriers keep that order: left alone, the compiler issues all D (D + 1) loads of an item at once (256 VGPRs, one
+    // wave per SIMD), or, behind a barrier per row, waits out one round trip per row
+    constexpr int NG = (D + LM_KR - 1) / LM_KR;
+    double jp[2][LM_KR], jl[2][LM_KR][D];
+    auto load_rows = [&](int gq, int b) {
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double jp = Jp[6 * k + a];
+      for (int u = 0; u < LM_KR; ++u) {
+        const int k = gq * LM_KR + u;
+        if (k < D) {
+          jp[b][u] = Jp[6 * k + a];
 #pragma unroll
-      for (int c = 0; c < D; ++c) Ea[c] += jp * Jl[D * k + c];
+          for (int c = 0; c < D; ++c) jl[b][u][c] = Jl[D * k + c];
+        }
+      }
+    };
+    load_rows(0, 0);
+#pragma unroll
+    for (int gq = 0; gq < NG; ++gq) {
+      if (gq + 1 < NG) load_rows(gq + 1, (gq + 1) & 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < LM_KR; ++u) {
+        const int k = gq * LM_KR + u;
+        if (k < D) {
+#pragma unroll
+          for (int c = 0; c < D; ++c) Ea[c] += jp[gq & 1][u] * jl[gq & 1][u][c];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int c = 0; c < D; ++c) E[a * D + c] = Ea[c];
@@ -887,11 +913,11 @@ __device__ __forceinline__ void k_schur_body(const GraphDev& G, int pj, int yb) 
         if (sl[u] < 0) continue;
         const int D = (int)(ed[u] & 15);
         const double* F = G.ebuf + (ed[u] >> 4) + 6 * D;
-        const int l = (sl[u] < SCHUR_PJ_CAP) ? pj_lm[sl[u]] : G.pose_lms[b0 + sl[u]];
+        const int l = (sl[u] < SCHUR_PJ_CAP) ? pj_lm[sl[u]] : global_of(G.pose_lms)[b0 + sl[u]];
         for (int y = sl[u]; y < nb; ++y) {
-          const int ly = (y < SCHUR_PJ_CAP) ? pj_lm[y] : G.pose_lms[b0 + y];
+          const int ly = (y < SCHUR_PJ_CAP) ? pj_lm[y] : global_of(G.pose_lms)[b0 + y];      // (global_of: an LDS-or-global choice of plain pointers is one flat load)
           if (ly != l) break;
-          const long long edy = (y < SCHUR_PJ_CAP) ? pj_ed[y] : G.pose_ed[b0 + y];
+          const long long edy = (y < SCHUR_PJ_CAP) ? pj_ed[y] : global_of(G.pose_ed)[b0 + y];
           const double* E = G.ebuf + (edy >> 4);
           if (D == 3) {
             double e[18];
@@ -1061,8 +1087,8 @@ __device__ __forceinline__ void k_schur_listed_body(const GraphDev& G, int pj, i
       }
       // own share of the block's pair list (x = q0 + sub, + 8, ...), three entries at a time: F_x E_y^T
       const int q0 = qc.x, q1 = qc.x + qc.y;
-      const longlong2* __restrict__ prs = reinterpret_cast<const longlong2*>(G.sp_pairs);
-      const char* __restrict__ ebase = reinterpret_cast<const char*>(G.ebuf);
+      const longlong2* __restrict__ prs = reinterpret_cast<const longlong2*>(static_cast<const long long*>(G.sp_pairs));
+      const char* __restrict__ ebase = reinterpret_cast<const char*>(static_cast<double*>(G.ebuf));
       for (int x0 = q0 + sub; x0 < q1; x0 += 24) {
         const longlong2 z2 = longlong2{0, 0};
         const longlong2 e0 = prs[x0];
