@@ -971,6 +971,45 @@ int slide_graph_closure_mahalanobis(slide_graph_t* g, int L, const int32_t* from
 int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
                                         const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof /* may be NULL */,
                                         double* C81 /* may be NULL */, double* r9 /* may be NULL */, int32_t* status /* may be NULL */);
+/* The JOINT compatibility of a key frame's landmark matches: Neira and Tardos' joint compatibility test in its greedy sequential form
+ * (the sequential compatibility nearest neighbour), on the single graph.  No counterpart in the reference; GTSAM users would stack the
+ * hypothesis' factors and take Marginals::jointMarginalCovariance over all their variables.  A frame proposes its matches at once, all
+ * from the newest pose, which carries most of each candidate's innovation covariance: the candidates are strongly correlated, and
+ * slide_graph_observation_mahalanobis, which tests each alone, accepts sets that no single pose error explains.
+ * The call takes n_groups hypotheses; group g is the candidates group_ptr[g] .. group_ptr[g + 1] - 1 in the caller's order, each
+ * described exactly as for slide_graph_observation_mahalanobis (robot, pose_idx, cls, lm_idx, meas17; the add call's base noise, no
+ * robust weight; the same state rules).  With a group's served candidates stacked, r = [r_1; ..], A = [A_1; ..],
+ *     C = I + A H^-1 A^T,     block (i, j) = [i == j] (I + Al_i H_ll^-1 Al_i^T) + W_i^T W_j,     L W = B,
+ * B_i the columns of the individual gate: H_ll is block diagonal and a group may not name a landmark twice.
+ * The rule, on the device, in the caller's order.  q(k): the prob quantile of chi-square with k degrees of freedom
+ * (slide_chi2_quantile, k = 1 .. SLIDE_INFO_GAIN_SWEEP_COLS).  The accepted set S starts empty; for candidate i of m_i = 3 / 9 / 7 rows
+ *     d2_single[i] = r_i^T C_ii^-1 r_i,
+ *     d2_joint[i]  = the stacked d2 of S + {i}, dof_joint[i] its dimension, by bordering the Cholesky factor of C_SS:
+ *                    X = C_iS L_S^-T,  D = C_ii - X X^T = G G^T,  y_i = G^-1 (r_i - X y_S),  d2_joint = d2_S + y_i^T y_i,
+ *     accepted[i]  = d2_single[i] <= q(m_i) and d2_joint[i] <= q(dof_joint[i]); the factor and y grow by the block then and stay as they
+ *                    were otherwise.
+ * prob == 0: evaluate only — every served candidate is accepted, d2_joint is the prefix sequence of the stacked test and group_d2 the
+ * joint compatibility of the whole hypothesis.  Per group: group_d2 / group_dof / group_count, the stacked d2, the rows and the number
+ * of the accepted set.  Groups are packed whole, in the caller's order, into sweeps of at most SLIDE_INFO_GAIN_SWEEP_COLS columns; a
+ * group's bits do not depend on what else is in the call or where it stands.  The graph is only read.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written, the message names observation_joint_compatibility and the reason), decided
+ * on the host before the graph or the device is looked at: n_groups < 0, a needed pointer NULL (every output is needed), a group_ptr
+ * that does not start at 0 or decreases, prob neither 0 nor inside (0, 1) (not a number among them), the per-candidate checks of
+ * slide_graph_observation_mahalanobis, the graph is NULL; then those of slide_graph_get_pose_covariances.  Per candidate, status[i]
+ * with zeros in its outputs: SLIDE_MISSING as the individual gate decides it — the candidate is skipped and the rest of its group
+ * served as if it were absent; SLIDE_ERR_NOT_SPD when a pivot of D or C_ii is not positive — the candidate is rejected and the chain
+ * goes on.  Per group, group_status[g] with zeros everywhere in the group, its neighbours served: SLIDE_ERR_INVALID when two served
+ * candidates name one landmark, SLIDE_ERR_CAPACITY when the served rows exceed SLIDE_INFO_GAIN_SWEEP_COLS (128 points). */
+int slide_graph_observation_joint_compatibility(slide_graph_t* g, int n_groups, const int32_t* group_ptr, const int32_t* robot,
+                                                const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx, const double* meas17,
+                                                double prob, int32_t* accepted, double* d2_single, double* d2_joint, int32_t* dof_joint,
+                                                int32_t* status, double* group_d2, int32_t* group_dof, int32_t* group_count,
+                                                int32_t* group_status);
+/* The prob quantile of chi-square with dof degrees of freedom, q with P(dof / 2, q / 2) = prob: Newton on the regularised incomplete
+ * gamma function (its series for x < a + 1, its continued fraction elsewhere).  Host code, no device is needed; no counterpart in the
+ * reference (boost::math::quantile(chi_squared(dof), prob) is the usual spelling).  SLIDE_ERR_INVALID for prob outside (0, 1) or not a
+ * number, dof < 1, q NULL. */
+int slide_chi2_quantile(double prob, int dof, double* q);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the

@@ -371,6 +371,45 @@ class SemanticFactorGraph {
     d2.resize(n);
     return d2;
   }
+  // The joint compatibility of a key frame's matches, tested together (slide_graph_observation_joint_compatibility; no counterpart in
+  // the reference): groups[g] is one hypothesis, its candidates tried in the given order.  A candidate is accepted iff it passes alone
+  // (d2Single against the prob quantile of its own rows) and stacked on those accepted before it (d2Joint against the quantile of
+  // dofJoint); prob == 0 evaluates only.  The per-candidate vectors run over the groups' candidates in order (group g starts at
+  // groupPtr[g]); groupD2 / groupDof / groupCount describe each group's accepted set.  status: SLIDE_MISSING (skipped),
+  // SLIDE_ERR_NOT_SPD (rejected); groupStatus: SLIDE_ERR_INVALID (a landmark named twice), SLIDE_ERR_CAPACITY (more than
+  // SLIDE_INFO_GAIN_SWEEP_COLS rows), zeros in the group then.  The graph is only read.
+  struct JointCompatibility {
+    std::vector<int32_t> groupPtr, accepted, dofJoint, status, groupDof, groupCount, groupStatus;
+    std::vector<double> d2Single, d2Joint, groupD2;
+  };
+  JointCompatibility observationJointCompatibility(const std::vector<std::vector<ObservationCandidate>>& groups, double prob = 0.99) const {
+    const size_t ng = groups.size();
+    JointCompatibility out;
+    out.groupPtr.assign(ng + 1, 0);
+    for (size_t g = 0; g < ng; ++g) out.groupPtr[g + 1] = out.groupPtr[g] + (int32_t)groups[g].size();
+    const size_t n = (size_t)out.groupPtr[ng];
+    std::vector<double> meas(17 * n + 1);
+    std::vector<int32_t> rb(n + 1), cls(n + 1);
+    std::vector<uint64_t> pi(n + 1), li(n + 1);
+    size_t k = 0;
+    for (const std::vector<ObservationCandidate>& grp : groups)
+      for (const ObservationCandidate& c : grp) {
+        rb[k] = (int32_t)c.robot; cls[k] = (int32_t)c.cls; pi[k] = c.poseIdx; li[k] = c.lmIdx;
+        for (int i = 0; i < 17; ++i) meas[17 * k + i] = c.meas[i];
+        ++k;
+      }
+    out.accepted.assign(n + 1, 0); out.dofJoint.assign(n + 1, 0); out.status.assign(n + 1, 0);
+    out.d2Single.assign(n + 1, 0.0); out.d2Joint.assign(n + 1, 0.0);
+    out.groupD2.assign(ng + 1, 0.0); out.groupDof.assign(ng + 1, 0); out.groupCount.assign(ng + 1, 0); out.groupStatus.assign(ng + 1, 0);
+    detail::check(slide_graph_observation_joint_compatibility(g_, (int)ng, out.groupPtr.data(), rb.data(), pi.data(), cls.data(), li.data(),
+                                                              meas.data(), prob, out.accepted.data(), out.d2Single.data(), out.d2Joint.data(),
+                                                              out.dofJoint.data(), out.status.data(), out.groupD2.data(), out.groupDof.data(),
+                                                              out.groupCount.data(), out.groupStatus.data()),
+                  "observationJointCompatibility");
+    out.accepted.resize(n); out.dofJoint.resize(n); out.status.resize(n); out.d2Single.resize(n); out.d2Joint.resize(n);
+    out.groupD2.resize(ng); out.groupDof.resize(ng); out.groupCount.resize(ng); out.groupStatus.resize(ng);
+    return out;
+  }
 
   // Robust loss on the loop-closure / relative-measurement factors (slide_graph_set_robust_loss; no counterpart in the reference —
   // GTSAM's noiseModel::Robust with mEstimator::Huber / Cauchy / GemanMcClure / DCS): kind 0 none, 1 .. 4 in that order; param <= 0:

@@ -43,7 +43,7 @@ EXPORTS = [
     "slide_slidegraph_default_params", "slide_find_inter_loop_closure_clipper", "slide_find_inter_loop_closures_clipper",
     "slide_closure_default_params", "slide_closure_canonicalize", "slide_closure_consistency_csr", "slide_select_consistent_closures",
     "slide_graph_select_closures", "slide_graph_get_pose_pair_covariances", "slide_graph_closure_mahalanobis",
-    "slide_graph_observation_mahalanobis",
+    "slide_graph_observation_mahalanobis", "slide_graph_observation_joint_compatibility", "slide_chi2_quantile",
     "slide_graph_set_robust_loss", "slide_graph_get_closure_weights",
     "slide_graph_set_observation_loss", "slide_graph_get_observation_weights",
     "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
@@ -170,6 +170,14 @@ def default_params(**kw) -> Params:
         else:
             setattr(p, k, v)
     return p
+
+
+def chi2_quantile(prob: float, dof: int) -> float:
+    """slide_chi2_quantile: the prob quantile of chi-square with dof degrees of freedom (host code, no device needed): what
+    SlideGraph.observation_joint_compatibility compares d2_single and d2_joint with."""
+    q = C.c_double(0.0)
+    _check(lib().slide_chi2_quantile(C.c_double(prob), C.c_int(dof), C.byref(q)))
+    return q.value
 
 
 def device_check(device: int = -1) -> None:
@@ -478,6 +486,31 @@ class SlideGraph:
         _check(self.L.slide_graph_observation_mahalanobis(self.h, C.c_int(n), _p(robot), _p(pidx), _p(cls), _p(lidx), _p(meas), _p(d2),
                                                           _p(dof), _p(Cm), _p(r), _p(status)))
         return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
+
+    def observation_joint_compatibility(self, groups, prob=0.99):
+        """slide_graph_observation_joint_compatibility: the joint compatibility of a key frame's landmark matches, tested together
+        (Neira and Tardos' test in its greedy sequential form).  groups: a list of hypotheses, each a list of the candidate tuples
+        observation_mahalanobis takes, tried in the given order.  A candidate is accepted iff it passes alone (d2_single against the
+        prob quantile of its own rows) and stacked on the candidates accepted before it (d2_joint against the quantile of dof_joint);
+        prob=0 evaluates only: every served candidate is accepted and d2_joint is the prefix sequence of the stacked test.  Returns a
+        dict: per candidate, in the groups' order, accepted, d2_single, d2_joint, dof_joint, status (SLIDE_MISSING: skipped, the rest
+        of its group served without it; SLIDE_ERR_NOT_SPD: rejected); per group group_d2, group_dof, group_count (the accepted set's
+        stacked d2, rows and size) and group_status (SLIDE_ERR_INVALID: a landmark named twice, SLIDE_ERR_CAPACITY: more than 384
+        rows; zeros in the group then); group_ptr, the groups' offsets into the candidate arrays."""
+        groups = [list(g) for g in groups]
+        ng = len(groups)
+        ptr = np.zeros(ng + 1, np.int32)
+        ptr[1:] = np.cumsum([len(g) for g in groups])
+        n, k, robot, pidx, cls, lidx, meas, _ = _observation_arrays([c for g in groups for c in g], False)
+        acc, dofj, status = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        d2s, d2j = np.zeros(k), np.zeros(k)
+        kg = max(ng, 1)
+        gd2, gdof, gcnt, gst = np.zeros(kg), np.zeros(kg, np.int32), np.zeros(kg, np.int32), np.zeros(kg, np.int32)
+        _check(self.L.slide_graph_observation_joint_compatibility(
+            self.h, C.c_int(ng), _p(ptr), _p(robot), _p(pidx), _p(cls), _p(lidx), _p(meas), C.c_double(prob), _p(acc), _p(d2s), _p(d2j), _p(dofj),
+            _p(status), _p(gd2), _p(gdof), _p(gcnt), _p(gst)))
+        return {"accepted": acc[:n].astype(bool), "d2_single": d2s[:n], "d2_joint": d2j[:n], "dof_joint": dofj[:n], "status": status[:n],
+                "group_d2": gd2[:ng], "group_dof": gdof[:ng], "group_count": gcnt[:ng], "group_status": gst[:ng], "group_ptr": ptr}
 
     def set_ghosts(self, own_robot, own_idx):
         r = _i(own_robot)

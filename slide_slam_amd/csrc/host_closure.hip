@@ -447,11 +447,15 @@ int slide_chol_batch_closure_mahalanobis(slide_chol_batch_t* b, int L, const int
 
 // The individual-compatibility gate of a list of candidate landmark observations (the closure gate's counterpart for the factors the
 // association produces).  The argument checks come first and need neither graph nor device; nothing is written on a refusal.
-static int obs_gate_bad(const char* what) { g_last_error = std::string("observation_mahalanobis: ") + what; return SLIDE_ERR_INVALID; }
-// (the list's own checks, shared with the batch's call: robot2, or null, is its second list of slots)
+static int obs_gate_bad(const char* what, const char* who = "observation_mahalanobis") {
+  g_last_error = std::string(who) + ": " + what;
+  return SLIDE_ERR_INVALID;
+}
+// (the list's own checks, shared with the batch's call — robot2, or null, is its second list of slots — and with the joint-compatibility
+// call, which names itself in the message)
 static int obs_gate_check_list(int n, const int32_t* robot, const int32_t* robot2, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
-                               const double* meas17, const double* d2) {
-  auto bad = obs_gate_bad;
+                               const double* meas17, const double* d2, const char* who = "observation_mahalanobis") {
+  auto bad = [who](const char* what) { return obs_gate_bad(what, who); };
   auto zero3 = [](const double* v) { return !(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0); };
   auto zero_quat = [](const double* p7) { return !(p7[3] * p7[3] + p7[4] * p7[4] + p7[5] * p7[5] + p7[6] * p7[6] > 0.0); };
   if (n < 0) return bad("n < 0");
@@ -484,6 +488,31 @@ int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* 
   LOCK(g);
   return g->g.observation_mahalanobis(n, robot, pose_idx, cls, lm_idx, meas17, d2, dof, C81, r9, status);
 }
+// The joint-compatibility test of groups of such candidates (obs_joint_kernels.hip).  The argument checks come first, need neither
+// graph nor device and write nothing: the groups' own, the probability, then the candidates' as above.
+int slide_graph_observation_joint_compatibility(slide_graph_t* g, int n_groups, const int32_t* group_ptr, const int32_t* robot,
+                                                const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx, const double* meas17,
+                                                double prob, int32_t* accepted, double* d2_single, double* d2_joint, int32_t* dof_joint,
+                                                int32_t* status, double* group_d2, int32_t* group_dof, int32_t* group_count,
+                                                int32_t* group_status) {
+  const char* who = "observation_joint_compatibility";
+  if (n_groups < 0) return obs_gate_bad("n_groups < 0", who);
+  if (n_groups > 0 && (!group_ptr || !group_d2 || !group_dof || !group_count || !group_status)) return obs_gate_bad("a needed pointer is NULL", who);
+  if (n_groups > 0 && group_ptr[0] != 0) return obs_gate_bad("group_ptr does not start at 0", who);
+  for (int i = 0; i < n_groups; ++i)
+    if (group_ptr[i + 1] < group_ptr[i]) return obs_gate_bad("group_ptr decreases", who);
+  if (!(prob == 0.0 || (prob > 0.0 && prob < 1.0))) return obs_gate_bad("prob is neither 0 (evaluate only) nor inside (0, 1)", who);
+  const int n = n_groups > 0 ? group_ptr[n_groups] : 0;
+  if (n > 0 && (!accepted || !d2_single || !d2_joint || !dof_joint || !status)) return obs_gate_bad("a needed pointer is NULL", who);
+  const int rc = obs_gate_check_list(n, robot, nullptr, pose_idx, cls, lm_idx, meas17, d2_joint, who);
+  if (rc != SLIDE_OK) return rc;
+  if (!g) return obs_gate_bad("the graph is NULL", who);
+  LOCK(g);
+  return g->g.observation_joint_compatibility(n_groups, group_ptr, robot, pose_idx, cls, lm_idx, meas17, prob, accepted, d2_single, d2_joint,
+                                              dof_joint, status, group_d2, group_dof, group_count, group_status);
+}
+// The `prob` quantile of chi-square with dof degrees of freedom, as the call above builds its table (host code; no device needed).
+int slide_chi2_quantile(double prob, int dof, double* q) { return chi2_quantile(prob, dof, q); }
 // The same on the joint graph of a CholBatch: slots where the call above takes robots, the landmark's slot of its own (NULL: the
 // pose's).  The argument checks are the single-graph call's and come before the batch or the device is looked at.
 int slide_chol_batch_observation_mahalanobis(slide_chol_batch_t* b, int n, const int32_t* pose_slot, const uint64_t* pose_idx, const int32_t* lm_slot,

@@ -174,6 +174,9 @@ using FormFill = std::function<void(int k0, int nc, double* B, int ld)>;
 using FormDone = std::function<int(int k0, int nc, const double* M)>;
 // (optional, single graph only) the first block column the sweep's forward substitution has to walk: B is zero above row NB * it
 using FormStart = std::function<int(int k0, int nc)>;
+struct FormBackend;      // (host_marginals.hip: what differs between one graph and the joint graph of a batch)
+// the `prob` quantile of chi-square with dof degrees of freedom (host code; SLIDE_ERR_INVALID for prob outside (0, 1) or dof < 1)
+int chi2_quantile(double prob, int dof, double* q);
 class CholBatch {
  public:
   explicit CholBatch(int n);
@@ -479,6 +482,17 @@ class HostGraph {
   // from meas17[17 k ..], the class's remaining arguments in the add call's order; arguments checked by the C ABI
   int observation_mahalanobis(int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
                               const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status);
+  // the joint-compatibility test of n_groups hypotheses (obs_joint_kernels.hip has the invariant and the rule): group g is the
+  // candidates group_ptr[g] .. group_ptr[g + 1] - 1, each described as observation_mahalanobis's; prob == 0: evaluate only.  Every
+  // output is written (per candidate, then per group); arguments checked by the C ABI
+  int observation_joint_compatibility(int n_groups, const int32_t* group_ptr, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
+                                      const uint64_t* lm_idx, const double* meas17, double prob, int32_t* accepted, double* d2_single,
+                                      double* d2_joint, int32_t* dof_joint, int32_t* status, double* group_d2, int32_t* group_dof,
+                                      int32_t* group_count, int32_t* group_status);
+  // what the two calls above resolve of a candidate on the host, and where a sweep of candidates starts its walk
+  struct ObsCand { int st = SLIDE_OK, type = 0, p = -1, l = -1; double z[15] = {}, sg[9] = {}; };
+  ObsCand obs_candidate(int robot, uint64_t pose_idx, int cls, uint64_t lm_idx, const double* meas17) const;
+  int obs_walk_start(const int32_t* pid, const int32_t* lid, int n) const;
   // what the three add calls store of their arguments (and the gate evaluates): z as br_z / cu_z / cy_z hold it, the cube's sigmas
   static void br_meas(const double* bearing, double range, double* z4);
   void cube_meas(const SE3& pose, const SE3& cube_world, const double* scale, double* z15, double* sigma9) const;
@@ -732,6 +746,7 @@ class HostGraph {
   DevArr<double> d_igval;
   int marginal_state(const char* who) const;      // SLIDE_ERR_INVALID (+ message) unless a single-graph factorisation is resident
   int sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done, const FormStart& start = nullptr);
+  void form_backend(FormBackend& be, const FormStart& start);      // this graph's back end of the quadratic-form drivers
   int ensure_sigma();
   int pose_id(int robot, uint64_t idx) const;     // the uploaded pose's index, or -1
   void robot_poses(int robot, std::vector<int>& out) const;

@@ -698,20 +698,70 @@ static int sigma_forms_core(const char* who, FormBackend& be, int ncand, int nk,
   }
   return SLIDE_OK;
 }
-int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done, const FormStart& start) {
+// (one graph's back end: B and W of nT rows, the forward half of the resident factor's substitution from block column kb on)
+void HostGraph::form_backend(FormBackend& be, const FormStart& start) {
   hipStream_t s = stream;
   const int T = G.T, nT = T * NB;
   const bool dense = h_prof.size() != (size_t)T;
-  FormBackend be;
   be.s = s; be.ld = nT; be.nrows = nT;
-  be.alloc = [&](Scratch& sc, int max_ncol) -> int {
+  be.alloc = [&be, nT](Scratch& sc, int max_ncol) -> int {
     be.B = sc.alloc<double>((size_t)max_ncol * nT);
     be.W = sc.alloc<double>((size_t)max_ncol * nT);
     return SLIDE_OK;
   };
   be.start = start;
-  be.fwd = [&](int ncol) { launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), be.B, be.W, ncol, s, std::min(be.kb, T - 1)); };
+  be.fwd = [this, &be, T, dense, s](int ncol) {
+    launch_multi_fwd(G.S, G.ld, T, G.Ld, G.Winv, dense ? nullptr : h_prof.data(), be.B, be.W, ncol, s, std::min(be.kb, T - 1));
+  };
+}
+int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& fill, const FormDone& done, const FormStart& start) {
+  FormBackend be;
+  form_backend(be, start);
   return sigma_forms_core(who, be, ncand, nk, fill, done);
+}
+// sigma_forms_core's sibling for GROUPS of unequal width whose whole gram is wanted (the joint-compatibility test): a sweep is a list
+// of groups packed by the caller, group g of it one "candidate" of launch_gram_blocks — cd[g] = {first column, columns, splits, .,
+// moff, poff, .} — with a job table of its own over (group, tile row >= tile column, split): only the lower 16 x 16 tiles of a
+// group's nk x nk gram are formed (k_gram_reduce adds the splits of every entry; the upper tiles' sums are of partials nobody wrote
+// and nobody reads).  The split count depends on the group's columns alone, so a group's bits do not depend on its neighbours.  Per
+// sweep: B zeroed, fill(si), the walk from start(si, groups) on, the gram's two launches, done(si, the table on the device, M).
+struct FormGroups { int ncol = 0; std::vector<GainCandDev> cd; std::vector<int4> jobs; size_t msz = 0, psz = 0; };
+using GroupFill = std::function<int(int si, double* B, int ld)>;
+using GroupDone = std::function<int(int si, const GainCandDev* d_cd, const double* M)>;
+static int sigma_forms_groups_core(const char* who, FormBackend& be, const std::vector<const FormGroups*>& sweeps, const GroupFill& fill,
+                                   const GroupDone& done) {
+  hipStream_t s = be.s;
+  if (be.nrows_neg > 0) { g_last_error = std::string(who) + ": groups are served on factors without signed rows only"; return SLIDE_ERR_INVALID; }
+  int max_ncol = 0;
+  size_t max_m = 0, max_p = 0, max_g = 0, max_j = 0;
+  for (const FormGroups* w : sweeps) {
+    max_ncol = std::max(max_ncol, w->ncol);
+    max_m = std::max(max_m, w->msz); max_p = std::max(max_p, w->psz);
+    max_g = std::max(max_g, w->cd.size()); max_j = std::max(max_j, w->jobs.size());
+  }
+  Scratch sc(s);
+  int rc = be.alloc(sc, max_ncol);
+  double* d_M = sc.alloc<double>(max_m);
+  double* d_part = sc.alloc<double>(max_p);
+  GainCandDev* d_cd = sc.alloc<GainCandDev>(max_g);
+  int4* d_jobs = sc.alloc<int4>(max_j);
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  if (rc != SLIDE_OK) return rc;
+  for (int si = 0; si < (int)sweeps.size(); ++si) {
+    const FormGroups& w = *sweeps[si];
+    const int ng = (int)w.cd.size();
+    SL_HIP(sc.upload(d_cd, w.cd));
+    SL_HIP(sc.upload(d_jobs, w.jobs));
+    SL_HIP(hipMemsetAsync(be.B, 0, (size_t)w.ncol * be.ld * sizeof(double), s));
+    if ((rc = fill(si, be.B, (int)be.ld)) != SLIDE_OK) return rc;
+    be.kb = be.start ? std::max(0, be.start(si, ng)) : 0;
+    if (be.kb > 0) SL_HIP(hipMemset2DAsync(be.W, be.ld * sizeof(double), 0, (size_t)be.kb * NB * sizeof(double), (size_t)w.ncol, s));
+    be.fwd(w.ncol);
+    launch_gram_blocks(be.W, be.ld, be.rows, be.nrows, d_cd, ng, d_jobs, (int)w.jobs.size(), d_part, d_M, s);
+    SL_HIP(hipGetLastError());
+    if ((rc = done(si, d_cd, d_M)) != SLIDE_OK) return rc;
+  }
+  return SLIDE_OK;
 }
 // Marginals::jointMarginalCovariance of n pose pairs: out144n[144 k ..] the 12 x 12 row-major block [[Saa, Sab], [Sba, Sbb]] of pair k
 // (pose a's six coordinates, then b's; tangent order [rot, trans]).  B: the unit columns of the two poses' rows, so W^T W is the block
@@ -824,6 +874,36 @@ int HostGraph::closure_mahalanobis(int L, const int32_t* from_robot, const uint6
         return SLIDE_OK;
       });
 }
+// What the observation gates resolve of a candidate before the device is asked: its pose and landmark ids (SLIDE_MISSING for a pose
+// or landmark the graph does not hold, or a landmark without a factor), its class's factor type, and z and the sigmas by the add
+// calls' own text (br_meas / cube_meas / cyl_meas; bearing_range_sigma, noise_model_cube_vec x max(|loc.t|, 0.1), cylinder_sigma).
+HostGraph::ObsCand HostGraph::obs_candidate(int robot, uint64_t pose_idx, int cls, uint64_t lm_idx, const double* a) const {
+  ObsCand c;
+  c.type = cls == SLIDE_CLS_ELLIPSOID ? FT_BR : cls == SLIDE_CLS_CUBE ? FT_CUBE : FT_CYL;
+  c.p = pose_id(robot, pose_idx);
+  c.l = lm_lid(cls, lm_idx);
+  c.st = c.p < 0 || c.l < 0 || lm_fids[c.l].empty() ? SLIDE_MISSING : SLIDE_OK;
+  if (c.st != SLIDE_OK) return c;
+  if (c.type == FT_BR) {
+    br_meas(a, a[3], c.z);
+    for (int i = 0; i < 3; ++i) c.sg[i] = P.bearing_range_sigma;
+  } else if (c.type == FT_CUBE) {
+    cube_meas(from7(a), from7(a + 7), a + 14, c.z, c.sg);
+  } else {
+    cyl_meas(from7(a), a + 7, a + 10, a[13], c.z);
+    for (int i = 0; i < 7; ++i) c.sg[i] = P.cylinder_sigma;
+  }
+  return c;
+}
+// The block column at which a sweep of n such candidates starts its forward substitution: that of the lowest pose it touches, the
+// candidates' poses and their landmarks' first observers.  (SLIDE_OBS_GATE_FULL_WALK=1, a measurement aid: column 0.)
+int HostGraph::obs_walk_start(const int32_t* pid, const int32_t* lid, int n) const {
+  const char* fw = std::getenv("SLIDE_OBS_GATE_FULL_WALK");
+  if (fw && fw[0] == '1') return 0;
+  int lo = 1 << 30;
+  for (int i = 0; i < n; ++i) lo = std::min(lo, std::min((int)pid[i], h_lm_first[lid[i]]));
+  return std::min((6 * lo) / NB, G.T - 1);
+}
 // The individual-compatibility test of n candidate landmark observations against the resident factor — the closure gate's counterpart
 // for the factors that make up most of a graph (obs_gate_kernels.hip has the invariant).  Candidate k is the factor
 // add_range_bearing / add_cube / add_cylinder would add between pose (robot, pose_idx) and the EXISTING landmark (cls, lm_idx): z and
@@ -848,29 +928,15 @@ int HostGraph::observation_mahalanobis(int n, const int32_t* robot, const uint64
     for (int e = 0; C81 && e < 81; ++e) C81[81 * (size_t)k + e] = 0.0;
     for (int e = 0; r9 && e < 9; ++e) r9[9 * (size_t)k + e] = 0.0;
     if (dof) dof[k] = landmark_dim(cls[k]);
-    const int p = pose_id(robot[k], pose_idx[k]), l = lm_lid(cls[k], lm_idx[k]);
-    const int st = p < 0 || l < 0 || lm_fids[l].empty() ? SLIDE_MISSING : SLIDE_OK;
-    if (status) status[k] = st;
-    if (st != SLIDE_OK) continue;
-    const double* a = meas17 + 17 * (size_t)k;
-    double z[15] = {}, sg[9] = {};
-    Group& g = groups[cls[k] == SLIDE_CLS_ELLIPSOID ? 0 : cls[k] == SLIDE_CLS_CUBE ? 1 : 2];
-    if (g.type == FT_BR) {
-      br_meas(a, a[3], z);
-      for (int i = 0; i < 3; ++i) sg[i] = P.bearing_range_sigma;
-    } else if (g.type == FT_CUBE) {
-      cube_meas(from7(a), from7(a + 7), a + 14, z, sg);
-    } else {
-      cyl_meas(from7(a), a + 7, a + 10, a[13], z);
-      for (int i = 0; i < 7; ++i) sg[i] = P.cylinder_sigma;
-    }
-    g.pid.push_back(p); g.lid.push_back(l); g.ids.push_back(k);
-    g.z.insert(g.z.end(), z, z + 15);
-    g.sg.insert(g.sg.end(), sg, sg + 9);
+    const ObsCand c = obs_candidate(robot[k], pose_idx[k], cls[k], lm_idx[k], meas17 + 17 * (size_t)k);
+    if (status) status[k] = c.st;
+    if (c.st != SLIDE_OK) continue;
+    Group& g = groups[c.type == FT_BR ? 0 : c.type == FT_CUBE ? 1 : 2];
+    g.pid.push_back(c.p); g.lid.push_back(c.l); g.ids.push_back(k);
+    g.z.insert(g.z.end(), c.z, c.z + 15);
+    g.sg.insert(g.sg.end(), c.sg, c.sg + 9);
   }
   hipStream_t s = stream;
-  const char* fw = std::getenv("SLIDE_OBS_GATE_FULL_WALK");      // (measurement aid: every sweep walks from block column 0)
-  const bool full_walk = fw && fw[0] == '1';
   for (Group& g : groups) {
     if (g.ids.empty()) continue;
     const int m = (int)g.ids.size(), nk = lf_rows(g.type), max_nc = std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / nk);
@@ -914,15 +980,229 @@ int HostGraph::observation_mahalanobis(int n, const int32_t* robot, const uint64
           }
           return SLIDE_OK;
         },
-        [&](int k0, int nc) -> int {
-          if (full_walk) return 0;
-          int lo = 1 << 30;
-          for (int i = k0; i < k0 + nc; ++i) lo = std::min(lo, std::min((int)g.pid[i], h_lm_first[g.lid[i]]));
-          return std::min((6 * lo) / NB, G.T - 1);
-        });
+        [&](int k0, int nc) -> int { return obs_walk_start(g.pid.data() + k0, g.lid.data() + k0, nc); });
     if (rc != SLIDE_OK) return rc;
   }
   return SLIDE_OK;
+}
+
+// The regularised incomplete gamma functions P(a, x) (*lower: by its series, x < a + 1) or Q(a, x) (by Lentz's continued fraction),
+// whichever converges fast at x, and the density x^(a-1) e^-x / Gamma(a) — the textbook pair.
+static double gamma_pq(double a, double x, bool* lower, double* dens) {
+  const double lg = std::lgamma(a), front = std::exp(-x + a * std::log(x) - lg);
+  *dens = front / x;
+  *lower = x < a + 1.0;
+  if (*lower) {
+    double ap = a, del = 1.0 / a, sum = del;
+    for (int n = 0; n < 100000; ++n) {
+      ap += 1.0;
+      del *= x / ap;
+      sum += del;
+      if (std::fabs(del) < std::fabs(sum) * 1e-17) break;
+    }
+    return sum * front;
+  }
+  const double tiny = 1e-300;
+  double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
+  for (int i = 1; i < 100000; ++i) {
+    const double an = -i * (i - a);
+    b += 2.0;
+    d = an * d + b;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = b + an / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (std::fabs(del - 1.0) < 3e-16) break;
+  }
+  return front * h;
+}
+// q with P(dof / 2, q / 2) = prob: Newton on x = q / 2 from the mean, kept inside the bracket the signs seen so far give (a step that
+// leaves it is replaced by the bracket's middle).  The residual is taken on the side the function was computed on (P - prob below
+// the mean's neighbourhood, (1 - prob) - Q above), so the upper tail keeps its digits.
+int chi2_quantile(double prob, int dof, double* q) {
+  if (!q || !(prob > 0.0) || !(prob < 1.0) || dof < 1) {
+    g_last_error = "chi2_quantile: prob outside (0, 1), dof < 1 or a NULL pointer";
+    return SLIDE_ERR_INVALID;
+  }
+  const double a = 0.5 * dof;
+  double lo = 0.0, hi = 0.0, x = a;      // (hi == 0: no upper end yet)
+  for (int it = 0; it < 200; ++it) {
+    bool lower;
+    double dens;
+    const double v = gamma_pq(a, x, &lower, &dens);
+    const double f = lower ? v - prob : (1.0 - prob) - v;      // (P(a, x) - prob either way)
+    if (f > 0.0) hi = x; else lo = x;
+    double xn = x - f / dens;
+    if (!(xn > lo) || (hi > 0.0 && !(xn < hi)) || !std::isfinite(xn)) xn = hi > 0.0 ? 0.5 * (lo + hi) : 2.0 * x;
+    const double step = std::fabs(xn - x);
+    x = xn;
+    if (step <= 1e-15 * x) break;
+  }
+  *q = 2.0 * x;
+  return SLIDE_OK;
+}
+
+// The joint-compatibility test of n_groups hypotheses against the resident factor (obs_joint_kernels.hip has the invariant and the
+// rule; observation_mahalanobis above tests each candidate alone).  Group g is the candidates group_ptr[g] .. group_ptr[g + 1] - 1 in
+// the caller's order, resolved as the individual gate resolves them (obs_candidate); a SLIDE_MISSING candidate is skipped and the rest
+// of its group served as if it were absent.  group_status: SLIDE_ERR_INVALID when two served candidates name one landmark (the
+// invariant needs distinct landmarks), SLIDE_ERR_CAPACITY when the served rows exceed SLIDE_INFO_GAIN_SWEEP_COLS; zeros everywhere in
+// such a group, its neighbours served.  The groups are packed whole, in the caller's order, into sweeps of at most
+// SLIDE_INFO_GAIN_SWEEP_COLS columns; a group's columns are contiguous, its candidates in the caller's order, classes mixed.  Per
+// sweep: one fill launch (k_obs_joint_lin, a class per wavefront), T - k0 substitution launches (the short walk over all its
+// candidates), the gram's two launches over the lower tiles of every group's whole W^T W, the chain (k_joint_compat_chain, one launch
+// per kind of group: factored in LDS up to GAIN_LDS_DIM rows, in the work buffer past it), one read-back.  A group's bits do not
+// depend on what else is in the call or where it stands.  prob == 0: evaluate only, every served candidate is accepted (its d2_joint
+// the prefix sequence of the stacked test).  Whole-call refusals as pose_covariances, nothing written.  Arguments checked by the caller.
+int HostGraph::observation_joint_compatibility(int n_groups, const int32_t* group_ptr, const int32_t* robot, const uint64_t* pose_idx,
+                                               const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double prob, int32_t* accepted,
+                                               double* d2_single, double* d2_joint, int32_t* dof_joint, int32_t* status, double* group_d2,
+                                               int32_t* group_dof, int32_t* group_count, int32_t* group_status) {
+  static_assert(JOINT_MAX_ROWS == SLIDE_INFO_GAIN_SWEEP_COLS, "a group fills one sweep at the most");
+  int rc = marginal_state("observation_joint_compatibility");
+  if (rc != SLIDE_OK) return rc;
+  // q(1 .. JOINT_MAX_ROWS) of the call's probability, built once and kept while the probability stays (zeros: evaluate only)
+  std::vector<double> qtab(JOINT_MAX_ROWS, 0.0);
+  if (prob > 0.0) {
+    static std::mutex q_mtx;
+    static double q_prob = 0.0;
+    static std::vector<double> q_tab;
+    std::lock_guard<std::mutex> lk(q_mtx);
+    if (q_prob != prob) {
+      q_tab.assign(JOINT_MAX_ROWS, 0.0);
+      q_prob = 0.0;
+      for (int d = 0; d < JOINT_MAX_ROWS; ++d)
+        if ((rc = chi2_quantile(prob, d + 1, &q_tab[d])) != SLIDE_OK) return rc;
+      q_prob = prob;
+    }
+    qtab = q_tab;
+  }
+  const int n = n_groups > 0 ? group_ptr[n_groups] : 0;
+  std::vector<ObsCand> cs(n);
+  for (int k = 0; k < n; ++k) {
+    cs[k] = obs_candidate(robot[k], pose_idx[k], cls[k], lm_idx[k], meas17 + 17 * (size_t)k);
+    accepted[k] = 0; d2_single[k] = 0.0; d2_joint[k] = 0.0; dof_joint[k] = 0;
+    status[k] = cs[k].st;
+  }
+  // the sweeps: whole groups in the caller's order; every candidate of a packed group has an entry of the sweep's table
+  struct Sweep : FormGroups {
+    std::vector<int> gid, src;      // the caller's group of each group, the caller's candidate of each entry
+    std::vector<int2> gcand;
+    std::vector<int4> tab;
+    std::vector<int32_t> pid, lid;  // the served candidates' ids (the walk's start)
+    std::vector<double> z, sg;
+    size_t wsz = 0;
+    int lds_rows = 0;
+    bool big = false;
+  };
+  std::vector<Sweep> sweeps;
+  for (int g = 0; g < n_groups; ++g) {
+    group_d2[g] = 0.0; group_dof[g] = 0; group_count[g] = 0; group_status[g] = SLIDE_OK;
+    int rows = 0;
+    bool twice = false;
+    std::vector<int> seen;
+    for (int k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
+      if (cs[k].st != SLIDE_OK) continue;
+      rows += lf_rows(cs[k].type);
+      twice = twice || std::find(seen.begin(), seen.end(), cs[k].l) != seen.end();
+      seen.push_back(cs[k].l);
+    }
+    if (twice) { group_status[g] = SLIDE_ERR_INVALID; continue; }
+    if (rows > SLIDE_INFO_GAIN_SWEEP_COLS) { group_status[g] = SLIDE_ERR_CAPACITY; continue; }
+    if (rows == 0) continue;
+    if (sweeps.empty() || sweeps.back().ncol + rows > SLIDE_INFO_GAIN_SWEEP_COLS) sweeps.emplace_back();
+    Sweep& w = sweeps.back();
+    const int gi = (int)w.cd.size(), nsplit = gain_gram_splits(rows), nt = (rows + 15) / 16;
+    const size_t nn = (size_t)rows * rows;
+    w.cd.push_back(GainCandDev{w.ncol, rows, nsplit, 0, (long long)w.msz, (long long)w.psz, (long long)w.wsz});
+    w.gid.push_back(g);
+    w.gcand.push_back(make_int2((int)w.tab.size(), group_ptr[g + 1] - group_ptr[g]));
+    for (int ta = 0; ta < nt; ++ta)
+      for (int tb = 0; tb <= ta; ++tb)
+        for (int sp = 0; sp < nsplit; ++sp) w.jobs.push_back(make_int4(gi, ta, tb, sp));
+    w.msz += nn;
+    w.psz += nn * nsplit;
+    if (rows > GAIN_LDS_DIM) { w.wsz += nn; w.big = true; }
+    else w.lds_rows = std::max(w.lds_rows, rows);
+    for (int k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
+      const ObsCand& c = cs[k];
+      const bool on = c.st == SLIDE_OK;
+      w.tab.push_back(make_int4(on ? c.type : -1, c.p, c.l, w.ncol));
+      w.src.push_back(k);
+      w.z.insert(w.z.end(), c.z, c.z + 15);
+      w.sg.insert(w.sg.end(), c.sg, c.sg + 9);
+      if (!on) continue;
+      w.pid.push_back(c.p); w.lid.push_back(c.l);
+      w.ncol += lf_rows(c.type);
+    }
+  }
+  if (sweeps.empty()) return SLIDE_OK;
+  size_t max_c = 0, max_g = 0, max_w = 0;
+  std::vector<const FormGroups*> forms;
+  for (const Sweep& w : sweeps) {
+    max_c = std::max(max_c, w.tab.size()); max_g = std::max(max_g, w.cd.size()); max_w = std::max(max_w, w.wsz);
+    forms.push_back(&w);
+  }
+  hipStream_t s = stream;
+  // what comes back, in one buffer: {d2_single, d2_joint} per entry, d2 per group, then {accepted, dof_joint, not SPD} per entry and
+  // {rows, count} per group as ints
+  const size_t o_gd = 2 * max_c, o_i = o_gd + max_g, n_int = 3 * max_c + 2 * max_g, n_out = o_i + (n_int + 1) / 2;
+  Scratch sc(s);
+  int4* d_tab = sc.alloc<int4>(max_c);
+  int2* d_gcand = sc.alloc<int2>(max_g);
+  double* d_z = sc.alloc<double>(15 * max_c);
+  double* d_sg = sc.alloc<double>(9 * max_c);
+  double* d_r = sc.alloc<double>(9 * max_c);
+  double* d_G0 = sc.alloc<double>(81 * max_c);
+  double* d_q = sc.alloc<double>(JOINT_MAX_ROWS);
+  double* d_work = sc.alloc<double>(max_w);
+  double* d_out = sc.alloc<double>(n_out);
+  if (!sc.ok()) { g_last_error = "observation_joint_compatibility: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_q, qtab));
+  int* d_outi = reinterpret_cast<int*>(d_out + o_i);
+  std::vector<double> h(n_out);
+  FormBackend be;
+  form_backend(be, [&](int si, int) -> int { return obs_walk_start(sweeps[si].pid.data(), sweeps[si].lid.data(), (int)sweeps[si].pid.size()); });
+  return sigma_forms_groups_core(
+      "observation_joint_compatibility", be, forms,
+      [&](int si, double* B, int nT) -> int {
+        const Sweep& w = sweeps[si];
+        SL_HIP(sc.upload(d_tab, w.tab));
+        SL_HIP(sc.upload(d_gcand, w.gcand));
+        SL_HIP(sc.upload(d_z, w.z));
+        SL_HIP(sc.upload(d_sg, w.sg));
+        launch_obs_joint_lin(G, d_tab, d_z, d_sg, (int)w.tab.size(), B, nT, d_r, d_G0, s);
+        return SLIDE_OK;
+      },
+      [&](int si, const GainCandDev* d_cd, const double* M) -> int {
+        const Sweep& w = sweeps[si];
+        const int ng = (int)w.cd.size(), nc = (int)w.tab.size();
+        if (launch_joint_compat_chain(d_cd, d_gcand, ng, d_tab, M, d_G0, d_r, d_q, prob > 0.0 ? 0 : 1, d_work, w.lds_rows, w.big, d_out, d_outi,
+                                      d_out + o_gd, d_outi + 3 * max_c, s)) {
+          g_last_error = "observation_joint_compatibility: the device refuses the chain kernel's LDS";
+          return SLIDE_ERR_HIP;
+        }
+        SL_HIP(hipGetLastError());
+        SL_HIP(hipMemcpyAsync(h.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+        const int* hi = reinterpret_cast<const int*>(h.data() + o_i);
+        for (int e = 0; e < nc; ++e) {
+          const int k = w.src[e];
+          if (w.tab[e].x < 0) continue;
+          if (hi[3 * e + 2]) { status[k] = SLIDE_ERR_NOT_SPD; continue; }
+          accepted[k] = hi[3 * e]; dof_joint[k] = hi[3 * e + 1];
+          d2_single[k] = h[2 * e]; d2_joint[k] = h[2 * e + 1];
+        }
+        for (int gi = 0; gi < ng; ++gi) {
+          const int g = w.gid[gi];
+          group_d2[g] = h[o_gd + gi];
+          group_dof[g] = hi[3 * max_c + 2 * gi];
+          group_count[g] = hi[3 * max_c + 2 * gi + 1];
+        }
+        return SLIDE_OK;
+      });
 }
 
 // ---- marginals on the joint graph: the selected inverse over the exact joint pass's factor (joint_cov_kernels.hip) -------

@@ -435,4 +435,21 @@ void launch_joint_obs_gate_lin(const GraphDev* Gs, const JointPoseTab* tab, int 
                                const double* sg9, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s);
 void launch_obs_gate_finish(int m, const double* M, const double* G0, const double* r9, int n, double* out, int* flag, hipStream_t s);
 
+// The joint-compatibility test of groups of candidate observations (obs_joint_kernels.hip has the invariant and the rule).  A sweep
+// holds whole groups; cand[k] = {type (FT_BR / FT_CUBE / FT_CYL; < 0: a skipped candidate), pose id, landmark id, first column of the
+// sweep's B}, in the caller's order, classes mixed; z15 / sg9 / r9 / G0 per entry of that table as above.  The fill is k_obs_gate_lin's
+// body, one wavefront per candidate with the candidate's own class and column.
+constexpr int JOINT_MAX_ROWS = 384;      // rows of a group at the most (one sweep: SLIDE_INFO_GAIN_SWEEP_COLS)
+constexpr int JOINT_TB = 16;             // columns of the factor one step of the chain's triangular solve takes (a shuffle's width)
+void launch_obs_joint_lin(const GraphDev& G, const int4* cand, const double* z15, const double* sg9, int n, double* B, int nT, double* r9,
+                          double* G0, hipStream_t s);
+// grp[g]: the group as one "candidate" of launch_gram_blocks (c0, nk, nsplit, moff, poff; woff its nk x nk slice of `work`, used past
+// GAIN_LDS_DIM rows); gcand[g] = {its first entry of cand, their count}; Mg: the groups' grams (lower 16 x 16 tiles valid);
+// qtab[d - 1]: the chi-square quantile of d = 1 .. JOINT_MAX_ROWS degrees of freedom.  out_d: {d2_single, d2_joint} and out_i:
+// {accepted, dof_joint, 1 where a pivot was not > 0} per entry of cand; gout_d: d2 and gout_i: {rows, count} of each group's accepted
+// set.  lds_rows: the rows of the largest group of at most GAIN_LDS_DIM rows (0: none); any_big: a larger group is in the table.
+int launch_joint_compat_chain(const GainCandDev* grp, const int2* gcand, int ngroups, const int4* cand, const double* Mg, const double* G0,
+                              const double* r9, const double* qtab, int evaluate_only, double* work, int lds_rows, bool any_big, double* out_d,
+                              int* out_i, double* gout_d, int* gout_i, hipStream_t s);
+
 }  // namespace sl

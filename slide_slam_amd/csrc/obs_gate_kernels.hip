@@ -207,6 +207,25 @@ void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const 
   if (n > 0) hipLaunchKernelGGL(k_obs_gate_lin, dim3(n), dim3(64), 0, s, G, type, pid, lid, z15, sg9, n, B, nT, r9, G0);
 }
 
+// The same fill for the joint-compatibility test (obs_joint_kernels.hip), one wavefront per candidate of one graph: the classes are
+// mixed and a candidate's columns start where its group's layout puts them.  cand[k] = {type, pose id, landmark id, first column of
+// B}; type < 0: a candidate the group skips, nothing written.  It sits here because it shares the body above.
+__global__ __launch_bounds__(64) void k_obs_joint_lin(GraphDev G, const int4* __restrict__ cand, const double* __restrict__ z15,
+                                                      const double* __restrict__ sg9, int n, double* __restrict__ B, int nT,
+                                                      double* __restrict__ r9, double* __restrict__ G0) {
+  __shared__ double rec[144];
+  const int k = blockIdx.x;
+  if (k >= n) return;
+  const int4 c = cand[k];
+  if (c.x < 0) return;
+  obs_gate_lin_body(G, G, c.x, c.y, c.z, z15 + 15 * (size_t)k, sg9 + 9 * (size_t)k, rec, B + (size_t)c.w * nT, (size_t)nT, 6 * (size_t)c.y, 0,
+                    nullptr, -1, r9 + 9 * (size_t)k, G0 + 81 * (size_t)k);
+}
+void launch_obs_joint_lin(const GraphDev& G, const int4* cand, const double* z15, const double* sg9, int n, double* B, int nT, double* r9,
+                          double* G0, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_obs_joint_lin, dim3(n), dim3(64), 0, s, G, cand, z15, sg9, n, B, nT, r9, G0);
+}
+
 // The same fill on the JOINT graph of a CholBatch (slide_chol_batch_observation_mahalanobis), one wavefront per candidate.  ends[k] =
 // {graph of the pose, its pose id, graph of the landmark, its landmark id}: the two graphs may differ (robot a's pose against a landmark
 // only robot b has mapped).  Gs: the batch's table of its members' views; tab: per graph its prow map and its system's first row in
