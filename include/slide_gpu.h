@@ -575,6 +575,30 @@ int slide_dense_spd_solve_ex(const double* A, int n, const double* b, double* x,
  * column, 2: two block columns per launch.  After the call the band tiles hold L, the border rows W = B L^-T, the RHS row y = L^-1 b. */
 int slide_debug_chol_bordered(const double* S_in, int ld, int T, int nbr, const int* prof, const int* bfirst, const int* ord, int b0, int kofs,
                               int n_copies, int method, double* S_out, double* Ld_out, double* Winv_out, int* status_out, double* max_copy_diff);
+/* The same hook for a MIXED batch: n (1 .. 32) different systems in ONE launch sequence, each with its own tables, and with the launch
+ * shape under the caller's control.  Per system i: ld[i], T[i], nbr[i], b0[i], kofs[i] as above; S_in / S_out hold the systems one after
+ * the other (system i: ld[i] * T[i] * 64 doubles), Ld_out / Winv_out likewise (T[i] * 4096 / T[i] * 1024 doubles), status_out 8 ints each.
+ * prof / bfirst / ord are concatenated tables; prof_off[i] / bfirst_off[i] / ord_off[i] is where system i's T[i] resp. nbr[i] ints start,
+ * or -1 for NULL (dense / every row from column 0 / rows in their own order).  method 0 / 2 as above.  cu_share (0 .. 100): the percentage
+ * of the compute units the launch sequence may count on, as the production passes hand it to the launches.  assumed_cus: 0 = plan the
+ * launches for the device's own number of compute units, 1 .. that number = plan them as a device with that many would (a smaller count
+ * only: the grid never grows beyond what the device itself could be given); for the duration of this call, on this thread only.
+ * want_l32 != 0: every system with b0[i] == 0 also gets the packed f32 factor copy the joint solve's preconditioner streams
+ * (T (T-1) / 2 * 4096 + 4 floats, prefilled with the bit pattern 0x7fc0dead; tile (j, c), c < j, at 4096 * (c (T-1) - c (c-1) / 2 + j - c - 1),
+ * element (row, col) at col * 64 + row); L32_out receives them one after the other in system order (the others take no room).  The pair
+ * kernel does not write that copy: method 2 then runs the step kernels.  trace_out (5 ints per row, trace_cap rows; may be NULL): one row
+ * {k, a_split, a_joins, type-A workgroups, queue items} per launch actually issued (a_split: 0 for the pair kernel), *n_launches their
+ * number, *n_cu_out the number of compute units the plan was made for.  SLIDE_ERR_INVALID (nothing launched) for n outside 1 .. 32,
+ * cu_share outside 0 .. 100, assumed_cus above the device's count, an ld[i] below (B0 + nbr + 1) * 64. */
+int slide_debug_chol_batch(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* prof, const int* prof_off,
+                           const int* bfirst, const int* bfirst_off, const int* ord, const int* ord_off, const int* b0, const int* kofs,
+                           int method, int cu_share, int assumed_cus, int want_l32, double* S_out, double* Ld_out, double* Winv_out,
+                           int* status_out, float* L32_out, int* trace_out, int trace_cap, int* n_launches, int* n_cu_out);
+/* Its host-only twin: the launches slide_debug_chol_batch would issue for these systems on a device with assumed_cus (>= 1) compute
+ * units, from the same planning code, without touching a device.  Returns the number of launches (<= trace_cap rows written) or
+ * SLIDE_ERR_INVALID. */
+int slide_debug_chol_plan(int n, const int* T, const int* nbr, const int* prof, const int* prof_off, const int* bfirst, const int* bfirst_off,
+                          const int* b0, const int* kofs, int method, int cu_share, int assumed_cus, int* trace_out, int trace_cap);
 /* LDS flag waits of the pair kernel (method 2) that gave up since the library was loaded: 0 unless the kernel is broken (its waits are
  * bounded so that every wave reaches the end of its launch); the tests assert 0. */
 int slide_debug_pair_timeouts(void);

@@ -31,7 +31,7 @@ EXPORTS = [
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
     "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_closure_info_gain_batch", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_closure_info_gain", "slide_chol_batch_closure_info_gain_batch", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
-    "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
+    "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_chol_batch", "slide_debug_chol_plan", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
     "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_inter_loop_closures",
@@ -1033,6 +1033,71 @@ def debug_chol_bordered(S, ld, T, nbr, prof=None, bfirst=None, ord=None, b0=0, k
     _check(lib().slide_debug_chol_bordered(_p(S), C.c_int(ld), C.c_int(T), C.c_int(nbr), pp(pr), pp(bf), pp(od), C.c_int(b0), C.c_int(kofs),
                                            C.c_int(n_copies), C.c_int(method), _p(So), _p(Ld), _p(Wi), _p(st), C.byref(diff)))
     return dict(S=So, Ld=Ld, Winv=Wi, status=st, copy_diff=diff.value)
+
+
+def _chol_batch_tables(systems):
+    """The descriptors of debug_chol_batch / debug_chol_plan as the C calls' flat arrays.  systems: dicts with T, nbr and optionally
+    ld, prof, bfirst, ord, b0, kofs (as debug_chol_bordered takes them)."""
+    n = len(systems)
+    k = max(n, 1)
+    col = lambda key: np.array([int(s.get(key) or 0) for s in systems] + [0] * (k - n), np.int32)
+    flat, off = {}, {}
+    for key in ("prof", "bfirst", "ord"):
+        vals, o = [], np.full(k, -1, np.int32)
+        for i, s in enumerate(systems):
+            if s.get(key) is not None:
+                o[i] = len(vals)
+                vals += [int(x) for x in s[key]]
+                assert len(vals) - o[i] == (s["T"] if key == "prof" else s["nbr"]), key
+        flat[key], off[key] = np.array(vals + [0], np.int32), o
+    return n, col("ld"), col("T"), col("nbr"), col("b0"), col("kofs"), flat, off
+
+
+def debug_chol_plan(systems, method=0, cu_share=100, assumed_cus=256):
+    """slide_debug_chol_plan: the launches debug_chol_batch would issue for these systems on a device with assumed_cus compute units, by
+    the planning code of the real launches; no device needed.  Returns an (launches, 5) int array: k, a_split, a_joins, nAw, nB."""
+    n, _, T, nbr, b0, kofs, flat, off = _chol_batch_tables(systems)
+    cap = 2 * int(T.max()) + 2
+    trace = np.zeros((cap, 5), np.int32)
+    rc = lib().slide_debug_chol_plan(C.c_int(n), _p(T), _p(nbr), _p(flat["prof"]), _p(off["prof"]), _p(flat["bfirst"]), _p(off["bfirst"]),
+                                     _p(b0), _p(kofs), C.c_int(method), C.c_int(cu_share), C.c_int(assumed_cus), _p(trace), C.c_int(cap))
+    if rc < 0:
+        _check(rc)
+    assert rc <= cap
+    return trace[:rc].copy()
+
+
+def debug_chol_batch(systems, method=0, cu_share=100, assumed_cus=0, want_l32=False):
+    """slide_debug_chol_batch: factor n DIFFERENT bordered systems (dicts with S, ld, T, nbr and optionally prof, bfirst, ord, b0, kofs) in
+    one launch sequence, planned for assumed_cus compute units (0: the device's own).  Returns dict(systems=[dict(S, Ld, Winv, status,
+    L32 or None)], trace=(launches, 5) int array of k, a_split, a_joins, nAw, nB, n_cu)."""
+    n, ld, T, nbr, b0, kofs, flat, off = _chol_batch_tables(systems)
+    S = np.concatenate([np.ascontiguousarray(s["S"], dtype=np.float64).ravel() for s in systems]) if n else np.zeros(1)
+    sizes = [int(s["ld"]) * int(s["T"]) * 64 for s in systems]
+    assert all(np.size(s["S"]) == z for s, z in zip(systems, sizes))
+    l32_sizes = [t * (t - 1) // 2 * 4096 + 4 if (want_l32 and not b) else 0 for t, b in zip(T[:n].tolist(), b0[:n].tolist())]
+    Tt = int(T[:n].sum())
+    So, Ld, Wi, st = np.zeros_like(S), np.zeros(max(Tt, 1) * 4096), np.zeros(max(Tt, 1) * 1024), np.zeros(8 * max(n, 1), np.int32)
+    L32 = np.zeros(max(sum(l32_sizes), 1), np.float32)
+    cap = 2 * int(T.max()) + 2
+    trace = np.zeros((cap, 5), np.int32)
+    nl, ncu = C.c_int(0), C.c_int(0)
+    rc = lib().slide_debug_chol_batch(C.c_int(n), _p(S), _p(ld), _p(T), _p(nbr), _p(flat["prof"]), _p(off["prof"]), _p(flat["bfirst"]),
+                                      _p(off["bfirst"]), _p(flat["ord"]), _p(off["ord"]), _p(b0), _p(kofs), C.c_int(method),
+                                      C.c_int(cu_share), C.c_int(assumed_cus), C.c_int(1 if want_l32 else 0), _p(So), _p(Ld), _p(Wi),
+                                      _p(st), _p(L32), _p(trace), C.c_int(cap), C.byref(nl), C.byref(ncu))
+    if rc != SLIDE_OK:
+        err = SlideError(f"{ERR.get(rc, rc)}: {last_error()}")
+        err.code, err.n_launches = rc, nl.value
+        raise err
+    assert nl.value <= cap
+    out, so, to, lo = [], 0, 0, 0
+    for i in range(n):
+        t = int(T[i])
+        out.append(dict(S=So[so:so + sizes[i]], Ld=Ld[to * 4096:(to + t) * 4096], Winv=Wi[to * 1024:(to + t) * 1024], status=st[8 * i:8 * i + 8],
+                        L32=L32[lo:lo + l32_sizes[i]] if l32_sizes[i] else None))
+        so, to, lo = so + sizes[i], to + t, lo + l32_sizes[i]
+    return dict(systems=out, trace=trace[:nl.value].copy(), n_cu=ncu.value)
 
 
 # ---- stand-alone association / place recognition ---------------------------------------------------------

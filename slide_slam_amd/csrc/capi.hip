@@ -610,6 +610,122 @@ int slide_debug_chol_bordered(const double* S_in, int ld, int T, int nbr, const 
   return SLIDE_OK;
 }
 
+// ---- the same on a MIXED batch, every launch shape (slide_gpu.h) -----------------------------------------------------------------------
+// What both entries check of the systems' descriptors; fills the host side of the CholSystems (no device pointer).
+static bool debug_chol_systems(int n, const int* ld, const int* T, const int* nbr, const int* prof, const int* prof_off, const int* bfirst,
+                               const int* bfirst_off, const int* b0, const int* kofs, int method, int cu_share, std::vector<CholSystem>& sys) {
+  if (n < 1 || n > CHOL_STEP_BATCH_MAX || !T || !nbr || (method != 0 && method != 2) || cu_share < 0 || cu_share > 100) return false;
+  sys.assign(n, CholSystem{});
+  for (int i = 0; i < n; ++i) {
+    CholSystem& cs = sys[i];
+    cs.T = T[i]; cs.nbr = nbr[i]; cs.b0 = b0 ? b0[i] : 0; cs.kofs = kofs ? kofs[i] : 0;
+    if (cs.T < 1 || cs.nbr < 0 || cs.b0 < 0 || (cs.b0 > 0 && cs.b0 < cs.T)) return false;
+    if (ld) {
+      cs.ld = ld[i];
+      if (cs.ld < ((cs.b0 > 0 ? cs.b0 : cs.T) + cs.nbr + 1) * NB) return false;
+    }
+    if (prof_off && prof_off[i] >= 0) {
+      if (!prof) return false;
+      cs.h_prof = prof + prof_off[i];
+      for (int c = 0; c < cs.T; ++c)      // monotone, inside the band: the kernels index S by it
+        if (cs.h_prof[c] < c || cs.h_prof[c] >= cs.T || (c > 0 && cs.h_prof[c] < cs.h_prof[c - 1])) return false;
+    }
+    if (bfirst_off && bfirst_off[i] >= 0) {
+      if (!bfirst) return false;
+      cs.h_bfirst = bfirst + bfirst_off[i];
+    }
+  }
+  return true;
+}
+static int copy_trace(const std::vector<int>& trace, int* trace_out, int trace_cap) {
+  const int rows = (int)(trace.size() / 5);
+  if (trace_out && trace_cap > 0) std::memcpy(trace_out, trace.data(), (size_t)std::min(rows, trace_cap) * 5 * sizeof(int));
+  return rows;
+}
+int slide_debug_chol_plan(int n, const int* T, const int* nbr, const int* prof, const int* prof_off, const int* bfirst, const int* bfirst_off,
+                          const int* b0, const int* kofs, int method, int cu_share, int assumed_cus, int* trace_out, int trace_cap) {
+  std::vector<CholSystem> sys;
+  if (assumed_cus < 1 || !debug_chol_systems(n, nullptr, T, nbr, prof, prof_off, bfirst, bfirst_off, b0, kofs, method, cu_share, sys)) return SLIDE_ERR_INVALID;
+  int tick = 0;      // (never dereferenced: a dry run launches nothing)
+  CholPlanHook hook(assumed_cus, true);
+  launch_chol_batch(sys.data(), n, nullptr, nullptr, nullptr, false, cu_share, method == 2 ? &tick : nullptr);
+  return copy_trace(hook.trace, trace_out, trace_cap);
+}
+int slide_debug_chol_batch(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* prof, const int* prof_off,
+                           const int* bfirst, const int* bfirst_off, const int* ord, const int* ord_off, const int* b0, const int* kofs,
+                           int method, int cu_share, int assumed_cus, int want_l32, double* S_out, double* Ld_out, double* Winv_out,
+                           int* status_out, float* L32_out, int* trace_out, int trace_cap, int* n_launches, int* n_cu_out) {
+  if (n_launches) *n_launches = 0;
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  std::vector<CholSystem> sys;
+  if (!S_in || !ld || assumed_cus < 0 || assumed_cus > chol_device_cus() ||
+      !debug_chol_systems(n, ld, T, nbr, prof, prof_off, bfirst, bfirst_off, b0, kofs, method, cu_share, sys))
+    return SLIDE_ERR_INVALID;
+  for (int i = 0; i < n; ++i)
+    if (ord_off && ord_off[i] >= 0) {      // (the j-th active border row is tile row B0 + ord[j]: inside the border)
+      if (!ord) return SLIDE_ERR_INVALID;
+      for (int j = 0; j < sys[i].nbr; ++j)
+        if (ord[ord_off[i] + j] < 0 || ord[ord_off[i] + j] >= sys[i].nbr) return SLIDE_ERR_INVALID;
+    }
+  Tmp Tm;
+  int Tmax = 0;
+  std::vector<size_t> s_off(n + 1, 0), t_off(n + 1, 0), l_off(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    CholSystem& cs = sys[i];
+    const size_t T_ = cs.T, l32 = (want_l32 && cs.b0 == 0) ? T_ * (T_ - 1) / 2 * NB * NB + 4 : 0;
+    s_off[i + 1] = s_off[i] + (size_t)cs.ld * T_ * NB; t_off[i + 1] = t_off[i] + T_; l_off[i + 1] = l_off[i] + l32;
+    Tmax = std::max(Tmax, cs.T);
+    cs.S = Tm.up(S_in + s_off[i], (size_t)cs.ld * T_ * NB);
+    cs.Ld = Tm.up<double>(nullptr, T_ * NB * NB); cs.Winv = Tm.up<double>(nullptr, T_ * 1024);
+    cs.yv = Tm.up<double>(nullptr, T_ * NB); cs.dp = Tm.up<double>(nullptr, T_ * NB);
+    cs.status = Tm.up<int>(nullptr, 8);
+    if (ord_off && ord_off[i] >= 0) cs.ord = Tm.up(ord + ord_off[i], (size_t)cs.nbr);
+    if (l32) cs.L32 = Tm.up<float>(nullptr, l32);
+    if (!cs.S || !cs.Ld || !cs.Winv || !cs.yv || !cs.dp || !cs.status || (ord_off && ord_off[i] >= 0 && !cs.ord) || (l32 && !cs.L32)) {
+      g_last_error = "hipMalloc/hipMemcpy failed";
+      return SLIDE_ERR_HIP;
+    }
+    SL_HIP(hipMemset(cs.status, 0, 8 * sizeof(int)));
+    SL_HIP(hipMemset(cs.Ld, 0, T_ * NB * NB * sizeof(double)));
+    SL_HIP(hipMemset(cs.Winv, 0, T_ * 1024 * sizeof(double)));
+    if (l32) SL_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(cs.L32), 0x7fc0dead, l32));
+  }
+  int* d_ctr = Tm.up<int>(nullptr, (size_t)Tmax + 3);
+  int* d_tick = Tm.up<int>(nullptr, CHOL_STEP_BATCH_MAX);
+  if (!d_ctr || !d_tick) { g_last_error = "hipMalloc failed"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipMemset(d_ctr, 0, ((size_t)Tmax + 3) * sizeof(int)));
+  SL_HIP(hipMemset(d_tick, 0, CHOL_STEP_BATCH_MAX * sizeof(int)));
+  SL_HIP(hipDeviceSynchronize());
+  std::vector<int> trace;
+  int planned_cus = 0;
+  {
+    CholPlanHook hook(assumed_cus, false);      // (gone again before anything below can return)
+    launch_chol_batch(sys.data(), n, d_ctr, nullptr, nullptr, false, cu_share, method == 2 ? d_tick : nullptr);
+    trace.swap(hook.trace);
+    planned_cus = assumed_cus > 0 ? assumed_cus : chol_device_cus();
+  }
+  if (n_launches) *n_launches = copy_trace(trace, trace_out, trace_cap);
+  if (n_cu_out) *n_cu_out = planned_cus;
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  if (method == 2) {      // (the pair kernel's counters are back at zero once its launches are through)
+    int tk[CHOL_STEP_BATCH_MAX];
+    SL_HIP(hipMemcpy(tk, d_tick, sizeof(tk), hipMemcpyDeviceToHost));
+    for (int c = 0; c < CHOL_STEP_BATCH_MAX; ++c)
+      if (tk[c] != 0) { g_last_error = "pair kernel: a ticket counter was left at " + std::to_string(tk[c]); return SLIDE_ERR_HIP; }
+  }
+  for (int i = 0; i < n; ++i) {
+    const CholSystem& cs = sys[i];
+    const size_t T_ = cs.T;
+    if (S_out) SL_HIP(hipMemcpy(S_out + s_off[i], cs.S, (s_off[i + 1] - s_off[i]) * sizeof(double), hipMemcpyDeviceToHost));
+    if (Ld_out) SL_HIP(hipMemcpy(Ld_out + t_off[i] * NB * NB, cs.Ld, T_ * NB * NB * sizeof(double), hipMemcpyDeviceToHost));
+    if (Winv_out) SL_HIP(hipMemcpy(Winv_out + t_off[i] * 1024, cs.Winv, T_ * 1024 * sizeof(double), hipMemcpyDeviceToHost));
+    if (status_out) SL_HIP(hipMemcpy(status_out + 8 * (size_t)i, cs.status, 8 * sizeof(int), hipMemcpyDeviceToHost));
+    if (L32_out && cs.L32) SL_HIP(hipMemcpy(L32_out + l_off[i], cs.L32, (l_off[i + 1] - l_off[i]) * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return SLIDE_OK;
+}
+
 // ---- stand-alone association ------------------------------------------------------------------------
 
 // One class through the frame kernel on caller buffers.  n_cur == 0: pure K-NN gate at `qpos` (cloud = AoS float xyz, as the caller

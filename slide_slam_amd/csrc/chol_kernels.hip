@@ -3023,7 +3023,7 @@ void launch_chol_extract_y(const double* S, int ld, int T, double* yv, double* d
   hipLaunchKernelGGL(k_chol_extract_y, dim3((T * NB + 255) / 256), dim3(256), 0, s, S, ld, T, (b0 > 0 ? b0 : T) + nbr, yv, dp, status, prev);
 }
 struct StepPlan { int kb, nP, g0, g1, nX, TvA, TvB, TvX, nbA, nbB, nbX; long long nA, nB; };
-static int chol_n_cu() {
+int chol_device_cus() {
   static int n_cu = 0;
   if (!n_cu) {
     int dev = 0;
@@ -3032,6 +3032,18 @@ static int chol_n_cu() {
     if (n_cu <= 0) n_cu = 256;
   }
   return n_cu;
+}
+// the test hook of the launch shapes (kernels.hpp): the innermost CholPlanHook alive on this thread, or null
+static thread_local CholPlanHook* t_plan_hook = nullptr;
+CholPlanHook::CholPlanHook(int n_cu_, bool dry_) : n_cu(n_cu_), dry(dry_), prev(t_plan_hook) { t_plan_hook = this; }
+CholPlanHook::~CholPlanHook() { t_plan_hook = prev; }
+static int chol_n_cu() { return (t_plan_hook && t_plan_hook->n_cu > 0) ? t_plan_hook->n_cu : chol_device_cus(); }
+// one row of the hook's trace per launch; true: the launch is not to be issued
+static bool chol_hook_launch(int k, int a_split, int a_joins, long long nAw, long long nB) {
+  CholPlanHook* h = t_plan_hook;
+  if (!h) return false;
+  h->trace.insert(h->trace.end(), {k, a_split, a_joins, (int)nAw, (int)nB});
+  return h->dry;
 }
 // prof (host, T ints, or null = dense): prof[c] = last tile row of block column c inside the monotone profile of the factor (>= c).
 // Column k's tiles reach row prof[k]; the rank-128 pass of pair base kb (panels kb-2, kb-1) touches rows / columns <= prof[kb-1]; the
@@ -3121,16 +3133,35 @@ static PairPlan plan_pair(int k, int T, const int* prof, int nbr, const int* bfi
   }
   return p;
 }
+// The shape of ONE launch over all systems of a batch, decided here and nowhere else (the launches below and, through CholPlanHook, the
+// host-only slide_debug_chol_plan): the per-system plans, the type-A workgroups nAw and queue items nB of the launch, the queue workers
+// beside the type-A workgroups, and whether the type-A workgroups drain the queue after their chain.
+struct PairLaunch { PairPlan pl[CHOL_STEP_BATCH_MAX]; long long nAw, nB, extra; int a_joins; };
+static PairLaunch plan_pair_launch(const CholSystem* d, int n, int k, int n_cu) {
+  PairLaunch L{};
+  for (int i = 0; i < n; ++i) {
+    L.pl[i] = plan_pair(k, d[i].T, d[i].h_prof, d[i].nbr, d[i].h_bfirst, d[i].kofs);
+    L.nAw += (int)(2 * L.pl[i].nA);
+    L.nB += (int)L.pl[i].nB;
+  }
+  L.extra = L.nB < n_cu ? L.nB : n_cu;
+  const long long free_cu = n_cu - L.nAw > 8 ? n_cu - L.nAw : 8;
+  L.a_joins = L.nB > free_cu ? 1 : 0;
+  return L;
+}
 static void launch_chol_pair_steps(const CholSystem* d, int n, int* ctr, int* tickets, hipStream_t s) {
   const int n_cu = chol_n_cu();
   int Tmax = 0;
   for (int i = 0; i < n; ++i) Tmax = d[i].T > Tmax ? d[i].T : Tmax;
   for (int k = 0; k < Tmax; k += 2) {
+    const PairLaunch L = plan_pair_launch(d, n, k, n_cu);
+    if (L.nAw <= 0) continue;
+    if (chol_hook_launch(k, 0, L.a_joins, L.nAw, L.nB)) continue;
     CholPairArgs A{};
     A.n = n;
     A.a_base[0] = A.b_base[0] = 0;
     for (int i = 0; i < n; ++i) {
-      const PairPlan p = plan_pair(k, d[i].T, d[i].h_prof, d[i].nbr, d[i].h_bfirst, d[i].kofs);
+      const PairPlan& p = L.pl[i];
       A.S[i] = d[i].S; A.ld[i] = d[i].ld; A.Ld[i] = d[i].Ld; A.Winv[i] = d[i].Winv; A.status[i] = d[i].status;
       A.ncols[i] = p.ncols; A.Tv0[i] = p.Tv0; A.Tv1[i] = p.Tv1; A.nb0[i] = p.nb0; A.nb1[i] = p.nb1;
       A.TvB[i] = p.TvB; A.nbB[i] = p.nbB; A.nP[i] = p.nP;
@@ -3138,13 +3169,24 @@ static void launch_chol_pair_steps(const CholSystem* d, int n, int* ctr, int* ti
       A.a_base[i + 1] = A.a_base[i] + (int)(2 * p.nA);
       A.b_base[i + 1] = A.b_base[i] + (int)p.nB;
     }
-    const long long nAw = A.a_base[n], nB = A.b_base[n];
-    if (nAw <= 0) continue;
-    const long long extra = nB < n_cu ? nB : n_cu;
-    const long long free_cu = n_cu - nAw > 8 ? n_cu - nAw : 8;
-    const int a_joins = nB > free_cu ? 1 : 0;
-    hipLaunchKernelGGL(k_chol_pair_batched, dim3((unsigned)(nAw + extra)), dim3(PAIR_THREADS), 0, s, A, k, ctr, tickets, a_joins);
+    hipLaunchKernelGGL(k_chol_pair_batched, dim3((unsigned)(L.nAw + L.extra)), dim3(PAIR_THREADS), 0, s, A, k, ctr, tickets, L.a_joins);
   }
+}
+struct StepLaunch { StepPlan pl[CHOL_STEP_BATCH_MAX]; long long nAw, nB, extra; int a_split, a_joins; };
+static StepLaunch plan_step_launch(const CholSystem* d, int n, int k, int cu_share, int n_cu) {
+  StepLaunch L{};
+  long long nA2 = 0;
+  for (int i = 0; i < n; ++i) { L.pl[i] = plan_step(k, d[i].T, d[i].h_prof, d[i].nbr, d[i].h_bfirst, d[i].kofs); nA2 += 2 * L.pl[i].nA; L.nB += (int)L.pl[i].nB; }
+  // two workgroups per type-A tile only while the launch's share of the chip holds them: `cu_share` percent of the CUs (the launch
+  // sequences that run side by side divide the chip: three sequences of eight cut bands at 100 % each 0.63 ms, at 33 - 50 % 0.54)
+  static const int env_share = getenv("SLIDE_CHOL_BSPLIT") ? atoi(getenv("SLIDE_CHOL_BSPLIT")) : -1;
+  const int share = env_share >= 0 ? env_share : cu_share;
+  L.a_split = (k > 0 && (nA2 + L.nB) * 100 <= (long long)n_cu * share) ? 1 : 0;
+  for (int i = 0; i < n; ++i) L.nAw += (int)(L.pl[i].nA << L.a_split);
+  L.extra = L.nB < n_cu ? L.nB : n_cu;
+  const long long free_cu = n_cu - L.nAw > 8 ? n_cu - L.nAw : 8;
+  L.a_joins = L.nB > free_cu ? 1 : 0;
+  return L;
 }
 bool chol_pair_supported(const CholSystem* d, int n) {
   if (n < 1 || n > CHOL_STEP_BATCH_MAX) return false;
@@ -3214,16 +3256,12 @@ void launch_chol_batch(const CholSystem* d, int n, int* ctr, hipStream_t s, hipE
     Tmax = Tmax > 0 ? -Tmax : 0;
   } else if (pair && chol_pair_supported(d, n)) { launch_chol_pair_steps(d, n, ctr, pair_tickets, s); Tmax = Tmax > 0 ? -Tmax : 0; }
   for (int k = 0; k < Tmax; ++k) {
+    const StepLaunch SL = plan_step_launch(d, n, k, cu_share, n_cu);
+    const StepPlan* pl = SL.pl;
+    const int a_split = SL.a_split;
+    if (chol_hook_launch(k, a_split, SL.a_joins, SL.nAw, SL.nB)) continue;
     CholBatchArgs A{};
     A.n = n;
-    long long nA2 = 0, nBt = 0;
-    StepPlan pl[CHOL_STEP_BATCH_MAX];
-    for (int i = 0; i < n; ++i) { pl[i] = plan_step(k, d[i].T, d[i].h_prof, d[i].nbr, d[i].h_bfirst, d[i].kofs); nA2 += 2 * pl[i].nA; nBt += pl[i].nB; }
-    // two workgroups per type-A tile only while the launch's share of the chip holds them: `cu_share` percent of the CUs (the launch
-    // sequences that run side by side divide the chip: three sequences of eight cut bands at 100 % each 0.63 ms, at 33 - 50 % 0.54)
-    static const int env_share = getenv("SLIDE_CHOL_BSPLIT") ? atoi(getenv("SLIDE_CHOL_BSPLIT")) : -1;
-    const int share = env_share >= 0 ? env_share : cu_share;
-    const int a_split = (k > 0 && (nA2 + nBt) * 100 <= (long long)n_cu * share) ? 1 : 0;
     A.a_base[0] = A.b_base[0] = 0;
     for (int i = 0; i < n; ++i) {
       A.S[i] = d[i].S; A.ld[i] = d[i].ld; A.T[i] = d[i].T; A.Ld[i] = d[i].Ld; A.Winv[i] = d[i].Winv; A.status[i] = d[i].status;
@@ -3236,13 +3274,10 @@ void launch_chol_batch(const CholSystem* d, int n, int* ctr, hipStream_t s, hipE
       A.a_base[i + 1] = A.a_base[i] + (int)(pl[i].nA << a_split);
       A.b_base[i + 1] = A.b_base[i] + (int)pl[i].nB;
     }
-    const long long nAw = A.a_base[n], nB = A.b_base[n];
-    const long long extra = nB < n_cu ? nB : n_cu;
-    const long long free_cu = n_cu - nAw > 8 ? n_cu - nAw : 8;
-    const int a_joins = nB > free_cu ? 1 : 0;
     static const int xcd_map = getenv("SLIDE_CHOL_XCD") ? atoi(getenv("SLIDE_CHOL_XCD")) : 0;      // measured r5: 0.529 vs 0.526 ms of band factorisations (noise) - opt-in
-    hipLaunchKernelGGL(k_chol_step_batched, dim3((unsigned)(nAw + extra)), dim3(512), 0, s, A, k, k & ~1, ctr, a_joins, (xcd_map && n > 1) ? 1 : 0);
+    hipLaunchKernelGGL(k_chol_step_batched, dim3((unsigned)(SL.nAw + SL.extra)), dim3(512), 0, s, A, k, k & ~1, ctr, SL.a_joins, (xcd_map && n > 1) ? 1 : 0);
   }
+  if (t_plan_hook && t_plan_hook->dry) return;      // (slide_debug_chol_plan: the shapes only)
   if (Tmax < 0) Tmax = -Tmax;
   if (after_steps) (void)hipEventRecord(after_steps, s);
   if (!solve) {       // the caller continues with the border (k_border_syrk, the separator system) and runs launch_chol_bwd_batch itself

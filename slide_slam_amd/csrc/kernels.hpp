@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 #include "graph_dev.hpp"
 #include "sl_math.hpp"
@@ -98,7 +99,21 @@ struct CholSystem { double* S; int ld, T; double* Ld; double* Winv; double* yv; 
                                                  // every border tile row + the right-hand side (1 << 30: the row is zero in that segment)
 constexpr int CHOL_STEP_BATCH_MAX = 32;      // systems per launch of the batched step kernel (the segments of eight robots' bands in one launch sequence)
 void launch_chol_batch(const CholSystem* d, int n, int* ctr, hipStream_t s, hipEvent_t after_steps = nullptr, bool solve = true, int cu_share = 100, int* pair_tickets = nullptr);      // pair_tickets (CHOL_STEP_BATCH_MAX ints, zero, used by no other launch sequence at the same time): two block columns per launch (k_chol_pair_batched) when the systems allow it (chol_pair_supported)
-bool chol_pair_supported(const CholSystem* d, int n);            // up to 8 systems, one launch per block column; solve = false: steps + extraction of y only; cu_share: percent of the CUs this launch sequence may count on (sequences running side by side)
+// Test hook of launch_chol_batch's launch shapes (slide_debug_chol_batch / slide_debug_chol_plan).  While a CholPlanHook lives, on the
+// thread that made it: the launches are planned for n_cu compute units (0: the device's own), every launch issued appends
+// {k, a_split, a_joins, type-A workgroups, queue items} to `trace`, and with dry set nothing is launched at all (no device is touched when
+// n_cu > 0).  Scoped: the destructor puts back what was there before.  Without one launch_chol_batch tests one thread-local pointer per launch.
+struct CholPlanHook {
+  int n_cu; bool dry; std::vector<int> trace;
+  CholPlanHook(int n_cu_, bool dry_);
+  ~CholPlanHook();
+  CholPlanHook(const CholPlanHook&) = delete;
+  CholPlanHook& operator=(const CholPlanHook&) = delete;
+private:
+  CholPlanHook* prev;
+};
+int chol_device_cus();                         // compute units of the current device (what the launches are planned for without a hook)
+bool chol_pair_supported(const CholSystem* d, int n);           // up to 8 systems, one launch per block column; solve = false: steps + extraction of y only; cu_share: percent of the CUs this launch sequence may count on (sequences running side by side)
 void launch_chol_bwd_batch(const CholSystem* d, int n, hipStream_t s);       // yv -> dp of up to 8 factored systems (chained backward substitution)
 // Left-looking persistent factorisation (k_chol_ll): ALL block columns of the n systems in ONE launch, the kernel boundary per block
 // column replaced by flags between workgroups that start in ticket order.  The plan (task table, flags, device copies of the systems'
