@@ -346,6 +346,38 @@ int slide_chol_batch_observation_mahalanobis(slide_chol_batch_t* b, int n, const
                                              const int32_t* lm_slot /* may be NULL */, const int32_t* cls, const uint64_t* lm_idx,
                                              const double* meas17, double* d2, int32_t* dof /* may be NULL */, double* C81 /* may be NULL */,
                                              double* r9 /* may be NULL */, int32_t* status /* may be NULL */);
+/* slide_graph_observation_joint_compatibility on the JOINT graph: the joint compatibility of a frame's landmark matches, tested
+ * together on the factor of the last whole exact pass.  It mirrors that call — the groups (n_groups, group_ptr), prob (0: evaluate
+ * only), the rule, every output and the status words are its own — and names its candidates as
+ * slide_chol_batch_observation_mahalanobis names them: pose_slot, pose_idx, lm_slot (NULL: the pose's slot), cls, lm_idx, meas17.  A
+ * set of matches from one frame onto shared landmarks, or onto landmarks only another robot has mapped, is the hypothesis that ties
+ * two maps together; it comes from one pose, so its candidates are strongly correlated and the individual gate accepts sets that no
+ * single pose error explains.  No counterpart in the reference.
+ * K = L D L^T is the joint system of the last whole exact pass, D = -I on the lambda block of the inter-robot relative-pose factors.
+ * With a group's served candidates stacked in the caller's order,
+ *     C = I + A K^-1 A^T,     block (i, j) = [i == j] (I + G0_i) + W_i^T D W_j,     L W = B,
+ * B_i and G0_i exactly what the individual joint gate forms for candidate i (a private landmark: G0 = Al H_ll^-1 Al^T and the factor
+ * sum over the landmark's own graph's poses; a shared landmark: G0 = 0 and Al^T on its separator coordinates), the cross blocks the
+ * off-diagonal part of the signed gram.  A PRIVATE landmark — its identity is (lm_slot, lm_idx) — may not be named twice in a group:
+ * H_ll is block diagonal and the cross block would miss Al_i H_ll^-1 Al_j^T; the group gets SLIDE_ERR_INVALID.  A SHARED landmark may
+ * be named twice, also by two robots' poses through two different replicas: it is a separator variable the pass does not eliminate,
+ * everything about it is in K, and its identity is its separator offset, so two replicas are one landmark and give the same bits.
+ * Groups are packed whole, in the caller's order, into sweeps of at most SLIDE_INFO_GAIN_SWEEP_COLS columns; every sweep walks the
+ * whole forward half of the joint substitution; a group's bits do not depend on what else is in the call or where it stands.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written, the message names chol_batch_observation_joint_compatibility and the
+ * reason): the group and probability checks of slide_graph_observation_joint_compatibility and the candidate checks of
+ * slide_graph_observation_mahalanobis (lm_slot, where given, checked like pose_slot), made before the batch or the device is looked
+ * at, the batch is NULL; then those of slide_chol_batch_get_pose_covariances (no whole exact pass yet, the graphs changed since, PCG
+ * passes).  Per candidate, with zeros in its outputs: SLIDE_MISSING as slide_chol_batch_observation_mahalanobis decides it — the
+ * candidate is skipped and the rest of its group served as if it were absent; SLIDE_ERR_NOT_SPD when a pivot is not positive.  Per
+ * group, with zeros everywhere in the group and its neighbours served: SLIDE_ERR_INVALID (a private landmark twice),
+ * SLIDE_ERR_CAPACITY (more than SLIDE_INFO_GAIN_SWEEP_COLS served rows).  Runs on the batch's stream outside any capture and writes
+ * nothing a pass reads; the cached joint Sigma is neither used nor touched. */
+int slide_chol_batch_observation_joint_compatibility(slide_chol_batch_t* b, int n_groups, const int32_t* group_ptr, const int32_t* pose_slot,
+                                                     const uint64_t* pose_idx, const int32_t* lm_slot /* may be NULL */, const int32_t* cls,
+                                                     const uint64_t* lm_idx, const double* meas17, double prob, int32_t* accepted,
+                                                     double* d2_single, double* d2_joint, int32_t* dof_joint, int32_t* status, double* group_d2,
+                                                     int32_t* group_dof, int32_t* group_count, int32_t* group_status);
 /* ---- Robust loss on the exact joint multi-robot pass ------------------------------------------------------------------------------
  * No counterpart in the reference (its inter-robot factors are plain Between factors, graph.cpp:247-258); GTSAM users know it as
  * noiseModel::Robust on the closures of the joint graph.  slide_graph_set_robust_loss's rule, kinds, defaults and class_mask, as a

@@ -49,6 +49,7 @@ EXPORTS = [
     "slide_chol_batch_set_robust_loss", "slide_chol_batch_get_closure_weights", "slide_chol_batch_profile_robust_reweight",
     "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis", "slide_chol_batch_observation_mahalanobis",
     "slide_chol_batch_set_observation_loss", "slide_chol_batch_get_observation_weights", "slide_chol_batch_profile_linearize",
+    "slide_chol_batch_observation_joint_compatibility",
 ]
 
 
@@ -796,6 +797,29 @@ class CholBatch:
         _check(self.L.slide_chol_batch_observation_mahalanobis(C.c_void_p(self.h), C.c_int(n), _p(slot), _p(pidx), _p(lslot), _p(cls), _p(lidx),
                                                                _p(meas), _p(d2), _p(dof), _p(Cm), _p(r), _p(status)))
         return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
+
+    def observation_joint_compatibility(self, groups, prob=0.99):
+        """slide_chol_batch_observation_joint_compatibility: SlideGraph.observation_joint_compatibility on the JOINT graph — a frame's
+        landmark matches tested together on the factor of the last exact pass.  groups: a list of hypotheses, each a list of the
+        candidate tuples observation_mahalanobis takes here (slots for robots, an optional trailing lm_slot), tried in the given
+        order; prob=0 evaluates only.  A private landmark may be named once per group (SLIDE_ERR_INVALID for the group otherwise), a
+        shared one as often as the caller likes, through any replica.  Returns SlideGraph.observation_joint_compatibility's dict:
+        accepted, d2_single, d2_joint, dof_joint, status per candidate; group_d2, group_dof, group_count, group_status per group;
+        group_ptr.  The batch is only read."""
+        groups = [list(g) for g in groups]
+        ng = len(groups)
+        ptr = np.zeros(ng + 1, np.int32)
+        ptr[1:] = np.cumsum([len(g) for g in groups])
+        n, k, slot, pidx, cls, lidx, meas, lslot = _observation_arrays([c for g in groups for c in g], True)
+        acc, dofj, status = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        d2s, d2j = np.zeros(k), np.zeros(k)
+        kg = max(ng, 1)
+        gd2, gdof, gcnt, gst = np.zeros(kg), np.zeros(kg, np.int32), np.zeros(kg, np.int32), np.zeros(kg, np.int32)
+        _check(self.L.slide_chol_batch_observation_joint_compatibility(
+            C.c_void_p(self.h), C.c_int(ng), _p(ptr), _p(slot), _p(pidx), _p(lslot), _p(cls), _p(lidx), _p(meas), C.c_double(prob), _p(acc), _p(d2s),
+            _p(d2j), _p(dofj), _p(status), _p(gd2), _p(gdof), _p(gcnt), _p(gst)))
+        return {"accepted": acc[:n].astype(bool), "d2_single": d2s[:n], "d2_joint": d2j[:n], "dof_joint": dofj[:n], "status": status[:n],
+                "group_d2": gd2[:ng], "group_dof": gdof[:ng], "group_count": gcnt[:ng], "group_status": gst[:ng], "group_ptr": ptr}
 
     def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
         """slide_chol_batch_set_robust_loss: SlideGraph.set_robust_loss's loss (same kinds, names and defaults) on the exact joint

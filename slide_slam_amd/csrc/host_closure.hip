@@ -523,6 +523,29 @@ int slide_chol_batch_observation_mahalanobis(slide_chol_batch_t* b, int n, const
   if (!b) return obs_gate_bad("the batch is NULL");
   return b->b.joint_observation_mahalanobis(n, pose_slot, pose_idx, lm_slot, cls, lm_idx, meas17, d2, dof, C81, r9, status);
 }
+// The joint-compatibility test on the joint graph of a CholBatch: slide_graph_observation_joint_compatibility's groups, probability and
+// outputs, the candidates named as the call above names them.  The argument checks — that call's group and probability checks, then
+// the candidates' with lm_slot checked like pose_slot — come before the batch or the device is looked at and write nothing.
+int slide_chol_batch_observation_joint_compatibility(slide_chol_batch_t* b, int n_groups, const int32_t* group_ptr, const int32_t* pose_slot,
+                                                     const uint64_t* pose_idx, const int32_t* lm_slot, const int32_t* cls, const uint64_t* lm_idx,
+                                                     const double* meas17, double prob, int32_t* accepted, double* d2_single, double* d2_joint,
+                                                     int32_t* dof_joint, int32_t* status, double* group_d2, int32_t* group_dof,
+                                                     int32_t* group_count, int32_t* group_status) {
+  const char* who = "chol_batch_observation_joint_compatibility";
+  if (n_groups < 0) return obs_gate_bad("n_groups < 0", who);
+  if (n_groups > 0 && (!group_ptr || !group_d2 || !group_dof || !group_count || !group_status)) return obs_gate_bad("a needed pointer is NULL", who);
+  if (n_groups > 0 && group_ptr[0] != 0) return obs_gate_bad("group_ptr does not start at 0", who);
+  for (int i = 0; i < n_groups; ++i)
+    if (group_ptr[i + 1] < group_ptr[i]) return obs_gate_bad("group_ptr decreases", who);
+  if (!(prob == 0.0 || (prob > 0.0 && prob < 1.0))) return obs_gate_bad("prob is neither 0 (evaluate only) nor inside (0, 1)", who);
+  const int n = n_groups > 0 ? group_ptr[n_groups] : 0;
+  if (n > 0 && (!accepted || !d2_single || !d2_joint || !dof_joint || !status)) return obs_gate_bad("a needed pointer is NULL", who);
+  const int rc = obs_gate_check_list(n, pose_slot, lm_slot, pose_idx, cls, lm_idx, meas17, d2_joint, who);
+  if (rc != SLIDE_OK) return rc;
+  if (!b) return obs_gate_bad("the batch is NULL", who);
+  return b->b.joint_observation_joint_compatibility(n_groups, group_ptr, pose_slot, pose_idx, lm_slot, cls, lm_idx, meas17, prob, accepted, d2_single,
+                                                    d2_joint, dof_joint, status, group_d2, group_dof, group_count, group_status);
+}
 
 // sloam::FindRelativeMeasurementMatch sloam.cpp:321-412 (host-side bookkeeping: a few dozen stamps per call)
 int slide_find_relative_meas_match(int n_robots, const int64_t* pk_sec, const int64_t* pk_nsec, const int32_t* offsets,

@@ -268,6 +268,12 @@ class CholBatch {
   // shared one at its separator rows
   int joint_observation_mahalanobis(int n, const int32_t* pose_slot, const uint64_t* pose_idx, const int32_t* lm_slot, const int32_t* cls,
                                     const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status);
+  // the joint-compatibility test of groups of such candidates on the JOINT graph (HostGraph::observation_joint_compatibility with the
+  // call above's naming): a private landmark once per group, a shared one as often as the caller likes
+  int joint_observation_joint_compatibility(int n_groups, const int32_t* group_ptr, const int32_t* pose_slot, const uint64_t* pose_idx,
+                                            const int32_t* lm_slot, const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double prob,
+                                            int32_t* accepted, double* d2_single, double* d2_joint, int32_t* dof_joint, int32_t* status,
+                                            double* group_d2, int32_t* group_dof, int32_t* group_count, int32_t* group_status);
 
  private:
   int n;
@@ -440,6 +446,11 @@ class CholBatch {
   void joint_tree(JointTree& t) const;
   struct JointGain;                                // what the joint gain queries share: the tree, the solve's schedule, the grams' row lists
   int joint_sigma_forms(const char* who, JointGain& jg, int ncand, int nk, const FormFill& fill, const FormDone& done);
+  void joint_form_backend(FormBackend& be, JointGain& jg);      // the batch's back end of the quadratic-form drivers (jg outlives be)
+  // what the two observation queries resolve of a candidate on the host: {pose's graph, pose id, landmark's graph, landmark id}, the
+  // row at which a shared landmark enters the walk (-1: private) and its separator offset, z and the sigmas
+  struct JointObsCand { int st = SLIDE_OK, type = 0, sep_off = -1; int4 ends = {0, 0, 0, 0}; long long sep = -1; double z[15] = {}, sg[9] = {}; };
+  JointObsCand joint_obs_candidate(JointGain& jg, int pose_slot, uint64_t pose_idx, int lm_slot, int cls, uint64_t lm_idx, const double* meas17) const;
   int joint_robot(int slot) const;                 // robot id of the graph's own poses
   int joint_end(const JointGain& jg, int slot, uint64_t idx) const;      // one end of a pair or closure: its pose id in the graph of `slot`, or -1
   // the job's point landmarks: every graph's private ones (landmark ids), and of each shared slot that holds one, once, its offset in

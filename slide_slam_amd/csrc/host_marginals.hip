@@ -725,13 +725,17 @@ int HostGraph::sigma_forms(const char* who, int ncand, int nk, const FormFill& f
 // group's nk x nk gram are formed (k_gram_reduce adds the splits of every entry; the upper tiles' sums are of partials nobody wrote
 // and nobody reads).  The split count depends on the group's columns alone, so a group's bits do not depend on its neighbours.  Per
 // sweep: B zeroed, fill(si), the walk from start(si, groups) on, the gram's two launches, done(si, the table on the device, M).
+// Where the factor has rows with D = -I (the joint graph of a batch with lambda rows) the gram is SIGNED as sigma_forms_core signs it:
+// the same job table over rows_neg into Mneg, then k_gram_sub over the sweep's whole M — the never-written upper tiles hold sums of
+// partials nobody wrote in M and Mneg alike, and their difference is read by nobody; a variant restricted to the lower tiles would
+// save a few kilobytes of traffic in a launch that is bound by its latency.  The subtraction is entry by entry, so a group's bits
+// still depend on its own columns and the row lists alone.  A back end without such rows queues exactly the launches above.
 struct FormGroups { int ncol = 0; std::vector<GainCandDev> cd; std::vector<int4> jobs; size_t msz = 0, psz = 0; };
 using GroupFill = std::function<int(int si, double* B, int ld)>;
 using GroupDone = std::function<int(int si, const GainCandDev* d_cd, const double* M)>;
 static int sigma_forms_groups_core(const char* who, FormBackend& be, const std::vector<const FormGroups*>& sweeps, const GroupFill& fill,
                                    const GroupDone& done) {
   hipStream_t s = be.s;
-  if (be.nrows_neg > 0) { g_last_error = std::string(who) + ": groups are served on factors without signed rows only"; return SLIDE_ERR_INVALID; }
   int max_ncol = 0;
   size_t max_m = 0, max_p = 0, max_g = 0, max_j = 0;
   for (const FormGroups* w : sweeps) {
@@ -742,6 +746,7 @@ static int sigma_forms_groups_core(const char* who, FormBackend& be, const std::
   Scratch sc(s);
   int rc = be.alloc(sc, max_ncol);
   double* d_M = sc.alloc<double>(max_m);
+  double* d_Mneg = sc.alloc<double>(be.nrows_neg > 0 ? max_m : 0);
   double* d_part = sc.alloc<double>(max_p);
   GainCandDev* d_cd = sc.alloc<GainCandDev>(max_g);
   int4* d_jobs = sc.alloc<int4>(max_j);
@@ -758,6 +763,10 @@ static int sigma_forms_groups_core(const char* who, FormBackend& be, const std::
     if (be.kb > 0) SL_HIP(hipMemset2DAsync(be.W, be.ld * sizeof(double), 0, (size_t)be.kb * NB * sizeof(double), (size_t)w.ncol, s));
     be.fwd(w.ncol);
     launch_gram_blocks(be.W, be.ld, be.rows, be.nrows, d_cd, ng, d_jobs, (int)w.jobs.size(), d_part, d_M, s);
+    if (be.nrows_neg > 0) {
+      launch_gram_blocks(be.W, be.ld, be.rows_neg, be.nrows_neg, d_cd, ng, d_jobs, (int)w.jobs.size(), d_part, d_Mneg, s);
+      launch_gram_sub(d_M, d_Mneg, w.msz, s);
+    }
     SL_HIP(hipGetLastError());
     if ((rc = done(si, d_cd, d_M)) != SLIDE_OK) return rc;
   }
@@ -1044,6 +1053,155 @@ int chi2_quantile(double prob, int dof, double* q) {
   return SLIDE_OK;
 }
 
+// ---- what the two joint-compatibility calls share (one graph below, the joint graph of a CholBatch at the end of this file) -----------
+// The caller resolves its candidates (JcCand: the class's factor type or -1 for a skipped one, the two ids the sweep's table carries,
+// the landmark's identity and whether a group may name it once only, z and the sigmas); JcPlan packs whole groups into sweeps, holds
+// the quantile table, the device buffers of the fill and the chain and the read-back's layout, runs the chain and scatters.
+struct JcOutputs {
+  int32_t* accepted; double *d2_single, *d2_joint; int32_t *dof_joint, *status;
+  double* group_d2; int32_t *group_dof, *group_count, *group_status;
+};
+struct JcCand { int type = -1, p = -1, l = -1; long long ident = 0; bool once = true; const double *z = nullptr, *sg = nullptr; };
+struct JcSweep : FormGroups {
+  std::vector<int> gid, src;      // the caller's group of each group, the caller's candidate of each entry
+  std::vector<int2> gcand;
+  std::vector<int4> tab;          // {type (-1: skipped), p, l, first column} per entry: what the fill and the chain read
+  std::vector<double> z, sg;
+  size_t wsz = 0;
+  int lds_rows = 0;
+  bool big = false;
+};
+struct JcPlan {
+  std::vector<JcSweep> sweeps;
+  std::vector<const FormGroups*> forms;
+  std::vector<double> qtab, h;
+  size_t max_c = 0, max_g = 0, max_w = 0, o_gd = 0, o_i = 0, n_out = 0;
+  int4* d_tab = nullptr;
+  int2* d_gcand = nullptr;
+  double *d_z = nullptr, *d_sg = nullptr, *d_r = nullptr, *d_G0 = nullptr, *d_q = nullptr, *d_work = nullptr, *d_out = nullptr;
+  // q(1 .. JOINT_MAX_ROWS) of the call's probability, built once and kept while the probability stays (zeros: evaluate only)
+  int quantiles(double prob) {
+    qtab.assign(JOINT_MAX_ROWS, 0.0);
+    if (!(prob > 0.0)) return SLIDE_OK;
+    static std::mutex q_mtx;
+    static double q_prob = 0.0;
+    static std::vector<double> q_tab;
+    std::lock_guard<std::mutex> lk(q_mtx);
+    if (q_prob != prob) {
+      q_tab.assign(JOINT_MAX_ROWS, 0.0);
+      q_prob = 0.0;
+      for (int d = 0; d < JOINT_MAX_ROWS; ++d) {
+        const int rc = chi2_quantile(prob, d + 1, &q_tab[d]);
+        if (rc != SLIDE_OK) return rc;
+      }
+      q_prob = prob;
+    }
+    qtab = q_tab;
+    return SLIDE_OK;
+  }
+  // the sweeps: whole groups in the caller's order; every candidate of a packed group has an entry of the sweep's table.  A group
+  // that names a once-only landmark twice (SLIDE_ERR_INVALID) or has more than a sweep's rows (SLIDE_ERR_CAPACITY) is left out.
+  void pack(int n_groups, const int32_t* group_ptr, const std::vector<JcCand>& cs, const JcOutputs& o) {
+    for (int g = 0; g < n_groups; ++g) {
+      o.group_d2[g] = 0.0; o.group_dof[g] = 0; o.group_count[g] = 0; o.group_status[g] = SLIDE_OK;
+      int rows = 0;
+      bool twice = false;
+      std::vector<long long> seen;
+      for (int k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
+        if (cs[k].type < 0) continue;
+        rows += lf_rows(cs[k].type);
+        if (!cs[k].once) continue;
+        twice = twice || std::find(seen.begin(), seen.end(), cs[k].ident) != seen.end();
+        seen.push_back(cs[k].ident);
+      }
+      if (twice) { o.group_status[g] = SLIDE_ERR_INVALID; continue; }
+      if (rows > SLIDE_INFO_GAIN_SWEEP_COLS) { o.group_status[g] = SLIDE_ERR_CAPACITY; continue; }
+      if (rows == 0) continue;
+      if (sweeps.empty() || sweeps.back().ncol + rows > SLIDE_INFO_GAIN_SWEEP_COLS) sweeps.emplace_back();
+      JcSweep& w = sweeps.back();
+      const int gi = (int)w.cd.size(), nsplit = gain_gram_splits(rows), nt = (rows + 15) / 16;
+      const size_t nn = (size_t)rows * rows;
+      w.cd.push_back(GainCandDev{w.ncol, rows, nsplit, 0, (long long)w.msz, (long long)w.psz, (long long)w.wsz});
+      w.gid.push_back(g);
+      w.gcand.push_back(make_int2((int)w.tab.size(), group_ptr[g + 1] - group_ptr[g]));
+      for (int ta = 0; ta < nt; ++ta)
+        for (int tb = 0; tb <= ta; ++tb)
+          for (int sp = 0; sp < nsplit; ++sp) w.jobs.push_back(make_int4(gi, ta, tb, sp));
+      w.msz += nn;
+      w.psz += nn * nsplit;
+      if (rows > GAIN_LDS_DIM) { w.wsz += nn; w.big = true; }
+      else w.lds_rows = std::max(w.lds_rows, rows);
+      for (int k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
+        const JcCand& c = cs[k];
+        const bool on = c.type >= 0;
+        w.tab.push_back(make_int4(on ? c.type : -1, c.p, c.l, w.ncol));
+        w.src.push_back(k);
+        w.z.insert(w.z.end(), c.z, c.z + 15);
+        w.sg.insert(w.sg.end(), c.sg, c.sg + 9);
+        if (on) w.ncol += lf_rows(c.type);
+      }
+    }
+    for (const JcSweep& w : sweeps) {
+      max_c = std::max(max_c, w.tab.size()); max_g = std::max(max_g, w.cd.size()); max_w = std::max(max_w, w.wsz);
+      forms.push_back(&w);
+    }
+    // what comes back, in one buffer: {d2_single, d2_joint} per entry, d2 per group, then {accepted, dof_joint, not SPD} per entry and
+    // {rows, count} per group as ints
+    o_gd = 2 * max_c; o_i = o_gd + max_g;
+    n_out = o_i + (3 * max_c + 2 * max_g + 1) / 2;
+  }
+  // the buffers of the fill and the chain, from the query's scratch (the caller asks sc.ok() after its own allocations)
+  void alloc(Scratch& sc) {
+    d_tab = sc.alloc<int4>(max_c);
+    d_gcand = sc.alloc<int2>(max_g);
+    d_z = sc.alloc<double>(15 * max_c);
+    d_sg = sc.alloc<double>(9 * max_c);
+    d_r = sc.alloc<double>(9 * max_c);
+    d_G0 = sc.alloc<double>(81 * max_c);
+    d_q = sc.alloc<double>(JOINT_MAX_ROWS);
+    d_work = sc.alloc<double>(max_w);
+    d_out = sc.alloc<double>(n_out);
+    h.resize(n_out);
+  }
+  int upload(Scratch& sc, int si) {
+    const JcSweep& w = sweeps[si];
+    SL_HIP(sc.upload(d_tab, w.tab));
+    SL_HIP(sc.upload(d_gcand, w.gcand));
+    SL_HIP(sc.upload(d_z, w.z));
+    SL_HIP(sc.upload(d_sg, w.sg));
+    return SLIDE_OK;
+  }
+  // the chain on the sweep's (signed) gram, one read-back, the scatter into the caller's arrays
+  int finish(const char* who, int si, const GainCandDev* d_cd, const double* M, double prob, hipStream_t s, const JcOutputs& o) {
+    const JcSweep& w = sweeps[si];
+    const int ng = (int)w.cd.size(), nc = (int)w.tab.size();
+    int* d_outi = reinterpret_cast<int*>(d_out + o_i);
+    if (launch_joint_compat_chain(d_cd, d_gcand, ng, d_tab, M, d_G0, d_r, d_q, prob > 0.0 ? 0 : 1, d_work, w.lds_rows, w.big, d_out, d_outi,
+                                  d_out + o_gd, d_outi + 3 * max_c, s)) {
+      g_last_error = std::string(who) + ": the device refuses the chain kernel's LDS";
+      return SLIDE_ERR_HIP;
+    }
+    SL_HIP(hipGetLastError());
+    SL_HIP(hipMemcpyAsync(h.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    const int* hi = reinterpret_cast<const int*>(h.data() + o_i);
+    for (int e = 0; e < nc; ++e) {
+      const int k = w.src[e];
+      if (w.tab[e].x < 0) continue;
+      if (hi[3 * e + 2]) { o.status[k] = SLIDE_ERR_NOT_SPD; continue; }
+      o.accepted[k] = hi[3 * e]; o.dof_joint[k] = hi[3 * e + 1];
+      o.d2_single[k] = h[2 * e]; o.d2_joint[k] = h[2 * e + 1];
+    }
+    for (int gi = 0; gi < ng; ++gi) {
+      const int g = w.gid[gi];
+      o.group_d2[g] = h[o_gd + gi];
+      o.group_dof[g] = hi[3 * max_c + 2 * gi];
+      o.group_count[g] = hi[3 * max_c + 2 * gi + 1];
+    }
+    return SLIDE_OK;
+  }
+};
+
 // The joint-compatibility test of n_groups hypotheses against the resident factor (obs_joint_kernels.hip has the invariant and the
 // rule; observation_mahalanobis above tests each candidate alone).  Group g is the candidates group_ptr[g] .. group_ptr[g + 1] - 1 in
 // the caller's order, resolved as the individual gate resolves them (obs_candidate); a SLIDE_MISSING candidate is skipped and the rest
@@ -1063,146 +1221,41 @@ int HostGraph::observation_joint_compatibility(int n_groups, const int32_t* grou
   static_assert(JOINT_MAX_ROWS == SLIDE_INFO_GAIN_SWEEP_COLS, "a group fills one sweep at the most");
   int rc = marginal_state("observation_joint_compatibility");
   if (rc != SLIDE_OK) return rc;
-  // q(1 .. JOINT_MAX_ROWS) of the call's probability, built once and kept while the probability stays (zeros: evaluate only)
-  std::vector<double> qtab(JOINT_MAX_ROWS, 0.0);
-  if (prob > 0.0) {
-    static std::mutex q_mtx;
-    static double q_prob = 0.0;
-    static std::vector<double> q_tab;
-    std::lock_guard<std::mutex> lk(q_mtx);
-    if (q_prob != prob) {
-      q_tab.assign(JOINT_MAX_ROWS, 0.0);
-      q_prob = 0.0;
-      for (int d = 0; d < JOINT_MAX_ROWS; ++d)
-        if ((rc = chi2_quantile(prob, d + 1, &q_tab[d])) != SLIDE_OK) return rc;
-      q_prob = prob;
-    }
-    qtab = q_tab;
-  }
+  const char* who = "observation_joint_compatibility";
+  const JcOutputs o{accepted, d2_single, d2_joint, dof_joint, status, group_d2, group_dof, group_count, group_status};
+  JcPlan P;
+  if ((rc = P.quantiles(prob)) != SLIDE_OK) return rc;
   const int n = n_groups > 0 ? group_ptr[n_groups] : 0;
   std::vector<ObsCand> cs(n);
+  std::vector<JcCand> jc(n);
   for (int k = 0; k < n; ++k) {
     cs[k] = obs_candidate(robot[k], pose_idx[k], cls[k], lm_idx[k], meas17 + 17 * (size_t)k);
     accepted[k] = 0; d2_single[k] = 0.0; d2_joint[k] = 0.0; dof_joint[k] = 0;
     status[k] = cs[k].st;
+    jc[k] = JcCand{cs[k].st == SLIDE_OK ? cs[k].type : -1, cs[k].p, cs[k].l, cs[k].l, true, cs[k].z, cs[k].sg};
   }
-  // the sweeps: whole groups in the caller's order; every candidate of a packed group has an entry of the sweep's table
-  struct Sweep : FormGroups {
-    std::vector<int> gid, src;      // the caller's group of each group, the caller's candidate of each entry
-    std::vector<int2> gcand;
-    std::vector<int4> tab;
-    std::vector<int32_t> pid, lid;  // the served candidates' ids (the walk's start)
-    std::vector<double> z, sg;
-    size_t wsz = 0;
-    int lds_rows = 0;
-    bool big = false;
-  };
-  std::vector<Sweep> sweeps;
-  for (int g = 0; g < n_groups; ++g) {
-    group_d2[g] = 0.0; group_dof[g] = 0; group_count[g] = 0; group_status[g] = SLIDE_OK;
-    int rows = 0;
-    bool twice = false;
-    std::vector<int> seen;
-    for (int k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
-      if (cs[k].st != SLIDE_OK) continue;
-      rows += lf_rows(cs[k].type);
-      twice = twice || std::find(seen.begin(), seen.end(), cs[k].l) != seen.end();
-      seen.push_back(cs[k].l);
-    }
-    if (twice) { group_status[g] = SLIDE_ERR_INVALID; continue; }
-    if (rows > SLIDE_INFO_GAIN_SWEEP_COLS) { group_status[g] = SLIDE_ERR_CAPACITY; continue; }
-    if (rows == 0) continue;
-    if (sweeps.empty() || sweeps.back().ncol + rows > SLIDE_INFO_GAIN_SWEEP_COLS) sweeps.emplace_back();
-    Sweep& w = sweeps.back();
-    const int gi = (int)w.cd.size(), nsplit = gain_gram_splits(rows), nt = (rows + 15) / 16;
-    const size_t nn = (size_t)rows * rows;
-    w.cd.push_back(GainCandDev{w.ncol, rows, nsplit, 0, (long long)w.msz, (long long)w.psz, (long long)w.wsz});
-    w.gid.push_back(g);
-    w.gcand.push_back(make_int2((int)w.tab.size(), group_ptr[g + 1] - group_ptr[g]));
-    for (int ta = 0; ta < nt; ++ta)
-      for (int tb = 0; tb <= ta; ++tb)
-        for (int sp = 0; sp < nsplit; ++sp) w.jobs.push_back(make_int4(gi, ta, tb, sp));
-    w.msz += nn;
-    w.psz += nn * nsplit;
-    if (rows > GAIN_LDS_DIM) { w.wsz += nn; w.big = true; }
-    else w.lds_rows = std::max(w.lds_rows, rows);
-    for (int k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
-      const ObsCand& c = cs[k];
-      const bool on = c.st == SLIDE_OK;
-      w.tab.push_back(make_int4(on ? c.type : -1, c.p, c.l, w.ncol));
-      w.src.push_back(k);
-      w.z.insert(w.z.end(), c.z, c.z + 15);
-      w.sg.insert(w.sg.end(), c.sg, c.sg + 9);
-      if (!on) continue;
-      w.pid.push_back(c.p); w.lid.push_back(c.l);
-      w.ncol += lf_rows(c.type);
-    }
-  }
-  if (sweeps.empty()) return SLIDE_OK;
-  size_t max_c = 0, max_g = 0, max_w = 0;
-  std::vector<const FormGroups*> forms;
-  for (const Sweep& w : sweeps) {
-    max_c = std::max(max_c, w.tab.size()); max_g = std::max(max_g, w.cd.size()); max_w = std::max(max_w, w.wsz);
-    forms.push_back(&w);
-  }
+  P.pack(n_groups, group_ptr, jc, o);
+  if (P.sweeps.empty()) return SLIDE_OK;
   hipStream_t s = stream;
-  // what comes back, in one buffer: {d2_single, d2_joint} per entry, d2 per group, then {accepted, dof_joint, not SPD} per entry and
-  // {rows, count} per group as ints
-  const size_t o_gd = 2 * max_c, o_i = o_gd + max_g, n_int = 3 * max_c + 2 * max_g, n_out = o_i + (n_int + 1) / 2;
   Scratch sc(s);
-  int4* d_tab = sc.alloc<int4>(max_c);
-  int2* d_gcand = sc.alloc<int2>(max_g);
-  double* d_z = sc.alloc<double>(15 * max_c);
-  double* d_sg = sc.alloc<double>(9 * max_c);
-  double* d_r = sc.alloc<double>(9 * max_c);
-  double* d_G0 = sc.alloc<double>(81 * max_c);
-  double* d_q = sc.alloc<double>(JOINT_MAX_ROWS);
-  double* d_work = sc.alloc<double>(max_w);
-  double* d_out = sc.alloc<double>(n_out);
-  if (!sc.ok()) { g_last_error = "observation_joint_compatibility: out of device memory"; return SLIDE_ERR_HIP; }
-  SL_HIP(sc.upload(d_q, qtab));
-  int* d_outi = reinterpret_cast<int*>(d_out + o_i);
-  std::vector<double> h(n_out);
+  P.alloc(sc);
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(P.d_q, P.qtab));
   FormBackend be;
-  form_backend(be, [&](int si, int) -> int { return obs_walk_start(sweeps[si].pid.data(), sweeps[si].lid.data(), (int)sweeps[si].pid.size()); });
+  form_backend(be, [&](int si, int) -> int {      // (the walk's start: the served candidates' ids)
+    std::vector<int32_t> pid, lid;
+    for (const int4& e : P.sweeps[si].tab)
+      if (e.x >= 0) { pid.push_back(e.y); lid.push_back(e.z); }
+    return obs_walk_start(pid.data(), lid.data(), (int)pid.size());
+  });
   return sigma_forms_groups_core(
-      "observation_joint_compatibility", be, forms,
+      who, be, P.forms,
       [&](int si, double* B, int nT) -> int {
-        const Sweep& w = sweeps[si];
-        SL_HIP(sc.upload(d_tab, w.tab));
-        SL_HIP(sc.upload(d_gcand, w.gcand));
-        SL_HIP(sc.upload(d_z, w.z));
-        SL_HIP(sc.upload(d_sg, w.sg));
-        launch_obs_joint_lin(G, d_tab, d_z, d_sg, (int)w.tab.size(), B, nT, d_r, d_G0, s);
+        if ((rc = P.upload(sc, si)) != SLIDE_OK) return rc;
+        launch_obs_joint_lin(G, P.d_tab, P.d_z, P.d_sg, (int)P.sweeps[si].tab.size(), B, nT, P.d_r, P.d_G0, s);
         return SLIDE_OK;
       },
-      [&](int si, const GainCandDev* d_cd, const double* M) -> int {
-        const Sweep& w = sweeps[si];
-        const int ng = (int)w.cd.size(), nc = (int)w.tab.size();
-        if (launch_joint_compat_chain(d_cd, d_gcand, ng, d_tab, M, d_G0, d_r, d_q, prob > 0.0 ? 0 : 1, d_work, w.lds_rows, w.big, d_out, d_outi,
-                                      d_out + o_gd, d_outi + 3 * max_c, s)) {
-          g_last_error = "observation_joint_compatibility: the device refuses the chain kernel's LDS";
-          return SLIDE_ERR_HIP;
-        }
-        SL_HIP(hipGetLastError());
-        SL_HIP(hipMemcpyAsync(h.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-        const int* hi = reinterpret_cast<const int*>(h.data() + o_i);
-        for (int e = 0; e < nc; ++e) {
-          const int k = w.src[e];
-          if (w.tab[e].x < 0) continue;
-          if (hi[3 * e + 2]) { status[k] = SLIDE_ERR_NOT_SPD; continue; }
-          accepted[k] = hi[3 * e]; dof_joint[k] = hi[3 * e + 1];
-          d2_single[k] = h[2 * e]; d2_joint[k] = h[2 * e + 1];
-        }
-        for (int gi = 0; gi < ng; ++gi) {
-          const int g = w.gid[gi];
-          group_d2[g] = h[o_gd + gi];
-          group_dof[g] = hi[3 * max_c + 2 * gi];
-          group_count[g] = hi[3 * max_c + 2 * gi + 1];
-        }
-        return SLIDE_OK;
-      });
+      [&](int si, const GainCandDev* d_cd, const double* M) -> int { return P.finish(who, si, d_cd, M, prob, s, o); });
 }
 
 // ---- marginals on the joint graph: the selected inverse over the exact joint pass's factor (joint_cov_kernels.hip) -------
@@ -1699,6 +1752,8 @@ struct CholBatch::JointGain {
   std::vector<size_t> off;
   size_t N = 0, nl = 0, ldv = 1;
   std::vector<int> rows_slot, rows_all, rows_sh, lms, lm0;
+  std::vector<int> rows_pos, rows_neg;               // (joint_form_backend: form_rows' two lists)
+  std::vector<long long> sep_first;                  // (joint_obs_candidate: per separator row its entry row, built on first use)
   // the device side, from the query's scratch
   JSinvSys* d_sys = nullptr;
   int4* d_jobs = nullptr;
@@ -1956,13 +2011,15 @@ int CholBatch::joint_closure_info_gain_batch(int slot, int n_cand, const int32_t
 // pair of launches and the subtraction only where the job has lambda rows), what done() queues, one read-back.  A candidate's bits
 // depend on its own columns and the row lists alone.  joint_state first, under pass_mtx; nothing the pass reads is written and the
 // cached joint Sigma is neither used nor touched.
-int CholBatch::joint_sigma_forms(const char* who, JointGain& jg, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+// (the batch's back end of the quadratic-form drivers, for candidates of equal width and for groups alike: R and W of N rows, the
+// joint plan's forward half — it has no short walk, so be.start stays unset — and form_rows' two lists, kept in jg)
+void CholBatch::joint_form_backend(FormBackend& be, JointGain& jg) {
   hipStream_t s = master;
-  std::vector<int> pos, neg;
+  std::vector<int>&pos = jg.rows_pos, &neg = jg.rows_neg;
+  pos.clear(); neg.clear();
   jg.form_rows(pos, neg);
-  FormBackend be;
   be.s = s; be.ld = jg.N; be.nrows = (int)pos.size(); be.nrows_neg = (int)neg.size();
-  be.alloc = [&](Scratch& sc, int max_ncol) -> int {
+  be.alloc = [this, &be, &jg, &pos, &neg](Scratch& sc, int max_ncol) -> int {
     be.W = sc.alloc<double>(jg.N * max_ncol);
     be.B = sc.alloc<double>(jg.N * max_ncol);
     int* d_rows = sc.alloc<int>(pos.size() + neg.size());
@@ -1979,7 +2036,11 @@ int CholBatch::joint_sigma_forms(const char* who, JointGain& jg, int ncand, int 
     SL_HIP(sc.upload(jg.d_tab, tab));
     return SLIDE_OK;
   };
-  be.fwd = [&](int ncol) { jg.forward(be.W, be.B, ncol, s); };
+  be.fwd = [&be, &jg, s](int ncol) { jg.forward(be.W, be.B, ncol, s); };
+}
+int CholBatch::joint_sigma_forms(const char* who, JointGain& jg, int ncand, int nk, const FormFill& fill, const FormDone& done) {
+  FormBackend be;
+  joint_form_backend(be, jg);
   return sigma_forms_core(who, be, ncand, nk, fill, done);
 }
 // One end of a candidate: its pose id in the graph of `slot`, or -1 (a slot the batch does not have, a pose its graph does not hold)
@@ -2096,6 +2157,61 @@ int CholBatch::joint_closure_mahalanobis(int L, const int32_t* from_slot, const 
         return SLIDE_OK;
       });
 }
+// What the two observation queries on the joint graph resolve of a candidate before the device is asked (HostGraph::obs_candidate's
+// counterpart): the pose's id in the graph of pose_slot, the landmark's id in the graph of lm_slot, SLIDE_MISSING for a slot the batch
+// lacks, a pose or landmark its graph does not hold, or a landmark with neither a factor nor a shared slot; for a SHARED landmark its
+// separator offset sep_off and the joint row sep at which Al^T enters the walk; z and the sigmas by the add calls' own text with the
+// parameters of the POSE's graph.
+// Where a right-hand side on the separator coordinates [so, so + d) enters the walk: the separator's own rows of R are WRITTEN by
+// the walk (k_jms_sum: the sum of the robots' rows of separator coordinates), so the entry goes to those rows of the LOWEST robot
+// whose border holds them — one place whichever replica names the landmark, and 0 + x = x in the sum.  -1: no robot holds them.
+static long long sep_entry_row(const std::vector<long long>& sep_first, int so, int d) {
+  if (so < 0 || (size_t)(so + d) >= sep_first.size() || sep_first[so] < 0) return -1;
+  for (int c = 1; c < d; ++c)
+    if (sep_first[so + c] != sep_first[so] + c) return -1;      // (a landmark's coordinates are one run of its robot's border)
+  return sep_first[so];
+}
+CholBatch::JointObsCand CholBatch::joint_obs_candidate(JointGain& jg, int ps, uint64_t pose_idx, int ls, int cls, uint64_t lm_idx,
+                                                       const double* a) const {
+  JointObsCand c;
+  c.type = cls == SLIDE_CLS_ELLIPSOID ? FT_BR : cls == SLIDE_CLS_CUBE ? FT_CUBE : FT_CYL;
+  const int p = joint_end(jg, ps, pose_idx);
+  int l = -1;
+  if (ls >= 0 && ls < n) {
+    const HostGraph* gl = graphs[ls];
+    l = gl->lm_lid(cls, lm_idx);
+    if (l >= 0 && (size_t)l >= gl->up_L) l = -1;
+    if (l >= 0 && (size_t)l < gl->h_lm_bord.size() && gl->h_lm_bord[l] >= 0) {
+      int so = -1;
+      for (size_t q = 0; q < gl->h_sh_lid.size(); ++q)
+        if (gl->h_sh_lid[q] == l) { so = gl->h_sep_off[q]; break; }
+      if (so >= 0 && jg.sep_first.empty()) {      // per separator row: its joint row in the lowest robot that maps it (-1: none)
+        jg.sep_first.assign((size_t)jg.t.Tsep * NB + 1, -1);
+        for (int i = n - 1; i >= 0; --i)
+          for (int o = 0; o < jg.t.gn[i]; ++o)
+            if (jg.t.map[i][o] >= 0) jg.sep_first[jg.t.map[i][o]] = (long long)jg.off[1 + i] + (long long)jg.t.Tc[i] * NB + o;
+      }
+      c.sep = so >= 0 ? sep_entry_row(jg.sep_first, so, landmark_dim(cls)) : -1;
+      c.sep_off = c.sep >= 0 ? so : -1;
+      if (c.sep < 0) l = -1;
+    }
+    if (l >= 0 && c.sep < 0 && gl->lm_fids[l].empty()) l = -1;
+  }
+  c.st = p < 0 || l < 0 ? SLIDE_MISSING : SLIDE_OK;
+  if (c.st != SLIDE_OK) return c;
+  c.ends = make_int4(ps, p, ls, l);
+  const HostGraph* gp = graphs[ps];
+  if (c.type == FT_BR) {
+    HostGraph::br_meas(a, a[3], c.z);
+    for (int i = 0; i < 3; ++i) c.sg[i] = gp->P.bearing_range_sigma;
+  } else if (c.type == FT_CUBE) {
+    gp->cube_meas(from7(a), from7(a + 7), a + 14, c.z, c.sg);
+  } else {
+    HostGraph::cyl_meas(from7(a), a + 7, a + 10, a[13], c.z);
+    for (int i = 0; i < 7; ++i) c.sg[i] = gp->P.cylinder_sigma;
+  }
+  return c;
+}
 // HostGraph::observation_mahalanobis on the joint graph (obs_gate_kernels.hip has the invariant): candidate k is the factor
 // add_range_bearing / add_cube / add_cylinder would add between pose (pose_slot, pose_idx) and the EXISTING landmark (cls, lm_idx) of
 // the graph in lm_slot (null: the pose's slot) — the two may differ: robot a's pose against a landmark only robot b has mapped.  z and
@@ -2117,22 +2233,6 @@ int CholBatch::joint_observation_mahalanobis(int n_q, const int32_t* pose_slot, 
   if (rc != SLIDE_OK) return rc;
   JointGain jg;
   jg.build(*this, 0);
-  // Where a right-hand side on the separator coordinates [so, so + d) enters the walk: the separator's own rows of R are WRITTEN by
-  // the walk (k_jms_sum: the sum of the robots' rows of separator coordinates), so the entry goes to those rows of the LOWEST robot
-  // whose border holds them — one place whichever replica names the landmark, and 0 + x = x in the sum.  -1: no robot holds them.
-  std::vector<long long> sep_first;                  // per separator row: its joint row in the lowest robot that maps it (-1: none), built on first use
-  auto sep_entry_row = [&](int so, int d) -> long long {
-    if (sep_first.empty()) {
-      sep_first.assign((size_t)jg.t.Tsep * NB + 1, -1);
-      for (int i = n - 1; i >= 0; --i)
-        for (int o = 0; o < jg.t.gn[i]; ++o)
-          if (jg.t.map[i][o] >= 0) sep_first[jg.t.map[i][o]] = (long long)jg.off[1 + i] + (long long)jg.t.Tc[i] * NB + o;
-    }
-    if (so < 0 || (size_t)(so + d) >= sep_first.size() || sep_first[so] < 0) return -1;
-    for (int c = 1; c < d; ++c)
-      if (sep_first[so + c] != sep_first[so] + c) return -1;      // (a landmark's coordinates are one run of its robot's border)
-    return sep_first[so];
-  };
   struct Group { int type = 0; std::vector<int4> ends; std::vector<long long> sep; std::vector<double> z, sg; std::vector<int> ids; };
   Group groups[3];
   groups[0].type = FT_BR; groups[1].type = FT_CUBE; groups[2].type = FT_CYL;
@@ -2141,42 +2241,14 @@ int CholBatch::joint_observation_mahalanobis(int n_q, const int32_t* pose_slot, 
     for (int e = 0; C81 && e < 81; ++e) C81[81 * (size_t)k + e] = 0.0;
     for (int e = 0; r9 && e < 9; ++e) r9[9 * (size_t)k + e] = 0.0;
     if (dof) dof[k] = landmark_dim(cls[k]);
-    const int ps = pose_slot[k], ls = lm_slot ? lm_slot[k] : ps;
-    const int p = joint_end(jg, ps, pose_idx[k]);
-    int l = -1;
-    long long sep = -1;
-    if (ls >= 0 && ls < n) {
-      const HostGraph* gl = graphs[ls];
-      l = gl->lm_lid(cls[k], lm_idx[k]);
-      if (l >= 0 && (size_t)l >= gl->up_L) l = -1;
-      if (l >= 0 && (size_t)l < gl->h_lm_bord.size() && gl->h_lm_bord[l] >= 0) {
-        int so = -1;
-        for (size_t q = 0; q < gl->h_sh_lid.size(); ++q)
-          if (gl->h_sh_lid[q] == l) { so = gl->h_sep_off[q]; break; }
-        sep = so >= 0 ? sep_entry_row(so, landmark_dim(cls[k])) : -1;
-        if (sep < 0) l = -1;
-      }
-      if (l >= 0 && sep < 0 && gl->lm_fids[l].empty()) l = -1;
-    }
-    const int st = p < 0 || l < 0 ? SLIDE_MISSING : SLIDE_OK;
-    if (status) status[k] = st;
-    if (st != SLIDE_OK) continue;
-    const HostGraph* gp = graphs[ps];
-    const double* a = meas17 + 17 * (size_t)k;
-    double z[15] = {}, sg[9] = {};
-    Group& g = groups[cls[k] == SLIDE_CLS_ELLIPSOID ? 0 : cls[k] == SLIDE_CLS_CUBE ? 1 : 2];
-    if (g.type == FT_BR) {
-      HostGraph::br_meas(a, a[3], z);
-      for (int i = 0; i < 3; ++i) sg[i] = gp->P.bearing_range_sigma;
-    } else if (g.type == FT_CUBE) {
-      gp->cube_meas(from7(a), from7(a + 7), a + 14, z, sg);
-    } else {
-      HostGraph::cyl_meas(from7(a), a + 7, a + 10, a[13], z);
-      for (int i = 0; i < 7; ++i) sg[i] = gp->P.cylinder_sigma;
-    }
-    g.ends.push_back(make_int4(ps, p, ls, l)); g.sep.push_back(sep); g.ids.push_back(k);
-    g.z.insert(g.z.end(), z, z + 15);
-    g.sg.insert(g.sg.end(), sg, sg + 9);
+    const JointObsCand c = joint_obs_candidate(jg, pose_slot[k], pose_idx[k], lm_slot ? lm_slot[k] : pose_slot[k], cls[k], lm_idx[k],
+                                               meas17 + 17 * (size_t)k);
+    if (status) status[k] = c.st;
+    if (c.st != SLIDE_OK) continue;
+    Group& g = groups[c.type == FT_BR ? 0 : c.type == FT_CUBE ? 1 : 2];
+    g.ends.push_back(c.ends); g.sep.push_back(c.sep); g.ids.push_back(k);
+    g.z.insert(g.z.end(), c.z, c.z + 15);
+    g.sg.insert(g.sg.end(), c.sg, c.sg + 9);
   }
   hipStream_t s = master;
   for (Group& g : groups) {
@@ -2226,5 +2298,72 @@ int CholBatch::joint_observation_mahalanobis(int n_q, const int32_t* pose_slot, 
     if (rc != SLIDE_OK) return rc;
   }
   return SLIDE_OK;
+}
+// HostGraph::observation_joint_compatibility on the joint graph (obs_joint_kernels.hip has the invariant): the groups, prob, outputs
+// and status words are that call's, the candidates are named and resolved as joint_observation_mahalanobis names and resolves them
+// (joint_obs_candidate).  With a group's served candidates stacked, block (i, j) of C is [i == j] (I + G0_i) + W_i^T D W_j, L W = B on
+// the pass's K = L D L^T: B_i and G0_i exactly what the individual joint gate writes, the cross blocks the off-diagonal part of the
+// signed gram over form_rows' two lists.  A PRIVATE landmark — identity (lm_slot, local id) — may not be named twice in a group: H_ll
+// is block diagonal and the cross block would miss Al_i H_ll^-1 Al_j^T (group_status SLIDE_ERR_INVALID).  A SHARED landmark —
+// identity its separator offset, so two replicas are one landmark — may: it is a separator variable the pass does not eliminate,
+// everything about it is in K, and W_i^T D W_j is the whole cross block.  Whole groups are packed into sweeps as on one graph
+// (JcPlan); per sweep: one memset of R, one fill launch (k_joint_obs_joint_lin, classes mixed), one walk of the whole forward half of
+// the joint plan, the gram's two launches over the lower tiles (a second pair and k_gram_sub only where the job has lambda rows), the
+// chain, one read-back.  A group's bits do not depend on what else is in the call or where it stands.  Per candidate: SLIDE_MISSING
+// (skipped, the group served without it), SLIDE_ERR_NOT_SPD; per group: SLIDE_ERR_INVALID, SLIDE_ERR_CAPACITY (zeros, the neighbours
+// served).  Whole-call refusals: joint_state's, nothing written.  Nothing the pass reads is written; the cached joint Sigma is
+// neither used nor touched.  Arguments checked by the caller.
+int CholBatch::joint_observation_joint_compatibility(int n_groups, const int32_t* group_ptr, const int32_t* pose_slot, const uint64_t* pose_idx,
+                                                     const int32_t* lm_slot, const int32_t* cls, const uint64_t* lm_idx, const double* meas17,
+                                                     double prob, int32_t* accepted, double* d2_single, double* d2_joint, int32_t* dof_joint,
+                                                     int32_t* status, double* group_d2, int32_t* group_dof, int32_t* group_count,
+                                                     int32_t* group_status) {
+  const char* who = "chol_batch_observation_joint_compatibility";
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state(who, 0);
+  if (rc != SLIDE_OK) return rc;
+  JointGain jg;
+  jg.build(*this, 0);
+  const JcOutputs o{accepted, d2_single, d2_joint, dof_joint, status, group_d2, group_dof, group_count, group_status};
+  JcPlan P;
+  if ((rc = P.quantiles(prob)) != SLIDE_OK) return rc;
+  const int nq = n_groups > 0 ? group_ptr[n_groups] : 0;
+  std::vector<JointObsCand> cs(nq);
+  std::vector<JcCand> jc(nq);
+  for (int k = 0; k < nq; ++k) {
+    JointObsCand& c = cs[k];
+    c = joint_obs_candidate(jg, pose_slot[k], pose_idx[k], lm_slot ? lm_slot[k] : pose_slot[k], cls[k], lm_idx[k], meas17 + 17 * (size_t)k);
+    accepted[k] = 0; d2_single[k] = 0.0; d2_joint[k] = 0.0; dof_joint[k] = 0;
+    status[k] = c.st;
+    const bool shared = c.sep >= 0;
+    jc[k] = JcCand{c.st == SLIDE_OK ? c.type : -1, c.ends.y, c.ends.w, shared ? (long long)c.sep_off : ((long long)c.ends.z << 32) | (unsigned)c.ends.w,
+                   !shared, c.z, c.sg};
+  }
+  P.pack(n_groups, group_ptr, jc, o);
+  if (P.sweeps.empty()) return SLIDE_OK;
+  hipStream_t s = master;
+  Scratch sc(s);
+  P.alloc(sc);
+  int4* d_ends = sc.alloc<int4>(P.max_c);
+  long long* d_sep = sc.alloc<long long>(P.max_c);
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(P.d_q, P.qtab));
+  std::vector<int4> ends;
+  std::vector<long long> sep;
+  FormBackend be;
+  joint_form_backend(be, jg);
+  return sigma_forms_groups_core(
+      who, be, P.forms,
+      [&](int si, double* B, int ld) -> int {
+        const JcSweep& w = P.sweeps[si];
+        ends.clear(); sep.clear();
+        for (int k : w.src) { ends.push_back(cs[k].ends); sep.push_back(cs[k].sep); }
+        if ((rc = P.upload(sc, si)) != SLIDE_OK) return rc;
+        SL_HIP(sc.upload(d_ends, ends));
+        SL_HIP(sc.upload(d_sep, sep));
+        launch_joint_obs_joint_lin(d_Gs, jg.d_tab, P.d_tab, d_ends, d_sep, P.d_z, P.d_sg, (int)w.tab.size(), B, (size_t)ld, P.d_r, P.d_G0, s);
+        return SLIDE_OK;
+      },
+      [&](int si, const GainCandDev* d_cd, const double* M) -> int { return P.finish(who, si, d_cd, M, prob, s, o); });
 }
 }  // namespace sl

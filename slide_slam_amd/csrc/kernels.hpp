@@ -458,6 +458,10 @@ constexpr int JOINT_MAX_ROWS = 384;      // rows of a group at the most (one swe
 constexpr int JOINT_TB = 16;             // columns of the factor one step of the chain's triangular solve takes (a shuffle's width)
 void launch_obs_joint_lin(const GraphDev& G, const int4* cand, const double* z15, const double* sg9, int n, double* B, int nT, double* r9,
                           double* G0, hipStream_t s);
+// the same fill on the joint graph of a CholBatch: cand[k] = {type, ., ., first column} (what the chain reads of it), the pose and the
+// landmark named by ends[k] and sep_row[k] as launch_joint_obs_gate_lin names them
+void launch_joint_obs_joint_lin(const GraphDev* Gs, const JointPoseTab* tab, const int4* cand, const int4* ends, const long long* sep_row,
+                                const double* z15, const double* sg9, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s);
 // grp[g]: the group as one "candidate" of launch_gram_blocks (c0, nk, nsplit, moff, poff; woff its nk x nk slice of `work`, used past
 // GAIN_LDS_DIM rows); gcand[g] = {its first entry of cand, their count}; Mg: the groups' grams (lower 16 x 16 tiles valid);
 // qtab[d - 1]: the chi-square quantile of d = 1 .. JOINT_MAX_ROWS degrees of freedom.  out_d: {d2_single, d2_joint} and out_i:

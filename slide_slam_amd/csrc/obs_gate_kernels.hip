@@ -251,6 +251,30 @@ void launch_joint_obs_gate_lin(const GraphDev* Gs, const JointPoseTab* tab, int 
   if (n > 0) hipLaunchKernelGGL(k_joint_obs_gate_lin, dim3(n), dim3(64), 0, s, Gs, tab, type, ends, sep_row, z15, sg9, n, B, ld, r9, G0);
 }
 
+// The joint graph's fill for the joint-compatibility test (slide_chol_batch_observation_joint_compatibility; obs_joint_kernels.hip has
+// the invariant): k_joint_obs_gate_lin with a class, a first column and a separator row per wavefront, as k_obs_joint_lin is to
+// k_obs_gate_lin.  cand[k] = {type, ., ., first column of B} (the table k_joint_compat_chain reads; type < 0: a candidate the group
+// skips, nothing written), ends[k] and sep_row[k] as above.
+__global__ __launch_bounds__(64) void k_joint_obs_joint_lin(const GraphDev* __restrict__ Gs, const JointPoseTab* __restrict__ tab,
+                                                            const int4* __restrict__ cand, const int4* __restrict__ ends,
+                                                            const long long* __restrict__ sep_row, const double* __restrict__ z15,
+                                                            const double* __restrict__ sg9, int n, double* __restrict__ B, size_t ld,
+                                                            double* __restrict__ r9, double* __restrict__ G0) {
+  __shared__ double rec[144];
+  const int k = blockIdx.x;
+  if (k >= n) return;
+  const int4 c = cand[k];
+  if (c.x < 0) return;
+  const int4 e = ends[k];
+  obs_gate_lin_body(Gs[e.x], Gs[e.z], c.x, e.y, e.w, z15 + 15 * (size_t)k, sg9 + 9 * (size_t)k, rec, B + (size_t)c.w * ld, ld,
+                    (size_t)tab->off[e.x] + tab->prow[e.x][e.y], (size_t)tab->off[e.z], tab->prow[e.z], sep_row[k], r9 + 9 * (size_t)k,
+                    G0 + 81 * (size_t)k);
+}
+void launch_joint_obs_joint_lin(const GraphDev* Gs, const JointPoseTab* tab, const int4* cand, const int4* ends, const long long* sep_row,
+                                const double* z15, const double* sg9, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_joint_obs_joint_lin, dim3(n), dim3(64), 0, s, Gs, tab, cand, ends, sep_row, z15, sg9, n, B, ld, r9, G0);
+}
+
 // k_obs_gate_finish, one wavefront per candidate (four to a workgroup): C = (I + G0) + M, M the candidate's m x m gram W_k^T W_k at
 // m m k; entries (a, b) and (b, a) are one sum of the same operands, so C is symmetric bit for bit.  Lane 0 factors C = G G^T in
 // registers, solves G y = r and forms d2 = y^T y.  A pivot that is not > 0: flag[k] = 1 and zeros.  out: OBS_GATE_OUT doubles per

@@ -10,6 +10,19 @@
 // landmarks is F_i^T S^-1 F_j alone, which the columns of B carry already.  So C is the group's whole gram W^T W (cov_kernels.hip's
 // k_gram_blocks over the lower 16 x 16 tiles) plus I + G0_i on the diagonal blocks.
 //
+//
+// On the JOINT graph of a CholBatch (slide_chol_batch_observation_joint_compatibility) K = L D L^T is the joint system of the last whole
+// exact pass, D = -I on the lambda block of the inter-robot relative-pose factors, and with the same stacking
+//     C = I + A K^-1 A^T,     block (i, j) = [i == j] (I + G0_i) + W_i^T D W_j,     L W = B,
+// B_i and G0_i exactly what k_joint_obs_gate_lin writes for candidate i (obs_gate_kernels.hip; k_joint_obs_joint_lin is that fill with a
+// class and a column per wavefront).  Private landmark: G0 = Al H_ll^-1 Al^T, the factor sum over the landmark's own graph's poses in
+// joint rows.  Shared landmark: G0 = 0, Al^T on its separator coordinates through the lowest robot's rows.  The cross blocks are the
+// off-diagonal part of the SIGNED gram M - Mneg over JointGain::form_rows' two lists (host_marginals.hip).  A private landmark may not
+// be named twice in a group — identity (landmark's slot, local id): H_ll is block diagonal and the cross block would miss
+// Al_i H_ll^-1 Al_j^T.  A shared landmark may — identity its separator offset, two replicas being one landmark: it is a separator
+// variable the pass does not eliminate, everything about it is in K, and W_i^T D W_j is the whole cross block.  The chain below runs on
+// the signed gram as it is: it reads ([a == b] + G0[hi][lo]) + M[hi][lo] below the diagonal only, so C stays symmetric bit for bit.
+//
 // The rule (k_joint_compat_chain, one workgroup per group, the candidates in the caller's order): S the accepted set, L_S L_S^T = C_SS
 // and y_S = L_S^-1 r_S kept as they grow, d2_S = y_S^T y_S.  For candidate i
 //     d2_single = r_i^T C_ii^-1 r_i,

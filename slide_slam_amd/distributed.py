@@ -712,6 +712,13 @@ class PassDriver:
         self._joint_ok()
         return self.batch.observation_mahalanobis(candidates)
 
+    def observation_joint_compatibility(self, groups, prob=0.99):
+        """The joint compatibility of groups of such candidates, tested together on the joint graph:
+        CholBatch.observation_joint_compatibility (accepted, d2_single, d2_joint, dof_joint, status per candidate; group_d2, group_dof,
+        group_count, group_status per group; group_ptr)."""
+        self._joint_ok()
+        return self.batch.observation_joint_compatibility(groups, prob)
+
     # ---- robust loss and observation loss on the exact joint pass (CholBatch.set_robust_loss / set_observation_loss, slide_gpu.h) ------
     def _loss_agreed(self, who, what, kind, param, *classes):
         """What both loss setters check first: the driver carries losses at all, and the ranks of a job set the same one."""
