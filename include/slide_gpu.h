@@ -1066,6 +1066,72 @@ int slide_graph_observation_joint_compatibility(slide_graph_t* g, int n_groups, 
  * reference (boost::math::quantile(chi_squared(dof), prob) is the usual spelling).  SLIDE_ERR_INVALID for prob outside (0, 1) or not a
  * number, dof < 1, q NULL. */
 int slide_chi2_quantile(double prob, int dof, double* q);
+/* Duplicate landmarks: the Mahalanobis test of a list of landmark PAIRS against the graph as it stands.  The gates above judge a loop
+ * closure, an observation and a frame of observations; none of them judges the commonest association failure, one object mapped
+ * twice: an object that lost its match and was initialised again under a new id.  The reference has no answer (its Euclidean
+ * nearest-neighbour gate decides once, per frame, and never looks back); EKF-SLAM and GTSAM users write this query by hand from
+ * Marginals::jointMarginalCovariance({L(i), L(j)}).  A Euclidean distance cannot decide it: a true duplicate re-sighted after 35 poses
+ * of drift sits as far from its twin as a distinct object seen from the same poses.
+ * Pair k names two EXISTING landmarks (cls[k], idx_a[k]) and (cls[k], idx_b[k]) of one class: SLIDE_CLS_ELLIPSOID (D = 3) or
+ * SLIDE_CLS_CYLINDER (D = 7), which both retract additively, so the difference is exact.  Cubes are refused, on the host: a box pose is
+ * ambiguous under its own symmetries and a tangent difference means nothing without handling them.  The hypothesis is "a and b are one
+ * object, up to a model noise sigma[D]" (sigma_point3 / sigma_cylinder7, per call and class, every entry > 0; a class no pair names may
+ * pass NULL): two fits of one object from different views differ by centimetres.  In the tangent order of
+ * slide_graph_get_landmark_covariances (point xyz; cylinder [ray, root, radius]):
+ *     d     = est_b - est_a                       at the CURRENT ESTIMATE (what slide_graph_get_landmark returns)
+ *     r     = d / sigma
+ *     Sig_d = Sig_aa + Sig_bb - Sig_ab - Sig_ba   at the LAST LINEARISATION POINT (the resident factor)
+ *     C     = I + diag(1 / sigma) Sig_d diag(1 / sigma)
+ *     d2[k] = r^T C^-1 r                          chi-square with D degrees of freedom for one object
+ * No threshold is applied by the call: compare d2 with slide_chi2_quantile(0.99, D), 11.345 or 18.475.  The graph is only read.
+ * With the landmarks eliminated H_ll is block diagonal; with Al = -I / sigma on a and +I / sigma on b,
+ *     C = I + Al_a Hinv_a Al_a^T + Al_b Hinv_b Al_b^T + B^T S^-1 B,
+ *     B = - sum_{f in factors(a)} P_{p_f}^T F_f Al_a^T - sum_{f in factors(b)} P_{p_f}^T F_f Al_b^T,
+ * and the landmark-landmark cross block is never formed.  The host chooses one of two routes per pair, from the structure alone, so a
+ * pair's bits do not depend on the rest of the list; route[k] says which.  Route 0, direct: every pose that observes a or b lies inside
+ * one reach of the tile profile (always, on a dense profile), so every Sigma(p_f, p_g) needed is an entry of the selected inverse that
+ * slide_graph_get_pose_covariances computes once per factorisation; one wavefront per pair sums the four blocks, scales, factors C and
+ * solves — no substitution at all.  This is the common case, a landmark initialised again a few frames after it was lost.  Route 1,
+ * substitution: every other pair (a revisit across the profile) goes through the forward substitution of the gates above, B^T S^-1 B =
+ * W^T W with L W = B, SLIDE_INFO_GAIN_SWEEP_COLS / D pairs per sweep (128 points, 54 cylinders), the walk starting at the block column
+ * of the sweep's lowest observer.  SLIDE_LM_PAIR_SUBSTITUTE=1 in the environment sends every pair down route 1 (a measurement and test
+ * aid).
+ * Outputs follow slide_graph_observation_mahalanobis: dof[k] = D; C81 row-major with leading dimension 9, zero outside the D x D block,
+ * symmetric bit for bit; r9; route[k] 0 or 1.  dof, C81, r9, route and status may be NULL.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written, the message names landmark_pair_mahalanobis and the reason), decided on the
+ * host before the graph or the device is looked at: n < 0, a needed pointer NULL, a class that is neither of the two, a sigma that is
+ * non-finite or <= 0, the graph is NULL; then those of slide_graph_get_pose_covariances.  n == 0 on a graph that would be served:
+ * SLIDE_OK.  Per pair, into status[k] with zeros in its outputs: SLIDE_MISSING for a landmark the graph does not hold or one without a
+ * factor, SLIDE_ERR_INVALID when a and b are the same landmark, SLIDE_ERR_NOT_SPD when a pivot of C is not positive. */
+int slide_graph_landmark_pair_mahalanobis(slide_graph_t* g, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b,
+                                          const double* sigma_point3, const double* sigma_cylinder7, double* d2,
+                                          int32_t* dof /* may be NULL */, double* C81 /* may be NULL */, double* r9 /* may be NULL */,
+                                          int32_t* route /* may be NULL */, int32_t* status /* may be NULL */);
+/* Marginals::jointMarginalCovariance({L(a), L(b)}) for n landmark pairs of one class each, the counterpart of
+ * slide_graph_get_pose_pair_covariances.  All three classes are served: a covariance at the linearisation point has no symmetry
+ * problem.  out324n[324 k ..] = [[Saa, Sab], [Sba, Sbb]], the 2 D x 2 D block (D = 3 / 9 / 7) row-major with leading dimension 18, zero
+ * padded, in the tangent order of slide_graph_get_landmark_covariances.  Routes as above: the four blocks off the selected inverse, or
+ * 2 D unit columns through the forward substitution.  Route choice, refusals (the message names get_landmark_pair_covariances; any
+ * landmark class is accepted and there is no sigma) and the status words SLIDE_MISSING and SLIDE_ERR_INVALID are those of the test;
+ * route and status may be NULL.  It lets a caller rebuild Sig_d, or test another hypothesis than the difference. */
+int slide_graph_get_landmark_pair_covariances(slide_graph_t* g, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b,
+                                              double* out324n, int32_t* route /* may be NULL */, int32_t* status /* may be NULL */);
+/* Finding the candidates: a deterministic fixed-radius pair search on the device.  Every i < j of the n points xyz (3 doubles each)
+ * with |x_i - x_j| <= radius, the distance in double, and label[i] == label[j] where label is given; sorted by (i, j).  *n_pairs is
+ * always the total.  Above cap: SLIDE_ERR_CAPACITY, and nothing but n_pairs is written.  SLIDE_ERR_INVALID (nothing written, the
+ * message names pairs_within): n < 0, cap < 0, a needed pointer NULL (the outputs are needed when cap > 0), a radius that is non-finite
+ * or <= 0.  Count, scan, emit: ballot compaction orders the output, no atomic does.  No counterpart in the reference. */
+int slide_pairs_within(const double* xyz, const int32_t* label /* may be NULL */, int n, double radius, int64_t cap, int32_t* out_i,
+                       int32_t* out_j, double* out_dist, int64_t* n_pairs);
+/* The same search over the graph's device-resident landmark estimates of one class: the anchor is the point's xyz, the cube's
+ * translation or the cylinder's root.  sel_idx: the n_sel landmark keys to search among, or NULL: every landmark of the class, in the
+ * graph's order (n_sel is not read then).  sel_label (may be NULL): one label per selected landmark.  Pairs come back as landmark
+ * keys idx_a / idx_b with their distance, sorted by their positions in the selection.  A selected key the graph does not hold:
+ * SLIDE_MISSING for the call.  Refusals as slide_pairs_within (the message names landmark_pairs_within), and a class that is not a
+ * landmark class; then the graph is NULL. */
+int slide_graph_landmark_pairs_within(slide_graph_t* g, int cls, double radius, int n_sel, const uint64_t* sel_idx /* may be NULL */,
+                                      const int32_t* sel_label /* may be NULL */, int64_t cap, uint64_t* idx_a, uint64_t* idx_b, double* dist,
+                                      int64_t* n_pairs);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the

@@ -371,6 +371,72 @@ class SemanticFactorGraph {
     d2.resize(n);
     return d2;
   }
+  // Duplicate landmarks: are landmarks a and b of one class the same object mapped twice (slide_graph_landmark_pair_mahalanobis; no
+  // counterpart in the reference, whose association never compares two landmarks of the map)?  cls: SLIDE_CLS_ELLIPSOID (sigma: 3
+  // entries) or SLIDE_CLS_CYLINDER (7, tangent order [ray, root, radius]); cubes are refused.  d2[k] = r^T C^-1 r of pair k with
+  // r = (b - a) / sigma and C = I + diag(1 / sigma) (Saa + Sbb - Sab - Sba) diag(1 / sigma), chi-square with 3 / 7 degrees of freedom
+  // for one object — compare it with 11.345 / 18.475; no threshold is applied here.  Call it after solve(); the graph is only read.
+  // A pair with a fault of its own (status, when given: SLIDE_MISSING, SLIDE_ERR_INVALID for a == b, SLIDE_ERR_NOT_SPD) has d2 = 0:
+  // read the status before the value.  route, when given: 0 read off the selected inverse, 1 forward substitution.
+  struct LandmarkPair { size_t a = 0, b = 0; };
+  std::vector<double> landmarkPairMahalanobis(const int cls, const std::vector<LandmarkPair>& pairs, const std::vector<double>& sigma,
+                                              std::vector<int32_t>* status = nullptr, std::vector<int32_t>* route = nullptr) const {
+    const size_t n = pairs.size(), D = cls == SLIDE_CLS_CYLINDER ? 7 : 3;
+    if (sigma.size() != D) throw Error(SLIDE_ERR_INVALID, std::string("landmarkPairMahalanobis: sigma takes one entry per tangent coordinate"));
+    std::vector<double> d2(n + 1, 0.0);
+    std::vector<int32_t> c(n + 1, (int32_t)cls), st(n + 1, 0), rt(n + 1, 0);
+    std::vector<uint64_t> ia(n + 1, 0), ib(n + 1, 0);
+    for (size_t k = 0; k < n; ++k) { ia[k] = pairs[k].a; ib[k] = pairs[k].b; }
+    detail::check(slide_graph_landmark_pair_mahalanobis(g_, (int)n, c.data(), ia.data(), ib.data(), sigma.data(), sigma.data(), d2.data(), nullptr,
+                                                        nullptr, nullptr, rt.data(), st.data()),
+                  "landmarkPairMahalanobis");
+    if (status) status->assign(st.begin(), st.begin() + n);
+    if (route) route->assign(rt.begin(), rt.begin() + n);
+    d2.resize(n);
+    return d2;
+  }
+  // Marginals::jointMarginalCovariance of two landmarks of one class (slide_graph_get_landmark_pair_covariances): the 2 D x 2 D block
+  // [[Saa, Sab], [Sba, Sbb]] row-major, D = 3 / 9 / 7 for ellipsoids / cubes / cylinders, tangent order of the landmark covariances.
+  // Throws std::out_of_range for a landmark the graph does not hold, Error for one landmark named twice.
+  std::vector<double> jointLandmarkCovariance(const int cls, const size_t idxA, const size_t idxB) const {
+    const int D = cls == SLIDE_CLS_CYLINDER ? 7 : cls == SLIDE_CLS_CUBE ? 9 : 3;
+    std::array<double, 324> c{};
+    const int32_t cl = (int32_t)cls;
+    const uint64_t ia = idxA, ib = idxB;
+    int32_t st = SLIDE_OK;
+    detail::check(slide_graph_get_landmark_pair_covariances(g_, 1, &cl, &ia, &ib, c.data(), nullptr, &st), "jointLandmarkCovariance");
+    if (st == SLIDE_MISSING) throw std::out_of_range("jointLandmarkCovariance: landmark not in the graph");
+    if (st != SLIDE_OK) throw Error(st, std::string("jointLandmarkCovariance: both ends are the same landmark"));
+    std::vector<double> out((size_t)(4 * D * D));
+    for (int r = 0; r < 2 * D; ++r)
+      for (int q = 0; q < 2 * D; ++q) out[(size_t)(2 * D * r + q)] = c[(size_t)(18 * r + q)];
+    return out;
+  }
+  // The search and the test together: the pairs of landmarks of class cls whose anchors lie within radius
+  // (slide_graph_landmark_pairs_within over every landmark of the class) and that pass the test at the prob quantile of chi-square.
+  struct DuplicateLandmark { size_t a = 0, b = 0; double d2 = 0.0, dist = 0.0; };
+  std::vector<DuplicateLandmark> findDuplicateLandmarks(const int cls, const double radius, const std::vector<double>& sigma,
+                                                        const double prob = 0.99) const {
+    int64_t total = 0;
+    std::vector<uint64_t> ia(1), ib(1);
+    std::vector<double> dist(1);
+    int rc = slide_graph_landmark_pairs_within(g_, cls, radius, 0, nullptr, nullptr, 0, ia.data(), ib.data(), dist.data(), &total);
+    if (rc == SLIDE_ERR_CAPACITY) {      // (the first call counted)
+      ia.resize((size_t)total); ib.resize((size_t)total); dist.resize((size_t)total);
+      rc = slide_graph_landmark_pairs_within(g_, cls, radius, 0, nullptr, nullptr, total, ia.data(), ib.data(), dist.data(), &total);
+    }
+    detail::check(rc, "findDuplicateLandmarks");
+    std::vector<LandmarkPair> pairs((size_t)total);
+    for (size_t k = 0; k < pairs.size(); ++k) { pairs[k].a = (size_t)ia[k]; pairs[k].b = (size_t)ib[k]; }
+    std::vector<int32_t> st;
+    const std::vector<double> d2 = landmarkPairMahalanobis(cls, pairs, sigma, &st);
+    double q = 0.0;
+    detail::check(slide_chi2_quantile(prob, cls == SLIDE_CLS_CYLINDER ? 7 : 3, &q), "findDuplicateLandmarks");
+    std::vector<DuplicateLandmark> out;
+    for (size_t k = 0; k < pairs.size(); ++k)
+      if (st[k] == SLIDE_OK && d2[k] <= q) out.push_back(DuplicateLandmark{pairs[k].a, pairs[k].b, d2[k], dist[k]});
+    return out;
+  }
   // The joint compatibility of a key frame's matches, tested together (slide_graph_observation_joint_compatibility; no counterpart in
   // the reference): groups[g] is one hypothesis, its candidates tried in the given order.  A candidate is accepted iff it passes alone
   // (d2Single against the prob quantile of its own rows) and stacked on those accepted before it (d2Joint against the quantile of

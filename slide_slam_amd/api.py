@@ -50,6 +50,8 @@ EXPORTS = [
     "slide_chol_batch_get_pose_pair_covariances", "slide_chol_batch_closure_mahalanobis", "slide_chol_batch_observation_mahalanobis",
     "slide_chol_batch_set_observation_loss", "slide_chol_batch_get_observation_weights", "slide_chol_batch_profile_linearize",
     "slide_chol_batch_observation_joint_compatibility",
+    "slide_graph_landmark_pair_mahalanobis", "slide_graph_get_landmark_pair_covariances", "slide_pairs_within",
+    "slide_graph_landmark_pairs_within",
 ]
 
 
@@ -487,6 +489,79 @@ class SlideGraph:
         _check(self.L.slide_graph_observation_mahalanobis(self.h, C.c_int(n), _p(robot), _p(pidx), _p(cls), _p(lidx), _p(meas), _p(d2),
                                                           _p(dof), _p(Cm), _p(r), _p(status)))
         return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
+
+    @staticmethod
+    def _landmark_pair_arrays(cls, pairs):
+        rows = np.ascontiguousarray(pairs, dtype=np.uint64).reshape(-1, 2)
+        n = len(rows)
+        k = max(n, 1)
+        ia, ib = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+        ia[:n], ib[:n] = rows[:, 0], rows[:, 1]
+        return n, k, np.full(k, cls, np.int32), ia, ib
+
+    def landmark_pair_mahalanobis(self, cls, pairs, sigma):
+        """slide_graph_landmark_pair_mahalanobis: are landmarks a and b of class `cls` (CLS_ELLIPSOID or CLS_CYLINDER; cubes are
+        refused) one object mapped twice?  pairs: (idx_a, idx_b) rows; sigma: the model noise of the hypothesis in the class's tangent
+        order (3 or 7 entries, > 0, or one scalar for all).  Returns a dict: d2 (n) = r^T C^-1 r with r = (est_b - est_a) / sigma and
+        C = I + diag(1 / sigma) (Sig_aa + Sig_bb - Sig_ab - Sig_ba) diag(1 / sigma), chi-square with dof (n) = 3 / 7 degrees of freedom
+        for one object — compare it with chi2_quantile(0.99, dof), no threshold is applied here; status (SLIDE_MISSING, SLIDE_ERR_INVALID
+        for a == b, SLIDE_ERR_NOT_SPD; zeros then); route (0: read off the selected inverse, 1: forward substitution); C (n, 9, 9), zero
+        outside the dof x dof block, and r (n, 9).  Call it after a solve; the graph is only read."""
+        n, k, c, ia, ib = self._landmark_pair_arrays(cls, pairs)
+        D = 7 if cls == CLS_CYLINDER else 3
+        sg = np.ascontiguousarray(np.broadcast_to(_d(sigma).reshape(-1), (D,)) if np.size(sigma) == 1 else _d(sigma).reshape(-1))
+        if len(sg) != D:
+            raise SlideError(f"landmark_pair_mahalanobis: sigma takes {D} entries for this class, got {len(sg)}")
+        d2, dof, Cm, r = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9))
+        route, status = np.zeros(k, np.int32), np.zeros(k, np.int32)
+        _check(self.L.slide_graph_landmark_pair_mahalanobis(self.h, C.c_int(n), _p(c), _p(ia), _p(ib), _p(sg), _p(sg), _p(d2), _p(dof), _p(Cm),
+                                                            _p(r), _p(route), _p(status)))
+        return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "route": route[:n], "C": Cm[:n], "r": r[:n]}
+
+    def get_landmark_pair_covariances(self, cls, pairs):
+        """slide_graph_get_landmark_pair_covariances (Marginals::jointMarginalCovariance({L(a), L(b)})): pairs = (idx_a, idx_b) rows of
+        landmarks of class `cls`, any of the three.  Returns ((n, 2 d, 2 d) blocks [[Saa, Sab], [Sba, Sbb]], d = 7 / 9 / 3, in the
+        tangent order of get_landmark_covariances, (n,) int32 status, (n,) int32 route); a pair naming a landmark the graph does not
+        hold (SLIDE_MISSING) or one landmark twice (SLIDE_ERR_INVALID) has zeros and its code.  The graph is only read."""
+        n, k, c, ia, ib = self._landmark_pair_arrays(cls, pairs)
+        d = {CLS_CYLINDER: 7, CLS_CUBE: 9}.get(cls, 3)
+        out, route, status = np.zeros((k, 18, 18)), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        _check(self.L.slide_graph_get_landmark_pair_covariances(self.h, C.c_int(n), _p(c), _p(ia), _p(ib), _p(out), _p(route), _p(status)))
+        return out[:n, :2 * d, :2 * d].copy(), status[:n], route[:n]
+
+    def landmark_pairs_within(self, cls, radius, idx=None, labels=None):
+        """slide_graph_landmark_pairs_within: every pair of landmarks of class `cls` whose anchors (point xyz, cube translation,
+        cylinder root of the current estimate) lie within `radius`, searched on the device.  idx: the landmark keys to search among
+        (None: every landmark of the class, in the graph's order); labels: one per searched landmark, only equal labels pair.  Returns
+        (idx_a, idx_b, dist), sorted by the positions in the selection.  KeyError for a selected landmark the graph does not hold."""
+        sel = None if idx is None else np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        lab = None if labels is None else _i(labels).reshape(-1)
+        if sel is not None and lab is not None and len(lab) != len(sel):
+            raise SlideError("landmark_pairs_within: one label per selected landmark")
+        nsel = 0 if sel is None else len(sel)
+        total, cap = C.c_int64(0), 0
+        for _ in range(2):      # (the first call counts, the second has room)
+            ia, ib, dist = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1))
+            st = self.L.slide_graph_landmark_pairs_within(self.h, C.c_int(cls), C.c_double(radius), C.c_int(nsel), _p(sel) if sel is not None else None,
+                                                          _p(lab) if lab is not None else None, C.c_int64(cap), _p(ia), _p(ib), _p(dist),
+                                                          C.byref(total))
+            if st == SLIDE_MISSING:
+                raise KeyError(f"landmark of class {cls} not in the graph")
+            if st != -3:      # SLIDE_ERR_CAPACITY: now the total is known
+                _check(st)
+                break
+            cap = total.value
+        return ia[:total.value], ib[:total.value], dist[:total.value]
+
+    def duplicate_landmarks(self, cls, radius, sigma, prob=0.99, idx=None, labels=None):
+        """The landmarks of class `cls` (CLS_ELLIPSOID or CLS_CYLINDER) that are one object mapped twice: landmark_pairs_within
+        proposes the pairs within `radius`, landmark_pair_mahalanobis tests them under the model noise `sigma`, and the pairs with
+        status 0 and d2 <= chi2_quantile(prob, D) are kept.  Returns (idx_a, idx_b, d2, dist) of the kept pairs.  The graph is only
+        read; merging the pairs is the caller's."""
+        ia, ib, dist = self.landmark_pairs_within(cls, radius, idx, labels)
+        res = self.landmark_pair_mahalanobis(cls, np.stack([ia, ib], axis=1), sigma)
+        keep = (res["status"] == 0) & (res["d2"] <= chi2_quantile(prob, 7 if cls == CLS_CYLINDER else 3))
+        return ia[keep], ib[keep], res["d2"][keep], dist[keep]
 
     def observation_joint_compatibility(self, groups, prob=0.99):
         """slide_graph_observation_joint_compatibility: the joint compatibility of a key frame's landmark matches, tested together
@@ -1125,6 +1200,25 @@ def debug_chol_batch(systems, method=0, cu_share=100, assumed_cus=0, want_l32=Fa
 
 
 # ---- stand-alone association / place recognition ---------------------------------------------------------
+def pairs_within(xyz, radius, labels=None):
+    """slide_pairs_within: every pair i < j of the points xyz (n, 3) at most `radius` apart (and of one label, where labels are
+    given), found on the device; sorted by (i, j).  Returns (i, j, dist)."""
+    pts = _d(xyz).reshape(-1, 3)
+    lab = None if labels is None else _i(labels).reshape(-1)
+    if lab is not None and len(lab) != len(pts):
+        raise SlideError("pairs_within: one label per point")
+    total, cap = C.c_int64(0), 0
+    for _ in range(2):      # (the first call counts, the second has room)
+        oi, oj, dist = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1))
+        st = lib().slide_pairs_within(_p(pts), _p(lab) if lab is not None else None, C.c_int(len(pts)), C.c_double(radius), C.c_int64(cap),
+                                      _p(oi), _p(oj), _p(dist), C.byref(total))
+        if st != -3:      # SLIDE_ERR_CAPACITY: now the total is known
+            _check(st)
+            break
+        cap = total.value
+    return oi[:total.value], oj[:total.value], dist[:total.value]
+
+
 def submap_knn(cloud_xyz_f32, query_xyz, K):
     cloud = np.ascontiguousarray(cloud_xyz_f32, dtype=np.float32)
     n = cloud.shape[0]

@@ -254,6 +254,166 @@ void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, co
   if (n > 0) hipLaunchKernelGGL(k_lm_cov, dim3(n), dim3(64), 0, s, G, Sg, ld, lids, n, out, prow);
 }
 
+// ---- landmark pairs on the selected inverse (slide_graph_landmark_pair_mahalanobis / _get_landmark_pair_covariances, route 0) -------
+// With the landmarks eliminated H_ll is block diagonal, so the joint marginal of two landmarks a != b of one class (dimension D) is
+//     Sig_aa = Hinv_a + X(a, a),   Sig_bb = Hinv_b + X(b, b),   Sig_ab = X(a, b),
+//     X(u, v) = sum_{f in factors(u)} sum_{g in factors(v)} F_f^T Sigma(p_f, p_g) F_g,
+// F = E H_ll^-1 the factors' Schur records (ebuf) and Sigma the selected inverse: k_lm_cov's sum with the second factor list taken
+// from v.  The host sends a pair here only when every Sigma(p_f, p_g) it reads lies inside the tile profile.  One wavefront per pair.
+// X(u, v) (D x D, row-major, rows u's coordinates) into Xs; Qs: 54 doubles of LDS.  Every lane of the wavefront calls it.
+__device__ __forceinline__ void lm_pair_block(const GraphDev& G, const double* __restrict__ Sg, int ld, int u, int v, int D, double* Qs,
+                                              double* Xs) {
+  const int lane = threadIdx.x;
+  const int fu0 = G.lm_ptr[u], nfu = G.lm_ptr[u + 1] - fu0, fv0 = G.lm_ptr[v], nfv = G.lm_ptr[v + 1] - fv0;
+  double acc[2] = {0.0, 0.0};
+  const int a = lane / D, c = lane - (lane / D) * D;
+  for (int qf = 0; qf < nfu; ++qf) {
+    const int f = G.lm_fids[fu0 + qf];
+    const int rf = 6 * G.lf_pose[f];
+    if (lane < 6 * D) {
+      double s = 0.0;
+      for (int qg = 0; qg < nfv; ++qg) {
+        const int g = G.lm_fids[fv0 + qg];
+        const int rg = 6 * G.lf_pose[g];
+        const double* Fg = G.ebuf + G.lf_eoff[g] + 6 * D;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) s += sig_at(Sg, ld, rf + a, rg + b) * Fg[b * D + c];
+      }
+      Qs[lane] = s;
+    }
+    __syncthreads();
+    const double* Ff = G.ebuf + G.lf_eoff[f] + 6 * D;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = lane + 64 * h;
+      if (e < D * D) {
+        const int r = e / D, cc = e - r * D;
+        double s = 0.0;
+#pragma unroll
+        for (int aa = 0; aa < 6; ++aa) s += Ff[aa * D + r] * Qs[aa * D + cc];
+        acc[h] += s;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int e = lane + 64 * h;
+    if (e < D * D) Xs[e] = acc[h];
+  }
+  __syncthreads();
+}
+// The pair test: Sig_d = Sig_aa + Sig_bb - Sig_ab - Sig_ab^T, C = I + diag(1 / sigma) Sig_d diag(1 / sigma) from ONE triangle of the
+// sum, mirrored, so C is symmetric bit for bit; r = (est_b - est_a) / sigma in the class's tangent order (both classes retract
+// additively); then lane 0 factors C = G G^T in registers, solves G y = r and forms d2 = y^T y as k_obs_gate_finish does.  A pivot
+// that is not > 0: flag[k] = 1 and zeros.  out: OBS_GATE_OUT doubles per pair, that kernel's layout.
+template <int M>
+__global__ __launch_bounds__(64) void k_lm_pair_direct(GraphDev G, const double* __restrict__ Sg, int ld, const int2* __restrict__ pairs, int n,
+                                                       LmPairSigma sg, double* __restrict__ out, int* __restrict__ flag) {
+  __shared__ double Qs[54], Xaa[M * M], Xbb[M * M], Xab[M * M], Cs[M * M], rs[M];
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int la = pairs[k].x, lb = pairs[k].y;
+  lm_pair_block(G, Sg, ld, la, la, M, Qs, Xaa);
+  lm_pair_block(G, Sg, ld, lb, lb, M, Qs, Xbb);
+  lm_pair_block(G, Sg, ld, la, lb, M, Qs, Xab);
+  const double* Ha = G.lm_Hinv + 81 * (size_t)la;
+  const double* Hb = G.lm_Hinv + 81 * (size_t)lb;
+  if (lane < M * M) {
+    const int a = lane / M, b = lane - M * a, hi = a > b ? a : b, lo = a > b ? b : a;
+    const double saa = Ha[M * hi + lo] + Xaa[M * hi + lo], sbb = Hb[M * hi + lo] + Xbb[M * hi + lo];
+    const double sd = ((saa + sbb) - Xab[M * hi + lo]) - Xab[M * lo + hi];
+    Cs[lane] = (a == b ? 1.0 : 0.0) + sd / (sg.s[hi] * sg.s[lo]);
+  }
+  if (lane < M) {
+    const int c = lm_pair_coord(M, lane);
+    rs[lane] = (G.lm_est[15 * (size_t)lb + c] - G.lm_est[15 * (size_t)la + c]) / sg.s[lane];
+  }
+  __syncthreads();
+  double d2 = 0.0;
+  int bad = 0;
+  if (lane == 0) {
+    double Gm[M][M], y[M];
+    bool spd = true;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double d = Cs[(M + 1) * j];
+#pragma unroll
+      for (int q = 0; q < j; ++q) d -= Gm[j][q] * Gm[j][q];
+      if (!(d > 0.0)) spd = false;
+      const double g = sqrt(spd ? d : 1.0);
+      Gm[j][j] = g;
+#pragma unroll
+      for (int i = j + 1; i < M; ++i) {
+        double v = Cs[M * i + j];
+#pragma unroll
+        for (int q = 0; q < j; ++q) v -= Gm[i][q] * Gm[j][q];
+        Gm[i][j] = v / g;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double v = rs[i];
+#pragma unroll
+      for (int q = 0; q < i; ++q) v -= Gm[i][q] * y[q];
+      y[i] = v / Gm[i][i];
+      d2 += y[i] * y[i];
+    }
+    bad = spd ? 0 : 1;
+    flag[k] = bad;
+  }
+  d2 = __shfl(d2, 0);
+  bad = __shfl(bad, 0);
+  double* o = out + OBS_GATE_OUT * (size_t)k;
+  for (int e = lane; e < OBS_GATE_OUT; e += 64) {
+    double v = 0.0;
+    if (!bad) {
+      if (e == 0) v = d2;
+      else if (e < 82) {
+        const int a = (e - 1) / 9, b = (e - 1) - 9 * a;
+        if (a < M && b < M) v = Cs[M * a + b];
+      } else if (e - 82 < M) v = rs[e - 82];
+    }
+    o[e] = v;
+  }
+}
+void launch_lm_pair_direct(const GraphDev& G, const double* Sg, int ld, int D, const int2* pairs, int n, const LmPairSigma& sg, double* out,
+                           int* flag, hipStream_t s) {
+  if (n <= 0) return;
+  if (D == 3) hipLaunchKernelGGL(k_lm_pair_direct<3>, dim3(n), dim3(64), 0, s, G, Sg, ld, pairs, n, sg, out, flag);
+  else hipLaunchKernelGGL(k_lm_pair_direct<7>, dim3(n), dim3(64), 0, s, G, Sg, ld, pairs, n, sg, out, flag);
+}
+// The joint marginal itself: out[LM_PAIR_COV * k ..] = [[Sig_aa, Sig_ab], [Sig_ab^T, Sig_bb]], 2 D x 2 D row-major with leading
+// dimension 18, zero elsewhere.  The diagonal blocks are k_lm_cov's sums in k_lm_cov's order.  Any of the three classes.
+__global__ __launch_bounds__(64) void k_lm_pair_cov(GraphDev G, const double* __restrict__ Sg, int ld, const int2* __restrict__ pairs, int n,
+                                                    double* __restrict__ out) {
+  __shared__ double Qs[54], Xaa[81], Xbb[81], Xab[81];
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int la = pairs[k].x, lb = pairs[k].y;
+  const int D = lm_dim(G.lm_type[la]);
+  lm_pair_block(G, Sg, ld, la, la, D, Qs, Xaa);
+  lm_pair_block(G, Sg, ld, lb, lb, D, Qs, Xbb);
+  lm_pair_block(G, Sg, ld, la, lb, D, Qs, Xab);
+  const double* Ha = G.lm_Hinv + 81 * (size_t)la;
+  const double* Hb = G.lm_Hinv + 81 * (size_t)lb;
+  double* o = out + LM_PAIR_COV * (size_t)k;
+  for (int e = lane; e < LM_PAIR_COV; e += 64) {
+    const int r = e / 18, c = e - 18 * r;
+    double v = 0.0;
+    if (r < 2 * D && c < 2 * D) {
+      if (r < D && c < D) v = Ha[D * r + c] + Xaa[D * r + c];
+      else if (r >= D && c >= D) v = Hb[D * (r - D) + c - D] + Xbb[D * (r - D) + c - D];
+      else if (r < D) v = Xab[D * r + c - D];
+      else v = Xab[D * c + r - D];
+    }
+    o[e] = v;
+  }
+}
+void launch_lm_pair_cov(const GraphDev& G, const double* Sg, int ld, const int2* pairs, int n, double* out, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_lm_pair_cov, dim3(n), dim3(64), 0, s, G, Sg, ld, pairs, n, out);
+}
+
 // ---- many right-hand sides: U = S^-1 B (B: nrhs columns of nT = T * NB rows, column-major) --------------------------------------------
 // Forward, one launch per block column k: blockIdx.y = chunk of 16 columns; workgroup 0 solves the 64 x 16 block of L_kk and stores
 // x_k into X (tile row k), workgroup b > 0 applies tile (k + b, k) to its own rows of Y (in place).  Tile row k of Y is only read in

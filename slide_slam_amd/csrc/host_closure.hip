@@ -547,6 +547,75 @@ int slide_chol_batch_observation_joint_compatibility(slide_chol_batch_t* b, int 
                                                     d2_joint, dof_joint, status, group_d2, group_dof, group_count, group_status);
 }
 
+// The duplicate-landmark queries: the Mahalanobis test and the joint marginal of landmark pairs, and the fixed-radius search that
+// proposes the pairs.  The argument checks come first and need neither graph nor device; nothing is written on a refusal.
+static int lm_pair_check_list(const char* who, bool cov, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b, const double* sig3,
+                              const double* sig7, const void* out) {
+  auto bad = [who](const char* what) { return obs_gate_bad(what, who); };
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!cls || !idx_a || !idx_b || !out)) return bad("a needed pointer is NULL");
+  bool any3 = false, any7 = false;
+  for (int k = 0; k < n; ++k) {
+    if (cls[k] == SLIDE_CLS_ELLIPSOID) any3 = true;
+    else if (cls[k] == SLIDE_CLS_CYLINDER) any7 = true;
+    else if (cov && cls[k] == SLIDE_CLS_CUBE) continue;
+    else return bad(cov ? "a class that is not a landmark class"
+                        : "a class that is neither SLIDE_CLS_ELLIPSOID nor SLIDE_CLS_CYLINDER (a cube's tangent difference is ambiguous under its symmetries)");
+  }
+  if (cov) return SLIDE_OK;
+  if ((any3 && !sig3) || (any7 && !sig7)) return bad("a needed pointer is NULL");
+  for (int i = 0; any3 && i < 3; ++i)
+    if (!std::isfinite(sig3[i]) || !(sig3[i] > 0.0)) return bad("a sigma that is non-finite or <= 0");
+  for (int i = 0; any7 && i < 7; ++i)
+    if (!std::isfinite(sig7[i]) || !(sig7[i] > 0.0)) return bad("a sigma that is non-finite or <= 0");
+  return SLIDE_OK;
+}
+int slide_graph_landmark_pair_mahalanobis(slide_graph_t* g, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b,
+                                          const double* sigma_point3, const double* sigma_cylinder7, double* d2, int32_t* dof, double* C81,
+                                          double* r9, int32_t* route, int32_t* status) {
+  const char* who = "landmark_pair_mahalanobis";
+  const int rc = lm_pair_check_list(who, false, n, cls, idx_a, idx_b, sigma_point3, sigma_cylinder7, d2);
+  if (rc != SLIDE_OK) return rc;
+  if (!g) return obs_gate_bad("the graph is NULL", who);
+  LOCK(g);
+  return g->g.landmark_pairs(false, n, cls, idx_a, idx_b, sigma_point3, sigma_cylinder7, d2, dof, C81, r9, nullptr, route, status);
+}
+int slide_graph_get_landmark_pair_covariances(slide_graph_t* g, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b,
+                                              double* out324n, int32_t* route, int32_t* status) {
+  const char* who = "get_landmark_pair_covariances";
+  const int rc = lm_pair_check_list(who, true, n, cls, idx_a, idx_b, nullptr, nullptr, out324n);
+  if (rc != SLIDE_OK) return rc;
+  if (!g) return obs_gate_bad("the graph is NULL", who);
+  LOCK(g);
+  return g->g.landmark_pairs(true, n, cls, idx_a, idx_b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out324n, route, status);
+}
+static int pairs_within_check(const char* who, int n, double radius, int64_t cap, const void* o1, const void* o2, const void* o3, const void* n_pairs) {
+  if (n < 0) return obs_gate_bad("n < 0", who);
+  if (cap < 0) return obs_gate_bad("cap < 0", who);
+  if (!n_pairs || (cap > 0 && (!o1 || !o2 || !o3))) return obs_gate_bad("a needed pointer is NULL", who);
+  if (!std::isfinite(radius) || !(radius > 0.0)) return obs_gate_bad("a radius that is non-finite or <= 0", who);
+  return SLIDE_OK;
+}
+int slide_pairs_within(const double* xyz, const int32_t* label, int n, double radius, int64_t cap, int32_t* out_i, int32_t* out_j, double* out_dist,
+                       int64_t* n_pairs) {
+  const char* who = "pairs_within";
+  const int rc = pairs_within_check(who, n, radius, cap, out_i, out_j, out_dist, n_pairs);
+  if (rc != SLIDE_OK) return rc;
+  if (n > 0 && !xyz) return obs_gate_bad("a needed pointer is NULL", who);
+  if ((long long)n > (long long)INT32_MAX - 256) return obs_gate_bad("more than 2^31 - 257 points", who);
+  return pairs_within_host(xyz, label, n, radius, cap, out_i, out_j, out_dist, n_pairs);
+}
+int slide_graph_landmark_pairs_within(slide_graph_t* g, int cls, double radius, int n_sel, const uint64_t* sel_idx, const int32_t* sel_label,
+                                      int64_t cap, uint64_t* idx_a, uint64_t* idx_b, double* dist, int64_t* n_pairs) {
+  const char* who = "landmark_pairs_within";
+  if (cls != SLIDE_CLS_ELLIPSOID && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_CYLINDER) return obs_gate_bad("a class that is not a landmark class", who);
+  const int rc = pairs_within_check(who, sel_idx ? n_sel : 0, radius, cap, idx_a, idx_b, dist, n_pairs);
+  if (rc != SLIDE_OK) return rc;
+  if (!g) return obs_gate_bad("the graph is NULL", who);
+  LOCK(g);
+  return g->g.landmark_pairs_within(cls, radius, n_sel, sel_idx, sel_label, cap, idx_a, idx_b, dist, n_pairs);
+}
+
 // sloam::FindRelativeMeasurementMatch sloam.cpp:321-412 (host-side bookkeeping: a few dozen stamps per call)
 int slide_find_relative_meas_match(int n_robots, const int64_t* pk_sec, const int64_t* pk_nsec, const int32_t* offsets,
                                    const uint64_t* pose_counter, int host, int* n_pending_io, int64_t* m_sec, int64_t* m_nsec,

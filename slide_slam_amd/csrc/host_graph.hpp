@@ -504,6 +504,18 @@ class HostGraph {
   struct ObsCand { int st = SLIDE_OK, type = 0, p = -1, l = -1; double z[15] = {}, sg[9] = {}; };
   ObsCand obs_candidate(int robot, uint64_t pose_idx, int cls, uint64_t lm_idx, const double* meas17) const;
   int obs_walk_start(const int32_t* pid, const int32_t* lid, int n) const;
+  // Landmark PAIRS of one class each (host_marginals.hip has the text): the Mahalanobis test of "a and b are one object" (cov = false:
+  // sig3 / sig7 the model noise of points / cylinders; d2, dof, C81, r9 as the observation gate's) or the pair's joint marginal
+  // (cov = true: out324).  route[k]: 0 = read off the selected inverse, 1 = forward substitution; arguments checked by the C ABI
+  int landmark_pairs(bool cov, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b, const double* sig3, const double* sig7,
+                     double* d2, int32_t* dof, double* C81, double* r9, double* out324, int32_t* route, int32_t* status);
+  // what they resolve of a pair on the host: the landmarks' ids, the status word, the lowest observing pose and the route
+  struct LmPair { int st = SLIDE_OK, a = -1, b = -1, route = 0, lo = 0; };
+  LmPair lm_pair(int cls, uint64_t idx_a, uint64_t idx_b) const;
+  // every pair of the selected landmarks of a class whose anchors (point xyz, cube t, cylinder root of the current estimate) lie
+  // within radius, as landmark keys in the selection's order; sel_idx null: every landmark of the class in the graph's order
+  int landmark_pairs_within(int cls, double radius, int n_sel, const uint64_t* sel_idx, const int32_t* sel_label, int64_t cap, uint64_t* idx_a,
+                            uint64_t* idx_b, double* dist, int64_t* n_pairs);
   // what the three add calls store of their arguments (and the gate evaluates): z as br_z / cu_z / cy_z hold it, the cube's sigmas
   static void br_meas(const double* bearing, double range, double* z4);
   void cube_meas(const SE3& pose, const SE3& cube_world, const double* scale, double* z15, double* sigma9) const;
@@ -781,5 +793,10 @@ class HostGraph {
   int launch_phase(int phase, double* d_buf);      // hipGraph replay of enqueue_phase when nothing changed
   bool have_prev = false;
 };
+
+// slide_pairs_within (host_marginals.hip, pairs_kernels.hip): every pair i < j of n host points within radius, sorted by (i, j);
+// arguments checked by the C ABI
+int pairs_within_host(const double* xyz, const int32_t* label, int n, double radius, int64_t cap, int32_t* out_i, int32_t* out_j, double* out_dist,
+                      int64_t* n_pairs);
 
 }  // namespace sl

@@ -995,6 +995,236 @@ int HostGraph::observation_mahalanobis(int n, const int32_t* robot, const uint64
   return SLIDE_OK;
 }
 
+// ---- landmark pairs: are two landmarks of one class the same object? ----------------------------------------------------------------
+// What the pair queries resolve of a pair before the device is asked: the two landmarks' ids (SLIDE_MISSING for a landmark the graph
+// does not hold, or one without a factor; SLIDE_ERR_INVALID when a and b are one landmark), the lowest pose that observes either, and
+// the route, from the structure alone.  Route 0 needs every Sigma(p_f, p_g) between the observers of a and b inside the selected
+// inverse: with lo / hi the lowest and highest row of those poses, every block column of tile(lo) .. tile(hi) must reach tile(hi)
+// (prof[tile(lo)] >= tile(hi) says it all where the profile does not decrease; a dense profile always does).
+// SLIDE_LM_PAIR_SUBSTITUTE=1 (a measurement and test aid): route 1 for every pair.
+HostGraph::LmPair HostGraph::lm_pair(int cls, uint64_t idx_a, uint64_t idx_b) const {
+  LmPair p;
+  p.a = lm_lid(cls, idx_a);
+  p.b = lm_lid(cls, idx_b);
+  if (p.a < 0 || p.b < 0 || lm_fids[p.a].empty() || lm_fids[p.b].empty()) { p.st = SLIDE_MISSING; return p; }
+  if (p.a == p.b) { p.st = SLIDE_ERR_INVALID; return p; }
+  int lo = 1 << 30, hi = -1;
+  for (int l : {p.a, p.b})
+    for (int f : lm_fids[l]) { lo = std::min(lo, h_lf_pose[f]); hi = std::max(hi, h_lf_pose[f]); }
+  p.lo = lo;
+  const char* fs = std::getenv("SLIDE_LM_PAIR_SUBSTITUTE");
+  if (fs && fs[0] == '1') { p.route = 1; return p; }
+  if (h_prof.size() != (size_t)G.T) return p;
+  const int tl = (6 * lo) / NB, th = (6 * hi + 5) / NB;
+  for (int t = tl; t <= th && t < G.T; ++t)
+    if (h_prof[t] < th) { p.route = 1; break; }
+  return p;
+}
+// The two pair queries (cov_kernels.hip and obs_gate_kernels.hip have the invariants).  Pair k names the EXISTING landmarks
+// (cls[k], idx_a[k]) and (cls[k], idx_b[k]).  cov = false, the test: with d = est_b - est_a at the current estimate, r = d / sigma,
+// Sig_d = Sig_aa + Sig_bb - Sig_ab - Sig_ba at the last linearisation point, C = I + diag(1 / sigma) Sig_d diag(1 / sigma) and
+// d2 = r^T C^-1 r, chi-square with D degrees of freedom when a and b are one object up to the model noise sigma (sig3 for points,
+// sig7 for cylinders, tangent order); no threshold is applied.  cov = true: the pair's joint marginal, 2 D x 2 D with leading
+// dimension 18.  The pairs are grouped by class and route; results go back in the caller's order, and a pair's bits do not depend on
+// what else is in the list: route 0 is one wavefront per pair on the selected inverse (ensure_sigma only if some pair takes it),
+// route 1 sigma_forms with nk = D (2 D) columns per pair, the walk starting at the block column of the sweep's lowest observer.
+// status[k]: SLIDE_MISSING, SLIDE_ERR_INVALID (a == b), SLIDE_ERR_NOT_SPD (a pivot of C); zeros in its outputs then.  Whole-call
+// refusals as pose_covariances, nothing written.  Arguments checked by the caller.
+int HostGraph::landmark_pairs(bool cov, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b, const double* sig3,
+                              const double* sig7, double* d2, int32_t* dof, double* C81, double* r9, double* out324, int32_t* route,
+                              int32_t* status) {
+  const char* who = cov ? "get_landmark_pair_covariances" : "landmark_pair_mahalanobis";
+  int rc = marginal_state(who);
+  if (rc != SLIDE_OK) return rc;
+  struct Group { std::vector<int2> pr; std::vector<int> ids, lo; };
+  Group groups[3][2];      // [SLIDE_CLS_*][route]
+  bool any0 = false;
+  for (int k = 0; k < n; ++k) {
+    if (cov) {
+      for (int e = 0; e < LM_PAIR_COV; ++e) out324[LM_PAIR_COV * (size_t)k + e] = 0.0;
+    } else {
+      d2[k] = 0.0;
+      for (int e = 0; C81 && e < 81; ++e) C81[81 * (size_t)k + e] = 0.0;
+      for (int e = 0; r9 && e < 9; ++e) r9[9 * (size_t)k + e] = 0.0;
+      if (dof) dof[k] = landmark_dim(cls[k]);
+    }
+    const LmPair p = lm_pair(cls[k], idx_a[k], idx_b[k]);
+    if (status) status[k] = p.st;
+    if (route) route[k] = p.st == SLIDE_OK ? p.route : 0;
+    if (p.st != SLIDE_OK) continue;
+    Group& g = groups[cls[k]][p.route];
+    g.pr.push_back(make_int2(p.a, p.b)); g.ids.push_back(k); g.lo.push_back(p.lo);
+    any0 = any0 || p.route == 0;
+  }
+  if (any0 && (rc = ensure_sigma()) != SLIDE_OK) return rc;
+  hipStream_t s = stream;
+  for (int c = 0; c < 3; ++c)
+    for (int rt = 0; rt < 2; ++rt) {
+      const Group& g = groups[c][rt];
+      if (g.ids.empty()) continue;
+      const int m = (int)g.ids.size(), D = landmark_dim(c), nk = cov ? 2 * D : D;
+      const int max_nc = rt == 0 ? m : std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / nk);
+      const size_t per_out = cov ? LM_PAIR_COV : OBS_GATE_OUT;
+      LmPairSigma sg{};
+      for (int i = 0; i < D && !cov; ++i) sg.s[i] = (D == 3 ? sig3 : sig7)[i];
+      Scratch sc(s);
+      int2* d_pr = sc.alloc<int2>(m);
+      double* d_r = sc.alloc<double>(9 * (size_t)max_nc);
+      double* d_G0 = sc.alloc<double>(81 * (size_t)max_nc);
+      double* d_out = sc.alloc<double>(per_out * (size_t)max_nc);
+      int* d_flag = sc.alloc<int>(max_nc);
+      if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+      SL_HIP(sc.upload(d_pr, g.pr));
+      std::vector<double> h(per_out * (size_t)max_nc);
+      std::vector<int> hflag(max_nc, 0);
+      // the sweep's (route 1) or the group's (route 0) results, pairs k0 .. k0 + nc - 1 of the group, into the caller's arrays
+      auto read_back = [&](int k0, int nc) -> int {
+        SL_HIP(hipGetLastError());
+        SL_HIP(hipMemcpyAsync(h.data(), d_out, per_out * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (!cov) SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+        SL_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < nc; ++i) {
+          const size_t k = (size_t)g.ids[k0 + i];
+          const double* o = h.data() + per_out * (size_t)i;
+          if (cov) { std::copy(o, o + LM_PAIR_COV, out324 + LM_PAIR_COV * k); continue; }
+          if (hflag[i]) {
+            if (status) status[k] = SLIDE_ERR_NOT_SPD;
+            continue;
+          }
+          d2[k] = o[0];
+          if (C81) std::copy(o + 1, o + 82, C81 + 81 * k);
+          if (r9) std::copy(o + 82, o + 91, r9 + 9 * k);
+        }
+        return SLIDE_OK;
+      };
+      if (rt == 0) {
+        if (cov) launch_lm_pair_cov(G, d_sig.d, G.ld, d_pr, m, d_out, s);
+        else launch_lm_pair_direct(G, d_sig.d, G.ld, D, d_pr, m, sg, d_out, d_flag, s);
+        rc = read_back(0, m);
+      } else {
+        rc = sigma_forms(
+            who, m, nk,
+            [&](int k0, int nc, double* B, int nT) { launch_lm_pair_fill(G, D, cov, d_pr + k0, sg, nc, B, nT, d_r, d_G0, s); },
+            [&](int k0, int nc, const double* M) -> int {
+              if (cov) launch_lm_pair_cov_finish(G, D, d_pr + k0, M, nc, d_out, s);
+              else launch_obs_gate_finish(nk, M, d_G0, d_r, nc, d_out, d_flag, s);
+              return read_back(k0, nc);
+            },
+            [&](int k0, int nc) -> int {
+              const char* fw = std::getenv("SLIDE_OBS_GATE_FULL_WALK");
+              if (fw && fw[0] == '1') return 0;
+              int lo = 1 << 30;
+              for (int i = 0; i < nc; ++i) lo = std::min(lo, g.lo[k0 + i]);
+              return std::min((6 * lo) / NB, G.T - 1);
+            });
+      }
+      if (rc != SLIDE_OK) return rc;
+    }
+  return SLIDE_OK;
+}
+
+// ---- the fixed-radius pair search (pairs_kernels.hip) -----------------------------------------------------------------------------
+// Point q of n is the three doubles at d_pts + stride * (d_sel ? d_sel[q] : q), all on the device.  Launches: count, k_seg_scan, emit;
+// blocking read-backs: the total, then the pairs.  *n_pairs is always the total; above cap SLIDE_ERR_CAPACITY and the vectors stay
+// empty.
+static int pairs_within_dev(const char* who, hipStream_t s, const double* d_pts, int stride, const int* d_sel, const int32_t* d_label, int n,
+                            double radius, int64_t cap, std::vector<int32_t>& vi, std::vector<int32_t>& vj, std::vector<double>& vd,
+                            int64_t* n_pairs) {
+  *n_pairs = 0;
+  vi.clear(); vj.clear(); vd.clear();
+  if (n < 2) return SLIDE_OK;
+  Scratch sc(s);
+  int* d_cnt = sc.alloc<int>(n);
+  long long* d_off = sc.alloc<long long>(n);
+  int* d_seg = sc.alloc<int>(2);
+  long long* d_tot = sc.alloc<long long>(1);
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  const std::vector<int> seg{0, n};
+  SL_HIP(sc.upload(d_seg, seg));
+  launch_pairs_within(false, d_pts, stride, d_sel, d_label, n, radius, d_cnt, nullptr, nullptr, nullptr, nullptr, s);
+  launch_seg_scan64(d_cnt, d_seg, 1, d_off, d_tot, s);
+  long long tot = 0;
+  SL_HIP(hipMemcpyAsync(&tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  *n_pairs = tot;
+  if (tot > cap) { g_last_error = std::string(who) + ": more pairs than cap (n_pairs holds the total)"; return SLIDE_ERR_CAPACITY; }
+  if (tot == 0) return SLIDE_OK;
+  int32_t* d_i = sc.alloc<int32_t>((size_t)tot);
+  int32_t* d_j = sc.alloc<int32_t>((size_t)tot);
+  double* d_d = sc.alloc<double>((size_t)tot);
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  launch_pairs_within(true, d_pts, stride, d_sel, d_label, n, radius, nullptr, d_off, d_i, d_j, d_d, s);
+  vi.resize((size_t)tot); vj.resize((size_t)tot); vd.resize((size_t)tot);
+  SL_HIP(hipMemcpyAsync(vi.data(), d_i, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, s));
+  SL_HIP(hipMemcpyAsync(vj.data(), d_j, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, s));
+  SL_HIP(hipMemcpyAsync(vd.data(), d_d, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost, s));
+  SL_HIP(hipStreamSynchronize(s));
+  SL_HIP(hipGetLastError());
+  return SLIDE_OK;
+}
+// the search over n host points (xyz: 3 per point; label: one per point, or null); arguments checked by the caller
+int pairs_within_host(const double* xyz, const int32_t* label, int n, double radius, int64_t cap, int32_t* out_i, int32_t* out_j, double* out_dist,
+                      int64_t* n_pairs) {
+  *n_pairs = 0;
+  if (n < 2) return SLIDE_OK;
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  Scratch sc(nullptr);
+  double* d_pts = sc.alloc<double>(3 * (size_t)n);
+  int32_t* d_label = label ? sc.alloc<int32_t>(n) : nullptr;
+  if (!sc.ok()) { g_last_error = "pairs_within: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipMemcpyAsync(d_pts, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, nullptr));
+  if (label) SL_HIP(hipMemcpyAsync(d_label, label, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, nullptr));
+  std::vector<int32_t> vi, vj;
+  std::vector<double> vd;
+  const int rc = pairs_within_dev("pairs_within", nullptr, d_pts, 3, nullptr, d_label, n, radius, cap, vi, vj, vd, n_pairs);
+  if (rc != SLIDE_OK) return rc;
+  std::copy(vi.begin(), vi.end(), out_i);
+  std::copy(vj.begin(), vj.end(), out_j);
+  std::copy(vd.begin(), vd.end(), out_dist);
+  return SLIDE_OK;
+}
+// The same search over the device-resident estimate of the landmarks of one class: the anchor is the point's xyz, the cube's t or the
+// cylinder's root (lm_est, 15 doubles per landmark).  The selection: sel_idx (n_sel keys; one the graph does not hold: SLIDE_MISSING
+// for the call, nothing written) or, null, every landmark of the class the device holds, in the graph's order (n_sel is not read;
+// sel_label then has one entry per such landmark).  Pairs come back as keys, sorted by their positions in the selection.
+int HostGraph::landmark_pairs_within(int cls, double radius, int n_sel, const uint64_t* sel_idx, const int32_t* sel_label, int64_t cap,
+                                     uint64_t* idx_a, uint64_t* idx_b, double* dist, int64_t* n_pairs) {
+  std::vector<int> lids;
+  std::vector<uint64_t> keys;
+  if (sel_idx) {
+    for (int q = 0; q < n_sel; ++q) {
+      const int l = lm_lid(cls, sel_idx[q]);
+      if (l < 0) { g_last_error = "landmark_pairs_within: a selected landmark is not in the graph"; return SLIDE_MISSING; }
+      lids.push_back(l); keys.push_back(sel_idx[q]);
+    }
+  } else {
+    const uint64_t tag = lm_key(cls, 0) >> 56;
+    std::vector<std::pair<int, uint64_t>> all;
+    for (const auto& kv : key2lm)
+      if ((kv.first >> 56) == tag && (size_t)kv.second < up_L) all.emplace_back(kv.second, kv.first & ((1ull << 56) - 1ull));
+    std::sort(all.begin(), all.end());
+    for (const auto& e : all) { lids.push_back(e.first); keys.push_back(e.second); }
+  }
+  *n_pairs = 0;
+  const int n = (int)lids.size();
+  if (n < 2) return SLIDE_OK;
+  hipStream_t s = stream;
+  Scratch sc(s);
+  int* d_sel = sc.alloc<int>(n);
+  int32_t* d_label = sel_label ? sc.alloc<int32_t>(n) : nullptr;
+  if (!sc.ok()) { g_last_error = "landmark_pairs_within: out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_sel, lids));
+  if (sel_label) SL_HIP(hipMemcpyAsync(d_label, sel_label, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+  std::vector<int32_t> vi, vj;
+  std::vector<double> vd;
+  const int rc = pairs_within_dev("landmark_pairs_within", s, d_lm_est.d + (cls == SLIDE_CLS_CUBE ? 9 : 0), 15, d_sel, d_label, n, radius, cap, vi,
+                                  vj, vd, n_pairs);
+  if (rc != SLIDE_OK) return rc;
+  for (size_t k = 0; k < vi.size(); ++k) { idx_a[k] = keys[vi[k]]; idx_b[k] = keys[vj[k]]; dist[k] = vd[k]; }
+  return SLIDE_OK;
+}
+
 // The regularised incomplete gamma functions P(a, x) (*lower: by its series, x < a + 1) or Q(a, x) (by Lentz's continued fraction),
 // whichever converges fast at x, and the density x^(a-1) e^-x / Gamma(a) — the textbook pair.
 static double gamma_pq(double a, double x, bool* lower, double* dens) {

@@ -450,6 +450,30 @@ void launch_joint_obs_gate_lin(const GraphDev* Gs, const JointPoseTab* tab, int 
                                const double* sg9, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s);
 void launch_obs_gate_finish(int m, const double* M, const double* G0, const double* r9, int n, double* out, int* flag, hipStream_t s);
 
+// The Mahalanobis test and the joint marginal of landmark PAIRS of one class (dimension D): pairs[k] = {landmark a, landmark b}, a != b,
+// both with factors.  sg: the hypothesis' model noise in the class's tangent order.  Route 0 (cov_kernels.hip) reads the selected
+// inverse Sg and is complete in one launch: the host sends it only pairs whose observers all lie inside the tile profile.  Route 1
+// (obs_gate_kernels.hip) fills the pair's columns of B for the forward substitution of sigma_forms: nk = D difference columns
+// (cov = false; r9 and G0 as launch_obs_gate_lin leaves them, finished by launch_obs_gate_finish) or nk = 2 D unit columns (cov = true;
+// finished by launch_lm_pair_cov_finish from the pairs' nk x nk grams M).
+constexpr int LM_PAIR_COV = 324;      // per pair: the 2 D x 2 D joint marginal, row-major, leading dimension 18
+struct LmPairSigma { double s[9]; };
+// where coordinate i of a landmark's tangent sits in its 15 doubles of lm_est: point xyz; cylinder tangent [ray, root, radius] over
+// the value [root, ray, radius]
+__host__ __device__ __forceinline__ int lm_pair_coord(int D, int i) { return D == 7 ? (i < 3 ? i + 3 : (i < 6 ? i - 3 : 6)) : i; }
+void launch_lm_pair_direct(const GraphDev& G, const double* Sg, int ld, int D, const int2* pairs, int n, const LmPairSigma& sg, double* out,
+                           int* flag, hipStream_t s);
+void launch_lm_pair_cov(const GraphDev& G, const double* Sg, int ld, const int2* pairs, int n, double* out, hipStream_t s);
+void launch_lm_pair_fill(const GraphDev& G, int D, bool cov, const int2* pairs, const LmPairSigma& sg, int n, double* B, int nT, double* r9,
+                         double* G0, hipStream_t s);
+void launch_lm_pair_cov_finish(const GraphDev& G, int D, const int2* pairs, const double* M, int n, double* out, hipStream_t s);
+
+// Every pair i < j of n points with |x_i - x_j| <= radius (and label[i] == label[j] where labels are given), sorted by (i, j): the
+// count / k_seg_scan / emit idiom, one wavefront per row i, ballot compaction.  Point q is the three doubles at
+// pts + stride * (sel ? sel[q] : q); label is indexed by q.  count: cnt[i]; emit: row i writes from off[i] on.
+void launch_pairs_within(bool emit, const double* pts, int stride, const int* sel, const int32_t* label, int n, double radius, int* cnt,
+                         const long long* off, int32_t* out_i, int32_t* out_j, double* out_dist, hipStream_t s);
+
 // The joint-compatibility test of groups of candidate observations (obs_joint_kernels.hip has the invariant and the rule).  A sweep
 // holds whole groups; cand[k] = {type (FT_BR / FT_CUBE / FT_CYL; < 0: a skipped candidate), pose id, landmark id, first column of the
 // sweep's B}, in the caller's order, classes mixed; z15 / sg9 / r9 / G0 per entry of that table as above.  The fill is k_obs_gate_lin's

@@ -275,6 +275,87 @@ void launch_joint_obs_joint_lin(const GraphDev* Gs, const JointPoseTab* tab, con
   if (n > 0) hipLaunchKernelGGL(k_joint_obs_joint_lin, dim3(n), dim3(64), 0, s, Gs, tab, cand, ends, sep_row, z15, sg9, n, B, ld, r9, G0);
 }
 
+// The fill of a landmark PAIR (slide_graph_landmark_pair_mahalanobis / _get_landmark_pair_covariances, route 1), one wavefront per pair
+// of landmarks a != b of one class (dimension D), both private and eliminated.  The hypothesis "a and b are one object up to the noise
+// sigma" is the factor with Al = -I / sigma on a and +I / sigma on b and no pose block, so in the private-landmark branch's terms
+//     B  = - sum_{f in factors(a)} P_{p_f}^T F_f Al_a^T - sum_{f in factors(b)} P_{p_f}^T F_f Al_b^T
+//        = + F_f[.][j] / sigma_j at a's factors' poses, - F_f[.][j] / sigma_j at b's, in column j,
+//     G0 = (H_ll,a^-1 + H_ll,b^-1)[i][j] / (sigma_i sigma_j), one triangle computed and mirrored,
+//     r  = (est_b - est_a) / sigma in the class's tangent order,
+// and k_obs_gate_finish<D> forms C = I + G0 + W^T W and d2 as for an observation: the landmark-landmark cross block is never formed.
+// COV: 2 D unit columns instead — column j < D is coordinate j of a (- F_f[.][j] at a's factors' poses), column D + j coordinate j of
+// b — whose gram plus the two H_ll^-1 blocks is the pair's joint marginal (k_lm_pair_cov_finish); r9 and G0 are not touched.
+// Entry e = 6 j + a of the pair's columns (row a of a pose, column j) belongs to lane e mod 64 in every pass over the factors, a's in
+// the order of lm_fids and then b's: a pose met twice is an ordered read-modify-write, no atomics.  B is zero before the launch.
+template <bool COV>
+__global__ __launch_bounds__(64) void k_lm_pair_fill(GraphDev G, int D, const int2* __restrict__ pairs, LmPairSigma sg, int n,
+                                                     double* __restrict__ B, int nT, double* __restrict__ r9, double* __restrict__ G0) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int la = pairs[k].x, lb = pairs[k].y;
+  const int nk = COV ? 2 * D : D;
+  double* colB = B + (size_t)(nk * k) * nT;
+  for (int e = lane; e < 6 * nk; e += 64) {
+    const int jc = e / 6, a = e - 6 * jc;
+    double* cB = colB + (size_t)jc * nT;
+    for (int side = 0; side < 2; ++side) {
+      if (COV && side != (jc >= D ? 1 : 0)) continue;
+      const int l = side ? lb : la, c = COV && jc >= D ? jc - D : jc;
+      const double w = COV ? -1.0 : (side ? -1.0 : 1.0) / sg.s[c];
+      for (int qf = G.lm_ptr[l]; qf < G.lm_ptr[l + 1]; ++qf) {
+        const int f = G.lm_fids[qf];
+        const double* F = G.ebuf + G.lf_eoff[f] + 6 * D + a * D;
+        double* at = cB + 6 * (size_t)G.lf_pose[f] + a;
+        *at = *at + F[c] * w;
+      }
+    }
+  }
+  if (COV) return;
+  const double* Ha = G.lm_Hinv + 81 * (size_t)la;
+  const double* Hb = G.lm_Hinv + 81 * (size_t)lb;
+  if (lane < D * (D + 1) / 2) {
+    int i = 0;
+    while ((i + 1) * (i + 2) / 2 <= lane) ++i;
+    const int jc = lane - i * (i + 1) / 2;      // (i >= jc)
+    const double s = (Ha[D * i + jc] + Hb[D * i + jc]) / (sg.s[i] * sg.s[jc]);
+    G0[81 * (size_t)k + D * i + jc] = s;
+    G0[81 * (size_t)k + D * jc + i] = s;
+  }
+  if (lane < D) {
+    const int c = lm_pair_coord(D, lane);
+    r9[9 * (size_t)k + lane] = (G.lm_est[15 * (size_t)lb + c] - G.lm_est[15 * (size_t)la + c]) / sg.s[lane];
+  }
+}
+void launch_lm_pair_fill(const GraphDev& G, int D, bool cov, const int2* pairs, const LmPairSigma& sg, int n, double* B, int nT, double* r9,
+                         double* G0, hipStream_t s) {
+  if (n <= 0) return;
+  if (cov) hipLaunchKernelGGL(k_lm_pair_fill<true>, dim3(n), dim3(64), 0, s, G, D, pairs, sg, n, B, nT, r9, G0);
+  else hipLaunchKernelGGL(k_lm_pair_fill<false>, dim3(n), dim3(64), 0, s, G, D, pairs, sg, n, B, nT, r9, G0);
+}
+// out[LM_PAIR_COV k ..] = the pair's 2 D x 2 D gram (one triangle, mirrored) plus H_ll,a^-1 and H_ll,b^-1 on the diagonal blocks,
+// row-major with leading dimension 18, zero elsewhere.  One wavefront per pair.
+__global__ __launch_bounds__(64) void k_lm_pair_cov_finish(GraphDev G, int D, const int2* __restrict__ pairs, const double* __restrict__ Mg,
+                                                           int n, double* __restrict__ out) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int nk = 2 * D;
+  const double* M = Mg + (size_t)(nk * nk) * k;
+  for (int e = lane; e < LM_PAIR_COV; e += 64) {
+    const int r = e / 18, c = e - 18 * r;
+    double v = 0.0;
+    if (r < nk && c < nk) {
+      const int hi = r > c ? r : c, lo = r > c ? c : r;
+      v = M[nk * hi + lo];
+      if (hi < D) v += G.lm_Hinv[81 * (size_t)pairs[k].x + D * hi + lo];
+      else if (lo >= D) v += G.lm_Hinv[81 * (size_t)pairs[k].y + D * (hi - D) + lo - D];
+    }
+    out[LM_PAIR_COV * (size_t)k + e] = v;
+  }
+}
+void launch_lm_pair_cov_finish(const GraphDev& G, int D, const int2* pairs, const double* M, int n, double* out, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_lm_pair_cov_finish, dim3(n), dim3(64), 0, s, G, D, pairs, M, n, out);
+}
+
 // k_obs_gate_finish, one wavefront per candidate (four to a workgroup): C = (I + G0) + M, M the candidate's m x m gram W_k^T W_k at
 // m m k; entries (a, b) and (b, a) are one sum of the same operands, so C is symmetric bit for bit.  Lane 0 factors C = G G^T in
 // registers, solves G y = r and forms d2 = y^T y.  A pivot that is not > 0: flag[k] = 1 and zeros.  out: OBS_GATE_OUT doubles per
