@@ -378,6 +378,52 @@ int slide_chol_batch_observation_joint_compatibility(slide_chol_batch_t* b, int 
                                                      const uint64_t* lm_idx, const double* meas17, double prob, int32_t* accepted,
                                                      double* d2_single, double* d2_joint, int32_t* dof_joint, int32_t* status, double* group_d2,
                                                      int32_t* group_dof, int32_t* group_count, int32_t* group_status);
+/* slide_graph_landmark_pair_mahalanobis on the JOINT graph: are two landmarks — of one robot, or of TWO — one object?  Which landmarks
+ * two robots share is the separator of the exact joint pass, and a pair this test keeps across robots becomes a shared slot through
+ * slide_graph_set_shared / slide_graph_set_separator; the call itself merges nothing.  No counterpart in the reference, which merges
+ * the robots' maps on a Euclidean threshold.  A landmark is named as slide_chol_batch_observation_mahalanobis names one:
+ * (slot_a[k], cls[k], idx_a[k]) and (slot_b[k], cls[k], idx_b[k]), idx the landmark's index in the graph of its slot; a SHARED
+ * landmark may be named through any replica (it is read through its lowest one: either name gives the same bits).  Classes, the
+ * hypothesis, sigma_point3 / sigma_cylinder7, r, C, d2 and the outputs' layout are the single-graph call's; cubes are refused on the
+ * host as there.  K = L D L^T is the joint system of the last whole exact pass, D = -I on the lambda block, and
+ *     C = I + G0 + W^T D W,     L W = B,     d2 = r^T C^-1 r,     r = (est_b - est_a) / sigma.
+ * A PRIVATE landmark enters as on one graph, in joint rows: -+F_f[.][j] / sigma_j at its factors' poses in its OWN graph, and
+ * H_ll^-1 / (sigma_i sigma_j) into G0.  A SHARED landmark is a separator variable the pass does not eliminate: -+I / sigma on its
+ * separator coordinates (entered once, at its rows in the border of the lowest robot that holds it), nothing in G0, no factor sum.
+ * Served: private-private in one graph, private-private across graphs, private-shared, shared-shared.  The landmark block between two
+ * robots is the one the cached joint Sigma does not hold; every pair, also one of a single robot, takes the forward substitution
+ * (there is no direct route off the cached Sigma, and no route output).  SLIDE_INFO_GAIN_SWEEP_COLS / D pairs per sweep (128 points,
+ * 54 cylinders), every sweep one walk of the whole forward half; a pair's bits do not depend on the rest of the list.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing written, the message names chol_batch_landmark_pair_mahalanobis and the reason):
+ * those of slide_graph_landmark_pair_mahalanobis, made before the batch or the device is looked at (slot_a and slot_b are needed
+ * pointers; the batch is NULL), then those of slide_chol_batch_get_pose_covariances (no whole exact pass yet, a cut or profiled pass
+ * since, the graphs changed since, PCG passes, a job spread over processes).  Per pair, into status[k] with zeros in its outputs:
+ * SLIDE_MISSING for a slot the batch does not have, a landmark its graph does not hold, or a landmark with neither a factor nor a
+ * shared slot; SLIDE_ERR_INVALID for two names of one variable — one private landmark twice, or two replicas of one shared slot
+ * (told by their separator offset); SLIDE_ERR_NOT_SPD when a pivot of C is not positive.  n == 0 on a batch that would be served:
+ * SLIDE_OK.  Runs on the batch's stream outside any capture and writes nothing a pass reads; the cached joint Sigma is neither used
+ * nor touched. */
+int slide_chol_batch_landmark_pair_mahalanobis(slide_chol_batch_t* b, int n, const int32_t* cls, const int32_t* slot_a, const uint64_t* idx_a,
+                                               const int32_t* slot_b, const uint64_t* idx_b, const double* sigma_point3,
+                                               const double* sigma_cylinder7, double* d2, int32_t* dof /* may be NULL */,
+                                               double* C81 /* may be NULL */, double* r9 /* may be NULL */, int32_t* status /* may be NULL */);
+/* slide_graph_get_landmark_pair_covariances on the JOINT graph, the landmarks named as above: out324n[324 k ..] =
+ * [[Saa, Sab], [Sba, Sbb]], 2 D x 2 D (D = 3 / 9 / 7, all three classes) row-major with leading dimension 18, zero padded — Sab between
+ * landmarks of two robots included.  2 D unit columns per pair through the same forward half; the signed gram plus H_ll^-1 of each
+ * private side completes the block, a shared side adds nothing.  Refusals (the message names chol_batch_get_landmark_pair_covariances;
+ * any landmark class, no sigma) and the status words SLIDE_MISSING and SLIDE_ERR_INVALID are those of the test. */
+int slide_chol_batch_get_landmark_pair_covariances(slide_chol_batch_t* b, int n, const int32_t* cls, const int32_t* slot_a, const uint64_t* idx_a,
+                                                   const int32_t* slot_b, const uint64_t* idx_b, double* out324n,
+                                                   int32_t* status /* may be NULL */);
+/* slide_graph_landmark_pairs_within over the JOB's landmarks of one class: every member's private landmarks and each shared slot ONCE,
+ * through its lowest replica, in (slot, index) order; the anchors (point xyz, cube translation, cylinder root) are gathered from the
+ * members' device-resident estimates into one array and searched as slide_pairs_within searches.  cross_only != 0 drops the pairs
+ * whose two ends are private landmarks of the same member (a shared slot pairs with anything).  Pairs come back as (slot_a, idx_a,
+ * slot_b, idx_b, dist), sorted by their positions in that order; *n_pairs is always the total; above cap SLIDE_ERR_CAPACITY and nothing
+ * but n_pairs is written.  Refusals as slide_graph_landmark_pairs_within (the message names chol_batch_landmark_pairs_within; the
+ * batch is NULL), then those of slide_chol_batch_get_pose_covariances.  The batch is only read. */
+int slide_chol_batch_landmark_pairs_within(slide_chol_batch_t* b, int cls, double radius, int cross_only, int64_t cap, int32_t* slot_a,
+                                           uint64_t* idx_a, int32_t* slot_b, uint64_t* idx_b, double* dist, int64_t* n_pairs);
 /* ---- Robust loss on the exact joint multi-robot pass ------------------------------------------------------------------------------
  * No counterpart in the reference (its inter-robot factors are plain Between factors, graph.cpp:247-258); GTSAM users know it as
  * noiseModel::Robust on the closures of the joint graph.  slide_graph_set_robust_loss's rule, kinds, defaults and class_mask, as a

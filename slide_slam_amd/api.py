@@ -52,6 +52,7 @@ EXPORTS = [
     "slide_chol_batch_observation_joint_compatibility",
     "slide_graph_landmark_pair_mahalanobis", "slide_graph_get_landmark_pair_covariances", "slide_pairs_within",
     "slide_graph_landmark_pairs_within",
+    "slide_chol_batch_landmark_pair_mahalanobis", "slide_chol_batch_get_landmark_pair_covariances", "slide_chol_batch_landmark_pairs_within",
 ]
 
 
@@ -895,6 +896,74 @@ class CholBatch:
             _p(d2j), _p(dofj), _p(status), _p(gd2), _p(gdof), _p(gcnt), _p(gst)))
         return {"accepted": acc[:n].astype(bool), "d2_single": d2s[:n], "d2_joint": d2j[:n], "dof_joint": dofj[:n], "status": status[:n],
                 "group_d2": gd2[:ng], "group_dof": gdof[:ng], "group_count": gcnt[:ng], "group_status": gst[:ng], "group_ptr": ptr}
+
+    @staticmethod
+    def _landmark_pair_arrays(cls, pairs):
+        rows = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 4)
+        n = len(rows)
+        k = max(n, 1)
+        sa, sb, ia, ib = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+        sa[:n], ia[:n], sb[:n], ib[:n] = rows[:, 0], rows[:, 1].astype(np.uint64), rows[:, 2], rows[:, 3].astype(np.uint64)
+        return n, k, np.full(k, cls, np.int32), sa, ia, sb, ib
+
+    def landmark_pair_mahalanobis(self, cls, pairs, sigma):
+        """slide_chol_batch_landmark_pair_mahalanobis: SlideGraph.landmark_pair_mahalanobis on the JOINT graph — are two landmarks of
+        class `cls` (CLS_ELLIPSOID or CLS_CYLINDER; cubes are refused), of one robot or of two, one object?  pairs: rows
+        (slot_a, idx_a, slot_b, idx_b), idx the landmark's index in the graph of its slot; a shared landmark may be named through any
+        replica.  sigma: the hypothesis' model noise as there.  Returns that call's dict without `route` (every pair takes the
+        forward substitution): d2 to compare with chi2_quantile(0.99, dof) (no threshold is applied), dof, status (SLIDE_MISSING,
+        SLIDE_ERR_INVALID for two names of one variable, SLIDE_ERR_NOT_SPD; zeros then), C (n, 9, 9) and r (n, 9).  Call it after an
+        exact joint pass; the batch is only read."""
+        n, k, c, sa, ia, sb, ib = self._landmark_pair_arrays(cls, pairs)
+        D = 7 if cls == CLS_CYLINDER else 3
+        sg = np.ascontiguousarray(np.broadcast_to(_d(sigma).reshape(-1), (D,)) if np.size(sigma) == 1 else _d(sigma).reshape(-1))
+        if len(sg) != D:
+            raise SlideError(f"landmark_pair_mahalanobis: sigma takes {D} entries for this class, got {len(sg)}")
+        d2, dof, Cm, r, status = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9)), np.zeros(k, np.int32)
+        _check(self.L.slide_chol_batch_landmark_pair_mahalanobis(C.c_void_p(self.h), C.c_int(n), _p(c), _p(sa), _p(ia), _p(sb), _p(ib), _p(sg),
+                                                                 _p(sg), _p(d2), _p(dof), _p(Cm), _p(r), _p(status)))
+        return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
+
+    def get_landmark_pair_covariances(self, cls, pairs):
+        """slide_chol_batch_get_landmark_pair_covariances: the joint marginal [[Saa, Sab], [Sba, Sbb]] of landmark pairs of class
+        `cls` (any of the three) on the JOINT graph, the block between two robots' landmarks included.  pairs as
+        landmark_pair_mahalanobis takes them.  Returns ((n, 2 d, 2 d), (n,) int32 status); SLIDE_MISSING / SLIDE_ERR_INVALID pairs
+        have zeros and their code.  The batch is only read."""
+        n, k, c, sa, ia, sb, ib = self._landmark_pair_arrays(cls, pairs)
+        d = {CLS_CYLINDER: 7, CLS_CUBE: 9}.get(cls, 3)
+        out, status = np.zeros((k, 18, 18)), np.zeros(k, np.int32)
+        _check(self.L.slide_chol_batch_get_landmark_pair_covariances(C.c_void_p(self.h), C.c_int(n), _p(c), _p(sa), _p(ia), _p(sb), _p(ib),
+                                                                     _p(out), _p(status)))
+        return out[:n, :2 * d, :2 * d].copy(), status[:n]
+
+    def landmark_pairs_within(self, cls, radius, cross_only=False):
+        """slide_chol_batch_landmark_pairs_within: every pair of the JOB's landmarks of class `cls` — each member's private ones and
+        every shared slot once, through its lowest replica — whose anchors (point xyz, cube translation, cylinder root of the current
+        estimates) lie within `radius`.  cross_only: drop the pairs of two private landmarks of one member.  Returns
+        (slot_a, idx_a, slot_b, idx_b, dist), sorted by position in (slot, index) order."""
+        total, cap = C.c_int64(0), 0
+        for _ in range(2):      # (the first call counts, the second has room)
+            m = max(cap, 1)
+            sa, sb, ia, ib, dist = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m)
+            st = self.L.slide_chol_batch_landmark_pairs_within(C.c_void_p(self.h), C.c_int(cls), C.c_double(radius), C.c_int(1 if cross_only else 0),
+                                                               C.c_int64(cap), _p(sa), _p(ia), _p(sb), _p(ib), _p(dist), C.byref(total))
+            if st != -3:      # SLIDE_ERR_CAPACITY: now the total is known
+                _check(st)
+                break
+            cap = total.value
+        t = total.value
+        return sa[:t], ia[:t], sb[:t], ib[:t], dist[:t]
+
+    def duplicate_landmarks(self, cls, radius, sigma, prob=0.99, cross_only=False):
+        """The job's landmarks of class `cls` (CLS_ELLIPSOID or CLS_CYLINDER) that are one object mapped twice, by one robot or by two:
+        landmark_pairs_within proposes the pairs within `radius` (cross_only: not those of two private landmarks of one member),
+        landmark_pair_mahalanobis tests them under the model noise `sigma`, and the pairs with status 0 and
+        d2 <= chi2_quantile(prob, D) are kept.  Returns (slot_a, idx_a, slot_b, idx_b, d2, dist) of the kept pairs.  The batch is
+        only read; making a kept cross-robot pair a shared slot (set_shared / set_separator) is the caller's."""
+        sa, ia, sb, ib, dist = self.landmark_pairs_within(cls, radius, cross_only)
+        res = self.landmark_pair_mahalanobis(cls, np.stack([sa, ia.astype(np.int64), sb, ib.astype(np.int64)], axis=1), sigma)
+        keep = (res["status"] == 0) & (res["d2"] <= chi2_quantile(prob, 7 if cls == CLS_CYLINDER else 3))
+        return sa[keep], ia[keep], sb[keep], ib[keep], res["d2"][keep], dist[keep]
 
     def set_robust_loss(self, kind, param=0.0, closures=True, relative_meas=True):
         """slide_chol_batch_set_robust_loss: SlideGraph.set_robust_loss's loss (same kinds, names and defaults) on the exact joint

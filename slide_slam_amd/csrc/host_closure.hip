@@ -616,6 +616,38 @@ int slide_graph_landmark_pairs_within(slide_graph_t* g, int cls, double radius, 
   return g->g.landmark_pairs_within(cls, radius, n_sel, sel_idx, sel_label, cap, idx_a, idx_b, dist, n_pairs);
 }
 
+// The same three on the joint graph of a CholBatch: a landmark is (slot, cls, idx).  The argument checks are the single-graph calls'
+// (then the slots' pointers) and come before the batch or the device is looked at; nothing is written on a refusal.
+int slide_chol_batch_landmark_pair_mahalanobis(slide_chol_batch_t* b, int n, const int32_t* cls, const int32_t* slot_a, const uint64_t* idx_a,
+                                               const int32_t* slot_b, const uint64_t* idx_b, const double* sigma_point3,
+                                               const double* sigma_cylinder7, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status) {
+  const char* who = "chol_batch_landmark_pair_mahalanobis";
+  const int rc = lm_pair_check_list(who, false, n, cls, idx_a, idx_b, sigma_point3, sigma_cylinder7, d2);
+  if (rc != SLIDE_OK) return rc;
+  if (n > 0 && (!slot_a || !slot_b)) return obs_gate_bad("a needed pointer is NULL", who);
+  if (!b) return obs_gate_bad("the batch is NULL", who);
+  return b->b.joint_landmark_pairs(false, n, cls, slot_a, idx_a, slot_b, idx_b, sigma_point3, sigma_cylinder7, d2, dof, C81, r9, nullptr, status);
+}
+int slide_chol_batch_get_landmark_pair_covariances(slide_chol_batch_t* b, int n, const int32_t* cls, const int32_t* slot_a, const uint64_t* idx_a,
+                                                   const int32_t* slot_b, const uint64_t* idx_b, double* out324n, int32_t* status) {
+  const char* who = "chol_batch_get_landmark_pair_covariances";
+  const int rc = lm_pair_check_list(who, true, n, cls, idx_a, idx_b, nullptr, nullptr, out324n);
+  if (rc != SLIDE_OK) return rc;
+  if (n > 0 && (!slot_a || !slot_b)) return obs_gate_bad("a needed pointer is NULL", who);
+  if (!b) return obs_gate_bad("the batch is NULL", who);
+  return b->b.joint_landmark_pairs(true, n, cls, slot_a, idx_a, slot_b, idx_b, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out324n, status);
+}
+int slide_chol_batch_landmark_pairs_within(slide_chol_batch_t* b, int cls, double radius, int cross_only, int64_t cap, int32_t* slot_a,
+                                           uint64_t* idx_a, int32_t* slot_b, uint64_t* idx_b, double* dist, int64_t* n_pairs) {
+  const char* who = "chol_batch_landmark_pairs_within";
+  if (cls != SLIDE_CLS_ELLIPSOID && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_CYLINDER) return obs_gate_bad("a class that is not a landmark class", who);
+  const int rc = pairs_within_check(who, 0, radius, cap, idx_a, idx_b, dist, n_pairs);
+  if (rc != SLIDE_OK) return rc;
+  if (cap > 0 && (!slot_a || !slot_b)) return obs_gate_bad("a needed pointer is NULL", who);
+  if (!b) return obs_gate_bad("the batch is NULL", who);
+  return b->b.joint_landmark_pairs_within(cls, radius, cross_only != 0, cap, slot_a, idx_a, slot_b, idx_b, dist, n_pairs);
+}
+
 // sloam::FindRelativeMeasurementMatch sloam.cpp:321-412 (host-side bookkeeping: a few dozen stamps per call)
 int slide_find_relative_meas_match(int n_robots, const int64_t* pk_sec, const int64_t* pk_nsec, const int32_t* offsets,
                                    const uint64_t* pose_counter, int host, int* n_pending_io, int64_t* m_sec, int64_t* m_nsec,

@@ -274,6 +274,16 @@ class CholBatch {
                                             const int32_t* lm_slot, const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double prob,
                                             int32_t* accepted, double* d2_single, double* d2_joint, int32_t* dof_joint, int32_t* status,
                                             double* group_d2, int32_t* group_dof, int32_t* group_count, int32_t* group_status);
+  // landmark PAIRS on the JOINT graph (HostGraph::landmark_pairs with a landmark named (slot, cls, local idx), a shared one through
+  // any replica): the Mahalanobis test of "a and b are one object" (cov = false) or the pair's joint marginal, the landmark block
+  // between two robots included (cov = true: out324); every pair takes the forward substitution.  Arguments checked by the C ABI
+  int joint_landmark_pairs(bool cov, int n, const int32_t* cls, const int32_t* slot_a, const uint64_t* idx_a, const int32_t* slot_b,
+                           const uint64_t* idx_b, const double* sig3, const double* sig7, double* d2, int32_t* dof, double* C81, double* r9,
+                           double* out324, int32_t* status);
+  // every pair of the job's landmarks of a class (private ones of every member, each shared slot once) whose anchors lie within
+  // radius; cross_only: not the pairs of two private landmarks of one member
+  int joint_landmark_pairs_within(int cls, double radius, bool cross_only, int64_t cap, int32_t* slot_a, uint64_t* idx_a, int32_t* slot_b,
+                                  uint64_t* idx_b, double* dist, int64_t* n_pairs);
 
  private:
   int n;
@@ -451,6 +461,10 @@ class CholBatch {
   // row at which a shared landmark enters the walk (-1: private) and its separator offset, z and the sigmas
   struct JointObsCand { int st = SLIDE_OK, type = 0, sep_off = -1; int4 ends = {0, 0, 0, 0}; long long sep = -1; double z[15] = {}, sg[9] = {}; };
   JointObsCand joint_obs_candidate(JointGain& jg, int pose_slot, uint64_t pose_idx, int lm_slot, int cls, uint64_t lm_idx, const double* meas17) const;
+  // one landmark of the joint graph, named (slot, cls, local idx): its id in that slot's graph (-1: missing) and, for a shared one,
+  // its slot, its separator offset and the joint row at which it enters the walk (-1s: private)
+  struct JointLmEnd { int l = -1, sh = -1, sep_off = -1; long long sep = -1; };
+  JointLmEnd joint_lm_end(JointGain& jg, int slot, int cls, uint64_t lm_idx) const;
   int joint_robot(int slot) const;                 // robot id of the graph's own poses
   int joint_end(const JointGain& jg, int slot, uint64_t idx) const;      // one end of a pair or closure: its pose id in the graph of `slot`, or -1
   // the job's point landmarks: every graph's private ones (landmark ids), and of each shared slot that holds one, once, its offset in

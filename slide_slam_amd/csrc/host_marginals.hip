@@ -1126,10 +1126,10 @@ int HostGraph::landmark_pairs(bool cov, int n, const int32_t* cls, const uint64_
 // ---- the fixed-radius pair search (pairs_kernels.hip) -----------------------------------------------------------------------------
 // Point q of n is the three doubles at d_pts + stride * (d_sel ? d_sel[q] : q), all on the device.  Launches: count, k_seg_scan, emit;
 // blocking read-backs: the total, then the pairs.  *n_pairs is always the total; above cap SLIDE_ERR_CAPACITY and the vectors stay
-// empty.
+// empty.  neq: d_label holds group words and only pairs of DIFFERENT groups are kept (the sibling kernel; the joint graph's cross_only).
 static int pairs_within_dev(const char* who, hipStream_t s, const double* d_pts, int stride, const int* d_sel, const int32_t* d_label, int n,
                             double radius, int64_t cap, std::vector<int32_t>& vi, std::vector<int32_t>& vj, std::vector<double>& vd,
-                            int64_t* n_pairs) {
+                            int64_t* n_pairs, bool neq = false) {
   *n_pairs = 0;
   vi.clear(); vj.clear(); vd.clear();
   if (n < 2) return SLIDE_OK;
@@ -1141,7 +1141,8 @@ static int pairs_within_dev(const char* who, hipStream_t s, const double* d_pts,
   if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
   const std::vector<int> seg{0, n};
   SL_HIP(sc.upload(d_seg, seg));
-  launch_pairs_within(false, d_pts, stride, d_sel, d_label, n, radius, d_cnt, nullptr, nullptr, nullptr, nullptr, s);
+  if (neq) launch_pairs_within_neq(false, d_pts, stride, d_sel, d_label, n, radius, d_cnt, nullptr, nullptr, nullptr, nullptr, s);
+  else launch_pairs_within(false, d_pts, stride, d_sel, d_label, n, radius, d_cnt, nullptr, nullptr, nullptr, nullptr, s);
   launch_seg_scan64(d_cnt, d_seg, 1, d_off, d_tot, s);
   long long tot = 0;
   SL_HIP(hipMemcpyAsync(&tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, s));
@@ -1154,7 +1155,8 @@ static int pairs_within_dev(const char* who, hipStream_t s, const double* d_pts,
   int32_t* d_j = sc.alloc<int32_t>((size_t)tot);
   double* d_d = sc.alloc<double>((size_t)tot);
   if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
-  launch_pairs_within(true, d_pts, stride, d_sel, d_label, n, radius, nullptr, d_off, d_i, d_j, d_d, s);
+  if (neq) launch_pairs_within_neq(true, d_pts, stride, d_sel, d_label, n, radius, nullptr, d_off, d_i, d_j, d_d, s);
+  else launch_pairs_within(true, d_pts, stride, d_sel, d_label, n, radius, nullptr, d_off, d_i, d_j, d_d, s);
   vi.resize((size_t)tot); vj.resize((size_t)tot); vd.resize((size_t)tot);
   SL_HIP(hipMemcpyAsync(vi.data(), d_i, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, s));
   SL_HIP(hipMemcpyAsync(vj.data(), d_j, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, s));
@@ -2401,32 +2403,42 @@ static long long sep_entry_row(const std::vector<long long>& sep_first, int so, 
     if (sep_first[so + c] != sep_first[so] + c) return -1;      // (a landmark's coordinates are one run of its robot's border)
   return sep_first[so];
 }
+// One landmark of the joint graph as the joint queries name it, (slot, cls, local idx): its id l in the graph of `ls` (-1: a slot the
+// batch lacks, a landmark its graph does not hold, or one with neither a factor nor a shared slot) and, for a SHARED landmark, its
+// slot sh, its separator offset sep_off and the joint row sep at which a right-hand side on its coordinates enters the walk.
+CholBatch::JointLmEnd CholBatch::joint_lm_end(JointGain& jg, int ls, int cls, uint64_t lm_idx) const {
+  JointLmEnd e;
+  if (ls < 0 || ls >= n) return e;
+  const HostGraph* gl = graphs[ls];
+  int l = gl->lm_lid(cls, lm_idx);
+  if (l >= 0 && (size_t)l >= gl->up_L) l = -1;
+  if (l >= 0 && (size_t)l < gl->h_lm_bord.size() && gl->h_lm_bord[l] >= 0) {
+    int so = -1;
+    for (size_t q = 0; q < gl->h_sh_lid.size(); ++q)
+      if (gl->h_sh_lid[q] == l) { so = gl->h_sep_off[q]; e.sh = (int)q; break; }
+    if (so >= 0 && jg.sep_first.empty()) {      // per separator row: its joint row in the lowest robot that maps it (-1: none)
+      jg.sep_first.assign((size_t)jg.t.Tsep * NB + 1, -1);
+      for (int i = n - 1; i >= 0; --i)
+        for (int o = 0; o < jg.t.gn[i]; ++o)
+          if (jg.t.map[i][o] >= 0) jg.sep_first[jg.t.map[i][o]] = (long long)jg.off[1 + i] + (long long)jg.t.Tc[i] * NB + o;
+    }
+    e.sep = so >= 0 ? sep_entry_row(jg.sep_first, so, landmark_dim(cls)) : -1;
+    e.sep_off = e.sep >= 0 ? so : -1;
+    if (e.sep < 0) l = -1;
+  }
+  if (l >= 0 && e.sep < 0 && gl->lm_fids[l].empty()) l = -1;
+  e.l = l;
+  return e;
+}
 CholBatch::JointObsCand CholBatch::joint_obs_candidate(JointGain& jg, int ps, uint64_t pose_idx, int ls, int cls, uint64_t lm_idx,
                                                        const double* a) const {
   JointObsCand c;
   c.type = cls == SLIDE_CLS_ELLIPSOID ? FT_BR : cls == SLIDE_CLS_CUBE ? FT_CUBE : FT_CYL;
   const int p = joint_end(jg, ps, pose_idx);
-  int l = -1;
-  if (ls >= 0 && ls < n) {
-    const HostGraph* gl = graphs[ls];
-    l = gl->lm_lid(cls, lm_idx);
-    if (l >= 0 && (size_t)l >= gl->up_L) l = -1;
-    if (l >= 0 && (size_t)l < gl->h_lm_bord.size() && gl->h_lm_bord[l] >= 0) {
-      int so = -1;
-      for (size_t q = 0; q < gl->h_sh_lid.size(); ++q)
-        if (gl->h_sh_lid[q] == l) { so = gl->h_sep_off[q]; break; }
-      if (so >= 0 && jg.sep_first.empty()) {      // per separator row: its joint row in the lowest robot that maps it (-1: none)
-        jg.sep_first.assign((size_t)jg.t.Tsep * NB + 1, -1);
-        for (int i = n - 1; i >= 0; --i)
-          for (int o = 0; o < jg.t.gn[i]; ++o)
-            if (jg.t.map[i][o] >= 0) jg.sep_first[jg.t.map[i][o]] = (long long)jg.off[1 + i] + (long long)jg.t.Tc[i] * NB + o;
-      }
-      c.sep = so >= 0 ? sep_entry_row(jg.sep_first, so, landmark_dim(cls)) : -1;
-      c.sep_off = c.sep >= 0 ? so : -1;
-      if (c.sep < 0) l = -1;
-    }
-    if (l >= 0 && c.sep < 0 && gl->lm_fids[l].empty()) l = -1;
-  }
+  const JointLmEnd le = joint_lm_end(jg, ls, cls, lm_idx);
+  const int l = le.l;
+  c.sep = le.sep;
+  c.sep_off = le.sep_off;
   c.st = p < 0 || l < 0 ? SLIDE_MISSING : SLIDE_OK;
   if (c.st != SLIDE_OK) return c;
   c.ends = make_int4(ps, p, ls, l);
@@ -2595,5 +2607,167 @@ int CholBatch::joint_observation_joint_compatibility(int n_groups, const int32_t
         return SLIDE_OK;
       },
       [&](int si, const GainCandDev* d_cd, const double* M) -> int { return P.finish(who, si, d_cd, M, prob, s, o); });
+}
+
+// ---- landmark pairs on the joint graph: are two landmarks, of one robot or of two, the same object? ------------------------------------
+// HostGraph::landmark_pairs on the joint graph (obs_gate_kernels.hip's k_joint_lm_pair_fill has the invariant).  Pair k names the
+// EXISTING landmarks (slot_a, cls, idx_a) and (slot_b, cls, idx_b) as the joint observation gate names a landmark; a shared landmark
+// may be named through any replica and is read through its lowest one, so its two names give the same bits.  cov = false, the test:
+// r = (est_b - est_a) / sigma at the members' device-resident estimates, C = I + G0 + W^T D W with L W = B on the pass's
+// K = L D L^T, d2 = r^T C^-1 r by k_obs_gate_finish on the signed gram.  cov = true: 2 D unit columns per pair, whose signed gram
+// plus the private sides' H_ll^-1 is [[Saa, Sab], [Sba, Sbb]] — between two robots the one landmark block the cached joint Sigma does
+// not hold.  A PRIVATE side enters through its factors' poses in its own graph and its H_ll^-1; a SHARED side is a separator
+// variable: -+I / sigma on its separator coordinates at sep_entry_row's row, nothing in G0.  Grouped by class, nk = D (2 D) columns
+// per pair, 128 point / 54 cylinder pairs per sweep of the test; per sweep one fill launch, one walk of the whole forward half, the
+// gram, the finish, one read-back; a pair's bits do not depend on the list.  status[k] (or null): SLIDE_MISSING (joint_lm_end's),
+// SLIDE_ERR_INVALID (two names of one variable: one private landmark twice, or two replicas of one shared slot, told by their
+// separator offset), SLIDE_ERR_NOT_SPD; zeros then.  Whole-call refusals: joint_state's, nothing written.  No route off the cached
+// joint Sigma for pairs of one robot: every pair takes the substitution.  Nothing the pass reads is written; the cached joint Sigma is
+// neither used nor touched.  Arguments checked by the caller.
+int CholBatch::joint_landmark_pairs(bool cov, int n_q, const int32_t* cls, const int32_t* slot_a, const uint64_t* idx_a, const int32_t* slot_b,
+                                    const uint64_t* idx_b, const double* sig3, const double* sig7, double* d2, int32_t* dof, double* C81,
+                                    double* r9, double* out324, int32_t* status) {
+  const char* who = cov ? "chol_batch_get_landmark_pair_covariances" : "chol_batch_landmark_pair_mahalanobis";
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state(who, 0);
+  if (rc != SLIDE_OK) return rc;
+  JointGain jg;
+  jg.build(*this, 0);
+  struct Group { std::vector<int4> ends; std::vector<long long> sep; std::vector<int> ids; };
+  Group groups[3];      // [SLIDE_CLS_*]
+  for (int k = 0; k < n_q; ++k) {
+    if (cov) {
+      for (int e = 0; e < LM_PAIR_COV; ++e) out324[LM_PAIR_COV * (size_t)k + e] = 0.0;
+    } else {
+      d2[k] = 0.0;
+      for (int e = 0; C81 && e < 81; ++e) C81[81 * (size_t)k + e] = 0.0;
+      for (int e = 0; r9 && e < 9; ++e) r9[9 * (size_t)k + e] = 0.0;
+      if (dof) dof[k] = landmark_dim(cls[k]);
+    }
+    JointLmEnd ea = joint_lm_end(jg, slot_a[k], cls[k], idx_a[k]), eb = joint_lm_end(jg, slot_b[k], cls[k], idx_b[k]);
+    int ga = slot_a[k], gb = slot_b[k];
+    int st = ea.l < 0 || eb.l < 0 ? SLIDE_MISSING : SLIDE_OK;
+    if (st == SLIDE_OK) {
+      const bool sha = ea.sep >= 0, shb = eb.sep >= 0;
+      if (sha == shb && (sha ? ea.sep_off == eb.sep_off : (ga == gb && ea.l == eb.l))) st = SLIDE_ERR_INVALID;
+    }
+    if (status) status[k] = st;
+    if (st != SLIDE_OK) continue;
+    for (int side = 0; side < 2; ++side) {      // a shared landmark is read through its lowest replica
+      JointLmEnd& e = side ? eb : ea;
+      if (e.sep < 0) continue;
+      for (int i = 0; i < (side ? gb : ga); ++i)
+        if ((size_t)e.sh < graphs[i]->h_sh_lid.size() && graphs[i]->h_sh_lid[e.sh] >= 0 && (size_t)graphs[i]->h_sh_lid[e.sh] < graphs[i]->up_L) {
+          (side ? gb : ga) = i; e.l = graphs[i]->h_sh_lid[e.sh];
+          break;
+        }
+    }
+    Group& g = groups[cls[k]];
+    g.ends.push_back(make_int4(ga, ea.l, gb, eb.l)); g.sep.push_back(ea.sep); g.sep.push_back(eb.sep); g.ids.push_back(k);
+  }
+  hipStream_t s = master;
+  for (int c = 0; c < 3; ++c) {
+    const Group& g = groups[c];
+    if (g.ids.empty()) continue;
+    const int m = (int)g.ids.size(), D = landmark_dim(c), nk = cov ? 2 * D : D, max_nc = std::min(m, SLIDE_INFO_GAIN_SWEEP_COLS / nk);
+    const size_t per_out = cov ? LM_PAIR_COV : OBS_GATE_OUT;
+    LmPairSigma sg{};
+    for (int i = 0; i < D && !cov; ++i) sg.s[i] = (D == 3 ? sig3 : sig7)[i];
+    Scratch sc(s);
+    int4* d_ends = sc.alloc<int4>(m);
+    long long* d_sep = sc.alloc<long long>(2 * (size_t)m);
+    double* d_r = sc.alloc<double>(9 * (size_t)max_nc);
+    double* d_G0 = sc.alloc<double>(81 * (size_t)max_nc);
+    double* d_out = sc.alloc<double>(per_out * (size_t)max_nc);
+    int* d_flag = sc.alloc<int>(max_nc);
+    if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+    SL_HIP(sc.upload(d_ends, g.ends));
+    SL_HIP(sc.upload(d_sep, g.sep));
+    std::vector<double> h(per_out * (size_t)max_nc);
+    std::vector<int> hflag(max_nc, 0);
+    rc = joint_sigma_forms(
+        who, jg, m, nk,
+        [&](int k0, int nc, double* B, int ld) {
+          launch_joint_lm_pair_fill(d_Gs, jg.d_tab, D, cov, d_ends + k0, d_sep + 2 * (size_t)k0, sg, nc, B, (size_t)ld, d_r, d_G0, s);
+        },
+        [&](int k0, int nc, const double* M) -> int {
+          if (cov) launch_joint_lm_pair_cov_finish(d_Gs, D, d_ends + k0, d_sep + 2 * (size_t)k0, M, nc, d_out, s);
+          else launch_obs_gate_finish(nk, M, d_G0, d_r, nc, d_out, d_flag, s);
+          SL_HIP(hipGetLastError());
+          SL_HIP(hipMemcpyAsync(h.data(), d_out, per_out * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, s));
+          if (!cov) SL_HIP(hipMemcpyAsync(hflag.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+          SL_HIP(hipStreamSynchronize(s));
+          for (int i = 0; i < nc; ++i) {
+            const size_t k = (size_t)g.ids[k0 + i];
+            const double* o = h.data() + per_out * (size_t)i;
+            if (cov) { std::copy(o, o + LM_PAIR_COV, out324 + LM_PAIR_COV * k); continue; }
+            if (hflag[i]) {
+              if (status) status[k] = SLIDE_ERR_NOT_SPD;
+              continue;
+            }
+            d2[k] = o[0];
+            if (C81) std::copy(o + 1, o + 82, C81 + 81 * k);
+            if (r9) std::copy(o + 82, o + 91, r9 + 9 * k);
+          }
+          return SLIDE_OK;
+        });
+    if (rc != SLIDE_OK) return rc;
+  }
+  return SLIDE_OK;
+}
+// HostGraph::landmark_pairs_within over the job's landmarks of one class: every member's private ones and each shared slot ONCE,
+// through its lowest replica, in (slot, local index) order.  k_joint_lm_anchor_gather writes their anchors (point xyz, cube t,
+// cylinder root of the members' device-resident lm_est) and a group word each — the member's slot for a private landmark, n + the
+// shared slot for a shared one — into one contiguous array, on which the count / k_seg_scan / emit sequence runs; cross_only takes
+// the group-inequality sibling, which drops the pairs whose two ends are private landmarks of one member (a shared slot's word is
+// its own, so it pairs with anything).  Pairs come back as (slot, local index) of either end, sorted by position in that order.
+// *n_pairs is always the total; above cap SLIDE_ERR_CAPACITY, nothing else written.  joint_state's refusals first.
+int CholBatch::joint_landmark_pairs_within(int cls, double radius, bool cross_only, int64_t cap, int32_t* slot_a, uint64_t* idx_a, int32_t* slot_b,
+                                           uint64_t* idx_b, double* dist, int64_t* n_pairs) {
+  const char* who = "chol_batch_landmark_pairs_within";
+  std::lock_guard<std::mutex> pl(pass_mtx);
+  int rc = joint_state(who, 0);
+  if (rc != SLIDE_OK) return rc;
+  *n_pairs = 0;
+  std::vector<int4> ent;      // {member graph, landmark, group word, .}
+  std::vector<uint64_t> keys;
+  const uint64_t tag = HostGraph::lm_key(cls, 0) >> 56;
+  for (int i = 0; i < n; ++i) {
+    const HostGraph* g = graphs[i];
+    std::vector<std::pair<uint64_t, int>> all;
+    for (const auto& kv : g->key2lm)
+      if ((kv.first >> 56) == tag && (size_t)kv.second < g->up_L) all.emplace_back(kv.first & ((1ull << 56) - 1ull), kv.second);
+    std::sort(all.begin(), all.end());
+    for (const auto& e : all) {
+      int sh = -1;
+      for (size_t q = 0; q < g->h_sh_lid.size() && sh < 0; ++q)
+        if (g->h_sh_lid[q] == e.second) sh = (int)q;
+      bool lower = false;
+      for (int j = 0; j < i && sh >= 0 && !lower; ++j)
+        lower = (size_t)sh < graphs[j]->h_sh_lid.size() && graphs[j]->h_sh_lid[sh] >= 0 && (size_t)graphs[j]->h_sh_lid[sh] < graphs[j]->up_L;
+      if (lower) continue;
+      ent.push_back(make_int4(i, e.second, sh >= 0 ? n + sh : i, 0)); keys.push_back(e.first);
+    }
+  }
+  const int m = (int)ent.size();
+  if (m < 2) return SLIDE_OK;
+  hipStream_t s = master;
+  Scratch sc(s);
+  int4* d_ent = sc.alloc<int4>(m);
+  double* d_pts = sc.alloc<double>(3 * (size_t)m);
+  int32_t* d_group = sc.alloc<int32_t>(m);
+  if (!sc.ok()) { g_last_error = std::string(who) + ": out of device memory"; return SLIDE_ERR_HIP; }
+  SL_HIP(sc.upload(d_ent, ent));
+  launch_joint_lm_anchor_gather(d_Gs, d_ent, cls == SLIDE_CLS_CUBE ? 9 : 0, m, d_pts, d_group, s);
+  std::vector<int32_t> vi, vj;
+  std::vector<double> vd;
+  rc = pairs_within_dev(who, s, d_pts, 3, nullptr, cross_only ? d_group : nullptr, m, radius, cap, vi, vj, vd, n_pairs, cross_only);
+  if (rc != SLIDE_OK) return rc;
+  for (size_t k = 0; k < vi.size(); ++k) {
+    slot_a[k] = ent[vi[k]].x; idx_a[k] = keys[vi[k]];
+    slot_b[k] = ent[vj[k]].x; idx_b[k] = keys[vj[k]];
+    dist[k] = vd[k];
+  }
+  return SLIDE_OK;
 }
 }  // namespace sl

@@ -467,12 +467,26 @@ void launch_lm_pair_cov(const GraphDev& G, const double* Sg, int ld, const int2*
 void launch_lm_pair_fill(const GraphDev& G, int D, bool cov, const int2* pairs, const LmPairSigma& sg, int n, double* B, int nT, double* r9,
                          double* G0, hipStream_t s);
 void launch_lm_pair_cov_finish(const GraphDev& G, int D, const int2* pairs, const double* M, int n, double* out, hipStream_t s);
+// The same two on the JOINT graph of a CholBatch (obs_gate_kernels.hip): ends[k] = {graph of a, landmark a, graph of b, landmark b},
+// sep_row[2 k + side] = -1 for a private side, else the joint row at which that side's SHARED landmark enters the walk; Gs / tab as
+// launch_joint_obs_gate_lin takes them, B of ld rows per column.  The finish takes the pairs' SIGNED grams.
+void launch_joint_lm_pair_fill(const GraphDev* Gs, const JointPoseTab* tab, int D, bool cov, const int4* ends, const long long* sep_row,
+                               const LmPairSigma& sg, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s);
+void launch_joint_lm_pair_cov_finish(const GraphDev* Gs, int D, const int4* ends, const long long* sep_row, const double* M, int n, double* out,
+                                     hipStream_t s);
 
 // Every pair i < j of n points with |x_i - x_j| <= radius (and label[i] == label[j] where labels are given), sorted by (i, j): the
 // count / k_seg_scan / emit idiom, one wavefront per row i, ballot compaction.  Point q is the three doubles at
 // pts + stride * (sel ? sel[q] : q); label is indexed by q.  count: cnt[i]; emit: row i writes from off[i] on.
 void launch_pairs_within(bool emit, const double* pts, int stride, const int* sel, const int32_t* label, int n, double radius, int* cnt,
                          const long long* off, int32_t* out_i, int32_t* out_j, double* out_dist, hipStream_t s);
+// Its sibling for the joint graph of a CholBatch: group[q] (never null) is a group word per point and only pairs of DIFFERENT groups
+// are kept; the walk, the order and the bits of the distances are the search's above.  launch_joint_lm_anchor_gather writes that
+// search's input: ent[q] = {member graph, landmark, group word, .}; the landmark's anchor (the three doubles at coff of its lm_est)
+// into pts[3 q ..] and the group word into group[q].
+void launch_pairs_within_neq(bool emit, const double* pts, int stride, const int* sel, const int32_t* group, int n, double radius, int* cnt,
+                             const long long* off, int32_t* out_i, int32_t* out_j, double* out_dist, hipStream_t s);
+void launch_joint_lm_anchor_gather(const GraphDev* Gs, const int4* ent, int coff, int n, double* pts, int32_t* group, hipStream_t s);
 
 // The joint-compatibility test of groups of candidate observations (obs_joint_kernels.hip has the invariant and the rule).  A sweep
 // holds whole groups; cand[k] = {type (FT_BR / FT_CUBE / FT_CYL; < 0: a skipped candidate), pose id, landmark id, first column of the

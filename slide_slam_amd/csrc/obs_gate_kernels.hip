@@ -356,6 +356,107 @@ void launch_lm_pair_cov_finish(const GraphDev& G, int D, const int2* pairs, cons
   if (n > 0) hipLaunchKernelGGL(k_lm_pair_cov_finish, dim3(n), dim3(64), 0, s, G, D, pairs, M, n, out);
 }
 
+// The pair's fill on the JOINT graph of a CholBatch (slide_chol_batch_landmark_pair_mahalanobis / _get_landmark_pair_covariances), one
+// wavefront per pair.  Gs and tab as k_joint_obs_gate_lin takes them; ends[k] = {graph of a, landmark a, graph of b, landmark b};
+// sep_row[2 k], sep_row[2 k + 1]: per side -1 for a private landmark, else the joint row at which a SHARED landmark's first coordinate
+// enters the walk (sep_entry_row: its rows in the border of the lowest robot that holds it).  A private side enters as in
+// k_lm_pair_fill, its factors' poses being poses of ITS graph g at the joint rows tab->off[g] + tab->prow[g][lf_pose[f]]; a shared
+// side is a separator variable the pass does not eliminate: Al^T itself (-I / sigma for a, +I / sigma for b; COV: the unit column)
+// goes onto its separator coordinates, it has no factor sum and adds nothing to G0.  The host sends two different variables, so a
+// shared side's rows are met by no other write of the pair.  The ownership rule is k_lm_pair_fill's: entry 6 j + a of the pair's
+// columns belongs to one lane in every pass over the factors, a's in the order of lm_fids and then b's, so a pose met twice (both
+// landmarks private in one graph) is an ordered read-modify-write; no atomics.  B is zero before the launch.  r reads each side's
+// estimate in the graph that names it.
+template <bool COV>
+__global__ __launch_bounds__(64) void k_joint_lm_pair_fill(const GraphDev* __restrict__ Gs, const JointPoseTab* __restrict__ tab, int D,
+                                                           const int4* __restrict__ ends, const long long* __restrict__ sep_row, LmPairSigma sg,
+                                                           int n, double* __restrict__ B, size_t ld, double* __restrict__ r9,
+                                                           double* __restrict__ G0) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int4 e4 = ends[k];
+  const long long sa = sep_row[2 * (size_t)k], sb = sep_row[2 * (size_t)k + 1];
+  const int nk = COV ? 2 * D : D;
+  double* colB = B + (size_t)(nk * k) * ld;
+  for (int e = lane; e < 6 * nk; e += 64) {
+    const int jc = e / 6, a = e - 6 * jc;
+    double* cB = colB + (size_t)jc * ld;
+    for (int side = 0; side < 2; ++side) {
+      if (COV && side != (jc >= D ? 1 : 0)) continue;
+      if ((side ? sb : sa) >= 0) continue;
+      const int gi = side ? e4.z : e4.x, l = side ? e4.w : e4.y, c = COV && jc >= D ? jc - D : jc;
+      const GraphDev& G = Gs[gi];
+      const int* prow = tab->prow[gi];
+      const size_t off = (size_t)tab->off[gi];
+      const double w = COV ? -1.0 : (side ? -1.0 : 1.0) / sg.s[c];
+      for (int qf = G.lm_ptr[l]; qf < G.lm_ptr[l + 1]; ++qf) {
+        const int f = G.lm_fids[qf];
+        const double* F = G.ebuf + G.lf_eoff[f] + 6 * D + a * D;
+        double* at = cB + off + (size_t)prow[G.lf_pose[f]] + a;
+        *at = *at + F[c] * w;
+      }
+    }
+  }
+  if (lane < D) {
+    for (int side = 0; side < 2; ++side) {
+      const long long sr = side ? sb : sa;
+      if (sr < 0) continue;
+      double* at = colB + (size_t)(COV && side ? D + lane : lane) * ld + (size_t)sr + lane;
+      *at = *at + (COV ? 1.0 : (side ? 1.0 : -1.0) / sg.s[lane]);
+    }
+  }
+  if (COV) return;
+  const GraphDev& Ga = Gs[e4.x];
+  const GraphDev& Gb = Gs[e4.z];
+  if (lane < D * (D + 1) / 2) {
+    int i = 0;
+    while ((i + 1) * (i + 2) / 2 <= lane) ++i;
+    const int jc = lane - i * (i + 1) / 2;      // (i >= jc)
+    const double ha = sa < 0 ? Ga.lm_Hinv[81 * (size_t)e4.y + D * i + jc] : 0.0;
+    const double hb = sb < 0 ? Gb.lm_Hinv[81 * (size_t)e4.w + D * i + jc] : 0.0;
+    const double s = (ha + hb) / (sg.s[i] * sg.s[jc]);
+    G0[81 * (size_t)k + D * i + jc] = s;
+    G0[81 * (size_t)k + D * jc + i] = s;
+  }
+  if (lane < D) {
+    const int c = lm_pair_coord(D, lane);
+    r9[9 * (size_t)k + lane] = (Gb.lm_est[15 * (size_t)e4.w + c] - Ga.lm_est[15 * (size_t)e4.y + c]) / sg.s[lane];
+  }
+}
+void launch_joint_lm_pair_fill(const GraphDev* Gs, const JointPoseTab* tab, int D, bool cov, const int4* ends, const long long* sep_row,
+                               const LmPairSigma& sg, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s) {
+  if (n <= 0) return;
+  if (cov) hipLaunchKernelGGL(k_joint_lm_pair_fill<true>, dim3(n), dim3(64), 0, s, Gs, tab, D, ends, sep_row, sg, n, B, ld, r9, G0);
+  else hipLaunchKernelGGL(k_joint_lm_pair_fill<false>, dim3(n), dim3(64), 0, s, Gs, tab, D, ends, sep_row, sg, n, B, ld, r9, G0);
+}
+// k_lm_pair_cov_finish on the joint graph: the pair's 2 D x 2 D SIGNED gram (one triangle, mirrored) plus H_ll^-1 of each PRIVATE side
+// on its diagonal block, read in that side's graph; a shared side's block is the gram's alone.  One wavefront per pair.
+__global__ __launch_bounds__(64) void k_joint_lm_pair_cov_finish(const GraphDev* __restrict__ Gs, int D, const int4* __restrict__ ends,
+                                                                 const long long* __restrict__ sep_row, const double* __restrict__ Mg, int n,
+                                                                 double* __restrict__ out) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  if (k >= n) return;
+  const int nk = 2 * D;
+  const int4 e4 = ends[k];
+  const bool pa = sep_row[2 * (size_t)k] < 0, pb = sep_row[2 * (size_t)k + 1] < 0;
+  const double* M = Mg + (size_t)(nk * nk) * k;
+  for (int e = lane; e < LM_PAIR_COV; e += 64) {
+    const int r = e / 18, c = e - 18 * r;
+    double v = 0.0;
+    if (r < nk && c < nk) {
+      const int hi = r > c ? r : c, lo = r > c ? c : r;
+      v = M[nk * hi + lo];
+      if (hi < D) { if (pa) v += Gs[e4.x].lm_Hinv[81 * (size_t)e4.y + D * hi + lo]; }
+      else if (lo >= D) { if (pb) v += Gs[e4.z].lm_Hinv[81 * (size_t)e4.w + D * (hi - D) + lo - D]; }
+    }
+    out[LM_PAIR_COV * (size_t)k + e] = v;
+  }
+}
+void launch_joint_lm_pair_cov_finish(const GraphDev* Gs, int D, const int4* ends, const long long* sep_row, const double* M, int n, double* out,
+                                     hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_joint_lm_pair_cov_finish, dim3(n), dim3(64), 0, s, Gs, D, ends, sep_row, M, n, out);
+}
+
 // k_obs_gate_finish, one wavefront per candidate (four to a workgroup): C = (I + G0) + M, M the candidate's m x m gram W_k^T W_k at
 // m m k; entries (a, b) and (b, a) are one sum of the same operands, so C is symmetric bit for bit.  Lane 0 factors C = G G^T in
 // registers, solves G y = r and forms d2 = y^T y.  A pivot that is not > 0: flag[k] = 1 and zeros.  out: OBS_GATE_OUT doubles per

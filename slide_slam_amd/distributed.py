@@ -719,6 +719,30 @@ class PassDriver:
         self._joint_ok()
         return self.batch.observation_joint_compatibility(groups, prob)
 
+    def landmark_pair_mahalanobis(self, cls, pairs, sigma):
+        """Are two landmarks of class `cls`, of one robot or of two, one object?  pairs: rows (robot_a, idx_a, robot_b, idx_b), a robot
+        = its shard's slot, idx the landmark's index in that robot's graph: CholBatch.landmark_pair_mahalanobis (d2 to compare with
+        chi2_quantile(0.99, dof), dof, status, C, r)."""
+        self._joint_ok()
+        return self.batch.landmark_pair_mahalanobis(cls, pairs, sigma)
+
+    def get_landmark_pair_covariances(self, cls, pairs):
+        """((n, 2 d, 2 d), (n,) status) joint-graph marginals of landmark pairs, the block between two robots' landmarks included:
+        CholBatch.get_landmark_pair_covariances."""
+        self._joint_ok()
+        return self.batch.get_landmark_pair_covariances(cls, pairs)
+
+    def landmark_pairs_within(self, cls, radius, cross_only=False):
+        """(robot_a, idx_a, robot_b, idx_b, dist) of the job's landmarks of class `cls` within `radius` of each other, every shared
+        slot once: CholBatch.landmark_pairs_within."""
+        self._joint_ok()
+        return self.batch.landmark_pairs_within(cls, radius, cross_only)
+
+    def duplicate_landmarks(self, cls, radius, sigma, prob=0.99, cross_only=False):
+        """The search, then the test: the pairs kept at chi2_quantile(prob, D), CholBatch.duplicate_landmarks."""
+        self._joint_ok()
+        return self.batch.duplicate_landmarks(cls, radius, sigma, prob, cross_only)
+
     # ---- robust loss and observation loss on the exact joint pass (CholBatch.set_robust_loss / set_observation_loss, slide_gpu.h) ------
     def _loss_agreed(self, who, what, kind, param, *classes):
         """What both loss setters check first: the driver carries losses at all, and the ranks of a job set the same one."""
