@@ -1178,6 +1178,54 @@ int slide_pairs_within(const double* xyz, const int32_t* label /* may be NULL */
 int slide_graph_landmark_pairs_within(slide_graph_t* g, int cls, double radius, int n_sel, const uint64_t* sel_idx /* may be NULL */,
                                       const int32_t* sel_label /* may be NULL */, int64_t cap, uint64_t* idx_a, uint64_t* idx_b, double* dist,
                                       int64_t* n_pairs);
+/* Acting on what the two calls above find: MERGE duplicate landmarks into the graph — one variable, fused estimate.  No counterpart
+ * in the reference, whose graph is append-only; GTSAM users remove the dropped landmark's factors (removeFactorIndices) and add them
+ * again rekeyed, EKF-SLAM calls it landmark fusion.  Single-graph path only.
+ * Pair k says: landmark (cls[k], drop_idx[k]) and landmark (cls[k], keep_idx[k]) are one object; keep the latter.  All three classes.
+ * The call judges nothing: slide_graph_landmark_pair_mahalanobis is the caller's evidence, or the caller has its own.  Pairs are
+ * applied in list order, and a key dropped by an earlier pair — of this call or an earlier one — stands for its survivor at both
+ * ends, so chains and triangles such as (a, b), (a, c), (b, c) are legal.  After the call
+ *  - every factor of the dropped landmark is a factor of the survivor; its measurement, sigmas, robust-loss arrays and position in
+ *    insertion order are unchanged.  A pose that observed both now holds two factors on one landmark;
+ *  - the dropped key is an ALIAS of the survivor: slide_graph_get_landmark returns the survivor's estimate for it, a later
+ *    slide_graph_add_range_bearing / _add_cube / _add_cylinder (exists = 1) on it adds to the survivor, slide_graph_add_point_landmark
+ *    or exists = 0 on it is refused by the next update as "value inserted twice", and slide_graph_landmark_alias names the survivor.
+ *    A SlideBackend's association may thus go on matching the old id (its graph: slide_backend_graph);
+ *  - the dropped landmark's slot stays in the arrays as a tombstone without key and factors: slide_graph_stats' n_lm goes down by
+ *    one per drop, and slide_graph_marginal_traces, the information gain's landmark drop, slide_graph_landmark_pairs_within
+ *    (sel_idx NULL) and slide_graph_get_observation_weights (a moved factor's row names the survivor's own key) skip or resolve it.
+ * into[k]: the key pair k's landmarks resolve to when the call returns.  moved[k]: factors re-pointed by pair k; 0, with status
+ * SLIDE_OK, when both ends were one landmark already.  status[k]: SLIDE_MISSING when either key is absent (into[k] = 0),
+ * SLIDE_ERR_INVALID when keep_idx[k] == drop_idx[k], SLIDE_ERR_NOT_SPD when the fusion of its cluster failed (the structure is merged
+ * all the same and the survivor keeps its own estimate); such a pair changes nothing.  into, moved and status may be NULL.
+ * fuse = 0: the survivor keeps its estimate.  fuse = 1, for points and cylinders (both retract additively; a cube always keeps the
+ * survivor's estimate, a box pose being ambiguous under its symmetries): per survivor that gained members in this call, in the
+ * tangent order of slide_graph_get_landmark_covariances,
+ *     x = (sum_i H_i)^-1 sum_i H_i est_i,
+ * i over {survivor, members} in ascending internal id, H_i the member's own H_ll = sum Jl^T Jl at the LAST LINEARISATION, est_i its
+ * CURRENT ESTIMATE: the minimiser of the merged landmark's linearised cost with the poses held (each member's conditional cost is
+ * 1/2 (x - est_i)^T H_i (x - est_i), the back-substitution having left est_i at its conditional optimum).  A member without factors
+ * contributes nothing.  One wavefront per cluster (k_lm_merge_fuse), one launch per class, one read-back; the bits of x depend on the
+ * cluster alone, not on the list's order or on other clusters.
+ * A merge that moved something drops the resident factor: the marginal, gate and pair queries refuse until the next update, and that
+ * update — slide_graph_solve included — linearises every factor at the current estimate and factors from block column 0, the step
+ * slide_graph_gauss_newton(g, 1) takes (counted as a full update by slide_graph_get_incremental_stats).  Later updates are
+ * incremental again.
+ * Whole-call refusals (SLIDE_ERR_INVALID, nothing changed, the message names merge_landmarks and the reason), decided on the host:
+ * n < 0, a needed pointer NULL, a class that is not a landmark class, fuse neither 0 nor 1, the graph is NULL; a graph with shared
+ * slots, ghosts, separator offsets or a batch; with fuse = 1 whatever slide_graph_get_pose_covariances refuses (no resident
+ * single-graph factorisation, anything pending or merged since the last solve).  fuse = 0 has no such requirement and merges pending
+ * entries first, like every other call.  n == 0 on a graph that would be served: SLIDE_OK. */
+int slide_graph_merge_landmarks(slide_graph_t* g, int n, const int32_t* cls, const uint64_t* keep_idx, const uint64_t* drop_idx, int fuse,
+                                uint64_t* into /* may be NULL */, int32_t* moved /* may be NULL */, int32_t* status /* may be NULL */);
+/* The key landmark (cls, idx) resolves to: itself for a landmark never dropped, its survivor's own key after
+ * slide_graph_merge_landmarks dropped it.  SLIDE_MISSING (*into = idx) for a key the graph does not know; SLIDE_ERR_INVALID for a NULL
+ * pointer or a class that is not a landmark class.  Host only.  No counterpart in the reference. */
+int slide_graph_landmark_alias(slide_graph_t* g, int cls, uint64_t idx, uint64_t* into);
+/* Measurement aid: what the LAST slide_graph_merge_landmarks call of this graph spent, in ms — out4 = {host restructure, upload of the
+ * merged structure (wall, stream synchronised), the fusion with its table upload and read-back (wall), k_lm_merge_fuse's launches alone
+ * between two HIP events}; zeros for what did not run. */
+int slide_graph_merge_timing(slide_graph_t* g, double out4[4]);
 /* One LARGE problem (n >= 1024 associations; SURVEY A15 speaks of m ~ 1e4) runs on several co-resident workgroups — the rows of the
  * sparse product over the waves of up to 128 workgroups (cooperative launch), one grid barrier per gradient evaluation, everything
  * else repeated per workgroup so that the iterates equal the one-workgroup solve's bit for bit.  SLIDE_CLIPPER_WGS=<k> in the

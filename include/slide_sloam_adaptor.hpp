@@ -15,12 +15,14 @@
 #ifndef SLIDE_SLOAM_ADAPTOR_HPP_
 #define SLIDE_SLOAM_ADAPTOR_HPP_
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "slide_gpu.h"
@@ -436,6 +438,64 @@ class SemanticFactorGraph {
     for (size_t k = 0; k < pairs.size(); ++k)
       if (st[k] == SLIDE_OK && d2[k] <= q) out.push_back(DuplicateLandmark{pairs[k].a, pairs[k].b, d2[k], dist[k]});
     return out;
+  }
+  // Acting on the duplicates: merge landmark `drop` into landmark `keep` of one class (slide_graph_merge_landmarks; no counterpart in
+  // the reference — GTSAM users call removeFactorIndices and add the factors again rekeyed).  Every factor of drop becomes a factor
+  // of keep, the dropped key stays an alias of the survivor (getLandmark, later observations), pairs are applied in order and a
+  // dropped key stands for its survivor.  fuse (points and cylinders; call it after solve()): the survivor takes the
+  // information-weighted mean (sum H_i)^-1 sum H_i est_i of its cluster, else it keeps its estimate.  Per pair: into (the key it
+  // resolves to), moved (factors re-pointed), status (SLIDE_MISSING, SLIDE_ERR_INVALID for keep == drop, SLIDE_ERR_NOT_SPD for a
+  // failed fusion).  The next solve() is a full update; the marginal queries refuse until it ran.  A node would call it after a
+  // solve and before the next frame.
+  struct LandmarkMerge { size_t keep = 0, drop = 0; };
+  struct MergeResult { std::vector<size_t> into; std::vector<int32_t> moved, status; };
+  MergeResult mergeLandmarks(const int cls, const std::vector<LandmarkMerge>& pairs, const bool fuse = true) {
+    const size_t n = pairs.size();
+    std::vector<int32_t> c(n + 1, (int32_t)cls), mv(n + 1, 0), st(n + 1, 0);
+    std::vector<uint64_t> keep(n + 1, 0), drop(n + 1, 0), into(n + 1, 0);
+    for (size_t k = 0; k < n; ++k) { keep[k] = pairs[k].keep; drop[k] = pairs[k].drop; }
+    detail::check(slide_graph_merge_landmarks(g_, (int)n, c.data(), keep.data(), drop.data(), fuse ? 1 : 0, into.data(), mv.data(), st.data()),
+                  "mergeLandmarks");
+    MergeResult out;
+    out.into.assign(into.begin(), into.begin() + n);
+    out.moved.assign(mv.begin(), mv.begin() + n);
+    out.status.assign(st.begin(), st.begin() + n);
+    return out;
+  }
+  // The key a landmark resolves to: itself unless mergeLandmarks dropped it, then its survivor's.  Throws std::out_of_range for a
+  // landmark the graph does not know.
+  size_t landmarkAlias(const int cls, const size_t idx) const {
+    uint64_t into = 0;
+    const int rc = slide_graph_landmark_alias(g_, cls, idx, &into);
+    if (rc == SLIDE_MISSING) throw std::out_of_range("landmarkAlias: landmark not in the graph");
+    detail::check(rc, "landmarkAlias");
+    return (size_t)into;
+  }
+  // findDuplicateLandmarks, the clusters of its pairs (union-find; a cluster's smallest key survives), mergeLandmarks.  Returns the
+  // (keep, drop) rows it merged, sorted; result (when given): mergeLandmarks' per-row outputs.
+  std::vector<LandmarkMerge> mergeDuplicateLandmarks(const int cls, const double radius, const std::vector<double>& sigma, const double prob = 0.99,
+                                                     const bool fuse = true, MergeResult* result = nullptr) {
+    const std::vector<DuplicateLandmark> dup = findDuplicateLandmarks(cls, radius, sigma, prob);
+    std::vector<std::pair<size_t, size_t>> parent;      // (key, parent key), sorted by key
+    for (const DuplicateLandmark& d : dup) { parent.emplace_back(d.a, d.a); parent.emplace_back(d.b, d.b); }
+    std::sort(parent.begin(), parent.end());
+    parent.erase(std::unique(parent.begin(), parent.end()), parent.end());
+    auto slot = [&](size_t key) { return (size_t)(std::lower_bound(parent.begin(), parent.end(), std::make_pair(key, (size_t)0)) - parent.begin()); };
+    auto find = [&](size_t key) {
+      while (parent[slot(key)].second != key) key = parent[slot(key)].second;
+      return key;
+    };
+    for (const DuplicateLandmark& d : dup) {
+      const size_t ra = find(d.a), rb = find(d.b);
+      if (ra != rb) parent[slot(std::max(ra, rb))].second = std::min(ra, rb);
+    }
+    std::vector<LandmarkMerge> rows;
+    for (const auto& kv : parent)
+      if (find(kv.first) != kv.first) rows.push_back(LandmarkMerge{find(kv.first), kv.first});
+    std::sort(rows.begin(), rows.end(), [](const LandmarkMerge& x, const LandmarkMerge& y) { return x.keep != y.keep ? x.keep < y.keep : x.drop < y.drop; });
+    const MergeResult res = mergeLandmarks(cls, rows, fuse);
+    if (result) *result = res;
+    return rows;
   }
   // The joint compatibility of a key frame's matches, tested together (slide_graph_observation_joint_compatibility; no counterpart in
   // the reference): groups[g] is one hypothesis, its candidates tried in the given order.  A candidate is accepted iff it passes alone

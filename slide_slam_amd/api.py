@@ -51,7 +51,7 @@ EXPORTS = [
     "slide_chol_batch_set_observation_loss", "slide_chol_batch_get_observation_weights", "slide_chol_batch_profile_linearize",
     "slide_chol_batch_observation_joint_compatibility",
     "slide_graph_landmark_pair_mahalanobis", "slide_graph_get_landmark_pair_covariances", "slide_pairs_within",
-    "slide_graph_landmark_pairs_within",
+    "slide_graph_landmark_pairs_within", "slide_graph_merge_landmarks", "slide_graph_landmark_alias", "slide_graph_merge_timing",
     "slide_chol_batch_landmark_pair_mahalanobis", "slide_chol_batch_get_landmark_pair_covariances", "slide_chol_batch_landmark_pairs_within",
 ]
 
@@ -182,6 +182,37 @@ def chi2_quantile(prob: float, dof: int) -> float:
     q = C.c_double(0.0)
     _check(lib().slide_chi2_quantile(C.c_double(prob), C.c_int(dof), C.byref(q)))
     return q.value
+
+
+def merge_clusters(idx_a, idx_b):
+    """The clusters of the pairs (idx_a[k], idx_b[k]) — duplicate_landmarks' output — as the (keep, drop) rows merge_landmarks takes:
+    union-find over the pairs, one row (survivor, member) per member, the survivor being the cluster's smallest key.  Rows sorted by
+    (survivor, member): the result does not depend on the order, the orientation or the repetition of the pairs.  Pure Python."""
+    a = np.asarray(idx_a).reshape(-1)
+    b = np.asarray(idx_b).reshape(-1)
+    if len(a) != len(b):
+        raise SlideError("merge_clusters: idx_a and idx_b differ in length")
+    parent = {}
+
+    def find(x):
+        root = x
+        while parent[root] != root:
+            root = parent[root]
+        while parent[x] != root:
+            parent[x], x = root, parent[x]
+        return root
+
+    for x, y in zip(a.tolist(), b.tolist()):
+        x, y = int(x), int(y)
+        if x < 0 or y < 0:
+            raise SlideError("merge_clusters: a negative landmark index")
+        parent.setdefault(x, x)
+        parent.setdefault(y, y)
+        rx, ry = find(x), find(y)
+        if rx != ry:
+            parent[max(rx, ry)] = min(rx, ry)      # (the smaller root survives: a cluster's root is its smallest key)
+    rows = sorted((find(x), x) for x in parent if find(x) != x)
+    return np.array(rows, dtype=np.uint64).reshape(-1, 2)
 
 
 def device_check(device: int = -1) -> None:
@@ -558,11 +589,60 @@ class SlideGraph:
         """The landmarks of class `cls` (CLS_ELLIPSOID or CLS_CYLINDER) that are one object mapped twice: landmark_pairs_within
         proposes the pairs within `radius`, landmark_pair_mahalanobis tests them under the model noise `sigma`, and the pairs with
         status 0 and d2 <= chi2_quantile(prob, D) are kept.  Returns (idx_a, idx_b, d2, dist) of the kept pairs.  The graph is only
-        read; merging the pairs is the caller's."""
+        read; merging the pairs: `merge_landmarks` (merge_duplicates does both)."""
         ia, ib, dist = self.landmark_pairs_within(cls, radius, idx, labels)
         res = self.landmark_pair_mahalanobis(cls, np.stack([ia, ib], axis=1), sigma)
         keep = (res["status"] == 0) & (res["d2"] <= chi2_quantile(prob, 7 if cls == CLS_CYLINDER else 3))
         return ia[keep], ib[keep], res["d2"][keep], dist[keep]
+
+    def merge_landmarks(self, cls, pairs, fuse=True):
+        """slide_graph_merge_landmarks: pairs = (keep, drop) rows of landmarks of class `cls` that are one object mapped twice.  Every
+        factor of `drop` becomes a factor of `keep`, the dropped key stays as an alias of the survivor (get_landmark, later
+        observations), its slot as a tombstone no walk visits.  Pairs are applied in order and a dropped key stands for its survivor,
+        so chains and triangles are legal.  fuse (points and cylinders): the survivor takes (sum H_i)^-1 sum H_i est_i over its
+        cluster, H_i each member's own H_ll at the last linearisation — call it after a solve then; fuse=False keeps the survivor's
+        estimate and has no such requirement.  Returns a dict: into (the key each pair resolves to), moved (factors re-pointed by
+        the pair), status (SLIDE_MISSING, SLIDE_ERR_INVALID for keep == drop, SLIDE_ERR_NOT_SPD for a failed fusion).  The next
+        update is a full one at the current estimate; the marginal queries refuse until it ran."""
+        if cls not in (CLS_CYLINDER, CLS_CUBE, CLS_ELLIPSOID):
+            raise SlideError(f"merge_landmarks: {cls!r} is not a landmark class")
+        rows = np.asarray(pairs)
+        if rows.size and (rows.ndim != 2 or rows.shape[1] != 2):
+            raise SlideError("merge_landmarks: pairs are rows of (keep, drop)")
+        if rows.size and np.any(rows < 0):
+            raise SlideError("merge_landmarks: a negative landmark index")
+        n, k, c, keep, drop = self._landmark_pair_arrays(cls, rows)
+        into, moved, status = np.zeros(k, np.uint64), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        _check(self.L.slide_graph_merge_landmarks(self.h, C.c_int(n), _p(c), _p(keep), _p(drop), C.c_int(1 if fuse else 0), _p(into), _p(moved),
+                                                  _p(status)))
+        return {"into": into[:n], "moved": moved[:n], "status": status[:n]}
+
+    def landmark_alias(self, cls, idx):
+        """slide_graph_landmark_alias: the key landmark (cls, idx) resolves to — itself unless merge_landmarks dropped it, then its
+        survivor's.  KeyError for a landmark the graph does not know."""
+        out = C.c_uint64(0)
+        st = self.L.slide_graph_landmark_alias(self.h, C.c_int(cls), C.c_uint64(idx), C.byref(out))
+        if st == SLIDE_MISSING:
+            raise KeyError(f"landmark {idx} of class {cls} not in the graph")
+        _check(st)
+        return int(out.value)
+
+    def merge_timing(self):
+        """slide_graph_merge_timing: ms of the last merge_landmarks call — host restructure, upload, fusion with its read-back (wall),
+        k_lm_merge_fuse alone (HIP events)."""
+        out = np.zeros(4)
+        _check(self.L.slide_graph_merge_timing(self.h, _p(out)))
+        return {"host_ms": out[0], "upload_ms": out[1], "fuse_ms": out[2], "fuse_kernel_ms": out[3]}
+
+    def merge_duplicates(self, cls, radius, sigma, prob=0.99, idx=None, labels=None, fuse=True):
+        """duplicate_landmarks, then merge_clusters, then merge_landmarks: finds the landmarks of class `cls` mapped twice and merges
+        each cluster into its smallest key.  Returns (idx_a, idx_b, d2 of the kept pairs, merge_landmarks' dict with `pairs`, the
+        (survivor, member) rows it was given)."""
+        ia, ib, d2, _ = self.duplicate_landmarks(cls, radius, sigma, prob, idx, labels)
+        rows = merge_clusters(ia, ib)
+        res = self.merge_landmarks(cls, rows, fuse)
+        res["pairs"] = rows
+        return ia, ib, d2, res
 
     def observation_joint_compatibility(self, groups, prob=0.99):
         """slide_graph_observation_joint_compatibility: the joint compatibility of a key frame's landmark matches, tested together

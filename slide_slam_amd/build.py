@@ -32,6 +32,7 @@ SOURCES = [
     ("obs_gate_kernels.hip", ["-ffp-contract=off"]),    # (the observations' Mahalanobis gate: compared against chi-square quantiles)
     ("obs_joint_kernels.hip", ["-ffp-contract=off"]),   # (their joint-compatibility test: the same quantiles, decided on the device)
     ("pairs_kernels.hip", ["-ffp-contract=off"]),       # (the fixed-radius pair search: distances compared against a radius)
+    ("lm_merge_kernels.hip", []),                       # (landmark fusion: the solver kernels' arithmetic, k_landmark's sums)
     ("host_graph.hip", ["-ffp-contract=off"]),
     ("host_marginals.hip", ["-ffp-contract=off"]),     # (its Woodbury step runs on the host: same rounding as host_graph.hip)
     ("host_loss.hip", ["-ffp-contract=off"]),          # (the robust losses' host side, split off host_graph.hip the same way)

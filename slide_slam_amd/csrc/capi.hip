@@ -176,6 +176,25 @@ int slide_graph_get_landmark(slide_graph_t* g, int cls, uint64_t idx, double* ou
   LOCK(g);
   return g->g.get_landmark(cls, idx, out);
 }
+// landmark fusion (HostGraph::merge_landmarks): the argument checks come before the graph or the device is looked at
+int slide_graph_merge_landmarks(slide_graph_t* g, int n, const int32_t* cls, const uint64_t* keep_idx, const uint64_t* drop_idx, int fuse,
+                                uint64_t* into, int32_t* moved, int32_t* status) {
+  auto bad = [](const char* what) { g_last_error = std::string("merge_landmarks: ") + what; return SLIDE_ERR_INVALID; };
+  if (n < 0) return bad("n < 0");
+  if (n > 0 && (!cls || !keep_idx || !drop_idx)) return bad("a needed pointer is NULL");
+  for (int k = 0; k < n; ++k)
+    if (cls[k] != SLIDE_CLS_ELLIPSOID && cls[k] != SLIDE_CLS_CUBE && cls[k] != SLIDE_CLS_CYLINDER) return bad("a class that is not a landmark class");
+  if (fuse != 0 && fuse != 1) return bad("fuse is neither 0 nor 1");
+  if (!g) return bad("the graph is NULL");
+  LOCK(g);
+  return g->g.merge_landmarks(n, cls, keep_idx, drop_idx, fuse == 1, into, moved, status);
+}
+int slide_graph_landmark_alias(slide_graph_t* g, int cls, uint64_t idx, uint64_t* into) {
+  if (!g || !into || (cls != SLIDE_CLS_ELLIPSOID && cls != SLIDE_CLS_CUBE && cls != SLIDE_CLS_CYLINDER)) return SLIDE_ERR_INVALID;
+  LOCK(g);
+  return g->g.landmark_alias(cls, idx, into);
+}
+int slide_graph_merge_timing(slide_graph_t* g, double out4[4]) { if (!g || !out4) return SLIDE_ERR_INVALID; LOCK(g); g->g.merge_timing(out4); return SLIDE_OK; }
 int slide_graph_stats(slide_graph_t* g, int64_t out5[5]) { if (!g) return SLIDE_ERR_INVALID; LOCK(g); g->g.stats(out5); return SLIDE_OK; }
 int64_t slide_graph_rejected_count(slide_graph_t* g) { if (!g) return -1; LOCK(g); return g->g.rejected(); }
 int slide_graph_set_profiling(slide_graph_t* g, int on) {

@@ -351,6 +351,7 @@ int HostGraph::merge_pending() {
     } else {
       if (key2lm.count(v.key)) { refuse("value inserted twice:", v.key); continue; }
       key2lm[v.key] = (int)h_lm_type.size();
+      h_lm_key.push_back(v.key);
       h_lm_first.push_back(1 << 30);
       h_lm_type.push_back(v.type);
       h_lm_val.insert(h_lm_val.end(), v.val, v.val + 15);
@@ -2028,6 +2029,15 @@ int HostGraph::upload_new() {
   UP(d_lf_type, h_lf_type, up_lf, 1);
   UP(d_lf_pose, h_lf_pose, up_lf, 1);
   UP(d_lf_lm, h_lf_lm, up_lf, 1);
+  // (merge_landmarks re-pointed resident rows: UP sends the tail from up_lf on, so exactly those rows go, run by run)
+  for (size_t i = 0; i < lf_lm_moved.size();) {
+    size_t j = i + 1;
+    while (j < lf_lm_moved.size() && lf_lm_moved[j] == lf_lm_moved[j - 1] + 1) ++j;
+    const size_t f0 = (size_t)lf_lm_moved[i], f1 = std::min((size_t)lf_lm_moved[j - 1] + 1, up_lf);
+    if (f0 < f1 && d_lf_lm.upload(h_lf_lm.data() + f0, f0, f1 - f0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+    i = j;
+  }
+  lf_lm_moved.clear();
   UP(d_lf_slot, h_lf_slot, up_lf, 1);
   UP(d_lf_joff, h_lf_joff, up_lf, 1);
   UP(d_lf_eoff, h_lf_eoff, up_lf, 1);
@@ -2601,6 +2611,9 @@ int HostGraph::run_update(double relin_thr, int iterations) {
     bool keep = false;
     ~WfReset() { if (!keep) T = 0; }
   } wf_reset{wf_T};
+  // the first update after merge_landmarks: the kept linearisations of the moved factors were taken at the dropped landmark's value, so
+  // every variable folds its delta in and every factor is linearised at the current estimate — gauss_newton(1)'s step, whoever asks
+  if (relin_all_next) relin_thr = 0.0;
   G.relin_thr = relin_thr;
   note_linearisation();
   if (!status_clean) SL_HIP(hipMemsetAsync(d_status.d, 0, 8 * sizeof(int), s));      // (k_final_pack of the last update left them at zero otherwise)
@@ -2744,6 +2757,7 @@ int HostGraph::run_update(double relin_thr, int iterations) {
     pred_valid = (try_inc || wf_full_path);
   }
   factor_valid = true;
+  relin_all_next = false;
   ++fact_serial;
   fact_shape_now(fact_shape);
   fact_gen = S_gen;
@@ -3079,8 +3093,204 @@ int HostGraph::get_landmark(int cls, uint64_t idx, double* out) {
   SL_HIP(hipStreamSynchronize(stream));
   return SLIDE_OK;
 }
+// ---- landmark fusion: merging an object that was mapped twice (no counterpart in the reference) ----------------------------------
+// GTSAM users remove the dropped landmark's factors (removeFactorIndices) and add them again rekeyed; here pair k re-points every
+// factor of landmark (cls[k], drop_idx[k]) to landmark (cls[k], keep_idx[k]) in place: measurement, sigmas, weights, records and
+// position in insertion order stay.  Pairs are applied in list order and both keys are resolved through key2lm first, so a key
+// dropped earlier — in this call or another — stands for its survivor at either end.  The dropped key stays in key2lm as an alias of
+// the survivor; the dropped landmark's slot stays in every array as a tombstone (h_lm_key = 0, no factors: k_landmark writes
+// H_ll^-1 = 0 there, nothing of it enters the system).  into[k]: the key pair k's landmarks resolve to when the call returns;
+// moved[k]: factors re-pointed by pair k; status[k]: SLIDE_MISSING (a key the graph does not hold), SLIDE_ERR_INVALID (keep == drop),
+// SLIDE_ERR_NOT_SPD (fuse: the sum of the cluster's H_i has a pivot that is not positive; merged all the same, the survivor keeps its
+// own estimate).  fuse (points and cylinders; a cube keeps the survivor's estimate): per survivor that gained members in this call
+// k_lm_merge_fuse over {survivor, members}, launched while the device lists still describe every member on its own.
+int HostGraph::merge_landmarks(int n, const int32_t* cls, const uint64_t* keep_idx, const uint64_t* drop_idx, bool fuse, uint64_t* into,
+                               int32_t* moved, int32_t* status) {
+  const char* who = "merge_landmarks";
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  for (double& v : merge_ms) v = 0.0;
+  bool ghost_pending = false;
+  for (const PendFac& f : pend_facs) ghost_pending = ghost_pending || f.type == PF_GHOST;
+  if (batch || arrow_on() || up_gh > 0 || ghost_pending || !h_gh_pose.empty() || !h_gslot_pose.empty() || !h_sh_lid.empty() || !h_sep_off.empty()) {
+    g_last_error = std::string(who) + ": a graph with shared slots, ghosts, separator offsets or a batch is not served (single-graph path only)";
+    return SLIDE_ERR_INVALID;
+  }
+  if (fuse) {
+    // the members' H_i and estimates are those of the resident factorisation's linearisation: whatever marginal_state refuses
+    const int rc = marginal_state(who);
+    if (rc != SLIDE_OK) return rc;
+    if (!pend_vars.empty() || !pend_facs.empty() || topo_dirty) {
+      g_last_error = std::string(who) + ": the graph changed since the last solve (call solve first)";
+      return SLIDE_ERR_INVALID;
+    }
+  } else {
+    const int rc = merge_pending();
+    if (rc != SLIDE_OK) return rc;
+  }
+  const clk::time_point t_host = clk::now();
+  std::unordered_map<int, std::vector<int>> gained;      // survivor -> the landmarks this call dropped into it
+  std::vector<int> touched_poses, merged_into(std::max(n, 0), -1);
+  int lo_lm = 1 << 30;
+  for (int k = 0; k < n; ++k) {
+    if (into) into[k] = 0;
+    if (moved) moved[k] = 0;
+    if (status) status[k] = SLIDE_OK;
+    const auto a = key2lm.find(lm_key(cls[k], keep_idx[k])), b = key2lm.find(lm_key(cls[k], drop_idx[k]));
+    if (a == key2lm.end() || b == key2lm.end()) { if (status) status[k] = SLIDE_MISSING; continue; }
+    if (keep_idx[k] == drop_idx[k]) { if (status) status[k] = SLIDE_ERR_INVALID; continue; }
+    const int ka = a->second, kb = b->second;
+    if (ka == kb) continue;      // (one landmark already: nothing moves)
+    merged_into[k] = ka;
+    if (moved) moved[k] = (int32_t)lm_fids[kb].size();
+    // the factors: lf_lm, the survivor's list (ascending factor id), the observers' lists (re-sorted below)
+    for (int f : lm_fids[kb]) {
+      h_lf_lm[f] = ka;
+      if ((size_t)f < up_lf) lf_lm_moved.push_back(f);
+      touched_poses.push_back(h_lf_pose[f]);
+    }
+    std::vector<int> both(lm_fids[ka].size() + lm_fids[kb].size());
+    std::merge(lm_fids[ka].begin(), lm_fids[ka].end(), lm_fids[kb].begin(), lm_fids[kb].end(), both.begin());
+    lm_fids[ka].swap(both);
+    lm_fids[kb].clear();
+    // first / last observer: min / max of the two; the tombstone has none
+    dirty_min_pose = std::min(dirty_min_pose, std::min(h_lm_first[ka], h_lm_first[kb]));
+    h_lm_first[ka] = std::min(h_lm_first[ka], h_lm_first[kb]);
+    h_lm_last[ka] = std::max(h_lm_last[ka], h_lm_last[kb]);
+    h_lm_first[kb] = 1 << 30;
+    h_lm_last[kb] = -1;
+    // the keys: the dropped landmark's own key and every alias it carried now resolve to the survivor
+    std::vector<uint64_t>& al = lm_aliases[ka];
+    al.push_back(h_lm_key[kb]);
+    key2lm[h_lm_key[kb]] = ka;
+    const auto carried = lm_aliases.find(kb);
+    if (carried != lm_aliases.end()) {
+      for (uint64_t key : carried->second) { key2lm[key] = ka; lm_aliases[ka].push_back(key); }
+      lm_aliases.erase(kb);
+    }
+    h_lm_key[kb] = 0;
+    ++n_tomb;
+    std::vector<int>& ga = gained[ka];
+    ga.push_back(kb);
+    const auto gb = gained.find(kb);
+    if (gb != gained.end()) {
+      std::vector<int> mv = gb->second;
+      gained.erase(kb);
+      std::vector<int>& ga2 = gained[ka];
+      ga2.insert(ga2.end(), mv.begin(), mv.end());
+    }
+    lo_lm = std::min(lo_lm, std::min(ka, kb));
+  }
+  // (the key a pair resolves to when the call returns: a later pair may have dropped an earlier pair's survivor)
+  for (int k = 0; k < n && into; ++k) {
+    const auto a = key2lm.find(lm_key(cls[k], keep_idx[k]));
+    if (a != key2lm.end() && (!status || status[k] != SLIDE_MISSING)) into[k] = h_lm_key[a->second] & ((1ull << 56) - 1ull);
+  }
+  if (gained.empty()) { merge_ms[0] = ms_since(t_host); return SLIDE_OK; }
+  // the observers' lists back in (landmark id, factor id) order, as the Schur kernel merges them
+  std::sort(touched_poses.begin(), touched_poses.end());
+  touched_poses.erase(std::unique(touched_poses.begin(), touched_poses.end()), touched_poses.end());
+  for (int p : touched_poses)
+    std::sort(pose_fids[p].begin(), pose_fids[p].end(), [&](int x, int y) { return h_lf_lm[x] != h_lf_lm[y] ? h_lf_lm[x] < h_lf_lm[y] : x < y; });
+  // the profile's input: every observer of a survivor couples to its new last observer.  Reach only grows, so the profile only grows
+  for (const auto& kv : gained) {
+    const int last = h_lm_last[kv.first];
+    for (int f : lm_fids[kv.first]) h_reach[h_lf_pose[f]] = std::max(h_reach[h_lf_pose[f]], last);
+  }
+  std::sort(lf_lm_moved.begin(), lf_lm_moved.end());
+  lf_lm_moved.erase(std::unique(lf_lm_moved.begin(), lf_lm_moved.end()), lf_lm_moved.end());
+  csr_lm.touch(lo_lm);
+  if (!touched_poses.empty()) csr_pose.touch(touched_poses.front());
+  lm_first_from = std::min(lm_first_from, lo_lm);
+  topo_dirty = true;
+  merge_ms[0] = ms_since(t_host);
+  // fusion, on the lists the device still holds: one launch per class, one read-back of the status words
+  std::vector<int> failed;      // survivors whose cluster's sum was not positive definite
+  if (fuse) {
+    const clk::time_point t_fuse = clk::now();
+    hipStream_t s = stream;
+    std::vector<int> roots[2];      // [0] points, [1] cylinders
+    for (const auto& kv : gained)
+      if (h_lm_type[kv.first] == VT_POINT) roots[0].push_back(kv.first);
+      else if (h_lm_type[kv.first] == VT_CYL) roots[1].push_back(kv.first);
+    std::vector<int> tab;           // per class: ptr (nc + 1), surv (nc), status (nc), mem
+    struct Part { size_t ptr, surv, st, mem; int nc; } part[2];
+    for (int c = 0; c < 2; ++c) {
+      std::sort(roots[c].begin(), roots[c].end());
+      const int nc = (int)roots[c].size();
+      std::vector<int> ptr{0}, mem;
+      for (int r : roots[c]) {
+        std::vector<int> ms = gained[r];
+        ms.push_back(r);
+        std::sort(ms.begin(), ms.end());
+        mem.insert(mem.end(), ms.begin(), ms.end());
+        ptr.push_back((int)mem.size());
+      }
+      part[c] = Part{tab.size(), tab.size() + ptr.size(), tab.size() + ptr.size() + nc, tab.size() + ptr.size() + 2 * (size_t)nc, nc};
+      tab.insert(tab.end(), ptr.begin(), ptr.end());
+      tab.insert(tab.end(), roots[c].begin(), roots[c].end());
+      tab.insert(tab.end(), (size_t)nc, 0);
+      tab.insert(tab.end(), mem.begin(), mem.end());
+    }
+    if (part[0].nc + part[1].nc > 0) {
+      if (d_merge.ensure(tab.size(), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
+      SL_HIP(hipMemcpyAsync(d_merge.d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      SL_HIP(hipEventCreate(&e0));
+      SL_HIP(hipEventCreate(&e1));
+      (void)hipEventRecord(e0, s);
+      for (int c = 0; c < 2; ++c)
+        launch_lm_merge_fuse(G, c == 0 ? 3 : 7, d_merge.d + part[c].ptr, d_merge.d + part[c].mem, d_merge.d + part[c].surv, part[c].nc,
+                             d_merge.d + part[c].st, s);
+      (void)hipEventRecord(e1, s);
+      std::vector<int> st(tab.size());
+      SL_HIP(hipMemcpyAsync(st.data(), d_merge.d, tab.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+      const bool synced = hipStreamSynchronize(s) == hipSuccess;
+      float t = 0.f;
+      if (synced && hipEventElapsedTime(&t, e0, e1) == hipSuccess) merge_ms[3] = t;
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      if (!synced) return SLIDE_ERR_HIP;
+      SL_HIP(hipGetLastError());
+      for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < part[c].nc; ++i)
+          if (st[part[c].st + i] != 0) failed.push_back(roots[c][i]);
+    }
+    merge_ms[2] = ms_since(t_fuse);
+  }
+  if (!failed.empty() && status) {
+    for (int k = 0; k < n; ++k) {
+      if (merged_into[k] < 0) continue;
+      const int root = key2lm[lm_key(cls[k], keep_idx[k])];
+      if (std::find(failed.begin(), failed.end(), root) != failed.end()) status[k] = SLIDE_ERR_NOT_SPD;
+    }
+  }
+  // What the merge invalidates.  The uploaded counts do not change, so none of the guards that compare counts sees it:
+  drop_factor();              // the resident factor (and the kept solution) are the unmerged system's: marginal_state refuses until the next update
+  drop_stream_state();        // ... and so are the predicted relinearisation, the status words' state and the cached pose
+  if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }      // a captured pass bakes the profile's launches in
+  have_prev = false;
+  relin_all_next = true;      // run_update: the next update is a full one at the current estimate
+  const clk::time_point t_up = clk::now();
+  const int rc = upload_new();
+  if (rc == SLIDE_OK) SL_HIP(hipStreamSynchronize(stream));
+  merge_ms[1] = ms_since(t_up);
+  return rc;
+}
+int HostGraph::landmark_alias(int cls, uint64_t idx, uint64_t* into) {
+  *into = idx;
+  const uint64_t key = lm_key(cls, idx);
+  const auto it = key2lm.find(key);
+  if (it == key2lm.end()) {      // (a landmark still waiting for the next update is its own)
+    for (const PendVar& v : pend_vars)
+      if (v.key == key) return SLIDE_OK;
+    return SLIDE_MISSING;
+  }
+  *into = h_lm_key[it->second] & ((1ull << 56) - 1ull);
+  return SLIDE_OK;
+}
 void HostGraph::stats(int64_t* o) const {
-  o[0] = (int64_t)up_P; o[1] = (int64_t)up_L; o[2] = (int64_t)(up_pr + up_bt + up_lf); o[3] = last_relin;
+  o[0] = (int64_t)up_P; o[1] = (int64_t)(up_L - std::min(n_tomb, up_L)); o[2] = (int64_t)(up_pr + up_bt + up_lf); o[3] = last_relin;
   o[4] = (int64_t)G.T * NB;
 }
 int64_t HostGraph::rejected() const { return n_rejected; }

@@ -553,6 +553,15 @@ class HostGraph {
   }
   const double* pose_est_dev() const { return d_pose_est.d; }
   int lm_lid(int cls, uint64_t idx) const;                   // -1 when not merged yet
+  // Landmark fusion (host_graph.hip has the text): pair k says landmark (cls[k], drop_idx[k]) is the object (cls[k], keep_idx[k]) mapped
+  // a second time; its factors become the survivor's, its key an alias, its slot a tombstone.  fuse: the survivors of points and
+  // cylinders take the information-weighted mean of their cluster (k_lm_merge_fuse).  Arguments checked by the C ABI
+  int merge_landmarks(int n, const int32_t* cls, const uint64_t* keep_idx, const uint64_t* drop_idx, bool fuse, uint64_t* into, int32_t* moved,
+                      int32_t* status);
+  int landmark_alias(int cls, uint64_t idx, uint64_t* into);      // the key a landmark key resolves to (itself unless it was dropped), or SLIDE_MISSING
+  // what the last merge_landmarks call spent (measurement): host restructure, upload, k_lm_merge_fuse with its read-back (wall ms), and
+  // the kernel's launches alone between two events
+  void merge_timing(double* out4) const { for (int i = 0; i < 4; ++i) out4[i] = merge_ms[i]; }
   // one-robot-per-GPU mode: shared-landmark slots + the three phases of a distributed GN pass
   int set_shared(const int32_t* cls, const int64_t* idx, const int32_t* owner, int n_slots);
   int dist_phase(int phase, double* d_buf);
@@ -641,6 +650,16 @@ class HostGraph {
   std::vector<PendVar> pend_vars;
   std::vector<PendFac> pend_facs;
   std::unordered_map<uint64_t, int> key2pose, key2lm;
+  // merge_landmarks: key2lm sends a dropped key to its survivor.  h_lm_key: per landmark its own (first) key, 0 for a tombstone — a slot
+  // whose landmark was dropped: no key, no factors; lm_aliases: per survivor the dropped keys that resolve to it
+  std::vector<uint64_t> h_lm_key;
+  std::unordered_map<int, std::vector<uint64_t>> lm_aliases;
+  size_t n_tomb = 0;
+  bool lm_tomb(size_t l) const { return l < h_lm_key.size() && h_lm_key[l] == 0; }
+  std::vector<int> lf_lm_moved;         // factors below up_lf whose lf_lm row changed since the last upload (upload_new sends exactly those)
+  bool relin_all_next = false;          // the next update folds every delta in and linearises everything (run_update)
+  DevArr<int> d_merge;                  // k_lm_merge_fuse's cluster lists and status words
+  double merge_ms[4] = {0, 0, 0, 0};
   // merged host mirrors (initial values; theta itself lives in HBM)
   std::vector<double> h_pose_val, h_lm_val;
   std::vector<int> h_lm_type;

@@ -69,7 +69,7 @@ void HostGraph::ghost_row(const ClosureCols& c, size_t k, int slot, int gh, cons
 }
 void HostGraph::inverse_keys(bool poses, bool lms, std::vector<uint64_t>& pkey, std::vector<uint64_t>& lkey) const {
   if (poses) { pkey.assign(h_pose_val.size() / 12, 0); for (const auto& kv : key2pose) pkey[kv.second] = kv.first; }
-  if (lms) { lkey.assign(h_lm_type.size(), 0); for (const auto& kv : key2lm) lkey[kv.second] = kv.first; }
+  if (lms) lkey = h_lm_key;      // (a landmark's own first key: key2lm also holds the aliases merge_landmarks left)
 }
 void HostGraph::observation_rows(const ObsCols& c, size_t at, int count, int slot, const double* ws) const {
   std::vector<uint64_t> pkey, lkey;

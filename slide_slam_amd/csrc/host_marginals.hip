@@ -118,7 +118,7 @@ void HostGraph::robot_poses(int robot, std::vector<int>& out) const {
 void HostGraph::point_landmarks(std::vector<int>& out) const {
   out.clear();
   for (size_t l = 0; l < up_L && l < h_lm_type.size(); ++l)
-    if (h_lm_type[l] == VT_POINT) out.push_back((int)l);
+    if (h_lm_type[l] == VT_POINT && !lm_tomb(l)) out.push_back((int)l);      // (a tombstone of merge_landmarks is no landmark)
 }
 // isam->marginalCovariance(X(idx)) for n poses of one robot: out36n[36 q ..] row-major, tangent order [rot, trans]
 int HostGraph::pose_covariances(int robot, const uint64_t* idx, int n, double* out36n) {
@@ -1204,7 +1204,8 @@ int HostGraph::landmark_pairs_within(int cls, double radius, int n_sel, const ui
     const uint64_t tag = lm_key(cls, 0) >> 56;
     std::vector<std::pair<int, uint64_t>> all;
     for (const auto& kv : key2lm)
-      if ((kv.first >> 56) == tag && (size_t)kv.second < up_L) all.emplace_back(kv.second, kv.first & ((1ull << 56) - 1ull));
+      if ((kv.first >> 56) == tag && (size_t)kv.second < up_L && h_lm_key[kv.second] == kv.first)      // (not the aliases merge_landmarks left)
+        all.emplace_back(kv.second, kv.first & ((1ull << 56) - 1ull));
     std::sort(all.begin(), all.end());
     for (const auto& e : all) { lids.push_back(e.first); keys.push_back(e.second); }
   }

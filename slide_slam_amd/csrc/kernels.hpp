@@ -474,6 +474,11 @@ void launch_joint_lm_pair_fill(const GraphDev* Gs, const JointPoseTab* tab, int 
                                const LmPairSigma& sg, int n, double* B, size_t ld, double* r9, double* G0, hipStream_t s);
 void launch_joint_lm_pair_cov_finish(const GraphDev* Gs, int D, const int4* ends, const long long* sep_row, const double* M, int n, double* out,
                                      hipStream_t s);
+// Landmark fusion (lm_merge_kernels.hip; HostGraph::merge_landmarks): cluster c of n is the landmarks mem[ptr[c]] .. mem[ptr[c + 1] - 1]
+// (ascending ids, one class of dimension D = 3 or 7, the survivor surv[c] among them) as the graph's device lists still hold them.
+// x = (sum_i H_i)^-1 sum_i H_i est_i with H_i = sum Jl^T Jl over member i's records goes to lm_val and lm_est of the survivor, zero to
+// its lm_delta; status[c] = 1 and nothing written when a pivot of the sum is not positive, else 0.
+void launch_lm_merge_fuse(const GraphDev& G, int D, const int* ptr, const int* mem, const int* surv, int n, int* status, hipStream_t s);
 
 // Every pair i < j of n points with |x_i - x_j| <= radius (and label[i] == label[j] where labels are given), sorted by (i, j): the
 // count / k_seg_scan / emit idiom, one wavefront per row i, ballot compaction.  Point q is the three doubles at
