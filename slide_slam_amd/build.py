@@ -35,6 +35,7 @@ SOURCES = [
     ("lm_merge_kernels.hip", []),                       # (landmark fusion: the solver kernels' arithmetic, k_landmark's sums)
     ("host_graph.hip", ["-ffp-contract=off"]),
     ("host_marginals.hip", ["-ffp-contract=off"]),     # (its Woodbury step runs on the host: same rounding as host_graph.hip)
+    ("host_gates.hip", ["-ffp-contract=off"]),         # (the Mahalanobis gates' host side, split off host_marginals.hip: quantiles on the host)
     ("host_loss.hip", ["-ffp-contract=off"]),          # (the robust losses' host side, split off host_graph.hip the same way)
     ("host_backend.hip", ["-ffp-contract=off"]),
     ("host_clipper.hip", ["-ffp-contract=off"]),       # (the clique solver's host side, split off capi.hip: rounding of u against thresholds)

@@ -490,21 +490,29 @@ int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* 
 }
 // The joint-compatibility test of groups of such candidates (obs_joint_kernels.hip).  The argument checks come first, need neither
 // graph nor device and write nothing: the groups' own, the probability, then the candidates' as above.
+// (the groups' and the probability's, shared with the batch's call.  group_outs / cand_outs: every per-group / per-candidate output
+// is there; *n: the number of candidates the groups hold)
+static int joint_compat_check_groups(const char* who, int n_groups, const int32_t* group_ptr, double prob, bool group_outs, bool cand_outs, int* n) {
+  if (n_groups < 0) return obs_gate_bad("n_groups < 0", who);
+  if (n_groups > 0 && (!group_ptr || !group_outs)) return obs_gate_bad("a needed pointer is NULL", who);
+  if (n_groups > 0 && group_ptr[0] != 0) return obs_gate_bad("group_ptr does not start at 0", who);
+  for (int i = 0; i < n_groups; ++i)
+    if (group_ptr[i + 1] < group_ptr[i]) return obs_gate_bad("group_ptr decreases", who);
+  if (!(prob == 0.0 || (prob > 0.0 && prob < 1.0))) return obs_gate_bad("prob is neither 0 (evaluate only) nor inside (0, 1)", who);
+  *n = n_groups > 0 ? group_ptr[n_groups] : 0;
+  if (*n > 0 && !cand_outs) return obs_gate_bad("a needed pointer is NULL", who);
+  return SLIDE_OK;
+}
 int slide_graph_observation_joint_compatibility(slide_graph_t* g, int n_groups, const int32_t* group_ptr, const int32_t* robot,
                                                 const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx, const double* meas17,
                                                 double prob, int32_t* accepted, double* d2_single, double* d2_joint, int32_t* dof_joint,
                                                 int32_t* status, double* group_d2, int32_t* group_dof, int32_t* group_count,
                                                 int32_t* group_status) {
   const char* who = "observation_joint_compatibility";
-  if (n_groups < 0) return obs_gate_bad("n_groups < 0", who);
-  if (n_groups > 0 && (!group_ptr || !group_d2 || !group_dof || !group_count || !group_status)) return obs_gate_bad("a needed pointer is NULL", who);
-  if (n_groups > 0 && group_ptr[0] != 0) return obs_gate_bad("group_ptr does not start at 0", who);
-  for (int i = 0; i < n_groups; ++i)
-    if (group_ptr[i + 1] < group_ptr[i]) return obs_gate_bad("group_ptr decreases", who);
-  if (!(prob == 0.0 || (prob > 0.0 && prob < 1.0))) return obs_gate_bad("prob is neither 0 (evaluate only) nor inside (0, 1)", who);
-  const int n = n_groups > 0 ? group_ptr[n_groups] : 0;
-  if (n > 0 && (!accepted || !d2_single || !d2_joint || !dof_joint || !status)) return obs_gate_bad("a needed pointer is NULL", who);
-  const int rc = obs_gate_check_list(n, robot, nullptr, pose_idx, cls, lm_idx, meas17, d2_joint, who);
+  int n = 0;
+  int rc = joint_compat_check_groups(who, n_groups, group_ptr, prob, group_d2 && group_dof && group_count && group_status,
+                                     accepted && d2_single && d2_joint && dof_joint && status, &n);
+  if (rc == SLIDE_OK) rc = obs_gate_check_list(n, robot, nullptr, pose_idx, cls, lm_idx, meas17, d2_joint, who);
   if (rc != SLIDE_OK) return rc;
   if (!g) return obs_gate_bad("the graph is NULL", who);
   LOCK(g);
@@ -532,15 +540,10 @@ int slide_chol_batch_observation_joint_compatibility(slide_chol_batch_t* b, int 
                                                      int32_t* dof_joint, int32_t* status, double* group_d2, int32_t* group_dof,
                                                      int32_t* group_count, int32_t* group_status) {
   const char* who = "chol_batch_observation_joint_compatibility";
-  if (n_groups < 0) return obs_gate_bad("n_groups < 0", who);
-  if (n_groups > 0 && (!group_ptr || !group_d2 || !group_dof || !group_count || !group_status)) return obs_gate_bad("a needed pointer is NULL", who);
-  if (n_groups > 0 && group_ptr[0] != 0) return obs_gate_bad("group_ptr does not start at 0", who);
-  for (int i = 0; i < n_groups; ++i)
-    if (group_ptr[i + 1] < group_ptr[i]) return obs_gate_bad("group_ptr decreases", who);
-  if (!(prob == 0.0 || (prob > 0.0 && prob < 1.0))) return obs_gate_bad("prob is neither 0 (evaluate only) nor inside (0, 1)", who);
-  const int n = n_groups > 0 ? group_ptr[n_groups] : 0;
-  if (n > 0 && (!accepted || !d2_single || !d2_joint || !dof_joint || !status)) return obs_gate_bad("a needed pointer is NULL", who);
-  const int rc = obs_gate_check_list(n, pose_slot, lm_slot, pose_idx, cls, lm_idx, meas17, d2_joint, who);
+  int n = 0;
+  int rc = joint_compat_check_groups(who, n_groups, group_ptr, prob, group_d2 && group_dof && group_count && group_status,
+                                     accepted && d2_single && d2_joint && dof_joint && status, &n);
+  if (rc == SLIDE_OK) rc = obs_gate_check_list(n, pose_slot, lm_slot, pose_idx, cls, lm_idx, meas17, d2_joint, who);
   if (rc != SLIDE_OK) return rc;
   if (!b) return obs_gate_bad("the batch is NULL", who);
   return b->b.joint_observation_joint_compatibility(n_groups, group_ptr, pose_slot, pose_idx, lm_slot, cls, lm_idx, meas17, prob, accepted, d2_single,

@@ -174,7 +174,7 @@ using FormFill = std::function<void(int k0, int nc, double* B, int ld)>;
 using FormDone = std::function<int(int k0, int nc, const double* M)>;
 // (optional, single graph only) the first block column the sweep's forward substitution has to walk: B is zero above row NB * it
 using FormStart = std::function<int(int k0, int nc)>;
-struct FormBackend;      // (host_marginals.hip: what differs between one graph and the joint graph of a batch)
+struct FormBackend;      // (host_gates.hip: what differs between one graph and the joint graph of a batch)
 // the `prob` quantile of chi-square with dof degrees of freedom (host code; SLIDE_ERR_INVALID for prob outside (0, 1) or dof < 1)
 int chi2_quantile(double prob, int dof, double* q);
 class CholBatch {
@@ -242,7 +242,7 @@ class CholBatch {
   hipStream_t pass_stream();                             // the stream the passes run on (created on first use)
   int profile_pass(double* const* d_bufs, double* ms_steps, int* n_launches);
   int profile_arrow(double* const* d_bufs, double* out6, int* n_sep_steps);
-  // (the queries from here on: host_marginals.hip)
+  // (the queries from here on: host_marginals.hip; from the pose pairs on, host_gates.hip)
   // marginal covariances on the JOINT graph, from the factor the last exact joint pass (pass_all) left (joint_cov_kernels.hip): the
   // poses of the graph in `slot` by its pose indices, its landmarks by its landmark ids, logEntropy's trace sums (job-wide landmarks)
   int joint_pose_covariances(int slot, const uint64_t* idx, int n, double* out36n);
@@ -497,7 +497,7 @@ class HostGraph {
   int closure_info_gain_batch(int robot, int n_cand, const int32_t* off, const uint64_t* traj, const double* travel, const double* sigma6,
                               double* out3n, int32_t* status);      // candidate k = traj[off[k] .. off[k + 1]): out3n[3 k ..], status[k]
   // the joint marginal of pose pairs and the Mahalanobis gate of a list of loop closures, both as B^T Sigma B = W^T W with L W = B
-  // (host_marginals.hip sigma_forms, closure_kernels.hip); the arguments are checked by the C ABI before these are called
+  // (host_gates.hip sigma_forms, closure_kernels.hip); the arguments are checked by the C ABI before these are called
   int pose_pair_covariances(int n, const int32_t* robot_a, const uint64_t* idx_a, const int32_t* robot_b, const uint64_t* idx_b, double* out144n,
                             int32_t* status);
   int closure_mahalanobis(int L, const int32_t* from_robot, const uint64_t* from_idx, const int32_t* to_robot, const uint64_t* to_idx,
@@ -514,11 +514,14 @@ class HostGraph {
                                       const uint64_t* lm_idx, const double* meas17, double prob, int32_t* accepted, double* d2_single,
                                       double* d2_joint, int32_t* dof_joint, int32_t* status, double* group_d2, int32_t* group_dof,
                                       int32_t* group_count, int32_t* group_status);
-  // what the two calls above resolve of a candidate on the host, and where a sweep of candidates starts its walk
+  // what the two calls above resolve of a candidate on the host (obs_measurement: its class's factor type, z and the sigmas under
+  // this graph's parameters), and where a sweep starts its walk (of candidates; with `lo` its lowest pose)
   struct ObsCand { int st = SLIDE_OK, type = 0, p = -1, l = -1; double z[15] = {}, sg[9] = {}; };
   ObsCand obs_candidate(int robot, uint64_t pose_idx, int cls, uint64_t lm_idx, const double* meas17) const;
+  int obs_measurement(int cls, const double* meas17, double* z15, double* sigma9) const;
   int obs_walk_start(const int32_t* pid, const int32_t* lid, int n) const;
-  // Landmark PAIRS of one class each (host_marginals.hip has the text): the Mahalanobis test of "a and b are one object" (cov = false:
+  int walk_start(int lo) const;
+  // Landmark PAIRS of one class each (host_gates.hip has the text): the Mahalanobis test of "a and b are one object" (cov = false:
   // sig3 / sig7 the model noise of points / cylinders; d2, dof, C81, r9 as the observation gate's) or the pair's joint marginal
   // (cov = true: out324).  route[k]: 0 = read off the selected inverse, 1 = forward substitution; arguments checked by the C ABI
   int landmark_pairs(bool cov, int n, const int32_t* cls, const uint64_t* idx_a, const uint64_t* idx_b, const double* sig3, const double* sig7,
@@ -827,7 +830,7 @@ class HostGraph {
   bool have_prev = false;
 };
 
-// slide_pairs_within (host_marginals.hip, pairs_kernels.hip): every pair i < j of n host points within radius, sorted by (i, j);
+// slide_pairs_within (host_gates.hip, pairs_kernels.hip): every pair i < j of n host points within radius, sorted by (i, j);
 // arguments checked by the C ABI
 int pairs_within_host(const double* xyz, const int32_t* label, int n, double radius, int64_t cap, int32_t* out_i, int32_t* out_j, double* out_dist,
                       int64_t* n_pairs);

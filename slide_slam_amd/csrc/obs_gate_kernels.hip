@@ -10,7 +10,7 @@
 //     d2 = r^T C^-1 r,
 // F_f = E_f H_ll^-1 the 6 x D block of the factor's Schur record (ebuf + lf_eoff[f] + 6 D, as k_lm_cov and k_lm_V read it) and
 // H_ll^-1 the landmark's block of lm_Hinv: the pose-landmark cross block of the marginal is never formed.  B^T S^-1 B = W^T W with
-// L W = B is the forward substitution and gram of sigma_forms (host_marginals.hip); candidate k of a sweep owns the columns
+// L W = B is the forward substitution and gram of sigma_forms (host_gates.hip); candidate k of a sweep owns the columns
 // m k .. m k + m - 1 of B.
 //
 // On the JOINT graph of a CholBatch (slide_chol_batch_observation_mahalanobis) K = L D L^T is the exact joint pass's system and
@@ -18,7 +18,7 @@
 // for a PRIVATE landmark with G0 = Al H_ll^-1 Al^T and the B above in joint rows, the factors' poses being poses of the landmark's
 // graph (which need not be the candidate pose's); for a SHARED landmark — a separator variable the pass does not eliminate: its
 // H_ll^-1 and F are zero — with G0 = 0, no factor sum and Al^T as a right-hand side on the landmark's separator coordinates.  The
-// signed gram (D = -I on the lambda rows) is the joint closure gate's (closure_kernels.hip, host_marginals.hip's joint_sigma_forms).
+// signed gram (D = -I on the lambda rows) is the joint closure gate's (closure_kernels.hip, host_gates.hip's joint_sigma_forms).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"

@@ -17,7 +17,7 @@
 // B_i and G0_i exactly what k_joint_obs_gate_lin writes for candidate i (obs_gate_kernels.hip; k_joint_obs_joint_lin is that fill with a
 // class and a column per wavefront).  Private landmark: G0 = Al H_ll^-1 Al^T, the factor sum over the landmark's own graph's poses in
 // joint rows.  Shared landmark: G0 = 0, Al^T on its separator coordinates through the lowest robot's rows.  The cross blocks are the
-// off-diagonal part of the SIGNED gram M - Mneg over JointGain::form_rows' two lists (host_marginals.hip).  A private landmark may not
+// off-diagonal part of the SIGNED gram M - Mneg over JointGain::form_rows' two lists (host_sigma.hpp).  A private landmark may not
 // be named twice in a group — identity (landmark's slot, local id): H_ll is block diagonal and the cross block would miss
 // Al_i H_ll^-1 Al_j^T.  A shared landmark may — identity its separator offset, two replicas being one landmark: it is a separator
 // variable the pass does not eliminate, everything about it is in K, and W_i^T D W_j is the whole cross block.  The chain below runs on

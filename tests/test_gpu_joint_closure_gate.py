@@ -1,6 +1,6 @@
 """The Mahalanobis gate of loop closures and the joint marginal of pose pairs on the JOINT multi-robot graph, on the device
 (slide_chol_batch_closure_mahalanobis / slide_chol_batch_get_pose_pair_covariances: the forward half of the many-right-hand-side
-solve over the exact joint pass's tree and a signed gram, host_marginals.hip's joint_sigma_forms; closure_kernels.hip's
+solve over the exact joint pass's tree and a signed gram, host_gates.hip's joint_sigma_forms; closure_kernels.hip's
 k_joint_closure_gate_lin / k_joint_pair_identity / k_gram_sub) against the dense reference of tests/joint_closure_gate_cases.py.
 
 Per case: one Run (tests/test_gpu_joint_step.py), the reference at the values read before the pass, one exact joint pass, then the

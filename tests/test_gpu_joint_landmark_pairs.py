@@ -1,5 +1,5 @@
 """The duplicate-landmark queries on the JOINT multi-robot graph, on the device (slide_chol_batch_landmark_pair_mahalanobis /
-_get_landmark_pair_covariances: obs_gate_kernels.hip's k_joint_lm_pair_fill / k_joint_lm_pair_cov_finish through host_marginals.hip's
+_get_landmark_pair_covariances: obs_gate_kernels.hip's k_joint_lm_pair_fill / k_joint_lm_pair_cov_finish through host_gates.hip's
 joint_sigma_forms; slide_chol_batch_landmark_pairs_within: pairs_kernels.hip's gather and group-inequality sibling) against the dense
 reference of tests/joint_landmark_pair_cases.py.
 

@@ -1,6 +1,6 @@
 """The Mahalanobis gate of landmark observations on the JOINT multi-robot graph, on the device
 (slide_chol_batch_observation_mahalanobis: the forward half of the many-right-hand-side solve over the exact joint pass's tree and a
-signed gram, host_marginals.hip's joint_sigma_forms; obs_gate_kernels.hip's k_joint_obs_gate_lin / k_obs_gate_finish) against the dense
+signed gram, host_gates.hip's joint_sigma_forms; obs_gate_kernels.hip's k_joint_obs_gate_lin / k_obs_gate_finish) against the dense
 reference of tests/joint_observation_gate_cases.py.
 
 Per case: one Run (tests/test_gpu_joint_step.py), the reference at the values read before the pass, one exact joint pass, then the
