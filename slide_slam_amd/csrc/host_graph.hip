@@ -1976,12 +1976,29 @@ static int up_csr(CsrMirror& M, DevArr<int>& dptr, DevArr<int>& dval, const std:
   return dval.upload(M.val.data() + M.off0, M.off0, M.val.size() - M.off0, s);
 }
 
+// upload_new sends what merge_pending added, in four stages ("Where the layout is planned"); the layout itself is planned by host_layout.hpp.
 int HostGraph::upload_new() {
   thread_capture_mode_local();
   hipStream_t s = stream;
   if (!topo_dirty && uploaded_once) return SLIDE_OK;      // nothing was added since the last upload: values and topology are resident
   if (ub.begin() != SLIDE_OK) return SLIDE_ERR_HIP;
   struct BatchGuard { ~BatchGuard() { UploadBatch::current = nullptr; } } batch_guard;      // an error return abandons the batch
+  int rc = upload_tails(s);
+  // (the batch stays open across the border and the profile: the profile's two small arrays ride in the same copy; flushed right after)
+  if (rc == SLIDE_OK) rc = upload_border(s);
+  if (rc == SLIDE_OK) rc = upload_system(s);
+  if (rc != SLIDE_OK) return rc;
+  if (ub.flush(s) != SLIDE_OK) return SLIDE_ERR_HIP;   // (the host temporaries were copied into the pinned staging buffer)
+  topo_dirty = false;
+  uploaded_once = true;
+  up_P = h_pose_val.size() / 12; up_L = h_lm_type.size(); up_pr = h_pr_pose.size(); up_bt = h_bt_i.size(); up_lf = h_lf_type.size(); up_gh = h_gh_pose.size();
+  up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7; up_nbr = h_lf_nbr.size();
+  if (rb_arrays) { up_rb = up_bt; up_rbg = up_gh; }
+  if (ol_arrays) up_ol = up_lf;
+  return upload_view(s);
+}
+// stage 1: the tails of the host arrays, the CSR mirrors, the buffers of the linearisation
+int HostGraph::upload_tails(hipStream_t s) {
   const size_t Pn = h_pose_val.size() / 12, Ln = h_lm_type.size();
   const size_t npr = h_pr_pose.size(), nbt = h_bt_i.size(), nlf = h_lf_type.size();
 #define UP(dev, host, oldn, per) \
@@ -2100,173 +2117,24 @@ int HostGraph::upload_new() {
     if (d_lm_first.upload(h_lm_first.data() + f0, f0, Ln - f0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
     lm_first_from = 1 << 30;
   }
-  // (the batch stays open across the profile below: its two small arrays ride in the same copy; flushed right after)
-  // exact joint step: this robot's border = its shared landmarks and the lambda coordinates of its relative-pose factors
-  const bool arrow_now = arrow_on();
+  return SLIDE_OK;
+}
+// stage 2, exact joint step: this robot's border = its shared landmarks and the lambda coordinates of its relative-pose factors, behind the
+// poses of the cuts of its own chain (plan_border, host_layout.hpp)
+int HostGraph::upload_border(hipStream_t s) {
   int nbr_new = 0;
-  if (arrow_now) {
-    const int ns = (int)h_sh_lid.size(), m = h_sep_off.back();
-    const bool lam_on = lam_total > 0 && h_gh_gid.size() == h_gh_pose.size();
-    if (lam_total > 0 && !lam_on) { g_last_error = "exact joint step: slide_graph_set_ghost_ids must name every ghost factor of the graph"; return SLIDE_ERR_INVALID; }
-    h_lm_bord.assign(std::max<size_t>(Ln, 1), -1);
-    h_sep_map.assign(std::max(m + lam_total, 1), -1);
-    h_gh_bord.assign(std::max<size_t>(h_gh_pose.size(), 1), -1);
-    // border items: this robot's shared landmarks and the lambda coordinates of its relative-pose factors, ordered by the first block
-    // column of the band in which their coupling row is non-zero (the first observing key frame) — the rows that are still all-zero at a
-    // block column are then a SUFFIX of the border, which the steps and the border product skip (the maps below carry the permutation)
-    // Nested dissection of the own pose chain (CholBatch::set_segments): cut the chain at n_seg - 1 places; the separator behind a cut at
-    // pose q0 is [q0, q1) with q1 = 1 + the furthest pose any pose before q0 couples to (a landmark both observe, a relative-pose factor):
-    // nothing couples across it.  Its poses become the FIRST border rows (whole tiles: the second level factors them as a dense system).
-    segs.clear();
-    h_pose_sep.assign(std::max<size_t>(Pn, 1), -1);
-    nsep = nsep_dim = n_sep_poses = 0;
-    const int want_seg = batch ? batch->segments() : 1;
-    std::vector<std::pair<int, int>> seg_cuts;        // the windows [q0, q1) of poses behind the segments (all but the last)
-    std::vector<int> reach;
-    if (want_seg >= 2 && Pn >= 64) {
-      std::vector<int> lm_last(Ln, -1);
-      reach.assign(Pn, 0);
-      for (size_t f = 0; f < nlf; ++f) lm_last[h_lf_lm[f]] = std::max(lm_last[h_lf_lm[f]], h_lf_pose[f]);
-      for (size_t p = 0; p < Pn; ++p) reach[p] = (int)p;
-      for (size_t f = 0; f < nlf; ++f) reach[h_lf_pose[f]] = std::max(reach[h_lf_pose[f]], lm_last[h_lf_lm[f]]);
-      for (size_t b = 0; b < nbt; ++b) {
-        const int lo = std::min(h_bt_i[b], h_bt_j[b]), hi = std::max(h_bt_i[b], h_bt_j[b]);
-        reach[lo] = std::max(reach[lo], hi);
-      }
-      std::vector<int> run(Pn);                       // furthest reach of the poses 0 .. p
-      for (size_t p = 0; p < Pn; ++p) run[p] = std::max(reach[p], p ? run[p - 1] : 0);
-      std::vector<std::pair<int, int>> cuts;
-      int seg_start = 0;
-      bool ok = true;
-      std::vector<Seg> tmp;
-      for (int i = 1; i < want_seg && ok; ++i) {
-        const int q0 = (int)(Pn * (size_t)i / want_seg);
-        if (q0 <= seg_start + 8) continue;
-        const int q1 = run[q0 - 1] + 1;
-        if (q1 <= q0 || q1 + 8 >= (int)Pn) continue;      // (nothing couples across q0: no separator needed — or no room for a segment behind it)
-        const Seg sg{6 * seg_start / NB, (6 * q0 + NB - 1) / NB};
-        if (!tmp.empty() && sg.t0 < tmp.back().t1) { ok = false; break; }      // (a separator narrower than a tile: segments would share one)
-        tmp.push_back(sg);
-        cuts.emplace_back(q0, q1);
-        seg_start = q1;
-      }
-      if (ok && !cuts.empty()) {
-        const Seg last{6 * seg_start / NB, (int)((6 * Pn + NB - 1) / NB)};
-        if (last.t0 >= tmp.back().t1) {
-          tmp.push_back(last);
-          segs = tmp;
-          seg_cuts = cuts;
-          for (const auto& c : cuts)
-            for (int q = c.first; q < c.second; ++q) { h_pose_sep[q] = 6 * n_sep_poses; ++n_sep_poses; }
-          nsep_dim = 6 * n_sep_poses;
-          nsep = (nsep_dim + NB - 1) / NB;
-        }
-      }
-    }
-    struct Item { int cb, kind, id, dim, goff; };
-    std::vector<Item> items;
-    std::vector<char> taken((size_t)std::max(m, 0), 0);      // (a caller's own layout with overlapping slots would add two landmarks into the same separator coordinates)
-    for (int i = 0; i < ns; ++i) {
-      const int lid = h_sh_lid[i];
-      if (lid < 0 || (size_t)lid >= Ln) continue;
-      const int dim = lm_dim(h_lm_type[lid]);      // (the slots' coordinates may be laid out in any order: separator_offsets orders them along the robots' adjacency)
-      if (h_sep_off[i] + dim > m) { g_last_error = "separator offsets do not match the landmark classes of the shared slots"; return SLIDE_ERR_INVALID; }
-      for (int k = 0; k < dim; ++k) {
-        if (taken[(size_t)h_sep_off[i] + k]) { g_last_error = "separator offsets: the coordinate ranges of two shared slots overlap"; return SLIDE_ERR_INVALID; }
-        taken[(size_t)h_sep_off[i] + k] = 1;
-      }
-      int fp = 1 << 30;
-      for (int f : lm_fids[lid]) fp = std::min(fp, h_lf_pose[f]);
-      items.push_back(Item{fp == (1 << 30) ? 0 : 6 * fp / NB, 0, lid, dim, h_sep_off[i]});
-    }
-    if (lam_on)
-      for (size_t q = 0; q < h_gh_pose.size(); ++q) {
-        for (int k = 0; k < 6; ++k)
-          if (h_sep_map[m + 6 * h_gh_gid[q] + k] == -2) { g_last_error = "exact joint step: two ghost factors of one graph name the same measurement"; return SLIDE_ERR_INVALID; }
-        for (int k = 0; k < 6; ++k) h_sep_map[m + 6 * h_gh_gid[q] + k] = -2;
-        items.push_back(Item{6 * h_gh_pose[q] / NB, 1, (int)q, 6, m + 6 * h_gh_gid[q]});
-      }
-    std::stable_sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.cb < y.cb; });
-    int o = nsep * NB;                                 // (the separator poses' rows come first, in whole tiles)
-    for (const Item& it : items) {
-      if (it.kind == 0) h_lm_bord[it.id] = o; else h_gh_bord[it.id] = o;
-      for (int k = 0; k < it.dim; ++k) h_sep_map[it.goff + k] = o + k;
-      o += it.dim;
-    }
-    nbr_new = (o + NB - 1) / NB;
-    h_bfirst.assign(nbr_new + 1, 0);
-    for (int t = nsep; t < nbr_new; ++t) h_bfirst[t] = 1 << 30;      // (separator-pose rows: always active, 0)
-    o = nsep * NB;
-    for (const Item& it : items) {
-      for (int t = o / NB; t <= (o + it.dim - 1) / NB; ++t) h_bfirst[t] = std::min(h_bfirst[t], it.cb);
-      o += it.dim;
-    }
-    for (int t = 0; t < nbr_new; ++t) if (h_bfirst[t] == (1 << 30)) h_bfirst[t] = 0;
-    for (int t = 1; t < nbr_new; ++t) h_bfirst[t] = std::max(h_bfirst[t], h_bfirst[t - 1]);      // (non-decreasing by construction; kept so by force)
-    // per-segment activity of the border rows (see host_graph.hpp)
-    seg_ord.clear(); seg_sfirst.clear(); seg_tab.clear();
+  if (arrow_on()) {
+    BorderPlan B = plan_border(h_pose_val.size() / 12, h_lf_pose, h_lf_lm, h_lm_type, lm_fids, h_bt_i, h_bt_j, h_sh_lid, h_sep_off, h_gh_pose, h_gh_gid,
+                               lam_total, batch ? batch->segments() : 1);
+    if (B.refused) { g_last_error = B.refused; return SLIDE_ERR_INVALID; }
+    nbr_new = B.nbr;
+    h_lm_bord = std::move(B.lm_bord); h_sep_map = std::move(B.sep_map); h_gh_bord = std::move(B.gh_bord); h_bfirst = std::move(B.bfirst);
+    segs = std::move(B.segs); h_pose_sep = std::move(B.pose_sep);
+    nsep = B.nsep; nsep_dim = B.nsep_dim; n_sep_poses = B.n_sep_poses;
+    seg_ord = std::move(B.seg_ord); seg_sfirst = std::move(B.seg_sfirst); seg_tab = std::move(B.seg_tab);
     if (!segs.empty()) {
-      const int NS = (int)segs.size(), INF = 1 << 30;
-      std::vector<std::vector<int>> sf(NS, std::vector<int>(nbr_new + 1, INF));
-      auto seg_of = [&](int col) { for (int q = 0; q < NS; ++q) if (col >= segs[q].t0 && col < segs[q].t1) return q; return -1; };
-      auto touch = [&](int t_lo, int t_hi, int pose) {
-        if (pose < 0 || (size_t)pose >= Pn || h_pose_sep[pose] >= 0) return;      // (a cut's pose: that coupling lives in the border block)
-        const int c = 6 * pose / NB, q = seg_of(c);
-        if (q < 0) return;
-        for (int t = t_lo; t <= t_hi; ++t) sf[q][t] = std::min(sf[q][t], c);
-      };
-      int o2 = nsep * NB;
-      for (const Item& it : items) {
-        const int t_lo = o2 / NB, t_hi = (o2 + it.dim - 1) / NB;
-        if (it.kind == 0) { for (int f : lm_fids[it.id]) touch(t_lo, t_hi, h_lf_pose[f]); }
-        else touch(t_lo, t_hi, h_gh_pose[it.id]);
-        o2 += it.dim;
-      }
-      // the cuts' poses: window w lies between segment w and segment w + 1; before it, the poses whose reach crosses its start couple to
-      // it (contiguous up to the cut); behind it, the segment's first block columns do
-      int nb4 = 0;
-      for (size_t w = 0; w < seg_cuts.size(); ++w) {
-        const int q0 = seg_cuts[w].first, q1 = seg_cuts[w].second;
-        const int t_lo = 6 * nb4 / NB, t_hi = (6 * (nb4 + q1 - q0) - 1) / NB;
-        int pf = q0;
-        for (int pz = q0 - 1; pz >= 0 && 6 * pz / NB >= segs[w].t0; --pz) if (reach[pz] >= q0) pf = pz;
-        if (pf < q0) for (int t = t_lo; t <= t_hi; ++t) sf[w][t] = std::min(sf[w][t], std::max(6 * pf / NB, segs[w].t0));
-        if (w + 1 < segs.size()) for (int t = t_lo; t <= t_hi; ++t) sf[w + 1][t] = std::min(sf[w + 1][t], segs[w + 1].t0);
-        nb4 += q1 - q0;
-      }
-      seg_tab.push_back(NS);
-      for (int q = 0; q < NS; ++q) seg_tab.push_back(segs[q].t1);
-      std::vector<int> flat_ord;
-      for (int q = 0; q < NS; ++q) {
-        sf[q][nbr_new] = segs[q].t0;                  // the right-hand-side row rides from the segment's first block column
-        std::vector<int> ord(nbr_new);
-        for (int t = 0; t < nbr_new; ++t) ord[t] = t;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return sf[q][a] < sf[q][b]; });
-        std::vector<int> sorted(nbr_new + 1);
-        for (int j = 0; j < nbr_new; ++j) sorted[j] = sf[q][ord[j]];
-        sorted[nbr_new] = segs[q].t0;
-        seg_ord.push_back(ord); seg_sfirst.push_back(sorted);
-        flat_ord.insert(flat_ord.end(), ord.begin(), ord.end());
-        seg_tab.insert(seg_tab.end(), sf[q].begin(), sf[q].end());
-      }
-      {
-        // and, behind it, per block column of the band the set of border tile rows some segment works on there (k_border_apply reads
-        // only those): T, then T x (low, high) words of a 64-bit mask — T = 0: more than 64 border tile rows, no masks
-        const int Tb = (int)((6 * Pn + NB - 1) / NB);
-        seg_tab_head = (int)seg_tab.size();
-        if (nbr_new <= 64) {
-          seg_tab.push_back(Tb);
-          for (int c = 0; c < Tb; ++c) {
-            unsigned long long m = 0;
-            for (int q = 0; q < NS; ++q)
-              if (c < segs[q].t1)
-                for (int t = 0; t < nbr_new; ++t)
-                  if (sf[q][t] <= c && c >= segs[q].t0) m |= 1ull << t;
-            seg_tab.push_back((int)(unsigned)(m & 0xffffffffull));
-            seg_tab.push_back((int)(unsigned)(m >> 32));
-          }
-        } else seg_tab.push_back(0);
-      }
+      seg_tab_head = B.seg_tab_head;
+      const std::vector<int>& flat_ord = B.flat_ord;
       if (d_seg_ord.ensure(std::max<size_t>(flat_ord.size(), 1), 0, s) != SLIDE_OK || d_seg_tab.ensure(seg_tab.size(), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
       if (!flat_ord.empty()) SL_HIP(hipMemcpyAsync(d_seg_ord.d, flat_ord.data(), flat_ord.size() * sizeof(int), hipMemcpyHostToDevice, s));
       SL_HIP(hipMemcpyAsync(d_seg_tab.d, seg_tab.data(), seg_tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
@@ -2296,6 +2164,13 @@ int HostGraph::upload_new() {
     }
   }
   nbr = nbr_new;
+  return SLIDE_OK;
+}
+// stage 3: S, the factor buffers and the joint-solve buffers; the tile profile and what it clears in S
+int HostGraph::upload_system(hipStream_t s) {
+  const size_t Pn = h_pose_val.size() / 12;
+  const bool arrow_now = arrow_on();
+  const int nbr_new = nbr;      // (upload_border's)
   // dense reduced system
   const int T = (int)((6 * Pn + NB - 1) / NB);
   bool fresh_S = false;
@@ -2336,25 +2211,11 @@ int HostGraph::upload_new() {
       joint_Tcap = Tcap;
     }
   }
-  // Profile of the reduced pose system at tile level.  reach(p) = the last pose coupled to pose p (a landmark both observe, a
-  // relative-pose factor); block column c reaches the tile row of the farthest reach of its poses; the running maximum over c is
-  // closed under the fill of the factorisation (eliminating column c fills rows <= prof[c] of columns <= prof[c] only).
+  // the tile profile (plan_tile_profile, host_layout.hpp) from h_reach, which merge_pending keeps current: no pass over all factors per
+  // update.  force_dense: a measurement aid (slide_graph_set_dense_profile / SLIDE_CHOL_DENSE=1)
   {
-    const std::vector<int>& reach = h_reach;      // (kept current by merge_pending: no pass over all factors per update)
-    const bool dense = force_dense;      // measurement aid (slide_graph_set_dense_profile / SLIDE_CHOL_DENSE=1): ignore the structure
-    std::vector<int> prof(T), first(T);
-    for (int c = 0; c < T; ++c) prof[c] = dense ? T - 1 : c;
-    for (size_t p = 0; p < Pn && !dense; ++p) {
-      const int rt = (6 * reach[p] + 5) / NB;
-      const int ta = (int)(6 * p) / NB, tb = (int)(6 * p + 5) / NB;
-      prof[ta] = std::max(prof[ta], rt);
-      prof[tb] = std::max(prof[tb], rt);
-    }
-    for (int c = 1; c < T; ++c) prof[c] = std::max(prof[c], prof[c - 1]);
-    for (int r = 0, c = 0; r < T; ++r) {
-      while (prof[c] < r) ++c;
-      first[r] = c;
-    }
+    TileProfile tp = plan_tile_profile(h_reach, Pn, force_dense);
+    const std::vector<int>& prof = tp.prof;
     if (prof != h_prof) {
       // S outside the profile must hold zeros.  A freshly allocated S does; when T grows, the old right-hand-side row (one row of
       // the old last tile row + 1) becomes a matrix row and is cleared; when a tile LEAVES the profile (never on a growing graph) the
@@ -2369,8 +2230,8 @@ int HostGraph::upload_new() {
         else if (T > Told && Told > 0)      // (a graph with a border is re-allocated whenever T changes: fresh_S)
           SL_HIP(hipMemset2DAsync(d_S.d + (size_t)Told * NB, ld * sizeof(double), 0, sizeof(double), (size_t)Told * NB, s));
       }
-      h_prof = prof;
-      h_first = first;
+      h_prof = std::move(tp.prof);
+      h_first = std::move(tp.first);
       h_first.push_back(0);      // (one more entry: the right-hand-side row reaches every column — the catch-up product of an incremental update)
       if (d_prof.ensure(std::max<size_t>(T, 1), 0, s) != SLIDE_OK || d_first.ensure(std::max<size_t>(T + 1, 1), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
       if (T) {      // (into the open upload batch: staged at once, no copy or synchronisation of their own)
@@ -2379,14 +2240,14 @@ int HostGraph::upload_new() {
       ++prof_ver;
     }
   }
-  if (ub.flush(s) != SLIDE_OK) return SLIDE_ERR_HIP;   // (the host temporaries were copied into the pinned staging buffer)
-  topo_dirty = false;
-  uploaded_once = true;
-  up_P = Pn; up_L = Ln; up_pr = npr; up_bt = nbt; up_lf = nlf; up_gh = ngh;
-  up_br = h_br_z.size() / 4; up_cu = h_cu_z.size() / 15; up_cy = h_cy_z.size() / 7; up_nbr = h_lf_nbr.size();
-  if (rb_arrays) { up_rb = nbt; up_rbg = ngh; }
-  if (ol_arrays) up_ol = nlf;
-
+  return SLIDE_OK;
+}
+// stage 4: the device view of the graph, the pose adjacency, the segments' profiles, the Schur pair lists and the slot table
+int HostGraph::upload_view(hipStream_t s) {
+  const size_t Pn = h_pose_val.size() / 12, Ln = h_lm_type.size();
+  const size_t npr = h_pr_pose.size(), nbt = h_bt_i.size(), nlf = h_lf_type.size(), ngh = h_gh_pose.size();
+  const bool arrow_now = arrow_on();
+  const int T = (int)((6 * Pn + NB - 1) / NB);
   G.P = (int)Pn; G.L = (int)Ln;
   G.pose_val = d_pose_val.d; G.pose_delta = d_pose_delta.d; G.pose_est = d_pose_est.d;
   G.lm_type = d_lm_type.d; G.lm_val = d_lm_val.d; G.lm_delta = d_lm_delta.d; G.lm_est = d_lm_est.d;
@@ -2430,17 +2291,12 @@ int HostGraph::upload_new() {
     SL_HIP(hipMemset2DAsync(d_S.d + (size_t)T * NB, (size_t)(Tcap + nbr_alloc + 1) * NB * sizeof(double), 0, (size_t)(nbr + 1) * NB * sizeof(double), (size_t)T * NB, s));
   }
   G.pose_sep = (arrow_now && nsep > 0) ? d_pose_sep.d : nullptr; G.nsep = arrow_now ? nsep : 0; G.nsep_dim = arrow_now ? nsep_dim : 0;
-  // the segments' own profiles (their rows end where the separator begins: what lay beyond moved into the border)
+  // the segments' own profiles (plan_segment_profiles)
   seg_prof.clear(); seg_prof_off.clear();
   if (arrow_now && nsep > 0) {
-    std::vector<int> flat;
-    for (const Seg& sg : segs) {
-      std::vector<int> pv(sg.t1 - sg.t0);
-      for (int c = sg.t0; c < sg.t1; ++c) pv[c - sg.t0] = std::min(h_prof[c], sg.t1 - 1) - sg.t0;
-      seg_prof_off.push_back(flat.size());
-      flat.insert(flat.end(), pv.begin(), pv.end());
-      seg_prof.push_back(pv);
-    }
+    SegmentProfiles sp = plan_segment_profiles(h_prof, segs);
+    seg_prof = std::move(sp.seg_prof); seg_prof_off = std::move(sp.seg_prof_off);
+    const std::vector<int>& flat = sp.flat;
     if (d_seg_prof.ensure(std::max<size_t>(flat.size(), 1), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
     SL_HIP(hipMemcpyAsync(d_seg_prof.d, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice, s));
     SL_HIP(hipStreamSynchronize(s));
@@ -2457,62 +2313,19 @@ int HostGraph::upload_new() {
   }
   return sync_lm_slot();
 }
-// Pair lists of the Schur assembly.  k_schur's block (pi, pj) is the sum over the pairs (factor x of pose pi, factor y of pose pj) on one
-// landmark of F_x E_y^T; walking pose pi's list and looking every landmark up in pose pj's costs ~20 probes per block for ~2 hits.  Between
-// the passes of a batched job the topology does not change, so the hits are listed once, in the order the walk finds them (x ascending
-// in pi's list, y ascending in pj's).  Separator landmarks are left out (H_ll^-1 = 0 there: their F is zero).  Only inside a monotone
-// profile whose strips are at most 256 poses wide; otherwise (and on every streaming update, which changes the topology) k_schur walks.
+// The pair lists of the Schur assembly (plan_schur_pairs, host_layout.hpp), or none: then (and on every streaming update, which changes
+// the topology) k_schur walks.
 int HostGraph::build_schur_pairs(hipStream_t s) {
-  const int Pn = (int)pose_fids.size();
-  if (Pn == 0 || h_prof.empty() || !G.prof) return SLIDE_OK;
-  auto p_end = [&](int pj) { return std::min(Pn, ((h_prof[(6 * pj + 5) / NB] + 1) * NB + 5) / 6); };
-  int W = 1;
-  for (int pj = 0; pj < Pn; ++pj) W = std::max(W, p_end(pj) - pj);
-  if (W > 256) return SLIDE_OK;
-  // k_schur_lb addresses the E / F records by 32-bit byte offsets into ebuf — it truncates a pair entry's record offset to
-  // (unsigned)(entry >> 4) and multiplies by eight — so every record has to end below 4 GB = 2^29 doubles; past that the walk runs
-  if (ebuf_used >= (1LL << 29)) return SLIDE_OK;
-  std::vector<int> idx((size_t)2 * Pn * W, 0);
-  std::vector<long long> pairs;
-  auto ed_of = [&](int f) {
-    const int ty = h_lm_type[h_lf_lm[f]];
-    return ((long long)h_lf_eoff[f] << 4) | (ty == VT_POINT ? 3 : (ty == VT_CUBE ? 9 : 7));
-  };
-  const bool have_bord = !h_lm_bord.empty();
-  std::vector<std::vector<std::pair<int, int>>> rows(W);      // per d = pi - pj: (x, y) factor ids
-  for (int pj = 0; pj < Pn; ++pj) {
-    const int pe = p_end(pj);
-    for (auto& r : rows) r.clear();
-    // every factor y of pose pj: the other factors x of its landmark on poses pi in [pj, pe)
-    for (int y : pose_fids[pj]) {
-      const int l = h_lf_lm[y];
-      if (have_bord && (size_t)l < h_lm_bord.size() && h_lm_bord[l] >= 0) continue;
-      for (int x : lm_fids[l]) {
-        const int pi = h_lf_pose[x];
-        if (pi >= pj && pi < pe) rows[pi - pj].emplace_back(x, y);
-      }
-    }
-    for (int d = 0; d < pe - pj; ++d) {
-      auto& r = rows[d];
-      if (r.empty()) continue;
-      // the walk's order: x in the order of pose pi's list (landmark id, factor id), then y in the order of pose pj's list
-      std::sort(r.begin(), r.end(), [&](const std::pair<int, int>& a, const std::pair<int, int>& b) {
-        const int la = h_lf_lm[a.first], lb = h_lf_lm[b.first];
-        if (la != lb) return la < lb;
-        if (a.first != b.first) return a.first < b.first;
-        return a.second < b.second;
-      });
-      idx[2 * ((size_t)pj * W + d)] = (int)(pairs.size() / 2);
-      idx[2 * ((size_t)pj * W + d) + 1] = (int)r.size();
-      for (const auto& xy : r) { pairs.push_back(ed_of(xy.first)); pairs.push_back(ed_of(xy.second)); }
-    }
-  }
-  if (pairs.size() / 2 > (size_t)0x7fffffff) return SLIDE_OK;
+  if (!G.prof) return SLIDE_OK;
+  const SchurPairs sp = plan_schur_pairs(pose_fids, lm_fids, h_prof, h_lf_pose, h_lf_lm, h_lf_eoff, h_lm_type, h_lm_bord, ebuf_used);
+  if (sp.walk) return SLIDE_OK;
+  const std::vector<int>& idx = sp.idx;
+  const std::vector<long long>& pairs = sp.pairs;
   if (d_sp_idx.ensure(idx.size(), 0, s) != SLIDE_OK || d_sp_pairs.ensure(std::max<size_t>(pairs.size(), 2), 0, s) != SLIDE_OK) return SLIDE_ERR_HIP;
   SL_HIP(hipMemcpyAsync(d_sp_idx.d, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, s));
   if (!pairs.empty()) SL_HIP(hipMemcpyAsync(d_sp_pairs.d, pairs.data(), pairs.size() * sizeof(long long), hipMemcpyHostToDevice, s));
   SL_HIP(hipStreamSynchronize(s));      // (pageable temporaries)
-  G.sp_idx = d_sp_idx.d; G.sp_pairs = d_sp_pairs.d; G.sp_w = W;
+  G.sp_idx = d_sp_idx.d; G.sp_pairs = d_sp_pairs.d; G.sp_w = sp.W;
   return SLIDE_OK;
 }
 int HostGraph::sync_lm_slot() {
@@ -2521,15 +2334,9 @@ int HostGraph::sync_lm_slot() {
     G.lm_slot = nullptr;
     return SLIDE_OK;
   }
-  const size_t Ln = h_lm_type.size();
-  std::vector<int> slot(std::max<size_t>(Ln, 1), -1);
-  for (size_t i = 0; i < h_sh_lid.size(); ++i)
-    if (h_sh_lid[i] >= 0 && (size_t)h_sh_lid[i] < Ln) slot[h_sh_lid[i]] = (int)i;
-  // every slot k_sep_lm_delta_b writes a delta for (sh_lid[i] >= 0) is the slot its landmark's entry leads back to: then the exact pass's
-  // back-substitution writes those deltas itself (launch_arrow_finish_batched)
-  lm_slot_onto = true;
-  for (size_t i = 0; i < h_sh_lid.size(); ++i)
-    if (h_sh_lid[i] >= 0 && ((size_t)h_sh_lid[i] >= Ln || slot[h_sh_lid[i]] != (int)i)) lm_slot_onto = false;
+  LmSlot ls = plan_lm_slot(h_sh_lid, h_lm_type.size());
+  lm_slot_onto = ls.onto;
+  const std::vector<int>& slot = ls.slot;
   if (d_lm_slot.ensure(slot.size(), 0, stream) != SLIDE_OK) return SLIDE_ERR_HIP;
   SL_HIP(hipMemcpyAsync(d_lm_slot.d, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, stream));
   SL_HIP(hipStreamSynchronize(stream));      // (a pageable temporary)
@@ -3321,35 +3128,33 @@ int HostGraph::chi2(double* out4) {
   factor_valid = false;
   return SLIDE_OK;
 }
-int HostGraph::get_tile_profile(int* out, int cap) {
+// the getters below report the layout of the graph as it stands: pending additions are merged and uploaded first (0, or the negative error)
+int HostGraph::layout_current() {
   int rc = merge_pending();
   if (rc == SLIDE_OK) rc = upload_new();
-  if (rc != SLIDE_OK) return rc < 0 ? rc : -rc;
+  return rc < 0 ? rc : -rc;
+}
+int HostGraph::get_tile_profile(int* out, int cap) {
+  if (const int rc = layout_current()) return rc;
   const int T = (int)h_prof.size();
   for (int c = 0; c < T && c < cap; ++c) out[c] = h_prof[c];
   return T;
 }
 int HostGraph::get_border_profile(int* out, int cap) {
-  int rc = merge_pending();
-  if (rc == SLIDE_OK) rc = upload_new();
-  if (rc != SLIDE_OK) return rc < 0 ? rc : -rc;
+  if (const int rc = layout_current()) return rc;
   if (!arrow_on()) return 0;
   for (int i = 0; i < nbr && i < cap; ++i) out[i] = h_bfirst[i];
   return nbr;
 }
 // the per-segment activity table of the border rows (seg_tab, host_graph.hpp): returns its length, 0 when the band is not cut
 int HostGraph::get_segment_table(int* out, int cap) {
-  int rc = merge_pending();
-  if (rc == SLIDE_OK) rc = upload_new();
-  if (rc != SLIDE_OK) return rc < 0 ? rc : -rc;
+  if (const int rc = layout_current()) return rc;
   if (!arrow_on() || nsep <= 0 || seg_tab.empty()) return 0;
   for (int i = 0; i < seg_tab_head && i < cap; ++i) out[i] = seg_tab[i];      // (the per-column masks behind it are the kernels' business)
   return seg_tab_head;
 }
 int HostGraph::get_segments(int* out, int cap) {
-  int rc = merge_pending();
-  if (rc == SLIDE_OK) rc = upload_new();
-  if (rc != SLIDE_OK) return rc < 0 ? rc : -rc;
+  if (const int rc = layout_current()) return rc;
   if (!arrow_on() || nsep <= 0) return 1;
   for (size_t i = 0; i < segs.size() && 2 * (int)i + 1 < cap; ++i) { out[2 * i] = segs[i].t0; out[2 * i + 1] = segs[i].t1; }
   if (2 * (int)segs.size() < cap) out[2 * segs.size()] = n_sep_poses;

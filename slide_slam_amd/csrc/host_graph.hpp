@@ -16,6 +16,7 @@
 
 #include "../../include/slide_gpu.h"
 #include "graph_dev.hpp"
+#include "host_layout.hpp"
 #include "kernels.hpp"
 #include "sl_math.hpp"
 
@@ -623,7 +624,12 @@ class HostGraph {
  private:
   int merge_pending();
   int64_t n_rejected = 0;                 // factors / variables refused by merge_pending since creation (slide_graph_stats)
-  int upload_new();
+  int upload_new();                       // what merge_pending added goes to the device, in four stages:
+  int upload_tails(hipStream_t s);        //   the array tails, the CSR mirrors, the linearisation buffers
+  int upload_border(hipStream_t s);       //   the exact joint step's border (plan_border, host_layout.hpp)
+  int upload_system(hipStream_t s);       //   S, the factor buffers, the tile profile (plan_tile_profile) and what it clears in S
+  int upload_view(hipStream_t s);         //   the GraphDev view, the pose adjacency, the segments' profiles, the pair lists, the slot table
+  int layout_current();                   // merge_pending + upload_new for the layout getters: 0 or the negative error
   int run_update(double relin_thr, int iterations);
   int enqueue_iteration(bool lookahead, bool skip_relin = false, int c_d = 0, int wf_cd = -1);      // one GN / iSAM2-equivalent pass on `stream`; c_d > 0: block columns below it keep their factor
   // Incremental re-factorisation (iSAM2's "re-eliminate only the affected top of the tree", graph.cpp:260-272): the lowest pose whose
@@ -729,8 +735,8 @@ class HostGraph {
   DevArr<int> d_lf_type, d_lf_pose, d_lf_lm, d_lf_slot, d_lf_nbr;
   DevArr<int64_t> d_lf_joff, d_lf_eoff;
   DevArr<long long> d_pose_ed, d_sp_pairs;
-  DevArr<int> d_sp_idx;                   // pair lists of the Schur assembly (GraphDev::sp_idx), rebuilt by upload_new for graphs in an exact joint batch
-  int build_schur_pairs(hipStream_t s);
+  DevArr<int> d_sp_idx;                   // pair lists of the Schur assembly (GraphDev::sp_idx), rebuilt by upload_view for graphs in an exact joint batch
+  int build_schur_pairs(hipStream_t s);   // plan_schur_pairs (host_layout.hpp) and its two uploads
   DevArr<unsigned> d_pose_adj;
   DevArr<double> d_br_z, d_cu_z, d_cu_sigma, d_cy_z, d_jbuf, d_ebuf;
   DevArr<int> d_lm_ptr, d_lm_fids, d_pose_ptr, d_pose_fids, d_pose_lms, d_pose_bt_ptr, d_pose_bt;
@@ -740,9 +746,9 @@ class HostGraph {
   DevArr<double> d_S, d_Ld, d_Winv, d_yv, d_dp;
   DevArr<double> d_S0, d_pcg, d_pcg_scal;              // joint solve (pcg_kernels.hip)
   DevArr<int> d_lm_slot;                               // landmark -> shared slot or -1
-  int sync_lm_slot();                                  // rebuilds it from h_sh_lid (upload_new, set_shared)
-  bool lm_slot_onto = false;                           // sync_lm_slot: lm_slot[h_sh_lid[i]] == i for every slot i that names a landmark (no two slots on one landmark, none out of range)
-  DevArr<int> d_prof, d_first;                         // tile-level profile of the reduced system (graph_dev.hpp), host copies h_prof / h_first
+  int sync_lm_slot();                                  // rebuilds it from h_sh_lid (upload_view, set_shared): plan_lm_slot (host_layout.hpp) and its upload
+  bool lm_slot_onto = false;                           // plan_lm_slot's onto: lm_slot[h_sh_lid[i]] == i for every slot i that names a landmark (no two slots on one landmark, none out of range)
+  DevArr<int> d_prof, d_first;                         // tile-level profile of the reduced system (plan_tile_profile, host_layout.hpp), host copies h_prof / h_first
   std::vector<int> h_prof, h_first;
   int prof_ver = 0;
   int joint_Tcap = 0;                                   // Tcap the joint-solve buffers (S0, L32, ctab) are allocated for; 0 = not allocated
@@ -754,22 +760,17 @@ class HostGraph {
   bool have_self = false;
   int pcg_iters = 0;
   double pcg_tol = 0.0;
-  // exact joint step: this robot's border = its shared landmarks in slot order
+  // exact joint step: this robot's border, planned by plan_border (host_layout.hpp: BorderPlan describes every table below) and moved here
   std::vector<int> h_sep_off;                          // global offsets (n_slots + 1) or empty
   std::vector<int> h_lm_bord, h_sep_map, h_bfirst;     // landmark -> border offset; global separator coordinate -> border coordinate; first column block per border tile row
   // nested dissection of the own pose chain (exact joint passes; CholBatch::set_segments)
-  struct Seg { int t0, t1; };                          // tile columns [t0, t1) of a segment
+  using Seg = sl::Seg;                                 // tile columns [t0, t1) of a segment
   std::vector<Seg> segs;
   std::vector<int> h_pose_sep;                         // pose -> border offset of a separator pose, or -1
-  std::vector<std::vector<int>> seg_prof;              // per segment: its profile in its own numbering (host; plan_step)
+  std::vector<std::vector<int>> seg_prof;              // per segment: its profile in its own numbering (plan_segment_profiles; read by plan_step)
   DevArr<int> d_pose_sep, d_seg_prof;
   std::vector<size_t> seg_prof_off;
-  // per segment: which border tile rows are non-zero in it and from which block column on (a shared landmark seen only from the first
-  // half of the trajectory has no coupling to the second segment's poses; the poses of a cut couple to the few block columns before it and
-  // to the segment behind it).  seg_ord[s]: the border tile rows in the order of that first column (the rows still all-zero at a block
-  // column are then a suffix again, per segment); seg_sfirst[s]: the first columns in that order (plan_step); seg_tab: what the border
-  // product reads — nseg, the segments' last block columns + 1, then per segment the first column of every tile row + the right-hand side
-  std::vector<std::vector<int>> seg_ord, seg_sfirst;
+  std::vector<std::vector<int>> seg_ord, seg_sfirst;   // the per-segment activity of the border rows (BorderPlan; read by plan_step)
   std::vector<int> seg_tab;
   int seg_tab_head = 0;                               // ints of seg_tab in front of the per-column activity masks
   DevArr<int> d_seg_ord, d_seg_tab;
