@@ -680,6 +680,35 @@ int slide_debug_chol_plan(int n, const int* T, const int* nbr, const int* prof, 
 /* LDS flag waits of the pair kernel (method 2) that gave up since the library was loaded: 0 unless the kernel is broken (its waits are
  * bounded so that every wave reaches the end of its launch); the tests assert 0. */
 int slide_debug_pair_timeouts(void);
+/* Unit-test hook of the border product (k_border_syrk and its reductions) on caller data: n (1 .. 8) systems AFTER their steps, handed to
+ * launch_border_syrk (jobs == NULL: the plain (ib, jb, system) grid) or launch_border_syrk_jobs (a job table of njobs codes
+ * system << 20 | ib << 10 | jb, lds_pad bytes of idle LDS per workgroup) exactly as the exact joint passes do.  Per system i: S_in holds
+ * ld[i] x T[i]*64 doubles (column-major; W^T in the nbr[i] border row tiles from tile row B0 = b0[i] > 0 ? b0[i] : T[i] on, y^T in row 0 of
+ * the tile behind them, whose rows 1 .. 63 the caller keeps zero), bord_in ldb[i] x bord_cols[i] doubles (the border block in its first
+ * (nbr + 1) * 64 rows and nbr * 64 columns; what lies beyond must come back as it was), the systems one after the other in both.
+ * bfirst / segtab are concatenated tables, bfirst_off[i] / segtab_off[i] where system i's nbr[i] + 1 first columns resp. its
+ * segtab_len[i] ints in HostGraph::seg_tab's layout (nseg, the segments' end columns, per segment nbr + 1 first columns with 1 << 30 =
+ * inactive, then the masks' head) start, or -1 for none (the offset arrays themselves may be NULL).  has_src[i] != 0: system i reads its
+ * tiles from bord_src (laid out like bord_in) and writes bord = bord_src - W W^T.  ks > 1: split K of ONE system over ks chunks of its
+ * column blocks; fuse_add != 0: the fused two-system launch (system 0's block += system 1's), ks_sys[2] (or NULL: ks for both) chunks
+ * each; jb_end >= 0: the table and the reduction stop short of tile column jb_end.  The partial tiles live in scratch the hook allocates
+ * itself at the passes' own size, (nbr + 1) * nbr * (max chunks - 1) tiles per system (two systems' for the fused launch), zeroed — or,
+ * with use_prefill != 0, filled with `prefill` (what a reused buffer may hold) — between two guard tiles of a fixed bit pattern:
+ * SLIDE_ERR_HIP when a guard was written.  bord_out / S_out (may be NULL) receive every system's block and its S (which must be
+ * unchanged).  SLIDE_ERR_INVALID, nothing launched, for what the launchers do not define: ks > 1 or the fused launch together with a
+ * segtab; fuse_add with n != 2, unequal nbr, a bfirst, no job table or no system split; ks > 1 with n > 1 and no fuse_add; an odd ld or
+ * ldb; ld < (B0 + nbr + 1) * 64; ldb < (nbr + 1) * 64; a job code that names a system >= n or, split, a tile column >= jb_end; jb_end,
+ * lds_pad or ks_sys without what they belong to; a table the kernels would read out of bounds. */
+int slide_debug_border_product(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* b0, const double* bord_in,
+                               const int* ldb, const int* bord_cols, const int* bfirst, const int* bfirst_off, const int* segtab,
+                               const int* segtab_off, const int* segtab_len, const double* bord_src, const int* has_src, const int* jobs,
+                               int njobs, int lds_pad, int ks, const int* ks_sys, int jb_end, int fuse_add, int use_prefill, double prefill,
+                               double* bord_out, double* S_out);
+/* The same for k_border_apply: yv -= W x_loc over the band's columns of n (1 .. 8) systems in ONE launch (launch_border_apply).  S_in, ld,
+ * T, nbr, b0 and the segments' tables as above (a table whose masks' head is > 0 takes the mask walk, any other the full walk); yv_in /
+ * yv_out: T[i] * 64 doubles per system, x_loc: nbr[i] * 64, each one system after the other. */
+int slide_debug_border_apply(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* b0, const double* yv_in,
+                             const double* x_loc, const int* segtab, const int* segtab_off, const int* segtab_len, double* yv_out);
 
 /* ------------------------------------------------------------------------------------------------
  * S3 — association (include/core/sloam.h:88-108, src/core/sloam.cpp:73-306; *MapManager::getSubmap)

@@ -31,7 +31,7 @@ EXPORTS = [
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
     "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_closure_info_gain_batch", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_closure_info_gain", "slide_chol_batch_closure_info_gain_batch", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
-    "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_chol_batch", "slide_debug_chol_plan", "slide_debug_pair_timeouts", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
+    "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_chol_batch", "slide_debug_chol_plan", "slide_debug_pair_timeouts", "slide_debug_border_product", "slide_debug_border_apply", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
     "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_inter_loop_closures",
@@ -1346,6 +1346,82 @@ def debug_chol_batch(systems, method=0, cu_share=100, assumed_cus=0, want_l32=Fa
                         L32=L32[lo:lo + l32_sizes[i]] if l32_sizes[i] else None))
         so, to, lo = so + sizes[i], to + t, lo + l32_sizes[i]
     return dict(systems=out, trace=trace[:nl.value].copy(), n_cu=ncu.value)
+
+
+def _border_tables(systems, key, count):
+    """One optional int table per system, end to end, with the offsets (-1: none) and lengths the C calls take."""
+    vals, off, ln = [], np.full(max(len(systems), 1), -1, np.int32), np.zeros(max(len(systems), 1), np.int32)
+    for i, s in enumerate(systems):
+        if s.get(key) is not None:
+            t = [int(x) for x in s[key]]
+            assert count is None or len(t) == count(s), key
+            off[i], ln[i] = len(vals), len(t)
+            vals += t
+    # (values above 2^31 are the high mask words: the same bits as int32)
+    return np.array(vals + [0], np.int64).astype(np.uint32).view(np.int32), off, ln
+
+
+def debug_border_product(systems, jobs=None, lds_pad=0, ks=1, ks_sys=None, jb_end=-1, fuse_add=False, prefill=None):
+    """slide_debug_border_product: the border product of n systems after their steps (dicts with S, ld, T, nbr, bord, ldb and optionally
+    b0, bord_cols (columns of the bord buffer, default nbr * 64), bfirst (nbr + 1 ints), segtab (HostGraph::seg_tab's flat layout),
+    bord_src) through launch_border_syrk (jobs None) or launch_border_syrk_jobs (jobs: codes system << 20 | ib << 10 | jb).  prefill: the
+    value the split-K scratch holds in place of zero.  Returns [dict(bord, S)], flat as given.  Raises SlideError (code -1) for a
+    combination the launchers do not define."""
+    n = len(systems)
+    col = lambda key, dflt=None: np.array([int(s[key] if s.get(key) is not None else dflt(s)) for s in systems] or [0], np.int32)
+    ld, T, nbr, b0, ldb = col("ld"), col("T"), col("nbr"), col("b0", lambda s: 0), col("ldb")
+    cols = col("bord_cols", lambda s: s["nbr"] * 64)
+    S = np.concatenate([np.ascontiguousarray(s["S"], dtype=np.float64).ravel() for s in systems])
+    bord = np.concatenate([np.ascontiguousarray(s["bord"], dtype=np.float64).ravel() for s in systems])
+    s_sz = [int(ld[i]) * int(T[i]) * 64 for i in range(n)]
+    b_sz = [int(ldb[i]) * int(cols[i]) for i in range(n)]
+    assert all(np.size(s["S"]) == z for s, z in zip(systems, s_sz)) and all(np.size(s["bord"]) == z for s, z in zip(systems, b_sz))
+    bf, bf_off, _ = _border_tables(systems, "bfirst", lambda s: s["nbr"] + 1)
+    sg, sg_off, sg_len = _border_tables(systems, "segtab", None)
+    has_src = np.array([1 if s.get("bord_src") is not None else 0 for s in systems], np.int32)
+    src = None
+    if has_src.any():
+        src = np.concatenate([np.ascontiguousarray(s["bord_src"] if s.get("bord_src") is not None else np.zeros(z), dtype=np.float64).ravel()
+                              for s, z in zip(systems, b_sz)])
+        assert src.size == bord.size
+    jb = None if jobs is None else np.ascontiguousarray(jobs, dtype=np.int32)
+    kk = None if ks_sys is None else np.ascontiguousarray(ks_sys, dtype=np.int32)
+    assert kk is None or kk.size == 2
+    pp = lambda a: None if a is None else _p(a)
+    bo, So = np.zeros_like(bord), np.zeros_like(S)
+    rc = lib().slide_debug_border_product(C.c_int(n), _p(S), _p(ld), _p(T), _p(nbr), _p(b0), _p(bord), _p(ldb), _p(cols), _p(bf), _p(bf_off),
+                                          _p(sg), _p(sg_off), _p(sg_len), pp(src), _p(has_src), pp(jb), C.c_int(0 if jb is None else jb.size),
+                                          C.c_int(lds_pad), C.c_int(ks), pp(kk), C.c_int(jb_end), C.c_int(1 if fuse_add else 0),
+                                          C.c_int(0 if prefill is None else 1), C.c_double(0.0 if prefill is None else prefill), _p(bo), _p(So))
+    if rc != SLIDE_OK:
+        err = SlideError(f"{ERR.get(rc, rc)}: {last_error()}")
+        err.code = rc
+        raise err
+    out, so, bo_ = [], 0, 0
+    for i in range(n):
+        out.append(dict(bord=bo[bo_:bo_ + b_sz[i]], S=So[so:so + s_sz[i]]))
+        so, bo_ = so + s_sz[i], bo_ + b_sz[i]
+    return out
+
+
+def debug_border_apply(systems):
+    """slide_debug_border_apply: yv -= W x_loc of n systems (dicts with S, ld, T, nbr, yv (T * 64), x_loc (nbr * 64) and optionally b0,
+    segtab) in one launch_border_apply.  Returns the systems' yv."""
+    n = len(systems)
+    col = lambda key: np.array([int(s.get(key) or 0) for s in systems] or [0], np.int32)
+    ld, T, nbr, b0 = col("ld"), col("T"), col("nbr"), col("b0")
+    cat = lambda key: np.concatenate([np.ascontiguousarray(s[key], dtype=np.float64).ravel() for s in systems])
+    S, yv, x = cat("S"), cat("yv"), cat("x_loc")
+    assert S.size == int((ld.astype(np.int64) * T * 64)[:n].sum()) and yv.size == int(T[:n].sum()) * 64 and x.size == int(nbr[:n].sum()) * 64
+    sg, sg_off, sg_len = _border_tables(systems, "segtab", None)
+    out = np.zeros_like(yv)
+    rc = lib().slide_debug_border_apply(C.c_int(n), _p(S), _p(ld), _p(T), _p(nbr), _p(b0), _p(yv), _p(x), _p(sg), _p(sg_off), _p(sg_len), _p(out))
+    if rc != SLIDE_OK:
+        err = SlideError(f"{ERR.get(rc, rc)}: {last_error()}")
+        err.code = rc
+        raise err
+    offs = np.concatenate([[0], np.cumsum(T[:n].astype(np.int64) * 64)])
+    return [out[offs[i]:offs[i + 1]] for i in range(n)]
 
 
 # ---- stand-alone association / place recognition ---------------------------------------------------------

@@ -745,6 +745,158 @@ int slide_debug_chol_batch(int n, const double* S_in, const int* ld, const int* 
   return SLIDE_OK;
 }
 
+// ---- the border product and its apply on caller data (slide_gpu.h) ---------------------------------------------------------------------
+// A segments' table as the kernels index it (HostGraph::seg_tab): nseg, nseg end columns, nseg x (nbr + 1) first columns, then the masks'
+// head (0, or Tb >= T and Tb x (low, high) words with no bit at or above nbr).  What the kernels would read out of bounds is refused here.
+static bool debug_segtab_ok(const int* st, int len, int T, int nbr) {
+  if (!st || len < 2 || st[0] < 1) return false;
+  const int nseg = st[0];
+  const long long head = 1 + (long long)nseg + (long long)nseg * (nbr + 1);
+  if (len < head + 1) return false;
+  for (int q = 0; q < nseg; ++q)
+    if (st[1 + q] < 0 || st[1 + q] > T) return false;
+  for (long long e = 1 + nseg; e < head; ++e)
+    if (st[e] < 0) return false;
+  const int Tb = st[head];
+  if (Tb == 0) return true;
+  if (Tb < T || len < head + 1 + 2LL * Tb) return false;
+  for (int c = 0; c < Tb; ++c) {
+    const unsigned long long m = (unsigned long long)(unsigned)st[head + 1 + 2 * c] | ((unsigned long long)(unsigned)st[head + 2 + 2 * c] << 32);
+    if (nbr < 64 && (m >> nbr)) return false;
+  }
+  return true;
+}
+// what both entries check of a system's shape (the launchers index S by it)
+static bool debug_border_shape_ok(int ld, int T, int nbr, int b0) {
+  if (T < 1 || nbr < 1 || nbr > 1023 || b0 < 0 || (b0 > 0 && b0 < T) || (ld & 1)) return false;
+  return ld >= ((b0 > 0 ? b0 : T) + nbr + 1) * NB;
+}
+constexpr unsigned long long BORDER_GUARD = 0x7FF8B0DE5C4A7C11ull;      // a quiet-NaN payload in the tiles around the scratch: no partial product equals it
+int slide_debug_border_product(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* b0, const double* bord_in,
+                               const int* ldb, const int* bord_cols, const int* bfirst, const int* bfirst_off, const int* segtab,
+                               const int* segtab_off, const int* segtab_len, const double* bord_src, const int* has_src, const int* jobs,
+                               int njobs, int lds_pad, int ks, const int* ks_sys, int jb_end, int fuse_add, int use_prefill, double prefill,
+                               double* bord_out, double* S_out) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (n < 1 || n > CHOL_BATCH_HOST_MAX || !S_in || !ld || !T || !nbr || !bord_in || !ldb || !bord_cols || ks < 1 || ks > 64 || lds_pad < 0 || lds_pad > 65536) return SLIDE_ERR_INVALID;
+  if ((jobs && njobs < 1) || (!jobs && (fuse_add || jb_end >= 0 || lds_pad > 0)) || (ks_sys && !fuse_add)) return SLIDE_ERR_INVALID;
+  bool any_seg = false, any_bfirst = false;
+  std::vector<size_t> s_off(n + 1, 0), b_off(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (!debug_border_shape_ok(ld[i], T[i], nbr[i], b0 ? b0[i] : 0)) return SLIDE_ERR_INVALID;
+    if ((ldb[i] & 1) || ldb[i] < (nbr[i] + 1) * NB || bord_cols[i] < nbr[i] * NB) return SLIDE_ERR_INVALID;
+    if (bfirst_off && bfirst_off[i] >= 0) {
+      if (!bfirst) return SLIDE_ERR_INVALID;
+      for (int j = 0; j <= nbr[i]; ++j)
+        if (bfirst[bfirst_off[i] + j] < 0) return SLIDE_ERR_INVALID;
+      any_bfirst = true;
+    }
+    if (segtab_off && segtab_off[i] >= 0) {
+      if (!segtab || !segtab_len || !debug_segtab_ok(segtab + segtab_off[i], segtab_len[i], T[i], nbr[i])) return SLIDE_ERR_INVALID;
+      any_seg = true;
+    }
+    if (has_src && has_src[i] && !bord_src) return SLIDE_ERR_INVALID;
+    s_off[i + 1] = s_off[i] + (size_t)ld[i] * T[i] * NB;
+    b_off[i + 1] = b_off[i] + (size_t)ldb[i] * bord_cols[i];
+  }
+  int ka = ks, kb = ks;
+  if (fuse_add) {      // (launch_border_syrk_jobs: two systems with the same border, each with its own number of chunks)
+    if (n != 2 || nbr[0] != nbr[1] || any_bfirst) return SLIDE_ERR_INVALID;
+    if (ks_sys) { ka = ks_sys[0]; kb = ks_sys[1]; }
+    if (ka < 1 || kb < 1 || ka > 64 || kb > 64) return SLIDE_ERR_INVALID;
+  }
+  const int km = std::max(ka, kb);
+  if (fuse_add && km < 2) return SLIDE_ERR_INVALID;      // (without scratch the launcher would run the plain table launch and add nothing)
+  if (km > 1 && (any_seg || (n > 1 && !fuse_add))) return SLIDE_ERR_INVALID;
+  if (jobs) {
+    if (jb_end == 0 || jb_end > nbr[0]) return SLIDE_ERR_INVALID;
+    for (int j = 0; j < njobs; ++j) {
+      if (jobs[j] < 0 || (jobs[j] >> 20) >= n) return SLIDE_ERR_INVALID;
+      if (jb_end >= 0 && km > 1 && (jobs[j] & 1023) >= jb_end) return SLIDE_ERR_INVALID;      // (a partial the reduction would never add)
+    }
+  }
+  Tmp Tm;
+  std::vector<CholSystem> sys(n, CholSystem{});
+  for (int i = 0; i < n; ++i) {
+    CholSystem& cs = sys[i];
+    cs.ld = ld[i]; cs.T = T[i]; cs.nbr = nbr[i]; cs.b0 = b0 ? b0[i] : 0; cs.ldb = ldb[i];
+    cs.S = Tm.up(S_in + s_off[i], s_off[i + 1] - s_off[i]);
+    cs.bord = Tm.up(bord_in + b_off[i], b_off[i + 1] - b_off[i]);
+    bool ok = cs.S && cs.bord;
+    if (bfirst_off && bfirst_off[i] >= 0) { cs.bfirst = Tm.up(bfirst + bfirst_off[i], (size_t)nbr[i] + 1); ok = ok && cs.bfirst; }
+    if (segtab_off && segtab_off[i] >= 0) { cs.segtab = Tm.up(segtab + segtab_off[i], (size_t)segtab_len[i]); ok = ok && cs.segtab; }
+    if (has_src && has_src[i]) { cs.bord_src = Tm.up(bord_src + b_off[i], b_off[i + 1] - b_off[i]); ok = ok && cs.bord_src; }
+    if (!ok) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  }
+  int* d_jobs = jobs ? Tm.up(jobs, (size_t)njobs) : nullptr;
+  if (jobs && !d_jobs) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  // the partial tiles, exactly as many as HostGraph allocates, between two guard tiles
+  const size_t tile = (size_t)NB * NB, body = (size_t)(nbr[0] + 1) * nbr[0] * (km - 1) * (fuse_add ? 2 : 1) * tile;
+  double* d_scr = nullptr;
+  if (km > 1) {
+    std::vector<double> h(body + 2 * tile, use_prefill ? prefill : 0.0);
+    double guard;
+    std::memcpy(&guard, &BORDER_GUARD, sizeof(guard));
+    std::fill(h.begin(), h.begin() + tile, guard);
+    std::fill(h.end() - tile, h.end(), guard);
+    d_scr = Tm.up(h.data(), h.size());
+    if (!d_scr) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  }
+  SL_HIP(hipDeviceSynchronize());
+  double* scratch = d_scr ? d_scr + tile : nullptr;
+  if (jobs) launch_border_syrk_jobs(sys.data(), n, d_jobs, njobs, lds_pad, nullptr, scratch, ks, jb_end, fuse_add ? ks_sys : nullptr, fuse_add != 0);
+  else launch_border_syrk(sys.data(), n, nullptr, scratch, ks);
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  if (d_scr) {
+    std::vector<unsigned long long> g(2 * tile);
+    SL_HIP(hipMemcpy(g.data(), d_scr, tile * sizeof(double), hipMemcpyDeviceToHost));
+    SL_HIP(hipMemcpy(g.data() + tile, d_scr + tile + body, tile * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < 2 * tile; ++e)
+      if (g[e] != BORDER_GUARD) {
+        g_last_error = std::string("border product: the guard tile ") + (e < tile ? "in front of" : "behind") + " the scratch was written at element " + std::to_string(e % tile);
+        return SLIDE_ERR_HIP;
+      }
+  }
+  for (int i = 0; i < n; ++i) {
+    if (bord_out) SL_HIP(hipMemcpy(bord_out + b_off[i], sys[i].bord, (b_off[i + 1] - b_off[i]) * sizeof(double), hipMemcpyDeviceToHost));
+    if (S_out) SL_HIP(hipMemcpy(S_out + s_off[i], sys[i].S, (s_off[i + 1] - s_off[i]) * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return SLIDE_OK;
+}
+int slide_debug_border_apply(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* b0, const double* yv_in,
+                             const double* x_loc, const int* segtab, const int* segtab_off, const int* segtab_len, double* yv_out) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (n < 1 || n > CHOL_BATCH_HOST_MAX || !S_in || !ld || !T || !nbr || !yv_in || !x_loc || !yv_out) return SLIDE_ERR_INVALID;
+  std::vector<size_t> s_off(n + 1, 0), y_off(n + 1, 0), x_off(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (!debug_border_shape_ok(ld[i], T[i], nbr[i], b0 ? b0[i] : 0)) return SLIDE_ERR_INVALID;
+    if (segtab_off && segtab_off[i] >= 0 && (!segtab || !segtab_len || !debug_segtab_ok(segtab + segtab_off[i], segtab_len[i], T[i], nbr[i]))) return SLIDE_ERR_INVALID;
+    s_off[i + 1] = s_off[i] + (size_t)ld[i] * T[i] * NB;
+    y_off[i + 1] = y_off[i] + (size_t)T[i] * NB;
+    x_off[i + 1] = x_off[i] + (size_t)nbr[i] * NB;
+  }
+  Tmp Tm;
+  std::vector<CholSystem> sys(n, CholSystem{});
+  std::vector<const double*> xl(n);
+  for (int i = 0; i < n; ++i) {
+    CholSystem& cs = sys[i];
+    cs.ld = ld[i]; cs.T = T[i]; cs.nbr = nbr[i]; cs.b0 = b0 ? b0[i] : 0;
+    cs.S = Tm.up(S_in + s_off[i], s_off[i + 1] - s_off[i]);
+    cs.yv = Tm.up(yv_in + y_off[i], y_off[i + 1] - y_off[i]);
+    xl[i] = Tm.up(x_loc + x_off[i], x_off[i + 1] - x_off[i]);
+    bool ok = cs.S && cs.yv && xl[i];
+    if (segtab_off && segtab_off[i] >= 0) { cs.segtab = Tm.up(segtab + segtab_off[i], (size_t)segtab_len[i]); ok = ok && cs.segtab; }
+    if (!ok) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  }
+  SL_HIP(hipDeviceSynchronize());
+  launch_border_apply(sys.data(), n, xl.data(), nullptr);
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  for (int i = 0; i < n; ++i) SL_HIP(hipMemcpy(yv_out + y_off[i], sys[i].yv, (y_off[i + 1] - y_off[i]) * sizeof(double), hipMemcpyDeviceToHost));
+  return SLIDE_OK;
+}
+
 // ---- stand-alone association ------------------------------------------------------------------------
 
 // One class through the frame kernel on caller buffers.  n_cur == 0: pure K-NN gate at `qpos` (cloud = AoS float xyz, as the caller

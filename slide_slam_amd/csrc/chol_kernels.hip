@@ -2773,7 +2773,11 @@ __device__ __forceinline__ void border_syrk_body(const SyrkArgs& A) {
   const double* S = A.S[r];
   const int wq = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
   const int ch = (wq >> 1) & 1, rh = wq & 1;      // column half, row half of the tile
-  if (A.jobs && ib == nbr && rh == 1 && !bsrc) return;     // right-hand-side row tile: only its first row is in use (the others are zero and stay zero)
+  // right-hand-side row tile: only its first row is in use, so a table launch leaves rows 32 .. 63 alone — in bord and in the chunks'
+  // partials.  The reductions add those rows of the partials all the same: they take whatever the scratch holds there (zero only while
+  // the buffer is used with one ks; lam_scratch is not), which is harmless because nothing reads beyond row 0 of that tile
+  // (k_lam_prepare, k_sep_top_add, k_chol_extract_y; the step kernels keep a tile's rows apart) — tests/test_gpu_border_product.py pins it
+  if (A.jobs && ib == nbr && rh == 1 && !bsrc) return;
   const int B0 = A.b0[r];
   const double* pj0 = S + (size_t)lk * ld + (size_t)(B0 + jb) * NB + 32 * ch + 2 * lr;
   const double* pi0 = S + (size_t)lk * ld + (size_t)(B0 + ib) * NB + 32 * rh + 2 * lr;

@@ -974,7 +974,7 @@ int CholBatch::prepare_separator() {
       const size_t nb = (size_t)(sep_nl + 1) * NB * sep_nl * NB;
       SL_HIP(hipMalloc(reinterpret_cast<void**>(&sep_bord), nb * sizeof(double)));
       if (lam_ks_cap(sep_nl) > 1)
-        SL_HIP(hipMalloc(reinterpret_cast<void**>(&lam_scratch), 2 * (size_t)(sep_nl + 1) * sep_nl * (lam_ks_cap(sep_nl) - 1) * NB * NB * sizeof(double)));      // (x 2: both leaves' partial tiles in one launch)
+        SL_HIP(hipMalloc(reinterpret_cast<void**>(&lam_scratch), 2 * (size_t)(sep_nl + 1) * sep_nl * (lam_ks_cap(sep_nl) - 1) * NB * NB * sizeof(double)));      // (x 2: both leaves' partial tiles in one launch; not zeroed, and used with several ks in one pass: the fused table launch's reduction reads the never-written idle half of the right-hand-side tiles' partials into rows 32 .. 63 of sep_bord's right-hand-side tiles, which nothing reads — k_border_syrk)
       {
         std::vector<int> codes;      // the lambda block's tiles + right-hand-side row, for both leaves as two systems (launch_border_syrk_jobs)
         for (int sy = 0; sy < 2; ++sy)
