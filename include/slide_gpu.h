@@ -794,6 +794,24 @@ slide_graph_t* slide_backend_graph(slide_backend_t* b);                    /* bo
 int slide_backend_counts(slide_backend_t* b, uint64_t out4[4], uint64_t* pose_counters, int n_robots);
 /* map model read-back (getRawMap): cylinder -> 7 doubles; cube / ellipsoid -> xyz + scale (6 doubles) */
 int slide_backend_map_model(slide_backend_t* b, int cls, int idx, double* out, int* hits, int* label);
+/* The association gate of the streaming path: a frame's matches tested at the PREDICTED pose before they are added.  No counterpart in
+ * the reference, which accepts a match on its Euclidean threshold alone (sloam.cpp:73-203).  Off by default (prob == 0): a back-end
+ * that never calls this, or calls it with 0, launches what it launched and gives the bits it gave.
+ * With 0 < prob < 1 the gate runs in slide_backend_process_frame for SLIDE_FRAME_HOST / _HOST_DEFERRED frames of a robot whose
+ * pose counter is > 0, after the association kernel's read-back and before the map is updated: every matched detection becomes a
+ * candidate of slide_graph_predicted_observation_mahalanobis (from pose = pose counter - 1, rel7 and est7 = prev * rel of the frame,
+ * the matched landmark id, the measurement the frame would add), ONE call tests them, and a candidate with status 0 and
+ * d2 > slide_chi2_quantile(prob, dof) is rejected: SLIDE_GATE_DROP — no factor, no hit, no map entry, *_id[i] = -1; SLIDE_GATE_NEW —
+ * treated as unmatched: a new map entry and a new landmark.  Either way *_match[i] = SLIDE_MATCH_GATED.  A candidate whose status
+ * is not 0 keeps its match.  Where the query is refused for the graph's state (frames added since the last solve, for example a
+ * foreign packet not yet solved), the frame is associated ungated and counted as skipped; so is the robot's first frame, which has
+ * no from pose.  A SLIDE_FRAME_FOREIGN frame is neither tested nor counted.  SLIDE_ERR_INVALID: b NULL, prob outside [0, 1) or not a number, on_reject neither value. */
+#define SLIDE_GATE_DROP 0
+#define SLIDE_GATE_NEW 1
+#define SLIDE_MATCH_GATED (-2)
+int slide_backend_set_association_gate(slide_backend_t* b, double prob, int on_reject);
+/* {frames gated, frames skipped, candidates tested, candidates rejected} since the back-end was created, counted while the gate is on */
+int slide_backend_gate_stats(slide_backend_t* b, int64_t out4[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * S4 — inter-robot map-to-map association
@@ -1102,6 +1120,32 @@ int slide_graph_closure_mahalanobis(slide_graph_t* g, int L, const int32_t* from
 int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls,
                                         const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof /* may be NULL */,
                                         double* C81 /* may be NULL */, double* r9 /* may be NULL */, int32_t* status /* may be NULL */);
+/* slide_graph_observation_mahalanobis at a PREDICTED pose: "is this match compatible, before I add it", as an EKF gates at the
+ * predicted state.  No counterpart in the reference, whose association accepts a match at poseEstimate = prev * rel on a Euclidean
+ * threshold alone (sloam.cpp:73-203), and none in GTSAM short of adding the pose and its factor and taking
+ * Marginals::jointMarginalCovariance on the grown graph.
+ * Let pose k = (robot, from_idx) be in the graph with estimate X_k, X_n = est7 the predicted pose and rel7 the odometry step whose
+ * Between factor slide_graph_add_keypose_between(g, robot, from_idx, ., rel7, est7) would add, with that call's sigmas
+ * s = noise_model_odom_vec x max(|t_rel|, noise_floor).  The solver linearises that factor as H_F = -diag(1 / s) Ad,
+ * H_T = diag(1 / s), Ad = Ad(X_n^-1 X_k); the new pose touches nothing else, so the marginal of the augmented graph is
+ * Sig(n, .) = Ad Sig(k, .), Sig(n, n) = Ad Sig(k, k) Ad^T + diag(s^2); the Between's residual does not enter.  Candidate i is the
+ * observation from X_n of the EXISTING landmark (cls[i], lm_idx[i]) that slide_graph_add_range_bearing / _add_cube / _add_cylinder
+ * would add; meas17 as for slide_graph_observation_mahalanobis; r and A = [Ap | Al] its whitened residual and Jacobian at
+ * (X_n, the landmark's estimate) by the solver's text for the class, no robust weight.  Then
+ *     C  = I + Al H_ll^-1 Al^T + Ap diag(s^2) Ap^T + B^T S^-1 B,   B = P_k^T (Ap Ad)^T - sum_{f in factors(l)} P_{p_f}^T F_f Al^T,
+ *     d2 = r^T C^-1 r:
+ * exactly what slide_graph_observation_mahalanobis would return on the graph extended by the pose and its Between factor, linearised
+ * at those values, chi-square with dof = 3 / 9 / 7 for a true match — with no add, no factorisation and no change to the graph.  No
+ * threshold is applied.  Outputs, sweeps (128 / 42 / 54 candidates) and status words are that call's; a sweep's walk starts at the
+ * block column of min(pose k, the landmarks' first observers); a candidate's bits do not depend on the rest of the list.
+ * Whole-call refusals decided before the graph is looked at (SLIDE_ERR_INVALID, nothing written, the message names
+ * predicted_observation_mahalanobis): that call's argument checks, rel7 or est7 NULL or non-finite, a zero quaternion, the graph is
+ * NULL.  Then SLIDE_MISSING for a from pose the graph does not hold (nothing written), then the refusals of
+ * slide_graph_get_pose_covariances.  Per candidate: SLIDE_MISSING (a landmark the graph does not hold), SLIDE_ERR_NOT_SPD. */
+int slide_graph_predicted_observation_mahalanobis(slide_graph_t* g, int robot, uint64_t from_idx, const double rel7[7], const double est7[7], int n,
+                                                  const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double* d2,
+                                                  int32_t* dof /* may be NULL */, double* C81 /* may be NULL */, double* r9 /* may be NULL */,
+                                                  int32_t* status /* may be NULL */);
 /* The JOINT compatibility of a key frame's landmark matches: Neira and Tardos' joint compatibility test in its greedy sequential form
  * (the sequential compatibility nearest neighbour), on the single graph.  No counterpart in the reference; GTSAM users would stack the
  * hypothesis' factors and take Marginals::jointMarginalCovariance over all their variables.  A frame proposes its matches at once, all

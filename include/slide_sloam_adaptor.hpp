@@ -373,6 +373,35 @@ class SemanticFactorGraph {
     d2.resize(n);
     return d2;
   }
+  // The same gate at a PREDICTED pose (slide_graph_predicted_observation_mahalanobis; no counterpart in the reference, which matches
+  // at poseEstimate = prevKeyPose * relativeMotion on a Euclidean threshold alone): "is this match compatible, before I add it".
+  // predictedPose is the value addKeyPoseAndBetween(fromIdx, fromIdx + 1, relativeMotion, predictedPose, robotID) would give the new
+  // pose; neither it nor anything else is added.  The candidates are observationMahalanobis's, their robot and poseIdx fields ignored:
+  // every one sits at the predicted pose.  d2[k] is what observationMahalanobis would return on the graph extended by the pose and
+  // its Between factor.  Returns false, d2 untouched, when the graph does not hold the from pose (SLIDE_MISSING).
+  template <class Pose>
+  bool predictedObservationMahalanobis(const size_t fromIdx, const Pose& relativeMotion, const Pose& predictedPose, const int& robotID,
+                                       const std::vector<ObservationCandidate>& candidates, std::vector<double>& d2,
+                                       std::vector<int32_t>* dof = nullptr, std::vector<int32_t>* status = nullptr) const {
+    const size_t n = candidates.size();
+    double r[7], p[7]; detail::to7(relativeMotion, r); detail::to7(predictedPose, p);
+    std::vector<double> meas(17 * n + 1), out(n + 1, 0.0);
+    std::vector<int32_t> cls(n + 1), df(n + 1, 0), st(n + 1, 0);
+    std::vector<uint64_t> li(n + 1);
+    for (size_t k = 0; k < n; ++k) {
+      const ObservationCandidate& c = candidates[k];
+      cls[k] = (int32_t)c.cls; li[k] = c.lmIdx;
+      for (int i = 0; i < 17; ++i) meas[17 * k + i] = c.meas[i];
+    }
+    const int rc = slide_graph_predicted_observation_mahalanobis(g_, robotID, fromIdx, r, p, (int)n, cls.data(), li.data(), meas.data(), out.data(),
+                                                                 df.data(), nullptr, nullptr, st.data());
+    detail::check(rc, "predictedObservationMahalanobis");
+    if (rc == SLIDE_MISSING) return false;
+    if (dof) dof->assign(df.begin(), df.begin() + n);
+    if (status) status->assign(st.begin(), st.begin() + n);
+    d2.assign(out.begin(), out.begin() + n);
+    return true;
+  }
   // Duplicate landmarks: are landmarks a and b of one class the same object mapped twice (slide_graph_landmark_pair_mahalanobis; no
   // counterpart in the reference, whose association never compares two landmarks of the map)?  cls: SLIDE_CLS_ELLIPSOID (sigma: 3
   // entries) or SLIDE_CLS_CYLINDER (7, tangent order [ray, root, radius]); cubes are refused.  d2[k] = r^T C^-1 r of pair k with
@@ -631,6 +660,19 @@ class SemanticFactorGraphWrapper : public SemanticFactorGraph {
     return robotID >= 0 && robotID < SLIDE_MAX_ROBOTS ? (size_t)pc[robotID] : 0;
   }
   slide_backend_t* backend() const { return b_; }
+  // The association gate (slide_backend_set_association_gate; no counterpart in the reference): with 0 < prob < 1 addSLOAMObservation
+  // tests every match of a host frame at the predicted pose (predictedObservationMahalanobis) before it is added and rejects those
+  // above the prob quantile — onReject SLIDE_GATE_DROP: the detection is left out (its *_match SLIDE_MATCH_GATED, its *_id -1),
+  // SLIDE_GATE_NEW: it becomes a new landmark (its *_match SLIDE_MATCH_GATED).  prob 0, the default state: off.
+  void setAssociationGate(const double prob, const int onReject = SLIDE_GATE_DROP) {
+    detail::check(slide_backend_set_association_gate(b_, prob, onReject), "setAssociationGate");
+  }
+  // {frames gated, frames skipped, candidates tested, candidates rejected}
+  std::array<int64_t, 4> gateStats() const {
+    std::array<int64_t, 4> out{};
+    detail::check(slide_backend_gate_stats(b_, out.data()), "gateStats");
+    return out;
+  }
 
   // ---- the reference's own S2 signatures (graphWrapper.h:82-122) over the S1 entry points --------------------------------------
   // For a caller that keeps the reference's map managers and association (RunSloam, *MapManager::updateMap) on the host and hands

@@ -21,6 +21,8 @@ ERR = {-1: "SLIDE_ERR_INVALID", -2: "SLIDE_ERR_NOT_SPD", -3: "SLIDE_ERR_CAPACITY
 CHART_CAYLEY, CHART_EXPMAP = 0, 1
 CLS_CYLINDER, CLS_CUBE, CLS_ELLIPSOID = 0, 1, 2
 FRAME_HOST, FRAME_HOST_DEFERRED, FRAME_FOREIGN = 0, 1, 2
+GATE_DROP, GATE_NEW = 0, 1      # SLIDE_GATE_*: what SlideBackend.set_association_gate does with a rejected match
+MATCH_GATED = -2                # SLIDE_MATCH_GATED: *_match of a detection whose match the association gate rejected
 
 # every symbol include/slide_gpu.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
@@ -53,6 +55,7 @@ EXPORTS = [
     "slide_graph_landmark_pair_mahalanobis", "slide_graph_get_landmark_pair_covariances", "slide_pairs_within",
     "slide_graph_landmark_pairs_within", "slide_graph_merge_landmarks", "slide_graph_landmark_alias", "slide_graph_merge_timing",
     "slide_chol_batch_landmark_pair_mahalanobis", "slide_chol_batch_get_landmark_pair_covariances", "slide_chol_batch_landmark_pairs_within",
+    "slide_graph_predicted_observation_mahalanobis", "slide_backend_set_association_gate", "slide_backend_gate_stats",
 ]
 
 
@@ -520,6 +523,23 @@ class SlideGraph:
         d2, dof, Cm, r, status = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9)), np.zeros(k, np.int32)
         _check(self.L.slide_graph_observation_mahalanobis(self.h, C.c_int(n), _p(robot), _p(pidx), _p(cls), _p(lidx), _p(meas), _p(d2),
                                                           _p(dof), _p(Cm), _p(r), _p(status)))
+        return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
+
+    def predicted_observation_mahalanobis(self, robot, from_idx, rel7, est7, candidates):
+        """slide_graph_predicted_observation_mahalanobis: observation_mahalanobis at a PREDICTED pose — est7, the value
+        add_keypose_between(robot, from_idx, ., rel7, est7) would give a new pose — before that pose or anything else is added: the
+        gate that call would compute on the graph extended by the pose and its Between factor.  candidates: the tuples
+        observation_mahalanobis takes; their robot and pose_idx fields are IGNORED (every candidate sits at the predicted pose), so
+        a frame's list can be passed to either call.  Returns that call's dict.  Raises SlideError("SLIDE_MISSING...") when the
+        graph does not hold the from pose."""
+        n, k, _, _, cls, lidx, meas, _ = _observation_arrays(candidates, False)
+        d2, dof, Cm, r, status = np.zeros(k), np.zeros(k, np.int32), np.zeros((k, 9, 9)), np.zeros((k, 9)), np.zeros(k, np.int32)
+        rc = self.L.slide_graph_predicted_observation_mahalanobis(self.h, C.c_int(robot), C.c_uint64(from_idx), _p(_d(rel7)), _p(_d(est7)),
+                                                                  C.c_int(n), _p(cls), _p(lidx), _p(meas), _p(d2), _p(dof), _p(Cm), _p(r),
+                                                                  _p(status))
+        if rc == SLIDE_MISSING:
+            raise SlideError(f"SLIDE_MISSING: {last_error()}")
+        _check(rc)
         return {"d2": d2[:n], "dof": dof[:n], "status": status[:n], "C": Cm[:n], "r": r[:n]}
 
     @staticmethod
@@ -1212,6 +1232,21 @@ class SlideBackend:
             _check(rc)
         return dict(status=int(rc), pose7=np.array(R.out_pose7[:]), cyl_match=cm, cube_match=bm, ell_match=em,
                     cyl_id=cid, cube_id=bid, ell_id=eid, t_assoc=R.ms_association * 1e-3, t_graph=R.ms_graph * 1e-3)
+
+    def set_association_gate(self, prob, on_reject="drop"):
+        """slide_backend_set_association_gate: with 0 < prob < 1, process_frame tests every match of a host frame at the predicted
+        pose (SlideGraph.predicted_observation_mahalanobis) before it is added and rejects those with d2 above chi2_quantile(prob,
+        dof): on_reject "drop" leaves the detection out (its *_match MATCH_GATED, its *_id -1), "new" makes it a new landmark (its
+        *_match MATCH_GATED).  prob 0 (the default state) turns the gate off."""
+        if on_reject not in ("drop", "new"):
+            raise SlideError(f"set_association_gate: on_reject is {on_reject!r}, not 'drop' or 'new'")
+        _check(self.L.slide_backend_set_association_gate(self.h, C.c_double(prob), C.c_int(GATE_NEW if on_reject == "new" else GATE_DROP)))
+
+    def gate_stats(self):
+        """slide_backend_gate_stats: dict(frames_gated, frames_skipped, tested, rejected)."""
+        out = np.zeros(4, np.int64)
+        _check(self.L.slide_backend_gate_stats(self.h, _p(out)))
+        return dict(frames_gated=int(out[0]), frames_skipped=int(out[1]), tested=int(out[2]), rejected=int(out[3]))
 
     def ingest_solve(self):
         return self.L.slide_backend_ingest_solve(self.h)

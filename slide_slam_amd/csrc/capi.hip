@@ -1091,6 +1091,23 @@ int slide_backend_map_model(slide_backend_t* b, int cls, int idx, double* out, i
   BLOCK(b);
   return b->b.map_model(cls, idx, out, hits, label);
 }
+// The association gate of the streaming path (host_backend.hip, gate_frame): prob == 0 turns it off
+int slide_backend_set_association_gate(slide_backend_t* b, double prob, int on_reject) {
+  if (!b) { g_last_error = "set_association_gate: the back-end is NULL"; return SLIDE_ERR_INVALID; }
+  if (!(prob >= 0.0 && prob < 1.0)) { g_last_error = "set_association_gate: prob is neither 0 (off) nor inside (0, 1)"; return SLIDE_ERR_INVALID; }
+  if (on_reject != SLIDE_GATE_DROP && on_reject != SLIDE_GATE_NEW) {
+    g_last_error = "set_association_gate: on_reject is neither SLIDE_GATE_DROP nor SLIDE_GATE_NEW";
+    return SLIDE_ERR_INVALID;
+  }
+  BLOCK(b);
+  return b->b.set_association_gate(prob, on_reject);
+}
+int slide_backend_gate_stats(slide_backend_t* b, int64_t out4[4]) {
+  if (!b || !out4) { g_last_error = "gate_stats: a NULL pointer"; return SLIDE_ERR_INVALID; }
+  BLOCK(b);
+  for (int i = 0; i < 4; ++i) out4[i] = b->b.gate_stats[i];
+  return SLIDE_OK;
+}
 
 int slide_backend_landmark_table(slide_backend_t* b, int cls, double* xyz, int32_t* label, int cap) {
   if (!b || cls < 0 || cls > 2) return SLIDE_ERR_INVALID;

@@ -41,6 +41,7 @@ int HostBackend::associate(const SE3& poseEstimate, const slide_detections_t& de
     A.det_world[c].resize((size_t)nd[c] * dstride[c]);
     A.match_sub[c].assign(nd[c], -1);
     A.match_map[c].assign(nd[c], -1);
+    A.gated[c].assign(nd[c], FrameAssoc::GATED_NO);
   }
   for (int i = 0; i < det.n_cyl; ++i) {
     double* o = &A.det_body[0][7 * (size_t)i];
@@ -102,11 +103,90 @@ int HostBackend::associate(const SE3& poseEstimate, const slide_detections_t& de
     firstScan = false;
     for (int c = 0; c < 3; ++c) { A.match_sub[c].assign(nd[c], -1); A.match_map[c].assign(nd[c], -1); }
   }
-  // updateMap (cylinderMapManager.cpp:35-68, cubeMapManager.cpp:104-130, ellipsoidMapManager.cpp:111-145)
+  return SLIDE_OK;
+}
+
+int HostBackend::set_association_gate(double prob, int on_reject) {
+  if (prob > 0.0)
+    for (int dof : {3, 7, 9}) {
+      const int rc = chi2_quantile(prob, dof, &gate_q[dof]);
+      if (rc != SLIDE_OK) return rc;
+    }
+  gate_prob = prob;
+  gate_on_reject = on_reject;
+  return SLIDE_OK;
+}
+
+// The association gate (slide_backend_set_association_gate; no counterpart in the reference): between the association kernel's
+// read-back and updateMap, every matched detection of a host frame is tested at the predicted pose poseEstimate = prev * rel, which
+// the graph does not hold yet, by ONE call of HostGraph::predicted_observation_mahalanobis — from pose pose_counter - 1, the frame's
+// rel, the matched landmark's id and the measurement add_observation would pass.  A candidate with status 0 and
+// d2 > chi2_quantile(prob, dof) is rejected: gated[c][i] says how, match_sub[c][i] becomes -1 for a SLIDE_GATE_NEW (the detection goes
+// on as an unmatched one) and SLIDE_MATCH_GATED for a drop.  A candidate with another status keeps its match.  A frame the query
+// refuses for the graph's state (additions since the last solve; the robot's first frame has no from pose) goes on ungated and is
+// counted as skipped.
+int HostBackend::gate_frame(int mode, int robot, const double* rel7, const SE3& poseEstimate, const slide_detections_t& det, FrameAssoc& A) {
+  if (mode != SLIDE_FRAME_HOST && mode != SLIDE_FRAME_HOST_DEFERRED) return SLIDE_OK;
+  const uint64_t pc = pose_counter[robot];
+  // (a foreign packet added since the last solve is still pending: the resident factor is not the graph this frame joins)
+  if (pc == 0 || g.has_pending()) { gate_stats[1] += 1; return SLIDE_OK; }
+  const int cls_of[3] = {SLIDE_CLS_CYLINDER, SLIDE_CLS_CUBE, SLIDE_CLS_ELLIPSOID};
+  double p7[7];
+  to7(poseEstimate, p7);
+  std::vector<int32_t> cls;
+  std::vector<uint64_t> lm;
+  std::vector<double> meas;
+  std::vector<int2> src;      // {class slot, detection}
+  for (int c = 0; c < 3; ++c)
+    for (int i = 0; i < (int)A.match_sub[c].size(); ++i) {
+      if (A.match_sub[c][i] == -1) continue;
+      double a[17] = {};
+      if (c == 0) {
+        const double* w = &A.det_world[0][7 * (size_t)i];
+        for (int k = 0; k < 7; ++k) { a[k] = p7[k]; a[7 + k] = w[k]; }
+      } else if (c == 1) {
+        to7(from12(&A.det_world[1][12 * (size_t)i]), a + 7);
+        for (int k = 0; k < 7; ++k) a[k] = p7[k];
+        for (int k = 0; k < 3; ++k) a[14 + k] = det.cube_scale[3 * (size_t)i + k];
+      } else {
+        const double* w = &A.det_world[2][12 * (size_t)i];
+        const V3 body = transform_to(poseEstimate, V3{w[9], w[10], w[11]});
+        const double range = norm(body);
+        if (!(range > 0.0)) continue;      // (no bearing: the match is kept as it is)
+        a[0] = body.x / range; a[1] = body.y / range; a[2] = body.z / range; a[3] = range;
+      }
+      cls.push_back(cls_of[c]); lm.push_back((uint64_t)A.match_map[c][i]); src.push_back(make_int2(c, i));
+      meas.insert(meas.end(), a, a + 17);
+    }
+  const int n = (int)src.size();
+  std::vector<double> d2((size_t)std::max(n, 1), 0.0);
+  std::vector<int32_t> dof((size_t)std::max(n, 1), 0), st((size_t)std::max(n, 1), 0);
+  const int rc = g.predicted_observation_mahalanobis(robot, pc - 1, rel7, p7, n, cls.data(), lm.data(), meas.data(), d2.data(), dof.data(), nullptr,
+                                                     nullptr, st.data());
+  if (rc == SLIDE_ERR_INVALID || rc == SLIDE_MISSING) { gate_stats[1] += 1; return SLIDE_OK; }
+  if (rc != SLIDE_OK) return rc;
+  gate_stats[0] += 1;
+  gate_stats[2] += n;
+  for (int k = 0; k < n; ++k) {
+    if (st[k] != SLIDE_OK || !(d2[k] > gate_q[dof[k]])) continue;
+    const int c = src[k].x, i = src[k].y;
+    gate_stats[3] += 1;
+    if (gate_on_reject == SLIDE_GATE_NEW) { A.gated[c][i] = FrameAssoc::GATED_NEW; A.match_sub[c][i] = -1; A.match_map[c][i] = -1; }
+    else { A.gated[c][i] = FrameAssoc::GATED_DROP; A.match_sub[c][i] = SLIDE_MATCH_GATED; }
+  }
+  return SLIDE_OK;
+}
+
+// updateMap (cylinderMapManager.cpp:35-68, cubeMapManager.cpp:104-130, ellipsoidMapManager.cpp:111-145)
+void HostBackend::update_map(const slide_detections_t& det, FrameAssoc& A) {
+  const int nd[3] = {det.n_cyl, det.n_cube, det.n_ell};
+  const int dstride[3] = {7, 12, 12};
+  const int32_t* labels[3] = {det.cyl_label, det.cube_label, det.ell_label};
   for (int c = 0; c < 3; ++c) {
     ClassMap& M = maps[c];
     const double* scales = c == 1 ? det.cube_scale : det.ell_scale;
     for (int i = 0; i < nd[c]; ++i) {
+      if (A.gated[c][i] == FrameAssoc::GATED_DROP) continue;
       const double* w = &A.det_world[c][(size_t)i * dstride[c]];
       if (A.match_sub[c][i] == -1) {
         const double* pos = c == 0 ? w : w + 9;
@@ -127,10 +207,9 @@ int HostBackend::associate(const SE3& poseEstimate, const slide_detections_t& de
       }
     }
   }
-  return SLIDE_OK;
 }
 
-// graphWrapper.cpp:99-237 (detections in the world frame)
+// graphWrapper.cpp:99-237 (detections in the world frame); a detection the association gate dropped adds nothing and gets id -1
 int HostBackend::add_observation(const FrameAssoc& A, const slide_detections_t& det, const SE3& rel, const SE3& pose, int robot,
                                  bool opt, slide_frame_result_t* res, bool* optimized) {
   const uint64_t pc = pose_counter[robot];
@@ -143,6 +222,7 @@ int HostBackend::add_observation(const FrameAssoc& A, const slide_detections_t& 
   const SE3 gpose = from7(p7);
   (void)gpose;
   for (int i = 0; i < det.n_cyl; ++i) {
+    if (A.gated[0][i] == FrameAssoc::GATED_DROP) { if (res && res->cyl_id) res->cyl_id[i] = -1; continue; }
     const double* w = &A.det_world[0][7 * (size_t)i];
     uint64_t id;
     const bool isnew = A.match_sub[0][i] == -1;
@@ -151,6 +231,7 @@ int HostBackend::add_observation(const FrameAssoc& A, const slide_detections_t& 
     if (res && res->cyl_id) res->cyl_id[i] = (int32_t)id;
   }
   for (int i = 0; i < det.n_cube; ++i) {
+    if (A.gated[1][i] == FrameAssoc::GATED_DROP) { if (res && res->cube_id) res->cube_id[i] = -1; continue; }
     const SE3 cw = from12(&A.det_world[1][12 * (size_t)i]);
     const bool isnew = A.match_sub[1][i] == -1;
     const uint64_t id = isnew ? cube_counter++ : (uint64_t)A.match_map[1][i];
@@ -158,6 +239,7 @@ int HostBackend::add_observation(const FrameAssoc& A, const slide_detections_t& 
     if (res && res->cube_id) res->cube_id[i] = (int32_t)id;
   }
   for (int i = 0; i < det.n_ell; ++i) {
+    if (A.gated[2][i] == FrameAssoc::GATED_DROP) { if (res && res->ell_id) res->ell_id[i] = -1; continue; }
     const double* w = &A.det_world[2][12 * (size_t)i];
     const V3 pw{w[9], w[10], w[11]};
     const V3 body = transform_to(pose, pw);            // (pose^-1 * ellipsoid_world).translation()
@@ -243,13 +325,15 @@ int HostBackend::process_frame(int mode, int robot, const double* rel7, const do
   const double t0 = now_ms();
   int rc = associate(poseEstimate, det, !foreign, A);
   if (rc != SLIDE_OK) return rc;
+  if (gate_prob > 0.0 && (rc = gate_frame(mode, robot, rel7, poseEstimate, det, A)) != SLIDE_OK) return rc;
+  update_map(det, A);
   const double t1 = now_ms();
   bool optimized = false;
   rc = add_observation(A, det, rel, poseEstimate, robot, !foreign, res, &optimized);
   if (res) {
-    for (int i = 0; i < det.n_cyl; ++i) if (res->cyl_match) res->cyl_match[i] = A.match_sub[0][i];
-    for (int i = 0; i < det.n_cube; ++i) if (res->cube_match) res->cube_match[i] = A.match_sub[1][i];
-    for (int i = 0; i < det.n_ell; ++i) if (res->ell_match) res->ell_match[i] = A.match_sub[2][i];
+    for (int i = 0; i < det.n_cyl; ++i) if (res->cyl_match) res->cyl_match[i] = A.gated[0][i] ? SLIDE_MATCH_GATED : A.match_sub[0][i];
+    for (int i = 0; i < det.n_cube; ++i) if (res->cube_match) res->cube_match[i] = A.gated[1][i] ? SLIDE_MATCH_GATED : A.match_sub[1][i];
+    for (int i = 0; i < det.n_ell; ++i) if (res->ell_match) res->ell_match[i] = A.gated[2][i] ? SLIDE_MATCH_GATED : A.match_sub[2][i];
     res->optimized = optimized ? 1 : 0;
     to7(poseEstimate, res->out_pose7);
   }

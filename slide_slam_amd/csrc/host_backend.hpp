@@ -26,6 +26,10 @@ struct ClassMap {
 struct FrameAssoc {
   std::vector<double> det_body[3], det_world[3];
   std::vector<int> match_sub[3], match_map[3];
+  // the association gate's verdict per detection (zeros while the gate is off): GATED_NEW — the match was rejected and the detection
+  // goes on as an unmatched one (match_sub is -1 by then); GATED_DROP — rejected and left out of the map and the graph
+  enum { GATED_NO = 0, GATED_NEW = 1, GATED_DROP = 2 };
+  std::vector<int> gated[3];
 };
 
 class HostBackend {
@@ -37,6 +41,8 @@ class HostBackend {
   int ingest_solve();
   int end_frame(int robot, double* out7);
   int map_model(int cls, int idx, double* out, int* hits, int* label);
+  int set_association_gate(double prob, int on_reject);      // (arguments checked by the C ABI)
+  int64_t gate_stats[4] = {0, 0, 0, 0};      // frames gated, frames skipped, candidates tested, candidates rejected
 
   HostGraph g;
   slide_params_t P;
@@ -48,6 +54,10 @@ class HostBackend {
 
  private:
   int associate(const SE3& poseEstimate, const slide_detections_t& det, bool first_scan_shortcut, FrameAssoc& A);
+  int gate_frame(int mode, int robot, const double* rel7, const SE3& poseEstimate, const slide_detections_t& det, FrameAssoc& A);
+  void update_map(const slide_detections_t& det, FrameAssoc& A);
+  double gate_prob = 0.0, gate_q[10] = {};      // (the quantiles of gate_prob at 3 / 7 / 9 degrees of freedom, by dof)
+  int gate_on_reject = SLIDE_GATE_DROP;
   int add_observation(const FrameAssoc& A, const slide_detections_t& det, const SE3& rel, const SE3& pose, int robot, bool opt,
                       slide_frame_result_t* res, bool* optimized);
   int refresh_maps();

@@ -488,6 +488,26 @@ int slide_graph_observation_mahalanobis(slide_graph_t* g, int n, const int32_t* 
   LOCK(g);
   return g->g.observation_mahalanobis(n, robot, pose_idx, cls, lm_idx, meas17, d2, dof, C81, r9, status);
 }
+// The same gate at a predicted pose.  The list's checks are the call above's (every candidate at the one robot), then the step's and
+// the prediction's own; all of them before the graph is looked at.
+int slide_graph_predicted_observation_mahalanobis(slide_graph_t* g, int robot, uint64_t from_idx, const double rel7[7], const double est7[7], int n,
+                                                  const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof,
+                                                  double* C81, double* r9, int32_t* status) {
+  const char* who = "predicted_observation_mahalanobis";
+  if (n < 0) return obs_gate_bad("n < 0", who);
+  if (!robot_ok(robot)) return obs_gate_bad("a robot outside [0, SLIDE_MAX_ROBOTS)", who);
+  if (!rel7 || !est7) return obs_gate_bad("a needed pointer is NULL", who);
+  const std::vector<int32_t> robots((size_t)std::max(n, 1), robot);
+  const std::vector<uint64_t> poses((size_t)std::max(n, 1), from_idx);
+  const int rc = obs_gate_check_list(n, robots.data(), nullptr, poses.data(), cls, lm_idx, meas17, d2, who);
+  if (rc != SLIDE_OK) return rc;
+  if (!closure_finite(rel7, 7) || !closure_finite(est7, 7)) return obs_gate_bad("rel7 or est7 holds a non-finite value", who);
+  for (const double* p7 : {rel7, est7})
+    if (!(p7[3] * p7[3] + p7[4] * p7[4] + p7[5] * p7[5] + p7[6] * p7[6] > 0.0)) return obs_gate_bad("a zero quaternion", who);
+  if (!g) return obs_gate_bad("the graph is NULL", who);
+  LOCK(g);
+  return g->g.predicted_observation_mahalanobis(robot, from_idx, rel7, est7, n, cls, lm_idx, meas17, d2, dof, C81, r9, status);
+}
 // The joint-compatibility test of groups of such candidates (obs_joint_kernels.hip).  The argument checks come first, need neither
 // graph nor device and write nothing: the groups' own, the probability, then the candidates' as above.
 // (the groups' and the probability's, shared with the batch's call.  group_outs / cand_outs: every per-group / per-candidate output

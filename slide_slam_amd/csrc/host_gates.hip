@@ -355,15 +355,42 @@ int HostGraph::obs_walk_start(const int32_t* pid, const int32_t* lid, int n) con
 // Whole-call refusals as pose_covariances, nothing written.  Arguments checked by the caller.
 int HostGraph::observation_mahalanobis(int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
                                        const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status) {
-  int rc = marginal_state("observation_mahalanobis");
+  return obs_gate("observation_mahalanobis", nullptr, 0, 0, n, robot, pose_idx, cls, lm_idx, meas17, d2, dof, C81, r9, status);
+}
+// The same gate at a PREDICTED pose, as an EKF gates at the predicted state (obs_gate_kernels.hip, k_obs_gate_lin_pred, has the
+// identity).  The n candidates sit at est7, the value add_keypose_between(robot, from_idx, ., rel7, est7) would give a new pose n; the
+// Between factor's sigmas are that call's own, noise_model_odom_vec x max(|t_rel|, noise_floor).  The result is the gate
+// observation_mahalanobis would compute on the graph extended by pose n and that factor, linearised at those values: no add, no
+// factorisation, the graph untouched.  Candidates resolve as obs_candidate resolves them at pose (robot, from_idx) — the pose whose
+// rows of B they enter through — are grouped, swept and finished as above, and a sweep's walk starts at the block column of
+// min(from pose, the landmarks' first observers).  A from pose the graph does not hold: SLIDE_MISSING, nothing written; then
+// marginal_state's refusals.  Arguments checked by the caller.
+int HostGraph::predicted_observation_mahalanobis(int robot, uint64_t from_idx, const double* rel7, const double* est7, int n, const int32_t* cls,
+                                                 const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
+                                                 int32_t* status) {
+  const char* who = "predicted_observation_mahalanobis";
+  if (pose_id(robot, from_idx) < 0) { g_last_error = std::string(who) + ": the from pose is not in the graph"; return SLIDE_MISSING; }
+  PredPoseDev pred{};
+  to12(from7(est7), pred.x);
+  const double dist = std::max(norm(from7(rel7).t), P.noise_floor);      // (add_keypose_between's own text)
+  for (int i = 0; i < 6; ++i) { const double sg = P.noise_model_odom_vec[i] * dist; pred.s2[i] = sg * sg; }
+  return obs_gate(who, &pred, robot, from_idx, n, nullptr, nullptr, cls, lm_idx, meas17, d2, dof, C81, r9, status);
+}
+// (the two gates' one body.  pred == null: candidate k at the graph's pose (robot[k], pose_idx[k]); else every candidate at the
+// predicted pose *pred behind the graph's pose (pred_robot, pred_from), whose id this fills into pred->k once the state is checked)
+int HostGraph::obs_gate(const char* who, PredPoseDev* pred, int pred_robot, uint64_t pred_from, int n, const int32_t* robot,
+                        const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof,
+                        double* C81, double* r9, int32_t* status) {
+  int rc = marginal_state(who);
   if (rc != SLIDE_OK) return rc;
-  GateSink sink = GateSink::test("observation_mahalanobis", 9, d2, C81, r9, dof, status);
+  if (pred) pred->k = pose_id(pred_robot, pred_from);
+  GateSink sink = GateSink::test(who, 9, d2, C81, r9, dof, status);
   struct Group { int type = 0; std::vector<int32_t> pid, lid; std::vector<double> z, sg; std::vector<int> ids; };
   Group groups[3];
   groups[0].type = FT_BR; groups[1].type = FT_CUBE; groups[2].type = FT_CYL;
   for (int k = 0; k < n; ++k) {
     sink.clear(k, landmark_dim(cls[k]));
-    const ObsCand c = obs_candidate(robot[k], pose_idx[k], cls[k], lm_idx[k], meas17 + 17 * (size_t)k);
+    const ObsCand c = obs_candidate(pred ? pred_robot : robot[k], pred ? pred_from : pose_idx[k], cls[k], lm_idx[k], meas17 + 17 * (size_t)k);
     if (c.st != SLIDE_OK) { sink.refuse(k, c.st); continue; }
     Group& g = groups[c.type == FT_BR ? 0 : c.type == FT_CUBE ? 1 : 2];
     g.pid.push_back(c.p); g.lid.push_back(c.l); g.ids.push_back(k);
@@ -387,7 +414,8 @@ int HostGraph::observation_mahalanobis(int n, const int32_t* robot, const uint64
     rc = sigma_forms(
         sink.who, m, nk,
         [&](int k0, int nc, double* B, int nT) {
-          launch_obs_gate_lin(G, g.type, d_pid + k0, d_lid + k0, d_z + 15 * (size_t)k0, d_sg + 9 * (size_t)k0, nc, B, nT, sink.d_r, sink.d_G0, s);
+          if (pred) launch_obs_gate_lin_pred(G, g.type, *pred, d_lid + k0, d_z + 15 * (size_t)k0, d_sg + 9 * (size_t)k0, nc, B, nT, sink.d_r, sink.d_G0, s);
+          else launch_obs_gate_lin(G, g.type, d_pid + k0, d_lid + k0, d_z + 15 * (size_t)k0, d_sg + 9 * (size_t)k0, nc, B, nT, sink.d_r, sink.d_G0, s);
         },
         [&](int k0, int nc, const double* M) -> int {
           launch_obs_gate_finish(nk, M, sink.d_G0, sink.d_r, nc, sink.d_out, sink.d_flag, s);

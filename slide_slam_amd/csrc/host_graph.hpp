@@ -508,6 +508,14 @@ class HostGraph {
   // from meas17[17 k ..], the class's remaining arguments in the add call's order; arguments checked by the C ABI
   int observation_mahalanobis(int n, const int32_t* robot, const uint64_t* pose_idx, const int32_t* cls, const uint64_t* lm_idx,
                               const double* meas17, double* d2, int32_t* dof, double* C81, double* r9, int32_t* status);
+  // the same gate at a PREDICTED pose (host_gates.hip has the text): every candidate sits at est7, the value the Between factor
+  // add_keypose_between(robot, from_idx, ., rel7, est7) would tie to pose (robot, from_idx); nothing is added.  SLIDE_MISSING for a
+  // from pose the graph does not hold (nothing written); arguments checked by the C ABI
+  int predicted_observation_mahalanobis(int robot, uint64_t from_idx, const double* rel7, const double* est7, int n, const int32_t* cls,
+                                        const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
+                                        int32_t* status);
+  // additions no solve has merged yet (the resident factor, where there is one, does not describe the graph they will give)
+  bool has_pending() const { return !pend_vars.empty() || !pend_facs.empty(); }
   // the joint-compatibility test of n_groups hypotheses (obs_joint_kernels.hip has the invariant and the rule): group g is the
   // candidates group_ptr[g] .. group_ptr[g + 1] - 1, each described as observation_mahalanobis's; prob == 0: evaluate only.  Every
   // output is written (per candidate, then per group); arguments checked by the C ABI
@@ -521,6 +529,9 @@ class HostGraph {
   ObsCand obs_candidate(int robot, uint64_t pose_idx, int cls, uint64_t lm_idx, const double* meas17) const;
   int obs_measurement(int cls, const double* meas17, double* z15, double* sigma9) const;
   int obs_walk_start(const int32_t* pid, const int32_t* lid, int n) const;
+  int obs_gate(const char* who, PredPoseDev* pred, int pred_robot, uint64_t pred_from, int n, const int32_t* robot, const uint64_t* pose_idx,
+               const int32_t* cls, const uint64_t* lm_idx, const double* meas17, double* d2, int32_t* dof, double* C81, double* r9,
+               int32_t* status);
   int walk_start(int lo) const;
   // Landmark PAIRS of one class each (host_gates.hip has the text): the Mahalanobis test of "a and b are one object" (cov = false:
   // sig3 / sig7 the model noise of points / cylinders; d2, dof, C81, r9 as the observation gate's) or the pair's joint marginal

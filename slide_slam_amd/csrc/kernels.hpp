@@ -443,6 +443,11 @@ void launch_closure_gate_finish(const double* M, const double* r6, int n, double
 constexpr int OBS_GATE_OUT = 91;      // per candidate: d2, C (81, row-major, leading dimension 9), r (9)
 void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const int32_t* lid, const double* z15, const double* sg9, int n,
                          double* B, int nT, double* r9, double* G0, hipStream_t s);
+// the same gate at a PREDICTED pose: every candidate sits at the pose value x (12 doubles) that a Between factor of sigmas sqrt(s2)
+// would tie to the graph's pose k; the candidates name their landmarks only
+struct PredPoseDev { double x[12]; double s2[6]; int k; };
+void launch_obs_gate_lin_pred(const GraphDev& G, int type, const PredPoseDev& P, const int32_t* lid, const double* z15, const double* sg9, int n,
+                              double* B, int nT, double* r9, double* G0, hipStream_t s);
 // the same fill on the joint graph of a CholBatch: Gs the members' views (device), tab as the joint closure gate's, ends[k] = {graph of
 // the pose, its pose id, graph of the landmark, its landmark id}, sep_row[k] the joint row at which a separator landmark's first
 // coordinate enters the walk, or -1 (a private landmark: its factors' poses are rows of the landmark's graph)

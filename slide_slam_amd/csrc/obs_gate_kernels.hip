@@ -56,19 +56,20 @@ __device__ __forceinline__ void og_cyl_err(const SE3& X, const double* q, const 
 // read-modify-write, and no atomics are needed; G0 = Al H_ll^-1 Al^T, one triangle computed and mirrored.  Separator landmark (an
 // exact pass leaves its H_ll^-1 and F zero: it is not eliminated): Al^T goes to its own rows, no factor sum, G0 = 0.  B is zero before
 // the launch and the candidates own disjoint columns.  Stored for the finish: r (r9k, 9) and G0 (G0k, 81, m x m packed).
-__device__ __forceinline__ void obs_gate_lin_body(const GraphDev& Gp, const GraphDev& Gl, int type, int p, int l, const double* __restrict__ z,
-                                                  const double* __restrict__ sg, double* __restrict__ rec, double* __restrict__ colB,
-                                                  size_t ld, size_t row_p, size_t off_l, const int* __restrict__ prow_l, long long sep_row,
-                                                  double* __restrict__ r9k, double* __restrict__ G0k) {
+//
+// obs_gate_lin_rec is the linearisation alone — the record [r | Ap | Al] of the candidate at the pose value X (retracted under chart_p,
+// differences of step dl) and lm_est[l], staged in rec behind a barrier — so that the gate of a PREDICTED pose (k_obs_gate_lin_pred
+// below), whose X is no row of pose_est, linearises by the same text.
+__device__ __forceinline__ void obs_gate_lin_rec(const SE3& X, int chart_p, double dl, const GraphDev& Gl, int type, int l,
+                                                 const double* __restrict__ z, const double* __restrict__ sg, double* __restrict__ rec) {
   const int lane = threadIdx.x;
-  const int m = lf_rows(type), D = m;
-  const SE3 X = from12(Gp.pose_est + 12 * (size_t)p);
+  const int m = lf_rows(type);
   const double* lv = Gl.lm_est + 15 * (size_t)l;
   double* Jp = rec + m;
   double* Jl = rec + 7 * m;
   const int j = lane & 31, col = j >> 1;
   const bool st = lane < 32;
-  const double dl = Gp.numdiff_delta, fac = 1.0 / (2.0 * dl);
+  const double fac = 1.0 / (2.0 * dl);
   const double d = (j & 1) ? -dl : dl;
   if (type == FT_BR) {
     const double w = 1.0 / sg[0];
@@ -114,7 +115,7 @@ __device__ __forceinline__ void obs_gate_lin_body(const GraphDev& Gp, const Grap
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) cs[kk] = lv[12 + kk] + ((col == 12 + kk) ? d : 0.0);
     double e[9];
-    og_cube_err(retract(X, dX, Gp.chart), retract(C, dC, Gl.chart), cs, z, e);
+    og_cube_err(retract(X, dX, chart_p), retract(C, dC, Gl.chart), cs, z, e);
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
       const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
@@ -134,7 +135,7 @@ __device__ __forceinline__ void obs_gate_lin_body(const GraphDev& Gp, const Grap
 #pragma unroll
     for (int kk = 0; kk < 7; ++kk) q[kk] = lv[kk] + ((vi == kk) ? d : 0.0);
     double e[7];
-    og_cyl_err(retract(X, dX, Gp.chart), q, z, e);
+    og_cyl_err(retract(X, dX, chart_p), q, z, e);
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       const double hx = __shfl(e[i], 30, 32), eo = __shfl_xor(e[i], 1, 32), w = 1.0 / sg[i];
@@ -147,6 +148,16 @@ __device__ __forceinline__ void obs_gate_lin_body(const GraphDev& Gp, const Grap
     }
   }
   __syncthreads();
+}
+__device__ __forceinline__ void obs_gate_lin_body(const GraphDev& Gp, const GraphDev& Gl, int type, int p, int l, const double* __restrict__ z,
+                                                  const double* __restrict__ sg, double* __restrict__ rec, double* __restrict__ colB,
+                                                  size_t ld, size_t row_p, size_t off_l, const int* __restrict__ prow_l, long long sep_row,
+                                                  double* __restrict__ r9k, double* __restrict__ G0k) {
+  const int lane = threadIdx.x;
+  const int m = lf_rows(type), D = m;
+  const double* Jp = rec + m;
+  const double* Jl = rec + 7 * m;
+  obs_gate_lin_rec(from12(Gp.pose_est + 12 * (size_t)p), Gp.chart, Gp.numdiff_delta, Gl, type, l, z, sg, rec);
   if (sep_row >= 0) {
     if (lane < 6 * m) {
       const int jc = lane / 6, a = lane - 6 * jc;
@@ -205,6 +216,76 @@ __global__ __launch_bounds__(64) void k_obs_gate_lin(GraphDev G, int type, const
 void launch_obs_gate_lin(const GraphDev& G, int type, const int32_t* pid, const int32_t* lid, const double* z15, const double* sg9, int n,
                          double* B, int nT, double* r9, double* G0, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_obs_gate_lin, dim3(n), dim3(64), 0, s, G, type, pid, lid, z15, sg9, n, B, nT, r9, G0);
+}
+
+// The gate at a PREDICTED pose (slide_graph_predicted_observation_mahalanobis), one wavefront per candidate of one graph.  The pose X_n
+// of the candidates is not in the graph: it is the value add_keypose_between(., k, ., rel, X_n) would give a new pose n, tied to the
+// graph's pose k by a Between factor of sigmas sg (P.s2 = sg^2).  That factor linearises to H_F = -diag(1 / sg) Ad, H_T = diag(1 / sg)
+// with Ad = Ad(X_n^-1 X_k) (closure_gate_lin_body), n touches nothing else, so eliminating n from the augmented system leaves H as it
+// is and the augmented marginal is Sig(n, .) = Ad Sig(k, .), Sig(n, n) = Ad Sig(k, k) Ad^T + diag(sg^2): the Between's residual does
+// not enter.  The gate of the augmented graph is therefore the gate above with
+//     B  = P_k^T (Ap Ad)^T - sum_{f in factors(l)} P_{p_f}^T F_f Al^T,     G0 = Al H_ll^-1 Al^T + Ap diag(sg^2) Ap^T,
+// r and A = [Ap | Al] taken at (X_n, lm_est[l]) by obs_gate_lin_rec: no add, no factorisation, the graph untouched.  Ad is staged in
+// LDS beside the record (lane 0, before the record's own barrier); lane 6 j + a owns entry (row a, column j) of B at every pose as in the body
+// above — (Ap Ad)[j][a] at pose k first, then the factor sum in the order of lm_fids, pose k among them when it observes l — and G0 is
+// one triangle computed and mirrored.  The landmark is private (one graph).
+__global__ __launch_bounds__(64) void k_obs_gate_lin_pred(GraphDev G, int type, PredPoseDev P, const int32_t* __restrict__ lid,
+                                                          const double* __restrict__ z15, const double* __restrict__ sg9, int n,
+                                                          double* __restrict__ B, int nT, double* __restrict__ r9, double* __restrict__ G0) {
+  __shared__ double rec[144];
+  __shared__ double Ads[36];
+  const int kc = blockIdx.x, lane = threadIdx.x;
+  if (kc >= n) return;
+  const int m = lf_rows(type), D = m, l = lid[kc];
+  const double* Jp = rec + m;
+  const double* Jl = rec + 7 * m;
+  const SE3 Xn = from12(P.x);
+  if (lane == 0) {
+    double Ad[36];
+    adjoint(between(Xn, from12(G.pose_est + 12 * (size_t)P.k)), Ad);
+#pragma unroll
+    for (int i = 0; i < 36; ++i) Ads[i] = Ad[i];
+  }
+  obs_gate_lin_rec(Xn, G.chart, G.numdiff_delta, G, type, l, z15 + 15 * (size_t)kc, sg9 + 9 * (size_t)kc, rec);
+  double* colB = B + (size_t)(m * kc) * nT;
+  const int f0 = G.lm_ptr[l], f1 = G.lm_ptr[l + 1];
+  if (lane < 6 * m) {
+    const int jc = lane / 6, a = lane - 6 * jc;
+    double* cB = colB + (size_t)jc * nT;
+    double s = 0.0;
+    for (int c = 0; c < 6; ++c) s += Jp[6 * jc + c] * Ads[6 * c + a];
+    cB[6 * (size_t)P.k + a] = s;
+    for (int qf = f0; qf < f1; ++qf) {
+      const int f = G.lm_fids[qf];
+      const double* F = G.ebuf + G.lf_eoff[f] + 6 * D + a * D;
+      double t = 0.0;
+      for (int c = 0; c < D; ++c) t += F[c] * Jl[jc * D + c];
+      double* at = cB + 6 * (size_t)G.lf_pose[f] + a;
+      *at = *at - t;
+    }
+  }
+  if (lane < m * (m + 1) / 2) {
+    int i = 0;
+    while ((i + 1) * (i + 2) / 2 <= lane) ++i;
+    const int jc = lane - i * (i + 1) / 2;      // (i >= jc)
+    const double* Hi = G.lm_Hinv + 81 * (size_t)l;
+    double s = 0.0;
+    for (int c = 0; c < D; ++c) {
+      double t = 0.0;
+      for (int dd = 0; dd < D; ++dd) t += Hi[c * D + dd] * Jl[jc * D + dd];
+      s += Jl[i * D + c] * t;
+    }
+    double u = 0.0;
+    for (int c = 0; c < 6; ++c) u += Jp[6 * i + c] * (P.s2[c] * Jp[6 * jc + c]);
+    s += u;
+    G0[81 * (size_t)kc + m * i + jc] = s;
+    G0[81 * (size_t)kc + m * jc + i] = s;
+  }
+  if (lane < m) r9[9 * (size_t)kc + lane] = rec[lane];
+}
+void launch_obs_gate_lin_pred(const GraphDev& G, int type, const PredPoseDev& P, const int32_t* lid, const double* z15, const double* sg9, int n,
+                              double* B, int nT, double* r9, double* G0, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_obs_gate_lin_pred, dim3(n), dim3(64), 0, s, G, type, P, lid, z15, sg9, n, B, nT, r9, G0);
 }
 
 // The same fill for the joint-compatibility test (obs_joint_kernels.hip), one wavefront per candidate of one graph: the classes are
