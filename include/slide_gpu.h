@@ -709,6 +709,42 @@ int slide_debug_border_product(int n, const double* S_in, const int* ld, const i
  * yv_out: T[i] * 64 doubles per system, x_loc: nbr[i] * 64, each one system after the other. */
 int slide_debug_border_apply(int n, const double* S_in, const int* ld, const int* T, const int* nbr, const int* b0, const double* yv_in,
                              const double* x_loc, const int* segtab, const int* segtab_off, const int* segtab_len, double* yv_out);
+/* Unit-test hooks of the kernels that READ the factor (cov_kernels.hip, joint_cov_kernels.hip, k_cov_fwd / k_cov_gram), on a caller-given
+ * factor: no factorisation runs inside them.  The factor's layout is the one slide_debug_chol_bordered returns: S_in (ld x T*64 doubles,
+ * column-major) with L(i, k) in tile (i, k) for k < i <= prof[k] (prof: T ints or NULL = dense), Ld_in (T x 64 x 64) with the sub-diagonal
+ * 16x16 blocks of L_kk, Winv_in (T x 1024) with the inverses of its four diagonal 16x16 blocks ((L_bb^-1)[r][j] at b*256 + j*16 + r).
+ * Every hook uploads, synchronises, calls the production launcher on the null stream, synchronises and downloads.  SLIDE_ERR_INVALID,
+ * nothing launched, for what the launchers do not define: T < 1, ld < T*64, an odd ld, a prof that decreases or has prof[k] < k or >= T,
+ * nrhs < 1, ncol_alloc < nrhs, k0 outside 0 .. T-1 (or != 0 with mode 0), a stage or mode other than 0 / 1, a row0 whose six rows leave
+ * the system, a gram row outside 0 .. ldx-1.
+ * slide_debug_selected_inverse: Sg and Z (ld * T * 64 doubles each, pre-filled by the caller) through launch_selected_inverse (stage 1,
+ * as the marginals call it) or its first launch alone (stage 0: k_sinv_prep); both come back, and S_out / Ld_out / Winv_out (may be
+ * NULL) receive the factor as the device holds it afterwards (unchanged). */
+int slide_debug_selected_inverse(const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, const int* prof, int stage,
+                                 double* Sg, double* Z, double* S_out, double* Ld_out, double* Winv_out);
+/* B and X: ncol_alloc columns of T*64 rows each, in and out.  mode 0: launch_multi_solve (X = S^-1 B over the first nrhs columns, B
+ * overwritten); mode 1: launch_multi_fwd from block column k0 on (W = L^-1 B into X). */
+int slide_debug_multi_solve(const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, const int* prof, double* B, double* X,
+                            int ncol_alloc, int nrhs, int mode, int k0);
+/* launch_gram on X (ncol columns, leading dimension ldx) over the rows `rows` (nrows ints, or NULL: 0 .. nrows-1) into M: ncol x ncol
+ * doubles plus one guard row of ncol behind them, in and out. */
+int slide_debug_gram(const double* X, long long ldx, int ncol, const int* rows, int nrows, double* M);
+/* launch_pose_covariance for the pose whose first row is row0, on six unit columns built as HostGraph::pose_covariance builds them; S_in
+ * must be zero outside the profile (k_cov_fwd walks the dense column).  cov36: 36 doubles; Y_out (6 x T*64, may be NULL): the walk. */
+int slide_debug_pose_covariance(const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, int row0, double* cov36, double* Y_out);
+/* The joint-tree selected inverse (k_jsinv_prep, k_jsinv_tile) on n (1 .. 9) caller-given systems, one after the other in every buffer.
+ * System i: factor columns 0 .. Tb[i]-1 in S_in (ld[i] x Tb[i]*64), Tb[i] .. Tc[i]-1 in B_in (ldb[i] x (Tc[i]-Tb[i])*64, rows and columns
+ * counted from Tb[i]), Ld_in / Winv_in for all Tc[i] columns (split at Tb[i] inside the hook), D = -I on the columns >= neg0[i], Sg and Z
+ * (lds[i] x Trow[i]*64 doubles each, in and out; Trow[i] >= Tc[i] tile rows; the caller's Sg holds the Sigma of the rows past the columns,
+ * k_jsig_gather's part).  rp (nrp ints) / rows (nrows ints): the columns' tile-row lists, system i's column c at rp[col0[i] + c] ..
+ * rp[col0[i] + c + 1].  jobs: njobs (system, column) pairs, grouped into nsteps steps by step_off (nsteps + 1 ints).  launch_jsinv_prep
+ * over all jobs; with stage 1 then one launch_jsinv_step per step with that step's largest row count (CholBatch's sequence).
+ * SLIDE_ERR_INVALID, nothing launched: a row at or beyond Trow[i] or <= its column, a row or a job listed twice, leading dimensions below
+ * what the lists reach, offsets that leave their tables. */
+int slide_debug_joint_selected_inverse(int n, const double* S_in, const int* ld, const int* Tb, const double* B_in, const int* ldb, const int* Tc,
+                                       const double* Ld_in, const double* Winv_in, const int* neg0, const int* col0, const int* lds,
+                                       const int* Trow, const int* rp, int nrp, const int* rows, int nrows, const int* jobs, int njobs,
+                                       const int* step_off, int nsteps, int stage, double* Sg, double* Z);
 
 /* ------------------------------------------------------------------------------------------------
  * S3 — association (include/core/sloam.h:88-108, src/core/sloam.cpp:73-306; *MapManager::getSubmap)

@@ -33,7 +33,7 @@ EXPORTS = [
     "slide_graph_gauss_newton", "slide_graph_get_pose", "slide_graph_get_pose12", "slide_graph_get_all_poses",
     "slide_graph_get_landmark", "slide_graph_get_pose_covariance", "slide_graph_get_pose_covariances", "slide_graph_get_landmark_covariances", "slide_graph_marginal_traces", "slide_graph_closure_info_gain", "slide_graph_closure_info_gain_batch", "slide_graph_stats", "slide_graph_rejected_count", "slide_graph_set_shared", "slide_graph_dist_phase", "slide_chol_batch_create", "slide_chol_batch_destroy", "slide_graph_join_chol_batch", "slide_graph_dist_pass_local", "slide_chol_batch_pass", "slide_chol_batch_get_pose_covariances", "slide_chol_batch_get_landmark_covariances", "slide_chol_batch_marginal_traces", "slide_chol_batch_closure_info_gain", "slide_chol_batch_closure_info_gain_batch", "slide_chol_batch_pass_part", "slide_chol_batch_stream", "slide_chol_batch_set_pcg", "slide_graph_set_pcg", "slide_chol_batch_set_pcg_tolerance", "slide_graph_set_pcg_tolerance", "slide_graph_set_separator", "slide_chol_batch_set_exact_joint", "slide_chol_batch_sep_buffer_len", "slide_chol_batch_sep_exchange_len", "slide_chol_batch_profile_exact_joint", "slide_graph_get_border_profile", "slide_graph_get_incremental_stats", "slide_graph_set_wildfire", "slide_graph_get_wildfire_stats", "slide_graph_get_segments", "slide_graph_get_segment_table", "slide_chol_batch_set_segments", "slide_clipper_dense_clique_batch", "slide_clipper_last_solve_info", "slide_last_device_ms", "slide_chol_batch_set_separator_profile", "slide_chol_batch_set_separator_blocks", "slide_chol_batch_set_separator_owner", "slide_chol_batch_sep_segment", "slide_graph_set_incremental", "slide_graph_set_ghost_ids", "slide_graph_get_pcg_stats", "slide_graph_get_tile_profile", "slide_graph_set_dense_profile", "slide_graph_chi2", "slide_chol_batch_profile", "slide_graph_set_ghosts", "slide_graph_add_relative_meas_ghost",
     "slide_backend_landmark_table", "slide_graph_set_profiling", "slide_graph_get_profile",
-    "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_chol_batch", "slide_debug_chol_plan", "slide_debug_pair_timeouts", "slide_debug_border_product", "slide_debug_border_apply", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
+    "slide_dense_spd_solve", "slide_dense_spd_solve_ex", "slide_debug_chol_bordered", "slide_debug_chol_batch", "slide_debug_chol_plan", "slide_debug_pair_timeouts", "slide_debug_border_product", "slide_debug_border_apply", "slide_debug_selected_inverse", "slide_debug_multi_solve", "slide_debug_gram", "slide_debug_pose_covariance", "slide_debug_joint_selected_inverse", "slide_submap_knn", "slide_assoc_match_cylinders", "slide_assoc_match_boxes", "slide_assoc_sweep_batch_device", "slide_assoc_sweep_batch",
     "slide_backend_create", "slide_backend_destroy", "slide_backend_process_frame", "slide_backend_ingest_solve",
     "slide_backend_end_frame", "slide_backend_graph", "slide_backend_counts", "slide_backend_map_model",
     "slide_place_default_params", "slide_match_maps", "slide_match_maps_sweep", "slide_find_inter_loop_closure", "slide_find_inter_loop_closures",
@@ -1457,6 +1457,92 @@ def debug_border_apply(systems):
         raise err
     offs = np.concatenate([[0], np.cumsum(T[:n].astype(np.int64) * 64)])
     return [out[offs[i]:offs[i + 1]] for i in range(n)]
+
+
+def _debug_rc(rc):
+    if rc != SLIDE_OK:
+        err = SlideError(f"{ERR.get(rc, rc)}: {last_error()}")
+        err.code = rc
+        raise err
+
+
+def _debug_factor(f):
+    """S, ld, T, Ld, Winv, prof pointer (and the array it points into) of a caller-given factor (dict with S, ld, T, Ld, Winv, prof)."""
+    ld, T = int(f["ld"]), int(f["T"])
+    S, Ld, Wi = _d(f["S"]).ravel(), _d(f["Ld"]).ravel(), _d(f["Winv"]).ravel()
+    assert S.size == max(ld * T * 64, 0) and Ld.size == max(T, 0) * 4096 and Wi.size == max(T, 0) * 1024
+    pr = None if f.get("prof") is None else _i(f["prof"])
+    assert pr is None or pr.size == T
+    return S, ld, T, Ld, Wi, (None if pr is None else _p(pr))
+
+
+def debug_selected_inverse(f, Sg, Z, stage=1):
+    """slide_debug_selected_inverse: launch_selected_inverse (stage 1) or k_sinv_prep alone (stage 0) on the caller-given factor f (dict
+    with S, ld, T, Ld, Winv, prof or None) with Sg / Z (ld * T * 64 each) as the pre-filled output buffers.  Returns dict(Sg, Z, S, Ld,
+    Winv), the last three as the device held them afterwards.  Raises SlideError (code -1) for what the launcher does not define."""
+    S, ld, T, Ld, Wi, pr = _debug_factor(f)
+    Sg, Z = _d(Sg).ravel().copy(), _d(Z).ravel().copy()
+    assert Sg.size == S.size and Z.size == S.size
+    So, Lo, Wo = np.zeros_like(S), np.zeros_like(Ld), np.zeros_like(Wi)
+    _debug_rc(lib().slide_debug_selected_inverse(_p(S), C.c_int(ld), C.c_int(T), _p(Ld), _p(Wi), pr, C.c_int(stage), _p(Sg), _p(Z), _p(So),
+                                                 _p(Lo), _p(Wo)))
+    return dict(Sg=Sg, Z=Z, S=So, Ld=Lo, Winv=Wo)
+
+
+def debug_multi_solve(f, B, X, nrhs, mode=0, k0=0):
+    """slide_debug_multi_solve: launch_multi_solve (mode 0) or launch_multi_fwd from block column k0 (mode 1) on the factor f; B and X:
+    (ncol_alloc, T * 64) arrays (a row = one column of the device's buffer).  Returns (B, X) afterwards, same shape."""
+    S, ld, T, Ld, Wi, pr = _debug_factor(f)
+    B, X = _d(B).copy(), _d(X).copy()
+    assert B.ndim == 2 and B.shape == X.shape and B.shape[1] == max(T, 0) * 64
+    _debug_rc(lib().slide_debug_multi_solve(_p(S), C.c_int(ld), C.c_int(T), _p(Ld), _p(Wi), pr, _p(B), _p(X), C.c_int(B.shape[0]),
+                                            C.c_int(nrhs), C.c_int(mode), C.c_int(k0)))
+    return B, X
+
+
+def debug_gram(X, rows, nrows, M):
+    """slide_debug_gram: launch_gram on X ((ncol, ldx): a row = one column of the device's buffer) over `rows` (or None: 0 .. nrows - 1)
+    into M ((ncol + 1, ncol), pre-filled; the last row is the guard).  Returns M afterwards."""
+    X, M = _d(X), _d(M).copy()
+    ncol, ldx = X.shape
+    assert M.shape == (ncol + 1, ncol)
+    rw = None if rows is None else _i(rows)
+    assert rw is None or rw.size == nrows
+    _debug_rc(lib().slide_debug_gram(_p(X), C.c_longlong(ldx), C.c_int(ncol), None if rw is None else _p(rw), C.c_int(nrows), _p(M)))
+    return M
+
+
+def debug_pose_covariance(f, row0):
+    """slide_debug_pose_covariance: launch_pose_covariance for the six rows from row0 on the factor f.  Returns (cov (6, 6), Y (6, T * 64))."""
+    S, ld, T, Ld, Wi, _ = _debug_factor(f)
+    cov, Y = np.zeros(36), np.zeros((6, max(T, 1) * 64))
+    _debug_rc(lib().slide_debug_pose_covariance(_p(S), C.c_int(ld), C.c_int(T), _p(Ld), _p(Wi), C.c_int(row0), _p(cov), _p(Y)))
+    return cov.reshape(6, 6), Y
+
+
+def debug_joint_selected_inverse(systems, rp, rows, jobs, step_off, stage=1):
+    """slide_debug_joint_selected_inverse: systems = dicts with S (ld x Tb * 64), ld, Tb, B (ldb x (Tc - Tb) * 64), ldb, Tc, Ld, Winv (all
+    Tc columns), neg0, col0, lds, Trow and the pre-filled Sg, Z (lds x Trow * 64 each); rp / rows the flat row lists; jobs a list of
+    (system, column); step_off the steps' first jobs and the end.  Returns [dict(Sg, Z)], flat as given."""
+    n = len(systems)
+    col = lambda key: np.array([int(s[key]) for s in systems] or [0], np.int32)
+    cat = lambda key: np.concatenate([_d(s[key]).ravel() for s in systems] + [np.zeros(1)])
+    ld, Tb, ldb, Tc, neg0, col0, lds, Trow = (col(k) for k in ("ld", "Tb", "ldb", "Tc", "neg0", "col0", "lds", "Trow"))
+    S, B, Ld, Wi, Sg, Z = (cat(k) for k in ("S", "B", "Ld", "Winv", "Sg", "Z"))
+    g_sz = [int(s["lds"]) * int(s["Trow"]) * 64 for s in systems]
+    for s, z in zip(systems, g_sz):
+        assert np.size(s["S"]) == s["ld"] * s["Tb"] * 64 and np.size(s["B"]) == s["ldb"] * (s["Tc"] - s["Tb"]) * 64
+        assert np.size(s["Ld"]) == s["Tc"] * 4096 and np.size(s["Winv"]) == s["Tc"] * 1024 and np.size(s["Sg"]) == z and np.size(s["Z"]) == z
+    rp_, rows_ = _i(rp), _i(list(rows) + [0])
+    jb, so = _i(np.asarray(jobs, np.int32).reshape(-1, 2)), _i(step_off)
+    _debug_rc(lib().slide_debug_joint_selected_inverse(C.c_int(n), _p(S), _p(ld), _p(Tb), _p(B), _p(ldb), _p(Tc), _p(Ld), _p(Wi), _p(neg0),
+                                                       _p(col0), _p(lds), _p(Trow), _p(rp_), C.c_int(rp_.size), _p(rows_), C.c_int(len(rows)),
+                                                       _p(jb), C.c_int(jb.shape[0]), _p(so), C.c_int(so.size - 1), C.c_int(stage), _p(Sg), _p(Z)))
+    out, o = [], 0
+    for z in g_sz:
+        out.append(dict(Sg=Sg[o:o + z], Z=Z[o:o + z]))
+        o += z
+    return out
 
 
 # ---- stand-alone association / place recognition ---------------------------------------------------------

@@ -897,6 +897,184 @@ int slide_debug_border_apply(int n, const double* S_in, const int* ld, const int
   return SLIDE_OK;
 }
 
+// ---- the readers of the factor on caller data (slide_gpu.h): selected inverse, many-column solves, gram, single-pose walk ---------------
+// No factorisation runs here: S / Ld / Winv are the caller's, in the layout of chol_kernels.hip.
+// what every entry checks of the factor's shape (the launchers index S, Ld, Winv and the profile by it)
+static bool debug_factor_shape_ok(int ld, int T, const int* prof) {
+  if (T < 1 || ld < T * NB || (ld & 1)) return false;
+  if (prof)
+    for (int k = 0; k < T; ++k)
+      if (prof[k] < k || prof[k] >= T || (k > 0 && prof[k] < prof[k - 1])) return false;
+  return true;
+}
+struct DebugFactor {
+  double *S = nullptr, *Ld = nullptr, *Winv = nullptr;
+  int* prof = nullptr;
+  bool up(Tmp& Tm, const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, const int* prof_in) {
+    S = Tm.up(S_in, (size_t)ld * T * NB);
+    Ld = Tm.up(Ld_in, (size_t)T * NB * NB);
+    Winv = Tm.up(Winv_in, (size_t)T * 1024);
+    if (prof_in) prof = Tm.up(prof_in, (size_t)T);
+    return S && Ld && Winv && (!prof_in || prof);
+  }
+};
+int slide_debug_selected_inverse(const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, const int* prof, int stage,
+                                 double* Sg, double* Z, double* S_out, double* Ld_out, double* Winv_out) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (!S_in || !Ld_in || !Winv_in || !Sg || !Z || (stage != 0 && stage != 1) || !debug_factor_shape_ok(ld, T, prof)) return SLIDE_ERR_INVALID;
+  const size_t len = (size_t)ld * T * NB;
+  Tmp Tm;
+  DebugFactor F;
+  double* dSg = Tm.up(Sg, len);
+  double* dZ = Tm.up(Z, len);
+  if (!F.up(Tm, S_in, ld, T, Ld_in, Winv_in, prof) || !dSg || !dZ) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipDeviceSynchronize());
+  if (stage == 0) launch_selected_inverse_prep(F.S, ld, T, F.Ld, F.Winv, prof, F.prof, dSg, dZ, nullptr);
+  else launch_selected_inverse(F.S, ld, T, F.Ld, F.Winv, prof, F.prof, dSg, dZ, nullptr);
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  SL_HIP(hipMemcpy(Sg, dSg, len * sizeof(double), hipMemcpyDeviceToHost));
+  SL_HIP(hipMemcpy(Z, dZ, len * sizeof(double), hipMemcpyDeviceToHost));
+  if (S_out) SL_HIP(hipMemcpy(S_out, F.S, len * sizeof(double), hipMemcpyDeviceToHost));
+  if (Ld_out) SL_HIP(hipMemcpy(Ld_out, F.Ld, (size_t)T * NB * NB * sizeof(double), hipMemcpyDeviceToHost));
+  if (Winv_out) SL_HIP(hipMemcpy(Winv_out, F.Winv, (size_t)T * 1024 * sizeof(double), hipMemcpyDeviceToHost));
+  return SLIDE_OK;
+}
+int slide_debug_multi_solve(const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, const int* prof, double* B, double* X,
+                            int ncol_alloc, int nrhs, int mode, int k0) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (!S_in || !Ld_in || !Winv_in || !B || !X || (mode != 0 && mode != 1) || !debug_factor_shape_ok(ld, T, prof)) return SLIDE_ERR_INVALID;
+  if (nrhs < 1 || ncol_alloc < nrhs || k0 < 0 || k0 >= T || (mode == 0 && k0 != 0)) return SLIDE_ERR_INVALID;
+  const size_t len = (size_t)ncol_alloc * T * NB;
+  Tmp Tm;
+  DebugFactor F;
+  double* dB = Tm.up(B, len);
+  double* dX = Tm.up(X, len);
+  if (!F.up(Tm, S_in, ld, T, Ld_in, Winv_in, nullptr) || !dB || !dX) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipDeviceSynchronize());
+  if (mode == 0) launch_multi_solve(F.S, ld, T, F.Ld, F.Winv, prof, dB, dX, nrhs, nullptr);
+  else launch_multi_fwd(F.S, ld, T, F.Ld, F.Winv, prof, dB, dX, nrhs, nullptr, k0);
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  SL_HIP(hipMemcpy(B, dB, len * sizeof(double), hipMemcpyDeviceToHost));
+  SL_HIP(hipMemcpy(X, dX, len * sizeof(double), hipMemcpyDeviceToHost));
+  return SLIDE_OK;
+}
+int slide_debug_gram(const double* X, long long ldx, int ncol, const int* rows, int nrows, double* M) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (!X || !M || ncol < 1 || nrows < 1 || ldx < 1 || (!rows && nrows > ldx)) return SLIDE_ERR_INVALID;
+  if (rows)
+    for (int q = 0; q < nrows; ++q)
+      if (rows[q] < 0 || rows[q] >= ldx) return SLIDE_ERR_INVALID;
+  const size_t mlen = (size_t)ncol * ncol + ncol;      // (one guard row behind the block)
+  Tmp Tm;
+  double* dX = Tm.up(X, (size_t)ldx * ncol);
+  double* dM = Tm.up(M, mlen);
+  int* d_rows = rows ? Tm.up(rows, (size_t)nrows) : nullptr;
+  if (!dX || !dM || (rows && !d_rows)) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipDeviceSynchronize());
+  launch_gram(dX, (size_t)ldx, ncol, d_rows, nrows, dM, nullptr);
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  SL_HIP(hipMemcpy(M, dM, mlen * sizeof(double), hipMemcpyDeviceToHost));
+  return SLIDE_OK;
+}
+int slide_debug_pose_covariance(const double* S_in, int ld, int T, const double* Ld_in, const double* Winv_in, int row0, double* cov36, double* Y_out) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (!S_in || !Ld_in || !Winv_in || !cov36 || !debug_factor_shape_ok(ld, T, nullptr) || row0 < 0 || row0 + 6 > T * NB) return SLIDE_ERR_INVALID;
+  const size_t nT = (size_t)T * NB;
+  Tmp Tm;
+  DebugFactor F;
+  double* dY = Tm.up<double>(nullptr, 6 * nT + 36);
+  if (!F.up(Tm, S_in, ld, T, Ld_in, Winv_in, nullptr) || !dY) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipMemset(dY, 0, (6 * nT + 36) * sizeof(double)));      // (the six unit columns, as HostGraph::pose_covariance builds them)
+  const double one = 1.0;
+  for (int c = 0; c < 6; ++c) SL_HIP(hipMemcpy(dY + (size_t)c * nT + row0 + c, &one, sizeof(double), hipMemcpyHostToDevice));
+  SL_HIP(hipDeviceSynchronize());
+  launch_pose_covariance(F.S, ld, T, F.Ld, F.Winv, dY, row0, dY + 6 * nT, nullptr);
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  SL_HIP(hipMemcpy(cov36, dY + 6 * nT, 36 * sizeof(double), hipMemcpyDeviceToHost));
+  if (Y_out) SL_HIP(hipMemcpy(Y_out, dY, 6 * nT * sizeof(double), hipMemcpyDeviceToHost));
+  return SLIDE_OK;
+}
+int slide_debug_joint_selected_inverse(int n, const double* S_in, const int* ld, const int* Tb, const double* B_in, const int* ldb, const int* Tc,
+                                       const double* Ld_in, const double* Winv_in, const int* neg0, const int* col0, const int* lds,
+                                       const int* Trow, const int* rp, int nrp, const int* rows, int nrows, const int* jobs, int njobs,
+                                       const int* step_off, int nsteps, int stage, double* Sg, double* Z) {
+  if (slide_device_check(-1) != SLIDE_OK) return SLIDE_ERR_HIP;
+  if (n < 1 || n > 1 + JSIG_ROBOTS_MAX || !S_in || !ld || !Tb || !B_in || !ldb || !Tc || !Ld_in || !Winv_in || !neg0 || !col0 || !lds || !Trow ||
+      !rp || nrp < 2 || !rows || nrows < 0 || !jobs || njobs < 1 || !step_off || nsteps < 1 || (stage != 0 && stage != 1) || !Sg || !Z)
+    return SLIDE_ERR_INVALID;
+  for (int e = 0; e < nrp; ++e)
+    if (rp[e] < 0 || rp[e] > nrows || (e > 0 && rp[e] < rp[e - 1])) return SLIDE_ERR_INVALID;
+  std::vector<size_t> s_off(n + 1, 0), b_off(n + 1, 0), t_off(n + 1, 0), g_off(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (Tc[i] < 1 || Tb[i] < 0 || Tb[i] > Tc[i] || Trow[i] < Tc[i] || lds[i] < Trow[i] * NB || neg0[i] < 0) return SLIDE_ERR_INVALID;
+    if (Tb[i] > 0 && ld[i] < Trow[i] * NB) return SLIDE_ERR_INVALID;
+    if (Tc[i] > Tb[i] && ldb[i] < (Trow[i] - Tb[i]) * NB) return SLIDE_ERR_INVALID;
+    if (col0[i] < 0 || col0[i] + Tc[i] + 1 > nrp) return SLIDE_ERR_INVALID;
+    for (int c = 0; c < Tc[i]; ++c)      // a column's rows: below it, inside the system's tile rows, each once
+      for (int q = rp[col0[i] + c]; q < rp[col0[i] + c + 1]; ++q) {
+        if (rows[q] <= c || rows[q] >= Trow[i]) return SLIDE_ERR_INVALID;
+        for (int p = rp[col0[i] + c]; p < q; ++p)
+          if (rows[p] == rows[q]) return SLIDE_ERR_INVALID;
+      }
+    s_off[i + 1] = s_off[i] + (size_t)ld[i] * Tb[i] * NB;
+    b_off[i + 1] = b_off[i] + (size_t)ldb[i] * (Tc[i] - Tb[i]) * NB;
+    t_off[i + 1] = t_off[i] + (size_t)Tc[i];
+    g_off[i + 1] = g_off[i] + (size_t)lds[i] * Trow[i] * NB;
+  }
+  if (step_off[0] != 0 || step_off[nsteps] != njobs) return SLIDE_ERR_INVALID;
+  for (int q = 0; q < nsteps; ++q)
+    if (step_off[q + 1] < step_off[q]) return SLIDE_ERR_INVALID;
+  for (int j = 0; j < njobs; ++j) {
+    const int sy = jobs[2 * j], k = jobs[2 * j + 1];
+    if (sy < 0 || sy >= n || k < 0 || k >= Tc[sy]) return SLIDE_ERR_INVALID;
+    for (int p = 0; p < j; ++p)
+      if (jobs[2 * p] == sy && jobs[2 * p + 1] == k) return SLIDE_ERR_INVALID;
+  }
+  Tmp Tm;
+  std::vector<JSinvSys> Y(n);
+  for (int i = 0; i < n; ++i) {
+    JSinvSys& y = Y[i];
+    const size_t nb = (size_t)Tb[i], nc = (size_t)Tc[i];
+    y.S = Tm.up(S_in + s_off[i], s_off[i + 1] - s_off[i]); y.ld = ld[i]; y.Tb = Tb[i];
+    y.B = Tm.up(B_in + b_off[i], b_off[i + 1] - b_off[i]); y.ldb = ldb[i];
+    y.Ld = Tm.up(Ld_in + t_off[i] * NB * NB, nb * NB * NB); y.Winv = Tm.up(Winv_in + t_off[i] * 1024, nb * 1024);
+    y.Ld2 = Tm.up(Ld_in + (t_off[i] + nb) * NB * NB, (nc - nb) * NB * NB); y.Winv2 = Tm.up(Winv_in + (t_off[i] + nb) * 1024, (nc - nb) * 1024);
+    y.neg0 = neg0[i]; y.col0 = col0[i]; y.lds = lds[i];
+    y.Sg = Tm.up(Sg + g_off[i], g_off[i + 1] - g_off[i]);
+    y.Z = Tm.up(Z + g_off[i], g_off[i + 1] - g_off[i]);
+    if (!y.S || !y.B || !y.Ld || !y.Winv || !y.Ld2 || !y.Winv2 || !y.Sg || !y.Z) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  }
+  std::vector<int2> hj(njobs);
+  for (int j = 0; j < njobs; ++j) hj[j] = make_int2(jobs[2 * j], jobs[2 * j + 1]);
+  auto nr = [&](int j) { const int b = col0[hj[j].x] + hj[j].y; return rp[b + 1] - rp[b]; };
+  int max_rows = 0;
+  for (int j = 0; j < njobs; ++j) max_rows = std::max(max_rows, nr(j));
+  JSinvSys* d_sys = Tm.up(Y.data(), (size_t)n);
+  int2* d_jobs = Tm.up(hj.data(), (size_t)njobs);
+  int* d_rp = Tm.up(rp, (size_t)nrp);
+  int* d_rows = Tm.up(rows, (size_t)nrows);
+  if (!d_sys || !d_jobs || !d_rp || !d_rows) { g_last_error = "hipMalloc/hipMemcpy failed"; return SLIDE_ERR_HIP; }
+  SL_HIP(hipDeviceSynchronize());
+  launch_jsinv_prep(d_sys, d_jobs, njobs, max_rows, d_rp, d_rows, nullptr);      // (CholBatch::ensure_joint_sigma's sequence)
+  if (stage == 1)
+    for (int q = 0; q < nsteps; ++q) {
+      int mr = 0;
+      for (int j = step_off[q]; j < step_off[q + 1]; ++j) mr = std::max(mr, nr(j));
+      launch_jsinv_step(d_sys, d_jobs + step_off[q], step_off[q + 1] - step_off[q], mr, d_rp, d_rows, nullptr);
+    }
+  SL_HIP(hipDeviceSynchronize());
+  SL_HIP(hipGetLastError());
+  for (int i = 0; i < n; ++i) {
+    SL_HIP(hipMemcpy(Sg + g_off[i], Y[i].Sg, (g_off[i + 1] - g_off[i]) * sizeof(double), hipMemcpyDeviceToHost));
+    SL_HIP(hipMemcpy(Z + g_off[i], Y[i].Z, (g_off[i + 1] - g_off[i]) * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return SLIDE_OK;
+}
+
 // ---- stand-alone association ------------------------------------------------------------------------
 
 // One class through the frame kernel on caller buffers.  n_cur == 0: pure K-NN gate at `qpos` (cloud = AoS float xyz, as the caller

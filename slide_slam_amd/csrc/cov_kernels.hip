@@ -172,12 +172,18 @@ __global__ __launch_bounds__(256) void k_sinv_tile(double* __restrict__ Sg, cons
 }
 
 // host: the selected inverse of the factor (prof: host copy of the tile profile, or null: dense; d_prof the device copy or null)
-void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
-                             double* Sg, double* Z, hipStream_t s) {
+// its first launch alone: Z(i, k) of every tile inside the profile and L_kk^-T L_kk^-1 into the diagonal tiles of Sg
+void launch_selected_inverse_prep(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
+                                  double* Sg, double* Z, hipStream_t s) {
   if (T <= 0) return;
   int band = 0;
   for (int k = 0; k < T; ++k) band = std::max(band, (prof ? prof[k] : T - 1) - k);
   hipLaunchKernelGGL(k_sinv_prep, dim3(T, band + 1), dim3(256), 0, s, S, ld, T, Ld, Winv, prof ? d_prof : nullptr, Sg, Z);
+}
+void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
+                             double* Sg, double* Z, hipStream_t s) {
+  if (T <= 0) return;
+  launch_selected_inverse_prep(S, ld, T, Ld, Winv, prof, d_prof, Sg, Z, s);
   for (int k = T - 1; k >= 0; --k) {
     const int i1 = prof ? prof[k] : T - 1;
     if (i1 <= k) continue;

@@ -144,6 +144,9 @@ void launch_pose_covariance(const double* S, int ld, int T, const double* Ld, co
 // with Z (S's size) as scratch; marginal blocks out of it; many right-hand sides on the factor; the information-gain products
 void launch_selected_inverse(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
                              double* Sg, double* Z, hipStream_t s);
+// its first launch alone (k_sinv_prep: Z and the diagonal tiles' L_kk^-T L_kk^-1); launch_selected_inverse starts with this call
+void launch_selected_inverse_prep(const double* S, int ld, int T, const double* Ld, const double* Winv, const int* prof, const int* d_prof,
+                                  double* Sg, double* Z, hipStream_t s);
 void launch_pose_blocks(const double* Sg, int ld, const int* poses, int n, double* out, hipStream_t s, const int* prow = nullptr);     // out: 36 per pose; prow: a pose's first row (null: 6 p)
 void launch_landmark_covariances(const GraphDev& G, const double* Sg, int ld, const int* lids, int n, double* out, hipStream_t s,
                                  const int* prow = nullptr);      // out: 81 per landmark (d x d used)
