@@ -2021,15 +2021,19 @@ extern "C" void slide_debug_chain_stamps(unsigned long long* out) { (void)hipMem
 // whose workgroups poll the entries of the blocks they depend on ("flag in data": one round trip per link of the chain).
 constexpr unsigned long long BWD_SENT = CHAIN_SENTINEL;      // (kernels.hpp: k_pcg_update pre-fills the forward chain's output with it)
 
-__global__ void k_chol_extract_y(const double* __restrict__ S, int ld, int T, int Tr, double* __restrict__ yv, double* __restrict__ dp, int* status,
-                                 double* __restrict__ prev) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+// coordinate c of k_chol_extract_y (also run by k_lam_solve1)
+__device__ __forceinline__ void extract_y_elem(const double* __restrict__ S, int ld, int T, int Tr, double* __restrict__ yv, double* __restrict__ dp,
+                                               int* status, double* __restrict__ prev, int c) {
   if (c == 0) status[4] = 0;            // ticket counter of the chained backward substitution that follows
   if (c < T * NB) {
     yv[c] = S[(size_t)c * ld + (size_t)Tr * NB];      // (Tr: tile row of the right-hand side, T + border rows)
     if (prev) prev[c] = dp[c];                        // (bounded back-substitution: the last solve's solution, see bwd_chain_body<.., true>)
     dp[c] = __longlong_as_double((long long)BWD_SENT);
   }
+}
+__global__ void k_chol_extract_y(const double* __restrict__ S, int ld, int T, int Tr, double* __restrict__ yv, double* __restrict__ dp, int* status,
+                                 double* __restrict__ prev) {
+  extract_y_elem(S, ld, T, Tr, yv, dp, status, prev, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // the same for up to 8 systems in one launch (blockIdx.y = system): eight 5 us launches in a row at the end of the bands' steps otherwise
@@ -2740,7 +2744,8 @@ struct SyrkArgs {
   const double* bsrc[CHOL_BATCH_MAX];  // or null: where the tiles' values before the product are read (CholSystem::bord_src); null: bord itself
   int ks; double* scratch;
   size_t scratch_stride;     // split K with two systems in one launch: system r's partial tiles start at scratch + r * scratch_stride
-  int ks_sys[2];             // ... and each may have its own number of chunks (0: ks) — a leaf's product is cut the way a rank owning that leaf cuts it
+  int ks_sys[4];             // ... and each may have its own number of chunks (0: ks) — a leaf's product is cut the way a rank owning that leaf cuts it
+  double* scratch2; size_t scratch_stride2;      // a second pair of systems (2, 3) in the same launch, with a scratch buffer of their own (launch_border_syrk_pairs)
   const int* jobs;       // or null: (system << 20 | ib << 10 | jb) per workgroup, longest sums first (launch_border_syrk_jobs)
   const int* segtab[CHOL_BATCH_MAX];      // or null: CholSystem::segtab — the sum runs over the segments in which both tile rows are non-zero
 };
@@ -2762,7 +2767,7 @@ __device__ __forceinline__ void border_syrk_body(const SyrkArgs& A) {
   if (!st && A.bfirst[r]) c0 = max(A.bfirst[r][ib], A.bfirst[r][jb]);
   int ksr = A.ks;                                 // chunks of this system's column blocks
   if (A.ks > 1) {
-    if (A.scratch_stride && r < 2 && A.ks_sys[r] > 0) ksr = A.ks_sys[r];
+    if (A.scratch_stride && r < 4 && A.ks_sys[r] > 0) ksr = A.ks_sys[r];
     if (q >= ksr) return;
     const int len = (T - c0 + ksr - 1) / ksr;
     c0 += q * len;
@@ -2786,7 +2791,8 @@ __device__ __forceinline__ void border_syrk_body(const SyrkArgs& A) {
   const int ldin = ldb;
   if (q > 0) {       // partial of a later chunk: a 64 x 64 scratch tile (leading dimension NB)
     ldb = NB;
-    cbh = A.scratch + (size_t)r * A.scratch_stride + ((size_t)(jb * (nbr + 1) + ib) * (ksr - 1) + (q - 1)) * (NB * NB) + (size_t)(32 * ch + 2 * lk) * NB + 32 * rh + 2 * lr;
+    double* sc = r < 2 ? A.scratch + (size_t)r * A.scratch_stride : A.scratch2 + (size_t)(r - 2) * A.scratch_stride2;
+    cbh = sc + ((size_t)(jb * (nbr + 1) + ib) * (ksr - 1) + (q - 1)) * (NB * NB) + (size_t)(32 * ch + 2 * lk) * NB + 32 * rh + 2 * lr;
   }
   // The k-steps of ALL segments as ONE sequence (round 4): the operand loads run RD - 1 steps ahead of the matrix pipe ACROSS segment
   // boundaries — a cut band's job has three short sums (one to three block columns each), and a prefetch pipeline that drains and
@@ -2875,32 +2881,58 @@ static void launch_syrk_kernel(dim3 grid, size_t lds, hipStream_t s, const SyrkA
   else if (rd == 8) hipLaunchKernelGGL(k_border_syrk_rd8, grid, dim3(256), lds, s, A);
   else hipLaunchKernelGGL(k_border_syrk, grid, dim3(256), lds, s, A);
 }
-__global__ __launch_bounds__(256) void k_border_syrk_reduce(double* __restrict__ bord, int ldb, int nbr, int ks, const double* __restrict__ scratch,
-                                                            const int* __restrict__ bfirst, int T) {
-  // one element per thread: blockIdx.x = 16 ib + the tile's sixteenth (a workgroup per tile looping over its 4096 elements took 54 us
-  // for ~180 tiles, all of it load latency); gridDim.y may stop short of nbr: only the tile columns the product was run for
-  const int ib = blockIdx.x >> 4, jb = blockIdx.y;
+// elements e0 + u * stride, u < N, of tile (ib, jb): the tile's own value, then the chunks' partials in chunk order — every element's
+// sum on its own, the N loads of a chunk issued together (k_border_syrk_reduce: N = 1; k_lam_solve1)
+template <int N>
+__device__ __forceinline__ void border_reduce_elems(double* __restrict__ bord, int ldb, int nbr, int ks, const double* __restrict__ scratch,
+                                                    const int* __restrict__ bfirst, int T, int ib, int jb, int e0, int stride) {
   if (ib > nbr || jb >= nbr || ib < jb) return;
   int c0 = 0;
   if (bfirst) c0 = max(bfirst[ib], bfirst[jb]);
   const int len = (T - c0 + ks - 1) / ks;
-  const int e = (blockIdx.x & 15) * 256 + threadIdx.x;
-  const int col = e / NB, row = e - col * NB;
-  double* dst = bord + (size_t)(jb * NB + col) * ldb + (size_t)ib * NB + row;
-  double v = *dst;
-  for (int q = 1; q < ks; ++q)
-    if (c0 + q * len < T) v += scratch[((size_t)(jb * (nbr + 1) + ib) * (ks - 1) + (q - 1)) * (NB * NB) + (size_t)col * NB + row];
-  *dst = v;
+  double* dst[N];
+  double v[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const int e = e0 + u * stride;
+    const int col = e / NB, row = e - col * NB;
+    dst[u] = bord + (size_t)(jb * NB + col) * ldb + (size_t)ib * NB + row;
+    v[u] = *dst[u];
+  }
+  int nq = ks;                                    // chunks that hold column blocks: q with c0 + q len < T (the first ones)
+  while (nq > 1 && c0 + (nq - 1) * len >= T) --nq;
+  const double* sq = scratch + (size_t)(jb * (nbr + 1) + ib) * (ks - 1) * (NB * NB) + e0;      // (element (row, col) of a partial tile at col * NB + row = e)
+  int q = 1;
+  for (; q + 1 < nq; q += 2) {                    // two chunks' loads in flight together, added in chunk order
+    double p[N], p2[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) { p[u] = sq[(size_t)(q - 1) * (NB * NB) + u * stride]; p2[u] = sq[(size_t)q * (NB * NB) + u * stride]; }
+#pragma unroll
+    for (int u = 0; u < N; ++u) { v[u] += p[u]; v[u] += p2[u]; }
+  }
+  if (q < nq) {
+    double p[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) p[u] = sq[(size_t)(q - 1) * (NB * NB) + u * stride];
+#pragma unroll
+    for (int u = 0; u < N; ++u) v[u] += p[u];
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) *dst[u] = v[u];
+}
+__global__ __launch_bounds__(256) void k_border_syrk_reduce(double* __restrict__ bord, int ldb, int nbr, int ks, const double* __restrict__ scratch,
+                                                            const int* __restrict__ bfirst, int T) {
+  // one element per thread: blockIdx.x = 16 ib + the tile's sixteenth (a workgroup per tile looping over its 4096 elements took 54 us
+  // for ~180 tiles, all of it load latency); gridDim.y may stop short of nbr: only the tile columns the product was run for
+  border_reduce_elems<1>(bord, ldb, nbr, ks, scratch, bfirst, T, blockIdx.x >> 4, blockIdx.y, (blockIdx.x & 15) * 256 + threadIdx.x, 0);
 }
 // Two systems with the same border whose results are ADDED (a canonical whole pass: each half's partial top block minus its leaf's Schur
 // complement): A <- (A + its partials, in chunk order) + (B + its partials, in chunk order) — what two ranks owning a leaf each compute
 // and then exchange, bit for bit, in one launch instead of two reductions and a sum
-__global__ __launch_bounds__(256) void k_border_syrk_reduce2(double* __restrict__ bordA, int ldbA, const double* __restrict__ bordB, int ldbB, int nbr,
-                                                             int ksA, int ksB, const double* __restrict__ scratchA, const double* __restrict__ scratchB,
-                                                             int TA, int TB) {
-  const int ib = blockIdx.x >> 4, jb = blockIdx.y;
+__device__ __forceinline__ void border_reduce2_elem(double* __restrict__ bordA, int ldbA, const double* __restrict__ bordB, int ldbB, int nbr,
+                                                    int ksA, int ksB, const double* __restrict__ scratchA, const double* __restrict__ scratchB,
+                                                    int TA, int TB, int ib, int jb, int e) {
   if (ib > nbr || jb >= nbr || ib < jb) return;
-  const int e = (blockIdx.x & 15) * 256 + threadIdx.x;
   const int col = e / NB, row = e - col * NB;
   double* dst = bordA + (size_t)(jb * NB + col) * ldbA + (size_t)ib * NB + row;
   double va = *dst, vb = bordB[(size_t)(jb * NB + col) * ldbB + (size_t)ib * NB + row];
@@ -2911,9 +2943,62 @@ __global__ __launch_bounds__(256) void k_border_syrk_reduce2(double* __restrict_
     if (q * lenB < TB) vb += scratchB[((size_t)(jb * (nbr + 1) + ib) * (ksB - 1) + (q - 1)) * (NB * NB) + (size_t)col * NB + row];
   *dst = va + vb;
 }
+__global__ __launch_bounds__(256) void k_border_syrk_reduce2(double* __restrict__ bordA, int ldbA, const double* __restrict__ bordB, int ldbB, int nbr,
+                                                             int ksA, int ksB, const double* __restrict__ scratchA, const double* __restrict__ scratchB,
+                                                             int TA, int TB) {
+  border_reduce2_elem(bordA, ldbA, bordB, ldbB, nbr, ksA, ksB, scratchA, scratchB, TA, TB, blockIdx.x >> 4, blockIdx.y,
+                      (blockIdx.x & 15) * 256 + threadIdx.x);
+}
+// two such pairs in one launch (blockIdx.z = pair): the top block's tile columns jb < jb_end and the lambda block, behind the one
+// product launch that formed both (launch_border_syrk_pairs); the grid covers the larger pair, the other one's workgroups beyond its
+// tiles leave at once
+struct Reduce2Pair { double* bordA; const double* bordB; const double* scratchA; const double* scratchB; int ldbA, ldbB, nbr, jb_end, ksA, ksB, TA, TB; };
+struct Reduce2Args { Reduce2Pair p[2]; };
+__global__ __launch_bounds__(256) void k_border_syrk_reduce2p(Reduce2Args A) {
+  const Reduce2Pair& P = A.p[blockIdx.z];
+  if ((int)blockIdx.y >= P.jb_end) return;
+  border_reduce2_elem(P.bordA, P.ldbA, P.bordB, P.ldbB, P.nbr, P.ksA, P.ksB, P.scratchA, P.scratchB, P.TA, P.TB, blockIdx.x >> 4, blockIdx.y,
+                      (blockIdx.x & 15) * 256 + threadIdx.x);
+}
+// A lambda block of ONE tile (at most ten relative-pose factors), behind the product over the last column blocks: what
+// k_border_syrk_reduce, k_lam_prepare, the one k_chol_step of T = 1 (a single type-A workgroup: the right-hand-side tile, nothing
+// queued), k_chol_extract_y and k_chol_bwd_chain (T = 1: nothing to poll) do in five launches, by the same device code in the same
+// order in ONE workgroup of the step kernel's shape.  Each part reads what other threads of the part before it wrote to global memory:
+// __syncthreads() between them (a workgroup-scope release / acquire around the barrier: the stores are drained before it).
+// Leaves bord, S (factor tiles in place), Ld, Winv, yv, dp, ctr[1] = 0 and status — the not-SPD flag of the chain wave, and the ticket
+// word at 1: the one ticket k_chol_bwd_chain's workgroup draws — as the separate launches leave them.  ks <= 1: no partials to add.
+union LamSolveLds { ALds a; ChainLds c; };      // the factorisation's image, then the substitution's
+__global__ __launch_bounds__(512) void k_lam_solve1(double* bord, int ks, const double* __restrict__ scratch, int Tsum, int lam, double* S,
+                                                    double* Ld, double* Winv, double* yv, double* dp, int* status, int* ctr) {
+  __shared__ LamSolveLds U;
+  constexpr int ld = 2 * NB;                      // of bord and of S: the tile column and its right-hand-side row tile
+  const int tid = threadIdx.x;
+  // waves 0 .. 3: tile (0, 0), waves 4 .. 7: the right-hand-side tile (1, 0); sixteen elements per thread
+  if (ks > 1) border_reduce_elems<16>(bord, ld, 1, ks, scratch, nullptr, Tsum, tid >> 8, 0, tid & 255, 256);
+  __syncthreads();
+  // seven groups of 65 threads (rows 0 .. 63 and the right-hand-side row), every seventh column each
+  if (tid < 7 * (NB + 1)) lam_prepare_elems<10>(bord, 1, lam, S, tid % (NB + 1), tid / (NB + 1), 7);
+  if (tid == 0) ctr[1] = 0;                       // (k_chol_step clears the next step's work counter)
+  __syncthreads();
+  step_type_a(S, ld, 0, 1, 1, 0, -1, Ld, Winv, status, U.a, nullptr, 0, 0);
+  __syncthreads();
+  extract_y_elem(S, ld, 1, 1, yv, dp, status, nullptr, tid);
+  __syncthreads();
+  if (tid == 0) status[4] = 1;
+  bwd_chain_body<false>(U.c, S, ld, 1, Ld, Winv, yv, dp, status, 0, nullptr, nullptr);
+}
+void launch_lam_solve1(double* bord, int ks, const double* scratch, int Tsum, int lam, double* S, double* Ld, double* Winv, double* yv, double* dp,
+                       int* status, int* ctr, hipStream_t s) {
+  hipLaunchKernelGGL(k_lam_solve1, dim3(1), dim3(512), 0, s, bord, scratch ? ks : 1, scratch, Tsum, lam, S, Ld, Winv, yv, dp, status, ctr);
+}
 // scratch (or null): (nbr + 1) * nbr * (ks - 1) tiles of NB * NB doubles — with it, ONE system's product is split over ks chunks of its
 // column blocks (a system with a handful of border tiles would otherwise occupy a handful of CUs for the whole K)
-void launch_border_syrk(const CholSystem* d, int n, hipStream_t s, double* scratch, int ks) {
+LamFuse lam_fuse_env() {
+  LamFuse F{3};
+  if (const char* e = getenv("SLIDE_LAM_FUSE")) F.mask = atoi(e);
+  return F;
+}
+void launch_border_syrk(const CholSystem* d, int n, hipStream_t s, double* scratch, int ks, bool reduce) {
   SyrkArgs A{};
   A.n = n;
   int nb = 0;
@@ -2926,7 +3011,7 @@ void launch_border_syrk(const CholSystem* d, int n, hipStream_t s, double* scrat
   if (scratch && n == 1 && ks > 1) {
     A.ks = ks; A.scratch = scratch;
     launch_syrk_kernel(dim3(nb + 1, nb, ks), 0, s, A);
-    hipLaunchKernelGGL(k_border_syrk_reduce, dim3(16 * (nb + 1), nb), dim3(256), 0, s, d[0].bord, d[0].ldb, d[0].nbr, ks, scratch, d[0].bfirst, d[0].T);
+    if (reduce) hipLaunchKernelGGL(k_border_syrk_reduce, dim3(16 * (nb + 1), nb), dim3(256), 0, s, d[0].bord, d[0].ldb, d[0].nbr, ks, scratch, d[0].bfirst, d[0].T);
     return;
   }
   A.ks = 1; A.scratch = nullptr;
@@ -2970,6 +3055,33 @@ void launch_border_syrk_jobs(const CholSystem* d, int n, const int* jobs, int nj
     return;
   }
   launch_syrk_kernel(dim3(njobs), lds_pad, s, A);
+}
+// TWO fuse_add pairs of launch_border_syrk_jobs in one product launch and one reduction: top[0..1] (systems 0, 1 of the table: the top
+// block's tile columns jb < jb_end, ks_top chunks each, partial tiles in scratch_top) and lam[0..1] (systems 2, 3: the lambda block,
+// ks_lam[r] chunks, partial tiles in scratch_lam).  Every tile is formed by the workgroups, chunk boundaries and scratch offsets of the two
+// separate launches, and reduced in their order: the same bits.  Both scratch buffers non-null, each pair with one border size.
+void launch_border_syrk_pairs(const CholSystem* top, const CholSystem* lam, const int* jobs, int njobs, hipStream_t s, double* scratch_top,
+                              int ks_top, int jb_end, double* scratch_lam, const int* ks_lam) {
+  if (njobs <= 0) return;
+  SyrkArgs A{};
+  A.n = 4;
+  for (int i = 0; i < 4; ++i) {
+    const CholSystem& d = i < 2 ? top[i] : lam[i - 2];
+    A.S[i] = d.S; A.ld[i] = d.ld; A.T[i] = d.T; A.nbr[i] = d.nbr; A.bord[i] = d.bord; A.ldb[i] = d.ldb; A.bfirst[i] = d.bfirst; A.bsrc[i] = d.bord_src;
+    A.segtab[i] = d.segtab; A.b0[i] = d.b0 > 0 ? d.b0 : d.T;
+  }
+  A.jobs = jobs;
+  const int nbt = top[0].nbr, nbl = lam[0].nbr;
+  const int kt = std::max(1, ks_top), ka = std::max(1, ks_lam[0]), kb = std::max(1, ks_lam[1]), kl = std::max(ka, kb), km = std::max(kt, kl);
+  A.ks = km;
+  A.scratch = scratch_top; A.scratch_stride = std::max<size_t>(1, (size_t)(nbt + 1) * nbt * (kt - 1) * NB * NB);
+  A.scratch2 = scratch_lam; A.scratch_stride2 = std::max<size_t>(1, (size_t)(nbl + 1) * nbl * (kl - 1) * NB * NB);
+  A.ks_sys[0] = A.ks_sys[1] = kt; A.ks_sys[2] = ka; A.ks_sys[3] = kb;
+  launch_syrk_kernel(dim3(njobs, 1, km), 0, s, A);
+  Reduce2Args R{};
+  R.p[0] = {top[0].bord, top[1].bord, scratch_top, scratch_top + A.scratch_stride, top[0].ldb, top[1].ldb, nbt, jb_end, kt, kt, top[0].T, top[1].T};
+  R.p[1] = {lam[0].bord, lam[1].bord, scratch_lam, scratch_lam + A.scratch_stride2, lam[0].ldb, lam[1].ldb, nbl, nbl, ka, kb, lam[0].T, lam[1].T};
+  hipLaunchKernelGGL(k_border_syrk_reduce2p, dim3(16 * (std::max(nbt, nbl) + 1), std::max(jb_end, nbl), 2), dim3(256), 0, s, R);
 }
 // y -= W x_loc before the backward substitution of the band (x_loc: the separator's solution in the system's own border order, zeros
 // in the padding): one wave per column of the band, lanes over the border rows (contiguous down a column of S)

@@ -876,6 +876,7 @@ void CholBatch::free_separator() {
   for (double** p : {&sep_top2, &sep_bord2}) if (*p) { (void)hipFree(*p); *p = nullptr; }
   if (d_sep_jobs2) { (void)hipFree(d_sep_jobs2); d_sep_jobs2 = nullptr; }
   if (d_lam_jobs2) { (void)hipFree(d_lam_jobs2); d_lam_jobs2 = nullptr; }
+  if (d_sep_jobs4) { (void)hipFree(d_sep_jobs4); d_sep_jobs4 = nullptr; }
   sep_cap = 0; lam_cap = -1;
 }
 void CholBatch::set_segments(int n) {
@@ -1067,6 +1068,17 @@ int CholBatch::prepare_separator() {
       n_sep_jobs2 = (int)codes2.size();
       SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_sep_jobs2), codes2.size() * sizeof(int)));
       SL_HIP(hipMemcpyAsync(d_sep_jobs2, codes2.data(), codes2.size() * sizeof(int), hipMemcpyHostToDevice, master)); SL_HIP(hipStreamSynchronize(master));
+      // ... and with the lambda block's tiles of both leaves behind them as systems 2 and 3 (d_lam_jobs2's order): ONE launch for both products
+      if (d_sep_jobs4) { SL_HIP(hipFree(d_sep_jobs4)); d_sep_jobs4 = nullptr; }
+      n_sep_jobs4 = 0;
+      if (sep_nl > 0) {
+        for (int sy = 2; sy < 4; ++sy)
+          for (int jb = 0; jb < sep_nl; ++jb)
+            for (int ib = jb; ib <= sep_nl; ++ib) codes2.push_back(sy << 20 | ib << 10 | jb);
+        n_sep_jobs4 = (int)codes2.size();
+        SL_HIP(hipMalloc(reinterpret_cast<void**>(&d_sep_jobs4), codes2.size() * sizeof(int)));
+        SL_HIP(hipMemcpyAsync(d_sep_jobs4, codes2.data(), codes2.size() * sizeof(int), hipMemcpyHostToDevice, master)); SL_HIP(hipStreamSynchronize(master));
+      }
     }
     if (sep_ks > 1) {
       const size_t len = 2 * (size_t)(nb + 1) * nb * (sep_ks - 1) * NB * NB * sizeof(double);      // (two systems' partial tiles: launch_border_syrk_jobs with n = 2)
@@ -1262,8 +1274,13 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
           if (sep_scratch && (sep_nl == 0 || (lam_scratch && d_lam_jobs2))) {
             // both leaves in ONE launch each for the top block's columns and for the lambda block, every leaf's column blocks cut the way a
             // rank owning that leaf cuts them, and one reduction each that also adds the second half's result onto the first
-            launch_border_syrk_jobs(tp2, 2, d_sep_jobs2, n_sep_jobs2, 0, master, sep_scratch, sep_ks, Tt, nullptr, true);
-            if (sep_nl > 0) launch_border_syrk_jobs(sl2, 2, d_lam_jobs2, n_lam_jobs2, 0, master, lam_scratch, 1, -1, ks_lam, true);
+            if (sep_nl > 0 && d_sep_jobs4 && (lam_fuse_env().mask & 1)) {
+              // ... and the lambda block's tiles in the top block's launch: one product launch, one reduction for both
+              launch_border_syrk_pairs(tp2, sl2, d_sep_jobs4, n_sep_jobs4, master, sep_scratch, sep_ks, Tt, lam_scratch, ks_lam);
+            } else {
+              launch_border_syrk_jobs(tp2, 2, d_sep_jobs2, n_sep_jobs2, 0, master, sep_scratch, sep_ks, Tt, nullptr, true);
+              if (sep_nl > 0) launch_border_syrk_jobs(sl2, 2, d_lam_jobs2, n_lam_jobs2, 0, master, lam_scratch, 1, -1, ks_lam, true);
+            }
           } else {
             for (int hh = 0; hh < 2; ++hh) {
               launch_border_syrk_jobs(&tp2[hh], 1, d_sep_jobs, n_sep_jobs, 0, master, sep_scratch, sep_ks, Tt);
@@ -1308,13 +1325,19 @@ int CholBatch::enqueue_arrow(double* const* d_bufs, int part, hipEvent_t e0, hip
       static const bool env_canon3 = !(getenv("SLIDE_SEP_CANONICAL") && getenv("SLIDE_SEP_CANONICAL")[0] == '0');
       if (owned || (whole && sep_dissected() && env_canon3 && n <= 8)) { sr.S = sepS + (size_t)sTL * NB * ld_s; sr.T = sTt; sr.b0 = sep_Ts; }
       const int ks = std::max(1, std::min(lam_ks_cap(sep_nl), sr.T / 2));      // few border tiles: split the column blocks
-      launch_border_syrk(&sr, 1, master, lam_scratch, ks);
-      launch_lam_prepare(sep_bord, sep_nl, sep_lam, lamS, master);
-      const int ld_l = (sep_nl + 1) * NB;
-      for (int k = 0; k < sep_nl; ++k)
-        launch_chol_step(lamS, ld_l, k, sep_nl, lam_Ld + (size_t)k * NB * NB, lam_Winv + (size_t)k * 1024, lam_status, lam_ctr, nullptr, nullptr, master);
-      launch_chol_extract_y(lamS, ld_l, sep_nl, lam_yv, lam_dp, lam_status, master);
-      launch_chol_bwd_all(lamS, ld_l, sep_nl, lam_Ld, lam_Winv, lam_yv, lam_dp, lam_status, nullptr, master);
+      if (sep_nl == 1 && (lam_fuse_env().mask & 2)) {
+        // one tile of lambdas: the product's partial tiles are added, the block negated, factored and solved by one workgroup
+        launch_border_syrk(&sr, 1, master, lam_scratch, ks, false);
+        launch_lam_solve1(sep_bord, ks, lam_scratch, sr.T, sep_lam, lamS, lam_Ld, lam_Winv, lam_yv, lam_dp, lam_status, lam_ctr, master);
+      } else {
+        launch_border_syrk(&sr, 1, master, lam_scratch, ks);
+        launch_lam_prepare(sep_bord, sep_nl, sep_lam, lamS, master);
+        const int ld_l = (sep_nl + 1) * NB;
+        for (int k = 0; k < sep_nl; ++k)
+          launch_chol_step(lamS, ld_l, k, sep_nl, lam_Ld + (size_t)k * NB * NB, lam_Winv + (size_t)k * 1024, lam_status, lam_ctr, nullptr, nullptr, master);
+        launch_chol_extract_y(lamS, ld_l, sep_nl, lam_yv, lam_dp, lam_status, master);
+        launch_chol_bwd_all(lamS, ld_l, sep_nl, lam_Ld, lam_Winv, lam_yv, lam_dp, lam_status, nullptr, master);
+      }
       const double* xl = lam_dp;
       if (!owned) launch_border_apply(&ss, 1, &xl, master);
       else {      // the own leaf's and the top block's columns only (the other leaf's hold nothing of this pass)

@@ -347,6 +347,7 @@ class CholBatch {
   double *sep_top2 = nullptr, *sep_bord2 = nullptr; int sep_ld2 = 0; unsigned sep_mask_b = 0;
   int* d_lam_jobs2 = nullptr; int n_lam_jobs2 = 0;      // the same for the lambda block
   int* d_sep_jobs2 = nullptr; int n_sep_jobs2 = 0;      // the top block's product over BOTH leaves as two systems of one launch (system << 20 | ib << 10 | jb)
+  int* d_sep_jobs4 = nullptr; int n_sep_jobs4 = 0;      // that table and, behind it, the lambda block's as systems 2, 3: both products in one launch (launch_border_syrk_pairs)
   bool sep_dissected() const { return sep_leafT[0] > 0 && sep_leafT[1] > 0; }
   // lambda coordinates of the inter-robot relative-pose factors: border rows of the separator system, their own small system
   int sep_lam = 0, sep_nl = 0, lam_cap = -1;

@@ -66,6 +66,28 @@ void launch_sep_gather(const GraphDev* h, int n, const int* const* maps, const S
 void launch_sep_top_add(const SepLayout& Y, int c0, const double* sys2, int ld2, const double* bord2, hipStream_t s);      // tile columns >= c0 of the system (and the lambda block) += the other half's partial
 void launch_sep_unpack(const SepLayout& Y, hipStream_t s, int c0 = 0, int c1 = -1, bool to_packed = false);      // tile columns [c0, c1) (virtual: lambda tiles behind the landmarks'); to_packed: the reverse copy
 void launch_lam_prepare(const double* bord, int nl, int lam, double* out, hipStream_t s);      // M = -(K22 - L21 L21^T), rhs = -(r2 - L21 z1)
+// elements (r, c0 + u * cstride), u < N, of that (k_lam_prepare in solver_kernels.hip: N = 1; k_lam_solve1 in chol_kernels.hip): row r
+// of the nl tile columns, r = nl * NB the right-hand-side row; the negated entry, unit diagonal on the padding.  The N loads are issued
+// together, then the stores.
+template <int N>
+__device__ __forceinline__ void lam_prepare_elems(const double* __restrict__ bord, int nl, int lam, double* __restrict__ out, int r, int c0, int cstride) {
+  const int NT = nl * NB, ld = (nl + 1) * NB;
+  if (r > NT) return;
+  const bool rhs = r == NT;
+  double v[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const int c = c0 + u * cstride;
+    const bool live = c < NT && (rhs || r >= c);
+    v[u] = (r == c) ? 1.0 : 0.0;
+    if (live && c < lam && (rhs || r < lam)) v[u] = -bord[(size_t)c * ld + r];
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const int c = c0 + u * cstride;
+    if (c < NT && (rhs || r >= c)) out[(size_t)c * ld + r] = v[u];
+  }
+}
 void launch_sep_xloc(int n, const int* const* maps, int ms, int lam, const double* xs, const double* xl, double* const* xloc, hipStream_t s);
 void launch_arrow_finish_batched(const GraphDev* d, const GraphDev* h, int n, const double* xs, const int* sep_off, hipStream_t s, bool slots_onto);      // slots_onto: lm_slot reaches every slot of every graph (HostGraph::lm_slot_onto)
 struct AsmMerge { int mask; };                   // SLIDE_ASM_MERGE (default 6) — solver_kernels.hip, launch_phase3_arrow_batched
@@ -126,9 +148,23 @@ int chol_ll_plan_tasks(const CholLLPlan* p);
 int chol_ll_plan_columns(const CholLLPlan* p);
 void launch_chol_ll(const CholLLPlan* p, const CholSystem* d, int n, hipStream_t s, int* trace = nullptr);      // trace: diagnostic, 16 host-pinned ints per task (ll_mark / ll_time) or null
 // Exact joint step (the border of the systems = the separator's coupling rows, W^T after the steps):
-void launch_border_syrk(const CholSystem* d, int n, hipStream_t s, double* scratch = nullptr, int ks = 1);          // bord(i, j) -= sum_c W^T(i, c) W^T(j, c)^T, i >= j, right-hand-side row included; scratch + ks: split K (one system)
+void launch_border_syrk(const CholSystem* d, int n, hipStream_t s, double* scratch = nullptr, int ks = 1, bool reduce = true);          // bord(i, j) -= sum_c W^T(i, c) W^T(j, c)^T, i >= j, right-hand-side row included; scratch + ks: split K (one system); reduce = false: the chunks' partials stay in scratch for the caller's own reduction (launch_lam_solve1)
+// SLIDE_LAM_FUSE, a bit mask read whenever a pass's launch sequence is built (one process can take both sides): 1 = the lambda block's
+// products over the two leaves ride in the launch of the top block's (a canonical whole pass), 2 = a lambda block of one tile is reduced,
+// factored and solved by ONE workgroup (k_lam_solve1).  Default 3; 0 = the separate launches.
+struct LamFuse { int mask; };
+LamFuse lam_fuse_env();
+// sep_nl == 1, behind launch_border_syrk(.., scratch, ks, false) over Tsum column blocks: bord += the partials (k_border_syrk_reduce's
+// order), S = -bord padded (k_lam_prepare), its factorisation (the k_chol_step of T = 1), yv / dp (k_chol_extract_y), dp = the solution
+// (k_chol_bwd_chain) — one launch of one workgroup; scratch null or ks <= 1: the product was not split
+void launch_lam_solve1(double* bord, int ks, const double* scratch, int Tsum, int lam, double* S, double* Ld, double* Winv, double* yv, double* dp,
+                       int* status, int* ctr, hipStream_t s);
 void launch_border_syrk_jobs(const CholSystem* d, int n, const int* jobs, int njobs, int lds_pad, hipStream_t s, double* scratch = nullptr, int ks = 1, int jb_end = -1,
                              const int* ks_sys = nullptr, bool fuse_add = false);      // fuse_add (n = 2, same border): system 0's block += system 1's, each split its own way (ks_sys)      // the same, workgroups in the order of a job table (system << 20 | ib << 10 | jb), lds_pad bytes of idle LDS per workgroup (bounds the residency)
+// two fuse_add pairs in ONE product launch and ONE reduction (a canonical whole pass with lambdas): top[0..1] = systems 0, 1 of the job
+// table (tile columns jb < jb_end, ks_top chunks each), lam[0..1] = systems 2, 3 (ks_lam[r] chunks), each pair with its own scratch
+void launch_border_syrk_pairs(const CholSystem* top, const CholSystem* lam, const int* jobs, int njobs, hipStream_t s, double* scratch_top,
+                              int ks_top, int jb_end, double* scratch_lam, const int* ks_lam);
 void launch_border_apply(const CholSystem* d, int n, const double* const* xloc, hipStream_t s);   // yv -= W x_loc (x_loc: nbr * NB doubles per system)
 // one of the two triangular solves with the finished factors of up to 8 systems on arbitrary vectors (T * NB doubles each): out = L^-1 in
 // (fwd) or L^-T in (bwd); the preconditioner of the joint solve (pcg_kernels.hip)

@@ -1843,15 +1843,7 @@ __global__ __launch_bounds__(256) void k_sep_unpack(SepLayout Y, int c0, int c1,
 // r2 - L21 z1; M = -(that) is positive definite and M lambda = -(r2 - L21 z1).  out: Tl = nl tile columns, ld = (nl + 1) * NB, unit
 // diagonal on the padding.
 __global__ __launch_bounds__(256) void k_lam_prepare(const double* __restrict__ bord, int nl, int lam, double* __restrict__ out) {
-  const int r = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-  const int NT = nl * NB, ld = (nl + 1) * NB;
-  if (r > NT || c >= NT) return;
-  const bool rhs = r == NT;
-  if (!rhs && r < c) return;
-  double v;
-  if (c < lam && (rhs || r < lam)) v = -bord[(size_t)c * ld + r];
-  else v = (r == c) ? 1.0 : 0.0;
-  out[(size_t)c * ld + r] = v;
+  lam_prepare_elems<1>(bord, nl, lam, out, blockIdx.x * 256 + threadIdx.x, blockIdx.y, 0);      // (kernels.hpp)
 }
 // the separator's solution back to the robots: x_loc (border order, for k_border_apply) and, after the landmark back-substitution,
 // the shared landmarks' own deltas
